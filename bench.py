@@ -2,6 +2,8 @@
 """Headline benchmark: synthesised 256x256 vehicle crops / second on N MI355X (BASELINE.json).
 
     python bench.py --gpus N --steps K --warmup W          (starts its own N ranks when N > 1)
+    python bench.py ... --full                             (+ every secondary measurement, see below)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One *step* = one pass of the hot path over one batch of synthetic crops per rank:
@@ -10,7 +12,12 @@ quantisation [+ EdgeGenerator + InpaintGenerator with --inpaint], then (N > 1) t
 rendered uint8 crops to rank 0 over RCCL.  The default workload is BASELINE.json configs[1]:
 batch 32 of 256x256 crops per GPU.  Tensors are fp32 (the reference's dtype) everywhere.
 
-Precision legs.  The conv contraction exists in two arithmetics and ONE run times both, each with the full
+A plain run does only what the headline needs: set-up, the DVFS settle and W warm-up steps, K timed steps of the
+f16x3 leg, the outputs of the last timed step written with --dump-outputs DIR, and the result line.  Everything else
+below (the f32 and bf16 legs, the roofline pass, power sampling, the CPU baseline and the secondary figures) runs only
+with --full; the --no-* options switch parts of --full off.
+
+Precision legs.  The conv contraction exists in two arithmetics and a --full run times both, each with the full
 protocol (W warm-up steps, K timed steps between barrier + synchronize, max over ranks, roofline pass):
   f32   : exact fp32 MFMA (v_mfma_f32_32x32x2_f32: bit-for-bit an fmaf chain) - the reference's arithmetic.
   f16x3 : fp32 operands split into scaled fp16 pairs, three fp16 MFMA products, fp32 accumulation
@@ -20,14 +27,14 @@ protocol (W warm-up steps, K timed steps between barrier + synchronize, max over
           range raise a device-side status word and the pass is redone in f32 (never a silent clamp) - the
           benchmark checks that word once after the timed steps and refuses the leg if it was raised.
 The headline `value` is the f16x3 leg (fp32-class accuracy, defended by the tests above); "precision_legs" carries
-both legs in the same line.  --precision limits the run to one leg.
+every leg that ran in the same line.  --precision chooses the legs (default: f16x3, or all three with --full).
 
 Inputs and weights are synthetic (no datasets / checkpoints in this environment) and resident in HBM before
 the timed region; VUnet's sampler noise is drawn on the CPU generator inside the step, as the reference does.
 Weak scaling: each rank processes its own batch (vehicles are independent); --vehicles V is the strong-scaling
 mode of BASELINE configs[3] (one frame's V vehicles sharded over the ranks, e.g. --gpus 8 --vehicles 64).
 
-Extra fields: "roofline" (conv kernels: algorithmic FLOPs of SURVEY.md §8d - and the FLOPs as launched - divided
+Extra fields of a --full run: "roofline" (conv kernels: algorithmic FLOPs of SURVEY.md §8d - and the FLOPs as launched - divided
 by the kernels' HIP-event time on the launch stream, measured live in a second pass of the same K steps),
 "cpu_baseline" (the CPU oracle = a port of the reference's torch graph, timed on this host's cores on a bounded
 sample of the same workload, the whole leg capped at 60 s; N=1, rank 0 only), "ssim_vs_cpu_ref" / "kp_idx_exact" (quality of the GPU path on
@@ -69,10 +76,10 @@ def parse_args():
     ap.add_argument("--batch", type=int, default=32, help="crops per GPU per step")
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--inpaint", action="store_true", help="BASELINE configs[2]: add EdgeConnect")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=8, help="crops in the CPU baseline sample")
-    ap.add_argument("--no-clip", action="store_true", help="skip the secondary clip-mode figure")
-    ap.add_argument("--no-prof", action="store_true", help="skip the roofline leg (second pass with per-launch HIP events)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-baseline leg")
+    ap.add_argument("--cpu-sample", type=int, default=8, help="crops in the CPU baseline sample (--full)")
+    ap.add_argument("--no-clip", action="store_true", help="--full without the secondary figures (clip / frame mode, configs[0])")
+    ap.add_argument("--no-prof", action="store_true", help="--full without the roofline leg (second pass with per-launch HIP events)")
     ap.add_argument("--broadcast-weights", dest="broadcast_weights", action="store_true", default=True,
                     help="N > 1 (default): only rank 0 builds the checkpoints, the others receive them through "
                          "pipeline.broadcast_state_dicts (RCCL broadcast of one flat blob per network) - what a real "
@@ -82,10 +89,46 @@ def parse_args():
     ap.add_argument("--replay", action="store_true",
                     help="issue each pass as ONE recorded-plan replay (fusg_plan) instead of ~370 launches from Python: "
                          "matters at small --batch, where the interpreter bounds the pass")
-    ap.add_argument("--precision", choices=["f16x3", "f32", "bf16", "both", "all"], default="all",
-                    help="which precision legs to time (default all three; the headline is f16x3 when it ran, bf16 is the "
-                         "reduced-precision path of BASELINE configs[4] and never the headline of an fp32 configuration)")
-    return ap.parse_args()
+    ap.add_argument("--precision", choices=["f16x3", "f32", "bf16", "both", "all"], default=None,
+                    help="which precision legs to time (default f16x3, all three with --full; the headline is f16x3 when it "
+                         "ran, bf16 is the reduced-precision path of BASELINE configs[4] and never the headline of an fp32 "
+                         "configuration)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement: the f32 and bf16 legs, the roofline pass, power sampling, the "
+                         "CPU baseline, clip / frame mode and configs[0] (a plain run times the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the headline leg's last timed step (rank 0) as "
+                         "DIR/<name>.npy, float32 (int32 indices as float64), at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(outputs, path, budget=DUMP_BUDGET_BYTES):
+    """Write host copies of one step's outputs (name -> CPU tensor, all with the crops as leading dimension) as
+    path/<name>.npy: integer indices as float64 (exact), everything else as float32.  When the arrays together exceed
+    `budget` bytes, every array keeps the same fixed, seeded sample of crops (rows of the leading dimension, in order).
+    Returns {name: shape written}."""
+    import numpy as np
+    arrs = {}
+    for k, v in sorted(outputs.items()):
+        a = v.numpy()
+        arrs[k] = a.astype(np.float64 if a.dtype in (np.int32, np.int64, np.float64) else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    rows = min((a.shape[0] for a in arrs.values()), default=0)
+    if total > budget and rows > 1:
+        keep = max(1, rows * budget // total)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrs.items()}
 
 
 def spawn_ranks(n: int) -> int:
@@ -479,17 +522,19 @@ def main():
         del gather_ms[:]
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            out = step()
         barrier()
         dt = time.perf_counter() - t0
         out_of_range = pipe.finish()                    # one 4-byte read for all K steps
+        if args.dump_outputs and rank == 0:             # host copies now: a replayed plan reuses its output tensors
+            leg_outputs[prec] = {k: v.detach().cpu() for k, v in out.items()}
         # Roofline pass: the SAME K steps again with one HIP-event pair around every conv launch, recorded on
         # the launch stream.  Kept out of the timed region above because ~460 event records per step cost
         # ~10 % of wall time; kernel durations themselves are unaffected (rocprofv3 agrees, profiles/).
         # The branches of the pass are serialised for this leg (FUSG_STREAMS=0): kernels that share the GPU with
         # another stream's kernels would each read longer than they are.
         roofline = None
-        if not args.no_prof:
+        if args.full and not args.no_prof:
             streams_env = os.environ.get("FUSG_STREAMS")
             os.environ["FUSG_STREAMS"] = "0"
             step()
@@ -569,9 +614,11 @@ def main():
             leg["power"] = power
         return leg
 
-    legs_wanted = {"both": ["f16x3", "f32"], "all": ["f16x3", "f32", "bf16"]}.get(args.precision, [args.precision])
+    precision = args.precision or ("all" if args.full else "f16x3")
+    legs_wanted = {"both": ["f16x3", "f32"], "all": ["f16x3", "f32", "bf16"]}.get(precision, [precision])
+    leg_outputs = {}
     sampler = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         pr = torch.cuda.get_device_properties(local_rank)
         bdf = None
         if all(hasattr(pr, a) for a in ("pci_domain_id", "pci_bus_id", "pci_device_id")):
@@ -583,14 +630,21 @@ def main():
     head = legs_wanted[0]
     if legs[head]["range_status_raised"]:
         # cannot happen with the synthetic inputs; if it does, the f16x3 figure is not a valid measurement
+        if head != "f32" and "f32" not in legs and args.precision is None:
+            legs["f32"] = run_leg("f32")            # a plain run: the f32 leg that --full would have timed anyway
         if "f32" in legs and head != "f32":
             head = "f32"
         else:
             raise SystemExit("bench.py: the f16x3 range status was raised during the timed steps - leg invalid")
     ops.set_precision(head)
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(leg_outputs[head], args.dump_outputs)
+        print("bench.py: outputs of the last timed %s step -> %s: %s" % (head, args.dump_outputs, json.dumps(shapes)),
+              file=sys.stderr, flush=True)
+    leg_outputs.clear()
 
     extra = {}
-    if rank == 0 and world == 1 and not args.no_clip and not args.inpaint:
+    if args.full and rank == 0 and world == 1 and not args.no_clip and not args.inpaint:
         # secondary figure: clip mode = 1 HG + 6 ICN + 1 VUnet-full + 5 VUnet-later per vehicle,
         # 8 vehicles x 6 frames per pass (ICN and the VUnet shape half run at batch 48)
         from future_urban_scene_generation_amd.pipeline import synth_clip
@@ -607,7 +661,7 @@ def main():
                               "vehicle_clips_per_s": round(V / cdt, 2), "frames_per_s": round(V * F / cdt, 1),
                               "range_status_raised": bool(bad)}
         del clip
-    if rank == 0 and world == 1 and not args.no_clip and args.res == 256:
+    if args.full and rank == 0 and world == 1 and not args.no_clip and args.res == 256:
         # secondary figure: frame mode = the chained per-frame driver (VehiclePipeline.run_frame: detector boxes -> box
         # crops -> hourglass -> argmax -> pose fit, plane warps -> ICN inputs -> ICN -> Lab image, VUnet inputs -> VUnet,
         # resize-back + ordered paste of every vehicle), 8 vehicles on a 720 x 1280 frame, everything device-resident;
@@ -668,10 +722,10 @@ def main():
                                             "are issued before frame i's range status is read back), 8 vehicles on a 720 x 1280 frame"}
         del scene, scene2
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline, quality = cpu_baseline_leg(args, batch, pipe, torch)
         extra.update(quality)
-    if rank == 0 and world == 1 and not args.no_clip and not args.inpaint and args.res == 256:
+    if args.full and rank == 0 and world == 1 and not args.no_clip and not args.inpaint and args.res == 256:
         extra["configs0_vunet_forward_b1"] = vunet_forward_leg(args, pipe, torch, with_cpu=not args.no_cpu_baseline,
                                                                threads=cpu_baseline["cores"] if cpu_baseline else None)
 

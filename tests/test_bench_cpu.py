@@ -78,3 +78,39 @@ def test_oracle_crop_pass_deadline():
         oracle.crop_pass(sds, b, deadline=time.perf_counter() - 1.0)
     torch.manual_seed(0)
     assert "vunet_u8" in oracle.crop_pass(sds, b, deadline=time.perf_counter() + 600)
+
+
+def test_dump_outputs_float_arrays_and_seeded_sample(tmp_path):
+    """--dump-outputs: every output as <name>.npy in float32 (int32 indices in float64, exact); over the byte budget
+    every array keeps the same fixed, seeded rows, so two runs (or two builds) compare output for output."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    outs = {"kp_idx": torch.randint(0, 1 << 24, (8, 12), dtype=torch.int32, generator=g) + (1 << 24),
+            "icn_u8": torch.randint(0, 256, (8, 16, 16, 3), dtype=torch.uint8, generator=g),
+            "mu_app_0": torch.randn(8, 4, 2, 2, generator=g)}
+    shapes = bench.dump_outputs(outs, str(tmp_path / "all"))
+    assert shapes == {k: list(v.shape) for k, v in outs.items()}
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in outs}
+    assert got["kp_idx"].dtype == np.float64 and got["icn_u8"].dtype == np.float32 and got["mu_app_0"].dtype == np.float32
+    for k, v in outs.items():
+        assert np.array_equal(got[k], v.numpy().astype(got[k].dtype))
+    total = sum(a.nbytes for a in got.values())
+    budget = total // 3
+    for d in ("s1", "s2"):
+        shapes = bench.dump_outputs(outs, str(tmp_path / d), budget=budget)
+        assert len({s[0] for s in shapes.values()}) == 1 and 1 <= shapes["kp_idx"][0] < 8
+    s1 = {k: np.load(str(tmp_path / "s1" / (k + ".npy"))) for k in outs}
+    s2 = {k: np.load(str(tmp_path / "s2" / (k + ".npy"))) for k in outs}
+    assert sum(a.nbytes for a in s1.values()) <= budget
+    rows = [int(np.flatnonzero((got["kp_idx"] == r).all(axis=1))[0]) for r in s1["kp_idx"]]
+    assert rows == sorted(set(rows))
+    for k in outs:
+        assert np.array_equal(s1[k], s2[k]) and np.array_equal(s1[k], got[k][rows])
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0"], {"FUSG_BENCH_DRYRUN": "1"})
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -19,7 +19,7 @@ def test_bench_gpus2_self_spawn():
     if torch.cuda.device_count() < 2:
         env["FUSG_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "2", "--res", "128", "--settle-s", "0", "--no-cpu-baseline", "--no-clip"],
+                        "--batch", "2", "--res", "128", "--settle-s", "0", "--full", "--no-cpu-baseline", "--no-clip"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -118,3 +118,39 @@ def test_rccl_collectives_with_a_one_rank_communicator():
     line = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][0]
     assert line["rccl_ranks"] == world and line["dist_backend"] == "nccl" and "dist_ranks" not in line and line["value"] > 0
     assert line["weights"].startswith("broadcast from rank 0")
+
+
+def _plain_bench(out_dir):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "2", "--res", "128", "--settle-s", "0", "--dump-outputs", str(out_dir)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return lines[0]
+
+
+def test_plain_bench_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the f16x3 leg only, for exactly --steps steps, and --dump-outputs writes the last
+    timed step's outputs as float .npy files; a second run with the same arguments computes the same outputs."""
+    import numpy as np
+    line = _plain_bench(tmp_path / "a")
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "crops/s"
+    assert line["higher_is_better"] is True and line["dtype"].startswith("f32 tensors")
+    assert abs(line["value"] - 2 * 1000.0 / line["ms_per_step"]) <= 0.01 * line["value"]
+    assert set(line["precision_legs"]) == {"f16x3"} and line["roofline"] is None and line["cpu_baseline"] is None
+    assert "clip_mode" not in line and "frame_mode" not in line and "power" not in line
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert {"kp_idx", "icn_u8", "vunet_u8"} <= set(a)
+    assert a["kp_idx"].shape == (2, 12) and a["kp_idx"].dtype == np.float64
+    for k in ("icn_u8", "vunet_u8"):
+        assert a[k].shape == (2, 128, 128, 3) and a[k].dtype == np.float32
+        assert a[k].min() >= 0 and a[k].max() <= 255 and np.array_equal(a[k], np.round(a[k])) and a[k].std() > 0
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    _plain_bench(tmp_path / "b")
+    b = {f[:-4]: np.load(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b"))}
+    assert set(b) == set(a)
+    assert np.array_equal(a["kp_idx"], b["kp_idx"])
+    for k in a:
+        assert np.abs(a[k] - b[k]).max() <= (1.0 if k.endswith("_u8") else 1e-3 * max(1.0, np.abs(a[k]).max())), k

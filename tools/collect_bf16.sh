@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 for cfg in "256 32" "512 16"; do
   set -- $cfg; res=$1; b=$2
   args="--res $res --batch $b --precision bf16 --no-cpu-baseline --no-clip"
-  FUSG_STREAMS=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats --output-format csv -- python3 $R/bench.py --steps 6 --warmup 3 $args > $out/stats_$res.log 2>&1
+  FUSG_STREAMS=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats --output-format csv -- python3 $R/bench.py --full --steps 6 --warmup 3 $args > $out/stats_$res.log 2>&1
   grep '^{"metric"' $out/stats_$res.log > $out/${tag}_bench_bf16_${res}_serial_under_rocprof.json
   cp $(ls $out/stats/*/*_kernel_stats.csv | head -1) $out/${tag}_bench_bf16_${res}_kernel_stats.csv
   rm -rf $out/stats

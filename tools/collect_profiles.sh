@@ -7,12 +7,12 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/$tag
 mkdir -p $out
 cd $R
-timeout -k 10 600 python bench.py > $out/bench_cfg1.log 2>&1 && grep '^{"metric"' $out/bench_cfg1.log > $out/${tag}_bench_cfg1.json
+timeout -k 10 600 python bench.py --full > $out/bench_cfg1.log 2>&1 && grep '^{"metric"' $out/bench_cfg1.log > $out/${tag}_bench_cfg1.json
 echo "bench cfg1 (both precision legs) done"
-timeout -k 10 500 python bench.py --inpaint --no-cpu-baseline > $out/bench_cfg2.log 2>&1 && grep '^{"metric"' $out/bench_cfg2.log > $out/${tag}_bench_cfg2_inpaint.json
+timeout -k 10 500 python bench.py --full --inpaint --no-cpu-baseline > $out/bench_cfg2.log 2>&1 && grep '^{"metric"' $out/bench_cfg2.log > $out/${tag}_bench_cfg2_inpaint.json
 echo "bench cfg2 done"
-timeout -k 10 500 python bench.py --res 512 --batch 16 --precision f16x3 --no-cpu-baseline --no-clip > $out/bench_512.log 2>&1 && grep '^{"metric"' $out/bench_512.log > $out/${tag}_bench_512_b16_f16x3.json
-timeout -k 10 300 python bench.py --res 512 --batch 16 --precision bf16 --no-cpu-baseline --no-clip > $out/bench_512_bf16.log 2>&1 && grep '^{"metric"' $out/bench_512_bf16.log > $out/${tag}_bench_512_b16_bf16.json
+timeout -k 10 500 python bench.py --full --res 512 --batch 16 --precision f16x3 --no-cpu-baseline --no-clip > $out/bench_512.log 2>&1 && grep '^{"metric"' $out/bench_512.log > $out/${tag}_bench_512_b16_f16x3.json
+timeout -k 10 300 python bench.py --full --res 512 --batch 16 --precision bf16 --no-cpu-baseline --no-clip > $out/bench_512_bf16.log 2>&1 && grep '^{"metric"' $out/bench_512_bf16.log > $out/${tag}_bench_512_b16_bf16.json
 echo "bench 512 done"
 FUSG_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --batch 16 --precision f16x3 --no-cpu-baseline --no-clip --no-prof > $out/bench_2rank.log 2>&1 && grep '^{"metric"' $out/bench_2rank.log > $out/${tag}_bench_2ranks_one_card_gloo.json
 echo "2-rank rehearsal done"
@@ -20,11 +20,11 @@ timeout -k 10 300 python tools/small_batch.py 2>&1 | grep -v amdgpu.ids > $out/$
 echo "small batch done"
 cd /tmp && export TMPDIR=/tmp
 # kernel-trace stats of the serialised pass (what the roofline leg measures)
-FUSG_STREAMS=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats --output-format csv -- python3 $R/bench.py --steps 10 --warmup 5 --precision f16x3 --no-cpu-baseline --no-clip > $out/stats.log 2>&1
+FUSG_STREAMS=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats --output-format csv -- python3 $R/bench.py --full --steps 10 --warmup 5 --precision f16x3 --no-cpu-baseline --no-clip > $out/stats.log 2>&1
 grep '^{"metric"' $out/stats.log > $out/${tag}_bench_cfg1_serial_under_rocprof.json
 cp $(ls $out/stats/*/*_kernel_stats.csv | head -1) $out/${tag}_bench_cfg1_kernel_stats.csv
 # the exact-fp32 leg (round 4: halo kernel mode 2, fused Bottleneck in fp32)
-FUSG_STREAMS=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats32 --output-format csv -- python3 $R/bench.py --steps 5 --warmup 3 --precision f32 --no-cpu-baseline --no-clip > $out/stats32.log 2>&1
+FUSG_STREAMS=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats32 --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 3 --precision f32 --no-cpu-baseline --no-clip > $out/stats32.log 2>&1
 grep '^{"metric"' $out/stats32.log > $out/${tag}_bench_f32_serial_under_rocprof.json
 cp $(ls $out/stats32/*/*_kernel_stats.csv | head -1) $out/${tag}_bench_f32_kernel_stats.csv
 echo "rocprof stats done"
