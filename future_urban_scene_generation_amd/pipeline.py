@@ -148,14 +148,16 @@ class VehiclePipeline:
     """Holds the five networks on one device and runs batches of crops through them."""
 
     def __init__(self, device, inpaint: bool = False, state_dicts: Optional[Dict[str, dict]] = None, seed: int = 0,
-                 broadcast_src: Optional[int] = None, group=None, cad: bool = False):
+                 broadcast_src: Optional[int] = None, group=None, cad: bool = False, cad_bank=None):
         """state_dicts: checkpoints (the reference's keys) per network; a missing network gets the synthetic weights of
         `seed`.  broadcast_src: with an initialised process group, only that rank needs to hold `state_dicts` (a real
         checkpoint read from disk on rank 0): they are distributed with `broadcast_state_dicts` first (north_star: RCCL
         broadcast of the shared weights), so every rank renders with identical parameters.
         cad: also hold the reference's CAD-model classifier (VGG-19, 10 classes; state_dicts['vgg'] = `cads/model.pth`,
         run_test.py:47-58) and run it on the hourglass's crop in every pass (trajectory_inference.py:66-69): 'cad_logits' /
-        `run_frame`'s 'cad_idx'.  Not part of BASELINE's crop pass: `bench.py` leaves it off."""
+        `run_frame`'s 'cad_idx'.  Not part of BASELINE's crop pass: `bench.py` leaves it off.
+        cad_bank: a `render.CadBank` - enables the geometry mode of `run_frame` / `run_later_frame` (a scene without 'masks':
+        the sketches, masks, planes and visibilities are rendered on the device from the fitted pose)."""
         from .edgeconnect.models import EdgeModel, InpaintingModel
         from .stacked_hourglass.models import HourglassNet
         from .synth import synth_state_dict
@@ -165,6 +167,7 @@ class VehiclePipeline:
         self.inpaint = inpaint
         self.group = group
         self.cad = None
+        self.cad_bank = cad_bank
         if broadcast_src is not None:
             import torch.distributed as dist
             if not _one_rank(group):
@@ -380,6 +383,8 @@ class VehiclePipeline:
         self.vunet.set_vehicle_seeds(vehicle_seeds)
 
         def hg():
+            if "kp_idx" in batch:                                 # geometry mode: the hourglass ran before the render
+                return {k: batch[k] for k in ("kp_idx", "cad_logits") if k in batch}
             out = {"kp_idx": ops.argmax_hw(self.hg(batch["hg_x"])["heatmaps"][-1])}
             if self.cad is not None:                              # same crop, same branch (:66-69): a stream of its own costs more
                 out["cad_logits"] = self.cad(batch["hg_x"])
@@ -445,7 +450,11 @@ class VehiclePipeline:
 
         Returns 'kp_idx' int32 [V, 12], 'kp_xy' float32 [V, 12, 2], 'pose' = list of (error, rvec [3, 1], tvec [3, 1]),
         'icn_u8' / 'vunet_u8' uint8 [V, R, R, 3] (BGR), 'frame_icn' / 'frame_vunet' uint8 [H, W, 3], 'geom' int32 [V, 8],
-        'state' = what `run_later_frame` needs to render the same vehicles' future frames (VUnet appearance code, central crop)."""
+        'state' = what `run_later_frame` needs to render the same vehicles' future frames (VUnet appearance code, central crop).
+
+        Geometry mode (a pipeline built with cad_bank, a scene without 'masks'): see `_geometry_frame`."""
+        if "masks" not in scene and self.cad_bank is not None:
+            return self._geometry_frame(scene, check, replay)
         rng = torch.get_rng_state() if check == "sync" else None
         import torch.distributed as dist
         world = dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -470,6 +479,153 @@ class VehiclePipeline:
         out["pose"] = [select_and_flip(rv[i], tv[i], er[i]) for i in range(rv.shape[0])]
         return out
 
+    # ------------------------------------------------------------------------------------------ geometry mode
+    def _geometry_checks(self, replay):
+        if replay:
+            raise NotImplementedError("geometry mode (cad_bank, scene without 'masks') runs eagerly: replay=True is not supported")
+        if not _one_rank(self.group):
+            raise NotImplementedError("geometry mode (cad_bank, scene without 'masks') runs on one rank: the pose fit is "
+                                      "rank-0-only in the sharded path")
+
+    @staticmethod
+    def _given_geometry_only(scenes):
+        for scene in scenes:
+            if "masks" not in scene:
+                raise NotImplementedError("geometry mode (cad_bank, scene without 'masks') is not pipelined: call run_frame "
+                                          "per frame")
+            yield scene
+
+    @staticmethod
+    def _select(scene: Dict, keep, keys) -> Dict:
+        """The scene restricted to the vehicles `keep` (host index list) for the per-vehicle `keys`."""
+        import numpy as np
+        out = dict(scene)
+        idx = torch.as_tensor(keep, dtype=torch.long)
+        for k in keys:
+            v = scene.get(k)
+            if v is None or k == "inpaint":
+                continue
+            if torch.is_tensor(v):
+                out[k] = v.index_select(0, idx.to(v.device))
+            elif isinstance(v, np.ndarray):
+                out[k] = v[np.asarray(keep, dtype=np.int64)]
+            else:
+                out[k] = [v[i] for i in keep]
+        if scene.get("inpaint") is not None and "inpaint" in keys:
+            out["inpaint"] = VehiclePipeline._select(scene["inpaint"], keep, list(scene["inpaint"].keys()))
+        return out
+
+    def _geometry_frame(self, scene: Dict, check, replay) -> Dict:
+        """run_frame in geometry mode: scene = 'frame', 'bboxes', 'focals', 'centers' (+ 'cad_idx' [V] when the pipeline has
+        no CAD classifier, optional 'background', 'inpaint', 'vehicle_seeds').  The reference's order (trajectory_inference.py:
+        55-253, warp_learn/vehicle_utils.py:12-32): hourglass -> argmax -> keypoints -> pose fit on the device -> host
+        select_and_flip -> extrinsics; render + plane visibility on the device (render.vehicle_geometry, one D2H of the
+        counts); then the given-geometry path of `run_frame` on the vehicles whose render is not empty.
+        Returns run_frame's keys ('kp_idx', 'kp_xy', 'pose' (+ 'cad_idx') for every vehicle; 'icn_u8', 'vunet_u8', 'geom'
+        (+ 'inpaint_u8') for the rendered ones, in order), 'geometry' = the derived scene keys of every vehicle ('masks',
+        'src_sketch', 'dst_sketch', 'src_planes', 'src_kp', 'dst_kp', 'src_vis', 'dst_vis', 'kp3d', 'cad_idx'), 'skipped' =
+        the vehicles whose render is empty (the reference's `except: continue`, :252-253: no networks, no paste) and
+        'state' for `run_later_frame`."""
+        import numpy as np
+
+        from . import frame_ops as fo
+        from . import ops
+        from . import render as rd
+        from .utils.pnp_utils import cpc_fit_device, select_and_flip
+        self._geometry_checks(replay)
+        dev, bank = self.device, self.cad_bank
+        frame = scene["frame"]
+        H, W, _ = frame.shape
+        bboxes = np.asarray(scene["bboxes"]).reshape(-1, 4)
+        V, R = bboxes.shape[0], 256
+
+        @torch.no_grad()
+        def keypoints():
+            geom_box = fo.box_geometry((H, W), bboxes, dev)
+            hg_x = fo.crop_resize(frame, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD)        # :58-65
+            pre = {"kp_idx": ops.argmax_hw(self.hg(hg_x)["heatmaps"][-1])}                              # :75-79
+            if self.cad is not None:
+                pre["cad_logits"] = self.cad(hg_x)                                                      # :66-69
+            pre["kp_xy"] = fo.keypoints_to_frame(pre["kp_idx"], geom_box, (R // 4, R // 4))              # :95-97
+            return pre
+
+        with torch.cuda.device(dev):
+            pre = self._guarded(keypoints, (), check, None) if V else {}
+            if self.cad is not None:
+                cad_idx = pre["cad_logits"].argmax(1).cpu().numpy() if V else np.zeros(0, np.int64)
+            else:
+                if scene.get("cad_idx") is None:
+                    raise ValueError("geometry mode: the scene needs 'cad_idx' [V] (or a pipeline built with cad=True)")
+                cad_idx = np.asarray(scene["cad_idx"], np.int64).reshape(V)
+            if V:
+                f32 = lambda a: ops.h2d(np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32).reshape(-1, 2), (V, 2))), dev)   # noqa: E731
+                raw = cpc_fit_device(f32(scene["focals"]), f32(scene["centers"]), pre["kp_xy"],
+                                     ops.h2d(bank.kp3d[cad_idx], dev))                                       # :104-105
+                rv, tv, er = (t.cpu().numpy() for t in raw)
+                pose = [select_and_flip(rv[i], tv[i], er[i]) for i in range(V)]
+                kp_xy = pre["kp_xy"].cpu().numpy()
+            else:
+                pose, kp_xy = [], np.zeros((0, 12, 2), np.float32)
+            K = rd.intrinsic(scene["focals"], scene["centers"])
+            g = rd.vehicle_geometry(bank, frame, cad_idx, [(p[1], p[2]) for p in pose], K, kp_xy=kp_xy)
+        keep = [v for v in range(V) if g["covered"][v] > 0]
+        geometry = {k: g[k] for k in ("masks", "src_sketch", "dst_sketch", "src_planes", "src_kp", "dst_kp", "src_vis", "dst_vis")}
+        geometry["kp3d"] = bank.kp3d[cad_idx]
+        geometry["cad_idx"] = cad_idx
+        sub = self._select({**scene, **geometry}, keep, PER_VEHICLE_KEYS + ("cad_idx", "inpaint"))
+        sub.pop("cad_idx", None)
+        if V:
+            hg = {"kp_idx": pre["kp_idx"]}
+            if self.cad is not None:
+                hg["cad_logits"] = pre["cad_logits"]
+            sub["_hg"] = self._select(hg, keep, list(hg))
+        out = self.run_frame(sub, check=check)
+        out["kp_idx"] = pre["kp_idx"] if V else out["kp_idx"]
+        out["kp_xy"] = pre["kp_xy"] if V else out["kp_xy"]
+        out["pose"] = pose
+        if self.cad is not None:
+            out["cad_idx"] = torch.as_tensor(cad_idx, device=dev)
+        out["geometry"] = geometry
+        out["skipped"] = [v for v in range(V) if v not in keep]
+        if out.get("state") is not None:
+            out["state"]["geometry"] = {"vehicles": keep, "cad_idx": cad_idx[keep], "pose": [pose[v] for v in keep],
+                                        "focals": scene["focals"], "centers": scene["centers"],
+                                        **self._select(geometry, keep, ("src_planes", "src_kp", "src_vis"))}
+        return out
+
+    def _geometry_later_frame(self, scene: Dict, state: Dict, check, replay) -> Dict:
+        """run_later_frame in geometry mode: scene = 'frame' (+ 'background', 'vehicle_seeds') and 'steps' = (theta, tr) per
+        vehicle of the first frame (`render.trajectory_steps`).  Each vehicle the first frame rendered is moved (mesh and
+        3-D keypoints by v @ z_rot(theta) + tr, trajectory_inference.py:359-363), rendered at the first frame's extrinsic,
+        its moved keypoints projected with K (:364-367) -> 'dst_sketch', 'masks', 'dst_kp', 'dst_vis'
+        (render.vehicle_geometry); then the given-geometry path of `run_later_frame` for the vehicles whose render is not
+        empty.  Returns its keys (for those vehicles, in order), 'geometry' (the derived keys of every vehicle of the
+        state) and 'skipped' (first-frame vehicle indices: skipped there or rendering empty now - not pasted)."""
+        import numpy as np
+
+        from . import render as rd
+        self._geometry_checks(replay)
+        gs = state["geometry"]
+        veh = list(gs["vehicles"])
+        steps = [scene["steps"][v] for v in veh]
+        K = rd.intrinsic(gs["focals"], gs["centers"])
+        with torch.cuda.device(self.device):
+            g = rd.vehicle_geometry(self.cad_bank, scene["frame"], gs["cad_idx"], [(p[1], p[2]) for p in gs["pose"]], K, steps=steps)
+        keep = [i for i in range(len(veh)) if g["covered"][i] > 0]
+        geometry = {k: g[k] for k in ("masks", "dst_sketch", "dst_kp", "dst_vis")}
+        geometry["kp3d"] = g["kp3d"]
+        sub = self._select({**scene, **geometry, "src_planes": gs["src_planes"], "src_kp": gs["src_kp"], "src_vis": gs["src_vis"]},
+                           keep, ("masks", "dst_sketch", "dst_kp", "dst_vis", "src_planes", "src_kp", "src_vis"))
+        if scene.get("vehicle_seeds") is not None:
+            sub["vehicle_seeds"] = [scene["vehicle_seeds"][veh[i]] for i in keep]
+        sub.pop("steps", None)
+        sub_state = dict(state, geometry=None, appearance=[self._select({"a": a}, keep, ("a",))["a"] for a in state["appearance"]],
+                         central=self._select({"c": state["central"]}, keep, ("c",))["c"])
+        out = self.run_later_frame(sub, sub_state, check=check)
+        out["geometry"] = geometry
+        out["skipped"] = [v for v in range(len(scene["steps"])) if v not in [veh[i] for i in keep]]
+        return out
+
     def run_frames(self, scenes, replay: bool = True):
         """`run_frame` over a sequence of frames (the reference's outer loop, trajectory_inference.py:283-300), software-
         pipelined one frame deep: frame i+1's host work (40 homography fits, ~40 launches of glue, the networks' replay)
@@ -479,6 +635,8 @@ class VehiclePipeline:
         is the caller's (nothing aliases a later frame's buffers).  A frame whose split-fp16 range status is raised is
         redone in exact fp32 before it is yielded, with the RNG state it was issued under."""
         import torch.distributed as dist
+        if self.cad_bank is not None:
+            scenes = self._given_geometry_only(scenes)
         if not _one_rank(self.group):
             # sharded frames, one frame deep as well: every rank issues its shard of frame i+1 before frame i's crops are
             # gathered; the gather and rank 0's frame-level part run on a communication stream that waits for frame i's
@@ -708,6 +866,8 @@ class VehiclePipeline:
                                          out=(tgt["vu_x"], tgt["vu_y"]) if tgt else None)       # :203-228
             # ---- the three networks: the crop pass of `run` (three stream branches), eagerly or as one plan replay
             nets_in = {"hg_x": hg_x, "icn_x": icn_x, "vu_x": vu_x, "vu_y": vu_y}
+            if scene.get("_hg") is not None:                      # geometry mode: keypoints (and CAD logits) already computed
+                nets_in.update(scene["_hg"])
             if inp is not None:                                   # :121: create_inpaint_inputs_shape's four tensors, given
                 nets_in.update(ec_img=inp["img"], ec_gray=inp["gray"], ec_edge=inp["edge"], ec_mask=inp["mask"])
             if replay:
@@ -789,7 +949,11 @@ class VehiclePipeline:
         images independent of batching); state: `run_frame(...)["state"]` of the same vehicles, same order.
         replay=True issues the two networks (ICN, VUnet shape half) as ONE recorded-plan replay per vehicle count, like
         `run_frame(replay=True)`: five of a clip's six frames are later frames, and at 8 vehicles the interpreter bounds the eager form.
-        Returns 'icn_u8' / 'vunet_u8' uint8 [V, R, R, 3] (BGR), 'frame_icn' / 'frame_vunet' uint8 [H, W, 3], 'geom'."""
+        Returns 'icn_u8' / 'vunet_u8' uint8 [V, R, R, 3] (BGR), 'frame_icn' / 'frame_vunet' uint8 [H, W, 3], 'geom'.
+
+        Geometry mode (state of a geometry-mode `run_frame`, a scene without 'masks'): see `_geometry_later_frame`."""
+        if "masks" not in scene and state.get("geometry") is not None:
+            return self._geometry_later_frame(scene, state, check, replay)
         rng = torch.get_rng_state() if (check == "sync" and scene.get("vehicle_seeds") is None) else None
         import torch.distributed as dist
         if not _one_rank(self.group) and state.get("sharded"):

@@ -1,0 +1,413 @@
+"""Per-vehicle geometry on the MI355X: the posed CAD model rendered into a normal-colour sketch and its mask, the plane
+visibilities and the plane corner points - what the reference computes between the pose fit and the plane warp
+(warp_learn/vehicle_utils.py:12-32) with an Open3D window per vehicle and frame (warp_learn/render_open3d.py:29-49) and
+OpenCV polygon fills (warp_learn/online_visibility.py:105-150).  The image work runs in ``csrc/render.hip``
+(``fusg_render_normals_u8``, ``fusg_plane_visibility``); the host keeps what is a few numbers per vehicle (the pose ->
+extrinsic, the 3-D keypoint projections, the plane distances).
+
+Conventions (each restated from the reference line given):
+  - vertices are scaled x5 at load (run_test.py:148-151), the 3-D keypoints too, in float32 (trajectory_inference.py:87-90);
+  - the mesh moves as a row vector, p = v @ z_rot(theta) + tr (trajectory_inference.py:363), the camera is E[:3, :3] p + E[:3, 3];
+  - the render uses Open3D's default principal point (W/2 - 0.5, H/2 - 0.5), not K's cx, cy ("this must be left as they
+    are", render_open3d.py:20); the keypoint projections use K.  The mismatch is the reference's and is kept;
+  - vertex normals as Open3D's compute_vertex_normals: unnormalised face cross products summed per vertex, then normalised;
+    computed once per bank mesh in float64 and rotated per job by z_rot(theta); colour (n + 1) / 2 -> round(255 c);
+  - a plane is visible when its uncovered area is more than 0.9 of its area (online_visibility.py:145-148), in float64;
+    camera position = inv(E)[:3, 3], plane distance = |camera - mean of the plane's 3-D keypoints| (:58-72).
+Parity with Open3D / OpenCV themselves is unpinned (neither is a dependency); tests pin the kernels to a numpy
+restatement of these conventions (tests/render_ref.py).
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .warp_learn import planes_utils as pu
+
+KP_NAMES = ("left_back_trunk", "left_back_wheel", "left_front_light", "left_front_wheel", "right_back_trunk", "right_back_wheel",
+            "right_front_light", "right_front_wheel", "upper_left_rearwindow", "upper_left_windshield", "upper_right_rearwindow",
+            "upper_right_windshield")                                # utils/keypoint_utils.py:9-13 (_KP_NAMES)
+# compute_visibility's planes: the five texture planes plus the two it adds for occlusion only (online_visibility.py:107-113)
+VIS_PLANES = dict(pu.CAR_TEXTURE_PLANES,
+                  front_bt=["left_front_light", "right_front_light", "right_front_wheel", "left_front_wheel"],
+                  back_bt=["left_back_trunk", "right_back_trunk", "right_back_wheel", "left_back_wheel"])
+TEXTURE_PLANES = tuple(pu.CAR_TEXTURE_PLANES.keys())
+SCALE = 5.0                                                          # _____SCALE_F (run_test.py:148)
+NEAR_Z = 1e-3                                                        # csrc/render.hip: triangles with a vertex nearer are dropped
+JOB_DTYPE = np.dtype([("R", "<f8", 9), ("tr", "<f8", 3), ("E", "<f8", 12), ("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"),
+                      ("cy", "<f8"), ("v_off", "<i4"), ("nv", "<i4"), ("t_off", "<i4"), ("nt", "<i4")])   # fusg_render_job
+
+
+def z_rot(alpha: float) -> np.ndarray:
+    """utils/geometry.py:80-110 (counter-clockwise rotation about Z, numpy form)."""
+    cz, sz = np.cos(alpha), np.sin(alpha)
+    return np.asarray([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+
+
+def vertex_normals(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:
+    """Open3D's TriangleMesh.compute_vertex_normals in float64: per face the unnormalised cross product
+    (v1 - v0) x (v2 - v0), summed onto its three vertices in face order, then normalised (a zero sum stays zero)."""
+    v = np.asarray(vertices, np.float64)
+    t = np.asarray(triangles, np.int64)
+    fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    n = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(n, t[:, k], fn)
+    norm = np.sqrt((n * n).sum(1, keepdims=True))
+    return np.where(norm > 0, n / np.where(norm > 0, norm, 1.0), n)
+
+
+# ---------------------------------------------------------------------------------------------- PLY
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """vertices float64 [n, 3] (x, y, z) and triangles int64 [m, 3] (face vertex_indices) of an ascii or
+    binary_little_endian PLY file - what o3d.io.read_triangle_mesh gives the reference (utils/cad_utils.py:24).  Faces
+    of more than three vertices are fanned (0, i, i + 1).  Other properties are read past and ignored."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data[data.index(b"\n", end) + 1:]
+    fmt, elements = None, []
+    for line in data[:end].decode("ascii", "replace").splitlines():
+        w = line.split()
+        if not w:
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == "property" and elements:
+            if w[1] == "list":
+                elements[-1][2].append((w[4], "list", _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]))
+            else:
+                elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r} not supported (ascii, binary_little_endian)")
+    verts, faces = None, []
+    if fmt == "ascii":
+        toks = body.split()
+        pos = 0
+        for name, count, props in elements:
+            rows = []
+            for _ in range(count):
+                row = {}
+                for p in props:
+                    if p[1] == "list":
+                        n = int(toks[pos]); pos += 1
+                        row[p[0]] = [int(x) for x in toks[pos:pos + n]]; pos += n
+                    else:
+                        row[p[0]] = float(toks[pos]); pos += 1
+                rows.append(row)
+            if name == "vertex":
+                verts = np.array([[r["x"], r["y"], r["z"]] for r in rows], np.float64).reshape(-1, 3)
+            elif name == "face":
+                faces = [r.get("vertex_indices", r.get("vertex_index", [])) for r in rows]
+    else:
+        pos = 0
+        for name, count, props in elements:
+            if all(p[1] != "list" for p in props):
+                dt = np.dtype([(p[0], "<" + p[1]) for p in props])
+                arr = np.frombuffer(body, dt, count, pos)
+                pos += count * dt.itemsize
+                if name == "vertex":
+                    verts = np.stack([arr["x"], arr["y"], arr["z"]], 1).astype(np.float64)
+                continue
+            rows = []
+            for _ in range(count):
+                row = {}
+                for p in props:
+                    if p[1] == "list":
+                        ct, it = np.dtype("<" + p[2]), np.dtype("<" + p[3])
+                        n = int(np.frombuffer(body, ct, 1, pos)[0]); pos += ct.itemsize
+                        row[p[0]] = np.frombuffer(body, it, n, pos).astype(np.int64).tolist(); pos += n * it.itemsize
+                    else:
+                        dt = np.dtype("<" + p[1])
+                        row[p[0]] = np.frombuffer(body, dt, 1, pos)[0]; pos += dt.itemsize
+                rows.append(row)
+            if name == "face":
+                faces = [r.get("vertex_indices", r.get("vertex_index", [])) for r in rows]
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    tris = [(f[0], f[i], f[i + 1]) for f in faces for i in range(1, len(f) - 1)]
+    return verts, np.array(tris, np.int64).reshape(-1, 3)
+
+
+# ---------------------------------------------------------------------------------------------- CAD bank
+class CadBank:
+    """The CAD models of a run (run_test.py:146-151): per model the vertices (x5), triangles, unit vertex normals of the
+    unmoved mesh and the 12 3-D keypoints (x5, float32, in KP_NAMES order).  Uploaded once per device (`device_arrays`)."""
+
+    def __init__(self, meshes: Sequence[Tuple[np.ndarray, np.ndarray, object]], scale: float = SCALE):
+        """meshes: (vertices [n, 3], triangles [m, 3], kp3d) per model, in the file's units; kp3d a dict name -> xyz (the
+        yaml's kpoints_3d) or an array [12, 3] in KP_NAMES order.  Triangle indices are checked here."""
+        self.vertices, self.triangles, self.normals, kps = [], [], [], []
+        for i, (v, t, kp) in enumerate(meshes):
+            v = np.asarray(v, np.float64).reshape(-1, 3) * scale
+            t = np.asarray(t).reshape(-1, 3)
+            if len(v) == 0 or len(t) == 0:
+                raise ValueError(f"CadBank: model {i} has no vertices or no triangles")
+            if t.min() < 0 or t.max() >= len(v):
+                raise ValueError(f"CadBank: model {i} has a triangle index outside [0, {len(v)})")
+            if isinstance(kp, dict):
+                kp = [kp[n] for n in KP_NAMES]
+            kp = np.asarray(kp, np.float32).reshape(len(KP_NAMES), 3)
+            self.vertices.append(np.ascontiguousarray(v))
+            self.triangles.append(np.ascontiguousarray(t, dtype=np.int32))
+            self.normals.append(vertex_normals(v, t))
+            kps.append(kp * np.float32(scale))                      # float32 arithmetic, as trajectory_inference.py:87-90
+        self.kp3d = np.stack(kps)                                   # float32 [M, 12, 3]
+        self.v_off = np.cumsum([0] + [len(v) for v in self.vertices])
+        self.t_off = np.cumsum([0] + [len(t) for t in self.triangles])
+        self._dev: Dict[torch.device, Dict[str, torch.Tensor]] = {}
+
+    @classmethod
+    def from_files(cls, cad_root: str, indices: Sequence[int] = range(10), pascal_class: str = "car") -> "CadBank":
+        """The reference's file layout (utils/cad_utils.py:8-24): pascal_<class>_cad_NNN.ply with pascal_<class>_cad_NNN.yaml
+        holding 'kpoints_3d'."""
+        import yaml
+        meshes = []
+        for i in indices:
+            stem = os.path.join(str(cad_root), f"pascal_{pascal_class}_cad_{i:03d}")
+            v, t = read_ply(stem + ".ply")
+            with open(stem + ".yaml") as f:
+                kp = yaml.safe_load(f)["kpoints_3d"]
+            meshes.append((v, t, kp))
+        return cls(meshes)
+
+    def __len__(self) -> int:
+        return len(self.vertices)
+
+    def device_arrays(self, device) -> Dict[str, torch.Tensor]:
+        dev = torch.device(device)
+        if dev not in self._dev:
+            # C order: the kernels index rows of 3 (np.concatenate keeps the Fortran order of an F-ordered input)
+            self._dev[dev] = {k: torch.from_numpy(np.ascontiguousarray(np.concatenate(a))).to(dev)
+                              for k, a in (("verts", self.vertices), ("normals", self.normals), ("tris", self.triangles))}
+        return self._dev[dev]
+
+
+def extrinsic_from_pose(rvec, tvec) -> np.ndarray:
+    """utils/geometry.py:203-220: 4x4 [R(rvec) | tvec] in the vectors' dtype (float32 after select_and_flip)."""
+    from .utils.pnp_utils import rodrigues
+    r = np.asarray(rvec).reshape(3)
+    E = np.eye(4, dtype=r.dtype)
+    E[:3, :3] = rodrigues(r)
+    E[:3, 3] = np.asarray(tvec).reshape(3)
+    return E
+
+
+def render_jobs(bank: CadBank, mesh_idx: Sequence[int], E: Sequence[np.ndarray], fx: float, fy: float, frame_hw: Tuple[int, int],
+                R: Optional[Sequence[np.ndarray]] = None, tr: Optional[Sequence[np.ndarray]] = None) -> np.ndarray:
+    """fusg_render_job records (host); R / tr default to the unmoved mesh; principal point = Open3D's default."""
+    H, W = frame_hw
+    J = len(mesh_idx)
+    jobs = np.zeros(J, JOB_DTYPE)
+    for j, m in enumerate(mesh_idx):
+        m = int(m)
+        if not 0 <= m < len(bank):
+            raise IndexError(f"render: mesh {m} not in a bank of {len(bank)}")
+        jobs[j]["R"] = (np.eye(3) if R is None else np.asarray(R[j], np.float64)).reshape(9)
+        jobs[j]["tr"] = np.zeros(3) if tr is None else np.asarray(tr[j], np.float64).reshape(3)
+        jobs[j]["E"] = np.asarray(E[j], np.float64)[:3, :4].reshape(12)
+        jobs[j]["fx"], jobs[j]["fy"] = fx, fy
+        jobs[j]["cx"], jobs[j]["cy"] = W / 2 - 0.5, H / 2 - 0.5    # render_open3d.py:20: Open3D's, not K's
+        jobs[j]["v_off"], jobs[j]["nv"] = bank.v_off[m], len(bank.vertices[m])
+        jobs[j]["t_off"], jobs[j]["nt"] = bank.t_off[m], len(bank.triangles[m])
+    return jobs
+
+
+def render_vehicles(bank: CadBank, mesh_idx: Sequence[int], E: Sequence[np.ndarray], fx: float, fy: float,
+                    frame_hw: Tuple[int, int], device, R=None, tr=None, tri_id: bool = False) -> Dict[str, torch.Tensor]:
+    """get_rendered (render_open3d.py:29-49) for J posed meshes in one launch: 'sketch' uint8 [J, H, W, 3], 'mask' uint8
+    [J, H, W] (1 = vehicle: the complement of the reference's object_mask), 'covered' int32 [J] (device tensors), and
+    with tri_id=True 'tri' int32 [J, H, W] (winning triangle within its mesh, -1 = background)."""
+    dev = torch.device(device)
+    H, W = frame_hw
+    jobs = render_jobs(bank, mesh_idx, E, fx, fy, frame_hw, R, tr)
+    J = len(jobs)
+    out = {"sketch": torch.zeros((J, H, W, 3), dtype=torch.uint8, device=dev),
+           "mask": torch.zeros((J, H, W), dtype=torch.uint8, device=dev),
+           "covered": torch.zeros((J,), dtype=torch.int32, device=dev)}
+    if tri_id:
+        out["tri"] = torch.full((J, H, W), -1, dtype=torch.int32, device=dev)
+    if J == 0:
+        return out
+    arr = bank.device_arrays(dev)
+    max_nv = int(jobs["nv"].max())
+    ws_bytes = J * (16 + 40 * max_nv)
+    with torch.cuda.device(dev):
+        jobs_d = ops.h2d(np.frombuffer(jobs.tobytes(), np.uint8), dev)
+        ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+        L.check(L.lib().fusg_render_normals_u8(arr["verts"].data_ptr(), arr["normals"].data_ptr(), arr["verts"].shape[0],
+                                               arr["tris"].data_ptr(), arr["tris"].shape[0], jobs_d.data_ptr(), J, max_nv, H, W,
+                                               ws.data_ptr(), ws.numel() * 8, out["sketch"].data_ptr(), out["mask"].data_ptr(),
+                                               out["tri"].data_ptr() if tri_id else None, out["covered"].data_ptr(),
+                                               ops.stream_ptr()), "render_normals_u8")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- visibility
+def project_points(points_3d: np.ndarray, K: np.ndarray, E: np.ndarray) -> np.ndarray:
+    """online_visibility.py:27-55 (pin-hole with K): [n, 3] -> [n, 2]."""
+    p = np.asarray(points_3d)
+    ph = np.concatenate([p, np.ones((p.shape[0], 1))], 1)
+    q = np.asarray(K) @ np.asarray(E)[:3, :] @ ph.T
+    q /= q[2, :]
+    return q.T[:, :2]
+
+
+def visibility_inputs(kp3d: np.ndarray, E: np.ndarray, K: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The host part of compute_visibility for one vehicle: kp3d [12, 3] (KP_NAMES order, already moved), E 4x4, K 3x3 ->
+    polygons int32 [7, 8, 2] (the keypoints projected with K one at a time and int()-truncated, :76-77, :127-131), vertex
+    counts int32 [7] and per plane the bitmask of the planes strictly nearer the camera (:58-72, :96-100)."""
+    kp = {n: np.asarray(kp3d[i]) for i, n in enumerate(KP_NAMES)}
+    cam = np.linalg.inv(E)[:3, -1][np.newaxis]
+    names = list(VIS_PLANES)
+    dist = [float(np.linalg.norm(cam - np.mean([kp[k] for k in VIS_PLANES[p]], 0), axis=1)[0]) for p in names]
+    k2 = {n: project_points(np.asarray(kp[n])[np.newaxis], K, E)[0] for n in KP_NAMES}
+    pts = np.zeros((7, pu.MAX_VERTS, 2), np.int32)
+    nv = np.zeros(7, np.int32)
+    nearer = np.zeros(7, np.int32)
+    for i, p in enumerate(names):
+        # int() as the reference; clipped to +-2^20 px (a keypoint near the camera plane projects arbitrarily far:
+        # the polygon rule's int32 arithmetic needs the bound, the clip leaves the frame's pixels unchanged for any sane pose)
+        v = [tuple(int(min(max(c, -1048576.0), 1048576.0)) for c in k2[k]) for k in VIS_PLANES[p]]
+        pts[i, :len(v)] = v
+        nv[i] = len(v)
+        nearer[i] = sum(1 << q for q in range(7) if dist[q] < dist[i])
+    return pts, nv, nearer
+
+
+def plane_visibility(kp3d: Sequence[np.ndarray], E: Sequence[np.ndarray], K: np.ndarray, frame_hw: Tuple[int, int],
+                     device) -> torch.Tensor:
+    """compute_visibility's areas for J vehicles in one launch: counts int32 [J, 7, 2] = (absolute, occluded) on the
+    device, planes in VIS_PLANES order.  `visible` turns them into the reference's booleans."""
+    dev = torch.device(device)
+    H, W = frame_hw
+    J = len(kp3d)
+    counts = torch.zeros((J, 7, 2), dtype=torch.int32, device=dev)
+    if J == 0:
+        return counts
+    ins = [visibility_inputs(kp3d[j], E[j], K) for j in range(J)]
+    with torch.cuda.device(dev):
+        pts, nv, nearer = (ops.h2d(np.stack([i[k] for i in ins]), dev) for k in range(3))
+        L.check(L.lib().fusg_plane_visibility(pts.data_ptr(), nv.data_ptr(), nearer.data_ptr(), J, H, W, counts.data_ptr(),
+                                              ops.stream_ptr()), "plane_visibility")
+    return counts
+
+
+def visible(counts) -> np.ndarray:
+    """counts [J, 7, 2] (host) -> bool [J, 7]: occluded > 0.9 * absolute in float64 (online_visibility.py:145-148; an empty
+    plane, 0 > 0, is not visible)."""
+    c = np.asarray(counts).astype(np.float64)
+    return c[..., 1] > 0.9 * c[..., 0]
+
+
+# ---------------------------------------------------------------------------------------------- the scene keys
+def plane_corners(kp_xy: np.ndarray, frame_hw: Tuple[int, int]) -> List[np.ndarray]:
+    """get_planes' corner points from frame-pixel keypoints [12, 2]: normalised by (W, H) (vehicle_utils.py:23-25,
+    normalize_kpoints) and handed to planes_utils.plane_polygons (* (W, H), int32)."""
+    H, W = frame_hw
+    k = np.array(kp_xy, np.float64).reshape(len(KP_NAMES), 2)
+    k[:, 0] /= W
+    k[:, 1] /= H
+    return pu.plane_polygons((H, W), {n: k[i] for i, n in enumerate(KP_NAMES)})
+
+
+def project_keypoints(kp3d: np.ndarray, rvec, tvec, K: np.ndarray) -> np.ndarray:
+    """cv2.projectPoints(kp3d, rvec, tvec, K, zero distortion) (trajectory_inference.py:364-367): [n, 3] -> [n, 2]."""
+    from .utils.pnp_utils import rodrigues
+    X = np.asarray(kp3d, np.float64).reshape(-1, 3)
+    Rm = rodrigues(np.asarray(rvec, np.float64).reshape(3))
+    pc = X @ Rm.T + np.asarray(tvec, np.float64).reshape(1, 3)
+    K = np.asarray(K, np.float64)
+    return np.stack([K[0, 0] * (pc[:, 0] / pc[:, 2]) + K[0, 2], K[1, 1] * (pc[:, 1] / pc[:, 2]) + K[1, 2]], 1)
+
+
+def intrinsic(focals, centers) -> np.ndarray:
+    f, c = np.asarray(focals, np.float64).reshape(2), np.asarray(centers, np.float64).reshape(2)
+    return np.array([[f[0], 0.0, c[0]], [0.0, f[1], c[1]], [0.0, 0.0, 1.0]])
+
+
+def vehicle_geometry(bank: CadBank, frame: torch.Tensor, mesh_idx: Sequence[int], poses: Sequence[Tuple[np.ndarray, np.ndarray]],
+                     K: np.ndarray, kp_xy: Optional[np.ndarray] = None, steps: Optional[Sequence[Tuple[float, np.ndarray]]] = None
+                     ) -> Dict:
+    """get_vehicle_information (vehicle_utils.py:12-32) for the V vehicles of a frame, rendered and counted on the device
+    with ONE device-to-host copy (the plane counts and covered-pixel counts).  poses: (rvec, tvec) per vehicle (the
+    first frame's, after select_and_flip); K: 3x3 intrinsics.
+
+    First frame (steps None): the unmoved meshes; plane corners from the detected keypoints kp_xy [V, 12, 2] (frame
+    pixels); returns the scene keys of `VehiclePipeline.run_frame`: 'masks', 'src_sketch' = 'dst_sketch', 'src_planes',
+    'src_kp' = 'dst_kp', 'src_vis' = 'dst_vis' (the reference calls get_vehicle_information twice with the same inputs,
+    trajectory_inference.py:166-169).
+    Later frame (steps = (theta, tr) per vehicle, `trajectory_steps`): meshes and 3-D keypoints moved by v @ z_rot(theta)
+    + tr, rendered at the first frame's extrinsic, the moved keypoints projected with K (:359-376); returns 'masks',
+    'dst_sketch', 'dst_kp', 'dst_vis'.
+    Both also return 'covered' (host int [V]: pixels of each render; 0 = the reference's `except: continue`), 'kp3d'
+    (the moved 3-D keypoints, float64 or float32 [V, 12, 3]) and 'extrinsic' [V, 4, 4]."""
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    dev = frame.device
+    V = len(mesh_idx)
+    E = [extrinsic_from_pose(r, t) for r, t in poses]
+    if steps is None:
+        Rs, trs = None, None
+        kp3d = [bank.kp3d[int(m)] for m in mesh_idx]
+    else:
+        Rs = [z_rot(th) for th, _ in steps]
+        trs = [np.asarray(t, np.float64).reshape(3) for _, t in steps]
+        kp3d = [bank.kp3d[int(m)] @ Rs[v] + trs[v] for v, m in enumerate(mesh_idx)]     # :360-362
+    with torch.cuda.device(dev):
+        r = render_vehicles(bank, mesh_idx, E, float(K[0, 0]), float(K[1, 1]), (H, W), dev, Rs, trs)
+        counts = plane_visibility(kp3d, E, K, (H, W), dev)
+        host = torch.cat([counts.view(V, 14), r["covered"].view(V, 1)], 1).cpu().numpy()
+    vis = visible(host[:, :14].reshape(V, 7, 2))[:, :len(TEXTURE_PLANES)].astype(np.uint8)
+    out = {"masks": r["mask"], "covered": host[:, 14].astype(np.int64), "kp3d": np.stack(kp3d) if V else np.zeros((0, 12, 3)),
+           "extrinsic": np.stack(E) if V else np.zeros((0, 4, 4), np.float32), "counts": host[:, :14].reshape(V, 7, 2)}
+    if steps is None:
+        kp = [plane_corners(kp_xy[v], (H, W)) for v in range(V)]
+        planes = torch.stack([pu.fill_planes(frame, kp[v]) for v in range(V)]) if V else \
+            torch.zeros((0, len(TEXTURE_PLANES), H, W, 3), dtype=torch.uint8, device=dev)
+        out.update(src_sketch=r["sketch"], dst_sketch=r["sketch"], src_planes=planes, src_kp=kp, dst_kp=kp, src_vis=vis, dst_vis=vis)
+    else:
+        kp = [plane_corners(project_keypoints(kp3d[v], *poses[v], K), (H, W)) for v in range(V)]
+        out.update(dst_sketch=r["sketch"], dst_kp=kp, dst_vis=vis)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- trajectories
+def trajectory_steps(meter_coords) -> List[Tuple[float, np.ndarray]]:
+    """trajectory_inference.py:256-297: a vehicle's future positions in metres [N, 2] (row 0 = now) -> (theta, tr) per
+    future step n = 1 .. N-1, for `v @ z_rot(theta) + tr` (:360-363).  theta = heading of the step relative to the mean
+    heading of the first 19 steps; tr = (0, -distance, 0) @ z_rot(theta), or @ z_rot(0) where the turn is sharp (the
+    reference's +-20 degree gates: the step's instant turn for interior steps, theta itself for the first and the last two).
+    `trajectories_to_meters` (dataset IO) is out of scope."""
+    mc = np.asarray(meter_coords, np.float64).reshape(-1, 2)
+    x_start, y_start = mc[0]
+    theta_start = np.arctan2(np.mean(mc[1:20, 1] - y_start), np.mean(mc[1:20, 0] - x_start))
+    last = len(mc[1:])
+    steps = []
+    for n, cur in enumerate(mc[1:], 1):
+        distance = np.linalg.norm(mc[0] - cur)
+        x_cur, y_cur = cur
+        theta = np.arctan2(y_cur - y_start, x_cur - x_start) - theta_start
+        delta_t = np.zeros(3)
+        delta_t[1] = -distance                                       # get_delta_t_vec('y', -distance)
+        if 1 < n < last - 1:
+            cur_theta = np.degrees(np.arctan2(y_cur - mc[n - 1, 1], x_cur - mc[n - 1, 0]))
+            next_theta = np.degrees(np.arctan2(mc[n + 1, 1] - y_cur, mc[n + 1, 0] - x_cur))
+            straight = -20 < cur_theta - next_theta < 20
+        else:
+            straight = -20 < np.degrees(theta) < 20
+        steps.append((float(theta), delta_t @ z_rot(theta if straight else 0)))
+    return steps

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FUSG_VERSION 115
+#define FUSG_VERSION 116
 
 typedef enum fusg_status {
     FUSG_OK = 0,
@@ -433,6 +433,40 @@ int fusg_keypoints_to_frame(const int32_t* idx, const int32_t* geom, float* out,
 int fusg_pnp_cpc(const float* points3d, const float* points2d, const float* focals, const float* centers,
                  const float* rvec0, const float* tvec0, int32_t B, int32_t npoints, int32_t nstarts, int32_t max_iter,
                  float* rvec, float* tvec, float* err, void* stream);
+
+/* ---- per-vehicle geometry (device versions of the reference's Open3D render and compute_visibility; parity with
+ * Open3D / OpenCV unpinned) ------------------------------------------------------------------------------ */
+/* One render job: a bank mesh (vertices [v_off, v_off + nv), triangles [t_off, t_off + nt) of the bank arrays, triangle
+ * indices local to the mesh) moved as p = v @ R + tr (row vector, R = z_rot(theta): trajectory_inference.py:363), put in
+ * the camera as Xc = E[0:3, 0:3] p + E[0:3, 3] and projected with fx, fy, cx, cy (the caller passes Open3D's principal
+ * point, render_open3d.py:20).  240 bytes; fusg_sizeof_render_job() gives the compiled size. */
+typedef struct fusg_render_job {
+    double R[9], tr[3], E[12];
+    double fx, fy, cx, cy;
+    int32_t v_off, nv, t_off, nt;
+} fusg_render_job;
+/* get_rendered (warp_learn/render_open3d.py:29-49) for n_jobs posed meshes at once: a triangle rasteriser writing
+ * sketch uint8 [n_jobs, h, w, 3] = round(255 * (n + 1) / 2) of the perspective-correct interpolated vertex normal of the
+ * nearest triangle (0 where no triangle covers the pixel) and mask uint8 [n_jobs, h, w] = 1 where one does (the
+ * complement of the reference's object_mask).  Pixel centres at integer (x, y), coordinates snapped to 1/256 px, int64
+ * edge functions with the top-left rule, no back-face culling, depth ties to the lower triangle index; a triangle with
+ * a vertex at Zc <= 1e-3 is dropped (no near-plane clipping).  verts / normals = DEVICE float64 [n_verts, 3] (normals:
+ * unit vertex normals of the unmoved mesh, rotated by R per job); tris = DEVICE int32 [n_tris, 3]; jobs = DEVICE
+ * fusg_render_job [n_jobs] with nv <= max_nv; workspace = DEVICE, 16-byte aligned, n_jobs * (16 + 40 * max_nv) bytes.
+ * Optional (NULL = not written): tri_id int32 [n_jobs, h, w] = the winning triangle's index within its mesh (-1: none),
+ * covered int32 [n_jobs] = covered pixels per job.  Deterministic: the bytes do not depend on scheduling. */
+int fusg_render_normals_u8(const double* verts, const double* normals, int64_t n_verts, const int32_t* tris, int64_t n_tris,
+                           const fusg_render_job* jobs, int32_t n_jobs, int32_t max_nv, int32_t h, int32_t w,
+                           void* workspace, int64_t workspace_bytes, uint8_t* sketch, uint8_t* mask, int32_t* tri_id,
+                           int32_t* covered, void* stream);
+/* The areas of compute_visibility (warp_learn/online_visibility.py:105-150) for 7 planes per job (left, right, roof,
+ * front, back, front_bt, back_bt): counts int32 [n_jobs, 7, 2] = (absolute, occluded), absolute = pixels of the h x w
+ * frame inside or on polygon p, occluded = those of them in no polygon q whose bit is set in nearer[p] (the planes
+ * nearer the camera).  Membership is the rule of fusg_fill_poly_planes_u8.  pts_xy = DEVICE int32 [n_jobs, 7, 8, 2],
+ * nverts = DEVICE int32 [n_jobs, 7] (<= 8), nearer = DEVICE int32 [n_jobs, 7]; counts are zeroed by the call. */
+int fusg_plane_visibility(const int32_t* pts_xy, const int32_t* nverts, const int32_t* nearer, int32_t n_jobs, int32_t h,
+                          int32_t w, int32_t* counts, void* stream);
+int fusg_sizeof_render_job(void);
 
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
