@@ -422,8 +422,9 @@ static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
     }
     const bool gen = d->pad_mode != FUSG_PAD_ZERO || d->upsample != 0;
     // halo kernel: stride 1 (any dilation / padding mode / fused upsample), or stride 2 in parity-quadrant form
-    // (wfrag_order 1: k3/k4, pad 1, one source, even H and W); everything else takes the generic gather
-    const bool s2d_form = d->wfrag_order == 1 && d->stride == 2 && x0.h % 2 == 0 && x0.w % 2 == 0;
+    // (wfrag_order 1: k3/k4, pad 1, one source, even H and W, zero or reflect padding - the quadrant staging has no clamp);
+    // everything else takes the generic gather
+    const bool s2d_form = d->wfrag_order == 1 && d->stride == 2 && x0.h % 2 == 0 && x0.w % 2 == 0 && d->pad_mode != FUSG_PAD_REPLICATE;
     const bool f32_halo = d->precision == FUSG_PREC_F32 && d->wfrag_f32 != nullptr && (((uintptr_t)d->wfrag_f32) & 15) == 0 &&
                           getenv("FUSG_NO_F32_HALO") == nullptr;
     const bool halo_ok = (d->precision == FUSG_PREC_F16X3 || f32_halo) && nphase == 1 && d->ksplit <= 1 &&

@@ -20,7 +20,7 @@
 //     wave order: deterministic) by all 256 threads, which also run the epilogue (bias, activation, residuals, DepthToSpace /
 //     SpaceToDepth / strided stores: the same mapping functions as every other kernel).
 //
-// Geometry handled: stride 1 or 2, k x k with k <= 3 (dense tap grid, dilation 1), zero padding, sources with a multiple of
+// Geometry handled: stride 1 or 2, kh x kw with kh, kw <= 3 (dense tap grid, dilation 1), zero padding, sources with a multiple of
 // 32 channels, Ho * Wo a divisor or a multiple of 32 with Wo | 32.  Everything else keeps the other kernels.
 #pragma once
 #include "conv_kernel_h3.h"
@@ -229,7 +229,8 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
             if (tt < nsteps) {
                 int cl, tap;
                 step_of(tt, cl, tap);
-                const int ky = sk.kw == 1 ? tap : (tap * 11) >> 5, kx = tap - ky * sk.kw;       // tap / 3 for tap < 16
+                // tap / kw for every kw the host admits (1..3): (tap * 11) >> 5 is tap / 3 for tap < 16
+                const int ky = sk.kw == 1 ? tap : (sk.kw == 2 ? tap >> 1 : (tap * 11) >> 5), kx = tap - ky * sk.kw;
                 h8 ah[2], al[2];
 #pragma unroll
                 for (int f = 0; f < 2; ++f) {

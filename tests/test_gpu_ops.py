@@ -862,6 +862,8 @@ SMALL = [  # B, c0, c1, cout, k, stride, H, W, pre_op, residual, store
     (4, 256, 0, 128, 1, 1, 4, 4, "affine_relu", False, "normal"),   # hourglass Bottleneck conv1 (bn1 + ReLU on load)
     (4, 128, 0, 256, 1, 1, 4, 4, "relu", True, "normal"),        # hourglass Bottleneck conv3 + residual
     (2, 128, 0, 128, 3, 1, 4, 16, "elu", True, "normal"),        # non-square: Wo = 16, two image rows per workgroup
+    (2, 32, 0, 32, (2, 2), 1, 7, 7, "none", False, "normal"),    # 2 x 2 taps (the tap decode was tap / 3 for every kw)
+    (2, 64, 0, 32, (3, 2), 1, 8, 7, "elu", True, "normal"),      # 3 x 2 taps: four of six decoded to the wrong pixel before
 ]
 
 
@@ -883,11 +885,12 @@ def test_small_image_kernel(B, c0, c1, cout, k, stride, H, W, pre, res, store, p
     residual) against torch (float64) on the CPU; on f16x3 the launch must really be that kernel, and it must agree with the
     launch it replaces (FUSG_NO_SMALL, read per call)."""
     cin = c0 + c1
+    kh, kw = (k, k) if isinstance(k, int) else k
     x0 = _rand(B, c0, H, W, seed=1)
     x1 = _rand(B, c1, H, W, seed=2) if c1 else None
-    w = _rand(cout, cin, k, k, seed=3, scale=1.0 / (cin * k * k) ** 0.5)
+    w = _rand(cout, cin, kh, kw, seed=3, scale=1.0 / (cin * kh * kw) ** 0.5)
     b = _rand(cout, seed=4)
-    pad = k // 2
+    pad = kh // 2
     plan = pack.pack_conv(w, b, c_split=(c0, c1) if c1 else None, stride=stride, pad=pad)
     xc = torch.cat([x0, x1], 1) if c1 else x0
     sc = sh = None
