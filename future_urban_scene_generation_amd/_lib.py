@@ -80,6 +80,7 @@ _TP = C.POINTER(Tensor)
 _SIGS = {
     "fusg_conv2d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "fusg_conv2d_plan": (C.c_int64, [C.POINTER(ConvDesc)]),
+    "fusg_conv2d_route": (C.c_int, [C.POINTER(ConvDesc)]),
     "fusg_hg_bottleneck": (C.c_int, [C.POINTER(BneckDesc), C.c_void_p]),
     "fusg_chan_stats": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_void_p]),
     "fusg_in_finalize": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,5 +1,5 @@
 // Host side of the fused implicit-GEMM convolution: descriptor validation, tile / split-K
-// heuristics, launch, and the deterministic split-K slab reduction.  Kernel: conv_kernel.h.
+// heuristics, routing to a kernel family, launch, and the deterministic split-K slab reduction.  Kernel: conv_kernel.h.
 #include <stdlib.h>
 #include <mutex>
 #include "conv_kernel_tapunit.h"
@@ -144,8 +144,10 @@ const float* zero_line() {
     return z[dev];
 }
 
-// Does this launch take the small-spatial kernel (conv_kernel_small.h), and with which K ranges?  Shared by the planner
-// (workspace size) and the launcher.
+// a device pointer that is present and 16-byte aligned
+static bool aligned16(const void* p) { return p != nullptr && (((uintptr_t)p) & 15) == 0; }
+
+// Does this launch take the small-spatial kernel (conv_kernel_small.h), and with which K ranges?  (plan_impl)
 struct SmallCfg { int nimg, rpi, rpi_shift, tpi, wide, RIN, WIN, NPIX, nchw, ksplit, nch32, ntaps; long mt; };
 static bool small_cfg(const fusg_conv_desc* d, int precision, SmallCfg* out) {
     // (FUSG_NO_SMALL is read per call: tests and the A/B tools flip it at run time)
@@ -153,7 +155,7 @@ static bool small_cfg(const fusg_conv_desc* d, int precision, SmallCfg* out) {
     const int nphase = d->nphase > 0 ? d->nphase : 1;
     if (precision != FUSG_PREC_F16X3 || nphase != 1 || d->kh < 1 || d->kw < 1 || d->kh > 3 || d->kw > 3 || d->dil != 1 ||
         (d->pad_mode != FUSG_PAD_ZERO && d->pad_mode != FUSG_PAD_REPLICATE) || d->upsample != 0 || (d->stride != 1 && d->stride != 2) ||
-        d->tile_list || d->stats_out || !d->wfrag || (((uintptr_t)d->wfrag) & 15) != 0 || (d->wfrag_order != 0 && d->wfrag_order != 1))
+        d->tile_list || d->stats_out || !aligned16(d->wfrag) || (d->wfrag_order != 0 && d->wfrag_order != 1))
         return false;
     const int ntaps = d->kh * d->kw;
     if (d->c0k <= 0 || d->c0k % 32 || d->k_pad % ntaps) return false;
@@ -214,17 +216,19 @@ static bool small_cfg(const fusg_conv_desc* d, int precision, SmallCfg* out) {
     return true;
 }
 
-static int64_t plan_impl(fusg_conv_desc* d) {
+// Tile, K split and workspace bytes.  Reads only shapes, so it also serves fusg_conv2d_plan on a bare descriptor.
+// `small` (may be NULL) receives the small kernel's configuration; small->ksplit == 0: the launch does not take it.
+static int64_t plan_impl(fusg_conv_desc* d, SmallCfg* small) {
     const long M = (long)d->src0.n * d->qh * d->qw;
     const int nphase = d->nphase > 0 ? d->nphase : 1;
-    {
-        SmallCfg sc;
-        if (small_cfg(d, d->precision == FUSG_PREC_BF16 ? FUSG_PREC_F16X3 : d->precision, &sc)) {
-            d->tile = FUSG_TILE_128x32;
-            d->ksplit = sc.ksplit;
-            return sc.ksplit > 1 ? (int64_t)sc.ksplit * M * d->cout_pad * (int64_t)sizeof(float) : 0;
-        }
+    SmallCfg sc;
+    if (small_cfg(d, d->precision == FUSG_PREC_BF16 ? FUSG_PREC_F16X3 : d->precision, &sc)) {
+        d->tile = FUSG_TILE_128x32;
+        d->ksplit = sc.ksplit;
+        if (small) *small = sc;
+        return sc.ksplit > 1 ? (int64_t)sc.ksplit * M * d->cout_pad * (int64_t)sizeof(float) : 0;
     }
+    if (small) small->ksplit = 0;
     if (d->tile == FUSG_TILE_AUTO) {
         int bn = d->cout_pad >= 128 && d->cout_pad % 128 == 0 ? 128 : (d->cout_pad % 64 == 0 ? 64 : 32);
         int bm = 128;
@@ -257,19 +261,57 @@ static int64_t plan_impl(fusg_conv_desc* d) {
     return (int64_t)nphase * d->ksplit * M * d->cout_pad * (int64_t)sizeof(float);
 }
 
-}  // namespace fusg
+// Column-tile width of the halo and tap-unit kernels: the widest of 128 / 64 / 32 that divides cout_pad and is at most
+// `cap`, halved while a grid of `mt` row tiles would have fewer than `min_wg` workgroups; FUSG_HALO_BN overrides.
+static int column_tile(int cout_pad, int cap, long mt = 0, long min_wg = 0) {
+    int bn = cout_pad % 128 == 0 ? 128 : (cout_pad % 64 == 0 ? 64 : 32);
+    if (bn > cap) bn = cap;
+    while (bn > 32 && mt * (cout_pad / bn) < min_wg) bn /= 2;
+    if (const int v = env_switches().halo_bn; (v == 32 || v == 64 || v == 128) && cout_pad % v == 0) bn = v;
+    return bn;
+}
 
-using namespace fusg;
+// LDS offsets of the tap-unit kernels' K units (`unit` channels of one tap, taps row-major; halo rows RP apart, pixels
+// c0k apart).  Returns the number of units.
+static int tapunit_offsets(int* uoff, const fusg_conv_desc& d, int unit, int RP) {
+    const int upp = d.c0k / unit, nunits = d.kh * d.kw * upp;
+    for (int j = 0; j < nunits; ++j) {
+        const int tap = j / upp, u = j - tap * upp, ky = tap / d.kw, kx = tap - ky * d.kw;
+        uoff[j] = ky * RP + kx * d.c0k + u * unit;
+    }
+    return nunits;
+}
 
-extern "C" int64_t fusg_conv2d_plan(fusg_conv_desc* d) { return plan_impl(d); }
+// The taps of a stride-2 layer in parity-quadrant slab order (include/fusg.h wfrag_order 1, pack.s2d_tap_order): input row
+// 2Y - 1 + ky has parity (ky - 1) & 1, so quadrant q = 2 ((ky - 1) & 1) + ((kx - 1) & 1); fn(q, ky, kx) quadrant by quadrant.
+template <class Fn> static void for_each_quadrant_tap(int kh, int kw, Fn fn) {
+    for (int q = 0; q < 4; ++q)
+        for (int ky = 0; ky < kh; ++ky)
+            if (((ky - 1) & 1) == (q >> 1))
+                for (int kx = 0; kx < kw; ++kx)
+                    if (((kx - 1) & 1) == (q & 1)) fn(q, ky, kx);
+}
 
-static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
-    fusg_conv_desc dd = *din;
-    fusg_conv_desc* d = &dd;
-    // FUSG_PREC_BF16: single-pass bf16 on the halo kernel where the layer qualifies, F16X3 everywhere else
+// What route_conv decided: the kernel family and what its launch needs beyond the descriptor.
+struct ConvRoute {
+    int family;                 // FUSG_CONV_*
+    int vec_epi;                // 16-byte epilogue accesses (ConvK::vec_epi)
+    SmallCfg sc;                // FUSG_CONV_SMALL: its configuration (plan_impl)
+    int mode;                   // halo / tap-unit arithmetic: 0 split-fp16, 1 bf16, 2 exact fp32
+    int bn;                     // halo / tap-unit: column-tile width
+    bool ksw;                   // halo: K split over the waves (the 64k / 32k instantiations)
+    bool s2d;                   // halo: parity-quadrant form
+    int HH, HW;                 // halo / tap-unit: halo extent in (virtual) input pixels
+    int RP, unit;               // tap-unit: LDS pitch of a halo row, channels per K unit
+};
+
+// Validation and the family choice of fusg_conv2d - no HIP call, no allocation.  `d` is the caller's descriptor, copied: it
+// leaves planned (tile, ksplit) and with the arithmetic that runs (FUSG_PREC_BF16 -> F16X3).  Returns FUSG_OK or the error
+// fusg_conv2d reports (the workspace and split-K counters, the caller's allocations, are checked by the launch).
+static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
+    // FUSG_PREC_BF16: single-pass bf16 on the halo / tap-unit kernels where the layer qualifies, F16X3 everywhere else
     const bool want_bf16 = d->precision == FUSG_PREC_BF16;
     if (want_bf16) d->precision = FUSG_PREC_F16X3;
-    hipStream_t s = (hipStream_t)stream;
     const fusg_tensor& x0 = d->src0;
     FUSG_CHECK(is_nhwc(x0), "conv2d: src0 must be NHWC-physical f32 (sc=1, Cs%%4=0, 16B aligned)");
     const bool has1 = d->src1.data != nullptr;
@@ -277,9 +319,9 @@ static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
         FUSG_CHECK(is_nhwc(d->src1) && same_nhw(x0, d->src1), "conv2d: src1 must be NHWC-physical with src0's n,h,w");
     }
     FUSG_CHECK(d->bias && d->ktab, "conv2d: bias/ktab missing");
-    FUSG_CHECK(d->precision >= FUSG_PREC_F32 && d->precision <= FUSG_PREC_EMU_BF16X2, "conv2d: precision %d", din->precision);
+    FUSG_CHECK(d->precision >= FUSG_PREC_F32 && d->precision <= FUSG_PREC_EMU_BF16X2, "conv2d: precision %d", d->precision);
     if (d->precision != FUSG_PREC_F16X3) FUSG_CHECK(d->wpack, "conv2d: wpack missing");
-    else FUSG_CHECK(d->wpack_h && (((uintptr_t)d->wpack_h) & 15) == 0 && d->wscale && (((uintptr_t)d->wscale) & 15) == 0 && d->status,
+    else FUSG_CHECK(aligned16(d->wpack_h) && aligned16(d->wscale) && d->status,
                     "conv2d: F16X3 needs 16B-aligned wpack_h and wscale, and a status word");
     FUSG_CHECK((((uintptr_t)d->wpack) & 15) == 0 && (((uintptr_t)d->ktab) & 7) == 0, "conv2d: wpack/ktab misaligned");
     FUSG_CHECK(d->k_pad > 0 && d->k_pad % BK == 0, "conv2d: k_pad %d not a positive multiple of %d", d->k_pad, BK);
@@ -346,10 +388,252 @@ static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
                    rs[i]->c >= oc && rs[i]->h >= oh && rs[i]->w >= ow, "conv2d: residual %d shape mismatch", i);
     }
 
-    plan_impl(d);
+    // Plan after the bf16 rewrite above: a caller that did not plan (tile AUTO) gets the tile of the F16X3 kernels its layer
+    // falls back to, while ops.conv, which plans first, has planned with its own precision code (bf16: the 128-row tiles).
+    // Both are kept as they are - the tile and the K split fix the summation order of the generic kernels, hence their bits.
+    plan_impl(d, &r->sc);
     FUSG_CHECK(d->tile >= 1 && d->tile <= 5, "conv2d: tile %d", d->tile);
+    FUSG_CHECK(d->cout_pad % kTiles[d->tile].bn == 0, "conv2d: cout_pad %d not a multiple of tile N %d", d->cout_pad, kTiles[d->tile].bn);
+    {   // 16-byte epilogue accesses need channel-contiguous, 16-byte aligned destinations and residuals
+        auto vec_ok = [](const fusg_tensor& t) {
+            return t.sc == 1 && (((uintptr_t)t.data) & 15) == 0 && t.sw % 4 == 0 && t.sh % 4 == 0 && t.sn % 4 == 0;
+        };
+        bool v = d->cout % 4 == 0 && d->dst_c_off % 4 == 0 && vec_ok(o) && !env_switches().no_vec_epi;
+        if (d->store_mode == FUSG_STORE_D2S) v = v && (d->cout / 4) % 4 == 0;
+        if (d->res0.data) v = v && vec_ok(d->res0);
+        if (d->res1.data) v = v && vec_ok(d->res1);
+        r->vec_epi = v ? 1 : 0;
+    }
+    if (d->stats_out) {
+        if (!(r->vec_epi && d->act == FUSG_ACT_NONE && !d->res0.data && !d->res1.data && d->store_mode == FUSG_STORE_NORMAL &&
+              nphase == 1 && d->ksplit <= 1 && ((long)d->qh * d->qw) % 32 == 0)) {
+            set_error("conv2d: fused statistics need act NONE, no residual, NORMAL store, nphase 1, ksplit 1, qh*qw%%32==0 "
+                      "and a channel-contiguous aligned dst with cout%%4==0");
+            return FUSG_ERR_UNSUPPORTED;
+        }
+        const int slots = (int)(((long)d->qh * d->qw) / 32);
+        if (d->stats_slots > 0 && d->stats_slots < slots) { set_error("conv2d: stats_slots %d < %d slots of this launch", d->stats_slots, slots); return FUSG_ERR_INVALID; }
+    }
+
+    // ---- the family, in this order; a family whose LDS does not fit goes on to the next
+    const int ntaps = d->kh * d->kw;
+    // small images (<= 16 x 16): the latency-built kernel of conv_kernel_small.h
+    if (r->sc.ksplit > 0) { r->family = FUSG_CONV_SMALL; return FUSG_OK; }
+    // pointwise from <= 8 channels: the streaming VALU kernel above - an exact fp32 fmaf chain in the generic fp32 kernel's k
+    // order, so it serves both the split-fp16 and (round 4) the exact-fp32 precision with that kernel's bits
+    // (FUSG_NO_POINTWISE, read per call, keeps the MFMA kernels: tests compare the two)
+    if ((d->precision == FUSG_PREC_F16X3 || d->precision == FUSG_PREC_F32) && getenv("FUSG_NO_POINTWISE") == nullptr && nphase == 1 && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->upsample == 0 && !has1 &&
+        d->c0k >= 4 && d->c0k <= 8 && d->ksplit <= 1 && d->store_mode == FUSG_STORE_NORMAL && r->vec_epi && !d->stats_out &&
+        d->cout % 4 == 0 && d->pre_op <= FUSG_PRE_ELU && (d->q_oy | d->q_ox) == 0 && !d->tile_list && d->wpack && d->pad_h == 0 &&
+        d->pad_w == 0 && 256 % (d->cout_pad >> 2) == 0 && !env_switches().no_halo && !env_switches().no_pointwise) {
+        r->family = FUSG_CONV_POINTWISE;
+        return FUSG_OK;
+    }
+    // exact fp32 on the halo-family kernels (FUSG_NO_F32_HALO, read per call, keeps the generic fp32 gather)
+    const bool f32_frag = d->precision == FUSG_PREC_F32 && aligned16(d->wfrag_f32) && getenv("FUSG_NO_F32_HALO") == nullptr;
+    // few-channel k x k layers (the 7x7 stems): the tap-unit kernels, exact fp32 (round 4, conv_kernel_tapunit_f32.h) or
+    // split-fp16 / bf16 (conv_kernel_tapunit.h)
+    const bool tap_geom = d->wfrag_order == 2 && nphase == 1 && d->upsample == 0 && d->ksplit <= 1 && !has1 && d->c0k >= 4 &&
+                          d->c0k <= 24 && d->kh >= 1 && d->kw >= 1 && d->dil == 1 && d->qh % 8 == 0 && d->qw % 16 == 0 &&
+                          d->k_pad >= ntaps * d->c0k && (d->q_oy | d->q_ox) == 0 && !d->tile_list && !env_switches().no_halo;
+    if (tap_geom && (f32_frag || (d->precision == FUSG_PREC_F16X3 && aligned16(d->wfrag)))) {
+        const bool f32 = f32_frag;
+        r->HH = 7 * d->stride + d->kh; r->HW = 15 * d->stride + d->kw;
+        r->unit = f32 || d->c0k % 8 ? 4 : 8;
+        r->RP = f32 ? r->HW * d->c0k : (r->HW * d->c0k + 127) / 128 * 128;     // split-fp16 rows 256 B apart: conflict-free 16-lane read groups
+        const int nunits = ntaps * (d->c0k / r->unit), nsteps = (nunits + 16 / r->unit - 1) / (16 / r->unit);
+        const size_t lds = f32 ? (size_t)r->HH * r->RP * sizeof(float) : tapunit_lds_bytes(r->HH, r->RP);
+        if (nunits <= (f32 ? 320 : 160) && lds <= 80 * 1024 && r->HH * r->HW * (d->c0k / 4) <= 256 * 8) {
+            // FUSG_PREC_BF16: the stem in single-pass bf16 too (wfrag_bf16 in the tap-unit form, pack.py: frag_tapunit_bf16)
+            r->mode = f32 ? 2 : (want_bf16 && aligned16(d->wfrag_bf16) && getenv("FUSG_NO_BF16_TAPUNIT") == nullptr ? 1 : 0);
+            // thin split-fp16 / bf16 layers (a handful of k-steps: the launch is a stream of output stores) run 24-45 % faster on
+            // the 64-column tile: its 16 KiB epilogue detour leaves room for more resident workgroups than the 128-column one
+            r->bn = column_tile(d->cout_pad, !f32 && nsteps <= 4 ? 64 : 128);
+            r->family = f32 ? FUSG_CONV_TAPUNIT_F32 : r->mode ? FUSG_CONV_TAPUNIT_BF16 : FUSG_CONV_TAPUNIT;
+            return FUSG_OK;
+        }
+    }
+    // halo kernel: stride 1 (any dilation / padding mode / fused upsample), or stride 2 in parity-quadrant form
+    // (wfrag_order 1: k3/k4, pad 1, one source, even H and W, zero or reflect padding - the quadrant staging has no clamp);
+    // everything else takes the generic gather
+    const bool s2d = d->wfrag_order == 1 && d->stride == 2 && x0.h % 2 == 0 && x0.w % 2 == 0 && d->pad_mode != FUSG_PAD_REPLICATE;
+    if ((d->precision == FUSG_PREC_F16X3 || f32_frag) && nphase == 1 && d->ksplit <= 1 &&
+        ((d->stride == 1 && d->wfrag_order == 0) || (s2d && d->upsample == 0)) &&
+        d->kh >= 1 && d->kw >= 1 && d->dil >= 1 && d->c0k % 32 == 0 && d->c0k > 0 &&
+        (!has1 || (d->k_pad / ntaps - d->c0k) % 32 == 0) && d->qh % 8 == 0 && d->qw % 16 == 0 &&
+        d->k_pad % ntaps == 0 && aligned16(d->wfrag) && !env_switches().no_halo && (d->q_oy | d->q_ox) == 0) {
+        if (s2d && !(d->kh == d->kw && (d->kh == 3 || d->kh == 4) && d->pad_h == 1 && d->pad_w == 1 && d->dil == 1 && !has1)) {
+            set_error("conv2d: wfrag_order 1 needs stride 2, k3/k4, pad 1, dil 1, one source");
+            return FUSG_ERR_INVALID;
+        }
+        const int tiles_per_img = (d->qh / 8) * (d->qw / 16);
+        if (d->tile_list && d->tile_count > tiles_per_img) {
+            set_error("conv2d: tile_count %d > %d patches per image", d->tile_count, tiles_per_img);
+            return FUSG_ERR_INVALID;
+        }
+        r->s2d = s2d;
+        r->HH = s2d ? 10 : 8 + (d->kh - 1) * d->dil;
+        r->HW = s2d ? 18 : 16 + (d->kw - 1) * d->dil;
+        // (Round 3 tried 16 x 16 pixel patches for the 32 / 64-column tiles - half the workgroups, twice the work each,
+        // halo 1.27x instead of 1.41x of the patch: every such launch got 13 - 51 % SLOWER (32 -> 32 1x1 at 256 x 256
+        // 130 -> 186 us, 64 -> 32 3x3 311 -> 351 us), conv time of the pass 23.9 -> 24.5 ms; round 4's bf16 128-column tile on a
+        // 16 x 16 patch: 1.4x - 3x slower, profiles/r04_ab_experiments.txt.  Dropped.)
+        if (halo_fits(r->HH, r->HW)) {
+            const long mt = (long)x0.n * (d->tile_list ? d->tile_count : tiles_per_img);
+            // pointwise layers are bound by their output stores, not by operand staging: the 64-column tile (a quarter of
+            // the epilogue LDS, more resident workgroups) is 6-24 % faster there (hourglass 1x1s); k x k layers keep 128.
+            // Small grids: narrower column tiles until the launch has enough workgroups to fill the chip.
+            r->bn = column_tile(d->cout_pad, ntaps == 1 ? 64 : 128, mt, env_switches().halo_minwg);
+            // narrow column tiles of k x k layers on SMALL grids: K split over the waves (conv_kernel_halo.h, KS) when every wave
+            // gets a tap.  Measured per dispatch inside the pass (round 3, same card): grids of 256 - 1024 workgroups 2 - 14 %
+            // shorter (their time is one workgroup's latency); grids of 4096 - 16384 workgroups 19 - 42 % LONGER (the four
+            // partial tiles need 64 KiB of LDS: two workgroups per CU instead of three, and those launches move 3 - 4.4 TB/s -
+            // they live on bytes in flight).  Hence the limit.
+            r->ksw = !s2d && !d->tile_list && !env_switches().no_ksplit && mt * (d->cout_pad / r->bn) <= 1024 &&
+                     ((r->bn == 32 && ntaps >= 4) || (r->bn == 64 && ntaps >= 2));
+            const bool bf = want_bf16 && aligned16(d->wfrag_bf16);
+            r->mode = f32_frag ? 2 : (bf ? 1 : 0);
+            r->family = f32_frag ? FUSG_CONV_HALO_F32 : bf ? FUSG_CONV_HALO_BF16 : (s2d ? FUSG_CONV_HALO_S2D : FUSG_CONV_HALO);
+            return FUSG_OK;
+        }
+    }
+    if (d->tile_list) {
+        set_error("conv2d: tile_list needs a launch that qualifies for the halo kernel");
+        return FUSG_ERR_UNSUPPORTED;
+    }
+    r->family = d->precision == FUSG_PREC_F16X3 ? FUSG_CONV_GENERIC_F16X3 : FUSG_CONV_GENERIC_F32;
+    return FUSG_OK;
+}
+
+// ---- one launch per family: the family's parameter block around the common ConvK
+static hipError_t run_small(ConvK& k, const fusg_conv_desc& d, const SmallCfg& sc, hipStream_t s, int pk) {
+    k.MT = (int)sc.mt; k.NT = d.cout_pad / 32;                  // (k is also what the split-K reduce behind it reads)
+    k.ksplit = sc.ksplit;
+    SmallK h;
+    memset(&h, 0, sizeof(h));
+    h.c = k;
+    h.kh = d.kh; h.kw = d.kw; h.pad_h = d.pad_h; h.pad_w = d.pad_w; h.stride = d.stride;
+    h.nch0 = d.c0k / 32; h.nch32 = sc.nch32; h.ntaps = sc.ntaps;
+    h.wfrag = (const _Float16*)d.wfrag; h.nt32 = d.cout_pad / 32;
+    if (d.wfrag_order == 1) {                   // parity-quadrant slab order of the stride-2 3x3 layers
+        int slab = 0;
+        for_each_quadrant_tap(d.kh, d.kw, [&](int, int ky, int kx) { h.tapslab |= (unsigned long long)(slab++) << (4 * (ky * d.kw + kx)); });
+    } else {
+        for (int tp = 0; tp < sc.ntaps; ++tp) h.tapslab |= (unsigned long long)tp << (4 * tp);
+    }
+    h.nchw = sc.nchw; h.nimg = sc.nimg; h.rpi = sc.rpi; h.rpi_shift = sc.rpi_shift; h.tpi = sc.tpi; h.wide = sc.wide;
+    h.pad_mode = d.pad_mode;
+    h.RIN = sc.RIN; h.WIN = sc.WIN; h.NPIX = sc.NPIX;
+    // (the reciprocals are exact while dividend * divisor < 2^32: the dividends are tile indices (< 2^31 / tpi, checked in
+    // small_cfg), pixel indices inside a 32-row tile and step numbers)
+    auto magic = [](int dv) -> unsigned { return dv < 2 ? 0u : (unsigned)(((1UL << 32) + (unsigned long)dv - 1) / (unsigned long)dv); };
+    h.m_wo = magic(d.qw); h.m_hw = magic(d.qh * d.qw); h.m_win = magic(sc.WIN); h.m_rw = magic(sc.RIN * sc.WIN);
+    h.m_npix = magic(sc.NPIX); h.m_taps = magic(sc.ntaps); h.m_tpi = magic(sc.tpi);
+    return launch_small(h, dim3(k.MT * k.NT, 1, sc.ksplit), s, pk);
+}
+
+static hipError_t run_pointwise(const ConvK& k, const fusg_conv_desc& d, hipStream_t s) {
+    const int n4 = d.cout_pad >> 2, ppb = PW_ITEMS * 256 / n4;
+    hipLaunchKernelGGL(conv_pointwise_small, dim3((unsigned)(((long)k.M + ppb - 1) / ppb)), dim3(256),
+                       (size_t)(d.cout_pad * 8 + ppb * 8) * sizeof(float), s, k, k.M);
+    return hipGetLastError();
+}
+
+// the two tap-unit parameter blocks (TapUnitF: exact fp32, TapUnitK: split-fp16 / bf16) up to their weights
+template <class H> static dim3 tapunit_block(H& h, const ConvK& k, const fusg_conv_desc& d, const ConvRoute& r) {
+    memset(&h, 0, sizeof(h));
+    h.c = k;
+    h.stride = d.stride; h.pad_h = d.pad_h; h.pad_w = d.pad_w;
+    h.HH = r.HH; h.HW = r.HW; h.CP = d.c0k; h.PP = d.c0k; h.RP = r.RP;
+    h.nunits = tapunit_offsets(h.uoff, d, r.unit, h.RP);
+    h.nt32 = d.cout_pad / 32;
+    h.tiles_x = d.qw / 16; h.tiles_per_img = (d.qh / 8) * h.tiles_x;
+    h.c.MT = (int)d.src0.n * h.tiles_per_img; h.c.NT = d.cout_pad / r.bn;
+    h.c.ksplit = 1;
+    if (r.mode != 0) { h.c.wscale = nullptr; h.c.status = nullptr; }
+    return dim3(h.c.MT * h.c.NT, 1, 1);
+}
+
+static hipError_t run_tapunit(const ConvK& k, const fusg_conv_desc& d, const ConvRoute& r, hipStream_t s, int pk) {
+    if (r.mode == 2) {
+        TapUnitF h;
+        const dim3 grid = tapunit_block(h, k, d, r);
+        h.wfrag = (const float*)d.wfrag_f32;
+        return r.bn == 128 ? launch_tapunit_f32_128(h, grid, s, pk) : r.bn == 64 ? launch_tapunit_f32_64(h, grid, s, pk)
+                                                                                 : launch_tapunit_f32_32(h, grid, s, pk);
+    }
+    TapUnitK h;
+    const dim3 grid = tapunit_block(h, k, d, r);
+    h.nsteps = (h.nunits + 16 / r.unit - 1) / (16 / r.unit);
+    h.wfrag = (const _Float16*)(r.mode == 1 ? d.wfrag_bf16 : d.wfrag);
+    return r.bn == 128 ? launch_tapunit_128(h, grid, s, pk, r.unit, r.mode) : r.bn == 64 ? launch_tapunit_64(h, grid, s, pk, r.unit, r.mode)
+                                                                                         : launch_tapunit_32(h, grid, s, pk, r.unit, r.mode);
+}
+
+static hipError_t run_halo(const ConvK& k, const fusg_conv_desc& d, const ConvRoute& r, hipStream_t s, int pk) {
+    HaloK h;
+    memset(&h, 0, sizeof(h));
+    h.c = k;
+    h.kh = d.kh; h.kw = d.kw; h.dil = d.dil; h.pad_h = d.pad_h; h.pad_w = d.pad_w;
+    h.c1k = d.k_pad / (d.kh * d.kw) - d.c0k;
+    h.wfrag = (const _Float16*)(r.mode == 1 ? d.wfrag_bf16 : r.mode == 2 ? d.wfrag_f32 : d.wfrag);
+    if (r.mode != 0) { h.c.wscale = nullptr; h.c.status = nullptr; }
+    h.nt32 = d.cout_pad / 32;
+    h.c.NT = d.cout_pad / r.bn;
+    h.c.ksplit = 1;
+    h.HH = r.HH; h.HW = r.HW;
+    if (r.s2d) {                                // (quadrant slabs are consecutive: qwoff is the running sum of qtaps)
+        h.s2d = 1;
+        for_each_quadrant_tap(d.kh, d.kw, [&](int q, int ky, int kx) {
+            const int n = h.qtaps[q]++;
+            h.qtdy[q][n] = ((ky - 1) >> 1) + 1;                   // arithmetic shift: floor
+            h.qtdx[q][n] = ((kx - 1) >> 1) + 1;
+        });
+        for (int q = 1; q < 4; ++q) h.qwoff[q] = h.qwoff[q - 1] + h.qtaps[q - 1];
+    }
+    h.tiles_x = d.qw / 16; h.tiles_per_img = (d.qh / 8) * h.tiles_x;
+    h.c.MT = (int)d.src0.n * h.tiles_per_img;
+    if (d.tile_list) {
+        h.tile_list = d.tile_list; h.tile_count = d.tile_count;
+        h.c.MT = (int)d.src0.n * d.tile_count;
+    }
+    const dim3 grid(h.c.MT * h.c.NT, 1, 1);
+    return r.bn == 128 ? launch_halo_128(h, grid, s, pk, r.mode)
+                       : r.bn == 64 ? (r.ksw ? launch_halo_64k(h, grid, s, pk, r.mode) : launch_halo_64(h, grid, s, pk, r.mode))
+                                    : (r.ksw ? launch_halo_32k(h, grid, s, pk, r.mode) : launch_halo_32(h, grid, s, pk, r.mode));
+}
+
+// the generic gathers by [split-fp16][tile]
+typedef hipError_t (*GenericLaunch)(const ConvK&, dim3, hipStream_t, int, bool);
+static const GenericLaunch kGeneric[2][6] = {
+    {nullptr, launch_tile_128x128, launch_tile_128x64, launch_tile_128x32, launch_tile_64x64, launch_tile_64x128},
+    {nullptr, launch_h3_128x128, launch_h3_128x64, launch_h3_128x32, launch_h3_64x64, launch_h3_64x128}};
+
+}  // namespace fusg
+
+using namespace fusg;
+
+extern "C" int64_t fusg_conv2d_plan(fusg_conv_desc* d) { return plan_impl(d, nullptr); }
+
+extern "C" int fusg_conv2d_route(const fusg_conv_desc* din) {
+    fusg_conv_desc d = *din;
+    ConvRoute r;
+    const int rc = route_conv(&d, &r);
+    return rc != FUSG_OK ? rc : r.family;
+}
+
+static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
+    fusg_conv_desc dd = *din;
+    fusg_conv_desc* d = &dd;
+    ConvRoute r;
+    if (const int rc = route_conv(d, &r); rc != FUSG_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const fusg_tensor& x0 = d->src0;
+    const fusg_tensor& o = d->dst;
+    const bool has1 = d->src1.data != nullptr;
+    const int nphase = d->nphase > 0 ? d->nphase : 1;
+    const long Ml = (long)x0.n * d->qh * d->qw;
     const TileCfg tc = kTiles[d->tile];
-    FUSG_CHECK(d->cout_pad % tc.bn == 0, "conv2d: cout_pad %d not a multiple of tile N %d", d->cout_pad, tc.bn);
     if (d->ksplit > 1) FUSG_CHECK(d->workspace && (((uintptr_t)d->workspace) & 15) == 0, "conv2d: split-K needs a 16B-aligned workspace");
     if (d->ksplit > 1 && d->splitk_counters)
         FUSG_CHECK((long)((Ml + tc.bm - 1) / tc.bm) * (d->cout_pad / tc.bn) * nphase <= d->splitk_counters_len,
@@ -382,35 +666,9 @@ static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
     for (int i = 0; i < 4; ++i) { k.ooy[i] = d->out_oy[i]; k.oox[i] = d->out_ox[i]; }
     k.dst_c_off = d->dst_c_off; k.Cd = d->store_mode == FUSG_STORE_D2S ? d->cout / 4 : d->cout;
     k.ksplit = d->ksplit; k.steps_per_split = (k.nk + d->ksplit - 1) / d->ksplit;
-    {   // 16-byte epilogue accesses need channel-contiguous, 16-byte aligned destinations and residuals
-        auto vec_ok = [](const fusg_tensor& t) {
-            return t.sc == 1 && (((uintptr_t)t.data) & 15) == 0 && t.sw % 4 == 0 && t.sh % 4 == 0 && t.sn % 4 == 0;
-        };
-        bool v = d->cout % 4 == 0 && d->dst_c_off % 4 == 0 && vec_ok(o) && !env_switches().no_vec_epi;
-        if (d->store_mode == FUSG_STORE_D2S) v = v && (d->cout / 4) % 4 == 0;
-        if (d->res0.data) v = v && vec_ok(d->res0);
-        if (d->res1.data) v = v && vec_ok(d->res1);
-        k.vec_epi = v ? 1 : 0;
-    }
-    if (d->stats_out) {
-        if (!(k.vec_epi && d->act == FUSG_ACT_NONE && !d->res0.data && !d->res1.data && d->store_mode == FUSG_STORE_NORMAL &&
-              nphase == 1 && d->ksplit <= 1 && ((long)d->qh * d->qw) % 32 == 0)) {
-            set_error("conv2d: fused statistics need act NONE, no residual, NORMAL store, nphase 1, ksplit 1, qh*qw%%32==0 "
-                      "and a channel-contiguous aligned dst with cout%%4==0");
-            return FUSG_ERR_UNSUPPORTED;
-        }
-        k.stats = d->stats_out;
-        k.stats_slots = (int)(((long)d->qh * d->qw) / 32);
-        if (d->stats_slots > 0) {
-            if (d->stats_slots < k.stats_slots) { set_error("conv2d: stats_slots %d < %d slots of this launch", d->stats_slots, k.stats_slots); return FUSG_ERR_INVALID; }
-            k.stats_slots = d->stats_slots;
-        }
-    }
-
-    dim3 grid(k.MT * k.NT, nphase, d->ksplit);
-    const double flops = 2.0 * (double)Ml * d->cout * d->k_pad * nphase;   // padded-K flops; bench uses algorithmic ones
-    prof_begin(0, s, flops);
-    hipError_t e;
+    k.vec_epi = r.vec_epi;
+    k.stats = d->stats_out;
+    if (d->stats_out) k.stats_slots = d->stats_slots > 0 ? d->stats_slots : (int)(((long)d->qh * d->qw) / 32);
     int pk = PK_NONE;
     k.pre_relu = 0;
     switch (d->pre_op) {
@@ -420,303 +678,34 @@ static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
         case FUSG_PRE_AFFINE: pk = PK_AFFINE; break;
         default: break;
     }
-    const bool gen = d->pad_mode != FUSG_PAD_ZERO || d->upsample != 0;
-    // halo kernel: stride 1 (any dilation / padding mode / fused upsample), or stride 2 in parity-quadrant form
-    // (wfrag_order 1: k3/k4, pad 1, one source, even H and W, zero or reflect padding - the quadrant staging has no clamp);
-    // everything else takes the generic gather
-    const bool s2d_form = d->wfrag_order == 1 && d->stride == 2 && x0.h % 2 == 0 && x0.w % 2 == 0 && d->pad_mode != FUSG_PAD_REPLICATE;
-    const bool f32_halo = d->precision == FUSG_PREC_F32 && d->wfrag_f32 != nullptr && (((uintptr_t)d->wfrag_f32) & 15) == 0 &&
-                          getenv("FUSG_NO_F32_HALO") == nullptr;
-    const bool halo_ok = (d->precision == FUSG_PREC_F16X3 || f32_halo) && nphase == 1 && d->ksplit <= 1 &&
-                         ((d->stride == 1 && d->wfrag_order == 0) || (s2d_form && d->upsample == 0)) &&
-                         d->kh >= 1 && d->kw >= 1 && d->dil >= 1 && d->c0k % 32 == 0 && d->c0k > 0 &&
-                         (!has1 || (d->k_pad / (d->kh * d->kw) - d->c0k) % 32 == 0) && d->qh % 8 == 0 && d->qw % 16 == 0 &&
-                         d->k_pad % (d->kh * d->kw) == 0 && d->wfrag != nullptr && (((uintptr_t)d->wfrag) & 15) == 0 &&
-                         !env_switches().no_halo && (d->q_oy | d->q_ox) == 0;
-    // small images (<= 16 x 16): the latency-built kernel of conv_kernel_small.h
-    {
-        SmallCfg sc;
-        fusg_conv_desc probe = *din;                    // (plan_impl above has already overwritten d->ksplit / d->tile)
-        if (small_cfg(&probe, d->precision, &sc) && sc.ksplit == d->ksplit) {
-            SmallK h;
-            memset(&h, 0, sizeof(h));
-            h.c = k;
-            h.kh = d->kh; h.kw = d->kw; h.pad_h = d->pad_h; h.pad_w = d->pad_w; h.stride = d->stride;
-            h.nch0 = d->c0k / 32; h.nch32 = sc.nch32; h.ntaps = sc.ntaps;
-            h.wfrag = (const _Float16*)d->wfrag; h.nt32 = d->cout_pad / 32;
-            if (d->wfrag_order == 1) {                  // parity-quadrant slab order of the stride-2 3x3 layers (pack.s2d_tap_order)
-                int slab = 0;
-                for (int q = 0; q < 4; ++q)
-                    for (int ky = 0; ky < 3; ++ky) {
-                        if (((ky - 1) & 1) != (q >> 1)) continue;
-                        for (int kx = 0; kx < 3; ++kx)
-                            if (((kx - 1) & 1) == (q & 1)) h.tapslab |= (unsigned long long)(slab++) << (4 * (ky * 3 + kx));
-                    }
-            } else {
-                for (int tp = 0; tp < sc.ntaps; ++tp) h.tapslab |= (unsigned long long)tp << (4 * tp);
-            }
-            h.nchw = sc.nchw; h.nimg = sc.nimg; h.rpi = sc.rpi; h.rpi_shift = sc.rpi_shift; h.tpi = sc.tpi; h.wide = sc.wide;
-            h.pad_mode = d->pad_mode;
-            h.RIN = sc.RIN; h.WIN = sc.WIN; h.NPIX = sc.NPIX;
-            auto magic = [](int dv) -> unsigned { return dv < 2 ? 0u : (unsigned)(((1UL << 32) + (unsigned long)dv - 1) / (unsigned long)dv); };
-            h.m_wo = magic(d->qw); h.m_hw = magic(d->qh * d->qw); h.m_win = magic(sc.WIN); h.m_rw = magic(sc.RIN * sc.WIN);
-            h.m_npix = magic(sc.NPIX); h.m_taps = magic(sc.ntaps); h.m_tpi = magic(sc.tpi);
-            // (the reciprocals are exact while dividend * divisor < 2^32: the dividends are tile indices (< 2^31 / tpi, checked in
-            // small_cfg), pixel indices inside a 32-row tile and step numbers - the planner and this launcher must agree, or a
-            // layer planned for this kernel would run on the generic gather with this kernel's tile / split choice)
-            {
-                h.c.MT = (int)sc.mt; h.c.NT = d->cout_pad / 32;
-                h.c.ksplit = sc.ksplit;
-                dim3 sgrid(h.c.MT * h.c.NT, 1, sc.ksplit);
-                e = launch_small(h, sgrid, s, pk);
-                if (e != hipSuccess) { set_error("conv2d small-image launch: %s", hipGetErrorString(e)); prof_end(0, s); return FUSG_ERR_LAUNCH; }
-                if (sc.ksplit > 1) {
-                    const long total = (long)k.M * (k.Cout_pad >> 2);
-                    ConvK kr = h.c;
-                    hipLaunchKernelGGL(conv_splitk_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, kr, 1);
-                    e = hipGetLastError();
-                    if (e != hipSuccess) { set_error("conv2d split-K reduce launch: %s", hipGetErrorString(e)); prof_end(0, s); return FUSG_ERR_LAUNCH; }
-                }
-                note_conv_kernel(FUSG_CONV_SMALL);
-                prof_end(0, s);
-                return FUSG_OK;
-            }
-        }
+
+    const double flops = 2.0 * (double)Ml * d->cout * d->k_pad * nphase;   // padded-K flops; bench uses algorithmic ones
+    prof_begin(0, s, flops);
+    hipError_t e;
+    const char* what = "conv2d launch";
+    switch (r.family) {
+        case FUSG_CONV_SMALL:     what = "conv2d small-image launch"; e = run_small(k, *d, r.sc, s, pk); break;
+        case FUSG_CONV_POINTWISE: what = "conv2d pointwise launch"; e = run_pointwise(k, *d, s); break;
+        case FUSG_CONV_TAPUNIT_F32: case FUSG_CONV_TAPUNIT: case FUSG_CONV_TAPUNIT_BF16:
+            what = r.mode == 2 ? "conv2d fp32 tap-unit launch" : "conv2d tap-unit launch";
+            e = run_tapunit(k, *d, r, s, pk);
+            break;
+        case FUSG_CONV_GENERIC_F32: case FUSG_CONV_GENERIC_F16X3:
+            e = kGeneric[d->precision == FUSG_PREC_F16X3][d->tile](k, dim3(k.MT * k.NT, nphase, d->ksplit), s, pk,
+                                                                   d->pad_mode != FUSG_PAD_ZERO || d->upsample != 0);
+            break;
+        default:                  what = "conv2d halo launch"; e = run_halo(k, *d, r, s, pk); break;
     }
-    // pointwise from <= 8 channels: the streaming VALU kernel above - an exact fp32 fmaf chain in the generic fp32 kernel's k
-    // order, so it serves both the split-fp16 and (round 4) the exact-fp32 precision with that kernel's bits
-    // (FUSG_NO_POINTWISE, read per call, keeps the MFMA kernels: tests compare the two)
-    if ((d->precision == FUSG_PREC_F16X3 || d->precision == FUSG_PREC_F32) && getenv("FUSG_NO_POINTWISE") == nullptr && nphase == 1 && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->upsample == 0 && !has1 &&
-        d->c0k >= 4 && d->c0k <= 8 && d->ksplit <= 1 && d->store_mode == FUSG_STORE_NORMAL && k.vec_epi && !d->stats_out &&
-        d->cout % 4 == 0 && d->pre_op <= FUSG_PRE_ELU && (d->q_oy | d->q_ox) == 0 && !d->tile_list && d->wpack && d->pad_h == 0 &&
-        d->pad_w == 0 && 256 % (d->cout_pad >> 2) == 0 && !env_switches().no_halo && !env_switches().no_pointwise) {
-        const int n4 = d->cout_pad >> 2, ppb = PW_ITEMS * 256 / n4;
-        hipLaunchKernelGGL(conv_pointwise_small, dim3((unsigned)((Ml + ppb - 1) / ppb)), dim3(256),
-                           (size_t)(d->cout_pad * 8 + ppb * 8) * sizeof(float), s, k, (int)Ml);
-        e = hipGetLastError();
-        prof_end(0, s);
-        if (e != hipSuccess) { set_error("conv2d pointwise launch: %s", hipGetErrorString(e)); return FUSG_ERR_LAUNCH; }
-        note_conv_kernel(FUSG_CONV_POINTWISE);
-        return FUSG_OK;
-    }
-    // few-channel k x k layers (the 7x7 stems) in exact fp32 (round 4): conv_kernel_tapunit_f32.h
-    if (d->wfrag_order == 2 && d->precision == FUSG_PREC_F32 && d->wfrag_f32 != nullptr && (((uintptr_t)d->wfrag_f32) & 15) == 0 &&
-        getenv("FUSG_NO_F32_HALO") == nullptr) {
-        const int nunits = d->kh * d->kw * (d->c0k / 4);
-        const bool ok = nphase == 1 && d->upsample == 0 && d->ksplit <= 1 && !has1 && d->c0k >= 4 && d->c0k <= 24 && d->c0k % 4 == 0 &&
-                        d->kh >= 1 && d->kw >= 1 && d->dil == 1 && d->qh % 8 == 0 && d->qw % 16 == 0 && nunits <= 320 &&
-                        d->k_pad >= d->kh * d->kw * d->c0k && (d->q_oy | d->q_ox) == 0 && !d->tile_list && !env_switches().no_halo;
-        if (ok) {
-            TapUnitF h;
-            memset(&h, 0, sizeof(h));
-            h.c = k;
-            h.stride = d->stride; h.pad_h = d->pad_h; h.pad_w = d->pad_w;
-            h.HH = 7 * d->stride + d->kh; h.HW = 15 * d->stride + d->kw;
-            h.CP = d->c0k; h.PP = d->c0k;
-            h.RP = h.HW * h.PP;
-            h.nunits = nunits;
-            h.wfrag = (const float*)d->wfrag_f32;
-            h.nt32 = d->cout_pad / 32;
-            const int upp = d->c0k / 4;
-            for (int j = 0; j < nunits; ++j) {
-                const int tap = j / upp, u = j - tap * upp, ky = tap / d->kw, kx = tap - ky * d->kw;
-                h.uoff[j] = ky * h.RP + kx * h.PP + u * 4;
-            }
-            int bn = d->cout_pad % 128 == 0 ? 128 : (d->cout_pad % 64 == 0 ? 64 : 32);
-            if (const int v = env_switches().halo_bn; (v == 32 || v == 64 || v == 128) && d->cout_pad % v == 0) bn = v;
-            h.tiles_x = d->qw / 16; h.tiles_per_img = (d->qh / 8) * h.tiles_x;
-            h.c.MT = (int)x0.n * h.tiles_per_img; h.c.NT = d->cout_pad / bn;
-            h.c.ksplit = 1; h.c.wscale = nullptr; h.c.status = nullptr;
-            if ((size_t)h.HH * h.RP * sizeof(float) <= 80 * 1024 && h.HH * h.HW * (h.CP / 4) <= 256 * 8) {
-                dim3 hgrid(h.c.MT * h.c.NT, 1, 1);
-                e = bn == 128 ? launch_tapunit_f32_128(h, hgrid, s, pk) : bn == 64 ? launch_tapunit_f32_64(h, hgrid, s, pk)
-                                                                                   : launch_tapunit_f32_32(h, hgrid, s, pk);
-                if (e != hipSuccess) { set_error("conv2d fp32 tap-unit launch: %s", hipGetErrorString(e)); prof_end(0, s); return FUSG_ERR_LAUNCH; }
-                note_conv_kernel(FUSG_CONV_TAPUNIT_F32);
-                prof_end(0, s);
-                return FUSG_OK;
-            }
-        }
-    }
-    // few-channel k x k layers (the 7x7 stems): tap-unit kernel (conv_kernel_tapunit.h)
-    if (d->wfrag_order == 2) {
-        const int unit = d->c0k % 8 == 0 ? 8 : 4;
-        const int nunits = d->kh * d->kw * (d->c0k / unit);
-        const bool ok = d->precision == FUSG_PREC_F16X3 && nphase == 1 && d->upsample == 0 && d->ksplit <= 1 && !has1 &&
-                        d->wfrag != nullptr && (((uintptr_t)d->wfrag) & 15) == 0 && d->c0k >= 4 && d->c0k <= 24 && d->kh >= 1 &&
-                        d->kw >= 1 && d->dil == 1 && d->qh % 8 == 0 && d->qw % 16 == 0 && nunits <= 160 &&
-                        d->k_pad >= d->kh * d->kw * d->c0k && (d->q_oy | d->q_ox) == 0 && !d->tile_list &&
-                        !env_switches().no_halo;
-        if (ok) {
-            TapUnitK h;
-            memset(&h, 0, sizeof(h));
-            h.c = k;
-            h.stride = d->stride; h.pad_h = d->pad_h; h.pad_w = d->pad_w;
-            h.HH = 7 * d->stride + d->kh; h.HW = 15 * d->stride + d->kw;
-            h.CP = d->c0k; h.PP = d->c0k;
-            h.RP = (h.HW * h.PP + 127) / 128 * 128;               // rows 256 B apart: conflict-free 16-lane read groups
-            h.nunits = nunits; h.nsteps = (nunits + 16 / unit - 1) / (16 / unit);
-            h.wfrag = (const _Float16*)d->wfrag;
-            h.nt32 = d->cout_pad / 32;
-            // FUSG_PREC_BF16: the stem in single-pass bf16 too (wfrag_bf16 in the tap-unit form, pack.py: frag_tapunit_bf16)
-            const bool tbf = want_bf16 && d->wfrag_bf16 != nullptr && (((uintptr_t)d->wfrag_bf16) & 15) == 0 && getenv("FUSG_NO_BF16_TAPUNIT") == nullptr;
-            if (tbf) { h.wfrag = (const _Float16*)d->wfrag_bf16; h.c.wscale = nullptr; h.c.status = nullptr; }
-            const int upp = d->c0k / unit;
-            for (int j = 0; j < nunits; ++j) {
-                const int tap = j / upp, u = j - tap * upp, ky = tap / d->kw, kx = tap - ky * d->kw;
-                h.uoff[j] = ky * h.RP + kx * h.PP + u * unit;
-            }
-            int bn = d->cout_pad % 128 == 0 ? 128 : (d->cout_pad % 64 == 0 ? 64 : 32);
-            // thin layers (a handful of k-steps: the launch is a stream of output stores) run 24-45 % faster on the
-            // 64-column tile: its 16 KiB epilogue detour leaves room for more resident workgroups than the 128-column one
-            if (bn == 128 && h.nsteps <= 4) bn = 64;
-            if (const int v = env_switches().halo_bn; (v == 32 || v == 64 || v == 128) && d->cout_pad % v == 0) bn = v;
-            h.tiles_x = d->qw / 16; h.tiles_per_img = (d->qh / 8) * h.tiles_x;
-            h.c.MT = (int)x0.n * h.tiles_per_img; h.c.NT = d->cout_pad / bn;
-            h.c.ksplit = 1;
-            if (tapunit_lds_bytes(h.HH, h.RP) <= 80 * 1024 && h.HH * h.HW * (h.CP / 4) <= 256 * 8) {
-                dim3 hgrid(h.c.MT * h.c.NT, 1, 1);
-                e = bn == 128 ? launch_tapunit_128(h, hgrid, s, pk, unit, tbf) : bn == 64 ? launch_tapunit_64(h, hgrid, s, pk, unit, tbf)
-                                                                                          : launch_tapunit_32(h, hgrid, s, pk, unit, tbf);
-                if (e != hipSuccess) { set_error("conv2d tap-unit launch: %s", hipGetErrorString(e)); prof_end(0, s); return FUSG_ERR_LAUNCH; }
-                note_conv_kernel(tbf ? FUSG_CONV_TAPUNIT_BF16 : FUSG_CONV_TAPUNIT);
-                prof_end(0, s);
-                return FUSG_OK;
-            }
-        }
-    }
-    if (halo_ok) {
-        HaloK h;
-        memset(&h, 0, sizeof(h));
-        h.c = k;
-        h.kh = d->kh; h.kw = d->kw; h.dil = d->dil; h.pad_h = d->pad_h; h.pad_w = d->pad_w;
-        h.c1k = d->k_pad / (d->kh * d->kw) - d->c0k;
-        h.wfrag = (const _Float16*)d->wfrag;
-        h.nt32 = d->cout_pad / 32;
-        int bn = d->cout_pad % 128 == 0 ? 128 : (d->cout_pad % 64 == 0 ? 64 : 32);
-        // pointwise layers are bound by their output stores, not by operand staging: the 64-column tile (a quarter of
-        // the epilogue LDS, more resident workgroups) is 6-24 % faster there (hourglass 1x1s); k x k layers keep 128
-        if (bn == 128 && d->kh * d->kw == 1) bn = 64;
-        {   // small grids: narrower column tiles until the launch has enough workgroups to fill the chip
-            const long min_wg = env_switches().halo_minwg;
-            const long mt = (long)x0.n * (d->tile_list ? d->tile_count : (d->qh / 8) * (d->qw / 16));
-            while (bn > 32 && mt * (d->cout_pad / bn) < min_wg) bn /= 2;
-        }
-        if (const int v = env_switches().halo_bn; (v == 32 || v == 64 || v == 128) && d->cout_pad % v == 0) bn = v;
-        h.c.NT = d->cout_pad / bn;
-        h.c.ksplit = 1;
-        h.HH = 7 + (d->kh - 1) * d->dil + 1; h.HW = 15 + (d->kw - 1) * d->dil + 1;
-        if (s2d_form) {
-            // parity-quadrant form (include/fusg.h, wfrag_order): input row 2Y - 1 + ky = parity (ky-1)&1, sub-row Y + (ky-1 >> 1)
-            if (!(d->kh == d->kw && (d->kh == 3 || d->kh == 4) && d->pad_h == 1 && d->pad_w == 1 && d->dil == 1 && !has1 &&
-                  d->pad_mode != FUSG_PAD_REPLICATE)) {
-                set_error("conv2d: wfrag_order 1 needs stride 2, k3/k4, pad 1, dil 1, one source");
-                prof_end(0, s);
-                return FUSG_ERR_INVALID;
-            }
-            h.s2d = 1; h.HH = 10; h.HW = 18;
-            int slab = 0;
-            for (int q = 0; q < 4; ++q) {
-                h.qwoff[q] = slab;
-                int n = 0;
-                for (int ky = 0; ky < d->kh; ++ky) {
-                    if (((ky - 1) & 1) != (q >> 1)) continue;
-                    for (int kx = 0; kx < d->kw; ++kx) {
-                        if (((kx - 1) & 1) != (q & 1)) continue;
-                        const int dy = (ky - 1) >> 1, dx = (kx - 1) >> 1;          // arithmetic shift: floor
-                        h.qtdy[q][n] = dy + 1;
-                        h.qtdx[q][n] = dx + 1;
-                        ++n;
-                    }
-                }
-                h.qtaps[q] = n;
-                slab += n;
-            }
-        }
-        // (Round 3 tried 16 x 16 pixel patches for the 32 / 64-column tiles - half the workgroups, twice the work each,
-        // halo 1.27x instead of 1.41x of the patch: every such launch got 13 - 51 % SLOWER (32 -> 32 1x1 at 256 x 256
-        // 130 -> 186 us, 64 -> 32 3x3 311 -> 351 us), conv time of the pass 23.9 -> 24.5 ms.  Dropped.)
-        h.tiles_x = d->qw / 16; h.tiles_per_img = (d->qh / 8) * h.tiles_x;
-        h.c.MT = (int)x0.n * h.tiles_per_img;
-        if (d->tile_list) {
-            if (d->tile_count > h.tiles_per_img) { set_error("conv2d: tile_count %d > %d patches per image", d->tile_count, h.tiles_per_img); prof_end(0, s); return FUSG_ERR_INVALID; }
-            h.tile_list = d->tile_list; h.tile_count = d->tile_count;
-            h.c.MT = (int)x0.n * d->tile_count;
-        }
-        if (halo_fits(h.HH, h.HW)) {
-            dim3 hgrid(h.c.MT * h.c.NT, 1, 1);
-            const bool bf = want_bf16 && d->wfrag_bf16 != nullptr && (((uintptr_t)d->wfrag_bf16) & 15) == 0;
-            if (bf) { h.wfrag = (const _Float16*)d->wfrag_bf16; h.c.wscale = nullptr; h.c.status = nullptr; }
-            if (f32_halo) { h.wfrag = (const _Float16*)d->wfrag_f32; h.c.wscale = nullptr; h.c.status = nullptr; }
-            const int mode = f32_halo ? 2 : (bf ? 1 : 0);
-            // bf16 mode on a 16 x 16 pixel patch (conv_kernel_halo.h, BM == 256; FUSG_BF16_BIG=14|22 picks the wave layout).  OFF by
-            // default: measured 1.4x (1 x 4 waves) and 3x (2 x 2) SLOWER than the 8 x 16 patch (profiles/r04_ab_experiments.txt) - 128
-            // accumulator registers per wave leave one wave per SIMD, and nothing then overlaps the fp32 -> bf16 staging
-            if (bf && bn == 128 && !s2d_form && !d->tile_list && d->qh % 16 == 0 && d->qw % 16 == 0) {
-                static const int big = [] { const char* v = getenv("FUSG_BF16_BIG"); return v ? atoi(v) : 0; }();
-                const int HHb = 15 + (d->kh - 1) * d->dil + 1;
-                if (big != 0 && HHb * h.HW * 8 <= 256 * 12) {
-                    HaloK hb = h;
-                    hb.HH = HHb;
-                    hb.tiles_per_img = (d->qh / 16) * hb.tiles_x;
-                    hb.c.MT = (int)x0.n * hb.tiles_per_img;
-                    dim3 bgrid(hb.c.MT * hb.c.NT, 1, 1);
-                    e = big == 22 ? launch_halo_big22(hb, bgrid, s, pk) : launch_halo_big14(hb, bgrid, s, pk);
-                    if (e == hipSuccess) {
-                        note_conv_kernel(FUSG_CONV_HALO_BF16);
-                        prof_end(0, s);
-                        return FUSG_OK;
-                    }
-                    (void)hipGetLastError();                     // does not fit: the 8 x 16 patch below
-                }
-            }
-            // narrow column tiles of k x k layers on SMALL grids: K split over the waves (conv_kernel_halo.h, KS) when every wave
-            // gets a tap.  Measured per dispatch inside the pass (round 3, same card): grids of 256 - 1024 workgroups 2 - 14 %
-            // shorter (their time is one workgroup's latency); grids of 4096 - 16384 workgroups 19 - 42 % LONGER (the four
-            // partial tiles need 64 KiB of LDS: two workgroups per CU instead of three, and those launches move 3 - 4.4 TB/s -
-            // they live on bytes in flight).  Hence the limit.
-            const int ntaps = d->kh * d->kw;
-            const bool ks_ok = !s2d_form && !d->tile_list && !env_switches().no_ksplit && (long)h.c.MT * h.c.NT <= 1024;
-            const bool k4 = ks_ok && bn == 32 && ntaps >= 4, k2 = ks_ok && bn == 64 && ntaps >= 2;
-            e = bn == 128 ? launch_halo_128(h, hgrid, s, pk, mode)
-                          : bn == 64 ? (k2 ? launch_halo_64k(h, hgrid, s, pk, mode) : launch_halo_64(h, hgrid, s, pk, mode))
-                                     : (k4 ? launch_halo_32k(h, hgrid, s, pk, mode) : launch_halo_32(h, hgrid, s, pk, mode));
-            if (e != hipSuccess) { set_error("conv2d halo launch: %s", hipGetErrorString(e)); prof_end(0, s); return FUSG_ERR_LAUNCH; }
-            note_conv_kernel(f32_halo ? FUSG_CONV_HALO_F32 : bf ? FUSG_CONV_HALO_BF16 : (h.s2d ? FUSG_CONV_HALO_S2D : FUSG_CONV_HALO));
-            prof_end(0, s);
-            return FUSG_OK;
-        }
-    }
-    if (d->tile_list) {
-        set_error("conv2d: tile_list needs a launch that qualifies for the halo kernel");
-        prof_end(0, s);
-        return FUSG_ERR_UNSUPPORTED;
-    }
-    note_conv_kernel(d->precision == FUSG_PREC_F16X3 ? FUSG_CONV_GENERIC_F16X3 : FUSG_CONV_GENERIC_F32);
-    if (d->precision == FUSG_PREC_F16X3) {
-        switch (d->tile) {
-            case FUSG_TILE_128x128: e = launch_h3_128x128(k, grid, s, pk, gen); break;
-            case FUSG_TILE_128x64:  e = launch_h3_128x64(k, grid, s, pk, gen); break;
-            case FUSG_TILE_128x32:  e = launch_h3_128x32(k, grid, s, pk, gen); break;
-            case FUSG_TILE_64x64:   e = launch_h3_64x64(k, grid, s, pk, gen); break;
-            default:                e = launch_h3_64x128(k, grid, s, pk, gen); break;
-        }
-    } else
-    switch (d->tile) {
-        case FUSG_TILE_128x128: e = launch_tile_128x128(k, grid, s, pk, gen); break;
-        case FUSG_TILE_128x64:  e = launch_tile_128x64(k, grid, s, pk, gen); break;
-        case FUSG_TILE_128x32:  e = launch_tile_128x32(k, grid, s, pk, gen); break;
-        case FUSG_TILE_64x64:   e = launch_tile_64x64(k, grid, s, pk, gen); break;
-        default:                e = launch_tile_64x128(k, grid, s, pk, gen); break;
-    }
-    if (e != hipSuccess) { set_error("conv2d launch: %s", hipGetErrorString(e)); prof_end(0, s); return FUSG_ERR_LAUNCH; }
-    if (d->ksplit > 1 && k.counters == nullptr) {
+    // K ranges over workgroups: the slab reduce (the generic kernels combine in-launch when given split-K counters)
+    if (e == hipSuccess && k.ksplit > 1 && (r.family == FUSG_CONV_SMALL || k.counters == nullptr)) {
+        what = "conv2d split-K reduce launch";
         const long total = (long)nphase * k.M * (k.Cout_pad >> 2);
         hipLaunchKernelGGL(conv_splitk_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k, nphase);
         e = hipGetLastError();
-        if (e != hipSuccess) { set_error("conv2d split-K reduce launch: %s", hipGetErrorString(e)); prof_end(0, s); return FUSG_ERR_LAUNCH; }
     }
     prof_end(0, s);
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return FUSG_ERR_LAUNCH; }
+    note_conv_kernel(r.family);
     return FUSG_OK;
 }
 extern "C" int fusg_conv2d(const fusg_conv_desc* din, void* stream) { return fusg::plan_dispatch(conv2d_impl, stream, din); }

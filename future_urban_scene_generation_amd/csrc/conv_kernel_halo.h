@@ -137,7 +137,7 @@ constexpr int halo_waves_mode(int tm, int tn, int wm, int pk, int ni, int mode, 
     return halo_bf16_dense(tm, wm, pk, ni, mode, ks) ? FUSG_BF16_OCC : halo_waves(tm, tn);
 }
 template <int TM, int TN, int WM, int WN, int PK, int NI, int MODE, int KS = 1>
-__global__ __launch_bounds__(256, (32 * TM * WM == 256) ? 1 : halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS)) void conv_halo_h3(const HaloK hk) {
+__global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS)) void conv_halo_h3(const HaloK hk) {
     constexpr bool BF = MODE == 1, F32 = MODE == 2;
     constexpr int CH = HALO_CH, HPITCH = HALO_PP;
     constexpr int CPP = CH / 4;                    // 16-byte fp32 items per halo pixel
@@ -146,9 +146,7 @@ __global__ __launch_bounds__(256, (32 * TM * WM == 256) ? 1 : halo_waves_mode(TM
     constexpr int BM = 32 * TM * WM;               // 128 output pixels = 8 rows x 16 columns
     constexpr int BN = 32 * TN * WN;
     constexpr int PR = BM / 16;                    // patch rows
-    // BM == 256 ("big patch", bf16 mode only, launch_halo_big): a 16 x 16 pixel patch per workgroup - twice the MFMAs per weight
-    // fragment fetched and per step of bookkeeping, a halo of 1.27x instead of 1.41x the patch
-    static_assert((BM == 128 || (BM == 256 && MODE == 1 && KS == 1)) && WM * WN * KS == 4, "8x16 (or 16x16) pixel patch, 4 waves");
+    static_assert(BM == 128 && WM * WN * KS == 4, "8x16 pixel patch, 4 waves");
     static_assert(KS == 1 || (WM == 1 && TN == 1 && TM == 4), "K split: every wave owns the whole patch and one 32-column tile");
     extern __shared__ __attribute__((aligned(16))) _Float16 smem_h[];
     const int HP = hk.HH * hk.HW;
@@ -466,16 +464,9 @@ __global__ __launch_bounds__(256, (32 * TM * WM == 256) ? 1 : halo_waves_mode(TM
     // (Tried in round 3 and left off: weights TWO steps ahead through a ring of three fragment sets for the short steps -
     // bf16 mode, 16 MFMAs = 256 cycles per step, and the narrow split-fp16 tiles, 12 - 24 MFMAs.  Their waves spend 52 % /
     // 35 - 38 % of their cycles in s_waitcnt (profiles/r03_stalls_bf16_halo_256.txt, r03_pmc_narrow_layers.txt), yet the
-    // longer lead made both slower: bf16 leg conv 18.15 -> 18.6 ms, f16x3 leg 24.6 -> 25.2 ms.  FUSG_HALO_RING3 builds it.)
-#ifdef FUSG_HALO_RING3
-    constexpr bool RING3 = BF || TM * TN <= 2;
-#else
-    constexpr bool RING3 = false;
-#endif
-    BFrag bfC;
+    // longer lead made both slower: bf16 leg conv 18.15 -> 18.6 ms, f16x3 leg 24.6 -> 25.2 ms.)
     halo_issue(hA, 0, 0, 0);
     b_load(bfA, wnext);
-    if constexpr (RING3) { advance_w(); if (cgn < nch) b_load(bfB, wnext); }
     halo_commit(hA);
     __syncthreads();
     auto one_step = [&](const BFrag& use, BFrag& fill) __attribute__((always_inline)) {
@@ -486,7 +477,7 @@ __global__ __launch_bounds__(256, (32 * TM * WM == 256) ? 1 : halo_waves_mode(TM
             halo_issue(hA, cg + 1, qh, cqh);
         }
         if (cg == 1 && tap < 2 && nch <= 6) FUSG_HSTAMP(20 + 4 * tap);   // (slots 20.. belong to the chunk stamps of deeper layers)
-        advance_w();                                               // the step fetched now: one (bf16: two) ahead
+        advance_w();                                               // the step fetched now: one ahead
         if (cgn < nch) b_load(fill, wnext);
         if (cg == 1 && tap < 2 && nch <= 6) FUSG_HSTAMP(21 + 4 * tap);
         int dyp = ky * hk.dil, dxp = kx * hk.dil;                  // halo pixel offset of the tap
@@ -507,22 +498,11 @@ __global__ __launch_bounds__(256, (32 * TM * WM == 256) ? 1 : halo_waves_mode(TM
             FUSG_HSTAMP(3 * cg);
         }
     };
-    if constexpr (RING3) {
-        for (;;) {
-            one_step(bfA, bfC);
-            if (cg >= nch) break;
-            one_step(bfB, bfA);
-            if (cg >= nch) break;
-            one_step(bfC, bfB);
-            if (cg >= nch) break;
-        }
-    } else {
-        for (;;) {
-            one_step(bfA, bfB);
-            if (cg >= nch) break;
-            one_step(bfB, bfA);
-            if (cg >= nch) break;
-        }
+    for (;;) {
+        one_step(bfA, bfB);
+        if (cg >= nch) break;
+        one_step(bfB, bfA);
+        if (cg >= nch) break;
     }
 
     }
@@ -586,8 +566,7 @@ __global__ __launch_bounds__(256, (32 * TM * WM == 256) ? 1 : halo_waves_mode(TM
         return p.stats + ((long)b * p.stats_slots + t2 * (BM / 32) + ((wm * TM * 32) >> 5) + i) * p.Cout * 2;
     };
     if (p.vec_epi) {
-        constexpr bool HALVES = BM == 256 || (TM >= 4 && halo_bf16_dense(TM, WM, PK, NI, MODE, KS));
-        if constexpr (HALVES) {
+        if constexpr (TM >= 4 && halo_bf16_dense(TM, WM, PK, NI, MODE, KS)) {
             // the wave's tile (TM * 32 rows) leaves in two halves through a wave-private LDS region of half the size (64 KiB per
             // workgroup instead of 128: two workgroups still share a CU); residuals are read in the pass, not prefetched
             // (the prefetch set would be 128 more registers)
@@ -690,42 +669,7 @@ hipError_t launch_halo(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mod
     return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
 }
 
-// bf16 mode, 16 x 16 pixel patch x 128 columns (BM == 256): the host sets HH / tiles_per_img for 16 patch rows
-template <int TM, int TN, int WM, int WN>
-hipError_t launch_halo_big(const HaloK& k, dim3 grid, hipStream_t s, int pk) {
-    static_assert(32 * TM * WM == 256, "16 x 16 pixel patch");
-    const int HP = k.HH * k.HW;
-    size_t lds = (size_t)k.HH * halo_row_pitch(k.HW) * sizeof(_Float16);                        // ONE (bf16) halo image
-    constexpr size_t EPI = (size_t)4 * (TM / 2) * 32 * TN * 32 * sizeof(float);
-    if (lds < EPI) lds = EPI;
-    const int touch_off = (int)lds;
-    lds += TOUCH_LDS_BYTES;
-    if (HP * 8 > 256 * 12 || lds > 80 * 1024) return hipErrorInvalidValue;
-    const void* fn = pk == PK_NONE ? (const void*)conv_halo_h3<TM, TN, WM, WN, PK_NONE, 12, 1, 1>
-                   : pk == PK_ELU  ? (const void*)conv_halo_h3<TM, TN, WM, WN, PK_ELU, 12, 1, 1>
-                                   : (const void*)conv_halo_h3<TM, TN, WM, WN, PK_AFFINE, 12, 1, 1>;
-    if (hipError_t e = ensure_dyn_lds(fn, 80 * 1024 + TOUCH_LDS_BYTES); e != hipSuccess) return e;
-    HaloK kk = k;
-    kk.RP = halo_row_pitch(k.HW);
-    kk.touch_off = touch_off;
-    bool fits = true;
-    auto magic = [&fits](long nmax, int d) -> unsigned {
-        if (d < 1 || nmax * d >= (1L << 32)) fits = false;
-        return d < 2 ? 0u : (unsigned)(((1UL << 32) + (unsigned long)d - 1) / (unsigned long)d);
-    };
-    const long ntiles = (long)grid.x;
-    kk.m_hw = magic(256L * 12 + 255, k.HW);
-    kk.m_nt = magic(ntiles, k.c.NT);
-    kk.m_tpi = magic(ntiles, k.tiles_per_img);
-    kk.m_tx = magic((long)k.tiles_per_img, k.tiles_x);
-    if (!fits) return hipErrorInvalidValue;
-    void* args[] = {(void*)&kk};
-    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
-}
-
 hipError_t launch_halo_128(const HaloK&, dim3, hipStream_t, int, int);
-hipError_t launch_halo_big22(const HaloK&, dim3, hipStream_t, int);        // 16 x 16 patch, waves 2 x 2 (128 pixels x 64 columns each)
-hipError_t launch_halo_big14(const HaloK&, dim3, hipStream_t, int);        // 16 x 16 patch, waves 1 x 4 (256 pixels x 32 columns each)
 hipError_t launch_halo_64(const HaloK&, dim3, hipStream_t, int, int);
 hipError_t launch_halo_32(const HaloK&, dim3, hipStream_t, int, int);
 hipError_t launch_halo_32k(const HaloK&, dim3, hipStream_t, int, int);      // K split over the four waves

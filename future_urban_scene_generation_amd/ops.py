@@ -371,22 +371,15 @@ def _workspace(device, nbytes: int) -> torch.Tensor:
     return ws
 
 
-def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
-         out_c_off: int = 0, res0: Optional[torch.Tensor] = None, res1: Optional[torch.Tensor] = None,
-         pre_op: int = L.PRE_NONE, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_bstride: int = 0,
-         act: int = L.ACT_NONE, store: int = L.STORE_NORMAL, nchw_out: bool = False, tile: int = L.TILE_AUTO,
-         ksplit: int = 0, precision: Optional[str] = None, want_stats: bool = False,
-         out_stride: int = 1, out_off: Tuple[int, int] = (0, 0), tiles: Optional[torch.Tensor] = None,
-         q_window: Optional[Tuple[int, int, int, int]] = None, q_size: Optional[Tuple[int, int]] = None,
-         stats_into: Optional[Tuple[torch.Tensor, int]] = None):
-    """One fused convolution launch (fusg_conv2d).  Returns the output tensor (allocated NHWC-physical
-    unless `out` is given or `nchw_out` asks for a standard-contiguous NCHW result).
-    out_stride / out_off: write output pixel (qy, qx) at (qy*out_stride + out_off[0], qx*out_stride + out_off[1])
-    of `out` (phase launches).  tiles: int32 device tensor of 8x16-pixel patch indices - compute only those
-    (halo-kernel launches only).  q_window = (oy, ox, h, w): compute only that window of the output grid (into the
-    same positions of `out`, which must be given).  q_size = (qh, qw): output grid of a launch whose padding is not
-    symmetric (transposed-conv phases; zero padding only).  stats_into = (buffer [B, slots, cout, 2], first_slot): write
-    this launch's fused statistics slots there (the launch must qualify)."""
+def _conv_desc(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
+               out_c_off: int = 0, res0: Optional[torch.Tensor] = None, res1: Optional[torch.Tensor] = None,
+               pre_op: int = L.PRE_NONE, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_bstride: int = 0,
+               act: int = L.ACT_NONE, store: int = L.STORE_NORMAL, nchw_out: bool = False, tile: int = L.TILE_AUTO,
+               ksplit: int = 0, precision: Optional[str] = None, want_stats: bool = False,
+               out_stride: int = 1, out_off: Tuple[int, int] = (0, 0), tiles: Optional[torch.Tensor] = None,
+               q_window: Optional[Tuple[int, int, int, int]] = None, q_size: Optional[Tuple[int, int]] = None):
+    """The fusg_conv_desc of an ops.conv launch before planning -> (desc, out).  Takes CPU tensors too (no launch, no
+    torch.cuda call when a `status_scope` is open): tests describe launches to fusg_conv2d_route this way."""
     plan.to(x0.device)
     if RECORDER is not None:
         RECORDER.keep.append(plan.dev)             # packed weights / tables the recorded launch points into
@@ -476,6 +469,30 @@ def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *,
                     d.wfrag_f32 = ff.data_ptr()
                     if RECORDER is not None:
                         RECORDER.keep.append(ff)
+    return d, out
+
+
+def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
+         out_c_off: int = 0, res0: Optional[torch.Tensor] = None, res1: Optional[torch.Tensor] = None,
+         pre_op: int = L.PRE_NONE, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_bstride: int = 0,
+         act: int = L.ACT_NONE, store: int = L.STORE_NORMAL, nchw_out: bool = False, tile: int = L.TILE_AUTO,
+         ksplit: int = 0, precision: Optional[str] = None, want_stats: bool = False,
+         out_stride: int = 1, out_off: Tuple[int, int] = (0, 0), tiles: Optional[torch.Tensor] = None,
+         q_window: Optional[Tuple[int, int, int, int]] = None, q_size: Optional[Tuple[int, int]] = None,
+         stats_into: Optional[Tuple[torch.Tensor, int]] = None):
+    """One fused convolution launch (fusg_conv2d).  Returns the output tensor (allocated NHWC-physical
+    unless `out` is given or `nchw_out` asks for a standard-contiguous NCHW result).
+    out_stride / out_off: write output pixel (qy, qx) at (qy*out_stride + out_off[0], qx*out_stride + out_off[1])
+    of `out` (phase launches).  tiles: int32 device tensor of 8x16-pixel patch indices - compute only those
+    (halo-kernel launches only).  q_window = (oy, ox, h, w): compute only that window of the output grid (into the
+    same positions of `out`, which must be given).  q_size = (qh, qw): output grid of a launch whose padding is not
+    symmetric (transposed-conv phases; zero padding only).  stats_into = (buffer [B, slots, cout, 2], first_slot): write
+    this launch's fused statistics slots there (the launch must qualify)."""
+    d, out = _conv_desc(plan, x0, x1, out=out, out_c_off=out_c_off, res0=res0, res1=res1, pre_op=pre_op, pre=pre,
+                        pre_bstride=pre_bstride, act=act, store=store, nchw_out=nchw_out, tile=tile, ksplit=ksplit,
+                        precision=precision, want_stats=want_stats, out_stride=out_stride, out_off=out_off, tiles=tiles,
+                        q_window=q_window, q_size=q_size)
+    b, qh, qw = x0.shape[0], d.qh, d.qw
     lib = L.lib()
     nbytes = lib.fusg_conv2d_plan(C.byref(d))
     ws = None

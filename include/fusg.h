@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FUSG_VERSION 116
+#define FUSG_VERSION 117
 
 typedef enum fusg_status {
     FUSG_OK = 0,
@@ -218,6 +218,9 @@ int  fusg_conv2d(const fusg_conv_desc* d, void* stream);
 /* Heuristic used when tile == AUTO / to size the workspace: fills tile, ksplit and returns the
  * workspace size in bytes (0 when ksplit <= 1). */
 int64_t fusg_conv2d_plan(fusg_conv_desc* d);
+/* Dry run of fusg_conv2d: the FUSG_CONV_* family it would launch for this descriptor, or the negative FUSG_ERR_* it would
+ * return.  Launches nothing and touches no device; the split-K workspace (the caller's allocation) is not checked. */
+int  fusg_conv2d_route(const fusg_conv_desc* d);
 
 /*
  * One pre-activation Bottleneck of the stacked hourglass in ONE launch (split-fp16 arithmetic, FUSG_PREC_F16X3):

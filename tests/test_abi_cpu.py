@@ -41,6 +41,7 @@ def test_validation_without_gpu(lib):
     d = L.ConvDesc()
     assert lib.fusg_conv2d(C.byref(d), None) == -1          # FUSG_ERR_INVALID before any launch
     assert b"src0" in lib.fusg_last_error()
+    assert lib.fusg_conv2d_route(C.byref(d)) == -1    # the dry run refuses it the same way
     t = L.Tensor()
     assert lib.fusg_maxpool2(C.byref(t), C.byref(t), None) == -1
     assert lib.fusg_argmax_hw(C.byref(t), None, None) == -1

@@ -1,11 +1,17 @@
 """CPU: the routing sweep's own machinery (tests/conv_sweep.py) - its cases are reproducible and legal, the edge table's recorded
-families are what the restated router predicts, and the one comparator is tight enough to reject subtly wrong results."""
+families are what the restated router predicts, the library's router (fusg_conv2d_route, a dry run) agrees with that
+restatement, and the one comparator is tight enough to reject subtly wrong results."""
+import ctypes as C
+import os
 from collections import Counter
+from contextlib import contextmanager
 
 import pytest
 import torch
 
 import conv_sweep as cs
+from future_urban_scene_generation_amd import _lib as L
+from future_urban_scene_generation_amd import ops
 
 
 def test_random_draw_is_deterministic():
@@ -48,6 +54,75 @@ def test_every_off_switch_leads_elsewhere():
                 continue
             env, ks = sw
             assert cs.predict_family(c, p, env=env, ksplit=ks) != fam, (c.tag, p, fam)
+
+
+PER_CALL = ("FUSG_NO_SMALL", "FUSG_NO_POINTWISE", "FUSG_NO_F32_HALO", "FUSG_NO_BF16_TAPUNIT", "FUSG_SMALL_KSPLIT")
+
+
+@contextmanager
+def _env(env):
+    """Exactly the per-call switches of `env` set (the library and ops.conv read them per call)."""
+    old = {k: os.environ.pop(k, None) for k in PER_CALL}
+    os.environ.update(env or {})
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+def _nhwc(b, c, h, w, cpad=4):
+    """A CPU tensor laid out like ops.as_nhwc's: channels padded to a multiple of cpad, logical [b, c, h, w]."""
+    cp = (c + cpad - 1) // cpad * cpad
+    full = torch.zeros(b, h, w, cp).permute(0, 3, 1, 2)
+    return full if cp == c else full[:, :c]
+
+
+def _route(c, plan, prec, env=None, ksplit=None):
+    """The library's family for the case's ops.conv launch (tests/test_gpu_conv_sweep.py, _launch), on CPU tensors: the
+    descriptor ops.conv builds, planned by fusg_conv2d_plan, routed by fusg_conv2d_route."""
+    ho, wo = c.full_hw()
+    x0 = _nhwc(c.B, c.c0, c.H, c.W, c.cin_pad)
+    x1 = _nhwc(c.B, c.c1, c.H, c.W, c.cin_pad) if c.c1 else None
+    kw = dict(pre_op=cs.PRE[c.pre], act=c.act, precision=prec, ksplit=c.ksplit if ksplit is None else ksplit)
+    if c.pre.startswith("affine"):
+        ctot = plan.c0k + plan.c1k
+        shape = (c.B, ctot) if c.per_sample else (ctot,)
+        kw.update(pre=(torch.zeros(shape), torch.zeros(shape)), pre_bstride=ctot if c.per_sample else 0)
+    for i in range(c.res):
+        kw["res%d" % i] = _nhwc(c.B, c.cout, ho, wo)
+    if c.out == "nchw":
+        kw["nchw_out"] = True
+    elif c.out == "slice":
+        kw.update(out=ops.nhwc_empty(c.B, c.out_c_off + c.cout + 4, ho, wo, "cpu"), out_c_off=c.out_c_off)
+    elif c.out == "misaligned":
+        kw["out"] = torch.zeros(c.B * ho * wo * c.cout + 1)[1:].view(c.B, ho, wo, c.cout).permute(0, 3, 1, 2)
+    if c.qwin:
+        kw.update(out=ops.nhwc_empty(c.B, c.cout, ho, wo, "cpu"), q_window=c.qwin)
+    lib = L.lib()
+    with _env(env), ops.status_scope(torch.zeros(4, dtype=torch.int32)):
+        d, _ = ops._conv_desc(plan, x0, x1, **kw)
+        lib.fusg_conv2d_plan(C.byref(d))
+        return lib.fusg_conv2d_route(C.byref(d))
+
+
+def test_library_router_matches_restatement():
+    """For every case and precision of the sweep, fusg_conv2d_route picks the family predict_family restates - and again with
+    the off-switch of that family set (the next family in the router's order)."""
+    seen = Counter()
+    for c in cs.all_cases():
+        plan = cs.make_plan(c, torch.zeros(c.cout, c.cin, c.kh, c.kw), torch.zeros(c.cout))
+        for p in cs.PRECISIONS:
+            fam = cs.predict_family(c, p)
+            assert _route(c, plan, p) == fam, (c.tag, p)
+            seen[fam] += 1
+            sw = cs.off_switch(fam, c)
+            if sw is not None:
+                env, ks = sw
+                assert _route(c, plan, p, env, ks) == cs.predict_family(c, p, env=env, ksplit=ks), (c.tag, p, env, ks)
+    assert set(seen) == set(cs.FAMILIES), sorted(seen)
 
 
 @pytest.mark.parametrize("c", cs.all_cases(), ids=lambda c: c.tag)
