@@ -84,6 +84,85 @@ __global__ __launch_bounds__(256) void fill_poly_planes_kernel(U8View frame, Pol
     for (int c = 0; c < 3; ++c) d[c] = in ? s[c] : 0;
 }
 
+// The same planes for n_jobs vehicles in one launch, polygons in DEVICE memory.  HBM-write-bound (64 vehicles x 5 planes
+// of 720 x 1280 x 3 = 884 MB), so each lane owns one 16-byte piece of a plane's contiguous bytes and writes it with one
+// dwordx4 store (a wave: 1 KiB, whole 128-B lines).  The plane's first bytes up to a 16-byte address and its last partial
+// piece are written byte by byte.  A piece outside the polygon's frame-clipped vertex box is zeros without a frame read or a
+// membership test (poly_inside is true only inside that box); inside, each of its <= 6 pixels takes poly_inside once and reads
+// the frame where it is true.  blockIdx.y = job * n_planes + plane; no atomics, no ordering: every byte is written once.
+constexpr long POLY_BOX_SAFE = 1L << 29;     // beyond this on_line's int arithmetic may wrap: such a polygon gets the whole frame as box
+
+__global__ __launch_bounds__(256) void fill_poly_planes_batch_kernel(U8View frame, const int* __restrict__ pts_xy,
+                                                                     const int* __restrict__ nverts, U8View dst, long plane_bytes) {
+    __shared__ int spx[MAXV], spy[MAXV], snv;
+    const int q = blockIdx.y, tid = threadIdx.x;
+    if (tid < MAXV) {
+        spx[tid] = pts_xy[((long)q * MAXV + tid) * 2];
+        spy[tid] = pts_xy[((long)q * MAXV + tid) * 2 + 1];
+    }
+    if (tid == 0) {
+        const int n = nverts[q];
+        snv = n < 0 ? 0 : (n > MAXV ? MAXV : n);
+    }
+    __syncthreads();
+    const int nv = snv, W = dst.w, H = dst.h;
+    long bx0 = W, by0 = H, bx1 = -1, by1 = -1;
+    bool wide = false;
+    for (int i = 0; i < nv; ++i) {
+        const long x = spx[i], y = spy[i];
+        bx0 = x < bx0 ? x : bx0; bx1 = x > bx1 ? x : bx1; by0 = y < by0 ? y : by0; by1 = y > by1 ? y : by1;
+        wide = wide || x < -POLY_BOX_SAFE || x > POLY_BOX_SAFE || y < -POLY_BOX_SAFE || y > POLY_BOX_SAFE;
+    }
+    if (wide) { bx0 = 0; by0 = 0; bx1 = W - 1; by1 = H - 1; }
+    bx0 = bx0 < 0 ? 0 : bx0; by0 = by0 < 0 ? 0 : by0; bx1 = bx1 > W - 1 ? W - 1 : bx1; by1 = by1 > H - 1 ? H - 1 : by1;
+    const bool empty = bx0 > bx1 || by0 > by1;
+    unsigned char* d = dst.p + (long)q * dst.sn;
+    const long head = ((16 - (long)((unsigned long)d & 15)) & 15) < plane_bytes ? ((16 - (long)((unsigned long)d & 15)) & 15) : plane_bytes;
+    const long pieces = 1 + (plane_bytes - head + 15) / 16;
+    for (long k = (long)blockIdx.x * 256 + tid; k < pieces; k += (long)gridDim.x * 256) {
+        const long s = k == 0 ? 0 : head + 16 * (k - 1);
+        const long e0 = k == 0 ? head : s + 16;
+        const long e = e0 < plane_bytes ? e0 : plane_bytes;
+        if (s >= e) continue;
+        const long p0 = s / 3, p1 = (e - 1) / 3;
+        const long y0 = p0 / W, y1 = p1 / W;
+        bool zero = empty || y1 < by0 || y0 > by1;
+        if (!zero && y0 == y1) zero = p1 - y1 * W < bx0 || p0 - y0 * W > bx1;
+        unsigned char b[16];
+        if (zero) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) b[i] = 0;
+        } else {
+            unsigned in = 0;                                              // bit (pixel - p0): inside or on the outline
+            for (long p = p0; p <= p1; ++p) {
+                const long y = p / W, x = p - y * W;
+                if (x >= bx0 && x <= bx1 && y >= by0 && y <= by1 && poly_inside((int)x, (int)y, nv, spx, spy)) in |= 1u << (p - p0);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const long o = s + i, p = o / 3;
+                b[i] = 0;
+                if (o < e && ((in >> (p - p0)) & 1)) {
+                    const long y = p / W, x = p - y * W;
+                    b[i] = frame.p[y * frame.sh + x * frame.sw + (o - p * 3)];
+                }
+            }
+        }
+        if (e - s == 16 && k > 0) {                                       // 16-byte aligned by construction
+            uint4 v;
+            v.x = b[0] | (b[1] << 8) | (b[2] << 16) | ((unsigned)b[3] << 24);
+            v.y = b[4] | (b[5] << 8) | (b[6] << 16) | ((unsigned)b[7] << 24);
+            v.z = b[8] | (b[9] << 8) | (b[10] << 16) | ((unsigned)b[11] << 24);
+            v.w = b[12] | (b[13] << 8) | (b[14] << 16) | ((unsigned)b[15] << 24);
+            *reinterpret_cast<uint4*>(d + s) = v;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (s + i < e) d[s + i] = b[i];
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ resize + Lab
 // cv::resize INTER_LINEAR, uint8: source index / 11-bit weights of one destination coordinate (float arithmetic as in
 // resize.cpp), horizontal pass in int, vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2.
@@ -526,6 +605,27 @@ extern "C" int fusg_fill_poly_planes_u8(const fusg_tensor* frame, const int32_t*
     hipLaunchKernelGGL(fill_poly_planes_kernel, dim3(blocks2d(total)), dim3(256), 0, (hipStream_t)stream, u8view(*frame), ps, u8view(*dst), total);
     FUSG_LAUNCH_CHECK("fill_poly_planes_u8");
     return FUSG_OK;
+}
+
+static int fill_poly_planes_batch_u8_impl(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
+                                          int32_t n_planes, const fusg_tensor* dst, void* stream) {
+    FUSG_CHECK(frame && dst && pts_xy && nverts && n_jobs >= 0 && n_planes >= 1 && n_planes <= 8 && (long)n_jobs * n_planes <= 65535,
+               "fill_poly_planes_batch_u8: arguments (1..8 planes, n_jobs * n_planes <= 65535)");
+    if (n_jobs == 0) return FUSG_OK;
+    FUSG_CHECK(is_u8_hwc(*frame, 3) && is_u8_hwc(*dst, 3) && frame->n == 1 && dst->n == (long)n_jobs * n_planes && frame->h == dst->h &&
+               frame->w == dst->w && dst->sw == 3 && dst->sh == 3 * dst->w && dst->sn >= 3 * dst->h * dst->w,
+               "fill_poly_planes_batch_u8: shapes (dst [n_jobs * n_planes] planes of contiguous rows)");
+    const long plane_bytes = 3 * dst->h * dst->w;
+    const long pieces = 1 + (plane_bytes + 15) / 16;
+    const unsigned bx = (unsigned)((pieces + 255) / 256);
+    hipLaunchKernelGGL(fill_poly_planes_batch_kernel, dim3(bx, (unsigned)(n_jobs * n_planes)), dim3(256), 0, (hipStream_t)stream,
+                       u8view(*frame), (const int*)pts_xy, (const int*)nverts, u8view(*dst), plane_bytes);
+    FUSG_LAUNCH_CHECK("fill_poly_planes_batch_u8");
+    return FUSG_OK;
+}
+extern "C" int fusg_fill_poly_planes_batch_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
+                                              int32_t n_planes, const fusg_tensor* dst, void* stream) {
+    return fusg::plan_dispatch(fill_poly_planes_batch_u8_impl, stream, frame, pts_xy, nverts, n_jobs, n_planes, dst);
 }
 
 static int icn_inputs_impl(const fusg_tensor* sketch, const fusg_tensor* central, const fusg_tensor* planes, const int32_t* geom,

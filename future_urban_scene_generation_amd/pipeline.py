@@ -480,20 +480,8 @@ class VehiclePipeline:
         return out
 
     # ------------------------------------------------------------------------------------------ geometry mode
-    def _geometry_checks(self, replay):
-        if replay:
-            raise NotImplementedError("geometry mode (cad_bank, scene without 'masks') runs eagerly: replay=True is not supported")
-        if not _one_rank(self.group):
-            raise NotImplementedError("geometry mode (cad_bank, scene without 'masks') runs on one rank: the pose fit is "
-                                      "rank-0-only in the sharded path")
-
-    @staticmethod
-    def _given_geometry_only(scenes):
-        for scene in scenes:
-            if "masks" not in scene:
-                raise NotImplementedError("geometry mode (cad_bank, scene without 'masks') is not pipelined: call run_frame "
-                                          "per frame")
-            yield scene
+    def _is_geometry(self, scene) -> bool:
+        return "masks" not in scene and self.cad_bank is not None
 
     @staticmethod
     def _select(scene: Dict, keep, keys) -> Dict:
@@ -515,31 +503,33 @@ class VehiclePipeline:
             out["inpaint"] = VehiclePipeline._select(scene["inpaint"], keep, list(scene["inpaint"].keys()))
         return out
 
-    def _geometry_frame(self, scene: Dict, check, replay) -> Dict:
-        """run_frame in geometry mode: scene = 'frame', 'bboxes', 'focals', 'centers' (+ 'cad_idx' [V] when the pipeline has
-        no CAD classifier, optional 'background', 'inpaint', 'vehicle_seeds').  The reference's order (trajectory_inference.py:
-        55-253, warp_learn/vehicle_utils.py:12-32): hourglass -> argmax -> keypoints -> pose fit on the device -> host
-        select_and_flip -> extrinsics; render + plane visibility on the device (render.vehicle_geometry, one D2H of the
-        counts); then the given-geometry path of `run_frame` on the vehicles whose render is not empty.
-        Returns run_frame's keys ('kp_idx', 'kp_xy', 'pose' (+ 'cad_idx') for every vehicle; 'icn_u8', 'vunet_u8', 'geom'
-        (+ 'inpaint_u8') for the rendered ones, in order), 'geometry' = the derived scene keys of every vehicle ('masks',
-        'src_sketch', 'dst_sketch', 'src_planes', 'src_kp', 'dst_kp', 'src_vis', 'dst_vis', 'kp3d', 'cad_idx'), 'skipped' =
-        the vehicles whose render is empty (the reference's `except: continue`, :252-253: no networks, no paste) and
-        'state' for `run_later_frame`."""
+    @classmethod
+    def _kept_planes(cls, geometry: Dict, keep) -> Dict:
+        """The first frame's planes of the kept vehicles, what their later frames warp: 'src_planes', 'src_kp', 'src_vis'."""
+        sel = cls._select(geometry, keep, ("src_planes", "src_kp", "src_vis"))
+        return {k: sel[k] for k in ("src_planes", "src_kp", "src_vis")}
+
+    @torch.no_grad()
+    def _geometry_front(self, scene: Dict, check) -> Dict:
+        """Everything of a geometry-mode first frame before the networks, on the current stream, for the scene's vehicles (all of
+        them, or one rank's shard): hourglass -> argmax -> keypoints -> pose fit on the device -> host select_and_flip ->
+        extrinsics; render + plane visibility + plane cut-outs on the device (render.vehicle_geometry, one D2H of the counts).
+        check: range guard of the keypoint stage (`_guarded`).  Returns 'pre' (device 'kp_idx', 'kp_xy' (+ 'cad_logits')),
+        'raw' (the fit's host arrays rv, tv, er), 'pose', 'cad_idx', 'g' (vehicle_geometry's dict), 'keep' (vehicles whose render
+        is not empty), 'geometry' (the derived scene keys of every vehicle) and 'sub' = the given-geometry scene of the kept
+        vehicles ('_hg': their keypoint indices; '_pose_raw': their rows of this fit, passed through `_frame_finish`)."""
         import numpy as np
 
         from . import frame_ops as fo
         from . import ops
         from . import render as rd
         from .utils.pnp_utils import cpc_fit_device, select_and_flip
-        self._geometry_checks(replay)
         dev, bank = self.device, self.cad_bank
         frame = scene["frame"]
         H, W, _ = frame.shape
         bboxes = np.asarray(scene["bboxes"]).reshape(-1, 4)
         V, R = bboxes.shape[0], 256
 
-        @torch.no_grad()
         def keypoints():
             geom_box = fo.box_geometry((H, W), bboxes, dev)
             hg_x = fo.crop_resize(frame, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD)        # :58-65
@@ -559,12 +549,13 @@ class VehiclePipeline:
                 cad_idx = np.asarray(scene["cad_idx"], np.int64).reshape(V)
             if V:
                 f32 = lambda a: ops.h2d(np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32).reshape(-1, 2), (V, 2))), dev)   # noqa: E731
-                raw = cpc_fit_device(f32(scene["focals"]), f32(scene["centers"]), pre["kp_xy"],
-                                     ops.h2d(bank.kp3d[cad_idx], dev))                                       # :104-105
-                rv, tv, er = (t.cpu().numpy() for t in raw)
-                pose = [select_and_flip(rv[i], tv[i], er[i]) for i in range(V)]
+                raw_d = cpc_fit_device(f32(scene["focals"]), f32(scene["centers"]), pre["kp_xy"],
+                                       ops.h2d(bank.kp3d[cad_idx], dev))                                     # :104-105
+                raw = tuple(t.cpu().numpy() for t in raw_d)
+                pose = [select_and_flip(raw[0][i], raw[1][i], raw[2][i]) for i in range(V)]
                 kp_xy = pre["kp_xy"].cpu().numpy()
             else:
+                raw_d, raw = None, tuple(np.zeros(sh, np.float32) for sh in ((0, 4, 3), (0, 4, 3), (0, 4)))
                 pose, kp_xy = [], np.zeros((0, 12, 2), np.float32)
             K = rd.intrinsic(scene["focals"], scene["centers"])
             g = rd.vehicle_geometry(bank, frame, cad_idx, [(p[1], p[2]) for p in pose], K, kp_xy=kp_xy)
@@ -579,32 +570,138 @@ class VehiclePipeline:
             if self.cad is not None:
                 hg["cad_logits"] = pre["cad_logits"]
             sub["_hg"] = self._select(hg, keep, list(hg))
-        out = self.run_frame(sub, check=check)
+            sub["_pose_raw"] = tuple(t.index_select(0, torch.as_tensor(keep, dtype=torch.long, device=dev)) for t in raw_d)
+        return {"pre": pre, "raw": raw, "pose": pose, "cad_idx": cad_idx, "g": g, "keep": keep, "geometry": geometry, "sub": sub,
+                "V": V, "scene": scene}
+
+    def _geometry_assemble(self, f: Dict, out: Dict) -> Dict:
+        """run_frame's geometry-mode result from `_geometry_front`'s dict and the given-geometry result of the kept vehicles."""
+        V, pre, keep = f["V"], f["pre"], f["keep"]
         out["kp_idx"] = pre["kp_idx"] if V else out["kp_idx"]
         out["kp_xy"] = pre["kp_xy"] if V else out["kp_xy"]
-        out["pose"] = pose
+        out["pose"] = f["pose"]
         if self.cad is not None:
-            out["cad_idx"] = torch.as_tensor(cad_idx, device=dev)
-        out["geometry"] = geometry
+            out["cad_idx"] = torch.as_tensor(f["cad_idx"], device=self.device)
+        out["geometry"] = f["geometry"]
         out["skipped"] = [v for v in range(V) if v not in keep]
         if out.get("state") is not None:
-            out["state"]["geometry"] = {"vehicles": keep, "cad_idx": cad_idx[keep], "pose": [pose[v] for v in keep],
-                                        "focals": scene["focals"], "centers": scene["centers"],
-                                        **self._select(geometry, keep, ("src_planes", "src_kp", "src_vis"))}
+            sc = f["scene"]
+            out["state"]["geometry"] = {"vehicles": keep, "cad_idx": f["cad_idx"][keep], "pose": [f["pose"][v] for v in keep],
+                                        "focals": sc["focals"], "centers": sc["centers"], **self._kept_planes(f["geometry"], keep)}
         return out
 
-    def _geometry_later_frame(self, scene: Dict, state: Dict, check, replay) -> Dict:
-        """run_later_frame in geometry mode: scene = 'frame' (+ 'background', 'vehicle_seeds') and 'steps' = (theta, tr) per
-        vehicle of the first frame (`render.trajectory_steps`).  Each vehicle the first frame rendered is moved (mesh and
-        3-D keypoints by v @ z_rot(theta) + tr, trajectory_inference.py:359-363), rendered at the first frame's extrinsic,
-        its moved keypoints projected with K (:364-367) -> 'dst_sketch', 'masks', 'dst_kp', 'dst_vis'
-        (render.vehicle_geometry); then the given-geometry path of `run_later_frame` for the vehicles whose render is not
-        empty.  Returns its keys (for those vehicles, in order), 'geometry' (the derived keys of every vehicle of the
-        state) and 'skipped' (first-frame vehicle indices: skipped there or rendering empty now - not pasted)."""
+    def _geometry_frame(self, scene: Dict, check, replay) -> Dict:
+        """run_frame in geometry mode: scene = 'frame', 'bboxes', 'focals', 'centers' (+ 'cad_idx' [V] when the pipeline has
+        no CAD classifier, optional 'background', 'inpaint', 'vehicle_seeds', 'shard').  The reference's order (trajectory_inference.py:
+        55-253, warp_learn/vehicle_utils.py:12-32): hourglass -> argmax -> keypoints -> pose fit on the device -> host
+        select_and_flip -> extrinsics; render + plane visibility + plane cut-outs on the device (render.vehicle_geometry, one D2H of
+        the counts); then the given-geometry path of `run_frame` on the vehicles whose render is not empty - replay=True replays its
+        networks as the recorded pass of that many KEPT vehicles (the keypoint stage before the render stays eager).
+        Returns run_frame's keys ('kp_idx', 'kp_xy', 'pose' (+ 'cad_idx') for every vehicle; 'icn_u8', 'vunet_u8', 'geom'
+        (+ 'inpaint_u8') for the rendered ones, in order), 'geometry' = the derived scene keys of every vehicle ('masks',
+        'src_sketch', 'dst_sketch', 'src_planes', 'src_kp', 'dst_kp', 'src_vis', 'dst_vis', 'kp3d', 'cad_idx'), 'skipped' =
+        the vehicles whose render is empty (the reference's `except: continue`, :252-253: no networks, no paste) and
+        'state' for `run_later_frame`.
+
+        With a process group of more than one rank (and scene['shard'] not False) every rank runs its own vehicles
+        shard_range(V, rank, world) end to end - crop, hourglass, pose fit, select_and_flip, render, visibility, cut-outs, networks -
+        and rank 0 receives the crops, keypoint indices and frame keypoints, the fits and the covered counts of every vehicle
+        (`_geometry_frame_sharded`).  Rank 0's 'geometry' then holds only 'cad_idx' and 'kp3d': the per-pixel and per-plane keys
+        ('masks', 'src_sketch', 'dst_sketch', 'src_planes', 'src_kp', 'dst_kp', 'src_vis', 'dst_vis') stay on the ranks that own
+        the vehicles.  Every rank returns a RANK-LOCAL 'state' (its own vehicles' appearance codes, crops and geometry)."""
+        if not _one_rank(self.group) and scene.get("shard", True):
+            return self._geometry_frame_sharded(scene, check, replay)
+        with torch.cuda.device(self.device):
+            f = self._geometry_front(scene, check)
+        return self._geometry_assemble(f, self.run_frame(f["sub"], check=check, replay=replay))
+
+    def _geometry_frame_sharded(self, scene: Dict, check, replay) -> Dict:
+        """One rank's part of a sharded geometry-mode first frame (see `_geometry_frame`).  The range guard of the keypoint
+        stage and of the networks runs before the first collective.  The gathers are `gather_in_order` over the shard_range
+        sizes: a rank's crops and crop rows are spread back to their vehicles' rows of its shard (zeros where the render was
+        empty), so ranks whose kept counts differ still send what the gather expects.  Rank 0 re-renders the masks of the kept
+        vehicles from the gathered fits for its paste instead of gathering them: the render is deterministic
+        per job, and a pose is 28 numbers where a mask is H x W bytes."""
         import numpy as np
+        import torch.distributed as dist
 
         from . import render as rd
-        self._geometry_checks(replay)
+        from .utils.pnp_utils import select_and_flip
+        rng = torch.get_rng_state() if check == "sync" else None
+        dev, bank = self.device, self.cad_bank
+        rank, world = dist.get_rank(self.group), dist.get_world_size(self.group)
+        bboxes = np.asarray(scene["bboxes"]).reshape(-1, 4)
+        V = bboxes.shape[0]
+        lo, hi = shard_range(V, rank, world)
+        n = hi - lo
+        part = slice_scene(scene, lo, hi)
+        if scene.get("cad_idx") is not None:
+            part["cad_idx"] = np.asarray(scene["cad_idx"], np.int64).reshape(V)[lo:hi]
+        with torch.cuda.device(dev):
+            f = self._geometry_front(part, check)
+            local = self._guarded(self._frame_local, (f["sub"], replay), check, rng)
+            keep = f["keep"]
+            kidx = torch.as_tensor(keep, dtype=torch.long, device=dev)
+
+            def spread(t):
+                z = torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+                return z.index_copy_(0, kidx, t) if keep else z
+
+            ints = np.zeros((n, 14), np.int32)
+            flts = np.zeros((n, 52), np.float32)
+            if n:
+                ints[:, :12] = f["pre"]["kp_idx"].cpu().numpy()
+                ints[:, 12] = f["g"]["covered"]
+                ints[:, 13] = f["cad_idx"]
+                flts[:, :24] = f["pre"]["kp_xy"].cpu().numpy().reshape(n, 24)
+                flts[:, 24:36] = f["raw"][0].reshape(n, 12)
+                flts[:, 36:48] = f["raw"][1].reshape(n, 12)
+                flts[:, 48:52] = f["raw"][2].reshape(n, 4)
+            crops = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if self.inpaint else ())
+            got = {k: gather_in_order(spread(local[k]).contiguous(), V, self.group) for k in crops}
+            gi = gather_in_order(torch.from_numpy(ints).to(dev), V, self.group)
+            gf = gather_in_order(torch.from_numpy(flts).to(dev), V, self.group)
+        state = self._local_state(local, (lo, hi, V))
+        state["geometry"] = {"vehicles": [lo + v for v in keep], "cad_idx": f["cad_idx"][keep], "pose": [f["pose"][v] for v in keep],
+                             "focals": scene["focals"], "centers": scene["centers"], **self._kept_planes(f["geometry"], keep)}
+        if rank != 0:
+            return {"state": state}
+        gi, gf = gi.cpu().numpy(), gf.cpu().numpy()
+        cad_all = gi[:, 13].astype(np.int64)
+        rv, tv, er = gf[:, 24:36].reshape(V, 4, 3).copy(), gf[:, 36:48].reshape(V, 4, 3).copy(), gf[:, 48:52].copy()
+        pose = [select_and_flip(rv[v], tv[v], er[v]) for v in range(V)]
+        keep_all = [v for v in range(V) if gi[v, 12] > 0]
+        H, W = int(scene["frame"].shape[0]), int(scene["frame"].shape[1])
+        K = rd.intrinsic(scene["focals"], scene["centers"])
+        with torch.cuda.device(dev):
+            kall = torch.as_tensor(keep_all, dtype=torch.long, device=dev)
+            E = rd.extrinsics_from_poses([(pose[v][1], pose[v][2]) for v in keep_all])
+            masks = rd.render_vehicles(bank, cad_all[keep_all], E, float(K[0, 0]), float(K[1, 1]), (H, W), dev)["mask"]
+            kp_idx = gi[:, :12].copy()
+            full = {k: got[k].to(dev).index_select(0, kall) for k in crops}
+            full["kp_idx"] = torch.from_numpy(kp_idx[keep_all]).to(dev)
+            fin = self._select({**scene, "kp3d": bank.kp3d[cad_all]}, keep_all, ("bboxes", "kp3d", "inpaint"))
+            fin["masks"] = masks
+            fin["_pose_raw"] = tuple(torch.from_numpy(a[keep_all]).to(dev) for a in (rv, tv, er))
+            out = self._frame_finish(fin, full)
+            out.pop("_pose_raw")
+            out["kp_idx"] = torch.from_numpy(kp_idx).to(dev)
+            out["kp_xy"] = torch.from_numpy(gf[:, :24].reshape(V, 12, 2).copy()).to(dev)
+            if self.cad is not None:
+                out["cad_idx"] = torch.as_tensor(cad_all, device=dev)
+        out["pose"] = pose
+        out["geometry"] = {"cad_idx": cad_all, "kp3d": bank.kp3d[cad_all]}
+        out["skipped"] = [v for v in range(V) if v not in keep_all]
+        state["geometry"]["all"] = {"vehicles": keep_all, "cad_idx": cad_all[keep_all], "pose": [pose[v] for v in keep_all]}
+        out["state"] = state
+        return out
+
+    @torch.no_grad()
+    def _geometry_later_front(self, scene: Dict, state: Dict) -> Dict:
+        """The render of a geometry-mode later frame for the vehicles of `state` (all, or one rank's), on the current stream:
+        'g' (vehicle_geometry's dict), 'keep' (state positions whose render is not empty), 'geometry' and the given-geometry
+        'sub' scene / 'sub_state' of the kept vehicles."""
+        from . import render as rd
         gs = state["geometry"]
         veh = list(gs["vehicles"])
         steps = [scene["steps"][v] for v in veh]
@@ -619,12 +716,150 @@ class VehiclePipeline:
         if scene.get("vehicle_seeds") is not None:
             sub["vehicle_seeds"] = [scene["vehicle_seeds"][veh[i]] for i in keep]
         sub.pop("steps", None)
-        sub_state = dict(state, geometry=None, appearance=[self._select({"a": a}, keep, ("a",))["a"] for a in state["appearance"]],
+        sub_state = dict(state, geometry=None, sharded=False,
+                         appearance=[self._select({"a": a}, keep, ("a",))["a"] for a in state["appearance"]],
                          central=self._select({"c": state["central"]}, keep, ("c",))["c"])
-        out = self.run_later_frame(sub, sub_state, check=check)
-        out["geometry"] = geometry
-        out["skipped"] = [v for v in range(len(scene["steps"])) if v not in [veh[i] for i in keep]]
+        return {"g": g, "keep": keep, "veh": veh, "geometry": geometry, "sub": sub, "sub_state": sub_state, "scene": scene}
+
+    @staticmethod
+    def _geometry_later_assemble(f: Dict, out: Dict) -> Dict:
+        out["geometry"] = f["geometry"]
+        kept = [f["veh"][i] for i in f["keep"]]
+        out["skipped"] = [v for v in range(len(f["scene"]["steps"])) if v not in kept]
         return out
+
+    def _geometry_later_frame(self, scene: Dict, state: Dict, check, replay) -> Dict:
+        """run_later_frame in geometry mode: scene = 'frame' (+ 'background', 'vehicle_seeds') and 'steps' = (theta, tr) per
+        vehicle of the first frame (`render.trajectory_steps`).  Each vehicle the first frame rendered is moved (mesh and
+        3-D keypoints by v @ z_rot(theta) + tr, trajectory_inference.py:359-363), rendered at the first frame's extrinsic,
+        its moved keypoints projected with K (:364-367) -> 'dst_sketch', 'masks', 'dst_kp', 'dst_vis'
+        (render.vehicle_geometry); then the given-geometry path of `run_later_frame` for the vehicles whose render is not
+        empty (replay=True: its recorded pass of that many vehicles).  Returns its keys (for those vehicles, in order),
+        'geometry' (the derived keys of every vehicle of the state) and 'skipped' (first-frame vehicle indices: skipped there or
+        rendering empty now - not pasted).  A RANK-LOCAL state of a sharded first frame: see `_geometry_later_sharded`."""
+        if not _one_rank(self.group) and state.get("sharded"):
+            return self._geometry_later_sharded(scene, state, check, replay)
+        f = self._geometry_later_front(scene, state)
+        return self._geometry_later_assemble(f, self.run_later_frame(f["sub"], f["sub_state"], check=check, replay=replay))
+
+    def _geometry_later_sharded(self, scene: Dict, state: Dict, check, replay) -> Optional[Dict]:
+        """A later frame of a sharded geometry-mode clip: every rank moves, renders and runs the vehicles of its own state; the
+        crops, crop rows and covered counts travel to rank 0 over the first frame's shard_range sizes (spread to their vehicles'
+        rows), and rank 0 re-renders the kept vehicles' masks from the poses of its state and the scene's steps and pastes.  Rank 0
+        returns the result ('geometry' holds 'kp3d' of the first frame's rendered vehicles only), the other ranks None."""
+        import numpy as np
+
+        from . import render as rd
+        rng = torch.get_rng_state() if (check == "sync" and scene.get("vehicle_seeds") is None) else None
+        dev = self.device
+        lo, hi, V = state["shard"]
+        n = hi - lo
+        f = self._geometry_later_front(scene, state)
+        with torch.cuda.device(dev):
+            local = self._guarded(self._later_local, (f["sub"], f["sub_state"], replay), check, rng)
+            rows = [f["veh"][i] - lo for i in f["keep"]]
+            ridx = torch.as_tensor(rows, dtype=torch.long, device=dev)
+
+            def spread(t):
+                z = torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+                return z.index_copy_(0, ridx, t) if rows else z
+
+            cov = np.zeros((n, 1), np.int32)
+            for i, v in enumerate(f["veh"]):
+                cov[v - lo, 0] = f["g"]["covered"][i]
+            got = {k: gather_in_order(spread(local[k]).contiguous(), V, self.group) for k in ("icn_u8", "vunet_u8", "geom")}
+            gc = gather_in_order(torch.from_numpy(cov).to(dev), V, self.group)
+        if gc is None:
+            return None
+        gc = gc.cpu().numpy()[:, 0]
+        al = state["geometry"]["all"]
+        keep = [i for i, v in enumerate(al["vehicles"]) if gc[v] > 0]
+        kept = [al["vehicles"][i] for i in keep]
+        gs = state["geometry"]
+        H, W = int(scene["frame"].shape[0]), int(scene["frame"].shape[1])
+        K = rd.intrinsic(gs["focals"], gs["centers"])
+        steps = [scene["steps"][v] for v in kept]
+        Rs = np.stack([rd.z_rot(th) for th, _ in steps]) if kept else np.zeros((0, 3, 3))
+        trs = np.stack([np.asarray(t, np.float64).reshape(3) for _, t in steps]) if kept else np.zeros((0, 3))
+        with torch.cuda.device(dev):
+            E = rd.extrinsics_from_poses([(al["pose"][i][1], al["pose"][i][2]) for i in keep])
+            masks = rd.render_vehicles(self.cad_bank, al["cad_idx"][keep], E, float(K[0, 0]), float(K[1, 1]), (H, W), dev, Rs, trs)["mask"]
+            kidx = torch.as_tensor(kept, dtype=torch.long, device=dev)
+            full = {k: got[k].to(dev).index_select(0, kidx) for k in got}
+            out = self._later_finish({**scene, "masks": masks}, full)
+        cad = al["cad_idx"]
+        out["geometry"] = {"kp3d": np.stack([self.cad_bank.kp3d[int(m)] @ rd.z_rot(scene["steps"][v][0])
+                                             + np.asarray(scene["steps"][v][1], np.float64).reshape(3)
+                                             for m, v in zip(cad, al["vehicles"])]) if len(cad) else np.zeros((0, 12, 3))}
+        out["skipped"] = [v for v in range(len(scene["steps"])) if v not in kept]
+        return out
+
+    # ---- one frame in flight: the geometry stage of frame i+1 on a stream of its own
+    def _scenes_ready(self, scenes):
+        """The event a pipelined geometry stage waits for before it reads its scene: for a list or tuple of scenes (made before
+        the loop started) the caller's stream as it is NOW, so frame i+1's keypoint stage does not queue behind frame i's
+        networks; for any other iterable None (each stage then waits for the caller's stream as it is when the scene is drawn,
+        which is correct for scenes made on the fly and overlaps nothing)."""
+        if self.cad_bank is None or not isinstance(scenes, (list, tuple)) or self.device.type != "cuda":
+            return None
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return ev
+
+    def _issue_geometry_front(self, fn, ready, guarded) -> Dict:
+        """Run fn() (a geometry front: keypoints, pose fit and render with their host read-backs) on the pipeline's geometry
+        stream, ordered after `ready` (or after the caller's stream as it is now), under a status word of its own that is copied
+        to pinned memory and cleared on that stream; the caller's stream then waits for the stage."""
+        from . import ops
+        main = torch.cuda.current_stream(self.device)
+        st = self.__dict__.get("_geo_stream")
+        if st is None:
+            st = self.__dict__["_geo_stream"] = torch.cuda.Stream(device=self.device)
+        if ready is None:
+            ready = torch.cuda.Event()
+            ready.record(main)
+        st.wait_event(ready)
+        pin = None
+        with torch.cuda.stream(st):
+            if guarded:
+                word = self.__dict__.get("_geo_status")
+                if word is None:
+                    word = self.__dict__["_geo_status"] = ops.new_status_word(self.device)
+                with ops.defer_range_check(), ops.status_scope(word):
+                    f = fn()
+                ring = self.__dict__.setdefault("_geo_pins", [])
+                pin = ring.pop() if ring else torch.zeros(1, dtype=torch.int32, pin_memory=True)
+                pin.copy_(word[:1], non_blocking=True)
+                word.zero_()
+            else:
+                f = fn()
+            done = torch.cuda.Event()
+            done.record(st)
+        main.wait_event(done)
+
+        def keep_alive(o):                                        # tensors made on the geometry stream, used on the caller's
+            if torch.is_tensor(o):
+                if o.is_cuda:
+                    o.record_stream(main)
+            elif isinstance(o, dict):
+                for v in o.values():
+                    keep_alive(v)
+            elif isinstance(o, (list, tuple)):
+                for v in o:
+                    keep_alive(v)
+
+        keep_alive({k: v for k, v in f.items() if k != "scene"})
+        f["_pin"] = pin
+        return f
+
+    def _geometry_front_hit(self, f) -> bool:
+        pin = f.get("_pin")
+        if pin is None:
+            return False
+        hit = int(pin[0]) != 0
+        self.__dict__["_geo_pins"].append(pin)
+        f["_pin"] = None
+        return hit
 
     def run_frames(self, scenes, replay: bool = True):
         """`run_frame` over a sequence of frames (the reference's outer loop, trajectory_inference.py:283-300), software-
@@ -633,10 +868,13 @@ class VehiclePipeline:
         and raw pose come back through pinned buffers filled by stream-ordered copies and one event, so reading them
         waits for frame i only.  A generator: yields one `run_frame`-shaped dict per scene, in order; every tensor in it
         is the caller's (nothing aliases a later frame's buffers).  A frame whose split-fp16 range status is raised is
-        redone in exact fp32 before it is yielded, with the RNG state it was issued under."""
-        import torch.distributed as dist
-        if self.cad_bank is not None:
-            scenes = self._given_geometry_only(scenes)
+        redone in exact fp32 before it is yielded, with the RNG state it was issued under.
+        Geometry-mode scenes (a pipeline with cad_bank, no 'masks') are pipelined the same way on one rank: frame i+1's keypoint
+        stage, pose fit, render and their two host read-backs run on a stream of the pipeline's own (`_issue_geometry_front`), so
+        they do not wait for frame i's networks, which frame i+1's then follow on the caller's stream; a raised status of either
+        stage redoes the frame whole, geometry included.  For a list or tuple of scenes the geometry stage is ordered after what the
+        caller's stream held when the loop began; for another iterable, after what it holds when each scene is drawn.  Sharded
+        (process group), geometry scenes run frame by frame (`run_frame`)."""
         if not _one_rank(self.group):
             # sharded frames, one frame deep as well: every rank issues its shard of frame i+1 before frame i's crops are
             # gathered; the gather and rank 0's frame-level part run on a communication stream that waits for frame i's
@@ -644,7 +882,7 @@ class VehiclePipeline:
             # other ranks: {'state': ...}); a scene with shard = False is not pipelined.
             pending = None
             for scene in scenes:
-                if not scene.get("shard", True):
+                if not scene.get("shard", True) or self._is_geometry(scene):
                     if pending is not None:
                         yield self._collect_sharded(pending)
                         pending = None
@@ -658,25 +896,32 @@ class VehiclePipeline:
                 yield self._collect_sharded(pending)
             return
         pending = None
+        ready = self._scenes_ready(scenes)
         for scene in scenes:
-            ticket = self._issue_frame(scene, replay)
+            ticket = self._issue_frame(scene, replay, ready)
             if pending is not None:
                 yield self._collect_frame(pending)
             pending = ticket
         if pending is not None:
             yield self._collect_frame(pending)
 
-    def _issue_frame(self, scene, replay):
+    def _issue_frame(self, scene, replay, ready=None):
         from . import ops
         guarded = ops.range_guarded()
         rng = torch.get_rng_state() if (guarded and scene.get("vehicle_seeds") is None) else None
         word = self.status_word() if guarded else None
+        front = None
         with torch.cuda.device(self.device):
+            if self._is_geometry(scene):                         # keypoints -> pose -> render on the geometry stream first
+                front = self._issue_geometry_front(lambda: self._geometry_front(scene, None), ready, guarded)
+                scene_nets = front["sub"]
+            else:
+                scene_nets = scene
             if guarded:
                 with ops.defer_range_check(), ops.status_scope(word):
-                    out = self._run_frame(scene, replay)
+                    out = self._run_frame(scene_nets, replay)
             else:
-                out = self._run_frame(scene, replay)
+                out = self._run_frame(scene_nets, replay)
             # stream-ordered read-back: the three raw pose arrays and the status word into pinned memory, the word cleared
             # for the next frame (whose launches queue behind these copies), one event to wait on
             ring = self.__dict__.setdefault("_frame_pins", [])
@@ -691,14 +936,17 @@ class VehiclePipeline:
                 word.zero_()
             ev = torch.cuda.Event()
             ev.record()
-        return {"out": out, "pins": pins, "event": ev, "scene": scene, "replay": replay, "rng": rng, "guarded": guarded}
+        return {"out": out, "pins": pins, "event": ev, "scene": scene, "replay": replay, "rng": rng, "guarded": guarded, "front": front}
 
     def _collect_frame(self, t):
         from . import ops
         from .utils.pnp_utils import select_and_flip
         t["event"].synchronize()
         (rv, tv, er), status = t["pins"]
-        if t["guarded"] and int(status[0]) != 0:                  # rare: this frame again, in exact fp32
+        front = t["front"]
+        geo_hit = front is not None and self._geometry_front_hit(front)
+        hit = t["guarded"] and (int(status[0]) != 0 or geo_hit)
+        if hit:                                                   # rare: this frame again (geometry included), in exact fp32
             cur = torch.get_rng_state()
             if t["rng"] is not None:
                 torch.set_rng_state(t["rng"])
@@ -711,6 +959,8 @@ class VehiclePipeline:
         out = t["out"]
         rv, tv, er = rv.numpy().copy(), tv.numpy().copy(), er.numpy().copy()
         self.__dict__["_frame_pins"].append(t["pins"])
+        if front is not None:                                     # the pose of the geometry stage (the same fit, passed through)
+            return self._geometry_assemble(front, out)
         out["pose"] = [select_and_flip(rv[i], tv[i], er[i]) for i in range(rv.shape[0])]
         return out
 
@@ -848,7 +1098,8 @@ class VehiclePipeline:
                 return out
             replay = replay and ops.RECORDER is None
             cps = self.__dict__.setdefault("_frame_plans", {})
-            cp = cps.get((V, ops.PRECISION)) if replay else None
+            pkey = (V, ops.PRECISION) + (("kp_given",) if scene.get("_hg") is not None else ())
+            cp = cps.get(pkey) if replay else None
             if cp is not None and [n.generation for n in self._nets] != cp.generations:
                 cp = None
             tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
@@ -874,12 +1125,12 @@ class VehiclePipeline:
                 if cp is None:
                     # one recorded pass (with its private pool of intermediates) per vehicle count; a video whose count varies
                     # keeps the FRAME_PLANS most recently used ones
-                    cps.pop((V, ops.PRECISION), None)
+                    cps.pop(pkey, None)
                     while len(cps) >= FRAME_PLANS:
                         cps.pop(next(iter(cps)))
-                    cp = cps[(V, ops.PRECISION)] = CompiledPass(self, nets_in, seeds)
+                    cp = cps[pkey] = CompiledPass(self, nets_in, seeds)
                 else:
-                    cps[(V, ops.PRECISION)] = cps.pop((V, ops.PRECISION))     # most recently used last
+                    cps[pkey] = cps.pop(pkey)                 # most recently used last
                 out = dict(cp._issue(nets_in, seeds))
                 for k in ("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"):    # the plan's buffers belong to its next replay
                     if k in out:
@@ -918,13 +1169,18 @@ class VehiclePipeline:
                 out["frame_icn"], out["frame_vunet"] = back.clone(), back.clone()
                 return out
             f32 = lambda a: ops.h2d(np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32).reshape(-1, 2), (V, 2))), dev)   # noqa: E731
-            if self.cad is not None and scene.get("kp3d_bank") is not None:                    # :82-88: the chosen CAD model's keypoints
+            if scene.get("_pose_raw") is not None:
+                kp3d = None
+            elif self.cad is not None and scene.get("kp3d_bank") is not None:                  # :82-88: the chosen CAD model's keypoints
                 kp3d = ops.h2d(np.asarray(scene["kp3d_bank"], np.float32), dev)[out["cad_idx"]]
             else:
                 kp3d = ops.h2d(np.asarray(scene["kp3d"], np.float32), dev)
             geom_box = fo.box_geometry((H, W), bboxes, dev)
             out["kp_xy"] = fo.keypoints_to_frame(out["kp_idx"], geom_box, (R // 4, R // 4))   # :95-97 (64 x 64 heat-maps)
-            out["_pose_raw"] = cpc_fit_device(f32(scene["focals"]), f32(scene["centers"]), out["kp_xy"], kp3d)   # :104-105
+            if scene.get("_pose_raw") is not None:               # geometry mode: the pose was fitted before the render
+                out["_pose_raw"] = scene["_pose_raw"]
+            else:
+                out["_pose_raw"] = cpc_fit_device(f32(scene["focals"]), f32(scene["centers"]), out["kp_xy"], kp3d)   # :104-105
             box = {}
             if inp is not None:
                 rows = [[int(b[0]), int(b[1]), int(b[2]), int(b[3]), 0, 0, 0, 0] for b in np.asarray(inp["boxes"]).reshape(-1, 4)]
@@ -1055,23 +1311,32 @@ class VehiclePipeline:
         is issued - its homographies fitted on the host, its launches queued - before frame i's range status is read back (pinned,
         one event per frame), so the host part of a later frame (1 ms of homography fits) and the read-back overlap the previous
         frame's networks.  A generator: one `run_later_frame`-shaped dict per scene, in order; a frame whose status is raised is
-        redone in exact fp32 before it is yielded.  A sharded state (process group) is not pipelined: frame by frame."""
+        redone in exact fp32 before it is yielded.  The state of a geometry-mode first frame (scenes with 'steps', no 'masks') is
+        pipelined the same way, its render and covered-count read-back on the pipeline's geometry stream.  A sharded state
+        (process group, geometry mode included) is not pipelined: frame by frame."""
         from . import ops
         if not _one_rank(self.group) and state.get("sharded"):
             for sc in scenes:
                 yield self.run_later_frame(sc, state, replay=replay)
             return
         pending = None
+        ready = self._scenes_ready(scenes)
         for scene in scenes:
             guarded = ops.range_guarded()
             rng = torch.get_rng_state() if (guarded and scene.get("vehicle_seeds") is None) else None
             word = self.status_word() if guarded else None
+            front = None
             with torch.cuda.device(self.device):
+                if "masks" not in scene and state.get("geometry") is not None:     # the render on the geometry stream first
+                    front = self._issue_geometry_front(lambda: self._geometry_later_front(scene, state), ready, guarded)
+                    scene_nets, state_nets = front["sub"], front["sub_state"]
+                else:
+                    scene_nets, state_nets = scene, state
                 if guarded:
                     with ops.defer_range_check(), ops.status_scope(word):
-                        out = self._run_later_frame(scene, state, replay)
+                        out = self._run_later_frame(scene_nets, state_nets, replay)
                 else:
-                    out = self._run_later_frame(scene, state, replay)
+                    out = self._run_later_frame(scene_nets, state_nets, replay)
                 ring = self.__dict__.setdefault("_later_pins", [])
                 pin = ring.pop() if ring else torch.zeros(1, dtype=torch.int32, pin_memory=True)
                 if guarded:
@@ -1079,7 +1344,7 @@ class VehiclePipeline:
                     word.zero_()
                 ev = torch.cuda.Event()
                 ev.record()
-            ticket = {"out": out, "pin": pin, "event": ev, "scene": scene, "rng": rng, "guarded": guarded}
+            ticket = {"out": out, "pin": pin, "event": ev, "scene": scene, "rng": rng, "guarded": guarded, "front": front}
             if pending is not None:
                 yield self._collect_later(pending, state)
             pending = ticket
@@ -1089,10 +1354,12 @@ class VehiclePipeline:
     def _collect_later(self, t, state):
         from . import ops
         t["event"].synchronize()
-        hit = t["guarded"] and int(t["pin"][0]) != 0
+        front = t["front"]
+        geo_hit = front is not None and self._geometry_front_hit(front)
+        hit = t["guarded"] and (int(t["pin"][0]) != 0 or geo_hit)
         self.__dict__["_later_pins"].append(t["pin"])
         if not hit:
-            return t["out"]
+            return t["out"] if front is None else self._geometry_later_assemble(front, t["out"])
         cur = torch.get_rng_state()                                # rare: this frame again, in exact fp32
         if t["rng"] is not None:
             torch.set_rng_state(t["rng"])
@@ -1105,7 +1372,8 @@ class VehiclePipeline:
     def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False):
         """A vehicle clip the reference's way (trajectory_inference.py:55-250 then :267-450): the first frame through
         `run_frame`, every future frame through `run_later_frame` with the first frame's state.  Generator of 1 + len(later_scenes)
-        results.  Under a process group the whole clip is sharded by vehicle: a vehicle's six frames stay on one rank."""
+        results.  Under a process group the whole clip is sharded by vehicle: a vehicle's six frames stay on one rank (frame by
+        frame).  A geometry-mode clip (cad_bank, scenes without 'masks') goes through the same drivers."""
         first = self.run_frame(first_scene, replay=replay)
         state = first["state"]
         yield first if len(first) > 1 else None

@@ -213,17 +213,19 @@ def render_jobs(bank: CadBank, mesh_idx: Sequence[int], E: Sequence[np.ndarray],
     H, W = frame_hw
     J = len(mesh_idx)
     jobs = np.zeros(J, JOB_DTYPE)
-    for j, m in enumerate(mesh_idx):
-        m = int(m)
-        if not 0 <= m < len(bank):
-            raise IndexError(f"render: mesh {m} not in a bank of {len(bank)}")
-        jobs[j]["R"] = (np.eye(3) if R is None else np.asarray(R[j], np.float64)).reshape(9)
-        jobs[j]["tr"] = np.zeros(3) if tr is None else np.asarray(tr[j], np.float64).reshape(3)
-        jobs[j]["E"] = np.asarray(E[j], np.float64)[:3, :4].reshape(12)
-        jobs[j]["fx"], jobs[j]["fy"] = fx, fy
-        jobs[j]["cx"], jobs[j]["cy"] = W / 2 - 0.5, H / 2 - 0.5    # render_open3d.py:20: Open3D's, not K's
-        jobs[j]["v_off"], jobs[j]["nv"] = bank.v_off[m], len(bank.vertices[m])
-        jobs[j]["t_off"], jobs[j]["nt"] = bank.t_off[m], len(bank.triangles[m])
+    if J == 0:
+        return jobs
+    m = np.asarray(mesh_idx, np.int64).reshape(J)
+    bad = (m < 0) | (m >= len(bank))
+    if bad.any():
+        raise IndexError(f"render: mesh {int(m[bad][0])} not in a bank of {len(bank)}")
+    jobs["R"] = np.broadcast_to(np.eye(3).reshape(9), (J, 9)) if R is None else np.asarray(R, np.float64).reshape(J, 9)
+    jobs["tr"] = 0.0 if tr is None else np.asarray(tr, np.float64).reshape(J, 3)
+    jobs["E"] = np.asarray(E, np.float64).reshape(J, -1, 4)[:, :3, :4].reshape(J, 12)
+    jobs["fx"], jobs["fy"] = fx, fy
+    jobs["cx"], jobs["cy"] = W / 2 - 0.5, H / 2 - 0.5              # render_open3d.py:20: Open3D's, not K's
+    jobs["v_off"], jobs["nv"] = bank.v_off[m], np.diff(bank.v_off)[m]
+    jobs["t_off"], jobs["nt"] = bank.t_off[m], np.diff(bank.t_off)[m]
     return jobs
 
 
@@ -340,6 +342,118 @@ def intrinsic(focals, centers) -> np.ndarray:
     return np.array([[f[0], 0.0, c[0]], [0.0, f[1], c[1]], [0.0, 0.0, 1.0]])
 
 
+# ---------------------------------------------------------------------------------------------- the same, V vehicles at once
+# Vectorised forms of the per-vehicle functions above, equal to them bit for bit (tests/test_geometry_batch_cpu.py).  Every
+# elementwise step is the same IEEE operation in the same order; the matrix products are numpy matmuls of the same per-slice
+# shapes and layouts (one BLAS call per slice either way), np.linalg.inv is the same LAPACK solve per matrix, and the means and
+# norms reduce over <= 6 contiguous terms, which numpy sums in order.  Two pieces stay per vehicle: the norm of a rotation
+# vector (np.linalg.norm of a 1-D array is a BLAS dot) and the cos / sin of its angle (a scalar call may round differently
+# from an array one), both as `rodrigues` takes them.
+_VIS_IDX = [[KP_NAMES.index(k) for k in names] for names in VIS_PLANES.values()]
+_TEX_IDX = [[KP_NAMES.index(k) for k in names] for names in pu.CAR_TEXTURE_PLANES.values()]
+_CLIP_PX = 1048576.0
+
+
+def rotations(rvecs) -> np.ndarray:
+    """`rodrigues` of V rotation vectors: [V, 3] (any float dtype) -> float64 [V, 3, 3]."""
+    r = np.asarray(rvecs, np.float64).reshape(-1, 3)
+    V = r.shape[0]
+    th = np.array([float(np.linalg.norm(r[v])) for v in range(V)], np.float64)
+    cs = np.array([[np.cos(float(t)), np.sin(float(t))] for t in th], np.float64).reshape(V, 2)
+    small = th < 2.220446049250313e-16
+    u = r / np.where(small, 1.0, th)[:, None]
+    z = np.zeros(V)
+    skew = np.stack([z, -u[:, 2], u[:, 1], u[:, 2], z, -u[:, 0], -u[:, 1], u[:, 0], z], 1).reshape(V, 3, 3)
+    c, sn = cs[:, 0, None, None], cs[:, 1, None, None]
+    Rm = c * np.eye(3) + (1.0 - c) * (u[:, :, None] * u[:, None, :]) + sn * skew
+    Rm[small] = np.eye(3)
+    return Rm
+
+
+def extrinsics_from_poses(poses: Sequence[Tuple[np.ndarray, np.ndarray]], Rm: Optional[np.ndarray] = None) -> np.ndarray:
+    """`extrinsic_from_pose` of V poses (rvec, tvec): [V, 4, 4] in the vectors' dtype; Rm = `rotations` of the rvecs if known."""
+    V = len(poses)
+    if V == 0:
+        return np.zeros((0, 4, 4), np.float32)
+    dts = {np.asarray(r).dtype for r, _ in poses}
+    if len(dts) > 1:
+        return np.stack([extrinsic_from_pose(r, t) for r, t in poses])
+    dt = dts.pop()
+    E = np.zeros((V, 4, 4), dt)
+    E[:] = np.eye(4, dtype=dt)
+    E[:, :3, :3] = rotations([np.asarray(r).reshape(3) for r, _ in poses]) if Rm is None else Rm
+    E[:, :3, 3] = np.stack([np.asarray(t).reshape(3) for _, t in poses])
+    return E
+
+
+def visibility_inputs_batch(kp3d: np.ndarray, E: np.ndarray, K: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`visibility_inputs` of V vehicles: kp3d [V, 12, 3], E [V, 4, 4], K 3x3 -> pts int32 [V, 7, 8, 2], nv int32 [V, 7],
+    nearer int32 [V, 7].  (A keypoint that projects to NaN - the per-vehicle int() raises there - gives INT32_MIN.)"""
+    kp = np.asarray(kp3d)
+    E = np.asarray(E)
+    V = kp.shape[0]
+    pts = np.zeros((V, 7, pu.MAX_VERTS, 2), np.int32)
+    nv = np.zeros((V, 7), np.int32)
+    nearer = np.zeros((V, 7), np.int32)
+    if V == 0:
+        return pts, nv, nearer
+    cam = np.linalg.inv(E)[:, :3, -1]                                                  # [V, 3]
+    mean = np.stack([np.mean(kp[:, idx], axis=1) for idx in _VIS_IDX], 1)             # [V, 7, 3]
+    dist = np.linalg.norm(cam[:, None, :] - mean, axis=2)                              # [V, 7]
+    ph = np.concatenate([kp, np.ones(kp.shape[:2] + (1,))], 2)[..., None]            # [V, 12, 4, 1]
+    q = (np.asarray(K) @ E[:, :3, :])[:, None] @ ph                                    # [V, 12, 3, 1]
+    q /= q[:, :, 2:3, :]
+    k2 = q[:, :, :2, 0]                                                                # [V, 12, 2]
+    with np.errstate(invalid="ignore"):
+        k2i = np.clip(k2, -_CLIP_PX, _CLIP_PX).astype(np.int32)
+    for i, idx in enumerate(_VIS_IDX):
+        pts[:, i, :len(idx)] = k2i[:, idx]
+        nv[:, i] = len(idx)
+        nearer[:, i] = sum((dist[:, q_] < dist[:, i]).astype(np.int32) << q_ for q_ in range(7))
+    return pts, nv, nearer
+
+
+def plane_corners_batch(kp_xy: np.ndarray, frame_hw: Tuple[int, int]) -> List[np.ndarray]:
+    """`plane_corners` of V vehicles: kp_xy [V, 12, 2] -> per texture plane int32 [V, n, 2] (`corner_lists` gives the
+    per-vehicle lists)."""
+    H, W = frame_hw
+    k = np.array(kp_xy, np.float64).reshape(-1, len(KP_NAMES), 2)
+    k[..., 0] /= W
+    k[..., 1] /= H
+    out = []
+    for idx in _TEX_IDX:
+        p = k[:, idx]
+        p[..., 0] *= W
+        p[..., 1] *= H
+        out.append(np.int32(p))
+    return out
+
+
+def corner_lists(planes: Sequence[np.ndarray]) -> List[List[np.ndarray]]:
+    """Per texture plane [V, n, 2] -> per vehicle, per plane [n, 2] (the scene keys' form)."""
+    V = planes[0].shape[0] if planes else 0
+    return [[p[v] for p in planes] for v in range(V)]
+
+
+def corner_arrays(planes: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+    """Per texture plane [V, n, 2] -> the polygons of fusg_fill_poly_planes_batch_u8: pts int32 [V, P, 8, 2], nv int32 [V, P]."""
+    V, P = planes[0].shape[0], len(planes)
+    pts = np.zeros((V, P, pu.MAX_VERTS, 2), np.int32)
+    nv = np.zeros((V, P), np.int32)
+    for i, p in enumerate(planes):
+        pts[:, i, :p.shape[1]] = p
+        nv[:, i] = p.shape[1]
+    return pts, nv
+
+
+def project_keypoints_batch(kp3d: np.ndarray, Rm: np.ndarray, tvecs: np.ndarray, K: np.ndarray) -> np.ndarray:
+    """`project_keypoints` of V vehicles: kp3d [V, n, 3], Rm = `rotations` of the rvecs [V, 3, 3], tvecs [V, 3] -> [V, n, 2]."""
+    X = np.asarray(kp3d, np.float64)
+    pc = X @ np.asarray(Rm).transpose(0, 2, 1) + np.asarray(tvecs, np.float64).reshape(-1, 1, 3)
+    K = np.asarray(K, np.float64)
+    return np.stack([K[0, 0] * (pc[..., 0] / pc[..., 2]) + K[0, 2], K[1, 1] * (pc[..., 1] / pc[..., 2]) + K[1, 2]], -1)
+
+
 def vehicle_geometry(bank: CadBank, frame: torch.Tensor, mesh_idx: Sequence[int], poses: Sequence[Tuple[np.ndarray, np.ndarray]],
                      K: np.ndarray, kp_xy: Optional[np.ndarray] = None, steps: Optional[Sequence[Tuple[float, np.ndarray]]] = None
                      ) -> Dict:
@@ -359,28 +473,47 @@ def vehicle_geometry(bank: CadBank, frame: torch.Tensor, mesh_idx: Sequence[int]
     H, W = int(frame.shape[0]), int(frame.shape[1])
     dev = frame.device
     V = len(mesh_idx)
-    E = [extrinsic_from_pose(r, t) for r, t in poses]
+    mesh = np.asarray(mesh_idx, np.int64).reshape(V)
+    Rm = rotations([np.asarray(r).reshape(3) for r, _ in poses])
+    E = extrinsics_from_poses(poses, Rm)
     if steps is None:
         Rs, trs = None, None
-        kp3d = [bank.kp3d[int(m)] for m in mesh_idx]
+        kp3d = bank.kp3d[mesh]
     else:
-        Rs = [z_rot(th) for th, _ in steps]
-        trs = [np.asarray(t, np.float64).reshape(3) for _, t in steps]
-        kp3d = [bank.kp3d[int(m)] @ Rs[v] + trs[v] for v, m in enumerate(mesh_idx)]     # :360-362
-    with torch.cuda.device(dev):
-        r = render_vehicles(bank, mesh_idx, E, float(K[0, 0]), float(K[1, 1]), (H, W), dev, Rs, trs)
-        counts = plane_visibility(kp3d, E, K, (H, W), dev)
-        host = torch.cat([counts.view(V, 14), r["covered"].view(V, 1)], 1).cpu().numpy()
-    vis = visible(host[:, :14].reshape(V, 7, 2))[:, :len(TEXTURE_PLANES)].astype(np.uint8)
-    out = {"masks": r["mask"], "covered": host[:, 14].astype(np.int64), "kp3d": np.stack(kp3d) if V else np.zeros((0, 12, 3)),
-           "extrinsic": np.stack(E) if V else np.zeros((0, 4, 4), np.float32), "counts": host[:, :14].reshape(V, 7, 2)}
+        Rs = np.stack([z_rot(th) for th, _ in steps]) if V else np.zeros((0, 3, 3))
+        trs = np.stack([np.asarray(t, np.float64).reshape(3) for _, t in steps]) if V else np.zeros((0, 3))
+        kp3d = bank.kp3d[mesh] @ Rs + trs[:, None, :]                                  # :360-362
     if steps is None:
-        kp = [plane_corners(kp_xy[v], (H, W)) for v in range(V)]
-        planes = torch.stack([pu.fill_planes(frame, kp[v]) for v in range(V)]) if V else \
-            torch.zeros((0, len(TEXTURE_PLANES), H, W, 3), dtype=torch.uint8, device=dev)
+        corners = plane_corners_batch(kp_xy, (H, W)) if V else []
+    else:
+        tv = np.stack([np.asarray(t, np.float64).reshape(3) for _, t in poses]) if V else np.zeros((0, 3))
+        corners = plane_corners_batch(project_keypoints_batch(kp3d, Rm, tv, K), (H, W)) if V else []
+    kp = corner_lists(corners) if V else []
+    with torch.cuda.device(dev):
+        r = render_vehicles(bank, mesh, E, float(K[0, 0]), float(K[1, 1]), (H, W), dev, Rs, trs)
+        counts = torch.zeros((V, 7, 2), dtype=torch.int32, device=dev)
+        planes = torch.empty((V, len(TEXTURE_PLANES), H, W, 3), dtype=torch.uint8, device=dev)
+        if V:
+            # one H2D of every polygon of the frame: the visibility planes, then (first frame) the texture planes
+            vpts, vnv, near = visibility_inputs_batch(kp3d, E, K)
+            parts = [vpts.reshape(-1), vnv.reshape(-1), near.reshape(-1)]
+            if steps is None:
+                fpts, fnv = corner_arrays(corners)
+                parts += [fpts.reshape(-1), fnv.reshape(-1)]
+            buf = ops.h2d(np.concatenate(parts), dev)
+            off = np.cumsum([0] + [len(a) for a in parts])
+            seg = [buf[off[i]:off[i + 1]] for i in range(len(parts))]
+            L.check(L.lib().fusg_plane_visibility(seg[0].data_ptr(), seg[1].data_ptr(), seg[2].data_ptr(), V, H, W,
+                                                  counts.data_ptr(), ops.stream_ptr()), "plane_visibility")
+        host = torch.cat([counts.view(V, 14), r["covered"].view(V, 1)], 1).cpu().numpy()
+        if V and steps is None:                                   # queued after the read-back: it does not wait for the planes
+            pu.fill_planes_batch(frame, seg[3], seg[4], planes)
+    vis = visible(host[:, :14].reshape(V, 7, 2))[:, :len(TEXTURE_PLANES)].astype(np.uint8)
+    out = {"masks": r["mask"], "covered": host[:, 14].astype(np.int64), "kp3d": kp3d if V else np.zeros((0, 12, 3)),
+           "extrinsic": E, "counts": host[:, :14].reshape(V, 7, 2)}
+    if steps is None:
         out.update(src_sketch=r["sketch"], dst_sketch=r["sketch"], src_planes=planes, src_kp=kp, dst_kp=kp, src_vis=vis, dst_vis=vis)
     else:
-        kp = [plane_corners(project_keypoints(kp3d[v], *poses[v], K), (H, W)) for v in range(V)]
         out.update(dst_sketch=r["sketch"], dst_kp=kp, dst_vis=vis)
     return out
 

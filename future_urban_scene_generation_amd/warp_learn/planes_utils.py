@@ -271,6 +271,24 @@ def fill_planes(image: torch.Tensor, polygons: Sequence[np.ndarray]) -> torch.Te
     return out
 
 
+def fill_planes_batch(image: torch.Tensor, pts: torch.Tensor, nverts: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """`fill_planes` for V vehicles in one launch (fusg_fill_poly_planes_batch_u8): image [H, W, 3] CUDA uint8, pts DEVICE
+    int32 [V, P, 8, 2] (or flat), nverts DEVICE int32 [V, P] (or flat), out uint8 [V, P, H, W, 3] (written, returned)."""
+    V, P, H, W, _ = out.shape
+    if out.dtype != torch.uint8 or not out.is_contiguous() or tuple(image.shape) != (H, W, 3):
+        raise ValueError("fill_planes_batch: out must be a contiguous uint8 [V, P, H, W, 3] of the image's size")
+    if pts.dtype != torch.int32 or nverts.dtype != torch.int32 or not (pts.is_contiguous() and nverts.is_contiguous()) or \
+            pts.numel() != V * P * MAX_VERTS * 2 or nverts.numel() != V * P:
+        raise ValueError("fill_planes_batch: pts int32 [V, P, 8, 2] and nverts int32 [V, P], contiguous")
+    if V == 0:
+        return out
+    with torch.cuda.device(image.device):
+        L.check(L.lib().fusg_fill_poly_planes_batch_u8(C.byref(_u8desc(image[None])), pts.data_ptr(), nverts.data_ptr(), V, P,
+                                                       C.byref(_u8desc(out.view(V * P, H, W, 3))), ops.stream_ptr()),
+                "fill_poly_planes_batch_u8")
+    return out
+
+
 def get_planes(image: Image, src_kpoint_dict, pascal_class: str, planes_visibility):
     """Reference signature (planes_utils.py:11-37): (planes [P, H, W, 3], polygon list, visibilities uint8 [P])."""
     img, as_np = _to_dev(image)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FUSG_VERSION 117
+#define FUSG_VERSION 118
 
 typedef enum fusg_status {
     FUSG_OK = 0,
@@ -366,6 +366,12 @@ int fusg_warp_perspective_indexed_u8(const fusg_tensor* src, const double* minv,
  * to 8 int32 vertices.  pts_xy [nplanes][8][2] (x, y) and nverts [nplanes] are HOST arrays (read before return). */
 int fusg_fill_poly_planes_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t nplanes,
                              const fusg_tensor* dst, void* stream);
+/* get_planes for n_jobs vehicles in one launch: dst[j * n_planes + p] = frame * fillPoly(polygon (j, p)), the bytes of
+ * fusg_fill_poly_planes_u8 called once per job.  pts_xy = DEVICE int32 [n_jobs, n_planes, 8, 2] (x, y), nverts = DEVICE
+ * int32 [n_jobs, n_planes] (<= 8), n_planes 1..8, n_jobs * n_planes <= 65535; frame uint8 [h, w, 3]; dst uint8
+ * [n_jobs * n_planes, h, w, 3] with contiguous rows (sw = 3, sh = 3w).  n_jobs = 0 is a no-op. */
+int fusg_fill_poly_planes_batch_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
+                                   int32_t n_planes, const fusg_tensor* dst, void* stream);
 /* get_icn_inputs (warp_learn/models.py:323-366) for a batch of B vehicles: sketch [B] (RGB), central [B] (RGB, already
  * dst.h x dst.w), planes [B * P] (BGR, P <= 6, same frame size as sketch); geom = DEVICE int32 [B][8] =
  * (x0, y0, x1, y1, pad_x_before, pad_y_before, pad_x_after, pad_y_after) of square_crop_from_bbox
