@@ -144,6 +144,33 @@ def slice_scene(scene: Dict, lo: int, hi: int) -> Dict:
     return out
 
 
+def _tensors(o):
+    """Every tensor inside a nested dict / list / tuple, depth first."""
+    if torch.is_tensor(o):
+        yield o
+    elif isinstance(o, dict):
+        for v in o.values():
+            yield from _tensors(v)
+    elif isinstance(o, (list, tuple)):
+        for v in o:
+            yield from _tensors(v)
+
+
+def _redo_f32(fn, rng_state=None, restore: bool = False):
+    """fn() again in exact fp32, after a pass whose split-fp16 range status came back raised: under `rng_state` (the host
+    RNG state the pass was first issued under; None: it draws no global noise).  restore=True puts the RNG state of NOW back
+    afterwards - the pipelined drivers, whose next frame has already drawn its noise."""
+    from . import ops
+    cur = torch.get_rng_state() if (restore and rng_state is not None) else None
+    if rng_state is not None:
+        torch.set_rng_state(rng_state)
+    with ops.defer_range_check(), ops.precision("f32"):
+        out = fn()
+    if cur is not None:
+        torch.set_rng_state(cur)
+    return out
+
+
 class VehiclePipeline:
     """Holds the five networks on one device and runs batches of crops through them."""
 
@@ -204,6 +231,12 @@ class VehiclePipeline:
         # the FusedNets whose packed-weight caches a recorded pass points into (EdgeModel / InpaintingModel wrap theirs)
         self._nets = [getattr(n, "generator", n) for n in nets]
         self._status = None                       # this pipeline's own range-status word (ops.status_scope), made on first use
+        # made on first use: the branch streams of `_branches`; the geometry stage's stream and status word; the sharded
+        # drivers' communication stream
+        self._streams, self._geo_stream, self._geo_status, self._comm_stream = {}, None, None, None
+        self._pins = []                           # free pinned int32 status words of the in-flight stages (`_issue_guarded`)
+        self._frame_pins = []                     # free pinned triples for a frame's raw pose arrays (`_issue_frame`)
+        self._frame_plans = {}                    # recorded passes of the frame drivers, least recently used first (`_replay`)
 
     # The networks of one crop pass do not depend on each other (hourglass / ICN / VUnet; edge -> inpaint is one
     # chain), so each branch runs on its own HIP stream: the many small, latency-bound launches of the hourglass
@@ -224,7 +257,7 @@ class VehiclePipeline:
         from . import ops
         rec = ops.RECORDER                                  # recording a fusg_plan: dependencies go through it
         main = torch.cuda.current_stream(self.device)
-        pool = self.__dict__.setdefault("_streams", {})
+        pool = self._streams
         streams = []
         for name, _ in jobs[1:]:
             st = pool.get(name)
@@ -272,15 +305,7 @@ class VehiclePipeline:
         ops.fork_to(st)
         with torch.cuda.stream(st):
             res = fn()
-
-        def tensors(o):
-            if torch.is_tensor(o):
-                yield o
-            elif isinstance(o, (list, tuple)):
-                for q in o:
-                    yield from tensors(q)
-
-        return res, (lambda: ops.join_from(st, list(tensors(res))))
+        return res, (lambda: ops.join_from(st, list(_tensors(res))))
 
     def compile(self, batch: Dict[str, torch.Tensor], vehicle_seeds: Optional[Sequence[int]] = None, fn=None) -> "CompiledPass":
         """Record one crop pass for inputs of `batch`'s shapes into a fusg_plan and return the object that replays it:
@@ -339,15 +364,12 @@ class VehiclePipeline:
             hit = ops.range_exceeded(self.device, word=word)
         if not hit:
             return out
-        if rng_state is not None:
-            torch.set_rng_state(rng_state)
-        with ops.defer_range_check(), ops.precision("f32"):
-            return fn(*args)
+        return _redo_f32(lambda: fn(*args), rng_state)
 
     def finish(self) -> bool:
         """Synchronise the device and report (and clear) the range status of the passes issued with check="async":
         True = some pass staged an operand outside the split-fp16 range; its outputs must be recomputed
-        (`ops.precision("f32")`)."""
+        (under `ops.precision`, in exact fp32)."""
         from . import ops
         torch.cuda.synchronize(self.device)
         if not ops.range_guarded():
@@ -366,20 +388,21 @@ class VehiclePipeline:
         rng = torch.get_rng_state() if (vehicle_seeds is None and check == "sync") else None
         return self._guarded(self._run, (batch, vehicle_seeds), check, rng)
 
+    def _no_vehicles(self, R: int, *keys) -> Dict[str, torch.Tensor]:
+        """The named per-vehicle outputs for zero vehicles (a frame without vehicles, a rank whose shard is empty)."""
+        u8 = ((0, R, R, 3), torch.uint8)
+        kinds = {"kp_idx": ((0, 12), torch.int32), "geom": ((0, 8), torch.int32), "icn_u8": u8, "vunet_u8": u8, "inpaint_u8": u8,
+                 "central": u8, "cad_logits": ((0, 10), torch.float32), "cad_idx": ((0,), torch.int64),
+                 "mu_app_0": ((0, 128, R // 64, R // 64), torch.float32), "mu_app_1": ((0, 128, R // 32, R // 32), torch.float32)}
+        return {k: torch.empty(kinds[k][0], dtype=kinds[k][1], device=self.device) for k in keys}
+
     @torch.no_grad()
     def _run(self, batch, vehicle_seeds):
         from . import ops
         B, R = batch["hg_x"].shape[0], batch["hg_x"].shape[-1]
         if B == 0:                                                # a rank whose shard is empty (fewer vehicles than ranks)
-            dev = self.device
-            out = {"kp_idx": torch.empty((0, 12), dtype=torch.int32, device=dev),
-                   "icn_u8": torch.empty((0, R, R, 3), dtype=torch.uint8, device=dev),
-                   "vunet_u8": torch.empty((0, R, R, 3), dtype=torch.uint8, device=dev)}
-            if self.inpaint:
-                out["inpaint_u8"] = torch.empty((0, R, R, 3), dtype=torch.uint8, device=dev)
-            if self.cad is not None:
-                out["cad_logits"] = torch.empty((0, 10), dtype=torch.float32, device=dev)
-            return out
+            return self._no_vehicles(R, "kp_idx", "icn_u8", "vunet_u8", *(("inpaint_u8",) if self.inpaint else ()),
+                                     *(("cad_logits",) if self.cad is not None else ()))
         self.vunet.set_vehicle_seeds(vehicle_seeds)
 
         def hg():
@@ -453,7 +476,7 @@ class VehiclePipeline:
         'state' = what `run_later_frame` needs to render the same vehicles' future frames (VUnet appearance code, central crop).
 
         Geometry mode (a pipeline built with cad_bank, a scene without 'masks'): see `_geometry_frame`."""
-        if "masks" not in scene and self.cad_bank is not None:
+        if self._is_geometry(scene):
             return self._geometry_frame(scene, check, replay)
         rng = torch.get_rng_state() if check == "sync" else None
         import torch.distributed as dist
@@ -480,8 +503,10 @@ class VehiclePipeline:
         return out
 
     # ------------------------------------------------------------------------------------------ geometry mode
-    def _is_geometry(self, scene) -> bool:
-        return "masks" not in scene and self.cad_bank is not None
+    def _is_geometry(self, scene, state=None) -> bool:
+        """A first frame's scene is in geometry mode when the pipeline holds a CAD bank, a later frame's (`state` given) when
+        its first frame was."""
+        return "masks" not in scene and (self.cad_bank if state is None else state.get("geometry")) is not None
 
     @staticmethod
     def _select(scene: Dict, keep, keys) -> Dict:
@@ -508,6 +533,61 @@ class VehiclePipeline:
         """The first frame's planes of the kept vehicles, what their later frames warp: 'src_planes', 'src_kp', 'src_vis'."""
         sel = cls._select(geometry, keep, ("src_planes", "src_kp", "src_vis"))
         return {k: sel[k] for k in ("src_planes", "src_kp", "src_vis")}
+
+    @classmethod
+    def _geometry_state(cls, f: Dict, lo: int = 0) -> Dict:
+        """state['geometry'] of the kept vehicles of `_geometry_front`'s dict `f`; lo: the frame index of f's first vehicle."""
+        keep, sc = f["keep"], f["scene"]
+        return {"vehicles": [lo + v for v in keep], "cad_idx": f["cad_idx"][keep], "pose": [f["pose"][v] for v in keep],
+                "focals": sc["focals"], "centers": sc["centers"], **cls._kept_planes(f["geometry"], keep)}
+
+    # ---- what rank 0 gathers of a sharded geometry-mode first frame besides the crops: one int32 and one float32 row per vehicle
+    @staticmethod
+    def _pack_rows(f: Dict):
+        """`_geometry_front`'s dict -> int32 [n, 14] (kp_idx 12, covered, cad_idx), float32 [n, 52] (kp_xy 24, rv 12, tv 12, er 4)."""
+        import numpy as np
+        n = f["V"]
+        ints, flts = np.zeros((n, 14), np.int32), np.zeros((n, 52), np.float32)
+        if n:
+            ints[:, :12] = f["pre"]["kp_idx"].cpu().numpy()
+            ints[:, 12] = f["g"]["covered"]
+            ints[:, 13] = f["cad_idx"]
+            flts[:, :24] = f["pre"]["kp_xy"].cpu().numpy().reshape(n, 24)
+            flts[:, 24:36] = f["raw"][0].reshape(n, 12)
+            flts[:, 36:48] = f["raw"][1].reshape(n, 12)
+            flts[:, 48:52] = f["raw"][2].reshape(n, 4)
+        return ints, flts
+
+    @staticmethod
+    def _unpack_rows(ints, flts) -> Dict:
+        """The gathered rows of `_pack_rows` (host arrays of all V vehicles) back into their named parts, each a copy."""
+        import numpy as np
+        V = ints.shape[0]
+        return {"kp_idx": ints[:, :12].copy(), "covered": ints[:, 12].copy(), "cad_idx": ints[:, 13].astype(np.int64),
+                "kp_xy": flts[:, :24].reshape(V, 12, 2).copy(), "rv": flts[:, 24:36].reshape(V, 4, 3).copy(),
+                "tv": flts[:, 36:48].reshape(V, 4, 3).copy(), "er": flts[:, 48:52].copy()}
+
+    @staticmethod
+    def _spread(t: torch.Tensor, n: int, idx: torch.Tensor) -> torch.Tensor:
+        """t's rows at the rows `idx` (device int64) of n rows of zeros: a rank's kept crops back at their vehicles' rows of its
+        shard, so that ranks whose kept counts differ still send what the gather expects."""
+        z = torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=idx.device)
+        return z.index_copy_(0, idx, t) if idx.numel() else z
+
+    def _rerender_masks(self, scene: Dict, focals, centers, cad_idx, poses, steps=None) -> torch.Tensor:
+        """Rank 0's masks of vehicles it only holds the poses of (the render is deterministic per job, and a
+        pose is 28 numbers where a mask is H x W bytes); steps: a later frame's (theta, tr) per vehicle."""
+        import numpy as np
+
+        from . import render as rd
+        H, W = int(scene["frame"].shape[0]), int(scene["frame"].shape[1])
+        K = rd.intrinsic(focals, centers)
+        move = ()
+        if steps is not None:
+            move = (np.stack([rd.z_rot(th) for th, _ in steps]) if steps else np.zeros((0, 3, 3)),
+                    np.stack([np.asarray(t, np.float64).reshape(3) for _, t in steps]) if steps else np.zeros((0, 3)))
+        E = rd.extrinsics_from_poses([(p[1], p[2]) for p in poses])
+        return rd.render_vehicles(self.cad_bank, cad_idx, E, float(K[0, 0]), float(K[1, 1]), (H, W), self.device, *move)["mask"]
 
     @torch.no_grad()
     def _geometry_front(self, scene: Dict, check) -> Dict:
@@ -585,9 +665,7 @@ class VehiclePipeline:
         out["geometry"] = f["geometry"]
         out["skipped"] = [v for v in range(V) if v not in keep]
         if out.get("state") is not None:
-            sc = f["scene"]
-            out["state"]["geometry"] = {"vehicles": keep, "cad_idx": f["cad_idx"][keep], "pose": [f["pose"][v] for v in keep],
-                                        "focals": sc["focals"], "centers": sc["centers"], **self._kept_planes(f["geometry"], keep)}
+            out["state"]["geometry"] = self._geometry_state(f)
         return out
 
     def _geometry_frame(self, scene: Dict, check, replay) -> Dict:
@@ -625,7 +703,6 @@ class VehiclePipeline:
         import numpy as np
         import torch.distributed as dist
 
-        from . import render as rd
         from .utils.pnp_utils import select_and_flip
         rng = torch.get_rng_state() if check == "sync" else None
         dev, bank = self.device, self.cad_bank
@@ -633,7 +710,6 @@ class VehiclePipeline:
         bboxes = np.asarray(scene["bboxes"]).reshape(-1, 4)
         V = bboxes.shape[0]
         lo, hi = shard_range(V, rank, world)
-        n = hi - lo
         part = slice_scene(scene, lo, hi)
         if scene.get("cad_idx") is not None:
             part["cad_idx"] = np.asarray(scene["cad_idx"], np.int64).reshape(V)[lo:hi]
@@ -642,51 +718,31 @@ class VehiclePipeline:
             local = self._guarded(self._frame_local, (f["sub"], replay), check, rng)
             keep = f["keep"]
             kidx = torch.as_tensor(keep, dtype=torch.long, device=dev)
-
-            def spread(t):
-                z = torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-                return z.index_copy_(0, kidx, t) if keep else z
-
-            ints = np.zeros((n, 14), np.int32)
-            flts = np.zeros((n, 52), np.float32)
-            if n:
-                ints[:, :12] = f["pre"]["kp_idx"].cpu().numpy()
-                ints[:, 12] = f["g"]["covered"]
-                ints[:, 13] = f["cad_idx"]
-                flts[:, :24] = f["pre"]["kp_xy"].cpu().numpy().reshape(n, 24)
-                flts[:, 24:36] = f["raw"][0].reshape(n, 12)
-                flts[:, 36:48] = f["raw"][1].reshape(n, 12)
-                flts[:, 48:52] = f["raw"][2].reshape(n, 4)
+            ints, flts = self._pack_rows(f)
             crops = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if self.inpaint else ())
-            got = {k: gather_in_order(spread(local[k]).contiguous(), V, self.group) for k in crops}
+            got = {k: gather_in_order(self._spread(local[k], hi - lo, kidx).contiguous(), V, self.group) for k in crops}
             gi = gather_in_order(torch.from_numpy(ints).to(dev), V, self.group)
             gf = gather_in_order(torch.from_numpy(flts).to(dev), V, self.group)
         state = self._local_state(local, (lo, hi, V))
-        state["geometry"] = {"vehicles": [lo + v for v in keep], "cad_idx": f["cad_idx"][keep], "pose": [f["pose"][v] for v in keep],
-                             "focals": scene["focals"], "centers": scene["centers"], **self._kept_planes(f["geometry"], keep)}
+        state["geometry"] = self._geometry_state(f, lo)
         if rank != 0:
             return {"state": state}
-        gi, gf = gi.cpu().numpy(), gf.cpu().numpy()
-        cad_all = gi[:, 13].astype(np.int64)
-        rv, tv, er = gf[:, 24:36].reshape(V, 4, 3).copy(), gf[:, 36:48].reshape(V, 4, 3).copy(), gf[:, 48:52].copy()
+        u = self._unpack_rows(gi.cpu().numpy(), gf.cpu().numpy())
+        cad_all, rv, tv, er = u["cad_idx"], u["rv"], u["tv"], u["er"]
         pose = [select_and_flip(rv[v], tv[v], er[v]) for v in range(V)]
-        keep_all = [v for v in range(V) if gi[v, 12] > 0]
-        H, W = int(scene["frame"].shape[0]), int(scene["frame"].shape[1])
-        K = rd.intrinsic(scene["focals"], scene["centers"])
+        keep_all = [v for v in range(V) if u["covered"][v] > 0]
         with torch.cuda.device(dev):
             kall = torch.as_tensor(keep_all, dtype=torch.long, device=dev)
-            E = rd.extrinsics_from_poses([(pose[v][1], pose[v][2]) for v in keep_all])
-            masks = rd.render_vehicles(bank, cad_all[keep_all], E, float(K[0, 0]), float(K[1, 1]), (H, W), dev)["mask"]
-            kp_idx = gi[:, :12].copy()
+            masks = self._rerender_masks(scene, scene["focals"], scene["centers"], cad_all[keep_all], [pose[v] for v in keep_all])
             full = {k: got[k].to(dev).index_select(0, kall) for k in crops}
-            full["kp_idx"] = torch.from_numpy(kp_idx[keep_all]).to(dev)
+            full["kp_idx"] = torch.from_numpy(u["kp_idx"][keep_all]).to(dev)
             fin = self._select({**scene, "kp3d": bank.kp3d[cad_all]}, keep_all, ("bboxes", "kp3d", "inpaint"))
             fin["masks"] = masks
             fin["_pose_raw"] = tuple(torch.from_numpy(a[keep_all]).to(dev) for a in (rv, tv, er))
             out = self._frame_finish(fin, full)
             out.pop("_pose_raw")
-            out["kp_idx"] = torch.from_numpy(kp_idx).to(dev)
-            out["kp_xy"] = torch.from_numpy(gf[:, :24].reshape(V, 12, 2).copy()).to(dev)
+            out["kp_idx"] = torch.from_numpy(u["kp_idx"]).to(dev)
+            out["kp_xy"] = torch.from_numpy(u["kp_xy"]).to(dev)
             if self.cad is not None:
                 out["cad_idx"] = torch.as_tensor(cad_all, device=dev)
         out["pose"] = pose
@@ -757,17 +813,11 @@ class VehiclePipeline:
         f = self._geometry_later_front(scene, state)
         with torch.cuda.device(dev):
             local = self._guarded(self._later_local, (f["sub"], f["sub_state"], replay), check, rng)
-            rows = [f["veh"][i] - lo for i in f["keep"]]
-            ridx = torch.as_tensor(rows, dtype=torch.long, device=dev)
-
-            def spread(t):
-                z = torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-                return z.index_copy_(0, ridx, t) if rows else z
-
+            ridx = torch.as_tensor([f["veh"][i] - lo for i in f["keep"]], dtype=torch.long, device=dev)
             cov = np.zeros((n, 1), np.int32)
             for i, v in enumerate(f["veh"]):
                 cov[v - lo, 0] = f["g"]["covered"][i]
-            got = {k: gather_in_order(spread(local[k]).contiguous(), V, self.group) for k in ("icn_u8", "vunet_u8", "geom")}
+            got = {k: gather_in_order(self._spread(local[k], n, ridx).contiguous(), V, self.group) for k in ("icn_u8", "vunet_u8", "geom")}
             gc = gather_in_order(torch.from_numpy(cov).to(dev), V, self.group)
         if gc is None:
             return None
@@ -776,14 +826,9 @@ class VehiclePipeline:
         keep = [i for i, v in enumerate(al["vehicles"]) if gc[v] > 0]
         kept = [al["vehicles"][i] for i in keep]
         gs = state["geometry"]
-        H, W = int(scene["frame"].shape[0]), int(scene["frame"].shape[1])
-        K = rd.intrinsic(gs["focals"], gs["centers"])
-        steps = [scene["steps"][v] for v in kept]
-        Rs = np.stack([rd.z_rot(th) for th, _ in steps]) if kept else np.zeros((0, 3, 3))
-        trs = np.stack([np.asarray(t, np.float64).reshape(3) for _, t in steps]) if kept else np.zeros((0, 3))
         with torch.cuda.device(dev):
-            E = rd.extrinsics_from_poses([(al["pose"][i][1], al["pose"][i][2]) for i in keep])
-            masks = rd.render_vehicles(self.cad_bank, al["cad_idx"][keep], E, float(K[0, 0]), float(K[1, 1]), (H, W), dev, Rs, trs)["mask"]
+            masks = self._rerender_masks(scene, gs["focals"], gs["centers"], al["cad_idx"][keep], [al["pose"][i] for i in keep],
+                                         steps=[scene["steps"][v] for v in kept])
             kidx = torch.as_tensor(kept, dtype=torch.long, device=dev)
             full = {k: got[k].to(dev).index_select(0, kidx) for k in got}
             out = self._later_finish({**scene, "masks": masks}, full)
@@ -806,60 +851,79 @@ class VehiclePipeline:
         ev.record(torch.cuda.current_stream(self.device))
         return ev
 
-    def _issue_geometry_front(self, fn, ready, guarded) -> Dict:
-        """Run fn() (a geometry front: keypoints, pose fit and render with their host read-backs) on the pipeline's geometry
-        stream, ordered after `ready` (or after the caller's stream as it is now), under a status word of its own that is copied
-        to pinned memory and cleared on that stream; the caller's stream then waits for the stage."""
+    def _issue_guarded(self, fn, word=None):
+        """fn() issued on the current stream without waiting for it, under the status word `word()` (default: the pipeline's own,
+        `status_word`): the word is copied to a pinned int32 behind fn's launches and cleared for the next stage, whose launches
+        queue behind that copy, and one event is recorded.  In a precision without a range guard there is only the event.
+        Returns (fn's result, ticket); `_status_raised(ticket)` redeems the ticket."""
         from . import ops
-        main = torch.cuda.current_stream(self.device)
-        st = self.__dict__.get("_geo_stream")
-        if st is None:
-            st = self.__dict__["_geo_stream"] = torch.cuda.Stream(device=self.device)
-        if ready is None:
-            ready = torch.cuda.Event()
-            ready.record(main)
-        st.wait_event(ready)
         pin = None
-        with torch.cuda.stream(st):
-            if guarded:
-                word = self.__dict__.get("_geo_status")
-                if word is None:
-                    word = self.__dict__["_geo_status"] = ops.new_status_word(self.device)
-                with ops.defer_range_check(), ops.status_scope(word):
-                    f = fn()
-                ring = self.__dict__.setdefault("_geo_pins", [])
-                pin = ring.pop() if ring else torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                pin.copy_(word[:1], non_blocking=True)
-                word.zero_()
-            else:
-                f = fn()
-            done = torch.cuda.Event()
-            done.record(st)
-        main.wait_event(done)
+        if ops.range_guarded():
+            word = (word or self.status_word)()
+            with ops.defer_range_check(), ops.status_scope(word):
+                out = fn()
+            pin = self._pins.pop() if self._pins else torch.zeros(1, dtype=torch.int32, pin_memory=True)
+            pin.copy_(word[:1], non_blocking=True)
+            word.zero_()
+        else:
+            out = fn()
+        ev = torch.cuda.Event()
+        ev.record()
+        return out, (pin, ev)
 
-        def keep_alive(o):                                        # tensors made on the geometry stream, used on the caller's
-            if torch.is_tensor(o):
-                if o.is_cuda:
-                    o.record_stream(main)
-            elif isinstance(o, dict):
-                for v in o.values():
-                    keep_alive(v)
-            elif isinstance(o, (list, tuple)):
-                for v in o:
-                    keep_alive(v)
-
-        keep_alive({k: v for k, v in f.items() if k != "scene"})
-        f["_pin"] = pin
-        return f
-
-    def _geometry_front_hit(self, f) -> bool:
-        pin = f.get("_pin")
+    def _status_raised(self, ticket, wait: bool = True) -> bool:
+        """Wait for the stage behind `_issue_guarded`'s ticket (wait=False: the caller has waited for something queued behind
+        it) and say whether it raised its status word; the pinned int goes back to the ring."""
+        pin, ev = ticket
+        if wait:
+            ev.synchronize()
         if pin is None:
             return False
         hit = int(pin[0]) != 0
-        self.__dict__["_geo_pins"].append(pin)
-        f["_pin"] = None
+        self._pins.append(pin)
         return hit
+
+    @staticmethod
+    def _one_in_flight(items, issue, collect, direct=None):
+        """The one-deep software pipeline of the frame drivers, a generator: issue(item i+1) -> ticket runs before
+        collect(ticket of item i) is yielded; the last ticket is collected at the end.  An item for which issue returns None is
+        not pipelined: what is in flight is collected first, then direct(item) is yielded."""
+        pending = None
+        for item in items:
+            ticket = issue(item)
+            if pending is not None:
+                yield collect(pending)
+            pending = ticket
+            if ticket is None:
+                yield direct(item)
+        if pending is not None:
+            yield collect(pending)
+
+    def _geo_word(self) -> torch.Tensor:
+        from . import ops
+        if self._geo_status is None:
+            self._geo_status = ops.new_status_word(self.device)
+        return self._geo_status
+
+    def _issue_geometry_front(self, fn, ready) -> Dict:
+        """Run fn() (a geometry front: keypoints, pose fit and render with their host read-backs) on the pipeline's geometry
+        stream, ordered after `ready` (or after the caller's stream as it is now), under a status word of its own
+        (`_issue_guarded` on that stream); the caller's stream then waits for the stage.  The ticket is left in f['_ticket']."""
+        main = torch.cuda.current_stream(self.device)
+        if self._geo_stream is None:
+            self._geo_stream = torch.cuda.Stream(device=self.device)
+        if ready is None:
+            ready = torch.cuda.Event()
+            ready.record(main)
+        self._geo_stream.wait_event(ready)
+        with torch.cuda.stream(self._geo_stream):
+            f, ticket = self._issue_guarded(fn, self._geo_word)
+        main.wait_event(ticket[1])
+        for t in _tensors({k: v for k, v in f.items() if k != "scene"}):    # made on the geometry stream, used on the caller's
+            if t.is_cuda:
+                t.record_stream(main)
+        f["_ticket"] = ticket
+        return f
 
     def run_frames(self, scenes, replay: bool = True):
         """`run_frame` over a sequence of frames (the reference's outer loop, trajectory_inference.py:283-300), software-
@@ -879,86 +943,52 @@ class VehiclePipeline:
             # sharded frames, one frame deep as well: every rank issues its shard of frame i+1 before frame i's crops are
             # gathered; the gather and rank 0's frame-level part run on a communication stream that waits for frame i's
             # launches only, so they overlap frame i+1's networks.  Yields `run_frame`'s sharded results (rank 0: the frame,
-            # other ranks: {'state': ...}); a scene with shard = False is not pipelined.
-            pending = None
-            for scene in scenes:
-                if not scene.get("shard", True) or self._is_geometry(scene):
-                    if pending is not None:
-                        yield self._collect_sharded(pending)
-                        pending = None
-                    yield self.run_frame(scene, replay=replay)
-                    continue
-                ticket = self._issue_sharded(scene, replay)
-                if pending is not None:
-                    yield self._collect_sharded(pending)
-                pending = ticket
-            if pending is not None:
-                yield self._collect_sharded(pending)
+            # other ranks: {'state': ...}); a scene with shard = False, or a geometry-mode one, is not pipelined.
+            def issue(scene):
+                if scene.get("shard", True) and not self._is_geometry(scene):
+                    return self._issue_sharded(scene, replay)
+
+            yield from self._one_in_flight(scenes, issue, self._collect_sharded, lambda scene: self.run_frame(scene, replay=replay))
             return
-        pending = None
         ready = self._scenes_ready(scenes)
-        for scene in scenes:
-            ticket = self._issue_frame(scene, replay, ready)
-            if pending is not None:
-                yield self._collect_frame(pending)
-            pending = ticket
-        if pending is not None:
-            yield self._collect_frame(pending)
+        yield from self._one_in_flight(scenes, lambda scene: self._issue_frame(scene, replay, ready), self._collect_frame)
 
     def _issue_frame(self, scene, replay, ready=None):
         from . import ops
-        guarded = ops.range_guarded()
-        rng = torch.get_rng_state() if (guarded and scene.get("vehicle_seeds") is None) else None
-        word = self.status_word() if guarded else None
+        rng = torch.get_rng_state() if (ops.range_guarded() and scene.get("vehicle_seeds") is None) else None
         front = None
         with torch.cuda.device(self.device):
             if self._is_geometry(scene):                         # keypoints -> pose -> render on the geometry stream first
-                front = self._issue_geometry_front(lambda: self._geometry_front(scene, None), ready, guarded)
+                front = self._issue_geometry_front(lambda: self._geometry_front(scene, None), ready)
                 scene_nets = front["sub"]
             else:
                 scene_nets = scene
-            if guarded:
-                with ops.defer_range_check(), ops.status_scope(word):
-                    out = self._run_frame(scene_nets, replay)
-            else:
+
+            def frame():
+                # stream-ordered read-back: the three raw pose arrays into pinned memory behind the frame's launches; the
+                # status word follows them (`_issue_guarded`), then the one event to wait on
                 out = self._run_frame(scene_nets, replay)
-            # stream-ordered read-back: the three raw pose arrays and the status word into pinned memory, the word cleared
-            # for the next frame (whose launches queue behind these copies), one event to wait on
-            ring = self.__dict__.setdefault("_frame_pins", [])
-            raw = out.pop("_pose_raw")
-            hit = [i for i, pr in enumerate(ring) if all(a.shape == b.shape for a, b in zip(pr[0], raw))]
-            pins = ring.pop(hit[0]) if hit else \
-                ([torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in raw], torch.zeros(1, dtype=torch.int32, pin_memory=True))
-            for h, t in zip(pins[0], raw):
-                h.copy_(t, non_blocking=True)
-            if guarded:
-                pins[1].copy_(word[:1], non_blocking=True)
-                word.zero_()
-            ev = torch.cuda.Event()
-            ev.record()
-        return {"out": out, "pins": pins, "event": ev, "scene": scene, "replay": replay, "rng": rng, "guarded": guarded, "front": front}
+                raw = out.pop("_pose_raw")
+                ring = self._frame_pins
+                hit = [i for i, pr in enumerate(ring) if all(a.shape == b.shape for a, b in zip(pr, raw))]
+                pins = ring.pop(hit[0]) if hit else [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in raw]
+                for h, t in zip(pins, raw):
+                    h.copy_(t, non_blocking=True)
+                return out, pins
+
+            (out, pins), ticket = self._issue_guarded(frame)
+        return {"out": out, "pins": pins, "ticket": ticket, "scene": scene, "rng": rng, "front": front}
 
     def _collect_frame(self, t):
-        from . import ops
         from .utils.pnp_utils import select_and_flip
-        t["event"].synchronize()
-        (rv, tv, er), status = t["pins"]
-        front = t["front"]
-        geo_hit = front is not None and self._geometry_front_hit(front)
-        hit = t["guarded"] and (int(status[0]) != 0 or geo_hit)
+        hit, front = self._status_raised(t["ticket"]), t["front"]
+        if front is not None:                                     # (its event: the frame's was recorded behind it)
+            hit = self._status_raised(front.pop("_ticket"), wait=False) or hit
+        rv, tv, er = (h.numpy().copy() for h in t["pins"])
+        self._frame_pins.append(t["pins"])
         if hit:                                                   # rare: this frame again (geometry included), in exact fp32
-            cur = torch.get_rng_state()
-            if t["rng"] is not None:
-                torch.set_rng_state(t["rng"])
-            with ops.defer_range_check(), ops.precision("f32"):
-                out = self.run_frame(t["scene"], check=None, replay=False)
-            if t["rng"] is not None:
-                torch.set_rng_state(cur)
-            self.__dict__["_frame_pins"].append(t["pins"])
-            return out
+            return _redo_f32(lambda: self.run_frame(t["scene"], check=None, replay=False), t["rng"], restore=True)
         out = t["out"]
-        rv, tv, er = rv.numpy().copy(), tv.numpy().copy(), er.numpy().copy()
-        self.__dict__["_frame_pins"].append(t["pins"])
         if front is not None:                                     # the pose of the geometry stage (the same fit, passed through)
             return self._geometry_assemble(front, out)
         out["pose"] = [select_and_flip(rv[i], tv[i], er[i]) for i in range(rv.shape[0])]
@@ -972,48 +1002,24 @@ class VehiclePipeline:
         V = len(scene["bboxes"])
         lo, hi = shard_range(V, rank, world)
         sub = slice_scene(scene, lo, hi)
-        guarded = ops.range_guarded()
-        rng = torch.get_rng_state() if (guarded and scene.get("vehicle_seeds") is None) else None
-        word = self.status_word() if guarded else None
+        rng = torch.get_rng_state() if (ops.range_guarded() and scene.get("vehicle_seeds") is None) else None
         with torch.cuda.device(self.device):
-            if guarded:
-                with ops.defer_range_check(), ops.status_scope(word):
-                    local = self._frame_local(sub, replay)
-            else:
-                local = self._frame_local(sub, replay)
-            pin = None
-            if guarded:
-                ring = self.__dict__.setdefault("_shard_pins", [])
-                pin = ring.pop() if ring else torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                pin.copy_(word[:1], non_blocking=True)
-                word.zero_()
-            ev = torch.cuda.Event()
-            ev.record()
-        return {"local": local, "pin": pin, "event": ev, "scene": scene, "sub": sub, "shard": (lo, hi, V), "rng": rng, "guarded": guarded}
+            local, ticket = self._issue_guarded(lambda: self._frame_local(sub, replay))
+        return {"local": local, "ticket": ticket, "scene": scene, "sub": sub, "shard": (lo, hi, V), "rng": rng}
 
     def _collect_sharded(self, t):
-        from . import ops
         from .utils.pnp_utils import select_and_flip
-        t["event"].synchronize()                                  # this frame's launches only; the next frame's are already queued
         local = t["local"]
-        if t["guarded"]:
-            hit = int(t["pin"][0]) != 0
-            self.__dict__["_shard_pins"].append(t["pin"])
-            if hit:                                               # rare: this rank's shard again, in exact fp32 (before any collective)
-                cur = torch.get_rng_state()
-                if t["rng"] is not None:
-                    torch.set_rng_state(t["rng"])
-                with ops.defer_range_check(), ops.precision("f32"):
-                    local = self._frame_local(t["sub"], False)
-                if t["rng"] is not None:
-                    torch.set_rng_state(cur)
-                torch.cuda.synchronize(self.device)
+        if self._status_raised(t["ticket"]):                      # (waits for this frame's launches only; the next frame's are already queued)
+            # rare: this rank's shard again, in exact fp32 (before any collective)
+            local = _redo_f32(lambda: self._frame_local(t["sub"], False), t["rng"], restore=True)
+            torch.cuda.synchronize(self.device)
         main = torch.cuda.current_stream(self.device)
-        comm = self.__dict__.get("_comm_stream")
-        if comm is None:
-            comm = self.__dict__["_comm_stream"] = torch.cuda.Stream(device=self.device)
-        for v in local.values():
-            if torch.is_tensor(v) and v.is_cuda:
+        if self._comm_stream is None:
+            self._comm_stream = torch.cuda.Stream(device=self.device)
+        comm = self._comm_stream
+        for v in _tensors(local):
+            if v.is_cuda:
                 v.record_stream(comm)
         with torch.cuda.device(self.device), torch.cuda.stream(comm):
             out = self._frame_gather_finish(t["scene"], local, t["shard"])
@@ -1021,8 +1027,8 @@ class VehiclePipeline:
                 rv, tv, er = (x.cpu().numpy() for x in out.pop("_pose_raw"))          # waits for the communication stream only
                 out["pose"] = [select_and_flip(rv[i], tv[i], er[i]) for i in range(rv.shape[0])]
         main.wait_stream(comm)                                    # the caller consumes the results on its own stream
-        for v in out.values():
-            if torch.is_tensor(v) and v.is_cuda:
+        for v in _tensors(out):
+            if v.is_cuda:
                 v.record_stream(main)
         return out
 
@@ -1064,6 +1070,31 @@ class VehiclePipeline:
         out["state"] = state
         return out
 
+    def _plan(self, key) -> Optional["CompiledPass"]:
+        """The recorded pass kept under `key`, unless a network's packed weights have changed since it was recorded."""
+        cp = self._frame_plans.get(key)
+        return cp if cp is not None and [n.generation for n in self._nets] == cp.generations else None
+
+    def _replay(self, key, nets_in, seeds, fn=None, clone=None) -> Dict:
+        """One replay of the recorded pass `fn` (default `_run`) kept under `key`: one recorded pass (with its private pool of
+        intermediates) per vehicle count and precision, recorded on first use; a video whose count varies keeps the FRAME_PLANS
+        most recently used ones.  The plan's output buffers belong to its next replay: the outputs `clone` names (default: all
+        of them) are handed out as copies."""
+        cps = self._frame_plans
+        cp = self._plan(key)
+        if cp is None:
+            cps.pop(key, None)
+            while len(cps) >= FRAME_PLANS:
+                cps.pop(next(iter(cps)))
+            cp = cps[key] = CompiledPass(self, nets_in, seeds, fn)
+        else:
+            cps[key] = cps.pop(key)                               # most recently used last
+        out = dict(cp._issue(nets_in, seeds))
+        for k in (clone if clone is not None else list(out)):
+            if k in out:
+                out[k] = out[k].clone()
+        return out
+
     @torch.no_grad()
     def _frame_local(self, scene, replay=False):
         """The per-vehicle part of a frame for the vehicles `scene` lists (all of them, or one rank's shard): glue, the
@@ -1085,23 +1116,12 @@ class VehiclePipeline:
                 raise ValueError("run_frame: this pipeline was built with inpaint=True; the scene needs 'inpaint' = "
                                  "{'boxes' [V, 4], 'img' [V, 3, R, R], 'gray' / 'edge' / 'mask' [V, 1, R, R]}")
             if V == 0:                                            # no vehicle in the frame (or an empty shard)
-                e8 = lambda: torch.empty((0, R, R, 3), dtype=torch.uint8, device=dev)   # noqa: E731
-                out = {"kp_idx": torch.empty((0, 12), dtype=torch.int32, device=dev), "icn_u8": e8(), "vunet_u8": e8(),
-                       "geom": torch.empty((0, 8), dtype=torch.int32, device=dev)}
-                if inp is not None:
-                    out["inpaint_u8"] = e8()
-                if self.cad is not None:
-                    out["cad_idx"] = torch.empty((0,), dtype=torch.int64, device=dev)
                 # an empty shard still hands out a (zero-vehicle) state, so that `run_later_frame` takes part in the gathers
-                out.update(mu_app_0=torch.empty((0, 128, R // 64, R // 64), device=dev), mu_app_1=torch.empty((0, 128, R // 32, R // 32), device=dev),
-                           central=e8())
-                return out
+                return self._no_vehicles(R, "kp_idx", "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if inp is not None else ()),
+                                         *(("cad_idx",) if self.cad is not None else ()), "mu_app_0", "mu_app_1", "central")
             replay = replay and ops.RECORDER is None
-            cps = self.__dict__.setdefault("_frame_plans", {})
             pkey = (V, ops.PRECISION) + (("kp_given",) if scene.get("_hg") is not None else ())
-            cp = cps.get(pkey) if replay else None
-            if cp is not None and [n.generation for n in self._nets] != cp.generations:
-                cp = None
+            cp = self._plan(pkey) if replay else None
             tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
             # ---- host: the homography fits of every plane of every vehicle (1.2 ms for 8 vehicles), before any launch
             jobs = pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
@@ -1121,20 +1141,8 @@ class VehiclePipeline:
                 nets_in.update(scene["_hg"])
             if inp is not None:                                   # :121: create_inpaint_inputs_shape's four tensors, given
                 nets_in.update(ec_img=inp["img"], ec_gray=inp["gray"], ec_edge=inp["edge"], ec_mask=inp["mask"])
-            if replay:
-                if cp is None:
-                    # one recorded pass (with its private pool of intermediates) per vehicle count; a video whose count varies
-                    # keeps the FRAME_PLANS most recently used ones
-                    cps.pop(pkey, None)
-                    while len(cps) >= FRAME_PLANS:
-                        cps.pop(next(iter(cps)))
-                    cp = cps[pkey] = CompiledPass(self, nets_in, seeds)
-                else:
-                    cps[pkey] = cps.pop(pkey)                 # most recently used last
-                out = dict(cp._issue(nets_in, seeds))
-                for k in ("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"):    # the plan's buffers belong to its next replay
-                    if k in out:
-                        out[k] = out[k].clone()
+            if replay:                                            # ('icn_u8' is consumed by lab2bgr below, before the next replay)
+                out = self._replay(pkey, nets_in, seeds, clone=("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"))
             else:
                 out = self._run(nets_in, seeds)                                                # :75-79, :182, :230-234
             out["icn_u8"] = pu.lab2bgr(out["icn_u8"])                                          # to_image(from_LAB=True), :182
@@ -1208,7 +1216,7 @@ class VehiclePipeline:
         Returns 'icn_u8' / 'vunet_u8' uint8 [V, R, R, 3] (BGR), 'frame_icn' / 'frame_vunet' uint8 [H, W, 3], 'geom'.
 
         Geometry mode (state of a geometry-mode `run_frame`, a scene without 'masks'): see `_geometry_later_frame`."""
-        if "masks" not in scene and state.get("geometry") is not None:
+        if self._is_geometry(scene, state):
             return self._geometry_later_frame(scene, state, check, replay)
         rng = torch.get_rng_state() if (check == "sync" and scene.get("vehicle_seeds") is None) else None
         import torch.distributed as dist
@@ -1261,8 +1269,7 @@ class VehiclePipeline:
             raise ValueError(f"run_later_frame: the state holds {state['central'].shape[0]} vehicles, the scene {V}")
         with torch.cuda.device(dev):
             if V == 0:
-                e8 = torch.empty((0, R, R, 3), dtype=torch.uint8, device=dev)
-                return {"icn_u8": e8, "vunet_u8": e8.clone(), "geom": torch.empty((0, 8), dtype=torch.int32, device=dev)}
+                return self._no_vehicles(R, "icn_u8", "vunet_u8", "geom")
             jobs = pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
             warped = pu.warp_planes_batch(scene["src_planes"], jobs)                           # :376-381
             _, geom = fo.mask_bbox_geom(scene["masks"])
@@ -1270,21 +1277,8 @@ class VehiclePipeline:
             _, vu_y = fo.vunet_inputs(frame, scene["masks"], scene["dst_sketch"], scene["dst_sketch"], geom, R)   # :415-420 (y_tilde only)
             seeds = scene.get("vehicle_seeds")
             nets_in = {"icn_x": icn_x, "vu_y": vu_y, "app0": state["appearance"][0], "app1": state["appearance"][1]}
-            replay = replay and ops.RECORDER is None
-            if replay:
-                cps = self.__dict__.setdefault("_frame_plans", {})
-                key = ("later", V, ops.PRECISION)
-                cp = cps.get(key)
-                if cp is not None and [n.generation for n in self._nets] != cp.generations:
-                    cp = None
-                if cp is None:
-                    cps.pop(key, None)
-                    while len(cps) >= FRAME_PLANS:
-                        cps.pop(next(iter(cps)))
-                    cp = cps[key] = CompiledPass(self, nets_in, seeds, fn=self._later_nets)
-                else:
-                    cps[key] = cps.pop(key)                   # most recently used last
-                out = {k: v.clone() for k, v in cp._issue(nets_in, seeds).items()}     # the plan's buffers belong to its next replay
+            if replay and ops.RECORDER is None:
+                out = self._replay(("later", V, ops.PRECISION), nets_in, seeds, fn=self._later_nets)
             else:
                 out = self._later_nets(nets_in, seeds)
             out["icn_u8"] = pu.lab2bgr(out["icn_u8"])
@@ -1314,60 +1308,34 @@ class VehiclePipeline:
         redone in exact fp32 before it is yielded.  The state of a geometry-mode first frame (scenes with 'steps', no 'masks') is
         pipelined the same way, its render and covered-count read-back on the pipeline's geometry stream.  A sharded state
         (process group, geometry mode included) is not pipelined: frame by frame."""
-        from . import ops
         if not _one_rank(self.group) and state.get("sharded"):
             for sc in scenes:
                 yield self.run_later_frame(sc, state, replay=replay)
             return
-        pending = None
         ready = self._scenes_ready(scenes)
-        for scene in scenes:
-            guarded = ops.range_guarded()
-            rng = torch.get_rng_state() if (guarded and scene.get("vehicle_seeds") is None) else None
-            word = self.status_word() if guarded else None
-            front = None
-            with torch.cuda.device(self.device):
-                if "masks" not in scene and state.get("geometry") is not None:     # the render on the geometry stream first
-                    front = self._issue_geometry_front(lambda: self._geometry_later_front(scene, state), ready, guarded)
-                    scene_nets, state_nets = front["sub"], front["sub_state"]
-                else:
-                    scene_nets, state_nets = scene, state
-                if guarded:
-                    with ops.defer_range_check(), ops.status_scope(word):
-                        out = self._run_later_frame(scene_nets, state_nets, replay)
-                else:
-                    out = self._run_later_frame(scene_nets, state_nets, replay)
-                ring = self.__dict__.setdefault("_later_pins", [])
-                pin = ring.pop() if ring else torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                if guarded:
-                    pin.copy_(word[:1], non_blocking=True)
-                    word.zero_()
-                ev = torch.cuda.Event()
-                ev.record()
-            ticket = {"out": out, "pin": pin, "event": ev, "scene": scene, "rng": rng, "guarded": guarded, "front": front}
-            if pending is not None:
-                yield self._collect_later(pending, state)
-            pending = ticket
-        if pending is not None:
-            yield self._collect_later(pending, state)
+        yield from self._one_in_flight(scenes, lambda scene: self._issue_later(scene, state, replay, ready), self._collect_later)
 
-    def _collect_later(self, t, state):
+    def _issue_later(self, scene, state, replay, ready=None):
+        """A later frame issued without waiting for it (the counterpart of `_issue_frame`)."""
         from . import ops
-        t["event"].synchronize()
-        front = t["front"]
-        geo_hit = front is not None and self._geometry_front_hit(front)
-        hit = t["guarded"] and (int(t["pin"][0]) != 0 or geo_hit)
-        self.__dict__["_later_pins"].append(t["pin"])
-        if not hit:
-            return t["out"] if front is None else self._geometry_later_assemble(front, t["out"])
-        cur = torch.get_rng_state()                                # rare: this frame again, in exact fp32
-        if t["rng"] is not None:
-            torch.set_rng_state(t["rng"])
-        with ops.defer_range_check(), ops.precision("f32"):
-            out = self.run_later_frame(t["scene"], state, check=None, replay=False)
-        if t["rng"] is not None:
-            torch.set_rng_state(cur)
-        return out
+        rng = torch.get_rng_state() if (ops.range_guarded() and scene.get("vehicle_seeds") is None) else None
+        front = None
+        with torch.cuda.device(self.device):
+            if self._is_geometry(scene, state):                  # the render on the geometry stream first
+                front = self._issue_geometry_front(lambda: self._geometry_later_front(scene, state), ready)
+                scene_nets, state_nets = front["sub"], front["sub_state"]
+            else:
+                scene_nets, state_nets = scene, state
+            out, ticket = self._issue_guarded(lambda: self._run_later_frame(scene_nets, state_nets, replay))
+        return {"out": out, "ticket": ticket, "scene": scene, "state": state, "rng": rng, "front": front}
+
+    def _collect_later(self, t):
+        hit, front = self._status_raised(t["ticket"]), t["front"]
+        if front is not None:
+            hit = self._status_raised(front.pop("_ticket"), wait=False) or hit
+        if hit:                                                   # rare: this frame again, in exact fp32
+            return _redo_f32(lambda: self.run_later_frame(t["scene"], t["state"], check=None, replay=False), t["rng"], restore=True)
+        return t["out"] if front is None else self._geometry_later_assemble(front, t["out"])
 
     def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False):
         """A vehicle clip the reference's way (trajectory_inference.py:55-250 then :267-450): the first frame through
@@ -1472,7 +1440,9 @@ class CompiledPass:
         except Exception:                                                     # interpreter shutdown
             pass
 
-    def _issue(self, batch, vehicle_seeds):
+    def _refresh(self, batch, vehicle_seeds, next_slot, what: str) -> None:
+        """What precedes every replay: the inputs refreshed in place, the VUnet's noise drawn (the reference's draw order) into
+        the pinned ring slot `next_slot(plan)` says this replay reads."""
         from . import _lib as L
         for k in self.keys:
             src = batch[k]
@@ -1480,15 +1450,19 @@ class CompiledPass:
                 if src.shape != self.inputs[k].shape:
                     raise ValueError(f"CompiledPass: input '{k}' has shape {tuple(src.shape)}, recorded {tuple(self.inputs[k].shape)}")
                 self.inputs[k].copy_(src, non_blocking=True)
-        lib = L.lib()
-        slot = lib.fusg_plan_next_slot(self.rec.handle)                       # which pinned ring slot this run reads
+        slot = next_slot(self.rec.handle)
         if slot < 0:
-            L.check(-1, "plan_next_slot")
+            L.check(-1, what)
         vu = self.pipe.vunet
         vu.set_vehicle_seeds(vehicle_seeds)
         gens = vu.__dict__.get("_vehicle_gens")
-        for ring, shapes in self.rec.noise_slots:                             # the reference's draw order
+        for ring, shapes in self.rec.noise_slots:
             vu._fill_noise(ring[slot], shapes, gens)
+
+    def _issue(self, batch, vehicle_seeds):
+        from . import _lib as L
+        lib = L.lib()
+        self._refresh(batch, vehicle_seeds, lib.fusg_plan_next_slot, "plan_next_slot")
         if PLAN_THREADS:
             L.check(lib.fusg_plan_run_mt(self.rec.handle), "plan_run_mt")     # one issuing host thread per recorded stream
         else:
@@ -1510,18 +1484,7 @@ class CompiledPass:
         from . import _lib as L
         lib = L.lib()
         with torch.cuda.device(self.device):
-            for k in self.keys:
-                src = batch[k]
-                if src.data_ptr() != self.inputs[k].data_ptr():
-                    self.inputs[k].copy_(src, non_blocking=True)
-            slot = lib.fusg_plan_graph_slot(self.rec.handle)
-            if slot < 0:
-                L.check(-1, "plan_graph_slot")
-            vu = self.pipe.vunet
-            vu.set_vehicle_seeds(vehicle_seeds)
-            gens = vu.__dict__.get("_vehicle_gens")
-            for ring, shapes in self.rec.noise_slots:
-                vu._fill_noise(ring[slot], shapes, gens)
+            self._refresh(batch, vehicle_seeds, lib.fusg_plan_graph_slot, "plan_graph_slot")
             L.check(lib.fusg_plan_graph_launch(self.rec.handle, self.stream.cuda_stream), "plan_graph_launch")
         return self.outputs
 
@@ -1545,10 +1508,7 @@ class CompiledPass:
                 return out
             if not ops.range_exceeded(self.device, word=self.pipe.status_word()):
                 return out
-            if rng is not None:
-                torch.set_rng_state(rng)
-            with ops.defer_range_check(), ops.precision("f32"):
-                return self.fn(batch, vehicle_seeds)
+            return _redo_f32(lambda: self.fn(batch, vehicle_seeds), rng)
 
 
 def synth_clip(vehicles: int, frames: int, res: int, device, seed: int = 0) -> Dict[str, torch.Tensor]:
