@@ -77,12 +77,7 @@ __global__ __launch_bounds__(256, 2) void hg_bneck_h3(const BneckK k) {
     const int lp = lane & 15, lg = lane >> 4;           // pixel of the fragment, 8-k slot
     FUSG_STAMP_RT(8);
     FUSG_STAMP(0);
-    int tile;
-    {
-        const int nb = gridDim.x, bid = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int tile = xcd_tile();
     const int tpi = k.tiles_x * k.tiles_y;
     const int b = tile / tpi, t2 = tile - b * tpi;
     const int ty = t2 / k.tiles_x, tx = t2 - ty * k.tiles_x;
@@ -383,12 +378,7 @@ __global__ __launch_bounds__(256, 2) void hg_bneck_f32(const BneckK k) {
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int lp = lane & 15, lg = lane >> 4;
-    int tile;
-    {
-        const int nb = gridDim.x, bid = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int tile = xcd_tile();
     const int tpi = k.tiles_x * k.tiles_y;
     const int b = tile / tpi, t2 = tile - b * tpi;
     const int ty = t2 / k.tiles_x, tx = t2 - ty * k.tiles_x;
@@ -651,11 +641,9 @@ static int bneck_impl(const fusg_bneck_desc* d, void* stream) {
                          : (P == 128 ? (const void*)hg_bneck_h3<128> : (const void*)hg_bneck_h3<64>);
     const size_t lds = bneck_lds(P) + TOUCH_LDS_BYTES;
     k.touch_w = env_switches().no_touch ? 0 : 1;
-    if (hipError_t e = ensure_dyn_lds(fn, (int)lds); e != hipSuccess) { set_error("hg_bottleneck: %s", hipGetErrorString(e)); return FUSG_ERR_LAUNCH; }
     const double M = (double)x.n * x.h * x.w;
     prof_begin(0, s, 2.0 * M * ((double)x.c * P + 9.0 * P * P + 2.0 * P * P));   // the three convs' own FLOPs (no halo recompute)
-    void* args[] = {(void*)&k};
-    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)wgs), dim3(256), args, lds, s);
+    const hipError_t e = launch_kernel(fn, dim3((unsigned)wgs), lds, (int)lds, k, s);
     prof_end(0, s);
     if (e != hipSuccess) { set_error("hg_bottleneck launch: %s", hipGetErrorString(e)); return FUSG_ERR_LAUNCH; }
     note_conv_kernel(FUSG_CONV_BNECK);

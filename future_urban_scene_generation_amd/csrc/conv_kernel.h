@@ -20,6 +20,7 @@
 // each).  MFMA operand maps (cdna_hip_programming.md §3): A lane l holds A[row l&31][k l>>5],
 // B lane l holds B[k l>>5][col l&31]; C/D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5).
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace fusg {
@@ -139,6 +140,39 @@ __device__ __forceinline__ void epi_store(const ConvK& p, const PixOff& po, cons
     if (p.res1) v += p.res1[po.r1 + co.r1];
     p.dst[po.d + co.d] = v;
 }
+
+// ---- blocks every conv kernel family shares (one copy each) -------------------------------------------------------
+// n / d by the host's reciprocal m = ceil(2^32 / d) (0: d == 1), exact while n * d < 2^32: an integer division costs
+// ~25 VALU instructions on gfx950
+__device__ __forceinline__ int fdiv(int n, unsigned m) { return m ? (int)__umulhi((unsigned)n, m) : n; }
+// XCD-aware tile order: consecutive tiles (same A rows, different N) stay on one XCD's L2.
+__device__ __forceinline__ int xcd_tile() {
+    const int nb = gridDim.x, bid = blockIdx.x;
+    const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+
+// Pre-op on a staged item: ELU, or the per-(b,c) affine with padded items (`ok` false) forced to zero - the affine of a
+// padding zero is not zero.  The fused-ReLU clamp stays with each family (fmaxf, split4's floor).
+// (The two generic kernels pass ok = true and mask on their own: folding their mask in here changes their code.)
+template <int PK>
+__device__ __forceinline__ void pre_apply(f32x4& v, const f32x4& sc, const f32x4& sh, bool ok) {
+    if (PK == PK_ELU) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = elu1(v[c]);
+    } else if (PK == PK_AFFINE) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const float y = fmaf(v[c], sc[c], sh[c]); v[c] = ok ? y : 0.f; }
+    }
+}
+template <int PK>
+__device__ __forceinline__ void pre_apply(f32x4& v) {          // the kinds without parameters
+    static_assert(PK != PK_AFFINE, "the affine needs its scale and shift");
+    pre_apply<PK>(v, v, v, true);
+}
+// the floor a fused ReLU puts under the staged values (-inf: none)
+template <int PK>
+__device__ __forceinline__ float relu_floor(const ConvK& p) { return (PK != PK_ELU && p.pre_relu) ? 0.f : -__builtin_inff(); }
 
 
 // Vectorised epilogue.  The MFMA accumulator layout is column-per-lane (one output channel per lane,
@@ -350,13 +384,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32(const ConvK p) {
     const int kc = t & 7;
     const int r0 = t >> 3;
 
-    // XCD-aware tile order: consecutive tiles (same A rows, different N) stay on one XCD's L2.
-    int tile;
-    {
-        const int nb = gridDim.x, bid = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int tile = xcd_tile();
     const int nt = tile % p.NT;
     const int mt = tile / p.NT;
     const int phase = blockIdx.y;
@@ -447,18 +475,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32(const ConvK p) {
 #pragma unroll
         for (int i = 0; i < AP; ++i) {
             f32x4 v = areg[i];
-            if (PK == PK_ELU) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = elu1(v[c]);
-            } else if (PK == PK_AFFINE) {
-                if (!uni_b) {
-                    const long o = (long)max(rb[i], 0) * p.pre_bstride + st_cidx;
-                    sc = *(const f32x4*)(p.pre_scale + o);
-                    sh = *(const f32x4*)(p.pre_shift + o);
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = fmaf(v[c], sc[c], sh[c]);
+            if (PK == PK_AFFINE && !uni_b) {
+                const long o = (long)max(rb[i], 0) * p.pre_bstride + st_cidx;
+                sc = *(const f32x4*)(p.pre_scale + o);
+                sh = *(const f32x4*)(p.pre_shift + o);
             }
+            pre_apply<PK>(v, sc, sh, true);
             if (PK != PK_ELU && p.pre_relu) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f);
@@ -585,21 +607,33 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32(const ConvK p) {
         }
 }
 
+// ---- host side: one launch path, one choice of the instantiation by pre-op kind ----------------------------------
+// f(std::integral_constant<int, PK>) -> the kernel of that pre-op kind (anything but NONE / ELU is the affine)
+template <typename F>
+const void* pick_pk(int pk, F f) {
+    return pk == PK_NONE ? f(std::integral_constant<int, PK_NONE>{})
+         : pk == PK_ELU  ? f(std::integral_constant<int, PK_ELU>{})
+                         : f(std::integral_constant<int, PK_AFFINE>{});
+}
+// opt the kernel in to `lds_cap` bytes of dynamic LDS (once per device and kernel) and launch 256-thread workgroups
+// with `lds_bytes` of it and the argument struct by value
+template <typename Args>
+hipError_t launch_kernel(const void* fn, dim3 grid, size_t lds_bytes, int lds_cap, const Args& k, hipStream_t s) {
+    if (hipError_t e = ensure_dyn_lds(fn, lds_cap); e != hipSuccess) return e;
+    void* args[] = {(void*)&k};
+    return hipLaunchKernel(fn, grid, dim3(256), args, lds_bytes, s);
+}
+
 // one launcher per tile shape; instantiated in conv_tile_*.hip (separate TUs for parallel builds)
 template <int TM, int TN, int WM, int WN>
 hipError_t launch_tile(const ConvK& k, dim3 grid, hipStream_t s, int pk, bool gen) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     const size_t lds = (size_t)2 * (BM + BN) * LDK * sizeof(float);
-    const void* fn = nullptr;
-#define FUSG_PICK(PKV, GENV) fn = (const void*)conv_igemm_f32<TM, TN, WM, WN, PKV, GENV>
-    if (pk == PK_NONE) { if (gen) FUSG_PICK(PK_NONE, true); else FUSG_PICK(PK_NONE, false); }
-    else if (pk == PK_ELU) { if (gen) FUSG_PICK(PK_ELU, true); else FUSG_PICK(PK_ELU, false); }
-    else { if (gen) FUSG_PICK(PK_AFFINE, true); else FUSG_PICK(PK_AFFINE, false); }
-#undef FUSG_PICK
-    if (hipError_t e = ensure_dyn_lds(fn, (int)lds); e != hipSuccess) return e;
-    ConvK kk = k;
-    void* args[] = {(void*)&kk};
-    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+    const void* fn = pick_pk(pk, [gen](auto pkc) {
+        constexpr int PK = decltype(pkc)::value;
+        return gen ? (const void*)conv_igemm_f32<TM, TN, WM, WN, PK, true> : (const void*)conv_igemm_f32<TM, TN, WM, WN, PK, false>;
+    });
+    return launch_kernel(fn, grid, lds, (int)lds, k, s);
 }
 
 hipError_t launch_tile_128x128(const ConvK&, dim3, hipStream_t, int, bool);

@@ -119,12 +119,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_h3(const ConvK p) {
     const int kc = t & 7;
     const int r0 = t >> 3;
 
-    int tile;
-    {
-        const int nb = gridDim.x, bid = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int tile = xcd_tile();
     const int nt = tile % p.NT;
     const int mt = tile / p.NT;
     const int phase = blockIdx.y;
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_h3(const ConvK p) {
         bpiece[j] = q & 3;
     }
 
-    const float vfloor = (PK != PK_ELU && p.pre_relu) ? 0.f : -__builtin_inff();
+    const float vfloor = relu_floor<PK>(p);
     float amax = 0.f;
     struct Stage {
         f32x4 a[AP];
@@ -249,19 +244,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_h3(const ConvK p) {
 #pragma unroll
         for (int i = 0; i < AP; ++i) {
             f32x4 v = areg[i];
-            if (PK == PK_ELU) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = elu1(v[c]);
-            } else if (PK == PK_AFFINE) {
-                if (!uni_b) {
-                    const long o = (long)max(rb[i], 0) * p.pre_bstride + st_cidx;
-                    sc = *(const f32x4*)(p.pre_scale + o);
-                    sh = *(const f32x4*)(p.pre_shift + o);
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = fmaf(v[c], sc[c], sh[c]);
+            if (PK == PK_AFFINE && !uni_b) {
+                const long o = (long)max(rb[i], 0) * p.pre_bstride + st_cidx;
+                sc = *(const f32x4*)(p.pre_scale + o);
+                sh = *(const f32x4*)(p.pre_shift + o);
             }
-            if (PK == PK_AFFINE) {
+            pre_apply<PK>(v, sc, sh, true);
+            if (PK == PK_AFFINE) {                                 // (masked apart from the affine: the order the compiler was given)
                 const bool ok = (okmask >> i) & 1u;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) v[c] = ok ? v[c] : 0.f;
@@ -430,16 +419,11 @@ template <int TM, int TN, int WM, int WN>
 hipError_t launch_h3(const ConvK& k, dim3 grid, hipStream_t s, int pk, bool gen) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     const size_t lds = (size_t)2 * 2 * (BM + BN) * LDH * sizeof(_Float16);
-    const void* fn = nullptr;
-#define FUSG_PICK(PKV, GENV) fn = (const void*)conv_igemm_h3<TM, TN, WM, WN, PKV, GENV>
-    if (pk == PK_NONE) { if (gen) FUSG_PICK(PK_NONE, true); else FUSG_PICK(PK_NONE, false); }
-    else if (pk == PK_ELU) { if (gen) FUSG_PICK(PK_ELU, true); else FUSG_PICK(PK_ELU, false); }
-    else { if (gen) FUSG_PICK(PK_AFFINE, true); else FUSG_PICK(PK_AFFINE, false); }
-#undef FUSG_PICK
-    if (hipError_t e = ensure_dyn_lds(fn, (int)lds); e != hipSuccess) return e;
-    ConvK kk = k;
-    void* args[] = {(void*)&kk};
-    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+    const void* fn = pick_pk(pk, [gen](auto pkc) {
+        constexpr int PK = decltype(pkc)::value;
+        return gen ? (const void*)conv_igemm_h3<TM, TN, WM, WN, PK, true> : (const void*)conv_igemm_h3<TM, TN, WM, WN, PK, false>;
+    });
+    return launch_kernel(fn, grid, lds, (int)lds, k, s);
 }
 
 }  // namespace fusg

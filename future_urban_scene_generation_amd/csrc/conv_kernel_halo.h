@@ -29,7 +29,6 @@
 // Loop nest: source -> 32-channel chunk -> tap;  K index of a (chunk, tap) weight tile in the packed
 // panel = tap * Ctot + channel (same panels as the generic kernel, no re-packing).
 #pragma once
-#include <type_traits>
 #include "conv_kernel_h3.h"
 #ifndef FUSG_HALO_WAVES
 #define FUSG_HALO_WAVES 2
@@ -93,8 +92,6 @@ struct HaloK {
     // launch, which is VALU-issue-bound (profiles/r03_pmc_narrow_layers.txt).
     unsigned m_hw, m_nt, m_tpi, m_tx;
 };
-
-__device__ __forceinline__ int fdiv(int n, unsigned m) { return m ? (int)__umulhi((unsigned)n, m) : n; }     // m == 0: d == 1
 
 __device__ __forceinline__ void pix_offsets_yx(const ConvK& p, int b, int oy, int ox, PixOff& o) {
     long Y, X, cq = 0;
@@ -162,12 +159,7 @@ __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS))
     const int wm = (wave % (WM * WN)) / WN, wn = wave % WN;
     const int kc = t & (CPP - 1);
 
-    int tile;
-    {
-        const int nb = gridDim.x, bid = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int tile = xcd_tile();
     const int mt = fdiv(tile, hk.m_nt);
     const int nt = tile - mt * p.NT;
     int b, t2;
@@ -221,7 +213,7 @@ __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS))
     constexpr int FPT = BF ? 2 : 4;                            // fragments (1 KiB) per 32-column tile: [ct] or [ct][hi|lo]
     const _Float16* wfr = hk.wfrag + ((long)(nt * (BN / 32) + wn * TN) * FPT * 64 + lane) * 8;
     const long wstep = (long)hk.nt32 * FPT * 64 * 8;          // 16-bit elements per (tap, chunk) slab
-    const float vfloor = (PK != PK_ELU && p.pre_relu) ? 0.f : -__builtin_inff();
+    const float vfloor = relu_floor<PK>(p);
     float amax = 0.f;
     const int nchq = p.C0 / CH;                                 // chunks per quadrant (quadrant form)
     const int nch0 = hk.s2d ? 4 * nchq : p.C0 / CH, nch = nch0 + hk.c1k / CH;
@@ -278,14 +270,7 @@ __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS))
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             f32x4 v = S.r[j];
-            if (PK == PK_ELU) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = elu1(v[c]);
-            } else if (PK == PK_AFFINE) {
-                const bool ok = (hvalid >> j) & 1u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { const float y = fmaf(v[c], S.sc[c], S.sh[c]); v[c] = ok ? y : 0.f; }
-            }
+            pre_apply<PK>(v, S.sc, S.sh, (hvalid >> j) & 1u);
             if constexpr (F32) {
                 // (only a fused ReLU clamps: fmaxf(NaN, -inf) would turn a NaN into -inf, and a NaN must reach the output)
                 if (vfloor == 0.f) {
@@ -637,20 +622,17 @@ hipError_t launch_halo(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mod
     lds += TOUCH_LDS_BYTES;
     const int ni = (HP * 8 + 255) / 256;
     if (!halo_fits(k.HH, k.HW)) return hipErrorInvalidValue;
-    const void* fn = nullptr;
-#define FUSG_PICK_NI(PKV, MD)                                                                     \
-    if (ni <= 6) fn = (const void*)conv_halo_h3<TM, TN, WM, WN, PKV, 6, MD, KS>;                  \
-    else if (ni <= 8) fn = (const void*)conv_halo_h3<TM, TN, WM, WN, PKV, 8, MD, KS>;             \
-    else fn = (const void*)conv_halo_h3<TM, TN, WM, WN, PKV, 10, MD, KS>;
-    if (mode == 2) {
-        if (pk == PK_NONE) { FUSG_PICK_NI(PK_NONE, 2) } else if (pk == PK_ELU) { FUSG_PICK_NI(PK_ELU, 2) } else { FUSG_PICK_NI(PK_AFFINE, 2) }
-    } else if (mode == 1) {
-        if (pk == PK_NONE) { FUSG_PICK_NI(PK_NONE, 1) } else if (pk == PK_ELU) { FUSG_PICK_NI(PK_ELU, 1) } else { FUSG_PICK_NI(PK_AFFINE, 1) }
-    } else {
-        if (pk == PK_NONE) { FUSG_PICK_NI(PK_NONE, 0) } else if (pk == PK_ELU) { FUSG_PICK_NI(PK_ELU, 0) } else { FUSG_PICK_NI(PK_AFFINE, 0) }
-    }
-#undef FUSG_PICK_NI
-    if (hipError_t e = ensure_dyn_lds(fn, 96 * 1024 + TOUCH_LDS_BYTES); e != hipSuccess) return e;
+    const void* fn = pick_pk(pk, [ni, mode](auto pkc) {
+        constexpr int PK = decltype(pkc)::value;
+        auto by_ni = [ni](auto mdc) {
+            constexpr int MD = decltype(mdc)::value;
+            return ni <= 6 ? (const void*)conv_halo_h3<TM, TN, WM, WN, PK, 6, MD, KS>
+                 : ni <= 8 ? (const void*)conv_halo_h3<TM, TN, WM, WN, PK, 8, MD, KS>
+                           : (const void*)conv_halo_h3<TM, TN, WM, WN, PK, 10, MD, KS>;
+        };
+        return mode == 2 ? by_ni(std::integral_constant<int, 2>{}) : mode == 1 ? by_ni(std::integral_constant<int, 1>{})
+                                                                               : by_ni(std::integral_constant<int, 0>{});
+    });
     HaloK kk = k;
     kk.RP = halo_row_pitch(k.HW);
     kk.touch_off = touch_off;
@@ -665,8 +647,7 @@ hipError_t launch_halo(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mod
     kk.m_tpi = magic(ntiles, k.tiles_per_img);
     kk.m_tx = magic((long)k.tiles_per_img, k.tiles_x);
     if (!fits) return hipErrorInvalidValue;                    // > 2^32 / d tiles: not a shape this kernel is dispatched for
-    void* args[] = {(void*)&kk};
-    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+    return launch_kernel(fn, grid, lds, 96 * 1024 + TOUCH_LDS_BYTES, kk, s);
 }
 
 hipError_t launch_halo_128(const HaloK&, dim3, hipStream_t, int, int);

@@ -50,11 +50,9 @@ struct SmallK {
     int pad_mode;               // FUSG_PAD_ZERO or FUSG_PAD_REPLICATE (clamped coordinates: the ring windows of the ICN's up-convolutions)
     int RIN, WIN, NPIX;         // staged region per image (rows, columns), pixels in all = nimg * RIN * WIN
     int rpi_shift;              // log2(rpi)
-    unsigned m_wo, m_hw, m_win, m_rw, m_npix, m_taps, m_tpi;   // reciprocals (sdiv) of Wo, Ho*Wo, WIN, RIN*WIN, NPIX, ntaps, tpi: every dividend is < 2^16
+    unsigned m_wo, m_hw, m_win, m_rw, m_npix, m_taps, m_tpi;   // reciprocals (fdiv) of Wo, Ho*Wo, WIN, RIN*WIN, NPIX, ntaps, tpi: every dividend is < 2^16
     int part_off;               // byte offset of the partial tiles in dynamic LDS
 };
-
-__device__ __forceinline__ int sdiv(int n, unsigned m) { return m ? (int)__umulhi((unsigned)n, m) : n; }
 
 template <int PK>
 __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
@@ -70,9 +68,9 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
     // one row (wide) or 32 / Wo whole rows; nimg > 1: the whole outputs of images b0 .. b0 + nimg - 1
     int b0, p0 = 0, oy_t = 0, ox_t = 0;
     if (sk.nimg == 1) {
-        b0 = sdiv(mt, sk.m_tpi);
+        b0 = fdiv(mt, sk.m_tpi);
         p0 = (mt - b0 * sk.tpi) * SMALL_ROWS;
-        oy_t = sdiv(p0, sk.m_wo);
+        oy_t = fdiv(p0, sk.m_wo);
         ox_t = sk.wide ? p0 - oy_t * p.Wo : 0;
     } else {
         b0 = mt * sk.nimg;
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
     struct BSet { h8 f[SMALL_NS][2][2]; };                       // [step][16-column half][hi, lo]
     BSet bw;
     auto step_of = [&](int tt, int& cl, int& tap) __attribute__((always_inline)) {      // step -> (chunk, tap): chunk-major
-        cl = sdiv(tt, sk.m_taps);
+        cl = fdiv(tt, sk.m_taps);
         tap = tt - cl * sk.ntaps;
     };
     auto b_issue = [&](int step0) __attribute__((always_inline)) {
@@ -116,8 +114,8 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
 
     // ---- source pixel of every staged pixel (one thread per pixel: the divisions happen once)
     if (t < NPIX) {
-        const int j = sdiv(t, sk.m_rw), q = t - j * (sk.RIN * sk.WIN);
-        const int ry = sdiv(q, sk.m_win), rx = q - ry * sk.WIN;
+        const int j = fdiv(t, sk.m_rw), q = t - j * (sk.RIN * sk.WIN);
+        const int ry = fdiv(q, sk.m_win), rx = q - ry * sk.WIN;
         const int b = b0 + j;
         int iy = (oy_t + p.qy0) * sk.stride - sk.pad_h + ry, ix = (ox_t + p.qx0) * sk.stride - sk.pad_w + rx;
         bool ok = b < p.B;
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
     __syncthreads();
 
     // ---- stage the input region: gather -> pre-op -> fp16 split -> LDS, every chunk of this K range
-    const float vfloor = (PK != PK_ELU && p.pre_relu) ? 0.f : -__builtin_inff();
+    const float vfloor = relu_floor<PK>(p);
     float amax = 0.f;
     {
         const int kc = t & 7;
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
                 lo_[u] = -1;
                 if (it < nitems) {
                     const int q = it >> 3;
-                    const int c = sdiv(q, sk.m_npix), px = q - c * NPIX;
+                    const int c = fdiv(q, sk.m_npix), px = q - c * NPIX;
                     const int cg = cg0 + c;
                     const bool s1 = cg >= sk.nch0;
                     const int sp = pixsrc[px];
@@ -160,16 +158,13 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
             for (int u = 0; u < UN; ++u) {
                 if (lo_[u] < 0) continue;
                 f32x4 x = v[u];
-                if (PK == PK_ELU) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) x[c] = elu1(x[c]);
-                } else if (PK == PK_AFFINE) {
-                    const int b = min(b0 + sdiv(pxs[u], sk.m_rw), p.B - 1);       // the staged pixel's image (no division by H * W)
+                if constexpr (PK == PK_AFFINE) {
+                    const int b = min(b0 + fdiv(pxs[u], sk.m_rw), p.B - 1);       // the staged pixel's image (no division by H * W)
                     const f32x4 sc = *(const f32x4*)(p.pre_scale + (long)b * p.pre_bstride + cidx[u]);
                     const f32x4 sh = *(const f32x4*)(p.pre_shift + (long)b * p.pre_bstride + cidx[u]);
-                    const bool ok = srcp[u] >= 0;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) { const float y = fmaf(x[c], sc[c], sh[c]); x[c] = ok ? y : 0.f; }
+                    pre_apply<PK>(x, sc, sh, srcp[u] >= 0);
+                } else {
+                    pre_apply<PK>(x);
                 }
                 h4 hi, lo;
                 if constexpr (PK == PK_ELU) split4<false>(x, vfloor, hi, lo, amax); else split4(x, vfloor, hi, lo, amax);
@@ -187,7 +182,7 @@ __global__ __launch_bounds__(256, 1) void conv_small_h3(const SmallK sk) {
         int j = 0, rem = r;
         if (sk.nimg > 1) { j = min(r >> sk.rpi_shift, sk.nimg - 1); rem = r & (sk.rpi - 1); }      // (rows past the last image: masked below)
         int oyl = 0, ox = rem;
-        if (!(sk.nimg == 1 && sk.wide)) { oyl = sdiv(rem, sk.m_wo); ox = rem - oyl * p.Wo; }
+        if (!(sk.nimg == 1 && sk.wide)) { oyl = fdiv(rem, sk.m_wo); ox = rem - oyl * p.Wo; }
         abase[f] = (j * sk.RIN + oyl * sk.stride) * sk.WIN + ox * sk.stride;
     }
     __syncthreads();                                             // the staged image is complete (and pixsrc is dead)

@@ -47,12 +47,7 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
     const int wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
 
-    int tile;
-    {
-        const int nb = gridDim.x, bid = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int tile = xcd_tile();
     const int nt = tile % p.NT;
     const int mt = tile / p.NT;
     const int b = mt / hk.tiles_per_img;
@@ -66,7 +61,7 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
         constexpr int NI = 8;
         const int ipp = hk.CP >> 2;                                // items per pixel
         const int nitems = hk.HH * hk.HW * ipp;                    // <= 256 * NI (checked on the host)
-        const float vfloor = (PK != PK_ELU && p.pre_relu) ? 0.f : -__builtin_inff();
+        const float vfloor = relu_floor<PK>(p);
         float amax = 0.f;
         const long img_pix0 = (long)b * p.H * p.W;
         f32x4 hreg[NI];
@@ -99,17 +94,14 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
         for (int j = 0; j < NI; ++j) {
             if (hoff[j] < 0) continue;
             f32x4 v = hreg[j];
-            if (PK == PK_ELU) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = elu1(v[c]);
-            } else if (PK == PK_AFFINE) {
+            f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+            if (PK == PK_AFFINE) {
                 const int kc4 = ((t + 256 * j) % ipp) * 4;          // channel offset of the item
                 const long o = (long)b * p.pre_bstride + kc4;
-                const f32x4 sc = *(const f32x4*)(p.pre_scale + o), sh = *(const f32x4*)(p.pre_shift + o);
-                const bool ok = (hvalid >> j) & 1u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { const float y = fmaf(v[c], sc[c], sh[c]); v[c] = ok ? y : 0.f; }
+                sc = *(const f32x4*)(p.pre_scale + o);
+                sh = *(const f32x4*)(p.pre_shift + o);
             }
+            pre_apply<PK>(v, sc, sh, (hvalid >> j) & 1u);
             if constexpr (BF) {
                 if (vfloor == 0.f) {
 #pragma unroll
@@ -266,16 +258,12 @@ hipError_t launch_tapunit(const TapUnitK& k, dim3 grid, hipStream_t s, int pk, i
     size_t lds = tapunit_lds_bytes(k.HH, k.RP);
     if (lds < (size_t)4 * TM * 32 * TN * 32 * sizeof(float)) lds = (size_t)4 * TM * 32 * TN * 32 * sizeof(float);   // epilogue detour
     if (lds > 80 * 1024) return hipErrorInvalidValue;
-    const void* fn = nullptr;
-#define FUSG_PICK_U(PKV)                                                                      \
-    fn = mode == 1 ? (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PKV, 8, 1> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PKV, 4, 1>) \
-                   : (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PKV, 8, 0> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PKV, 4, 0>);
-    if (pk == PK_NONE) { FUSG_PICK_U(PK_NONE) } else if (pk == PK_ELU) { FUSG_PICK_U(PK_ELU) } else { FUSG_PICK_U(PK_AFFINE) }
-#undef FUSG_PICK_U
-    if (hipError_t e = ensure_dyn_lds(fn, 80 * 1024); e != hipSuccess) return e;
-    TapUnitK kk = k;
-    void* args[] = {(void*)&kk};
-    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+    const void* fn = pick_pk(pk, [unit, mode](auto pkc) {
+        constexpr int PK = decltype(pkc)::value;
+        return mode == 1 ? (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 8, 1> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 4, 1>)
+                         : (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 8, 0> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 4, 0>);
+    });
+    return launch_kernel(fn, grid, lds, 80 * 1024, k, s);
 }
 
 hipError_t launch_tapunit_128(const TapUnitK&, dim3, hipStream_t, int, int, int);

@@ -39,12 +39,7 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_f32(const TapUnitF hk) {
     const int lane = t & 63;
     const int wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    int tile;
-    {
-        const int nb = gridDim.x, bid = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = bid & 7, j = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int tile = xcd_tile();
     const int nt = tile % p.NT;
     const int mt = tile / p.NT;
     const int b = mt / hk.tiles_per_img;
@@ -87,17 +82,14 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_f32(const TapUnitF hk) {
         for (int j = 0; j < NI; ++j) {
             if (hoff[j] < 0) continue;
             f32x4 v = hreg[j];
-            if (PK == PK_ELU) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = elu1(v[c]);
-            } else if (PK == PK_AFFINE) {
+            f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+            if (PK == PK_AFFINE) {
                 const int kc4 = ((t + 256 * j) % ipp) * 4;
                 const long o = (long)b * p.pre_bstride + kc4;
-                const f32x4 sc = *(const f32x4*)(p.pre_scale + o), sh = *(const f32x4*)(p.pre_shift + o);
-                const bool ok = (hvalid >> j) & 1u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { const float y = fmaf(v[c], sc[c], sh[c]); v[c] = ok ? y : 0.f; }
+                sc = *(const f32x4*)(p.pre_scale + o);
+                sh = *(const f32x4*)(p.pre_shift + o);
             }
+            pre_apply<PK>(v, sc, sh, (hvalid >> j) & 1u);
             if (PK != PK_ELU && p.pre_relu) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f);
@@ -215,13 +207,8 @@ hipError_t launch_tapunit_f32(const TapUnitF& k, dim3 grid, hipStream_t s, int p
     size_t lds = (size_t)k.HH * k.RP * sizeof(float);
     if (lds < (size_t)4 * TM * 32 * TN * 32 * sizeof(float)) lds = (size_t)4 * TM * 32 * TN * 32 * sizeof(float);   // epilogue detour
     if (lds > 80 * 1024) return hipErrorInvalidValue;
-    const void* fn = pk == PK_NONE ? (const void*)conv_tapunit_f32<TM, TN, WM, WN, PK_NONE>
-                   : pk == PK_ELU  ? (const void*)conv_tapunit_f32<TM, TN, WM, WN, PK_ELU>
-                                   : (const void*)conv_tapunit_f32<TM, TN, WM, WN, PK_AFFINE>;
-    if (hipError_t e = ensure_dyn_lds(fn, 80 * 1024); e != hipSuccess) return e;
-    TapUnitF kk = k;
-    void* args[] = {(void*)&kk};
-    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+    const void* fn = pick_pk(pk, [](auto pkc) { return (const void*)conv_tapunit_f32<TM, TN, WM, WN, decltype(pkc)::value>; });
+    return launch_kernel(fn, grid, lds, 80 * 1024, k, s);
 }
 
 hipError_t launch_tapunit_f32_128(const TapUnitF&, dim3, hipStream_t, int);
