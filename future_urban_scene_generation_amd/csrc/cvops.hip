@@ -27,7 +27,8 @@ static inline unsigned blocks2d(long total) { return (unsigned)((total + 255) / 
 // dst(x, y) = bilinear(src, Minv * (x, y, 1)): coordinates in double, rounded to 1/32 pixel (INTER_BITS = 5), weights
 // (32-ax)(32-ay)*32 ... in 15-bit fixed point (table entry (0,0) is (32767, 0, 0, 1): imgwarp.cpp initInterTab2D),
 // (sum + 2^14) >> 15, constant border 0.
-// index (optional, device int32 [jobs][2]): job n reads image index[2n] of src and writes image index[2n + 1] of dst.
+// index (optional, device int32 [jobs][2]): job n reads image index[2n] of src and writes image index[2n + 1] of dst; a
+// job whose source is negative writes nothing (the empty rows of fusg_plane_homographies' fixed-size table).
 __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, const double* __restrict__ minv, U8View dst, long total,
                                                                   const int* __restrict__ index) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -36,6 +37,7 @@ __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, co
     const long r = idx / dst.w;
     const int y = (int)(r % dst.h);
     const int n = (int)(r / dst.h);
+    if (index && index[2 * n] < 0) return;
     const double* M = minv + (long)n * 9;
     const double X0 = M[0] * x + M[1] * y + M[2];
     const double Y0 = M[3] * x + M[4] * y + M[5];

@@ -175,7 +175,8 @@ class VehiclePipeline:
     """Holds the five networks on one device and runs batches of crops through them."""
 
     def __init__(self, device, inpaint: bool = False, state_dicts: Optional[Dict[str, dict]] = None, seed: int = 0,
-                 broadcast_src: Optional[int] = None, group=None, cad: bool = False, cad_bank=None):
+                 broadcast_src: Optional[int] = None, group=None, cad: bool = False, cad_bank=None,
+                 device_homography: bool = False):
         """state_dicts: checkpoints (the reference's keys) per network; a missing network gets the synthetic weights of
         `seed`.  broadcast_src: with an initialised process group, only that rank needs to hold `state_dicts` (a real
         checkpoint read from disk on rank 0): they are distributed with `broadcast_state_dicts` first (north_star: RCCL
@@ -184,7 +185,10 @@ class VehiclePipeline:
         run_test.py:47-58) and run it on the hourglass's crop in every pass (trajectory_inference.py:66-69): 'cad_logits' /
         `run_frame`'s 'cad_idx'.  Not part of BASELINE's crop pass: `bench.py` leaves it off.
         cad_bank: a `render.CadBank` - enables the geometry mode of `run_frame` / `run_later_frame` (a scene without 'masks':
-        the sketches, masks, planes and visibilities are rendered on the device from the fitted pose)."""
+        the sketches, masks, planes and visibilities are rendered on the device from the fitted pose).
+        device_homography: the frame drivers gate the planes and fit their homographies on the device
+        (`planes_utils.plane_homographies_device` + `warp_planes_fitted`) instead of on the host (`warp_jobs_frame` +
+        `warp_planes_batch`, the default and the reference-signature path)."""
         from .edgeconnect.models import EdgeModel, InpaintingModel
         from .stacked_hourglass.models import HourglassNet
         from .synth import synth_state_dict
@@ -195,6 +199,7 @@ class VehiclePipeline:
         self.group = group
         self.cad = None
         self.cad_bank = cad_bank
+        self.device_homography = bool(device_homography)
         if broadcast_src is not None:
             import torch.distributed as dist
             if not _one_rank(group):
@@ -1124,13 +1129,14 @@ class VehiclePipeline:
             cp = self._plan(pkey) if replay else None
             tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
             # ---- host: the homography fits of every plane of every vehicle (1.2 ms for 8 vehicles), before any launch
-            jobs = pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
+            jobs = None if self.device_homography else \
+                pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
             # ---- uint8 glue on the caller's stream
             geom_box = fo.box_geometry((H, W), bboxes, dev)
             img_bbox = fo.crop_resize(frame, geom_box, (R, R), 0)                              # :58-60
             hg_x = fo.crop_resize(frame, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD, out=tgt.get("hg_x"))   # :61-65
             central = fo.central_crop(img_bbox)                                                # vehicle_utils.py:49-52
-            warped = pu.warp_planes_batch(scene["src_planes"], jobs)                           # :171-175
+            warped = self._warp_planes(scene, jobs)                                            # :171-175
             _, geom = fo.mask_bbox_geom(scene["masks"])
             icn_x = pu.icn_inputs_device(warped, scene["dst_sketch"], central, geom, R, R, out=tgt.get("icn_x"))   # :179-180
             vu_x, vu_y = fo.vunet_inputs(frame, scene["masks"], scene["src_sketch"], scene["dst_sketch"], geom, R,
@@ -1151,6 +1157,15 @@ class VehiclePipeline:
             if "cad_logits" in out:
                 out["cad_idx"] = out.pop("cad_logits").argmax(1)                               # :69
         return out
+
+    def _warp_planes(self, scene, jobs):
+        """The source planes warped to the destination pose: from the host-fitted `jobs`, or (device_homography) from the
+        tables one kernel fits on the device."""
+        from .warp_learn import planes_utils as pu
+        if not self.device_homography:
+            return pu.warp_planes_batch(scene["src_planes"], jobs)
+        minv, index = pu.plane_homographies_device(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"], self.device)
+        return pu.warp_planes_fitted(scene["src_planes"], minv, index)
 
     @torch.no_grad()
     def _frame_finish(self, scene, out):
@@ -1270,8 +1285,9 @@ class VehiclePipeline:
         with torch.cuda.device(dev):
             if V == 0:
                 return self._no_vehicles(R, "icn_u8", "vunet_u8", "geom")
-            jobs = pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
-            warped = pu.warp_planes_batch(scene["src_planes"], jobs)                           # :376-381
+            jobs = None if self.device_homography else \
+                pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
+            warped = self._warp_planes(scene, jobs)                                            # :376-381
             _, geom = fo.mask_bbox_geom(scene["masks"])
             icn_x = pu.icn_inputs_device(warped, scene["dst_sketch"], state["central"], geom, R, R)   # :385-387
             _, vu_y = fo.vunet_inputs(frame, scene["masks"], scene["dst_sketch"], scene["dst_sketch"], geom, R)   # :415-420 (y_tilde only)

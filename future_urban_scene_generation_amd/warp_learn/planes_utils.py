@@ -392,6 +392,129 @@ def warp_planes_batch(src_planes: torch.Tensor, jobs_per_vehicle) -> torch.Tenso
     return warped.view(V, P, H, W, 3)
 
 
+# ---------------------------------------------------------------------------------------------- device homographies
+def find_homography_host(src_points, dst_points) -> Optional[np.ndarray]:
+    """`find_homography` computed by libfusg's host twin of the device solver (csrc/homography.h run on the CPU: the same
+    normalised DLT, through a cyclic Jacobi eigen-decomposition instead of LAPACK's, and the same Levenberg-Marquardt loop).
+    None where the twin reports the fit invalid.  Needs no GPU."""
+    s = np.ascontiguousarray(np.asarray(src_points, dtype=np.float64).reshape(-1, 2))
+    d = np.ascontiguousarray(np.asarray(dst_points, dtype=np.float64).reshape(-1, 2))
+    if len(s) != len(d):
+        return None
+    H = np.zeros(9)
+    ok = L.lib().fusg_find_homography_host(s.ctypes.data, d.ctypes.data, len(s), H.ctypes.data, None)
+    return H.reshape(3, 3) if ok else None
+
+
+def pack_plane_points(kp_v, P: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-vehicle lists of P corner-point arrays [n_p, 2] -> (int32 [V, P, MAX_VERTS, 2] zero-padded, int32 [V, P] counts)."""
+    V = len(kp_v)
+    pts = np.zeros((V, P, MAX_VERTS, 2), dtype=np.int32)
+    nv = np.zeros((V, P), dtype=np.int32)
+    for v in range(V):
+        if len(kp_v[v]) != P:
+            raise ValueError(f"vehicle {v}: {len(kp_v[v])} planes, expected {P}")
+        for i in range(P):
+            a = np.asarray(kp_v[v][i])
+            if a.ndim != 2 or a.shape[1] != 2 or len(a) > MAX_VERTS or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"vehicle {v} plane {i}: corner points must be integers [n <= {MAX_VERTS}, 2] (plane_polygons)")
+            pts[v, i, :len(a)] = a
+            nv[v, i] = len(a)
+    return pts, nv
+
+
+def _sym_planes(pascal_class: str = "car", texture_planes=None) -> Tuple[int, int, int]:
+    keys = list((texture_planes or pascal_texture_planes)[pascal_class].keys())
+    return len(keys), keys.index("left"), keys.index("right")
+
+
+def plane_homographies_device(src_kp, dst_kp, src_vis, dst_vis, device=None, pascal_class: str = "car", texture_planes=None,
+                              nverts=None, return_matrices: bool = False):
+    """`warp_jobs_frame` + the inversion and slot rule of `warp_planes_batch` on the device (fusg_plane_homographies): the
+    gate, both fits per plane and the inverse of H12 for every vehicle of a frame in one launch, nothing read back.
+
+    src_kp / dst_kp: the host lists a scene carries ([V][P] of int32 [n, 2], `plane_polygons`; every vehicle has the same
+    point count per plane) with src_vis / dst_vis host [V, P] - packed into ONE pinned upload -, or CUDA tensors already in
+    the padded layout: int32 [V, P, 8, 2], uint8 [V, P], and `nverts` int32 [P].
+    Returns (minv float64 [V * P, 9], index int32 [V * P, 2]): the tables `warp_planes_fitted` consumes; index[r, 0] = -1
+    where slot r receives no plane.  return_matrices=True adds H float64 [V, P, 2, 3, 3] (H12, H21 of the slot's job) and
+    status int32 [V, P] (0 nothing gated onto the slot, 1 job, 2 gated but the fit is invalid)."""
+    P, sa, sb = _sym_planes(pascal_class, texture_planes)
+    if isinstance(src_kp, torch.Tensor):
+        sp, dp, sv, dv, nv = src_kp, dst_kp, src_vis, dst_vis, nverts
+        dev = sp.device
+        V = int(sp.shape[0])
+        ok = all(isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.device == dev for t in (sp, dp, sv, dv, nv))
+        if not ok or sp.dtype != torch.int32 or dp.dtype != torch.int32 or nv.dtype != torch.int32 or sv.dtype != torch.uint8 or \
+                dv.dtype != torch.uint8 or tuple(sp.shape) != (V, P, MAX_VERTS, 2) or tuple(dp.shape) != (V, P, MAX_VERTS, 2) or \
+                tuple(sv.shape) != (V, P) or tuple(dv.shape) != (V, P) or tuple(nv.shape) != (P,):
+            raise ValueError("plane_homographies_device: device inputs are contiguous int32 [V, P, 8, 2] points, uint8 [V, P] "
+                             "visibilities and int32 [P] nverts on one device")
+    else:
+        dev = _device(device)
+        V = len(src_kp)
+        spn, nvs = pack_plane_points(src_kp, P)
+        dpn, nvd = pack_plane_points(dst_kp, P)
+        nvn = nvs[0] if V else np.zeros(P, np.int32)
+        if V and not ((nvs == nvn).all() and (nvd == nvn).all()):
+            raise ValueError("plane_homographies_device: every vehicle must have the same number of corner points per plane")
+        svn = (np.asarray(src_vis).reshape(V, P) != 0).astype(np.uint8)
+        dvn = (np.asarray(dst_vis).reshape(V, P) != 0).astype(np.uint8)
+        # one upload: [points src | points dst | nverts] as int32, then the visibility bytes (a multiple of 4 before them)
+        words = np.concatenate([spn.reshape(-1), dpn.reshape(-1), nvn.reshape(-1)])
+        blob = ops.h2d(np.concatenate([words.view(np.uint8), svn.reshape(-1), dvn.reshape(-1)]), dev)
+        n_pts, n_vis = V * P * MAX_VERTS * 2, V * P
+        iw = blob[:4 * words.size].view(torch.int32)
+        sp, dp, nv = iw[:n_pts], iw[n_pts:2 * n_pts], iw[2 * n_pts:]
+        sv, dv = blob[4 * words.size:4 * words.size + n_vis], blob[4 * words.size + n_vis:]
+    minv = torch.empty((V * P, 9), dtype=torch.float64, device=dev)
+    index = torch.empty((V * P, 2), dtype=torch.int32, device=dev)
+    Hm = torch.empty((V, P, 2, 3, 3), dtype=torch.float64, device=dev) if return_matrices else None
+    st = torch.empty((V, P), dtype=torch.int32, device=dev) if return_matrices else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().fusg_plane_homographies(sp.data_ptr(), dp.data_ptr(), nv.data_ptr(), sv.data_ptr(), dv.data_ptr(), V, P, sa, sb,
+                                                minv.data_ptr(), index.data_ptr(), Hm.data_ptr() if return_matrices else None,
+                                                st.data_ptr() if return_matrices else None, ops.stream_ptr()), "plane_homographies")
+    return (minv, index, Hm, st) if return_matrices else (minv, index)
+
+
+def plane_homographies_host(src_kp, dst_kp, src_vis, dst_vis, pascal_class: str = "car", texture_planes=None):
+    """The tables of `plane_homographies_device` computed on the CPU by the same code (fusg_plane_homographies_host): numpy
+    (minv [V * P, 9], index [V * P, 2], H [V, P, 2, 3, 3], status [V, P]).  Needs no GPU; the device's tables equal these bit
+    for bit."""
+    P, sa, sb = _sym_planes(pascal_class, texture_planes)
+    V = len(src_kp)
+    sp, nvs = pack_plane_points(src_kp, P)
+    dp, nvd = pack_plane_points(dst_kp, P)
+    nv = np.ascontiguousarray(nvs[0]) if V else np.zeros(P, np.int32)
+    if V and not ((nvs == nv).all() and (nvd == nv).all()):
+        raise ValueError("plane_homographies_host: every vehicle must have the same number of corner points per plane")
+    sv = np.ascontiguousarray((np.asarray(src_vis).reshape(V, P) != 0).astype(np.uint8))
+    dv = np.ascontiguousarray((np.asarray(dst_vis).reshape(V, P) != 0).astype(np.uint8))
+    minv, index = np.zeros((V * P, 9)), np.zeros((V * P, 2), np.int32)
+    Hm, st = np.zeros((V, P, 2, 3, 3)), np.zeros((V, P), np.int32)
+    L.check(L.lib().fusg_plane_homographies_host(sp.ctypes.data, dp.ctypes.data, nv.ctypes.data, sv.ctypes.data, dv.ctypes.data, V, P,
+                                                 sa, sb, minv.ctypes.data, index.ctypes.data, Hm.ctypes.data, st.ctypes.data),
+            "plane_homographies_host")
+    return minv, index, Hm, st
+
+
+def warp_planes_fitted(src_planes: torch.Tensor, minv: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """`warp_planes_batch` from the device tables of `plane_homographies_device`: src_planes CUDA uint8 [V, P, H, W, 3] ->
+    [V, P, H, W, 3], zeros where nothing is warped.  One launch over the V * P rows; a row without a job writes nothing."""
+    V, P, H, W, _ = src_planes.shape
+    if minv.dtype != torch.float64 or index.dtype != torch.int32 or tuple(minv.shape) != (V * P, 9) or \
+            tuple(index.shape) != (V * P, 2) or not (minv.is_contiguous() and index.is_contiguous()):
+        raise ValueError("warp_planes_fitted: minv float64 [V * P, 9] and index int32 [V * P, 2], contiguous")
+    flat = src_planes.reshape(V * P, H, W, 3).contiguous()
+    warped = torch.zeros_like(flat)
+    if V:
+        with torch.cuda.device(flat.device):
+            L.check(L.lib().fusg_warp_perspective_indexed_u8(C.byref(_u8desc(flat)), minv.data_ptr(), index.data_ptr(), V * P,
+                                                             C.byref(_u8desc(warped)), ops.stream_ptr()), "warp_perspective_indexed_u8")
+    return warped.view(V, P, H, W, 3)
+
+
 def warp_unwarp_planes(src_planes: Image, src_planes_kpoints: List[np.ndarray], dst_planes_kpoints: List[np.ndarray],
                        src_visibilities, dst_visibilities, pascal_class: str, pascal_texture_planes=pascal_texture_planes,
                        unwarp: bool = True):

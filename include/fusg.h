@@ -477,6 +477,34 @@ int fusg_plane_visibility(const int32_t* pts_xy, const int32_t* nverts, const in
                           int32_t w, int32_t* counts, void* stream);
 int fusg_sizeof_render_job(void);
 
+/* ---- plane homographies (the stage between the plane corner points and fusg_warp_perspective_indexed_u8) ---------- */
+/* warp_jobs + find_homography (warp_learn/planes_utils.py) + the slot rule and the inversion of warp_planes_batch for V
+ * vehicles of P <= 8 planes in one launch.  DEVICE inputs: src_pts / dst_pts int32 [V][P][8][2] (corner points, padded),
+ * nverts int32 [P] (corner points of plane p; a fit needs 4..8 and equal counts on both sides), src_vis / dst_vis uint8
+ * [V][P] (0 / 1).  sym_a, sym_b: the two symmetric planes (left, right), or -1, -1.  Per vehicle and source plane i:
+ * i is warped when it is visible in the source and its destination is visible - its own slot i, or, for a symmetric
+ * plane whose own destination is hidden, its partner's slot; H12 (src -> dst) and H21 (dst -> src) are fitted in double
+ * (normalised DLT through a cyclic Jacobi eigen-decomposition, Levenberg-Marquardt for more than 4 points) and the job
+ * exists when both fits and the inverse of H12 are valid; of two jobs on one slot the higher plane index wins.
+ * DEVICE outputs, one row per (vehicle, destination slot), row = v * P + j:
+ *   minv double [V * P][9]   inverse of the winning H12 (zeros: no job)
+ *   index int32 [V * P][2]   (source image v * P + i, or -1: no job; destination image = row) - with minv the arguments of
+ *                            fusg_warp_perspective_indexed_u8(jobs = V * P), which skips the rows of source -1
+ *   H double [V][P][2][9]    optional (NULL): the winning job's H12, H21 (zeros: no job)
+ *   status int32 [V][P]      optional (NULL): 0 no plane gated onto the slot, 1 job, 2 gated but no valid fit
+ * V = 0 launches nothing.  Results are bit-identical to fusg_plane_homographies_host (the same code, no contraction). */
+int fusg_plane_homographies(const int32_t* src_pts, const int32_t* dst_pts, const int32_t* nverts, const uint8_t* src_vis,
+                            const uint8_t* dst_vis, int32_t V, int32_t P, int32_t sym_a, int32_t sym_b, double* minv,
+                            int32_t* index, double* H, int32_t* status, void* stream);
+/* The same tables computed on the CPU from HOST arrays (no GPU needed). */
+int fusg_plane_homographies_host(const int32_t* src_pts, const int32_t* dst_pts, const int32_t* nverts, const uint8_t* src_vis,
+                                 const uint8_t* dst_vis, int32_t V, int32_t P, int32_t sym_a, int32_t sym_b, double* minv,
+                                 int32_t* index, double* H, int32_t* status);
+/* One fit on the CPU: src_xy / dst_xy HOST double [n][2] -> H_out [9] (H[8] = 1) and, when minv_out is not NULL, its
+ * inverse.  Returns 1, or 0 where planes_utils.find_homography returns None (n < 4, a zero deviation, rank loss) or H
+ * is singular; the outputs are zeros then. */
+int fusg_find_homography_host(const double* src_xy, const double* dst_xy, int32_t n, double* H_out, double* minv_out);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)
