@@ -45,7 +45,7 @@ class ConvDesc(C.Structure):            # fusg_conv_desc
                 ("tile_list", C.c_void_p), ("tile_count", C.c_int32), ("q_oy", C.c_int32), ("q_ox", C.c_int32),
                 ("stats_slots", C.c_int32),
                 ("wscale", C.c_void_p), ("status", C.c_void_p), ("wfrag_bf16", C.c_void_p), ("wfrag_f32", C.c_void_p),
-                ("splitk_counters", C.c_void_p), ("splitk_counters_len", C.c_int32), ("_pad2", C.c_int32)]
+                ("splitk_counters", C.c_void_p), ("splitk_counters_len", C.c_int32), ("tap_sparse", C.c_int32)]
 
 
 class BneckDesc(C.Structure):           # fusg_bneck_desc

@@ -1,0 +1,5 @@
+// Tap-sparse instantiations of the halo kernel (conv_kernel_halo.h, SP): BN = 32 column tile, K split over the four waves - the shape of conv_halo_32k.hip.
+#include "conv_kernel_halo.h"
+namespace fusg {
+hipError_t launch_halo_ts_32k(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode, int sp) { return launch_halo_ts<4,1,1,1,4>(k, grid, s, pk, mode, sp); }
+}  // namespace fusg

@@ -301,6 +301,7 @@ struct ConvRoute {
     int bn;                     // halo / tap-unit: column-tile width
     bool ksw;                   // halo: K split over the waves (the 64k / 32k instantiations)
     bool s2d;                   // halo: parity-quadrant form
+    int sp;                     // halo: tap-sparse pattern the launch skips by (fusg_conv_desc.tap_sparse), 0 = dense
     int HH, HW;                 // halo / tap-unit: halo extent in (virtual) input pixels
     int RP, unit;               // tap-unit: LDS pitch of a halo row, channels per K unit
 };
@@ -339,6 +340,18 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
     }
     const int nphase = d->nphase > 0 ? d->nphase : 1;
     FUSG_CHECK(nphase == 1 || nphase == 4, "conv2d: nphase %d", nphase);
+    r->sp = 0;
+    if (d->tap_sparse != 0) {
+        // the patterns describe ONE weight form (include/fusg.h): anything else would run dense weights that are not the layer
+        if (!((d->tap_sparse == 1 || d->tap_sparse == 2) && d->kh == 3 && d->kw == 3 && d->pad_h == 1 && d->pad_w == 1 &&
+              d->stride == 1 && d->dil == 1 && d->upsample == 0 && d->pad_mode == FUSG_PAD_ZERO && d->store_mode == FUSG_STORE_D2S && nphase == 1 &&
+              d->cout > 0 && d->cout % 128 == 0 && d->cout_pad == d->cout)) {
+            set_error("conv2d: tap_sparse %d needs a 3x3 zero-pad 1 stride 1 dil 1 D2S launch with nphase 1 and cout %% 128 == 0 "
+                      "(kh %d kw %d pad %d,%d stride %d dil %d store %d nphase %d cout %d)", d->tap_sparse, d->kh, d->kw,
+                      d->pad_h, d->pad_w, d->stride, d->dil, d->store_mode, nphase, d->cout);
+            return FUSG_ERR_UNSUPPORTED;
+        }
+    }
     FUSG_CHECK(d->qh > 0 && d->qw > 0, "conv2d: empty output grid");
     FUSG_CHECK(d->q_oy >= 0 && d->q_ox >= 0 && (d->store_mode == FUSG_STORE_NORMAL || (d->q_oy | d->q_ox) == 0) &&
                !(d->stats_out && (d->q_oy | d->q_ox)), "conv2d: q-space origin (%d, %d)", d->q_oy, d->q_ox);
@@ -493,6 +506,8 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
                      ((r->bn == 32 && ntaps >= 4) || (r->bn == 64 && ntaps >= 2));
             const bool bf = want_bf16 && aligned16(d->wfrag_bf16);
             r->mode = f32_frag ? 2 : (bf ? 1 : 0);
+            // tap-sparse weights: the sibling instantiations skip the dead taps (bf16 has none: it runs the dense weights)
+            r->sp = r->mode != 1 ? d->tap_sparse : 0;
             r->family = f32_frag ? FUSG_CONV_HALO_F32 : bf ? FUSG_CONV_HALO_BF16 : (s2d ? FUSG_CONV_HALO_S2D : FUSG_CONV_HALO);
             return FUSG_OK;
         }
@@ -598,6 +613,10 @@ static hipError_t run_halo(const ConvK& k, const fusg_conv_desc& d, const ConvRo
         h.c.MT = (int)d.src0.n * d.tile_count;
     }
     const dim3 grid(h.c.MT * h.c.NT, 1, 1);
+    if (r.sp)
+        return r.bn == 128 ? launch_halo_ts_128(h, grid, s, pk, r.mode, r.sp)
+                           : r.bn == 64 ? (r.ksw ? launch_halo_ts_64k(h, grid, s, pk, r.mode, r.sp) : launch_halo_ts_64(h, grid, s, pk, r.mode, r.sp))
+                                        : (r.ksw ? launch_halo_ts_32k(h, grid, s, pk, r.mode, r.sp) : launch_halo_ts_32(h, grid, s, pk, r.mode, r.sp));
     return r.bn == 128 ? launch_halo_128(h, grid, s, pk, r.mode)
                        : r.bn == 64 ? (r.ksw ? launch_halo_64k(h, grid, s, pk, r.mode) : launch_halo_64(h, grid, s, pk, r.mode))
                                     : (r.ksw ? launch_halo_32k(h, grid, s, pk, r.mode) : launch_halo_32(h, grid, s, pk, r.mode));

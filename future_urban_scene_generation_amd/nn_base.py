@@ -72,6 +72,23 @@ class WNConvP(nn.Module):
             self.bias.uniform_(-bound, bound)
 
 
+class WNConvTP(nn.Module):
+    """Holder with the schema of weight_norm(nn.ConvTranspose2d, dim=1): bias, weight_g [1, cout, 1, 1], weight_v
+    [cin, cout, k, k] (the norm runs over the input channels and the taps of each OUTPUT channel)."""
+
+    def __init__(self, cin: int, cout: int, k: int):
+        super().__init__()
+        self.cin, self.cout, self.k = cin, cout, k
+        self.bias = nn.Parameter(torch.empty(cout))
+        v = torch.empty(cin, cout, k, k)
+        nn.init.kaiming_uniform_(v, a=math.sqrt(5))
+        self.weight_g = nn.Parameter(v.permute(1, 0, 2, 3).reshape(cout, -1).norm(dim=1).reshape(1, cout, 1, 1).clone())
+        self.weight_v = nn.Parameter(v)
+        with torch.no_grad():
+            bound = 1 / math.sqrt(cout * k * k)                # torch's fan_in of a transposed filter: shape[1] * k * k
+            self.bias.uniform_(-bound, bound)
+
+
 class SNConvP(nn.Module):
     """Holder with the schema of nn.utils.spectral_norm(conv): [bias], weight_orig, weight_u, weight_v."""
 

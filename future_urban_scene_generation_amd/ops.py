@@ -371,13 +371,22 @@ def _workspace(device, nbytes: int) -> torch.Tensor:
     return ws
 
 
+# Do launches of tap-sparse plans (ConvPlan.tap_sparse: VUnet UpSample 'nearest' / 'conv2d_t') hand their pattern to the library,
+# i.e. run the halo kernel's tap-skipping instantiations?  Same bytes either way.  Off by default: the sparse launches have not
+# been timed against the dense ones yet (tools/upmodes_time.py), and an unmeasured kernel does not become the
+# default route.  FUSG_TAP_SPARSE=1 (read at import) or `ops.TAP_SPARSE_LAUNCH = True` turns them on; ops.conv(tap_sparse=...)
+# decides per launch.
+TAP_SPARSE_LAUNCH = _os.environ.get("FUSG_TAP_SPARSE", "0") == "1"
+
+
 def _conv_desc(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
                out_c_off: int = 0, res0: Optional[torch.Tensor] = None, res1: Optional[torch.Tensor] = None,
                pre_op: int = L.PRE_NONE, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_bstride: int = 0,
                act: int = L.ACT_NONE, store: int = L.STORE_NORMAL, nchw_out: bool = False, tile: int = L.TILE_AUTO,
                ksplit: int = 0, precision: Optional[str] = None, want_stats: bool = False,
                out_stride: int = 1, out_off: Tuple[int, int] = (0, 0), tiles: Optional[torch.Tensor] = None,
-               q_window: Optional[Tuple[int, int, int, int]] = None, q_size: Optional[Tuple[int, int]] = None):
+               q_window: Optional[Tuple[int, int, int, int]] = None, q_size: Optional[Tuple[int, int]] = None,
+               tap_sparse: Optional[int] = None):
     """The fusg_conv_desc of an ops.conv launch before planning -> (desc, out).  Takes CPU tensors too (no launch, no
     torch.cuda call when a `status_scope` is open): tests describe launches to fusg_conv2d_route this way."""
     plan.to(x0.device)
@@ -450,6 +459,7 @@ def _conv_desc(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = No
         assert tiles.dtype == torch.int32 and tiles.is_contiguous() and tiles.device == x0.device
         d.tile_list, d.tile_count = tiles.data_ptr(), int(tiles.numel())
     d.dst_c_off = int(out_c_off)
+    d.tap_sparse = int((plan.tap_sparse if TAP_SPARSE_LAUNCH else 0) if tap_sparse is None else tap_sparse)
     d.tile, d.ksplit = int(tile), int(ksplit)
     d.precision = _PREC[precision or PRECISION]
     d.wpack_h = dev["wpack_h"].data_ptr()
@@ -479,7 +489,7 @@ def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *,
          ksplit: int = 0, precision: Optional[str] = None, want_stats: bool = False,
          out_stride: int = 1, out_off: Tuple[int, int] = (0, 0), tiles: Optional[torch.Tensor] = None,
          q_window: Optional[Tuple[int, int, int, int]] = None, q_size: Optional[Tuple[int, int]] = None,
-         stats_into: Optional[Tuple[torch.Tensor, int]] = None):
+         stats_into: Optional[Tuple[torch.Tensor, int]] = None, tap_sparse: Optional[int] = None):
     """One fused convolution launch (fusg_conv2d).  Returns the output tensor (allocated NHWC-physical
     unless `out` is given or `nchw_out` asks for a standard-contiguous NCHW result).
     out_stride / out_off: write output pixel (qy, qx) at (qy*out_stride + out_off[0], qx*out_stride + out_off[1])
@@ -487,11 +497,12 @@ def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *,
     (halo-kernel launches only).  q_window = (oy, ox, h, w): compute only that window of the output grid (into the
     same positions of `out`, which must be given).  q_size = (qh, qw): output grid of a launch whose padding is not
     symmetric (transposed-conv phases; zero padding only).  stats_into = (buffer [B, slots, cout, 2], first_slot): write
-    this launch's fused statistics slots there (the launch must qualify)."""
+    this launch's fused statistics slots there (the launch must qualify).  tap_sparse: the fusg_conv_desc.tap_sparse pattern
+    of this launch (0 runs a tap-sparse plan's weights dense: same bytes); None: the plan's if TAP_SPARSE_LAUNCH, else 0."""
     d, out = _conv_desc(plan, x0, x1, out=out, out_c_off=out_c_off, res0=res0, res1=res1, pre_op=pre_op, pre=pre,
                         pre_bstride=pre_bstride, act=act, store=store, nchw_out=nchw_out, tile=tile, ksplit=ksplit,
                         precision=precision, want_stats=want_stats, out_stride=out_stride, out_off=out_off, tiles=tiles,
-                        q_window=q_window, q_size=q_size)
+                        q_window=q_window, q_size=q_size, tap_sparse=tap_sparse)
     b, qh, qw = x0.shape[0], d.qh, d.qw
     lib = L.lib()
     nbytes = lib.fusg_conv2d_plan(C.byref(d))

@@ -45,6 +45,7 @@ class ConvPlan:
     flops_per_pixel: float = 0.0   # algorithmic 2*MAC per q-space output pixel (all phases: per input pixel)
     pad_w: int = -1                # horizontal padding when it differs from `pad` (row-split heads: 0)
     rowsplit: Optional[dict] = None
+    tap_sparse: int = 0            # fusg_conv_desc.tap_sparse: 0 none, 1 nearest-up2-k3, 2 transpose-k3s2p1 (TAP_SPARSE_AXIS)
     dev: dict = field(default_factory=dict)
 
     def to(self, device) -> "ConvPlan":
@@ -393,6 +394,78 @@ def pack_conv_up2_phases(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> 
     return [pack_conv(wp, bias, stride=1, pad=1, pad_mode=L.PAD_REPLICATE) for wp in up2_phase_weights(weight)]
 
 
+# ---- the VUnet's 'nearest' and 'conv2d_t' upsampling as ONE 3x3 pad-1 conv of the low-res image with a DepthToSpace store ----
+# Output pixel (2y + py, 2x + px) is channel block 2 py + px of the dense form (DCR order).  Along an axis, parity p reads the
+# low-res offsets TAP_SPARSE_AXIS[pattern][p] (dense tap index dy = offset + 1); every other (tap, phase) block of the dense
+# weight is zero, which is what the halo kernel's tap-sparse instantiations skip (csrc/conv_kernel_halo.h, tap_sparse_mask).
+TAP_SPARSE_NEAREST, TAP_SPARSE_TRANSPOSE = 1, 2
+TAP_SPARSE_AXIS = {TAP_SPARSE_NEAREST: ((0, 1), (1, 2)), TAP_SPARSE_TRANSPOSE: ((1,), (1, 2))}
+# nearest: upsampled row 2y + py - 1 + ky is low-res row y - 1 + UP2K3_ROWMAP[py][ky]
+UP2K3_ROWMAP = ((0, 1, 1), (1, 1, 2))
+# transpose (oy = 2 iy - 1 + ky): parity 0 takes ky 1 from row y; parity 1 takes ky 2 from row y and ky 0 from row y + 1
+TK3_TAPS = (((1, 1),), ((2, 1), (0, 2)))                             # per parity: (ky, dense tap index)
+
+
+def tap_sparse_live(pattern: int) -> List[List[bool]]:
+    """[phase 2 py + px][tap 3 dy + dx] -> does the phase read the tap (False: the block of the dense weight is zero)."""
+    ax = TAP_SPARSE_AXIS[pattern]
+    return [[(dy in ax[ph >> 1]) and (dx in ax[ph & 1]) for dy in range(3) for dx in range(3)] for ph in range(4)]
+
+
+def up2_nearest_dense_weight(weight: torch.Tensor) -> torch.Tensor:
+    """Conv2d(k3, p1) filter [cout, cin, 3, 3] applied after nn.Upsample(2, nearest) -> the dense-equivalent low-res filter
+    [4 cout, cin, 3, 3]: taps that read the same low-res pixel are summed (fixed ky, kx ascending order, in the
+    dtype of `weight`).  The zero padding of the upsampled image is the zero padding of the low-res one: exact at the borders."""
+    w = weight.detach().to("cpu")
+    cout, cin = w.shape[:2]
+    assert tuple(w.shape[2:]) == (3, 3), w.shape
+    out = torch.zeros(4, cout, cin, 3, 3, dtype=w.dtype)
+    for py in range(2):
+        for px in range(2):
+            for ky in range(3):
+                for kx in range(3):
+                    dy, dx = UP2K3_ROWMAP[py][ky], UP2K3_ROWMAP[px][kx]
+                    out[2 * py + px, :, :, dy, dx] = out[2 * py + px, :, :, dy, dx] + w[:, :, ky, kx]
+    return out.reshape(4 * cout, cin, 3, 3)
+
+
+def transpose_k3s2p1op1_dense_weight(weight: torch.Tensor) -> torch.Tensor:
+    """nn.ConvTranspose2d(k3, s2, p1, output_padding=1) filter [cin, cout, 3, 3] -> the dense-equivalent low-res filter
+    [4 cout, cin, 3, 3]: a pure placement of the taps (no sums, no flip)."""
+    w = weight.detach().to("cpu")
+    cin, cout = w.shape[:2]
+    assert tuple(w.shape[2:]) == (3, 3), w.shape
+    wc = w.permute(1, 0, 2, 3)
+    out = torch.zeros(4, cout, cin, 3, 3, dtype=w.dtype)
+    for py in range(2):
+        for px in range(2):
+            for ky, dy in TK3_TAPS[py]:
+                for kx, dx in TK3_TAPS[px]:
+                    out[2 * py + px, :, :, dy, dx] = wc[:, :, ky, kx]
+    return out.reshape(4 * cout, cin, 3, 3)
+
+
+def _pack_tap_sparse_d2s(ws: torch.Tensor, bias: Optional[torch.Tensor], pattern: int) -> ConvPlan:
+    bs = None if bias is None else bias.detach().to("cpu", torch.float32).repeat(4)
+    plan = pack_conv(ws, bs, stride=1, pad=1)
+    # (the library refuses the pattern on other channel counts; those layers run the same weights dense)
+    plan.tap_sparse = pattern if plan.cout % 128 == 0 and plan.cout_pad == plan.cout else 0
+    return plan
+
+
+def pack_conv_up2_nearest_d2s(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> ConvPlan:
+    """nn.Upsample(2, nearest) -> Conv2d(k3, p1) as one 3x3 pad-1 conv of the LOW-res image with 4 cout channels, to be
+    launched with store=STORE_D2S (VUnet UpSample('nearest')).  16 of its 36 (tap, phase) blocks are non-zero."""
+    return _pack_tap_sparse_d2s(up2_nearest_dense_weight(weight.detach().to("cpu", torch.float32)), bias, TAP_SPARSE_NEAREST)
+
+
+def pack_conv_transpose_k3s2p1op1_d2s(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> ConvPlan:
+    """nn.ConvTranspose2d(k3, s2, p1, output_padding=1) (output 2H x 2W) as one 3x3 pad-1 conv of the input with 4 cout
+    channels, to be launched with store=STORE_D2S (VUnet UpSample('conv2d_t')).  9 of its 36 (tap, phase) blocks are
+    non-zero."""
+    return _pack_tap_sparse_d2s(transpose_k3s2p1op1_dense_weight(weight.detach().to("cpu", torch.float32)), bias, TAP_SPARSE_TRANSPOSE)
+
+
 def pack_conv_transpose_k4s2p1(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> ConvPlan:
     """nn.ConvTranspose2d(k=4, s=2, p=1) filter [cin, cout, 4, 4] -> four 2x2 phase convolutions.
 
@@ -466,11 +539,12 @@ def pack_conv_rowsplit(weight: torch.Tensor, bias: Optional[torch.Tensor], *, pa
 
 # ---- parameter folds (pure functions of the parameters; exact formulas of the reference's wrappers) ----
 
-def fold_weight_norm(v: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
-    """torch.nn.utils.weight_norm(dim=0) (vunet/layers.py:29-31): w = g * v / ||v||, norm over dims 1..3."""
+def fold_weight_norm(v: torch.Tensor, g: torch.Tensor, dim: int = 0) -> torch.Tensor:
+    """torch.nn.utils.weight_norm(dim=0) (vunet/layers.py:29-31): w = g * v / ||v||, norm over dims 1..3.
+    dim=1: the transposed convolution's form (layers.py:72-74), norm over every axis but the output channels'."""
     v = v.detach().to("cpu", torch.float32)
     g = g.detach().to("cpu", torch.float32)
-    return torch._weight_norm(v, g, 0)
+    return torch._weight_norm(v, g, dim)
 
 
 def fold_spectral_norm(w_orig: torch.Tensor, u: torch.Tensor, v: torch.Tensor, transposed: bool = False) -> torch.Tensor:

@@ -178,7 +178,7 @@ class VehiclePipeline:
                  broadcast_src: Optional[int] = None, group=None, cad: bool = False, cad_bank=None,
                  device_homography: bool = False):
         """state_dicts: checkpoints (the reference's keys) per network; a missing network gets the synthetic weights of
-        `seed`.  broadcast_src: with an initialised process group, only that rank needs to hold `state_dicts` (a real
+        `seed`; the VUnet is built in the configuration its checkpoint's keys show (`vunet.models.vunet_args_of`).  broadcast_src: with an initialised process group, only that rank needs to hold `state_dicts` (a real
         checkpoint read from disk on rank 0): they are distributed with `broadcast_state_dicts` first (north_star: RCCL
         broadcast of the shared weights), so every rank renders with identical parameters.
         cad: also hold the reference's CAD-model classifier (VGG-19, 10 classes; state_dicts['vgg'] = `cads/model.pth`,
@@ -192,7 +192,7 @@ class VehiclePipeline:
         from .edgeconnect.models import EdgeModel, InpaintingModel
         from .stacked_hourglass.models import HourglassNet
         from .synth import synth_state_dict
-        from .vunet.models import Vunet_fix_res
+        from .vunet.models import Vunet_fix_res, vunet_args_of
         from .warp_learn.models import G_Resnet
         self.device = torch.device(device)
         self.inpaint = inpaint
@@ -215,10 +215,13 @@ class VehiclePipeline:
 
         self.hg = HourglassNet(num_stacks=2, num_blocks=1, num_classes=12)             # run_test.py:62
         self.icn = G_Resnet(21)                                                         # run_test.py:74
-        self.vunet = Vunet_fix_res(Namespace(up_mode="subpixel", w_norm=True, drop_prob=0.2, vunet_256=True))
+        # the VUnet the checkpoint was trained as (run_test.py:82 and the synthetic weights: subpixel, w_norm, 256; a
+        # state_dicts['vunet'] of another --up_mode / w_norm / resolution builds that network)
+        vunet_sd = sd("vunet")
+        self.vunet = Vunet_fix_res(vunet_args_of(vunet_sd))
         self.hg.load_state_dict(sd("hg"))
         self.icn.load_state_dict(sd("icn"))
-        self.vunet.load_state_dict(sd("vunet"))
+        self.vunet.load_state_dict(vunet_sd)
         nets = [self.hg, self.icn, self.vunet]
         if inpaint:
             self.edge, self.inp = EdgeModel(None), InpaintingModel(None)

@@ -90,7 +90,11 @@ def synth_state_dict(net: str, schema: Mapping[str, Tuple[Sequence[int], str]], 
         if leaf == "weight_g":
             v = out[prefix + ".weight_v"]
             fan_in = v.shape[1] * v.shape[2] * v.shape[3]
-            vnorm = v.reshape(v.shape[0], -1).norm(dim=1).reshape(shape)
+            if len(shape) == 4 and shape[0] == 1 and shape[1] > 1:      # weight_norm(dim=1) of a transposed conv: [1, cout, 1, 1]
+                fan_in = v.shape[0] * v.shape[2] * v.shape[3]
+                vnorm = v.permute(1, 0, 2, 3).reshape(v.shape[1], -1).norm(dim=1).reshape(shape)
+            else:
+                vnorm = v.reshape(v.shape[0], -1).norm(dim=1).reshape(shape)
             out[key] = vnorm * (gain / (0.05 * fan_in ** 0.5)) * _uniform(shape, 0.8, 1.2, g)
         elif leaf == "weight_u":
             w = out[prefix + ".weight_orig"]

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..nn_base import ConvP, WNConvP
+from ..nn_base import ConvP, WNConvP, WNConvTP
 
 
 class Activation(nn.Module):
@@ -27,6 +27,17 @@ class MyConv2d(nn.Module):
         self.c_in, self.c_out, self.kernel_size, self.stride, self.padding, self.w_norm = \
             c_in, c_out, kernel_size, stride, padding, w_norm
         self.conv = WNConvP(c_in, c_out, kernel_size) if w_norm else ConvP(c_in, c_out, kernel_size)
+
+
+class DeConv2d(nn.Module):
+    """nn.ConvTranspose2d(output_padding=1) holder, weight [c_in, c_out, k, k]; w_norm: weight_norm(dim=1) (reference
+    layers.py:61-77).  The network runs the k3 s2 p1 form UpSample('conv2d_t') builds."""
+
+    def __init__(self, c_in, c_out, kernel_size, stride, padding, w_norm: bool):
+        super().__init__()
+        self.c_in, self.c_out, self.kernel_size, self.stride, self.padding, self.w_norm = \
+            c_in, c_out, kernel_size, stride, padding, w_norm
+        self.conv = WNConvTP(c_in, c_out, kernel_size) if w_norm else ConvP(c_in, c_out, kernel_size, transposed=True)
 
 
 class NiN(nn.Module):
@@ -49,12 +60,21 @@ class DownSample(nn.Module):
 
 
 class UpSample(nn.Module):
+    """The reference's three 2x upsampling layers (layers.py:121-155), each ONE 3x3 launch with a DepthToSpace store:
+    'subpixel' as it is, 'conv2d_t' and 'nearest' through their dense-equivalent phase weights (pack.py)."""
+
     def __init__(self, c_in, c_out, w_norm, mode):
         super().__init__()
-        if mode != "subpixel":
-            raise NotImplementedError(f"UpSample(mode={mode!r}): the reference runs 'subpixel' only (run_test.py:82)")
         self.mode = mode
-        self.depth4x = MyConv2d(c_in, 4 * c_out, 3, 1, 1, w_norm)
+        self.c_in, self.c_out = c_in, c_out
+        if mode == "subpixel":
+            self.depth4x = MyConv2d(c_in, 4 * c_out, 3, 1, 1, w_norm)
+        elif mode == "conv2d_t":
+            self.up = DeConv2d(c_in, c_out, 3, 2, 1, w_norm)
+        elif mode == "nearest":
+            self.conv = MyConv2d(c_in, c_out, 3, 1, 1, w_norm)
+        else:
+            raise ValueError(f"Unknown mode: {mode}.")
 
 
 class Sampler(nn.Module):

@@ -28,8 +28,8 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import ops, pack
-from ..nn_base import FusedNet, WNConvP, entry_point
-from .layers import (Activation, DepthToSpace, DownSample, MyConv2d, NiN, Residual, Sampler, SpaceToDepth,
+from ..nn_base import FusedNet, WNConvP, WNConvTP, entry_point
+from .layers import (Activation, DeConv2d, DepthToSpace, DownSample, MyConv2d, NiN, Residual, Sampler, SpaceToDepth,
                      UpSample)
 
 
@@ -89,6 +89,21 @@ class EndBlock(nn.Module):
         self.residual_0 = _res(c_in, c_middle, drop_prob, w_norm)
         self.residual_1 = _res(c_in, c_middle, drop_prob, w_norm)
         self.conv = MyConv2d(c_middle, c_out, 3, 1, 1, w_norm)
+
+
+def vunet_args_of(state_dict, drop_prob: float = 0.2) -> argparse.Namespace:
+    """The constructor arguments a reference-shaped VUnet checkpoint was trained with, read off its keys: `up_mode` from the
+    UpSample holder's nesting (depth4x / up / conv), `w_norm` from the weight_g entries, `vunet_256` from the extra 256-pixel
+    level.  `drop_prob` leaves no trace in a checkpoint and does nothing at inference."""
+    keys = list(state_dict.keys())
+    up = [k for k in keys if k.startswith("app_decoder_1_e.")]
+    if not up:
+        raise ValueError("not a Vunet_fix_res state_dict: no app_decoder_1_e.* entries")
+    mode = {"depth4x": "subpixel", "up": "conv2d_t", "conv": "nearest"}.get(up[0].split(".")[1])
+    if mode is None:
+        raise ValueError(f"Unknown UpSample entry: {up[0]}")
+    return argparse.Namespace(up_mode=mode, w_norm=any(k.endswith(".weight_g") for k in keys), drop_prob=drop_prob,
+                              vunet_256=any(k.startswith("shape_encoder_1_a.") for k in keys))
 
 
 class Vunet_fix_res(FusedNet):
@@ -163,8 +178,22 @@ class Vunet_fix_res(FusedNet):
             if isinstance(pm, Residual):
                 parents[pname + ".layers.2"] = pm
         P = {}
+        nearest = {pname + ".conv" for pname, pm in self.named_modules() if isinstance(pm, UpSample) and pm.mode == "nearest"}
         for name, m in self.named_modules():
+            if isinstance(m, DeConv2d):
+                # UpSample('conv2d_t'): ConvTranspose2d(k3, s2, p1, output_padding 1) as a low-res 3x3 + DepthToSpace store
+                h = m.conv
+                assert (m.kernel_size, m.stride, m.padding) == (3, 2, 1), name
+                w = pack.fold_weight_norm(h.weight_v, h.weight_g, dim=1) if isinstance(h, WNConvTP) else h.weight
+                P[name] = pack.pack_conv_transpose_k3s2p1op1_d2s(w, h.bias).to(device)
+                continue
             if not isinstance(m, MyConv2d):
+                continue
+            if name in nearest:
+                # UpSample('nearest'): interpolate x2 -> k3 p1 as a low-res 3x3 with pre-summed taps + DepthToSpace store
+                h = m.conv
+                w = pack.fold_weight_norm(h.weight_v, h.weight_g) if isinstance(h, WNConvP) else h.weight
+                P[name] = pack.pack_conv_up2_nearest_d2s(w, h.bias).to(device)
                 continue
             h = m.conv
             w = pack.fold_weight_norm(h.weight_v, h.weight_g) if isinstance(h, WNConvP) else h.weight
@@ -188,8 +217,12 @@ class Vunet_fix_res(FusedNet):
     def _nin(self, name: str, x, x1=None, out=None):
         return ops.conv(self._plans[name + ".layers.1"], x, x1, pre_op=L.PRE_ELU, out=out)
 
+    _UP_PLAN = {"subpixel": ".depth4x", "conv2d_t": ".up", "nearest": ".conv"}
+
     def _upsample(self, name: str, x):
-        return ops.conv(self._plans[name + ".depth4x"], x, store=L.STORE_D2S)
+        # every mode is one 3x3 launch on the low-res input with the DepthToSpace store; the plans of 'conv2d_t' and
+        # 'nearest' carry their tap sparsity (no fused ELU, no skip input: reference layers.py:140-152)
+        return ops.conv(self._plans[name + self._UP_PLAN[self.up_mode]], x, store=L.STORE_D2S)
 
     # ---- "fusion by cache blocking" of the high-resolution 32-channel blocks (round 4 experiment, FUSG_VU_SUBBATCH=n) ----
     # The verdict's fused Residual -> Residual block would keep the intermediates of the 256 x 256 / 128 x 128 levels out of

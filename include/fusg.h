@@ -211,7 +211,18 @@ typedef struct fusg_conv_desc {
      * order: bit-reproducible) and applies the epilogue inside the same launch; NULL, a second kernel does. */
     int32_t*       splitk_counters;
     int32_t        splitk_counters_len;
-    int32_t        _pad2;
+    /* Tap sparsity of the packed weights (0 = none; this word was padding, so 0 is every older caller): the descriptor is
+     * the dense-equivalent 3x3 / pad 1 / stride 1 DepthToSpace form of a 2x upsampling layer with C_out = cout / 4 output
+     * channels, phase 2 py + px of the 2 x 2 output cell in channel block [phase * C_out, +C_out), and whole (tap, phase)
+     * blocks of the weights are zero:
+     *   1  nn.Upsample(2, nearest) -> Conv2d(k3, p1) (pack.py: pack_conv_up2_nearest_d2s): 4 live taps of 9 per phase;
+     *   2  nn.ConvTranspose2d(k3, s2, p1, output_padding 1) (pack_conv_transpose_k3s2p1op1_d2s): 1, 2, 2, 4 live taps.
+     * Requires kh = kw = 3, zero padding 1, stride 1, dil 1, no upsample, D2S store, nphase 1, cout % 128 == 0 (C_out % 32 == 0) and
+     * cout_pad == cout, else FUSG_ERR_UNSUPPORTED.  A launch that takes the halo kernel in F16X3 or exact F32 then skips the
+     * weight loads and MFMAs of the dead taps (same bytes as the dense launch: the skipped products are exact zeros); every
+     * other route - the generic gather, the small-image kernel, FUSG_PREC_BF16 with wfrag_bf16 given - runs the dense weights,
+     * which are correct by construction.  FUSG_PREC_BF16 without wfrag_bf16 runs as F16X3, tap-sparse. */
+    int32_t        tap_sparse;
 } fusg_conv_desc;
 
 int  fusg_conv2d(const fusg_conv_desc* d, void* stream);
