@@ -121,6 +121,8 @@ _SIGS = {
     "fusg_plane_homographies": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 5),
     "fusg_plane_homographies_host": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 4),
     "fusg_find_homography_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "fusg_pose_geometry": (C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 11),
+    "fusg_pose_geometry_host": (C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 10),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

@@ -272,6 +272,13 @@ def h2d(a, device, dtype=None) -> torch.Tensor:
     return t.contiguous().pin_memory().to(device, non_blocking=True)
 
 
+def d2h(t: torch.Tensor) -> _np.ndarray:
+    """A device tensor to a host numpy array: a BLOCKING copy (the host waits for everything queued before it on the current
+    stream).  The frame drivers' device-pose front stage makes exactly one of these per frame and routes it through here, so a
+    test can count them."""
+    return t.cpu().numpy()
+
+
 def nhwc_empty(b: int, c: int, h: int, w: int, device, dtype=torch.float32, zero: bool = False) -> torch.Tensor:
     """Logical [b, c, h, w] view over a fresh NHWC buffer whose channel pitch is c rounded up to 4."""
     cp = (c + 3) // 4 * 4

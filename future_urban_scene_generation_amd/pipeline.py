@@ -176,7 +176,7 @@ class VehiclePipeline:
 
     def __init__(self, device, inpaint: bool = False, state_dicts: Optional[Dict[str, dict]] = None, seed: int = 0,
                  broadcast_src: Optional[int] = None, group=None, cad: bool = False, cad_bank=None,
-                 device_homography: bool = False):
+                 device_homography: bool = False, device_pose: bool = False):
         """state_dicts: checkpoints (the reference's keys) per network; a missing network gets the synthetic weights of
         `seed`; the VUnet is built in the configuration its checkpoint's keys show (`vunet.models.vunet_args_of`).  broadcast_src: with an initialised process group, only that rank needs to hold `state_dicts` (a real
         checkpoint read from disk on rank 0): they are distributed with `broadcast_state_dicts` first (north_star: RCCL
@@ -188,7 +188,12 @@ class VehiclePipeline:
         the sketches, masks, planes and visibilities are rendered on the device from the fitted pose).
         device_homography: the frame drivers gate the planes and fit their homographies on the device
         (`planes_utils.plane_homographies_device` + `warp_planes_fitted`) instead of on the host (`warp_jobs_frame` +
-        `warp_planes_batch`, the default and the reference-signature path)."""
+        `warp_planes_batch`, the default and the reference-signature path).
+        device_pose: geometry mode selects the fitted pose and derives its geometry - extrinsic, render jobs, visibility
+        polygons, plane corner points - on the device (`render.vehicle_geometry_device`, fusg_pose_geometry) instead of in numpy
+        between three read-backs (`render.vehicle_geometry`, the default): a frame's front stage then issues every launch through
+        the plane cut-outs around ONE blocking device-to-host copy of the small results.  With device_homography as well the
+        corner points reach the homography fit as device tensors."""
         from .edgeconnect.models import EdgeModel, InpaintingModel
         from .stacked_hourglass.models import HourglassNet
         from .synth import synth_state_dict
@@ -200,6 +205,7 @@ class VehiclePipeline:
         self.cad = None
         self.cad_bank = cad_bank
         self.device_homography = bool(device_homography)
+        self.device_pose = bool(device_pose)
         if broadcast_src is not None:
             import torch.distributed as dist
             if not _one_rank(group):
@@ -546,8 +552,12 @@ class VehiclePipeline:
     def _geometry_state(cls, f: Dict, lo: int = 0) -> Dict:
         """state['geometry'] of the kept vehicles of `_geometry_front`'s dict `f`; lo: the frame index of f's first vehicle."""
         keep, sc = f["keep"], f["scene"]
-        return {"vehicles": [lo + v for v in keep], "cad_idx": f["cad_idx"][keep], "pose": [f["pose"][v] for v in keep],
-                "focals": sc["focals"], "centers": sc["centers"], **cls._kept_planes(f["geometry"], keep)}
+        st = {"vehicles": [lo + v for v in keep], "cad_idx": f["cad_idx"][keep], "pose": [f["pose"][v] for v in keep],
+              "focals": sc["focals"], "centers": sc["centers"], **cls._kept_planes(f["geometry"], keep)}
+        if f.get("dev") is not None:                              # device_pose: the same, kept on the device for the later frames
+            sel = cls._select(f["dev"], keep, ("pose_d", "cad_idx_d", "src_kp_d"))
+            st.update(pose_d=sel["pose_d"], cad_idx_d=sel["cad_idx_d"], src_kp_d=sel["src_kp_d"], kp_nv_d=f["dev"]["kp_nv_d"])
+        return st
 
     # ---- what rank 0 gathers of a sharded geometry-mode first frame besides the crops: one int32 and one float32 row per vehicle
     @staticmethod
@@ -561,9 +571,10 @@ class VehiclePipeline:
             ints[:, 12] = f["g"]["covered"]
             ints[:, 13] = f["cad_idx"]
             flts[:, :24] = f["pre"]["kp_xy"].cpu().numpy().reshape(n, 24)
-            flts[:, 24:36] = f["raw"][0].reshape(n, 12)
-            flts[:, 36:48] = f["raw"][1].reshape(n, 12)
-            flts[:, 48:52] = f["raw"][2].reshape(n, 4)
+            raw = f["raw"] if f["raw"] is not None else tuple(t.cpu().numpy() for t in f["raw_d"])   # (device_pose: not read back before)
+            flts[:, 24:36] = raw[0].reshape(n, 12)
+            flts[:, 36:48] = raw[1].reshape(n, 12)
+            flts[:, 48:52] = raw[2].reshape(n, 4)
         return ints, flts
 
     @staticmethod
@@ -584,7 +595,9 @@ class VehiclePipeline:
 
     def _rerender_masks(self, scene: Dict, focals, centers, cad_idx, poses, steps=None) -> torch.Tensor:
         """Rank 0's masks of vehicles it only holds the poses of (the render is deterministic per job, and a
-        pose is 28 numbers where a mask is H x W bytes); steps: a later frame's (theta, tr) per vehicle."""
+        pose is 28 numbers where a mask is H x W bytes); steps: a later frame's (theta, tr) per vehicle.  The poses arrive as host
+        numbers after the gather, so the host path (extrinsics_from_poses, render_jobs) serves here with device_pose as well:
+        there is no device-resident fit to keep on the device."""
         import numpy as np
 
         from . import render as rd
@@ -627,6 +640,8 @@ class VehiclePipeline:
             pre["kp_xy"] = fo.keypoints_to_frame(pre["kp_idx"], geom_box, (R // 4, R // 4))              # :95-97
             return pre
 
+        if self.device_pose:
+            return self._geometry_front_device(scene, check, keypoints)
         with torch.cuda.device(dev):
             pre = self._guarded(keypoints, (), check, None) if V else {}
             if self.cad is not None:
@@ -647,20 +662,68 @@ class VehiclePipeline:
                 pose, kp_xy = [], np.zeros((0, 12, 2), np.float32)
             K = rd.intrinsic(scene["focals"], scene["centers"])
             g = rd.vehicle_geometry(bank, frame, cad_idx, [(p[1], p[2]) for p in pose], K, kp_xy=kp_xy)
+        return self._geometry_front_result(scene, pre, raw, raw_d, pose, cad_idx, g)
+
+    def _geometry_front_result(self, scene: Dict, pre: Dict, raw, raw_d, pose, cad_idx, g: Dict, dev_keys: Optional[Dict] = None) -> Dict:
+        """`_geometry_front`'s dict from the geometry `g` of either path; dev_keys (device_pose): the device copies of the pose,
+        CAD indices and corner points, selected with the kept vehicles into 'sub' and kept for the state."""
+        dev, bank = self.device, self.cad_bank
+        V = len(pose)
         keep = [v for v in range(V) if g["covered"][v] > 0]
         geometry = {k: g[k] for k in ("masks", "src_sketch", "dst_sketch", "src_planes", "src_kp", "dst_kp", "src_vis", "dst_vis")}
         geometry["kp3d"] = bank.kp3d[cad_idx]
         geometry["cad_idx"] = cad_idx
-        sub = self._select({**scene, **geometry}, keep, PER_VEHICLE_KEYS + ("cad_idx", "inpaint"))
+        extra = {} if dev_keys is None else {"src_kp_d": dev_keys["src_kp_d"], "dst_kp_d": dev_keys["src_kp_d"]}
+        sub = self._select({**scene, **geometry, **extra}, keep, PER_VEHICLE_KEYS + ("cad_idx", "inpaint") + tuple(extra))
         sub.pop("cad_idx", None)
+        if dev_keys is not None:
+            sub["kp_nv_d"] = dev_keys["kp_nv_d"]
         if V:
             hg = {"kp_idx": pre["kp_idx"]}
             if self.cad is not None:
                 hg["cad_logits"] = pre["cad_logits"]
             sub["_hg"] = self._select(hg, keep, list(hg))
             sub["_pose_raw"] = tuple(t.index_select(0, torch.as_tensor(keep, dtype=torch.long, device=dev)) for t in raw_d)
-        return {"pre": pre, "raw": raw, "pose": pose, "cad_idx": cad_idx, "g": g, "keep": keep, "geometry": geometry, "sub": sub,
-                "V": V, "scene": scene}
+        return {"pre": pre, "raw": raw, "raw_d": raw_d, "pose": pose, "cad_idx": cad_idx, "g": g, "keep": keep, "geometry": geometry,
+                "sub": sub, "V": V, "scene": scene, "dev": dev_keys}
+
+    @staticmethod
+    def _pose_tuples(pose) -> list:
+        """float32 [V, 7] (error, rvec, tvec) -> run_frame's 'pose': (error, rvec [3, 1], tvec [3, 1]) per vehicle."""
+        return [(p[0], p[1:4].reshape(3, 1).copy(), p[4:7].reshape(3, 1).copy()) for p in pose]
+
+    def _geometry_front_device(self, scene: Dict, check, keypoints) -> Dict:
+        """`_geometry_front` with device_pose: the CAD index stays on the device (the classifier's argmax, or the scene's
+        uploaded once), the fit takes the chosen models' keypoints from the bank's device table, and
+        `render.vehicle_geometry_device` selects the pose and derives, renders and counts everything with one blocking read-back
+        (pose, CAD indices, counts, corner points, extrinsic); the raw fit is not read back at all ('raw' is None)."""
+        import numpy as np
+
+        from . import ops
+        from . import render as rd
+        from .utils.pnp_utils import cpc_fit_device
+        dev, bank = self.device, self.cad_bank
+        frame = scene["frame"]
+        V = np.asarray(scene["bboxes"]).reshape(-1, 4).shape[0]
+        with torch.cuda.device(dev):
+            pre = self._guarded(keypoints, (), check, None) if V else {}
+            if self.cad is None and scene.get("cad_idx") is None:
+                raise ValueError("geometry mode: the scene needs 'cad_idx' [V] (or a pipeline built with cad=True)")
+            raw_d, kp_xy_d = None, None
+            if V:
+                cad_d = pre["cad_logits"].argmax(1) if self.cad is not None else \
+                    ops.h2d(np.asarray(scene["cad_idx"], np.int64).reshape(V), dev)
+                f32 = lambda a: ops.h2d(np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32).reshape(-1, 2), (V, 2))), dev)   # noqa: E731
+                # (an index outside the bank is clamped for the fit only: fusg_pose_geometry flags it and the geometry raises)
+                kp3d_d = bank.device_arrays(dev)["kp3d"].index_select(0, cad_d.clamp(0, len(bank) - 1))
+                raw_d = cpc_fit_device(f32(scene["focals"]), f32(scene["centers"]), pre["kp_xy"], kp3d_d)        # :104-105
+                kp_xy_d = pre["kp_xy"]
+            else:
+                cad_d = torch.zeros(0, dtype=torch.int64, device=dev)
+            K = rd.intrinsic(scene["focals"], scene["centers"])
+            g = rd.vehicle_geometry_device(bank, frame, cad_d, K, raw_d=raw_d, kp_xy_d=kp_xy_d)
+        dev_keys = {"pose_d": g["pose_d"], "cad_idx_d": cad_d, "src_kp_d": g["tex_pts_d"], "kp_nv_d": g["tex_nv_d"]}
+        return self._geometry_front_result(scene, pre, None, raw_d, self._pose_tuples(g["pose"]), g["cad_idx"], g, dev_keys)
 
     def _geometry_assemble(self, f: Dict, out: Dict) -> Dict:
         """run_frame's geometry-mode result from `_geometry_front`'s dict and the given-geometry result of the kept vehicles."""
@@ -770,13 +833,31 @@ class VehiclePipeline:
         veh = list(gs["vehicles"])
         steps = [scene["steps"][v] for v in veh]
         K = rd.intrinsic(gs["focals"], gs["centers"])
+        extra = {}
         with torch.cuda.device(self.device):
-            g = rd.vehicle_geometry(self.cad_bank, scene["frame"], gs["cad_idx"], [(p[1], p[2]) for p in gs["pose"]], K, steps=steps)
+            if self.device_pose:
+                # the first frame's selected pose and CAD indices as it left them on the device; a state made without
+                # device_pose holds the host copies only, which are uploaded then
+                import numpy as np
+
+                from . import ops
+                pose_d, cad_d = gs.get("pose_d"), gs.get("cad_idx_d")
+                if pose_d is None:
+                    rows = [[p[0], *np.asarray(p[1]).reshape(3), *np.asarray(p[2]).reshape(3)] for p in gs["pose"]]
+                    pose_d = ops.h2d(np.asarray(rows, np.float32).reshape(len(veh), 7), self.device)
+                    cad_d = ops.h2d(np.asarray(gs["cad_idx"], np.int64).reshape(len(veh)), self.device)
+                g = rd.vehicle_geometry_device(self.cad_bank, scene["frame"], cad_d, K, pose_d=pose_d, steps=steps)
+                if gs.get("src_kp_d") is not None:
+                    extra = {"src_kp_d": gs["src_kp_d"], "dst_kp_d": g["tex_pts_d"]}
+            else:
+                g = rd.vehicle_geometry(self.cad_bank, scene["frame"], gs["cad_idx"], [(p[1], p[2]) for p in gs["pose"]], K, steps=steps)
         keep = [i for i in range(len(veh)) if g["covered"][i] > 0]
         geometry = {k: g[k] for k in ("masks", "dst_sketch", "dst_kp", "dst_vis")}
         geometry["kp3d"] = g["kp3d"]
-        sub = self._select({**scene, **geometry, "src_planes": gs["src_planes"], "src_kp": gs["src_kp"], "src_vis": gs["src_vis"]},
-                           keep, ("masks", "dst_sketch", "dst_kp", "dst_vis", "src_planes", "src_kp", "src_vis"))
+        sub = self._select({**scene, **geometry, **extra, "src_planes": gs["src_planes"], "src_kp": gs["src_kp"], "src_vis": gs["src_vis"]},
+                           keep, ("masks", "dst_sketch", "dst_kp", "dst_vis", "src_planes", "src_kp", "src_vis") + tuple(extra))
+        if extra:
+            sub["kp_nv_d"] = gs["kp_nv_d"]
         if scene.get("vehicle_seeds") is not None:
             sub["vehicle_seeds"] = [scene["vehicle_seeds"][veh[i]] for i in keep]
         sub.pop("steps", None)
@@ -1167,7 +1248,15 @@ class VehiclePipeline:
         from .warp_learn import planes_utils as pu
         if not self.device_homography:
             return pu.warp_planes_batch(scene["src_planes"], jobs)
-        minv, index = pu.plane_homographies_device(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"], self.device)
+        if scene.get("src_kp_d") is not None and scene.get("dst_kp_d") is not None:
+            # device_pose: the corner points never left the device; the visibilities come from the read-back counts
+            import numpy as np
+
+            from . import ops
+            vis = [ops.h2d((np.asarray(scene[k]).reshape(-1, 5) != 0).astype(np.uint8), self.device) for k in ("src_vis", "dst_vis")]
+            minv, index = pu.plane_homographies_device(scene["src_kp_d"], scene["dst_kp_d"], vis[0], vis[1], nverts=scene["kp_nv_d"])
+        else:
+            minv, index = pu.plane_homographies_device(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"], self.device)
         return pu.warp_planes_fitted(scene["src_planes"], minv, index)
 
     @torch.no_grad()

@@ -194,7 +194,16 @@ class CadBank:
             # C order: the kernels index rows of 3 (np.concatenate keeps the Fortran order of an F-ordered input)
             self._dev[dev] = {k: torch.from_numpy(np.ascontiguousarray(np.concatenate(a))).to(dev)
                               for k, a in (("verts", self.vertices), ("normals", self.normals), ("tris", self.triangles))}
+            # the tables fusg_pose_geometry looks a vehicle's model up in
+            self._dev[dev].update(kp3d=torch.from_numpy(np.ascontiguousarray(self.kp3d, dtype=np.float32)).to(dev),
+                                  v_off=torch.from_numpy(self.v_off.astype(np.int32)).to(dev),
+                                  t_off=torch.from_numpy(self.t_off.astype(np.int32)).to(dev))
         return self._dev[dev]
+
+    @property
+    def max_nv(self) -> int:
+        """The largest vertex count of a model: sizes the render's workspace without reading a job back."""
+        return int(np.diff(self.v_off).max())
 
 
 def extrinsic_from_pose(rvec, tvec) -> np.ndarray:
@@ -508,13 +517,144 @@ def vehicle_geometry(bank: CadBank, frame: torch.Tensor, mesh_idx: Sequence[int]
         host = torch.cat([counts.view(V, 14), r["covered"].view(V, 1)], 1).cpu().numpy()
         if V and steps is None:                                   # queued after the read-back: it does not wait for the planes
             pu.fill_planes_batch(frame, seg[3], seg[4], planes)
-    vis = visible(host[:, :14].reshape(V, 7, 2))[:, :len(TEXTURE_PLANES)].astype(np.uint8)
-    out = {"masks": r["mask"], "covered": host[:, 14].astype(np.int64), "kp3d": kp3d if V else np.zeros((0, 12, 3)),
-           "extrinsic": E, "counts": host[:, :14].reshape(V, 7, 2)}
-    if steps is None:
+    return _geometry_result(r, host[:, :14].reshape(V, 7, 2), host[:, 14], kp3d if V else np.zeros((0, 12, 3)), E, kp, planes,
+                            steps is None)
+
+
+def _geometry_result(r: Dict[str, torch.Tensor], counts: np.ndarray, covered: np.ndarray, kp3d: np.ndarray, E: np.ndarray, kp: List,
+                     planes: torch.Tensor, first: bool) -> Dict:
+    """The tail `vehicle_geometry` and `vehicle_geometry_device` share: the read-back plane counts [V, 7, 2] and covered-pixel
+    counts [V] (host) -> the visibilities and the result dict of either."""
+    vis = visible(counts)[:, :len(TEXTURE_PLANES)].astype(np.uint8)
+    out = {"masks": r["mask"], "covered": np.asarray(covered).astype(np.int64), "kp3d": kp3d, "extrinsic": E, "counts": counts}
+    if first:
         out.update(src_sketch=r["sketch"], dst_sketch=r["sketch"], src_planes=planes, src_kp=kp, dst_kp=kp, src_vis=vis, dst_vis=vis)
     else:
         out.update(dst_sketch=r["sketch"], dst_kp=kp, dst_vis=vis)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the same, derived on the device
+_TEX_NV = [len(i) for i in _TEX_IDX]
+# fusg_pose_geometry's per-vehicle outputs: name, dtype, elements per vehicle
+_PG_OUT = (("jobs", np.uint8, JOB_DTYPE.itemsize), ("extrinsic", np.float64, 12), ("kp3d", np.float64, 36), ("pose", np.float32, 7),
+           ("vis_pts", np.int32, 7 * pu.MAX_VERTS * 2), ("vis_nv", np.int32, 7), ("nearer", np.int32, 7),
+           ("tex_pts", np.int32, len(_TEX_IDX) * pu.MAX_VERTS * 2), ("tex_nv", np.int32, len(_TEX_IDX)), ("status", np.int32, 1))
+_PG_CALL = ("pose", "extrinsic", "kp3d", "jobs", "vis_pts", "vis_nv", "nearer", "tex_pts", "tex_nv", "status")   # the ABI's order
+
+
+def _pg_layout(V: int, extra=()) -> Tuple[Dict[str, Tuple[int, np.dtype, int]], int]:
+    """One buffer for every small per-vehicle array: name -> (byte offset, dtype, elements); each part 8-byte aligned."""
+    lay, off = {}, 0
+    for name, dt, per in tuple(_PG_OUT) + tuple(extra):
+        n = V * per
+        lay[name] = (off, np.dtype(dt), n)
+        off += (n * np.dtype(dt).itemsize + 7) // 8 * 8
+    return lay, off
+
+
+def pose_geometry_host(bank: CadBank, cad_idx, K: np.ndarray, frame_hw: Tuple[int, int], raw=None, kp_xy=None, pose=None,
+                       steps=None) -> Dict[str, np.ndarray]:
+    """fusg_pose_geometry_host: the device path's per-vehicle arithmetic on the CPU (no GPU needed), numpy in and out.  A first
+    frame gives raw = (rvec [V, 4, 3], tvec [V, 4, 3], err [V, 4]) and kp_xy [V, 12, 2]; a later frame pose [V, 7] (a first
+    frame's 'pose') and steps [V, 4] = (theta, tr).  Returns fusg_pose_geometry's outputs by name ('jobs' as JOB_DTYPE)."""
+    H, W = frame_hw
+    cad = np.ascontiguousarray(np.asarray(cad_idx, np.int64).reshape(-1))
+    V = cad.shape[0]
+    f32 = lambda a, sh: None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape((V,) + sh))   # noqa: E731
+    rv, tv, er = (None, None, None) if raw is None else (f32(raw[0], (4, 3)), f32(raw[1], (4, 3)), f32(raw[2], (4,)))
+    ins = [rv, tv, er, f32(pose, (7,)), f32(kp_xy, (12, 2)),
+           None if steps is None else np.ascontiguousarray(np.asarray(steps, np.float64).reshape(V, 4)), cad]
+    tabs = [np.ascontiguousarray(bank.kp3d, dtype=np.float32), bank.v_off.astype(np.int32), bank.t_off.astype(np.int32)]
+    Kc = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+    out = {name: np.zeros(V * per, dt) for name, dt, per in _PG_OUT}
+    ptr = lambda a: None if a is None else a.ctypes.data     # noqa: E731
+    L.check(L.lib().fusg_pose_geometry_host(*(ptr(a) for a in ins), *(ptr(a) for a in tabs), len(bank), ptr(Kc), H, W, V,
+                                            *(ptr(out[k]) for k in _PG_CALL)), "pose_geometry_host")
+    shapes = {"extrinsic": (V, 12), "kp3d": (V, 12, 3), "pose": (V, 7), "vis_pts": (V, 7, pu.MAX_VERTS, 2), "vis_nv": (V, 7),
+              "nearer": (V, 7), "tex_pts": (V, len(_TEX_IDX), pu.MAX_VERTS, 2), "tex_nv": (V, len(_TEX_IDX)), "status": (V,)}
+    res = {k: out[k].reshape(sh) for k, sh in shapes.items()}
+    res["jobs"] = out["jobs"].view(JOB_DTYPE)
+    return res
+
+
+def steps_array(steps: Sequence[Tuple[float, np.ndarray]]) -> np.ndarray:
+    """(theta, tr) per vehicle (`trajectory_steps`) -> float64 [V, 4], fusg_pose_geometry's form."""
+    return np.array([[float(th), *np.asarray(t, np.float64).reshape(3)] for th, t in steps], np.float64).reshape(-1, 4)
+
+
+def vehicle_geometry_device(bank: CadBank, frame: torch.Tensor, cad_idx_d: torch.Tensor, K: np.ndarray, raw_d=None, pose_d=None,
+                            kp_xy_d: Optional[torch.Tensor] = None, steps=None) -> Dict:
+    """`vehicle_geometry` with the pose selected and its geometry derived on the device (fusg_pose_geometry): nothing of the
+    fit is read back before the render is queued.  cad_idx_d: CUDA int64 [V].  First frame: raw_d = `cpc_fit_device`'s (rvec
+    [V, 4, 3], tvec, err [V, 4]) and kp_xy_d float32 [V, 12, 2], both on the device; later frame: pose_d CUDA float32 [V, 7]
+    (a first frame's 'pose_d') and steps = (theta, tr) per vehicle (host).  Order of work: fusg_pose_geometry -> render of the
+    device jobs -> plane visibility -> ONE device-to-host copy of every small
+    result (`ops.d2h`) -> the plane cut-outs, queued behind that read-back.
+    Returns `vehicle_geometry`'s keys (host values from the read-back: within the last bits of the numpy path's, the integer
+    ones equal wherever no coordinate sits within that of an integer) and 'pose' float32 [V, 7] (error, rvec, tvec: host),
+    'pose_d' (the same, device), 'cad_idx' (host int64 [V]), 'status' (host int32 [V]), 'tex_pts_d' / 'tex_nv_d' (the corner
+    points as the device tensors `plane_homographies_device` takes: int32 [V, 5, 8, 2], [5]).  A cad_idx outside the bank
+    raises IndexError after the read-back (its job is empty: nothing was read out of range).
+    The render's workspace is sized by the bank's largest model, V * (16 + 40 * bank.max_nv) bytes, whichever models are in
+    view (the jobs are not read back to size it), and comes from torch's caching allocator on every frame: a bank with one very
+    large mesh pays for it on every frame."""
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    dev = frame.device
+    V = int(cad_idx_d.shape[0])
+    first = steps is None
+    P = len(TEXTURE_PLANES)
+    lay, nbytes = _pg_layout(V, (("counts", np.int32, 14), ("covered", np.int32, 1), ("cad_idx", np.int64, 1)))
+    tdt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64,
+           np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+    with torch.cuda.device(dev):
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        d = {k: buf[o:o + n * dt.itemsize].view(tdt[dt]) for k, (o, dt, n) in lay.items()}
+        r = {"sketch": torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev),
+             "mask": torch.zeros((V, H, W), dtype=torch.uint8, device=dev)}
+        planes = torch.empty((V, P, H, W, 3), dtype=torch.uint8, device=dev)
+        if V:
+            if cad_idx_d.dtype != torch.int64 or not cad_idx_d.is_cuda:
+                raise ValueError("vehicle_geometry_device: cad_idx_d is a CUDA int64 [V]")
+            arr = bank.device_arrays(dev)
+            f32 = lambda t, sh: t.to(torch.float32).contiguous().view((V,) + sh)        # noqa: E731
+            if first:
+                ins = [f32(raw_d[0], (4, 3)), f32(raw_d[1], (4, 3)), f32(raw_d[2], (4,)), None, f32(kp_xy_d, (12, 2)), None]
+            else:
+                ins = [None, None, None, f32(pose_d, (7,)), None, ops.h2d(steps_array(steps), dev)]
+            cad_c = cad_idx_d.contiguous()
+            d["cad_idx"].copy_(cad_c)
+            Kc = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+            ptr = lambda t: None if t is None else t.data_ptr()                           # noqa: E731
+            lib = L.lib()
+            L.check(lib.fusg_pose_geometry(*(ptr(t) for t in ins), cad_c.data_ptr(), arr["kp3d"].data_ptr(), arr["v_off"].data_ptr(),
+                                           arr["t_off"].data_ptr(), len(bank), Kc.ctypes.data, H, W, V,
+                                           *(d[k].data_ptr() for k in _PG_CALL), ops.stream_ptr()), "pose_geometry")
+            max_nv = bank.max_nv
+            ws = torch.empty((V * (16 + 40 * max_nv) + 15) // 16 * 2, dtype=torch.float64, device=dev)
+            L.check(lib.fusg_render_normals_u8(arr["verts"].data_ptr(), arr["normals"].data_ptr(), arr["verts"].shape[0],
+                                               arr["tris"].data_ptr(), arr["tris"].shape[0], d["jobs"].data_ptr(), V, max_nv, H, W,
+                                               ws.data_ptr(), ws.numel() * 8, r["sketch"].data_ptr(), r["mask"].data_ptr(), None,
+                                               d["covered"].data_ptr(), ops.stream_ptr()), "render_normals_u8")
+            L.check(lib.fusg_plane_visibility(d["vis_pts"].data_ptr(), d["vis_nv"].data_ptr(), d["nearer"].data_ptr(), V, H, W,
+                                              d["counts"].data_ptr(), ops.stream_ptr()), "plane_visibility")
+        host = ops.d2h(buf) if V else np.zeros(0, np.uint8)       # the one blocking copy of the stage
+        if V and first:                                           # queued after the read-back: it does not wait for the planes
+            pu.fill_planes_batch(frame, d["tex_pts"], d["tex_nv"], planes)
+    h = {k: host[o:o + n * dt.itemsize].view(dt) for k, (o, dt, n) in lay.items()}
+    bad = np.flatnonzero(h["status"] != 0)
+    if len(bad):
+        raise IndexError(f"render: mesh {int(h['cad_idx'][bad[0]])} not in a bank of {len(bank)}")
+    tex = h["tex_pts"].reshape(V, P, pu.MAX_VERTS, 2)
+    kp = corner_lists([tex[:, i, :n].copy() for i, n in enumerate(_TEX_NV)]) if V else []
+    E = np.zeros((V, 4, 4), np.float32)
+    E[:] = np.eye(4, dtype=np.float32)
+    E[:, :3, :] = h["extrinsic"].reshape(V, 3, 4)                 # (float32 values carried in float64: the cast is exact)
+    kp3d = h["kp3d"].reshape(V, 12, 3)
+    out = _geometry_result(r, h["counts"].reshape(V, 7, 2).copy(), h["covered"], kp3d.astype(np.float32) if first else kp3d.copy(),
+                           E, kp, planes, first)
+    out.update(pose=h["pose"].reshape(V, 7).copy(), pose_d=d["pose"].view(V, 7), cad_idx=h["cad_idx"].copy(), status=h["status"].copy(),
+               tex_pts_d=d["tex_pts"].view(V, P, pu.MAX_VERTS, 2), tex_nv_d=d["tex_nv"][:P] if V else d["tex_nv"])
     return out
 
 

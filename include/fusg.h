@@ -516,6 +516,38 @@ int fusg_plane_homographies_host(const int32_t* src_pts, const int32_t* dst_pts,
  * is singular; the outputs are zeros then. */
 int fusg_find_homography_host(const double* src_xy, const double* dst_xy, int32_t n, double* H_out, double* minv_out);
 
+/* ---- pose geometry (geometry mode's glue between fusg_pnp_cpc and the render; added without a version step: FUSG_VERSION
+ * stays 118, the entry points are new and nothing existing changed) ------------------------------------------------- */
+/* Per vehicle, what the frame driver computed in numpy between the pose fit and the render, in the same operation order
+ * (csrc/pose_geometry.h): select_and_flip of the four starts (np.argmin: first index on ties, the first NaN wins; sign
+ * flip through Rodrigues in float64, the result rounded to float32), the extrinsic [R(rvec) | tvec] (carried in the
+ * pose's float32), on a later frame the keypoints moved by kp3d @ z_rot(theta) + tr and projected with K, the texture-plane
+ * corner points (x / W * W, y / H * H, truncated), the seven visibility polygons (projected with K @ E[:3], clipped to
+ * +-2^20 px, truncated, INT32_MIN for NaN) with their "nearer" masks, and the render job record, Open3D's principal point
+ * (W / 2 - 0.5, H / 2 - 0.5) and v_off, nv, t_off, nt from the bank's offset tables.
+ * A first frame passes the raw fit rvec / tvec float32 [V][4][3], err float32 [V][4] and kp_xy float32 [V][12][2] (frame
+ * pixels) with pose_in = steps = NULL; a later frame passes pose_in float32 [V][7] (a first frame's `pose`) and steps
+ * double [V][4] = (theta, tr) with rvec = tvec = err = kp_xy = NULL.  cad_idx int64 [V]; the bank: bank_kp3d float32
+ * [n_cad][12][3], bank_v_off / bank_t_off int32 [n_cad + 1] (cumulative vertex / triangle counts).  All of these are
+ * DEVICE pointers; K = HOST double [9] (row-major intrinsics), h, w = the frame.
+ * DEVICE outputs: pose float32 [V][7] (error, rvec, tvec), extrinsic double [V][12] (rows of [R | t]), kp3d double
+ * [V][12][3] (moved on a later frame), jobs [V], vis_pts int32 [V][7][8][2], vis_nv / nearer int32 [V][7] (the arguments
+ * of fusg_plane_visibility), tex_pts int32 [V][5][8][2], tex_nv int32 [V][5] (those of fusg_fill_poly_planes_batch_u8 and
+ * fusg_plane_homographies), status int32 [V]: 0, or 1 = cad_idx outside [0, n_cad) - that vehicle gets zero keypoints and
+ * an empty job (nv = nt = 0) and the bank is not read for it.
+ * V = 0 launches nothing.  NULL or inconsistent arguments: FUSG_ERR_INVALID before any launch.  One thread per vehicle. */
+int fusg_pose_geometry(const float* rvec, const float* tvec, const float* err, const float* pose_in, const float* kp_xy,
+                       const double* steps, const int64_t* cad_idx, const float* bank_kp3d, const int32_t* bank_v_off,
+                       const int32_t* bank_t_off, int32_t n_cad, const double* K, int32_t h, int32_t w, int32_t V, float* pose,
+                       double* extrinsic, double* kp3d, fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv, int32_t* nearer,
+                       int32_t* tex_pts, int32_t* tex_nv, int32_t* status, void* stream);
+/* The same code on the CPU for HOST arrays (no GPU needed). */
+int fusg_pose_geometry_host(const float* rvec, const float* tvec, const float* err, const float* pose_in, const float* kp_xy,
+                            const double* steps, const int64_t* cad_idx, const float* bank_kp3d, const int32_t* bank_v_off,
+                            const int32_t* bank_t_off, int32_t n_cad, const double* K, int32_t h, int32_t w, int32_t V, float* pose,
+                            double* extrinsic, double* kp3d, fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv,
+                            int32_t* nearer, int32_t* tex_pts, int32_t* tex_nv, int32_t* status);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)
