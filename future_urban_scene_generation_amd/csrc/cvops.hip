@@ -10,6 +10,7 @@
 #include <mutex>
 #include "common.h"
 #include "polygon.h"
+#include "resize.h"
 
 namespace fusg {
 
@@ -166,19 +167,8 @@ __global__ __launch_bounds__(256) void fill_poly_planes_batch_kernel(U8View fram
 }
 
 // ------------------------------------------------------------------------------------------------ resize + Lab
-// cv::resize INTER_LINEAR, uint8: source index / 11-bit weights of one destination coordinate (float arithmetic as in
-// resize.cpp), horizontal pass in int, vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2.
-__device__ __forceinline__ void resize_coef(int d, int ssize, int dsize, int& s, int& a0, int& a1) {
-    const double scale = (double)ssize / dsize;
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int si = (int)floorf(f);
-    f -= (float)si;
-    if (si < 0) { f = 0.f; si = 0; }
-    if (si >= ssize - 1) { f = 0.f; si = ssize - 1; }
-    s = si;
-    a0 = (int)rintf((1.f - f) * 2048.f);
-    a1 = (int)rintf(f * 2048.f);
-}
+// cv::resize INTER_LINEAR, uint8: resize_coef (resize.h, shared with inpaint_inputs.h) gives the source index / 11-bit
+// weights of one destination coordinate; horizontal pass in int, vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2.
 
 struct LabTabs { const unsigned short* gamma; const unsigned short* cbrt; int coef[9]; };
 

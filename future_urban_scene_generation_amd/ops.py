@@ -858,6 +858,123 @@ def merge_u8(out_: torch.Tensor, img: torch.Tensor, mask: torch.Tensor) -> torch
 
 
 # ---------------------------------------------------------------------------------------------
+# EdgeConnect's inputs from a detector mask (csrc/inpaint_inputs.h: create_inpaint_inputs_shape, utils/inpaint_utils.py:35-58)
+# ---------------------------------------------------------------------------------------------
+INPAINT_KEYS = ("img", "gray", "edge", "mask")
+
+
+def gauss_table(sigma: float = 2.0) -> Tuple[_np.ndarray, int]:
+    """The one-sided Gaussian table Canny's smoothing takes, in numpy float64 exactly as SciPy builds its kernel (radius =
+    int(4 sigma + 0.5), exp(-0.5 / sigma^2 * x^2) over -radius..radius divided by its sum): (w[0..radius], radius)."""
+    sigma = float(sigma)
+    if not sigma > 0.0:
+        raise ValueError(f"inpaint_inputs: sigma must be positive, got {sigma}")
+    radius = int(4.0 * sigma + 0.5)
+    x = _np.arange(-radius, radius + 1)
+    phi = _np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return _np.ascontiguousarray(phi[radius:], dtype=_np.float64), radius
+
+
+def _inpaint_args(frame_shape, frame_dtype, det_shape, det_dtype, boxes, gauss_w, radius, max_box, u8) -> Tuple:
+    """What both forms of `inpaint_inputs` check before anything is touched: -> (V, H, W, host boxes or None, table, radius,
+    (max_box_h, max_box_w))."""
+    if frame_dtype != u8 or len(frame_shape) != 3 or frame_shape[2] != 3:
+        raise ValueError(f"inpaint_inputs: frame must be uint8 [H, W, 3], got {frame_dtype} {tuple(frame_shape)}")
+    H, W = int(frame_shape[0]), int(frame_shape[1])
+    if det_dtype != u8 or len(det_shape) != 4 or tuple(det_shape[1:]) != (1, H, W):
+        raise ValueError(f"inpaint_inputs: det_masks must be uint8 [V, 1, {H}, {W}], got {det_dtype} {tuple(det_shape)}")
+    V = int(det_shape[0])
+    gauss_w = _np.ascontiguousarray(gauss_w, dtype=_np.float64).reshape(-1)
+    if radius != gauss_w.shape[0] - 1 or not 0 <= radius <= 32:
+        raise ValueError(f"inpaint_inputs: radius {radius} must be the table's length - 1 ({gauss_w.shape[0] - 1}) and at most 32")
+    host = None
+    if not torch.is_tensor(boxes) or not boxes.is_cuda:
+        host = _np.ascontiguousarray(_np.asarray(boxes).reshape(-1, 4), dtype=_np.int64)
+        if host.shape[0] != V:
+            raise ValueError(f"inpaint_inputs: {host.shape[0]} boxes for {V} detector masks")
+        bad = (host[:, 0] < 0) | (host[:, 1] < 0) | (host[:, 2] < host[:, 0]) | (host[:, 3] < host[:, 1]) | (host[:, 2] > W) | (host[:, 3] > H)
+        if bad.any():
+            v = int(_np.nonzero(bad)[0][0])
+            raise ValueError(f"inpaint_inputs: box {v} = {host[v].tolist()} leaves the {W} x {H} frame (x0, y0, x1, y1, half-open)")
+        if max_box is None:
+            max_box = (int((host[:, 3] - host[:, 1]).max()), int((host[:, 2] - host[:, 0]).max())) if V else (0, 0)
+        host = host.astype(_np.int32)
+    elif tuple(boxes.shape) != (V, 4) or boxes.dtype != torch.int32:
+        raise ValueError(f"inpaint_inputs: device boxes must be int32 [{V}, 4], got {boxes.dtype} {tuple(boxes.shape)}")
+    if max_box is None:
+        max_box = (H, W)                                          # device boxes nobody has looked at: the frame bounds them
+    return V, H, W, host, gauss_w, int(radius), (int(max_box[0]), int(max_box[1]))
+
+
+def inpaint_inputs(frame: torch.Tensor, det_masks: torch.Tensor, boxes, sigma: float = 2.0, out=None, max_box=None):
+    """EdgeConnect's four inputs for V vehicles, built on the device (fusg_inpaint_inputs, five launches on the current
+    stream): frame CUDA uint8 [H, W, 3]; det_masks CUDA uint8 [V, 1, H, W], the detector's masks in frame coordinates
+    (non-zero = vehicle, read only inside the box); boxes [V, 4] = bbox_new_img (x0, y0, x1, y1, half-open) as a host array
+    (checked here, uploaded without a synchronisation) or a device int32 tensor (then max_box = (h, w) bounds the box
+    extents; default: the frame).  -> {'img' float32 [V, 3, 256, 256], 'gray', 'edge', 'mask' float32 [V, 1, 256, 256]};
+    out: a dict of such buffers (any strides) to write into."""
+    _require_gpu(frame, "frame")
+    _require_gpu(det_masks, "det_masks")
+    gw, radius = gauss_table(sigma)
+    V, H, W, host, gw, radius, mb = _inpaint_args(frame.shape, frame.dtype, det_masks.shape, det_masks.dtype, boxes, gw, radius, max_box,
+                                                  torch.uint8)
+    dev, R = frame.device, 256
+    with torch.cuda.device(dev):
+        if out is None:
+            out = {k: torch.empty((V, 3 if k == "img" else 1, R, R), dtype=torch.float32, device=dev) for k in INPAINT_KEYS}
+        for k in INPAINT_KEYS:
+            if tuple(out[k].shape) != (V, 3 if k == "img" else 1, R, R) or out[k].dtype != torch.float32 or out[k].device != dev:
+                raise ValueError(f"inpaint_inputs: out['{k}'] must be float32 {(V, 3 if k == 'img' else 1, R, R)} on {dev}")
+        if V == 0:
+            return out
+        bx = h2d(host, dev, torch.int32) if host is not None else boxes.contiguous()
+        lib = L.lib()
+        scratch = torch.empty((int(lib.fusg_inpaint_inputs_scratch_bytes(V, mb[0], mb[1])),), dtype=torch.uint8, device=dev)
+        fr, dm = frame.contiguous(), det_masks.contiguous()
+        L.check(lib.fusg_inpaint_inputs(C.byref(desc(fr[None].permute(0, 3, 1, 2))), C.byref(desc(dm)), bx.data_ptr(), gw.ctypes.data, radius,
+                                        mb[0], mb[1], *(C.byref(desc(out[k])) for k in INPAINT_KEYS), scratch.data_ptr(), stream_ptr()),
+                "inpaint_inputs")
+    return out
+
+
+def _np_desc(a: _np.ndarray, dtype: int) -> L.Tensor:
+    """fusg_tensor over a 4-D numpy array, logical [n, c, h, w] (strides in elements)."""
+    d = L.Tensor()
+    d.data = a.ctypes.data
+    d.n, d.c, d.h, d.w = a.shape
+    d.sn, d.sc, d.sh, d.sw = (s // a.itemsize for s in a.strides)
+    d.dtype = dtype
+    return d
+
+
+def inpaint_inputs_host(frame, det_masks, boxes, sigma: float = 2.0, gauss_w=None, radius=None, max_box=None):
+    """`inpaint_inputs` on the CPU by the same code (fusg_inpaint_inputs_host; no GPU needed): numpy in (frame uint8
+    [H, W, 3], det_masks uint8 [V, 1, H, W], boxes [V, 4]) and out.  gauss_w / radius: a table other than `gauss_table(sigma)`."""
+    frame, det_masks = _np.asarray(frame), _np.asarray(det_masks)
+    if gauss_w is None:
+        gauss_w, r = gauss_table(sigma)
+        radius = r if radius is None else radius
+    elif radius is None:
+        radius = len(gauss_w) - 1
+    V, H, W, host, gw, radius, mb = _inpaint_args(frame.shape, frame.dtype, det_masks.shape, det_masks.dtype, _np.asarray(boxes), gauss_w,
+                                                  radius, max_box, _np.uint8)
+    R = 256
+    out = {k: _np.zeros((V, 3 if k == "img" else 1, R, R), dtype=_np.float32) for k in INPAINT_KEYS}
+    if V == 0:
+        return out
+    lib = L.lib()
+    fr, dm = _np.ascontiguousarray(frame), _np.ascontiguousarray(det_masks)
+    nbytes = int(lib.fusg_inpaint_inputs_scratch_bytes(V, mb[0], mb[1]))
+    raw = _np.zeros(nbytes + 16, dtype=_np.uint8)
+    off = (-raw.ctypes.data) % 16
+    L.check(lib.fusg_inpaint_inputs_host(C.byref(_np_desc(fr[None].transpose(0, 3, 1, 2), L.U8)), C.byref(_np_desc(dm, L.U8)), host.ctypes.data,
+                                         gw.ctypes.data, radius, mb[0], mb[1], *(C.byref(_np_desc(out[k], L.F32)) for k in INPAINT_KEYS),
+                                         raw.ctypes.data + off), "inpaint_inputs_host")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------
 def prof_enable(on: bool) -> None:

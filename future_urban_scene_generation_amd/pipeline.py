@@ -470,7 +470,9 @@ class VehiclePipeline:
         are inputs here, and the pose is an output for that renderer.  A pipeline built with inpaint=True also takes
         'inpaint' = {'boxes' host int [V, 4] (bbox_new_img: the 1.3x detector box clipped to the frame), 'img' float32
         [V, 3, R, R], 'gray' / 'edge' / 'mask' float32 [V, 1, R, R] in [0, 1]} - what create_inpaint_inputs_shape hands
-        EdgeConnect (utils/inpaint_utils.py:35-58: Mask R-CNN mask, dilation, Canny - host steps, out of scope) - runs
+        EdgeConnect (utils/inpaint_utils.py:35-58) - or 'inpaint' = {'boxes', 'det_masks' uint8 [V, 1, H, W]}, the detector's
+        (Mask R-CNN's, out of scope) masks in frame coordinates, from which dilation, whitening, resize, gray and Canny build
+        the four tensors on the device (`ops.inpaint_inputs`, on the inpaint branch's stream beside the other glue) - runs
         EdgeModel -> InpaintingModel -> merge as a fourth branch (:124-129), composites every vehicle's inpainted box under
         its pasted crop in the reference's per-vehicle order (:130-145) and returns 'inpaint_u8' [V, R, R, 3] as well.
 
@@ -1201,9 +1203,7 @@ class VehiclePipeline:
         seeds = scene.get("vehicle_seeds")
         with torch.cuda.device(dev):
             inp = scene.get("inpaint") if self.inpaint else None
-            if self.inpaint and inp is None:
-                raise ValueError("run_frame: this pipeline was built with inpaint=True; the scene needs 'inpaint' = "
-                                 "{'boxes' [V, 4], 'img' [V, 3, R, R], 'gray' / 'edge' / 'mask' [V, 1, R, R]}")
+            ec_form = inpaint_scene_form(inp) if self.inpaint else None
             if V == 0:                                            # no vehicle in the frame (or an empty shard)
                 # an empty shard still hands out a (zero-vehicle) state, so that `run_later_frame` takes part in the gathers
                 return self._no_vehicles(R, "kp_idx", "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if inp is not None else ()),
@@ -1215,6 +1215,8 @@ class VehiclePipeline:
             # ---- host: the homography fits of every plane of every vehicle (1.2 ms for 8 vehicles), before any launch
             jobs = None if self.device_homography else \
                 pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
+            # ---- :121 from a detector mask: EdgeConnect's inputs built on the inpaint branch's stream, beside the glue below
+            ec, ec_join = self._inpaint_inputs(frame, inp, tgt) if ec_form == "det_masks" else (None, None)
             # ---- uint8 glue on the caller's stream
             geom_box = fo.box_geometry((H, W), bboxes, dev)
             img_bbox = fo.crop_resize(frame, geom_box, (R, R), 0)                              # :58-60
@@ -1229,7 +1231,10 @@ class VehiclePipeline:
             nets_in = {"hg_x": hg_x, "icn_x": icn_x, "vu_x": vu_x, "vu_y": vu_y}
             if scene.get("_hg") is not None:                      # geometry mode: keypoints (and CAD logits) already computed
                 nets_in.update(scene["_hg"])
-            if inp is not None:                                   # :121: create_inpaint_inputs_shape's four tensors, given
+            if ec is not None:                                    # :121: create_inpaint_inputs_shape's four tensors, built above
+                ec_join()
+                nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
+            elif inp is not None:                                 # ... or given
                 nets_in.update(ec_img=inp["img"], ec_gray=inp["gray"], ec_edge=inp["edge"], ec_mask=inp["mask"])
             if replay:                                            # ('icn_u8' is consumed by lab2bgr below, before the next replay)
                 out = self._replay(pkey, nets_in, seeds, clone=("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"))
@@ -1241,6 +1246,22 @@ class VehiclePipeline:
             if "cad_logits" in out:
                 out["cad_idx"] = out.pop("cad_logits").argmax(1)                               # :69
         return out
+
+    def _inpaint_inputs(self, frame, inp, tgt):
+        """EdgeConnect's four inputs from scene['inpaint'] = {'boxes', 'det_masks'} (`ops.inpaint_inputs`), issued on the
+        inpaint branch's stream, forked from the current one; `tgt`: a recorded pass's input buffers, written in place.
+        Returns (the four tensors, join): join() makes the current stream wait for them."""
+        from . import ops
+        out = {k: tgt["ec_" + k] for k in ops.INPAINT_KEYS} if tgt else None
+        if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
+            return ops.inpaint_inputs(frame, inp["det_masks"], inp["boxes"], out=out), (lambda: None)
+        st = self._streams.get("inpaint")
+        if st is None:
+            st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
+        ops.fork_to(st)
+        with torch.cuda.stream(st):
+            res = ops.inpaint_inputs(frame, inp["det_masks"], inp["boxes"], out=out)
+        return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
 
     def _warp_planes(self, scene, jobs):
         """The source planes warped to the destination pose: from the host-fitted `jobs`, or (device_homography) from the
@@ -1629,6 +1650,23 @@ def synth_clip(vehicles: int, frames: int, res: int, device, seed: int = 0) -> D
             "vu_y": synth_inputs("vunet", vehicles * frames, res, seed + 1)["y_tilde"].view(vehicles, frames, 3, res, res).to(device)}
 
 
+INPAINT_SCENE_FORMS = ("{'boxes' [V, 4], 'img' [V, 3, R, R], 'gray' / 'edge' / 'mask' [V, 1, R, R]} (EdgeConnect's inputs, given) or "
+                       "{'boxes' [V, 4], 'det_masks' uint8 [V, 1, H, W]} (the detector's masks: the inputs are built on the device)")
+
+
+def inpaint_scene_form(inp) -> str:
+    """Which of its two forms scene['inpaint'] has: 'given' (the four tensors) or 'det_masks'; ValueError when it is
+    missing, mixes the two or completes neither."""
+    keys = set(inp.keys()) if inp is not None else set()
+    given, some = {"img", "gray", "edge", "mask"} <= keys, bool({"img", "gray", "edge", "mask"} & keys)
+    if "boxes" in keys and given and "det_masks" not in keys:
+        return "given"
+    if "boxes" in keys and "det_masks" in keys and not some:
+        return "det_masks"
+    raise ValueError("run_frame: this pipeline was built with inpaint=True; the scene needs 'inpaint' = " + INPAINT_SCENE_FORMS
+                     + (f", got the keys {sorted(keys)}" if keys else ""))
+
+
 def synth_batch(batch: int, res: int, device, inpaint: bool = False, seed: int = 0, nhwc: bool = False) -> Dict[str, torch.Tensor]:
     """Synthetic, device-resident inputs of the shapes/ranges the reference feeds.
     nhwc=True (CUDA devices): the tensors are handed over in the layout the frame driver's glue kernels write and the
@@ -1652,12 +1690,13 @@ def synth_batch(batch: int, res: int, device, inpaint: bool = False, seed: int =
     return out
 
 
-def synth_frame(vehicles: int, frame_hw=(720, 1280), device="cuda", seed: int = 0, inpaint: bool = False) -> Dict:
+def synth_frame(vehicles: int, frame_hw=(720, 1280), device="cuda", seed: int = 0, inpaint=False) -> Dict:
     """A synthetic frame for `VehiclePipeline.run_frame`: smooth random texture, `vehicles` detector boxes, and per
     vehicle what the reference's renderer would hand over - an elliptical sketch (normal-map colours) with its mask,
     five texture-plane quadrilaterals (corner points before and after a small pose change, visibilities) and the planes
     cut out of the frame with them (`fusg_fill_poly_planes_u8`), plus 12 CAD keypoints and camera intrinsics.  All
-    pixel data lives on `device`; point lists and boxes are host arrays, as in the reference."""
+    pixel data lives on `device`; point lists and boxes are host arrays, as in the reference.  inpaint=True adds
+    scene['inpaint'] with EdgeConnect's four (synthetic) input tensors, inpaint="masks" with stand-in detector masks instead."""
     import numpy as np
 
     from .warp_learn import planes_utils as pu
@@ -1709,18 +1748,33 @@ def synth_frame(vehicles: int, frame_hw=(720, 1280), device="cuda", seed: int = 
     extra = {}
     if inpaint:                                                               # EdgeConnect's inputs per vehicle (given, see run_frame)
         from .synth import synth_inputs
-        e = synth_inputs("edge", vehicles, 256, seed)
+        e = synth_inputs("edge", vehicles, 256, seed) if inpaint != "masks" else None
         boxes = []
         for x0, y0, x1, y1 in bboxes:                                         # the 1.3x box, clipped to the frame
             cx, cy, bw, bh = (x0 + x1) / 2, (y0 + y1) / 2, 1.3 * (x1 - x0), 1.3 * (y1 - y0)
             bx0, by0 = max(0, int(cx - bw / 2)), max(0, int(cy - bh / 2))
             boxes.append([bx0, by0, max(bx0 + 2, min(W - 1, int(cx + bw / 2))), max(by0 + 2, min(H - 1, int(cy + bh / 2)))])
-        extra["inpaint"] = {"boxes": np.asarray(boxes, dtype=np.int64), "img": e["img"].to(dev), "gray": e["gray"].to(dev),
-                            "edge": e["edge"].to(dev), "mask": e["mask"].to(dev)}
+        if inpaint == "masks":                                                # ... or a stand-in for the detector's masks (built on the device)
+            extra["inpaint"] = {"boxes": np.asarray(boxes, dtype=np.int64), "det_masks": synth_det_masks(masks, boxes).to(dev)}
+        else:
+            extra["inpaint"] = {"boxes": np.asarray(boxes, dtype=np.int64), "img": e["img"].to(dev), "gray": e["gray"].to(dev),
+                                "edge": e["edge"].to(dev), "mask": e["mask"].to(dev)}
     return {**extra, "frame": frame, "bboxes": np.asarray(bboxes, dtype=np.int64), "masks": t8(masks), "src_sketch": t8(sk_src),
             "dst_sketch": t8(sk_dst), "src_planes": torch.stack(planes), "src_kp": src_kp, "dst_kp": dst_kp,
             "src_vis": np.stack(src_vis), "dst_vis": np.stack(dst_vis), "kp3d": np.stack(kp3d),
             "focals": np.array([1.1 * W, 1.1 * W], np.float32), "centers": np.array([W / 2, H / 2], np.float32)}
+
+
+def synth_det_masks(masks, boxes, grow: int = 3) -> torch.Tensor:
+    """A stand-in for a detector's masks, uint8 [V, 1, H, W] (255 = vehicle): each vehicle mask of `synth_frame` grown by
+    `grow` pixels (a square max filter) and cut to its inpaint box."""
+    import numpy as np
+    m = torch.from_numpy(np.ascontiguousarray(np.stack(masks))).float()[:, None]
+    m = torch.nn.functional.max_pool2d(m, 2 * grow + 1, stride=1, padding=grow)
+    out = torch.zeros(m.shape, dtype=torch.uint8)
+    for v, (x0, y0, x1, y1) in enumerate(boxes):
+        out[v, 0, y0:y1, x0:x1] = (m[v, 0, y0:y1, x0:x1] > 0).to(torch.uint8) * 255
+    return out
 
 
 def synth_later_frame(scene: Dict, step: int) -> Dict:

@@ -548,6 +548,33 @@ int fusg_pose_geometry_host(const float* rvec, const float* tvec, const float* e
                             double* extrinsic, double* kp3d, fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv,
                             int32_t* nearer, int32_t* tex_pts, int32_t* tex_nv, int32_t* status);
 
+/* ---- EdgeConnect's inputs from a detector mask (create_inpaint_inputs_shape, utils/inpaint_utils.py:35-58; like the pose
+ * geometry added without a version step: the entry points are new, nothing existing changed, and FUSG_VERSION 118 is what
+ * the suite pins) ------------------------------------------------------------------------------------------------------ */
+/* Per vehicle v: the detector mask inside the box is dilated by OpenCV's 8 x 8 ellipse (pixels outside the box do not
+ * exist), box pixels under a dilated 255 turn white, the box and the dilated mask are resized to 256 x 256 (cv::resize
+ * INTER_LINEAR), gray is taken from the resized image, the mask is binarised and scikit-image's Canny runs on gray with
+ * the hole masked out - the definition, step by step, heads csrc/inpaint_inputs.h.
+ * frame: u8 HWC (n = 1, c = 3); det_masks: u8 [V, 1, H, W] in frame coordinates (non-zero = vehicle; read only inside
+ * the box); boxes: DEVICE int32 [V][4] = (x0, y0, x1, y1), half-open; gauss_w: HOST double [radius + 1], the one-sided
+ * normalised Gaussian table (copied at the call), radius = int(4 sigma + 0.5) in 0..32; max_box_h / max_box_w: the
+ * largest box extents, what the scratch was sized for (the boxes live on the device, so the host cannot look) - a box
+ * that exceeds them or leaves the frame is treated as a zero-extent box.  Outputs, f32 with any strides: img
+ * [V, 3, 256, 256] and gray [V, 1, 256, 256] = v / 255, mask and edge [V, 1, 256, 256] exactly 0 or 1; a zero-extent
+ * box writes zeros to all four.  scratch: DEVICE, 16-byte aligned, the bytes the size query returns; it holds nothing between calls.
+ * Shapes and arguments are checked on the host before any launch (FUSG_ERR_INVALID); V = 0 launches nothing.  Five
+ * launches, grid.y = V, no atomics; bit-identical to the host twin (the same code, no contraction). */
+int fusg_inpaint_inputs(const fusg_tensor* frame, const fusg_tensor* det_masks, const int32_t* boxes, const double* gauss_w,
+                        int32_t radius, int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
+                        const fusg_tensor* edge, const fusg_tensor* mask, void* scratch, void* stream);
+/* Bytes of scratch for V vehicles whose boxes are at most max_box_h x max_box_w; -1 for a negative argument. */
+int64_t fusg_inpaint_inputs_scratch_bytes(int32_t V, int32_t max_box_h, int32_t max_box_w);
+/* The same code on the CPU in plain loops: every pointer (boxes and scratch too) is a HOST pointer, no GPU needed.  It can
+ * see the boxes, so one that leaves the frame or exceeds max_box_h x max_box_w is refused (FUSG_ERR_INVALID). */
+int fusg_inpaint_inputs_host(const fusg_tensor* frame, const fusg_tensor* det_masks, const int32_t* boxes, const double* gauss_w,
+                             int32_t radius, int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
+                             const fusg_tensor* edge, const fusg_tensor* mask, void* scratch);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)

@@ -1,0 +1,79 @@
+// Stand-alone sanitizer program for the host twin of EdgeConnect's input construction (csrc/inpaint_inputs.hip,
+// fusg_inpaint_inputs_host: the header's per-pixel code in plain loops).  CPU only - it never touches a GPU:
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//       -Xarch_host -fno-sanitize-recover=undefined tests/sanitize/inpaint_inputs_host_main.cpp \
+//       future_urban_scene_generation_amd/csrc/inpaint_inputs.hip -o inpaint_inputs_asan && ./inpaint_inputs_asan
+// It runs three vehicles on a 70 x 90 frame (a box in the frame's corner with a blob on its border, a 5 x 7 box, a zero-extent
+// box) with exactly-sized heap buffers, so that any read or write outside the frame, the masks, the outputs or the scratch is
+// reported, and prints a checksum of the outputs.
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cmath>
+#include <functional>
+#include <vector>
+#include <hip/hip_runtime.h>
+#include "../../include/fusg.h"
+
+namespace fusg {                                    // what the translation unit expects of the rest of the library
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    std::fputc('\n', stderr);
+}
+bool plan_recording() { return false; }
+void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
+}  // namespace fusg
+
+static fusg_tensor desc(void* p, int dtype, long n, long c, long h, long w, long sn, long sc, long sh, long sw) {
+    fusg_tensor t{};
+    t.data = p; t.dtype = dtype;
+    t.n = n; t.c = c; t.h = h; t.w = w;
+    t.sn = sn; t.sc = sc; t.sh = sh; t.sw = sw;
+    return t;
+}
+
+int main() {
+    const int H = 70, W = 90, V = 3, R = 256;
+    std::vector<unsigned char> frame((size_t)H * W * 3), det((size_t)V * H * W, 0);
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x)
+            for (int c = 0; c < 3; ++c) frame[((size_t)y * W + x) * 3 + c] = (unsigned char)(((x / 7 + y / 5) % 2 ? 200 : 40) + 3 * c + (x * y) % 11);
+    const int32_t boxes[V * 4] = {47, 29, 90, 70, 10, 10, 15, 17, 20, 20, 20, 40};
+    for (int y = 29; y < 70; ++y)
+        for (int x = 47; x < 90; ++x)
+            if ((x - 52) * (x - 52) + (y - 50) * (y - 50) < 150) det[(size_t)y * W + x] = (x + y) % 5 ? 255 : 128;
+    det[(size_t)H * W + 12 * W + 12] = 255;
+    const double sigma = 2.0;
+    const int radius = (int)(4.0 * sigma + 0.5);
+    std::vector<double> w((size_t)radius + 1);
+    double sum = 0.0;
+    for (int k = -radius; k <= radius; ++k) sum += std::exp(-0.5 / (sigma * sigma) * k * k);
+    for (int k = 0; k <= radius; ++k) w[k] = std::exp(-0.5 / (sigma * sigma) * k * k) / sum;
+    const int mh = 41, mw = 43;
+    const int64_t nbytes = fusg_inpaint_inputs_scratch_bytes(V, mh, mw);
+    void* scratch = nullptr;
+    if (nbytes <= 0 || posix_memalign(&scratch, 16, (size_t)nbytes)) return 2;
+    std::vector<float> img((size_t)V * 3 * R * R), gray((size_t)V * R * R), edge((size_t)V * R * R), mask((size_t)V * R * R);
+    const fusg_tensor tf = desc(frame.data(), FUSG_U8, 1, 3, H, W, (long)H * W * 3, 1, (long)W * 3, 3);
+    const fusg_tensor td = desc(det.data(), FUSG_U8, V, 1, H, W, (long)H * W, (long)H * W, W, 1);
+    const fusg_tensor ti = desc(img.data(), FUSG_F32, V, 3, R, R, 3L * R * R, (long)R * R, R, 1);
+    const fusg_tensor tg = desc(gray.data(), FUSG_F32, V, 1, R, R, (long)R * R, (long)R * R, R, 1);
+    const fusg_tensor te = desc(edge.data(), FUSG_F32, V, 1, R, R, (long)R * R, (long)R * R, R, 1);
+    const fusg_tensor tm = desc(mask.data(), FUSG_F32, V, 1, R, R, (long)R * R, (long)R * R, R, 1);
+    const int rc = fusg_inpaint_inputs_host(&tf, &td, boxes, w.data(), radius, mh, mw, &ti, &tg, &te, &tm, scratch);
+    if (rc != 0) { std::printf("host twin failed: %d\n", rc); return 1; }
+    double s[4] = {0, 0, 0, 0};
+    for (float v : img) s[0] += v;
+    for (float v : gray) s[1] += v;
+    for (float v : edge) s[2] += v;
+    for (float v : mask) s[3] += v;
+    std::printf("img %.3f gray %.3f edge px %.0f hole px %.0f\n", s[0], s[1], s[2], s[3]);
+    const int32_t outside[V * 4] = {47, 29, 91, 70, 10, 10, 15, 17, 20, 20, 20, 40};        // refused, nothing is read
+    if (fusg_inpaint_inputs_host(&tf, &td, outside, w.data(), radius, mh, mw + 1, &ti, &tg, &te, &tm, scratch) != FUSG_ERR_INVALID) return 3;
+    std::free(scratch);
+    return s[2] > 0 && s[3] > 0 ? 0 : 4;
+}
