@@ -126,6 +126,10 @@ _SIGS = {
     "fusg_inpaint_inputs": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [_TP] * 4 + [C.c_void_p] * 2),
     "fusg_inpaint_inputs_scratch_bytes": (C.c_int64, [C.c_int32] * 3),
     "fusg_inpaint_inputs_host": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [_TP] * 4 + [C.c_void_p]),
+    "fusg_inpaint_inputs_boxed": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [_TP] * 4
+                                  + [C.c_void_p] * 2),
+    "fusg_inpaint_inputs_boxed_host": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [_TP] * 4
+                                       + [C.c_void_p]),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

@@ -1,7 +1,10 @@
 // EdgeConnect's inputs on the device: fusg_inpaint_inputs (include/fusg.h) runs the steps of inpaint_inputs.h - the same
 // per-pixel code as the host twin below - as five launches over all V vehicles (grid.y = V), no atomics:
 //   dilate      32 x 8 box pixels per workgroup; the mask tile with its 4 / 3 pixel halo is staged in LDS (53 LDS reads per
-//               pixel instead of 53 global ones) and the dilated box is written to scratch once
+//               pixel instead of 53 global ones) and the dilated box is written to scratch once.  The tile is filled
+//               through `MaskSrc::px` from either mask source: frame-sized u8 planes (fusg_inpaint_inputs) or one packed
+//               buffer of box-sized u8 / f32 masks (fusg_inpaint_inputs_boxed: row pitch = the box width, so rows start
+//               unaligned; a tile row is 39 consecutive elements read by 39 consecutive lanes, coalesced either way)
 //   box pass    one thread per output pixel: resize of the whitened box (whitened on load) and of the dilated mask, gray,
 //               binarise -> img, gray, mask and the int16 gray / valid plane Canny reads
 //   smooth      one workgroup per image row: the axis-0 Gaussian of m and f per column (17 coalesced int16 reads), the
@@ -21,7 +24,8 @@ namespace fusg {
 struct F32Out { float* p; long sn, sc, sh, sw; };
 struct InpaintK {
     const unsigned char* frame; long fsh, fsw; int H, W;
-    const unsigned char* det; long dsn, dsh, dsw;
+    const unsigned char* det; long dsn, dsh, dsw;               // the masks as frame-sized planes, or (det == nullptr) ...
+    const void* bm; const int64_t* bm_off; long bm_n; int bm_f32;  // ... packed per box: [bh][bw] from element bm_off[v] of bm_n
     const int32_t* boxes;
     F32Out img, gray, edge, mask;
     unsigned char* dil; int16_t* gv; double* s; uint64_t* bits;
@@ -31,19 +35,43 @@ struct InpaintK {
 
 static inline F32Out f32out(const fusg_tensor& t) { return F32Out{(float*)t.data, t.sn, t.sc, t.sh, t.sw}; }
 
+// Does vehicle v's packed mask of bh x bw elements lie inside the buffer?  (bh * bw < 2^30: the frame's sides are < 32768)
+FUSG_HD bool packed_ok(long off, int bh, int bw, long n) { return off >= 0 && off <= n - (long)bh * bw; }
+// Vehicle v's box: ii::box_of, and with packed masks a box whose mask would leave the buffer has no pixels either - every
+// step (not only the one that reads the mask) sees the same zero-extent box, so all four outputs are zeros.
+FUSG_HD ii::Box vehicle_box(const InpaintK& k, int v) {
+    ii::Box b = ii::box_of(k.boxes + v * 4, k.H, k.W, k.max_h, k.max_w);
+    if (!k.det && !packed_ok(k.bm_off[v], b.bh, b.bw, k.bm_n)) b = ii::Box{0, 0, 0, 0};
+    return b;
+}
+// The detector mask of one vehicle, addressed in box coordinates; px(yy, xx): the u8 pixel the dilation reads (a float
+// mask binarised as the reference does, m * 255 > 0 ? 255 : 0 - a NaN gives 0)
+struct MaskSrc {
+    const unsigned char* u8; const float* f32; long sh, sw;
+    FUSG_HD int px(int yy, int xx) const {
+        const long i = (long)yy * sh + (long)xx * sw;
+        return f32 ? (f32[i] * 255.f > 0.f ? 255 : 0) : (int)u8[i];
+    }
+};
+FUSG_HD MaskSrc mask_src(const InpaintK& k, int v, const ii::Box& b) {
+    if (k.det) return MaskSrc{k.det + (long)v * k.dsn + (long)b.y0 * k.dsh + (long)b.x0 * k.dsw, nullptr, k.dsh, k.dsw};
+    const long off = b.bw > 0 && b.bh > 0 ? k.bm_off[v] : 0;
+    return k.bm_f32 ? MaskSrc{nullptr, (const float*)k.bm + off, b.bw, 1} : MaskSrc{(const unsigned char*)k.bm + off, nullptr, b.bw, 1};
+}
+
 // ------------------------------------------------------------------------------------------------ device kernels
 constexpr int DT_W = 32, DT_H = 8, DT_LW = DT_W + ii::KS - 1, DT_LH = DT_H + ii::KS - 1;
 
 __global__ __launch_bounds__(256) void inpaint_dilate_kernel(const InpaintK k, int tiles_x) {
     __shared__ unsigned char tile[DT_LH * DT_LW];
     const int v = blockIdx.y;
-    const ii::Box b = ii::box_of(k.boxes + v * 4, k.H, k.W, k.max_h, k.max_w);
+    const ii::Box b = vehicle_box(k, v);
     const int tx0 = (blockIdx.x % tiles_x) * DT_W, ty0 = (blockIdx.x / tiles_x) * DT_H;
     if (tx0 >= b.bw || ty0 >= b.bh) return;                       // workgroup-uniform
-    const unsigned char* src = k.det + (long)v * k.dsn + (long)b.y0 * k.dsh + (long)b.x0 * k.dsw;
+    const MaskSrc src = mask_src(k, v, b);
     for (int t = threadIdx.x; t < DT_LH * DT_LW; t += 256) {
         const int yy = ty0 - ii::ANCHOR + t / DT_LW, xx = tx0 - ii::ANCHOR + t % DT_LW;
-        tile[t] = ((unsigned)yy < (unsigned)b.bh && (unsigned)xx < (unsigned)b.bw) ? src[(long)yy * k.dsh + (long)xx * k.dsw] : 0;
+        tile[t] = ((unsigned)yy < (unsigned)b.bh && (unsigned)xx < (unsigned)b.bw) ? (unsigned char)src.px(yy, xx) : 0;
     }
     __syncthreads();
     const int x = tx0 + (threadIdx.x % DT_W), y = ty0 + (threadIdx.x / DT_W);
@@ -55,7 +83,7 @@ __global__ __launch_bounds__(256) void inpaint_dilate_kernel(const InpaintK k, i
 
 // the box pass of one output pixel, for host and device
 FUSG_HD void box_pass_px(const InpaintK& k, int v, int y, int x) {
-    const ii::Box b = ii::box_of(k.boxes + v * 4, k.H, k.W, k.max_h, k.max_w);
+    const ii::Box b = vehicle_box(k, v);
     const unsigned char* fr = k.frame + (long)b.y0 * k.fsh + (long)b.x0 * k.fsw;
     const unsigned char* dl = k.dil + (long)v * k.dil_v;
     const ii::BoxPx p = ii::box_px([&](int yy, int xx, int c) { return (int)fr[(long)yy * k.fsh + (long)xx * k.fsw + c]; },
@@ -194,16 +222,29 @@ static bool f32_nchw(const fusg_tensor* t, long V, int c) {
     return t && t->data && t->dtype == FUSG_F32 && t->n == V && t->c == c && t->h == ii::R && t->w == ii::R;
 }
 
-static int inpaint_check(const fusg_tensor* frame, const fusg_tensor* det, const int32_t* boxes, const double* gauss_w, int32_t radius,
+// the packed form's mask arguments (fusg_inpaint_inputs_boxed); V comes from img
+struct PackedMasks { const void* data; int32_t dtype; int64_t n; const int64_t* off; };
+
+static int inpaint_check(const fusg_tensor* frame, const fusg_tensor* det, const PackedMasks* pm, const int32_t* boxes, const double* gauss_w, int32_t radius,
                          int32_t max_h, int32_t max_w, const fusg_tensor* img, const fusg_tensor* gray, const fusg_tensor* edge,
                          const fusg_tensor* mask, void* scratch, const char* what, InpaintK& k, ii::Gauss& g) {
     FUSG_CHECK(frame && frame->data && frame->dtype == FUSG_U8 && frame->n == 1 && frame->c == 3 && frame->sc == 1 && frame->sw >= 3 &&
                frame->h >= 1 && frame->w >= 1 && frame->h < 32768 && frame->w < 32768 && frame->sh >= frame->w * frame->sw,
                "%s: frame must be one u8 HWC image of 3 channels", what);
-    FUSG_CHECK(det && det->dtype == FUSG_U8 && det->c == 1 && det->n >= 0 && det->n < (1 << 16) && (det->n == 0 || det->data) &&
-               det->h == frame->h && det->w == frame->w && det->sw >= 1 && det->sh >= det->w * det->sw && (det->n <= 1 || det->sn >= det->h * det->sh),
-               "%s: det_masks must be u8 [V, 1, H, W] of the frame's H x W", what);
-    const long V = det->n;
+    long V;
+    if (!pm) {
+        FUSG_CHECK(det && det->dtype == FUSG_U8 && det->c == 1 && det->n >= 0 && det->n < (1 << 16) && (det->n == 0 || det->data) &&
+                   det->h == frame->h && det->w == frame->w && det->sw >= 1 && det->sh >= det->w * det->sw && (det->n <= 1 || det->sn >= det->h * det->sh),
+                   "%s: det_masks must be u8 [V, 1, H, W] of the frame's H x W", what);
+        V = det->n;
+    } else {
+        FUSG_CHECK((pm->dtype == FUSG_U8 || pm->dtype == FUSG_F32) && pm->n >= 0 && (pm->n == 0 || pm->data) &&
+                   (pm->dtype != FUSG_F32 || (((uintptr_t)pm->data) & 3) == 0),
+                   "%s: box_masks must be one packed u8 or f32 buffer of n_elems >= 0 elements", what);
+        FUSG_CHECK(img && img->n >= 0 && img->n < (1 << 16), "%s: img must be f32 [V, 3, %d, %d]", what, ii::R, ii::R);
+        V = img->n;
+        FUSG_CHECK(V == 0 || pm->off, "%s: offsets is null", what);
+    }
     FUSG_CHECK(gauss_w && radius >= 0 && radius <= ii::MAX_RADIUS, "%s: gauss_w (host, radius + 1 doubles) with radius in 0..%d, got %d", what,
                ii::MAX_RADIUS, radius);
     FUSG_CHECK(max_h >= 0 && max_w >= 0 && max_h <= frame->h && max_w <= frame->w, "%s: max_box_h / max_box_w (%d, %d) must lie within the frame", what,
@@ -219,7 +260,8 @@ static int inpaint_check(const fusg_tensor* frame, const fusg_tensor* det, const
     const ii::Scratch sl = ii::scratch_layout(V, max_h, max_w);
     char* sc = (char*)scratch;
     k.frame = (const unsigned char*)frame->data; k.fsh = frame->sh; k.fsw = frame->sw; k.H = (int)frame->h; k.W = (int)frame->w;
-    k.det = (const unsigned char*)det->data; k.dsn = det->sn; k.dsh = det->sh; k.dsw = det->sw;
+    if (!pm) { k.det = (const unsigned char*)det->data; k.dsn = det->sn; k.dsh = det->sh; k.dsw = det->sw; }
+    else { k.det = nullptr; k.bm = pm->data; k.bm_off = pm->off; k.bm_n = (long)pm->n; k.bm_f32 = pm->dtype == FUSG_F32; }
     k.boxes = boxes;
     k.img = f32out(*img); k.gray = f32out(*gray); k.edge = f32out(*edge); k.mask = f32out(*mask);
     k.dil = (unsigned char*)sc; k.gv = (int16_t*)(sc + sl.off_gv); k.s = (double*)(sc + sl.off_s); k.bits = (uint64_t*)(sc + sl.off_bits);
@@ -253,36 +295,46 @@ extern "C" int fusg_inpaint_inputs(const fusg_tensor* frame, const fusg_tensor* 
                                    const fusg_tensor* edge, const fusg_tensor* mask, void* scratch, void* stream) {
     InpaintK k{};
     ii::Gauss g{};
-    const int rc = inpaint_check(frame, det_masks, boxes, gauss_w, radius, max_box_h, max_box_w, img, gray, edge, mask, scratch, "inpaint_inputs", k, g);
+    const int rc = inpaint_check(frame, det_masks, nullptr, boxes, gauss_w, radius, max_box_h, max_box_w, img, gray, edge, mask, scratch, "inpaint_inputs", k, g);
     if (rc != FUSG_OK || k.V == 0) return rc;
     return fusg::plan_dispatch(inpaint_launch, stream, k, g);     // the table is copied: a recorded call does not keep gauss_w
 }
 
-// ---- host twin: the same header's code on the CPU in plain loops (no GPU needed); every pointer is a host pointer
-extern "C" int fusg_inpaint_inputs_host(const fusg_tensor* frame, const fusg_tensor* det_masks, const int32_t* boxes, const double* gauss_w,
-                                        int32_t radius, int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
-                                        const fusg_tensor* edge, const fusg_tensor* mask, void* scratch) {
+extern "C" int fusg_inpaint_inputs_boxed(const fusg_tensor* frame, const void* box_masks, int32_t mask_dtype, int64_t n_elems,
+                                         const int64_t* offsets, const int32_t* boxes, const double* gauss_w, int32_t radius,
+                                         int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
+                                         const fusg_tensor* edge, const fusg_tensor* mask, void* scratch, void* stream) {
     InpaintK k{};
     ii::Gauss g{};
-    const int rc = inpaint_check(frame, det_masks, boxes, gauss_w, radius, max_box_h, max_box_w, img, gray, edge, mask, scratch, "inpaint_inputs_host", k, g);
+    const PackedMasks pm{box_masks, mask_dtype, n_elems, offsets};
+    const int rc = inpaint_check(frame, nullptr, &pm, boxes, gauss_w, radius, max_box_h, max_box_w, img, gray, edge, mask, scratch, "inpaint_inputs_boxed", k, g);
     if (rc != FUSG_OK || k.V == 0) return rc;
+    return fusg::plan_dispatch(inpaint_launch, stream, k, g);
+}
+
+// ---- host twin: the same header's code on the CPU in plain loops (no GPU needed); every pointer is a host pointer
+static int inpaint_host(const InpaintK& k, const ii::Gauss& g, const char* what) {
+    const int32_t* boxes = k.boxes;
     for (int v = 0; v < k.V; ++v) {
         const int32_t* b = boxes + v * 4;
         FUSG_CHECK(ii::box_ok(b, k.H, k.W, k.max_h, k.max_w),
-                   "inpaint_inputs_host: box %d = (%d, %d, %d, %d) must lie in the %d x %d frame and within max_box %d x %d", v, b[0], b[1], b[2],
+                   "%s: box %d = (%d, %d, %d, %d) must lie in the %d x %d frame and within max_box %d x %d", what, v, b[0], b[1], b[2],
                    b[3], k.W, k.H, k.max_w, k.max_h);
+        FUSG_CHECK(k.det || packed_ok(k.bm_off[v], b[3] - b[1], b[2] - b[0], k.bm_n),
+                   "%s: the %d x %d mask of box %d at offset %lld leaves the buffer of %ld elements", what, b[3] - b[1], b[2] - b[0], v,
+                   (long long)k.bm_off[v], k.bm_n);
     }
     constexpr int R = ii::R, WPR = ii::WPR;
     double* row_m = new double[2 * R * R];                        // the axis-0 Gaussians of one image
     double* row_f = row_m + R * R;
     uint64_t* kept = new uint64_t[2 * HY_WORDS];
     for (int v = 0; v < k.V; ++v) {
-        const ii::Box bx = ii::box_of(boxes + v * 4, k.H, k.W, k.max_h, k.max_w);
-        const unsigned char* src = k.det + (long)v * k.dsn + (long)bx.y0 * k.dsh + (long)bx.x0 * k.dsw;
+        const ii::Box bx = vehicle_box(k, v);
+        const MaskSrc src = mask_src(k, v, bx);
         for (int y = 0; y < bx.bh; ++y)
             for (int x = 0; x < bx.bw; ++x)
                 k.dil[(long)v * k.dil_v + (long)y * k.max_w + x] = (unsigned char)ii::dilate_px(
-                    [&](int yy, int xx) { return (int)src[(long)yy * k.dsh + (long)xx * k.dsw]; }, y, x, bx.bh, bx.bw, k.el);
+                    [&](int yy, int xx) { return src.px(yy, xx); }, y, x, bx.bh, bx.bw, k.el);
         for (int y = 0; y < R; ++y)
             for (int x = 0; x < R; ++x) box_pass_px(k, v, y, x);
         const int16_t* gv = k.gv + (long)v * R * R;
@@ -333,4 +385,26 @@ extern "C" int fusg_inpaint_inputs_host(const fusg_tensor* frame, const fusg_ten
     delete[] row_m;
     delete[] kept;
     return FUSG_OK;
+}
+
+extern "C" int fusg_inpaint_inputs_host(const fusg_tensor* frame, const fusg_tensor* det_masks, const int32_t* boxes, const double* gauss_w,
+                                        int32_t radius, int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
+                                        const fusg_tensor* edge, const fusg_tensor* mask, void* scratch) {
+    InpaintK k{};
+    ii::Gauss g{};
+    const int rc = inpaint_check(frame, det_masks, nullptr, boxes, gauss_w, radius, max_box_h, max_box_w, img, gray, edge, mask, scratch, "inpaint_inputs_host", k, g);
+    if (rc != FUSG_OK || k.V == 0) return rc;
+    return inpaint_host(k, g, "inpaint_inputs_host");
+}
+
+extern "C" int fusg_inpaint_inputs_boxed_host(const fusg_tensor* frame, const void* box_masks, int32_t mask_dtype, int64_t n_elems,
+                                              const int64_t* offsets, const int32_t* boxes, const double* gauss_w, int32_t radius,
+                                              int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
+                                              const fusg_tensor* edge, const fusg_tensor* mask, void* scratch) {
+    InpaintK k{};
+    ii::Gauss g{};
+    const PackedMasks pm{box_masks, mask_dtype, n_elems, offsets};
+    const int rc = inpaint_check(frame, nullptr, &pm, boxes, gauss_w, radius, max_box_h, max_box_w, img, gray, edge, mask, scratch, "inpaint_inputs_boxed_host", k, g);
+    if (rc != FUSG_OK || k.V == 0) return rc;
+    return inpaint_host(k, g, "inpaint_inputs_boxed_host");
 }

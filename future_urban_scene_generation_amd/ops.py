@@ -974,6 +974,145 @@ def inpaint_inputs_host(frame, det_masks, boxes, sigma: float = 2.0, gauss_w=Non
     return out
 
 
+# ---- the same from masks in BOX coordinates (fusg_inpaint_inputs_boxed): what a detector run on the box crop returns
+def _is_packed_pair(box_masks) -> bool:
+    """An already packed (buffer [n], offsets [V]) pair, as opposed to a sequence of per-vehicle pieces."""
+    return isinstance(box_masks, tuple) and len(box_masks) == 2 and getattr(box_masks[0], "ndim", 0) == 1 \
+        and getattr(box_masks[1], "ndim", 0) == 1
+
+
+def box_mask_pieces(box_masks, what: str = "inpaint_inputs_boxed"):
+    """A sequence of V per-vehicle masks [h_v, w_v] or [1, h_v, w_v] -> (the pieces as 2-D views, their (h, w), int64 offsets
+    [V] into their concatenation, is_cuda).  All uint8 or all float32; all CUDA tensors or all host tensors / arrays."""
+    pcs = []
+    for v, m in enumerate(box_masks):
+        m = m if torch.is_tensor(m) else _np.asarray(m)
+        if m.ndim == 3 and m.shape[0] == 1:
+            m = m[0]
+        if m.ndim != 2:
+            raise ValueError(f"{what}: box_masks[{v}] must be [h, w] or [1, h, w], got {tuple(m.shape)}")
+        pcs.append(m)
+    kinds = {(torch.is_tensor(m) and m.is_cuda, str(m.dtype).replace("torch.", "")) for m in pcs}
+    if len(kinds) > 1 or (kinds and next(iter(kinds))[1] not in ("uint8", "float32")):
+        raise ValueError(f"{what}: box_masks must be all uint8 or all float32, all on the device or all on the host, got {sorted(kinds)}")
+    shapes = [(int(m.shape[0]), int(m.shape[1])) for m in pcs]
+    offs = _np.zeros(len(pcs), dtype=_np.int64)
+    if pcs:
+        offs[1:] = _np.cumsum([h * w for h, w in shapes])[:-1]
+    return pcs, shapes, offs, bool(kinds) and next(iter(kinds))[0]
+
+
+def _boxed_check(shapes, offs, n_elems, host, what: str) -> None:
+    """With host boxes, before any launch: every piece has its clipped box's shape, every packed mask lies in the buffer."""
+    if host is None:
+        return
+    for v in range(host.shape[0]):
+        bh, bw = int(host[v, 3] - host[v, 1]), int(host[v, 2] - host[v, 0])
+        if shapes is not None and shapes[v] != (bh, bw):
+            raise ValueError(f"{what}: box_masks[{v}] is {shapes[v][0]} x {shapes[v][1]}, its box {host[v].tolist()} is {bh} x {bw} (h x w)")
+        if offs is not None and (offs[v] < 0 or offs[v] + bh * bw > n_elems):
+            raise ValueError(f"{what}: the {bh} x {bw} mask of box {v} at offset {int(offs[v])} leaves the buffer of {n_elems} elements")
+
+
+def _boxed_frame_args(frame_shape, frame_dtype, V, boxes, gauss_w, radius, max_box, u8):
+    """`_inpaint_args` for V box-coordinate masks: the frame-form checks with a mask shape that passes."""
+    H, W = (int(frame_shape[0]), int(frame_shape[1])) if len(frame_shape) == 3 else (0, 0)
+    return _inpaint_args(frame_shape, frame_dtype, (V, 1, H, W), u8, boxes, gauss_w, radius, max_box, u8)
+
+
+def inpaint_inputs_boxed(frame: torch.Tensor, box_masks, boxes, sigma: float = 2.0, out=None, max_box=None):
+    """`inpaint_inputs` from the detector's masks in BOX coordinates (fusg_inpaint_inputs_boxed; trajectory_inference.py:113-119,
+    :316-324: Mask R-CNN runs on the box crop): box_masks = a sequence of V tensors or arrays [h_v, w_v] or [1, h_v, w_v], h_v x
+    w_v = vehicle v's box - all uint8 (non-zero = vehicle, a dilated 255 whitens) or all float32 (binarised m * 255 > 0), all
+    CUDA (packed with one `torch.cat`) or all host (packed into one pinned buffer, one asynchronous copy, no synchronisation) -
+    or an already packed pair (buffer [n] CUDA uint8 / float32, offsets int64 [V], device or host).  With host boxes a piece
+    whose shape is not its box's raises ValueError before any launch; with device boxes a mask that would leave the buffer
+    makes its vehicle a zero-extent box (zeros) and is never read.  boxes, sigma, out, max_box and the result: as `inpaint_inputs`."""
+    what = "inpaint_inputs_boxed"
+    _require_gpu(frame, "frame")
+    dev, R = frame.device, 256
+    gw, radius = gauss_table(sigma)
+    if _is_packed_pair(box_masks):
+        buf, offs = box_masks
+        if not torch.is_tensor(buf) or not buf.is_cuda or buf.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"{what}: a packed buffer must be a CUDA uint8 or float32 tensor [n]")
+        pcs, shapes, V = None, None, int(offs.shape[0])
+        offs_host = None if (torch.is_tensor(offs) and offs.is_cuda) else _np.asarray(offs, dtype=_np.int64).reshape(-1)
+    else:
+        pcs, shapes, offs_host, on_dev = box_mask_pieces(box_masks, what)
+        V = len(pcs)
+    V, H, W, host, gw, radius, mb = _boxed_frame_args(frame.shape, frame.dtype, V, boxes, gw, radius, max_box, torch.uint8)
+    n_elems = int(buf.numel()) if pcs is None else int(sum(h * w for h, w in shapes))
+    _boxed_check(shapes, offs_host, n_elems, host, what)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = {k: torch.empty((V, 3 if k == "img" else 1, R, R), dtype=torch.float32, device=dev) for k in INPAINT_KEYS}
+        for k in INPAINT_KEYS:
+            if tuple(out[k].shape) != (V, 3 if k == "img" else 1, R, R) or out[k].dtype != torch.float32 or out[k].device != dev:
+                raise ValueError(f"{what}: out['{k}'] must be float32 {(V, 3 if k == 'img' else 1, R, R)} on {dev}")
+        if V == 0:
+            return out
+        if pcs is not None and on_dev:
+            buf = torch.cat([m.reshape(-1) for m in pcs])
+        elif pcs is not None:                                     # one pinned staging buffer, one copy
+            stage = torch.empty((n_elems,), dtype=torch.uint8 if str(pcs[0].dtype).endswith("uint8") else torch.float32, pin_memory=True)
+            view = stage.numpy()
+            for m, o, (h, w) in zip(pcs, offs_host, shapes):
+                view[o:o + h * w] = (m.numpy() if torch.is_tensor(m) else m).reshape(-1)
+            buf = h2d(stage, dev)
+        off_d = h2d(offs_host, dev, torch.int64) if offs_host is not None else offs.to(torch.int64).contiguous()
+        bx = h2d(host, dev, torch.int32) if host is not None else boxes.contiguous()
+        buf = buf.contiguous()
+        lib = L.lib()
+        scratch = torch.empty((int(lib.fusg_inpaint_inputs_scratch_bytes(V, mb[0], mb[1])),), dtype=torch.uint8, device=dev)
+        fr = frame.contiguous()
+        L.check(lib.fusg_inpaint_inputs_boxed(C.byref(desc(fr[None].permute(0, 3, 1, 2))), buf.data_ptr(), _DT[buf.dtype], n_elems,
+                                              off_d.data_ptr(), bx.data_ptr(), gw.ctypes.data, radius, mb[0], mb[1],
+                                              *(C.byref(desc(out[k])) for k in INPAINT_KEYS), scratch.data_ptr(), stream_ptr()), what)
+    return out
+
+
+def inpaint_inputs_boxed_host(frame, box_masks, boxes, sigma: float = 2.0, gauss_w=None, radius=None, max_box=None):
+    """`inpaint_inputs_boxed` on the CPU by the same code (fusg_inpaint_inputs_boxed_host; no GPU needed): numpy in (pieces or
+    a packed (buffer, offsets) pair) and out.  It sees the offsets: a mask that would leave the buffer is refused (the library's
+    FUSG_ERR_INVALID), a piece of the wrong shape raises ValueError."""
+    what = "inpaint_inputs_boxed_host"
+    frame = _np.asarray(frame)
+    if gauss_w is None:
+        gauss_w, r = gauss_table(sigma)
+        radius = r if radius is None else radius
+    elif radius is None:
+        radius = len(gauss_w) - 1
+    if _is_packed_pair(box_masks):
+        buf, offs = _np.ascontiguousarray(box_masks[0]), _np.ascontiguousarray(box_masks[1], dtype=_np.int64)
+        if buf.dtype not in (_np.uint8, _np.float32):
+            raise ValueError(f"{what}: a packed buffer must be uint8 or float32 [n], got {buf.dtype}")
+        shapes = None
+    else:
+        pcs, shapes, offs, on_dev = box_mask_pieces(box_masks, what)
+        if on_dev:
+            raise ValueError(f"{what}: box_masks must be host arrays")
+        pcs = [m.numpy() if torch.is_tensor(m) else m for m in pcs]
+        buf = _np.concatenate([m.reshape(-1) for m in pcs]) if pcs else _np.zeros(0, _np.uint8)
+    V = int(offs.shape[0])
+    V, H, W, host, gw, radius, mb = _boxed_frame_args(frame.shape, frame.dtype, V, _np.asarray(boxes), gauss_w, radius, max_box, _np.uint8)
+    _boxed_check(shapes, None, int(buf.size), host, what)
+    R = 256
+    out = {k: _np.zeros((V, 3 if k == "img" else 1, R, R), dtype=_np.float32) for k in INPAINT_KEYS}
+    if V == 0:
+        return out
+    lib = L.lib()
+    fr = _np.ascontiguousarray(frame)
+    nbytes = int(lib.fusg_inpaint_inputs_scratch_bytes(V, mb[0], mb[1]))
+    raw = _np.zeros(nbytes + 16, dtype=_np.uint8)
+    off = (-raw.ctypes.data) % 16
+    L.check(lib.fusg_inpaint_inputs_boxed_host(C.byref(_np_desc(fr[None].transpose(0, 3, 1, 2), L.U8)), buf.ctypes.data,
+                                               L.U8 if buf.dtype == _np.uint8 else L.F32, int(buf.size), offs.ctypes.data, host.ctypes.data,
+                                               gw.ctypes.data, radius, mb[0], mb[1], *(C.byref(_np_desc(out[k], L.F32)) for k in INPAINT_KEYS),
+                                               raw.ctypes.data + off), what)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------

@@ -140,8 +140,23 @@ def slice_scene(scene: Dict, lo: int, hi: int) -> Dict:
         if scene.get(k) is not None:
             out[k] = scene[k][lo:hi]
     if scene.get("inpaint") is not None:
-        out["inpaint"] = {k: v[lo:hi] for k, v in scene["inpaint"].items()}
+        out["inpaint"] = {k: (_box_masks_of(v, range(lo, hi)) if k == "box_masks" else v[lo:hi]) for k, v in scene["inpaint"].items()}
     return out
+
+
+def _box_masks_of(box_masks, keep):
+    """scene['inpaint']['box_masks'] restricted to the vehicles `keep` (host indices): the ragged list of per-vehicle pieces
+    indexed, a packed (buffer, offsets) pair with its offsets selected - the buffer is shared, nothing is copied."""
+    import numpy as np
+
+    from . import ops
+    if not ops._is_packed_pair(box_masks):
+        return [box_masks[v] for v in keep]
+    buf, offs = box_masks
+    idx = list(keep)
+    if torch.is_tensor(offs):
+        return (buf, offs.index_select(0, torch.as_tensor(idx, dtype=torch.long, device=offs.device)))
+    return (buf, np.asarray(offs, dtype=np.int64)[np.asarray(idx, dtype=np.int64)])
 
 
 def _tensors(o):
@@ -472,7 +487,9 @@ class VehiclePipeline:
         [V, 3, R, R], 'gray' / 'edge' / 'mask' float32 [V, 1, R, R] in [0, 1]} - what create_inpaint_inputs_shape hands
         EdgeConnect (utils/inpaint_utils.py:35-58) - or 'inpaint' = {'boxes', 'det_masks' uint8 [V, 1, H, W]}, the detector's
         (Mask R-CNN's, out of scope) masks in frame coordinates, from which dilation, whitening, resize, gray and Canny build
-        the four tensors on the device (`ops.inpaint_inputs`, on the inpaint branch's stream beside the other glue) - runs
+        the four tensors on the device (`ops.inpaint_inputs`, on the inpaint branch's stream beside the other glue), or
+        'inpaint' = {'boxes', 'box_masks'}: the same masks in BOX coordinates, as a detector run on the box crop returns them
+        (:113-119) - V pieces [h_v, w_v] uint8 / float32 or a packed (buffer, offsets) pair (`ops.inpaint_inputs_boxed`) - runs
         EdgeModel -> InpaintingModel -> merge as a fourth branch (:124-129), composites every vehicle's inpainted box under
         its pasted crop in the reference's per-vehicle order (:130-145) and returns 'inpaint_u8' [V, R, R, 3] as well.
 
@@ -534,7 +551,9 @@ class VehiclePipeline:
             v = scene.get(k)
             if v is None or k == "inpaint":
                 continue
-            if torch.is_tensor(v):
+            if k == "box_masks":                                  # ragged pieces or a packed pair
+                out[k] = _box_masks_of(v, keep)
+            elif torch.is_tensor(v):
                 out[k] = v.index_select(0, idx.to(v.device))
             elif isinstance(v, np.ndarray):
                 out[k] = v[np.asarray(keep, dtype=np.int64)]
@@ -862,6 +881,8 @@ class VehiclePipeline:
             sub["kp_nv_d"] = gs["kp_nv_d"]
         if scene.get("vehicle_seeds") is not None:
             sub["vehicle_seeds"] = [scene["vehicle_seeds"][veh[i]] for i in keep]
+        if self._later_inpaint(scene) is not None:               # per first-frame vehicle, like the seeds: a skipped one is not inpainted
+            sub["inpaint"] = self._select(scene["inpaint"], [veh[i] for i in keep], list(scene["inpaint"].keys()))
         sub.pop("steps", None)
         sub_state = dict(state, geometry=None, sharded=False,
                          appearance=[self._select({"a": a}, keep, ("a",))["a"] for a in state["appearance"]],
@@ -881,7 +902,8 @@ class VehiclePipeline:
         3-D keypoints by v @ z_rot(theta) + tr, trajectory_inference.py:359-363), rendered at the first frame's extrinsic,
         its moved keypoints projected with K (:364-367) -> 'dst_sketch', 'masks', 'dst_kp', 'dst_vis'
         (render.vehicle_geometry); then the given-geometry path of `run_later_frame` for the vehicles whose render is not
-        empty (replay=True: its recorded pass of that many vehicles).  Returns its keys (for those vehicles, in order),
+        empty (replay=True: its recorded pass of that many vehicles); scene['inpaint'] lists every first-frame vehicle, like
+        'steps', and is selected with the kept ones (a skipped vehicle is not inpainted).  Returns its keys (for those vehicles, in order),
         'geometry' (the derived keys of every vehicle of the state) and 'skipped' (first-frame vehicle indices: skipped there or
         rendering empty now - not pasted).  A RANK-LOCAL state of a sharded first frame: see `_geometry_later_sharded`."""
         if not _one_rank(self.group) and state.get("sharded"):
@@ -897,6 +919,10 @@ class VehiclePipeline:
         import numpy as np
 
         from . import render as rd
+        if self._later_inpaint(scene) is not None:
+            raise ValueError("run_later_frame: a sharded geometry-mode later frame with scene['inpaint'] is not supported (rank 0 would "
+                             "need every rank's inpainted boxes spread over the kept vehicles); inpaint later frames in geometry mode "
+                             "on one rank, or shard a given-geometry clip")
         rng = torch.get_rng_state() if (check == "sync" and scene.get("vehicle_seeds") is None) else None
         dev = self.device
         lo, hi, V = state["shard"]
@@ -1129,17 +1155,17 @@ class VehiclePipeline:
 
     GATHERED = ("kp_idx", "icn_u8", "vunet_u8", "geom")
 
-    def _gather_keys(self, first_frame: bool):
-        if not first_frame:
-            return ("icn_u8", "vunet_u8", "geom")
+    def _gather_keys(self, first_frame: bool, inpaint: bool = False):
+        if not first_frame:                                       # (inpaint: the later scene carries 'inpaint')
+            return ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
         return self.GATHERED + (("inpaint_u8",) if self.inpaint else ()) + (("cad_idx",) if self.cad is not None else ())
 
-    def _gather_local(self, local, V, first_frame=True):
+    def _gather_local(self, local, V, first_frame=True, inpaint=False):
         """The frame's only exchange: this rank's crops / keypoint indices / crop rows -> rank 0, in vehicle order (a few small
         messages; RCCL gather on device tensors, gloo through the host).  Returns the full dict on rank 0, None elsewhere."""
         import torch.distributed as dist
         full = {}
-        for k in self._gather_keys(first_frame):
+        for k in self._gather_keys(first_frame, inpaint):
             g = gather_in_order(local[k].contiguous(), V, self.group)
             full[k] = None if g is None else g.to(self.device)
         return full if dist.get_rank(self.group) == 0 else None
@@ -1216,7 +1242,7 @@ class VehiclePipeline:
             jobs = None if self.device_homography else \
                 pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
             # ---- :121 from a detector mask: EdgeConnect's inputs built on the inpaint branch's stream, beside the glue below
-            ec, ec_join = self._inpaint_inputs(frame, inp, tgt) if ec_form == "det_masks" else (None, None)
+            ec, ec_join = self._inpaint_inputs(frame, inp, tgt) if ec_form in ("det_masks", "box_masks") else (None, None)
             # ---- uint8 glue on the caller's stream
             geom_box = fo.box_geometry((H, W), bboxes, dev)
             img_bbox = fo.crop_resize(frame, geom_box, (R, R), 0)                              # :58-60
@@ -1248,19 +1274,26 @@ class VehiclePipeline:
         return out
 
     def _inpaint_inputs(self, frame, inp, tgt):
-        """EdgeConnect's four inputs from scene['inpaint'] = {'boxes', 'det_masks'} (`ops.inpaint_inputs`), issued on the
-        inpaint branch's stream, forked from the current one; `tgt`: a recorded pass's input buffers, written in place.
-        Returns (the four tensors, join): join() makes the current stream wait for them."""
+        """EdgeConnect's four inputs from scene['inpaint'] = {'boxes', 'det_masks'} (`ops.inpaint_inputs`) or {'boxes',
+        'box_masks'} (`ops.inpaint_inputs_boxed`), issued on the inpaint branch's stream, forked from the current one; `tgt`: a
+        recorded pass's input buffers, written in place.  Returns (the four tensors, join): join() makes the current stream
+        wait for them."""
         from . import ops
         out = {k: tgt["ec_" + k] for k in ops.INPAINT_KEYS} if tgt else None
+
+        def build():
+            if "box_masks" in inp:
+                return ops.inpaint_inputs_boxed(frame, inp["box_masks"], inp["boxes"], out=out)
+            return ops.inpaint_inputs(frame, inp["det_masks"], inp["boxes"], out=out)
+
         if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
-            return ops.inpaint_inputs(frame, inp["det_masks"], inp["boxes"], out=out), (lambda: None)
+            return build(), (lambda: None)
         st = self._streams.get("inpaint")
         if st is None:
             st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
         ops.fork_to(st)
         with torch.cuda.stream(st):
-            res = ops.inpaint_inputs(frame, inp["det_masks"], inp["boxes"], out=out)
+            res = build()
         return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
 
     def _warp_planes(self, scene, jobs):
@@ -1341,6 +1374,11 @@ class VehiclePipeline:
         images independent of batching); state: `run_frame(...)["state"]` of the same vehicles, same order.
         replay=True issues the two networks (ICN, VUnet shape half) as ONE recorded-plan replay per vehicle count, like
         `run_frame(replay=True)`: five of a clip's six frames are later frames, and at 8 vehicles the interpreter bounds the eager form.
+        With a pipeline built with inpaint=True the scene may carry 'inpaint' in any of `run_frame`'s three forms, for THIS frame's
+        boxes (:301-350): EdgeConnect's inputs come from this scene's frame, EdgeModel -> InpaintingModel -> merge runs as a third
+        stream branch, the composite starts from the frame ('background' is ignored, :340) and every vehicle's inpainted box is
+        pasted under its crop in vehicle order; the result gains 'inpaint_u8' [V, R, R, 3].  Without the key (or with
+        inpaint=False, which ignores it) nothing changes.  replay=True keeps the inpaint pass as a recorded plan of its own.
         Returns 'icn_u8' / 'vunet_u8' uint8 [V, R, R, 3] (BGR), 'frame_icn' / 'frame_vunet' uint8 [H, W, 3], 'geom'.
 
         Geometry mode (state of a geometry-mode `run_frame`, a scene without 'masks'): see `_geometry_later_frame`."""
@@ -1357,7 +1395,8 @@ class VehiclePipeline:
             if int(scene["masks"].shape[0]) != V:
                 raise ValueError(f"run_later_frame: the state was made for a frame of {V} vehicles, the scene holds {int(scene['masks'].shape[0])}")
             local = self._guarded(self._later_local, (slice_scene(scene, lo, hi), state, replay), check, rng)
-            full = self._gather_local(local, V, False)
+            # (every rank holds the same scene, so all of them gather 'inpaint_u8' or none does)
+            full = self._gather_local(local, V, False, self._later_inpaint(scene) is not None)
             return None if full is None else self._later_finish(scene, full)
         return self._guarded(self._run_later_frame, (scene, state, replay), check, rng)
 
@@ -1367,7 +1406,8 @@ class VehiclePipeline:
     @torch.no_grad()
     def _later_nets(self, batch, vehicle_seeds=None):
         """The two networks of a later frame (trajectory_inference.py:389, :424-426) as a pass function (`CompiledPass(fn=...)`):
-        batch = 'icn_x' [V, 21, R, R], 'vu_y' [V, 3, R, R], 'app0' / 'app1' = the first frame's appearance code."""
+        batch = 'icn_x' [V, 21, R, R], 'vu_y' [V, 3, R, R], 'app0' / 'app1' = the first frame's appearance code; with 'ec_img',
+        'ec_gray', 'ec_edge', 'ec_mask' EdgeModel -> InpaintingModel -> merge (:328-336) runs as a third branch -> 'inpaint_u8'."""
         from . import ops
         self.vunet.set_vehicle_seeds(vehicle_seeds)
 
@@ -1380,12 +1420,22 @@ class VehiclePipeline:
             xt, _, _ = vu.forward_dec_down(do, ds, [batch["app0"], batch["app1"]])         # :425
             return {"vunet_u8": ops.to_image_u8(xt)}                                       # :426
 
-        return self._branches([("icn", icn), ("vunet", vunet)])
+        def inpaint():
+            e = self.edge(batch["ec_gray"], batch["ec_edge"], batch["ec_mask"])            # :328-336
+            p = self.inp(batch["ec_img"], e, batch["ec_mask"])
+            return {"inpaint_u8": ops.merge_u8(p, batch["ec_img"], batch["ec_mask"])}
+
+        return self._branches([("icn", icn), ("vunet", vunet)] + ([("inpaint", inpaint)] if "ec_img" in batch else []))
+
+    def _later_inpaint(self, scene):
+        """A later scene's 'inpaint' entry, for a pipeline built with inpaint=True (None: today's path without inpainting)."""
+        return scene.get("inpaint") if self.inpaint else None
 
     @torch.no_grad()
     def _later_local(self, scene, state, replay=False):
         """The per-vehicle part of a later frame for the vehicles `scene` lists (all, or one rank's shard - `state` holds
-        exactly these vehicles): warp, ICN, VUnet shape half.  Returns 'icn_u8' (BGR), 'vunet_u8', 'geom'."""
+        exactly these vehicles): warp, ICN, VUnet shape half (+ EdgeConnect on THIS frame's boxes when the scene carries
+        'inpaint', :301-350).  Returns 'icn_u8' (BGR), 'vunet_u8', 'geom' (+ 'inpaint_u8')."""
         from . import frame_ops as fo
         from . import ops
         from .warp_learn import planes_utils as pu
@@ -1395,19 +1445,33 @@ class VehiclePipeline:
         V = int(scene["masks"].shape[0])
         if state["central"].shape[0] != V:
             raise ValueError(f"run_later_frame: the state holds {state['central'].shape[0]} vehicles, the scene {V}")
+        inp = self._later_inpaint(scene)
+        ec_form = inpaint_scene_form(inp) if inp is not None else None
         with torch.cuda.device(dev):
             if V == 0:
-                return self._no_vehicles(R, "icn_u8", "vunet_u8", "geom")
+                return self._no_vehicles(R, "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if inp is not None else ()))
+            replay = replay and ops.RECORDER is None
+            # (an inpaint marker in the key: the plans of scenes without 'inpaint' are the ones recorded before)
+            pkey = ("later", V, ops.PRECISION) + (("inpaint",) if inp is not None else ())
+            cp = self._plan(pkey) if (replay and inp is not None) else None
+            tgt = cp.inputs if cp is not None else {}            # a recorded pass's EdgeConnect inputs are written in place
             jobs = None if self.device_homography else \
                 pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
+            # ---- :326 from a detector mask: EdgeConnect's inputs of this frame's boxes, on the inpaint branch's stream
+            ec, ec_join = self._inpaint_inputs(frame, inp, tgt) if ec_form in ("det_masks", "box_masks") else (None, None)
             warped = self._warp_planes(scene, jobs)                                            # :376-381
             _, geom = fo.mask_bbox_geom(scene["masks"])
             icn_x = pu.icn_inputs_device(warped, scene["dst_sketch"], state["central"], geom, R, R)   # :385-387
             _, vu_y = fo.vunet_inputs(frame, scene["masks"], scene["dst_sketch"], scene["dst_sketch"], geom, R)   # :415-420 (y_tilde only)
             seeds = scene.get("vehicle_seeds")
             nets_in = {"icn_x": icn_x, "vu_y": vu_y, "app0": state["appearance"][0], "app1": state["appearance"][1]}
-            if replay and ops.RECORDER is None:
-                out = self._replay(("later", V, ops.PRECISION), nets_in, seeds, fn=self._later_nets)
+            if ec is not None:
+                ec_join()
+                nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
+            elif inp is not None:                                 # given
+                nets_in.update(ec_img=inp["img"], ec_gray=inp["gray"], ec_edge=inp["edge"], ec_mask=inp["mask"])
+            if replay:
+                out = self._replay(pkey, nets_in, seeds, fn=self._later_nets)
             else:
                 out = self._later_nets(nets_in, seeds)
             out["icn_u8"] = pu.lab2bgr(out["icn_u8"])
@@ -1417,16 +1481,24 @@ class VehiclePipeline:
     @torch.no_grad()
     def _later_finish(self, scene, out):
         """The frame-level part of a later frame, on the rank that holds every vehicle's crops: the ordered paste."""
+        import numpy as np
+
+        from . import ops
         from .warp_learn import planes_utils as pu
         frame = scene["frame"]
         out = dict(out)
+        inp = self._later_inpaint(scene)
         with torch.cuda.device(self.device):
-            back = scene.get("background", frame)
+            back = frame if inp is not None else scene.get("background", frame)   # :340: with --inpaint the composite starts from the frame
             if int(scene["masks"].shape[0]) == 0:
                 out["frame_icn"], out["frame_vunet"] = back.clone(), back.clone()
                 return out
-            out["frame_icn"] = pu.paste_back_device(back, out["icn_u8"], out["geom"], scene["masks"])       # :393-410
-            out["frame_vunet"] = pu.paste_back_device(back, out["vunet_u8"], out["geom"], scene["masks"])   # :428-445
+            box = {}
+            if inp is not None:                                   # :340-350: every vehicle's inpainted box under its crop, in vehicle order
+                rows = [[int(b[0]), int(b[1]), int(b[2]), int(b[3]), 0, 0, 0, 0] for b in np.asarray(inp["boxes"]).reshape(-1, 4)]
+                box = dict(box_images=out["inpaint_u8"], box_geom=ops.h2d(rows, self.device, torch.int32))
+            out["frame_icn"] = pu.paste_back_device(back, out["icn_u8"], out["geom"], scene["masks"], **box)       # :393-410
+            out["frame_vunet"] = pu.paste_back_device(back, out["vunet_u8"], out["geom"], scene["masks"], **box)   # :428-445
         return out
 
     def run_later_frames(self, scenes, state: Dict, replay: bool = False):
@@ -1651,18 +1723,22 @@ def synth_clip(vehicles: int, frames: int, res: int, device, seed: int = 0) -> D
 
 
 INPAINT_SCENE_FORMS = ("{'boxes' [V, 4], 'img' [V, 3, R, R], 'gray' / 'edge' / 'mask' [V, 1, R, R]} (EdgeConnect's inputs, given) or "
-                       "{'boxes' [V, 4], 'det_masks' uint8 [V, 1, H, W]} (the detector's masks: the inputs are built on the device)")
+                       "{'boxes' [V, 4], 'det_masks' uint8 [V, 1, H, W]} (the detector's masks: the inputs are built on the device) or "
+                       "{'boxes' [V, 4], 'box_masks' V pieces [h_v, w_v] uint8 / float32, or a packed (buffer, offsets) pair} (the "
+                       "detector's masks in box coordinates)")
 
 
 def inpaint_scene_form(inp) -> str:
-    """Which of its two forms scene['inpaint'] has: 'given' (the four tensors) or 'det_masks'; ValueError when it is
-    missing, mixes the two or completes neither."""
+    """Which of its three forms scene['inpaint'] has: 'given' (the four tensors), 'det_masks' (frame coordinates) or
+    'box_masks' (box coordinates); ValueError when it is missing, mixes them or completes none."""
     keys = set(inp.keys()) if inp is not None else set()
     given, some = {"img", "gray", "edge", "mask"} <= keys, bool({"img", "gray", "edge", "mask"} & keys)
-    if "boxes" in keys and given and "det_masks" not in keys:
+    if "boxes" in keys and given and not {"det_masks", "box_masks"} & keys:
         return "given"
-    if "boxes" in keys and "det_masks" in keys and not some:
+    if "boxes" in keys and "det_masks" in keys and not some and "box_masks" not in keys:
         return "det_masks"
+    if "boxes" in keys and "box_masks" in keys and not some and "det_masks" not in keys:
+        return "box_masks"
     raise ValueError("run_frame: this pipeline was built with inpaint=True; the scene needs 'inpaint' = " + INPAINT_SCENE_FORMS
                      + (f", got the keys {sorted(keys)}" if keys else ""))
 
@@ -1749,11 +1825,7 @@ def synth_frame(vehicles: int, frame_hw=(720, 1280), device="cuda", seed: int = 
     if inpaint:                                                               # EdgeConnect's inputs per vehicle (given, see run_frame)
         from .synth import synth_inputs
         e = synth_inputs("edge", vehicles, 256, seed) if inpaint != "masks" else None
-        boxes = []
-        for x0, y0, x1, y1 in bboxes:                                         # the 1.3x box, clipped to the frame
-            cx, cy, bw, bh = (x0 + x1) / 2, (y0 + y1) / 2, 1.3 * (x1 - x0), 1.3 * (y1 - y0)
-            bx0, by0 = max(0, int(cx - bw / 2)), max(0, int(cy - bh / 2))
-            boxes.append([bx0, by0, max(bx0 + 2, min(W - 1, int(cx + bw / 2))), max(by0 + 2, min(H - 1, int(cy + bh / 2)))])
+        boxes = synth_inpaint_boxes(bboxes, (H, W))
         if inpaint == "masks":                                                # ... or a stand-in for the detector's masks (built on the device)
             extra["inpaint"] = {"boxes": np.asarray(boxes, dtype=np.int64), "det_masks": synth_det_masks(masks, boxes).to(dev)}
         else:
@@ -1763,6 +1835,28 @@ def synth_frame(vehicles: int, frame_hw=(720, 1280), device="cuda", seed: int = 
             "dst_sketch": t8(sk_dst), "src_planes": torch.stack(planes), "src_kp": src_kp, "dst_kp": dst_kp,
             "src_vis": np.stack(src_vis), "dst_vis": np.stack(dst_vis), "kp3d": np.stack(kp3d),
             "focals": np.array([1.1 * W, 1.1 * W], np.float32), "centers": np.array([W / 2, H / 2], np.float32)}
+
+
+def synth_inpaint_boxes(bboxes, frame_hw, shift=None) -> list:
+    """bbox_new_img of every detector box: the 1.3x box (its centre moved by shift[v] = (dx, dy)), clipped to the frame."""
+    H, W = frame_hw
+    boxes = []
+    for v, (x0, y0, x1, y1) in enumerate(bboxes):
+        dx, dy = (0, 0) if shift is None else shift[v]
+        cx, cy, bw, bh = (x0 + x1) / 2 + dx, (y0 + y1) / 2 + dy, 1.3 * (x1 - x0), 1.3 * (y1 - y0)
+        bx0, by0 = max(0, int(cx - bw / 2)), max(0, int(cy - bh / 2))
+        boxes.append([bx0, by0, max(bx0 + 2, min(W - 1, int(cx + bw / 2))), max(by0 + 2, min(H - 1, int(cy + bh / 2)))])
+    return boxes
+
+
+def synth_box_masks(masks: torch.Tensor, boxes, dtype=torch.uint8) -> list:
+    """`synth_det_masks`'s planes [V, 1, H, W] cut to their boxes, as a detector run on the box crop returns them: V pieces
+    [h_v, w_v], uint8 as they are or float32 in [0, 1]."""
+    out = []
+    for v, (x0, y0, x1, y1) in enumerate(boxes):
+        m = masks[v, 0, int(y0):int(y1), int(x0):int(x1)]
+        out.append(m.contiguous() if dtype == torch.uint8 else (m.to(torch.float32) / 255.0).contiguous())
+    return out
 
 
 def synth_det_masks(masks, boxes, grow: int = 3) -> torch.Tensor:
@@ -1777,10 +1871,13 @@ def synth_det_masks(masks, boxes, grow: int = 3) -> torch.Tensor:
     return out
 
 
-def synth_later_frame(scene: Dict, step: int) -> Dict:
+def synth_later_frame(scene: Dict, step: int, inpaint=None) -> Dict:
     """The scene of `synth_frame` one trajectory step later, for `run_later_frame`: the same vehicles (masks, first-frame planes
     and their corner points), new plane corner points for the new pose (seeded by `step`), the source sketch as the new pose's
-    sketch, and one noise seed per (vehicle, step) when the first frame had per-vehicle seeds."""
+    sketch, and one noise seed per (vehicle, step) when the first frame had per-vehicle seeds.  inpaint: None (the scene as it
+    always was; a first frame's 'inpaint' entry passes through untouched) or the form of scene['inpaint'] for this step's boxes
+    (the 1.3x boxes moved by a few pixels, seeded by `step`): "given" (synthetic tensors), "masks" (`synth_det_masks`) or
+    "box_masks" (`synth_box_masks`, uint8)."""
     import numpy as np
     g = np.random.default_rng(1000 + step)
     out = dict(scene)
@@ -1788,4 +1885,24 @@ def synth_later_frame(scene: Dict, step: int) -> Dict:
     out["dst_sketch"] = scene["src_sketch"]
     if scene.get("vehicle_seeds") is not None:
         out["vehicle_seeds"] = [int(sd) * 64 + step for sd in scene["vehicle_seeds"]]
+    if inpaint is not None:
+        if inpaint not in ("given", "masks", "box_masks"):
+            raise ValueError(f"synth_later_frame: inpaint must be None, 'given', 'masks' or 'box_masks', got {inpaint!r}")
+        dev = scene["frame"].device
+        H, W = int(scene["frame"].shape[0]), int(scene["frame"].shape[1])
+        V = len(scene["bboxes"])
+        gb = np.random.default_rng(2000 + step)                                # (its own generator: the draws above stay as they were)
+        boxes = synth_inpaint_boxes(np.asarray(scene["bboxes"]).reshape(-1, 4).tolist(), (H, W), gb.integers(-6, 7, (V, 2)).tolist())
+        inp = {"boxes": np.asarray(boxes, dtype=np.int64).reshape(-1, 4)}
+        if inpaint == "given":
+            from .synth import synth_inputs
+            e = synth_inputs("edge", V, 256, 1000 + step)
+            inp.update({k: e[k].to(dev) for k in ("img", "gray", "edge", "mask")})
+        else:
+            planes = synth_det_masks(list(scene["masks"].cpu().numpy()), boxes) if V else torch.zeros((0, 1, H, W), dtype=torch.uint8)
+            if inpaint == "masks":
+                inp["det_masks"] = planes.to(dev)
+            else:
+                inp["box_masks"] = [m.to(dev) for m in synth_box_masks(planes, boxes)]
+        out["inpaint"] = inp
     return out

@@ -575,6 +575,26 @@ int fusg_inpaint_inputs_host(const fusg_tensor* frame, const fusg_tensor* det_ma
                              int32_t radius, int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
                              const fusg_tensor* edge, const fusg_tensor* mask, void* scratch);
 
+/* The same with the detector's masks in BOX coordinates, as Mask R-CNN run on the box crop returns them
+ * (trajectory_inference.py:113-119, :316-324) - also added without a version step.  The arguments are those of
+ * fusg_inpaint_inputs with det_masks replaced by box_masks: ONE packed DEVICE buffer of n_elems elements of mask_dtype
+ * (FUSG_U8: the byte as it is, non-zero = vehicle and only a dilated 255 whitens, as above; FUSG_F32: the reference's
+ * binarisation m * 255 > 0 ? 255 : 0, so a NaN gives 0), and offsets: DEVICE int64 [V] - vehicle v's mask is row-major
+ * [bh][bw] from element offsets[v], bh x bw its box as clipped above.  V is img's n.  The boxes and offsets live on the
+ * device: a vehicle whose offset is negative or whose offsets[v] + bh * bw exceeds n_elems is treated as a zero-extent box
+ * (zeros to all four outputs) and is never read.  Only the dilation's tile fill reads the masks; everything behind that
+ * pixel, the scratch and its size query are those of fusg_inpaint_inputs.  Bit-identical to the host twin. */
+int fusg_inpaint_inputs_boxed(const fusg_tensor* frame, const void* box_masks, int32_t mask_dtype, int64_t n_elems,
+                              const int64_t* offsets, const int32_t* boxes, const double* gauss_w, int32_t radius,
+                              int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
+                              const fusg_tensor* edge, const fusg_tensor* mask, void* scratch, void* stream);
+/* The same code on the CPU: every pointer is a HOST pointer.  It can see the boxes and offsets, so a mask that would leave
+ * the buffer is refused (FUSG_ERR_INVALID) like a box that leaves the frame. */
+int fusg_inpaint_inputs_boxed_host(const fusg_tensor* frame, const void* box_masks, int32_t mask_dtype, int64_t n_elems,
+                                   const int64_t* offsets, const int32_t* boxes, const double* gauss_w, int32_t radius,
+                                   int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
+                                   const fusg_tensor* edge, const fusg_tensor* mask, void* scratch);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)

@@ -1,0 +1,114 @@
+// Stand-alone sanitizer program for the host twin of EdgeConnect's input construction from BOX-coordinate masks
+// (csrc/inpaint_inputs.hip, fusg_inpaint_inputs_boxed_host).  CPU only - it never touches a GPU:
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//       -Xarch_host -fno-sanitize-recover=undefined tests/sanitize/inpaint_inputs_boxed_host_main.cpp \
+//       future_urban_scene_generation_amd/csrc/inpaint_inputs.hip -o inpaint_inputs_boxed_asan && ./inpaint_inputs_boxed_asan
+// The frame-form program's three vehicles on its 70 x 90 frame, their masks packed box by box into exactly-sized heap buffers
+// (uint8, and float32 with a NaN), so that any read outside a packed mask is reported; the outputs must equal the frame form's
+// byte for byte, and a buffer one element short, a negative offset and an offset past the end are refused before anything is read.
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cmath>
+#include <functional>
+#include <vector>
+#include <hip/hip_runtime.h>
+#include "../../include/fusg.h"
+
+namespace fusg {                                    // what the translation unit expects of the rest of the library
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    std::fputc('\n', stderr);
+}
+bool plan_recording() { return false; }
+void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
+}  // namespace fusg
+
+static fusg_tensor desc(void* p, int dtype, long n, long c, long h, long w, long sn, long sc, long sh, long sw) {
+    fusg_tensor t{};
+    t.data = p; t.dtype = dtype;
+    t.n = n; t.c = c; t.h = h; t.w = w;
+    t.sn = sn; t.sc = sc; t.sh = sh; t.sw = sw;
+    return t;
+}
+
+int main() {
+    const int H = 70, W = 90, V = 3, R = 256;
+    std::vector<unsigned char> frame((size_t)H * W * 3), det((size_t)V * H * W, 0);
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x)
+            for (int c = 0; c < 3; ++c) frame[((size_t)y * W + x) * 3 + c] = (unsigned char)(((x / 7 + y / 5) % 2 ? 200 : 40) + 3 * c + (x * y) % 11);
+    const int32_t boxes[V * 4] = {47, 29, 90, 70, 10, 10, 15, 17, 20, 20, 20, 40};
+    for (int y = 29; y < 70; ++y)
+        for (int x = 47; x < 90; ++x)
+            if ((x - 52) * (x - 52) + (y - 50) * (y - 50) < 150) det[(size_t)y * W + x] = (x + y) % 5 ? 255 : 128;
+    det[(size_t)H * W + 12 * W + 12] = 255;
+    // the same masks packed: vehicle 1 first, then vehicle 0; the zero-extent box points at the very end
+    int64_t offs[V];
+    std::vector<unsigned char> packed;
+    for (int v : {1, 0}) {
+        offs[v] = (int64_t)packed.size();
+        for (int y = boxes[v * 4 + 1]; y < boxes[v * 4 + 3]; ++y)
+            for (int x = boxes[v * 4]; x < boxes[v * 4 + 2]; ++x) packed.push_back(det[((size_t)v * H + y) * W + x]);
+    }
+    offs[2] = (int64_t)packed.size();
+    std::vector<float> packed_f(packed.size());
+    for (size_t i = 0; i < packed.size(); ++i) packed_f[i] = packed[i] ? 0.25f : (i % 3 ? 0.f : -1.f);      // the reference binarises m * 255 > 0
+    std::vector<unsigned char> packed_b(packed.size());
+    for (size_t i = 0; i < packed.size(); ++i) packed_b[i] = packed[i] ? 255 : 0;
+    packed_f[offs[0] + 1] = std::nanf("");                                                                 // a background pixel: NaN -> 0
+    const double sigma = 2.0;
+    const int radius = (int)(4.0 * sigma + 0.5);
+    std::vector<double> w((size_t)radius + 1);
+    double sum = 0.0;
+    for (int k = -radius; k <= radius; ++k) sum += std::exp(-0.5 / (sigma * sigma) * k * k);
+    for (int k = 0; k <= radius; ++k) w[k] = std::exp(-0.5 / (sigma * sigma) * k * k) / sum;
+    const int mh = 41, mw = 43;
+    const int64_t nbytes = fusg_inpaint_inputs_scratch_bytes(V, mh, mw);
+    void* scratch = nullptr;
+    if (nbytes <= 0 || posix_memalign(&scratch, 16, (size_t)nbytes)) return 2;
+    const size_t n1 = (size_t)V * R * R;
+    std::vector<float> out[3][4];
+    fusg_tensor t[3][4];
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 4; ++k) {
+            out[r][k].assign(k == 0 ? 3 * n1 : n1, -1.f);
+            t[r][k] = desc(out[r][k].data(), FUSG_F32, V, k == 0 ? 3 : 1, R, R, (k == 0 ? 3L : 1L) * R * R, (long)R * R, R, 1);
+        }
+    const fusg_tensor tf = desc(frame.data(), FUSG_U8, 1, 3, H, W, (long)H * W * 3, 1, (long)W * 3, 3);
+    const fusg_tensor td = desc(det.data(), FUSG_U8, V, 1, H, W, (long)H * W, (long)H * W, W, 1);
+    if (fusg_inpaint_inputs_host(&tf, &td, boxes, w.data(), radius, mh, mw, &t[0][0], &t[0][1], &t[0][2], &t[0][3], scratch)) return 1;
+    if (fusg_inpaint_inputs_boxed_host(&tf, packed.data(), FUSG_U8, (int64_t)packed.size(), offs, boxes, w.data(), radius, mh, mw,
+                                       &t[1][0], &t[1][1], &t[1][2], &t[1][3], scratch)) return 1;
+    for (int k = 0; k < 4; ++k)
+        if (out[0][k] != out[1][k]) { std::printf("boxed u8 differs from the frame form in output %d\n", k); return 5; }
+    // float32 masks against their uint8 binarisation
+    if (fusg_inpaint_inputs_boxed_host(&tf, packed_b.data(), FUSG_U8, (int64_t)packed_b.size(), offs, boxes, w.data(), radius, mh, mw,
+                                       &t[1][0], &t[1][1], &t[1][2], &t[1][3], scratch)) return 1;
+    if (fusg_inpaint_inputs_boxed_host(&tf, packed_f.data(), FUSG_F32, (int64_t)packed_f.size(), offs, boxes, w.data(), radius, mh, mw,
+                                       &t[2][0], &t[2][1], &t[2][2], &t[2][3], scratch)) return 1;
+    for (int k = 0; k < 4; ++k)
+        if (out[1][k] != out[2][k]) { std::printf("boxed f32 differs from its binarisation in output %d\n", k); return 6; }
+    double s[2] = {0, 0};
+    for (float v : out[0][2]) s[0] += v;
+    for (float v : out[0][3]) s[1] += v;
+    std::printf("edge px %.0f hole px %.0f\n", s[0], s[1]);
+    // refused before anything is read: one element short, a negative offset, an offset past the end
+    std::vector<unsigned char> shorter(packed.begin(), packed.end() - 1);
+    int64_t bad[V] = {offs[0], offs[1], offs[2]};
+    if (fusg_inpaint_inputs_boxed_host(&tf, shorter.data(), FUSG_U8, (int64_t)shorter.size(), offs, boxes, w.data(), radius, mh, mw,
+                                       &t[1][0], &t[1][1], &t[1][2], &t[1][3], scratch) != FUSG_ERR_INVALID) return 3;
+    bad[1] = -1;
+    if (fusg_inpaint_inputs_boxed_host(&tf, packed.data(), FUSG_U8, (int64_t)packed.size(), bad, boxes, w.data(), radius, mh, mw,
+                                       &t[1][0], &t[1][1], &t[1][2], &t[1][3], scratch) != FUSG_ERR_INVALID) return 3;
+    bad[1] = offs[1];
+    bad[2] = (int64_t)packed.size() + 1;
+    if (fusg_inpaint_inputs_boxed_host(&tf, packed.data(), FUSG_U8, (int64_t)packed.size(), bad, boxes, w.data(), radius, mh, mw,
+                                       &t[1][0], &t[1][1], &t[1][2], &t[1][3], scratch) != FUSG_ERR_INVALID) return 3;
+    std::free(scratch);
+    return s[0] > 0 && s[1] > 0 ? 0 : 4;
+}
