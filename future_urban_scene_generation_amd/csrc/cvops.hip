@@ -30,8 +30,10 @@ static inline unsigned blocks2d(long total) { return (unsigned)((total + 255) / 
 // (sum + 2^14) >> 15, constant border 0.
 // index (optional, device int32 [jobs][2]): job n reads image index[2n] of src and writes image index[2n + 1] of dst; a
 // job whose source is negative writes nothing (the empty rows of fusg_plane_homographies' fixed-size table).
+// src_mod > 0 (fusg_warp_perspective_frames_u8): the source image is index[2n] % src_mod - F frames' rows of a table fitted
+// for F * V vehicles all read ONE set of V * P source planes.
 __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, const double* __restrict__ minv, U8View dst, long total,
-                                                                  const int* __restrict__ index) {
+                                                                  const int* __restrict__ index, int src_mod) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int x = (int)(idx % dst.w);
@@ -53,7 +55,8 @@ __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, co
     const int ax = (int)(X & 31), ay = (int)(Y & 31);
     int w00 = (32 - ax) * (32 - ay) * 32, w01 = ax * (32 - ay) * 32, w10 = (32 - ax) * ay * 32, w11 = ax * ay * 32;
     if ((ax | ay) == 0) { w00 = 32767; w11 = 1; }
-    const unsigned char* s = src.p + (long)(index ? index[2 * n] : n) * src.sn;
+    const int si = index ? index[2 * n] : n;
+    const unsigned char* s = src.p + (long)(src_mod > 0 ? si % src_mod : si) * src.sn;
     const bool y0ok = sy >= 0 && sy < src.h, y1ok = sy + 1 >= 0 && sy + 1 < src.h;
     const bool x0ok = sx >= 0 && sx < src.w, x1ok = sx + 1 >= 0 && sx + 1 < src.w;
     const unsigned char* p00 = s + sy * src.sh + sx * src.sw;
@@ -349,12 +352,10 @@ __device__ __forceinline__ void paste_resized_px(const unsigned char* img, const
         d[c] = (unsigned char)(o < 0 ? 0 : (o > 255 ? 255 : o));
     }
 }
-__global__ __launch_bounds__(256) void paste_back_kernel(PasteIn a, long total) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
-    unsigned char* d = a.frame.p + (long)y * a.frame.sh + (long)x * a.frame.sw;
-    for (int v = a.V - 1; v >= 0; --v) {
+// The layers of one frame at pixel (x, y): vehicles v0 .. v0 + a.V - 1 of the stacked inputs, last covering layer first.
+// Writes d and returns true when a layer covers the pixel; d is left alone otherwise.
+__device__ __forceinline__ bool paste_layers_px(const PasteIn& a, int v0, int x, int y, unsigned char* d) {
+    for (int v = v0 + a.V - 1; v >= v0; --v) {
         if (a.masks.p[(long)v * a.masks.sn + (long)y * a.masks.sh + (long)x * a.masks.sw]) {
             const int* g = a.geom + v * 8;
             const int cw = g[2] - g[0], ch = g[3] - g[1];
@@ -362,18 +363,38 @@ __global__ __launch_bounds__(256) void paste_back_kernel(PasteIn a, long total) 
             const int cx = x - g[0] + g[4], cy = y - g[1] + g[5];
             const int xa = g[6], ya = g[7];
             const bool inside = cx >= g[4] && cy >= g[5] && cx < cw - xa && cy < ch - ya;
-            if (!inside) { d[0] = 0; d[1] = 0; d[2] = 0; return; }
+            if (!inside) { d[0] = 0; d[1] = 0; d[2] = 0; return true; }
             paste_resized_px(a.net.p + (long)v * a.net.sn, a.net, cx, cy, cw, ch, d);
-            return;
+            return true;
         }
         if (a.rgeom) {
             const int* r = a.rgeom + v * 8;
             if (x >= r[0] && x < r[2] && y >= r[1] && y < r[3]) {
                 paste_resized_px(a.rect.p + (long)v * a.rect.sn, a.rect, x - r[0], y - r[1], r[2] - r[0], r[3] - r[1], d);
-                return;
+                return true;
             }
         }
     }
+    return false;
+}
+__global__ __launch_bounds__(256) void paste_back_kernel(PasteIn a, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
+    paste_layers_px(a, 0, x, y, a.frame.p + (long)y * a.frame.sh + (long)x * a.frame.sw);
+}
+// F frames in one launch (fusg_paste_layers_frames_u8): blockIdx.y = frame f, whose layers are rows f * V .. f * V + V - 1 of
+// the stacked crops, masks and rows; a.frame = the F composites, every pixel of which is written - the layer that covers it,
+// or the pixel of the frame's own base image bases[f] (dense [H, W, 3]).
+__global__ __launch_bounds__(256) void paste_frames_kernel(PasteIn a, const unsigned char* const* __restrict__ bases, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int f = blockIdx.y;
+    const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
+    unsigned char* d = a.frame.p + (long)f * a.frame.sn + (long)y * a.frame.sh + (long)x * a.frame.sw;
+    if (paste_layers_px(a, f * a.V, x, y, d)) return;
+    const unsigned char* b = bases[f] + idx * 3;
+    d[0] = b[0]; d[1] = b[1]; d[2] = b[2];
 }
 
 
@@ -563,23 +584,31 @@ __global__ __launch_bounds__(256) void keypoints_to_frame_kernel(const int* idx,
 
 using namespace fusg;
 
-static int warp_perspective_u8_impl(const fusg_tensor* src, const double* minv, const fusg_tensor* dst, const int32_t* index, int32_t jobs, void* stream) {
+static int warp_perspective_u8_impl(const fusg_tensor* src, const double* minv, const fusg_tensor* dst, const int32_t* index, int32_t jobs,
+                                    int32_t src_mod, void* stream) {
     FUSG_CHECK(src && dst && minv && is_u8_hwc(*src, 3) && is_u8_hwc(*dst, 3) && (index ? jobs >= 0 : src->n == dst->n),
                "warp_perspective_u8: u8 HWC tensors of 3 channels, same n (or an index of (source, destination) images per job)");
     FUSG_CHECK(src->data != dst->data, "warp_perspective_u8: in-place not supported");
     const long total = (index ? (long)jobs : dst->n) * dst->h * dst->w;
     if (total == 0) return FUSG_OK;
-    hipLaunchKernelGGL(warp_perspective_u8_kernel, dim3(blocks2d(total)), dim3(256), 0, (hipStream_t)stream, u8view(*src), minv, u8view(*dst), total, index);
+    hipLaunchKernelGGL(warp_perspective_u8_kernel, dim3(blocks2d(total)), dim3(256), 0, (hipStream_t)stream, u8view(*src), minv, u8view(*dst), total, index, src_mod);
     FUSG_LAUNCH_CHECK("warp_perspective_u8");
     return FUSG_OK;
 }
 extern "C" int fusg_warp_perspective_u8(const fusg_tensor* src, const double* minv, const fusg_tensor* dst, void* stream) {
-    return fusg::plan_dispatch(warp_perspective_u8_impl, stream, src, minv, dst, (const int32_t*)nullptr, (int32_t)0);
+    return fusg::plan_dispatch(warp_perspective_u8_impl, stream, src, minv, dst, (const int32_t*)nullptr, (int32_t)0, (int32_t)0);
 }
 extern "C" int fusg_warp_perspective_indexed_u8(const fusg_tensor* src, const double* minv, const int32_t* index, int32_t jobs,
                                                 const fusg_tensor* dst, void* stream) {
     FUSG_CHECK(index != nullptr, "warp_perspective_indexed_u8: index is null");
-    return fusg::plan_dispatch(warp_perspective_u8_impl, stream, src, minv, dst, index, jobs);
+    return fusg::plan_dispatch(warp_perspective_u8_impl, stream, src, minv, dst, index, jobs, (int32_t)0);
+}
+extern "C" int fusg_warp_perspective_frames_u8(const fusg_tensor* src, const double* minv, const int32_t* index, int32_t jobs,
+                                               int32_t frames, const fusg_tensor* dst, void* stream) {
+    FUSG_CHECK(index != nullptr && minv != nullptr, "warp_perspective_frames_u8: a table is null");
+    FUSG_CHECK(src && dst && frames >= 1 && jobs >= 0 && src->n >= 1 && src->n <= 0x7fffffff / frames && dst->n == src->n * frames &&
+               jobs <= dst->n, "warp_perspective_frames_u8: frames >= 1, dst holds frames * src->n images, at most one job per image");
+    return fusg::plan_dispatch(warp_perspective_u8_impl, stream, src, minv, dst, index, jobs, (int32_t)src->n);
 }
 
 extern "C" int fusg_fill_poly_planes_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t nplanes,
@@ -671,6 +700,32 @@ extern "C" int fusg_paste_back_u8(const fusg_tensor* net, const fusg_tensor* mas
 extern "C" int fusg_paste_layers_u8(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
                                     const int32_t* rect_geom, const fusg_tensor* frame, void* stream) {
     return fusg::plan_dispatch(paste_layers_u8_impl, stream, net, masks, geom, rect, rect_geom, frame);
+}
+
+static int paste_layers_frames_u8_impl(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
+                                       const int32_t* rect_geom, const void* const* bases, int32_t frames, const fusg_tensor* dst, void* stream) {
+    FUSG_CHECK(frames >= 1 && frames <= 65535, "paste_layers_frames_u8: %d frames (1..65535)", frames);
+    FUSG_CHECK(geom && bases, "paste_layers_frames_u8: a table is null (geom, bases)");
+    FUSG_CHECK(net && masks && dst && is_u8_hwc(*net, 3) && is_u8_hwc(*dst, 3) && dst->n == frames && masks->data &&
+               masks->dtype == FUSG_U8 && masks->c == 1 && masks->h == dst->h && masks->w == dst->w, "paste_layers_frames_u8: shapes");
+    FUSG_CHECK(net->n % frames == 0 && masks->n == net->n, "paste_layers_frames_u8: %ld crops and %ld masks for %d frames (frames * V rows each)",
+               (long)net->n, (long)masks->n, frames);
+    FUSG_CHECK((rect == nullptr) == (rect_geom == nullptr) && (!rect || (is_u8_hwc(*rect, 3) && rect->n == net->n)),
+               "paste_layers_frames_u8: the box images come with their rectangles, one per crop");
+    PasteIn a;
+    memset(&a, 0, sizeof(a));
+    a.net = u8view(*net); a.masks = u8view(*masks); a.frame = u8view(*dst); a.geom = geom; a.V = (int)(net->n / frames);
+    if (rect) { a.rect = u8view(*rect); a.rgeom = rect_geom; }
+    const long total = dst->h * dst->w;
+    hipLaunchKernelGGL(paste_frames_kernel, dim3(blocks2d(total), (unsigned)frames), dim3(256), 0, (hipStream_t)stream, a,
+                       (const unsigned char* const*)bases, total);
+    FUSG_LAUNCH_CHECK("paste_layers_frames_u8");
+    return FUSG_OK;
+}
+extern "C" int fusg_paste_layers_frames_u8(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
+                                           const int32_t* rect_geom, const void* const* bases, int32_t frames, const fusg_tensor* dst,
+                                           void* stream) {
+    return fusg::plan_dispatch(paste_layers_frames_u8_impl, stream, net, masks, geom, rect, rect_geom, bases, frames, dst);
 }
 
 struct Norm3 { float m[3], s[3]; int has; };      // mode 1's mean / std, captured by value (host arrays at the ABI)

@@ -159,6 +159,51 @@ def _box_masks_of(box_masks, keep):
     return (buf, np.asarray(offs, dtype=np.int64)[np.asarray(idx, dtype=np.int64)])
 
 
+# ---- `run_later_frames_batched`: the frame-major bookkeeping of a pass over F frames of V vehicles (pure Python)
+LATER_MAX_BATCH = 64     # rows per batched later pass: the largest batch the frame drivers run anyway (a frame of 64 vehicles)
+
+
+def later_batch_row(f: int, v: int, V: int) -> int:
+    """The row of (frame f, vehicle v) in a batched later pass: frame-major."""
+    return f * V + v
+
+
+def later_batch_slice(f: int, V: int) -> slice:
+    """Frame f's V rows of a frame-major batch."""
+    return slice(f * V, (f + 1) * V)
+
+
+def later_batch_groups(F: int, V: int, max_batch: Optional[int] = None) -> List[Tuple[int, int]]:
+    """The passes of F later frames of V vehicles: consecutive groups [lo, hi) of max(1, max_batch // V) frames, so that a
+    pass holds at most max_batch rows - or one frame, where a single frame already has more (max_batch < V).  max_batch None:
+    LATER_MAX_BATCH.  V = 0: one group (there is nothing to bound)."""
+    if max_batch is None:
+        max_batch = LATER_MAX_BATCH
+    if int(max_batch) < 1:
+        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
+    if F <= 0:
+        return []
+    per = F if V == 0 else max(1, int(max_batch) // V)
+    return [(lo, min(F, lo + per)) for lo in range(0, F, per)]
+
+
+def later_batch_seeds(seeds_per_frame: Sequence[Optional[Sequence[int]]], V: int) -> Optional[List[int]]:
+    """The scenes' 'vehicle_seeds' (one list of V per frame, or None) concatenated in row order; None when no scene carries
+    seeds; ValueError when only some do, or a list is not V long."""
+    have = [s is not None for s in seeds_per_frame]
+    if not any(have):
+        return None
+    if not all(have):
+        raise ValueError("run_later_frames_batched: either every scene of the batch carries 'vehicle_seeds' or none does "
+                         f"(frames without: {[f for f, h in enumerate(have) if not h]})")
+    out: List[int] = []
+    for f, sd in enumerate(seeds_per_frame):
+        if len(sd) != V:
+            raise ValueError(f"run_later_frames_batched: frame {f} carries {len(sd)} vehicle_seeds for {V} vehicles")
+        out.extend(int(x) for x in sd)
+    return out
+
+
 def _tensors(o):
     """Every tensor inside a nested dict / list / tuple, depth first."""
     if torch.is_tensor(o):
@@ -1538,14 +1583,197 @@ class VehiclePipeline:
             return _redo_f32(lambda: self.run_later_frame(t["scene"], t["state"], check=None, replay=False), t["rng"], restore=True)
         return t["out"] if front is None else self._geometry_later_assemble(front, t["out"])
 
-    def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False):
+    # ---- the future frames of a clip as ONE pass: the networks at B = F * V
+    def run_later_frames_batched(self, scenes, state: Dict, replay: bool = False, check: Optional[str] = "sync",
+                                 max_batch: Optional[int] = None) -> list:
+        """`run_later_frame` for the F future frames of a clip at once: five of a clip's six frames are later frames of the SAME
+        vehicles, and frame by frame each is a pass of ~300 dependent launches at batch V.  Here everything between the uint8
+        frames and the composited uint8 frames is issued once for all F * V (frame, vehicle) pairs - one plane warp
+        (fusg_warp_perspective_frames_u8, from ONE copy of the first frame's planes), one mask_bbox_geom, icn_inputs and
+        vunet_inputs, `_later_nets` once at B = F * V, one lab2bgr and one ordered paste per composite for all F frames
+        (fusg_paste_layers_frames_u8).  Rows are frame-major: row f * V + v is frame f, vehicle v; the first frame's central
+        crops and appearance codes are repeated per frame, per-frame 'vehicle_seeds' concatenated in row order.
+
+        scenes: a sequence of F later scenes as `run_later_frame` takes them (same vehicles and order as `state`; each its own
+        'frame', 'masks', 'dst_*', optional 'background', 'vehicle_seeds', 'inpaint'); every scene's 'src_planes' is the first
+        frame's tensor (one tensor, shared).  Either all scenes carry 'vehicle_seeds' or none (ValueError otherwise; without
+        seeds the noise of the pass is drawn in row order, which is not the order of F separate frames).  With a pipeline built
+        with inpaint=True either all scenes carry 'inpaint' (any of the three forms, per scene) or none (ValueError): each
+        frame's EdgeConnect inputs are built from that frame's own image on the inpaint stream into its V rows of the batched
+        buffers, then EdgeModel -> InpaintingModel -> merge runs once at F * V.
+        replay=True: the two (three) networks are ONE recorded plan per (F, V, precision[, inpaint]), kept with the frame
+        drivers' other plans under ("later_batch", F, V, ...) - apart from the ("later", V, ...) plans of `run_later_frame`.
+        check: the range guard of `run` - one status word per pass; raised, the whole pass is redone in exact fp32 under the RNG
+        state it was issued with.
+        max_batch bounds the rows of a pass: the frames are split into consecutive groups of max(1, max_batch // V) frames, one
+        pass each (`later_batch_groups`).  Default LATER_MAX_BATCH = 64 rows, the largest batch the frame drivers run anyway (a
+        frame of 64 vehicles), so the networks' activations stay what that pass already needs; the warped planes take 5 * H * W
+        * 3 bytes per row - 13.8 MB at 720 x 1280, 885 MB for 64 rows (553 MB for a clip tail of 5 frames of 8 vehicles).
+        Returns a list of F dicts with `run_later_frame`'s keys and shapes, in scene order ('icn_u8', 'vunet_u8', 'geom',
+        'frame_icn', 'frame_vunet' (+ 'inpaint_u8')); a frame's tensors are views into the pass's stacked results.  V = 0: F
+        results of `run_later_frame`'s no-vehicle shape; F = 0: [].
+        Out of scope: a geometry-mode state (scenes without 'masks') and a sharded state (process group) go through
+        `run_later_frames`, frame by frame - the results of today."""
+        scenes = list(scenes)
+        F = len(scenes)
+        if F == 0:
+            return []
+        if (not _one_rank(self.group) and state.get("sharded")) or any(self._is_geometry(sc, state) for sc in scenes):
+            return list(self.run_later_frames(scenes, state, replay=replay))
+        V = int(state["central"].shape[0])
+        for f, sc in enumerate(scenes):
+            if int(sc["masks"].shape[0]) != V:
+                raise ValueError(f"run_later_frames_batched: the state holds {V} vehicles, scene {f} {int(sc['masks'].shape[0])}")
+        seeds = later_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], V)
+        inps = [self._later_inpaint(sc) for sc in scenes]
+        if any(i is not None for i in inps) and not all(i is not None for i in inps):
+            raise ValueError("run_later_frames_batched: either every scene of the batch carries 'inpaint' or none does "
+                             f"(frames without: {[f for f, i in enumerate(inps) if i is None]})")
+        for i in inps:
+            if i is not None:
+                inpaint_scene_form(i)                             # (ValueError for a malformed entry, before anything is issued)
+        if V == 0:
+            return [self._run_later_frame(sc, state) for sc in scenes]
+        if any(sc["src_planes"].data_ptr() != scenes[0]["src_planes"].data_ptr() or sc["src_planes"].shape != scenes[0]["src_planes"].shape
+               for sc in scenes):
+            raise ValueError("run_later_frames_batched: the scenes of a batch share the first frame's 'src_planes' (one tensor)")
+        out = []
+        for lo, hi in later_batch_groups(F, V, max_batch):
+            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
+            out.extend(self._guarded(self._run_later_batch, (scenes[lo:hi], state, replay), check, rng))
+        return out
+
+    def _run_later_batch(self, scenes, state, replay=False) -> list:
+        return self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay))
+
+    @torch.no_grad()
+    def _later_batch_stages(self, scenes, state, icn_out=None) -> Dict:
+        """The data movement of a batched later pass in front of the networks, frame-major over the F scenes: 'warped' uint8
+        [F * V, P, H, W, 3], 'masks' uint8 [F * V, H, W], 'geom' int32 [F * V, 8], 'icn_x' [F * V, 21, R, R] (icn_out: a recorded
+        pass's buffer, written in place), 'vu_y' [F * V, 3, R, R].  Nothing here depends on the batch size: every row holds the
+        bytes `_later_local` builds for its frame."""
+        import numpy as np
+
+        from . import frame_ops as fo
+        from .warp_learn import planes_utils as pu
+        F, R = len(scenes), 256
+        src_planes = scenes[0]["src_planes"]
+        kp = {k: [veh for sc in scenes for veh in sc[k]] for k in ("src_kp", "dst_kp")}
+        vis = {k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in scenes]) for k in ("src_vis", "dst_vis")}
+        with torch.cuda.device(self.device):
+            if self.device_homography:
+                minv, index = pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
+                warped = pu.warp_planes_frames_fitted(src_planes, minv, index, F)              # :376-381
+            else:
+                jobs = pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
+                warped = pu.warp_planes_frames_batch(src_planes, jobs, F)
+            cat = lambda k: scenes[0][k] if F == 1 else torch.cat([sc[k] for sc in scenes])    # noqa: E731
+            masks, sketch = cat("masks"), cat("dst_sketch")
+            _, geom = fo.mask_bbox_geom(masks)
+            icn_x = pu.icn_inputs_device(warped, sketch, state["central"].repeat(F, 1, 1, 1), geom, R, R, out=icn_out)   # :385-387
+            _, vu_y = fo.vunet_inputs(scenes[0]["frame"], masks, sketch, sketch, geom, R)      # :415-420 (y_tilde reads no frame)
+        return {"warped": warped, "masks": masks, "geom": geom, "icn_x": icn_x, "vu_y": vu_y}
+
+    def _inpaint_inputs_batch(self, scenes, V: int, tgt) -> Tuple[Dict, object]:
+        """EdgeConnect's four inputs of F frames, [F * V, c, R, R] each: frame f's V rows come from ITS image and boxes
+        (`ops.inpaint_inputs` / `inpaint_inputs_boxed`, or the scene's given tensors copied in), all on the inpaint branch's
+        stream, forked once; `tgt`: a recorded pass's input buffers, written in place.  Returns (the four tensors, join)."""
+        from . import ops
+        F, R = len(scenes), 256
+
+        def build():
+            bufs = {k: tgt["ec_" + k] for k in ops.INPAINT_KEYS} if tgt else \
+                {k: torch.empty((F * V, 3 if k == "img" else 1, R, R), dtype=torch.float32, device=self.device) for k in ops.INPAINT_KEYS}
+            for f, sc in enumerate(scenes):
+                inp, sl = sc["inpaint"], later_batch_slice(f, V)
+                rows = {k: bufs[k][sl] for k in ops.INPAINT_KEYS}
+                if "box_masks" in inp:
+                    ops.inpaint_inputs_boxed(sc["frame"], inp["box_masks"], inp["boxes"], out=rows)
+                elif "det_masks" in inp:
+                    ops.inpaint_inputs(sc["frame"], inp["det_masks"], inp["boxes"], out=rows)
+                else:                                             # given
+                    for k in ops.INPAINT_KEYS:
+                        rows[k].copy_(inp[k])
+            return bufs
+
+        if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
+            return build(), (lambda: None)
+        st = self._streams.get("inpaint")
+        if st is None:
+            st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
+        ops.fork_to(st)
+        with torch.cuda.stream(st):
+            res = build()
+        return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
+
+    @torch.no_grad()
+    def _later_batch_local(self, scenes, state, replay=False) -> Dict:
+        """The per-(frame, vehicle) part of a batched later pass: glue, the networks at B = F * V, Lab -> BGR.  Returns 'icn_u8'
+        (BGR), 'vunet_u8', 'geom', 'masks' (+ 'inpaint_u8'), F * V rows each, frame-major."""
+        from . import ops
+        from .warp_learn import planes_utils as pu
+        F, V = len(scenes), int(state["central"].shape[0])
+        inpaint = self._later_inpaint(scenes[0]) is not None
+        seeds = later_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], V)
+        with torch.cuda.device(self.device):
+            replay = replay and ops.RECORDER is None
+            pkey = ("later_batch", F, V, ops.PRECISION) + (("inpaint",) if inpaint else ())
+            cp = self._plan(pkey) if replay else None
+            tgt = cp.inputs if cp is not None else {}            # a recorded pass's big inputs are written in place
+            ec, ec_join = self._inpaint_inputs_batch(scenes, V, tgt) if inpaint else (None, None)
+            st = self._later_batch_stages(scenes, state, icn_out=tgt.get("icn_x"))
+            nets_in = {"icn_x": st["icn_x"], "vu_y": st["vu_y"],
+                       "app0": state["appearance"][0].repeat(F, 1, 1, 1), "app1": state["appearance"][1].repeat(F, 1, 1, 1)}
+            if ec is not None:
+                ec_join()
+                nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
+            if replay:
+                out = self._replay(pkey, nets_in, seeds, fn=self._later_nets)
+            else:
+                out = self._later_nets(nets_in, seeds)
+            out["icn_u8"] = pu.lab2bgr(out["icn_u8"])
+            out["geom"], out["masks"] = st["geom"], st["masks"]
+        return out
+
+    @torch.no_grad()
+    def _later_batch_finish(self, scenes, out) -> list:
+        """The frame-level part of a batched later pass: the ordered paste of all F frames, one launch per composite; then the
+        stacked results cut into `run_later_frame`'s dict per frame."""
+        import numpy as np
+
+        from . import ops
+        from .warp_learn import planes_utils as pu
+        F = len(scenes)
+        V = int(out["geom"].shape[0]) // F
+        inpaint = "inpaint_u8" in out
+        with torch.cuda.device(self.device):
+            # :340: with --inpaint the composite starts from the frame
+            bases = [sc["frame"] if inpaint else sc.get("background", sc["frame"]) for sc in scenes]
+            box = {}
+            if inpaint:                                           # :340-350: every vehicle's inpainted box under its crop, in vehicle order
+                rows = np.zeros((F * V, 8), np.int32)
+                for f, sc in enumerate(scenes):
+                    rows[later_batch_slice(f, V), :4] = np.asarray(sc["inpaint"]["boxes"]).reshape(V, 4)
+                box = dict(box_images=out["inpaint_u8"], box_geom=ops.h2d(rows, self.device, torch.int32))
+            frames = {k: pu.paste_back_frames_device(bases, out[c], out["geom"], out["masks"], **box)       # :393-410, :428-445
+                      for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+        keys = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
+        return [{**{k: out[k][later_batch_slice(f, V)] for k in keys}, "frame_icn": frames["frame_icn"][f],
+                 "frame_vunet": frames["frame_vunet"][f]} for f in range(F)]
+
+    def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False, batched: bool = False):
         """A vehicle clip the reference's way (trajectory_inference.py:55-250 then :267-450): the first frame through
         `run_frame`, every future frame through `run_later_frame` with the first frame's state.  Generator of 1 + len(later_scenes)
         results.  Under a process group the whole clip is sharded by vehicle: a vehicle's six frames stay on one rank (frame by
-        frame).  A geometry-mode clip (cad_bank, scenes without 'masks') goes through the same drivers."""
+        frame).  A geometry-mode clip (cad_bank, scenes without 'masks') goes through the same drivers.
+        batched=True renders the future frames as batched passes (`run_later_frames_batched`) instead of one frame in flight:
+        the same sequence of results, each frame's within that method's bars of the frame-by-frame form."""
         first = self.run_frame(first_scene, replay=replay)
         state = first["state"]
         yield first if len(first) > 1 else None
+        if batched:
+            yield from self.run_later_frames_batched(list(later_scenes), state, replay=replay)
+            return
         yield from self.run_later_frames(later_scenes, state, replay=replay)       # one later frame in flight
 
     def run_clip(self, clip: Dict[str, torch.Tensor], vehicle_seeds: Optional[Sequence[int]] = None,

@@ -515,6 +515,55 @@ def warp_planes_fitted(src_planes: torch.Tensor, minv: torch.Tensor, index: torc
     return warped.view(V, P, H, W, 3)
 
 
+def _warp_frames(flat: torch.Tensor, minv: torch.Tensor, index: torch.Tensor, jobs: int, frames: int) -> torch.Tensor:
+    """fusg_warp_perspective_frames_u8: `jobs` rows of (minv, index) warp the S shared images of `flat` into frames * S zeroed ones."""
+    S, H, W, _ = flat.shape
+    warped = torch.zeros((frames * S, H, W, 3), dtype=torch.uint8, device=flat.device)
+    if jobs:
+        with torch.cuda.device(flat.device):
+            L.check(L.lib().fusg_warp_perspective_frames_u8(C.byref(_u8desc(flat)), minv.data_ptr(), index.data_ptr(), int(jobs), int(frames),
+                                                            C.byref(_u8desc(warped)), ops.stream_ptr()), "warp_perspective_frames_u8")
+    return warped
+
+
+def warp_planes_frames_batch(src_planes: torch.Tensor, jobs_per_row, frames: int) -> torch.Tensor:
+    """`warp_planes_batch` for the F future frames of a clip in ONE launch, from ONE copy of the first frame's planes:
+    src_planes CUDA uint8 [V, P, H, W, 3], jobs_per_row[f * V + v] = warp_jobs(...) of vehicle v in frame f (frame-major, F * V
+    entries) -> [F * V, P, H, W, 3], zeros where nothing is warped."""
+    V, P, H, W, _ = src_planes.shape
+    if frames < 1 or len(jobs_per_row) != frames * V:
+        raise ValueError(f"warp_planes_frames_batch: {len(jobs_per_row)} job lists for {frames} frames of {V} vehicles")
+    flat = src_planes.reshape(V * P, H, W, 3).contiguous()
+    src_idx, dst_idx, Hs = [], [], []
+    for r, jobs in enumerate(jobs_per_row):
+        last = {}
+        for i, j, H12, _ in jobs:                                 # plane order: a later job on slot j overwrites an earlier one
+            last[j] = (i, H12)
+        for j, (i, H12) in last.items():
+            src_idx.append((r % V) * P + i)
+            dst_idx.append(r * P + j)
+            Hs.append(H12)
+    minv_d = index = None
+    if Hs:
+        minv = np.linalg.inv(np.asarray(Hs, dtype=np.float64).reshape(len(Hs), 3, 3)).reshape(len(Hs), 9)
+        minv_d = ops.h2d(minv, flat.device)
+        index = ops.h2d(np.stack([src_idx, dst_idx], 1).astype(np.int32), flat.device)
+    return _warp_frames(flat, minv_d, index, len(Hs), frames).view(frames * V, P, H, W, 3)
+
+
+def warp_planes_frames_fitted(src_planes: torch.Tensor, minv: torch.Tensor, index: torch.Tensor, frames: int) -> torch.Tensor:
+    """`warp_planes_fitted` for F frames from ONE copy of the first frame's planes: minv / index are the tables
+    `plane_homographies_device` fits for the F * V (frame, vehicle) rows (the source corner points repeated per frame), whose
+    source entries (row * P + i) the kernel folds back onto the V * P shared planes.  -> [F * V, P, H, W, 3]."""
+    V, P, H, W, _ = src_planes.shape
+    n = frames * V * P
+    if frames < 1 or minv.dtype != torch.float64 or index.dtype != torch.int32 or tuple(minv.shape) != (n, 9) or \
+            tuple(index.shape) != (n, 2) or not (minv.is_contiguous() and index.is_contiguous()):
+        raise ValueError("warp_planes_frames_fitted: minv float64 [F * V * P, 9] and index int32 [F * V * P, 2], contiguous")
+    flat = src_planes.reshape(V * P, H, W, 3).contiguous()
+    return _warp_frames(flat, minv, index, n if V else 0, frames).view(frames * V, P, H, W, 3)
+
+
 def warp_unwarp_planes(src_planes: Image, src_planes_kpoints: List[np.ndarray], dst_planes_kpoints: List[np.ndarray],
                        src_visibilities, dst_visibilities, pascal_class: str, pascal_texture_planes=pascal_texture_planes,
                        unwarp: bool = True):
@@ -652,6 +701,36 @@ def paste_back_device(frame: torch.Tensor, net_images: torch.Tensor, geom: torch
                                                  geom.data_ptr(), C.byref(_u8desc(box_images.contiguous())), box_geom.contiguous().data_ptr(),
                                                  C.byref(_u8desc(fr[None])), ops.stream_ptr()), "paste_layers_u8")
     return fr
+
+
+def paste_back_frames_device(bases: Sequence[torch.Tensor], net_images: torch.Tensor, geom: torch.Tensor, masks: torch.Tensor,
+                             box_images: Optional[torch.Tensor] = None, box_geom: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`paste_back_device` for F frames in ONE launch (fusg_paste_layers_frames_u8): bases = F CUDA uint8 [H, W, 3] images, the
+    one frame f's composite starts from (read, not copied first: the kernel writes every pixel of the result); net_images
+    [F * V, h, w, 3], geom int32 [F * V, 8], masks uint8 [F * V, H, W] (and box_images / box_geom) frame-major, row f * V + v =
+    frame f, vehicle v.  -> uint8 [F, H, W, 3]."""
+    F = len(bases)
+    if F < 1:
+        raise ValueError("paste_back_frames_device: at least one frame")
+    N, H, W = masks.shape
+    dev = masks.device
+    keep = [b.contiguous() for b in bases]                        # referenced until the launch is queued
+    if any(tuple(b.shape) != (H, W, 3) or b.dtype != torch.uint8 or b.device != dev for b in keep):
+        raise ValueError(f"paste_back_frames_device: every base image is uint8 {(H, W, 3)} on {dev}")
+    if N % F or net_images.shape[0] != N or geom.dtype != torch.int32 or tuple(geom.shape) != (N, 8):
+        raise ValueError(f"paste_back_frames_device: {N} masks, {net_images.shape[0]} crops, geom {tuple(geom.shape)} for {F} frames")
+    if (box_images is None) != (box_geom is None) or (box_images is not None and (
+            box_images.shape[0] != N or box_geom.dtype != torch.int32 or tuple(box_geom.shape) != (N, 8))):
+        raise ValueError("paste_back_frames_device: box_images [F * V, h, w, 3] come with box_geom int32 [F * V, 8]")
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    table = ops.h2d(np.asarray([b.data_ptr() for b in keep], dtype=np.int64), dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().fusg_paste_layers_frames_u8(
+            C.byref(_u8desc(net_images.contiguous())), C.byref(ops.desc(masks.contiguous().view(N, 1, H, W))), geom.contiguous().data_ptr(),
+            C.byref(_u8desc(box_images.contiguous())) if box_images is not None else None,
+            box_geom.contiguous().data_ptr() if box_geom is not None else None, table.data_ptr(), F, C.byref(_u8desc(out)),
+            ops.stream_ptr()), "paste_layers_frames_u8")
+    return out
 
 
 def paste_back(frame: Image, net_images: torch.Tensor, crop_infos: Sequence[dict], paste_masks: Image) -> Image:

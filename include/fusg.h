@@ -373,6 +373,13 @@ int fusg_warp_perspective_u8(const fusg_tensor* src, const double* minv, const f
  * planes_utils.py:57 starts from zeros). */
 int fusg_warp_perspective_indexed_u8(const fusg_tensor* src, const double* minv, const int32_t* index, int32_t jobs,
                                      const fusg_tensor* dst, void* stream);
+/* The same for the F future frames of a clip that share ONE set of source planes (VehiclePipeline.run_later_frames_batched):
+ * src holds the S = src->n planes of the first frame, dst frames * S images; job k reads image index[2k] % S of src and
+ * writes image index[2k + 1] of dst, so a table fitted for frames * V vehicles (fusg_plane_homographies: row = (f * V + v) * P
+ * + j, source row * P + i) addresses the shared planes as it stands and no copy of them per frame is made.  frames >= 1,
+ * jobs <= frames * S, index and minv not NULL (checked on the host before the launch). */
+int fusg_warp_perspective_frames_u8(const fusg_tensor* src, const double* minv, const int32_t* index, int32_t jobs,
+                                    int32_t frames, const fusg_tensor* dst, void* stream);
 /* get_planes (warp_learn/planes_utils.py:11-37): dst[p] = frame * fillPoly(polygon p) for up to 8 polygons of up
  * to 8 int32 vertices.  pts_xy [nplanes][8][2] (x, y) and nverts [nplanes] are HOST arrays (read before return). */
 int fusg_fill_poly_planes_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t nplanes,
@@ -405,6 +412,15 @@ int fusg_paste_back_u8(const fusg_tensor* net, const fusg_tensor* masks, const i
  * (DEVICE int32 [V][8]) both NULL = fusg_paste_back_u8. */
 int fusg_paste_layers_u8(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
                          const int32_t* rect_geom, const fusg_tensor* frame, void* stream);
+/* fusg_paste_layers_u8 for F frames of V vehicles each in ONE launch: net, masks, geom (and rect, rect_geom, both NULL for
+ * the plain paste) hold frames * V rows, frame-major (row f * V + v = frame f, vehicle v); within a frame the rule is
+ * unchanged - vehicle by vehicle, the box first, then the masked crop, the last layer covering a pixel wins.  bases = DEVICE
+ * table of `frames` pointers, bases[f] = the dense u8 [H, W, 3] image frame f's composite starts from (read only); dst u8
+ * [frames, H, W, 3] is written whole: the covering layer, or the base's pixel.  Checked on the host before the launch:
+ * frames >= 1, row counts that are frames * V, geom / bases not NULL, rect with rect_geom. */
+int fusg_paste_layers_frames_u8(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
+                                const int32_t* rect_geom, const void* const* bases, int32_t frames, const fusg_tensor* dst,
+                                void* stream);
 
 /* ---- frame-chain glue (pipeline.VehiclePipeline.run_frame): the uint8 -> float steps between the frame and the networks */
 /* square_crop_from_bbox (utils/crop_utils.py:4-52) + cv2.resize INTER_LINEAR for V windows: src u8 HWC [1] (every

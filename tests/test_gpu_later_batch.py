@@ -1,0 +1,491 @@
+"""GPU: a clip's future frames as ONE batched pass (VehiclePipeline.run_later_frames_batched, fusg_paste_layers_frames_u8,
+fusg_warp_perspective_frames_u8).  The data movement - warped planes, crop rows, both networks' inputs, EdgeConnect's inputs,
+the ordered paste - equals the per-frame path byte for byte; the rendered frames are compared with the vehicle-serial CPU
+oracle under the bars of tests/test_gpu_frame.py's later-frame test and tests/test_gpu_later_inpaint.py (not with the per-frame
+device path: a batch of 9 and a batch of 3 may route convolutions differently)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import later_inpaint_ref as lr                                             # noqa: E402
+import oracle                                                              # noqa: E402
+from conftest import record, synth_sd                                      # noqa: E402
+from future_urban_scene_generation_amd import frame_ops as fo              # noqa: E402
+from future_urban_scene_generation_amd import ops                          # noqa: E402
+from future_urban_scene_generation_amd import pipeline as pl               # noqa: E402
+from future_urban_scene_generation_amd.warp_learn import planes_utils as pu   # noqa: E402
+from oracle import cv_host as C                                            # noqa: E402
+
+DEV = "cuda:0"
+HW = (360, 640)
+KEYS = ("icn_u8", "vunet_u8", "geom", "frame_icn", "frame_vunet")
+
+
+def _d(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _host_threads():
+    return min(16, max(1, len(os.sched_getaffinity(0))))
+
+
+def _moved(first, f, seed=9):
+    """Future frame f of `first` the way test_run_later_frame_matches_the_oracle moves its vehicles: masks and sketch rolled by a
+    few pixels (more per frame), the plane corners moved with them plus a little jitter (related quadrilaterals: well-posed
+    fits), a frame of its own that differs visibly (the image rolled sideways) and one seed per (vehicle, frame)."""
+    g = np.random.default_rng(seed + f)
+    dy, dx = 5 + 3 * f, -7 - 2 * f
+    sc = {k: v for k, v in first.items() if k != "inpaint"}
+    sc["frame"] = torch.roll(first["frame"], shifts=37 * (f + 1), dims=1).contiguous()
+    sc["masks"] = torch.roll(first["masks"], shifts=(dy, dx), dims=(1, 2))
+    sc["dst_sketch"] = torch.roll(first["dst_sketch"], shifts=(dy, dx), dims=(1, 2))
+    sc["dst_kp"] = [[np.int32(p + np.array([dx, dy]) + g.integers(-2, 3, p.shape)) for p in veh] for veh in first["dst_kp"]]
+    sc["vehicle_seeds"] = [int(s) * 64 + f + 1 for s in first["vehicle_seeds"]]
+    return sc
+
+
+def _bars(got, ref, cpu, tag, base=None):
+    """The bars of test_run_later_frame_matches_the_oracle: crop rows and every frame pixel outside the masks exact, VUnet crops
+    within 1 LSB, ICN crop and both composited frames SSIM >= 0.999."""
+    assert np.array_equal(got["geom"].cpu().numpy(), ref["geom"]), tag
+    d = int(np.abs(got["vunet_u8"].cpu().numpy().astype(int) - ref["vunet_u8"].astype(int)).max())
+    print(f"{tag}: vunet_u8 max diff {d}")
+    record("later_batch_vunet_u8_max_diff", d)
+    assert d <= 1, (tag, d)
+    cover = cpu["masks"].max(0).astype(bool)
+    for k in ("icn_u8", "vunet_u8", "frame_icn", "frame_vunet"):
+        sv = oracle.ssim(got[k].cpu().numpy(), ref[k])
+        print(f"{tag}: {k} ssim {sv}")
+        record(f"later_batch_{k}_ssim", sv, worst=min)
+        assert sv >= 0.999, (tag, k, sv)
+    base = cpu["frame"] if base is None else base
+    for k in ("frame_icn", "frame_vunet"):
+        assert np.array_equal(got[k].cpu().numpy()[~cover], base[~cover]), (tag, k)
+
+
+@pytest.fixture(scope="module")
+def env():
+    """One pipeline, a first frame of 3 vehicles, its 3 future frames and (computed once, on 16 host threads) the oracle's
+    first-frame state and its result for every future frame."""
+    ops.set_precision("f16x3")
+    sds = {n: synth_sd(n) for n in ("hg", "icn", "vunet")}
+    pipe = pl.VehiclePipeline(DEV, state_dicts=sds)
+    # (seed 49: every plane of its three vehicles and of the three moved poses has a well-posed fit - the oracle's per-plane
+    # solver raises on the degenerate quadrilaterals some seeds draw - on which the vectorised and the per-plane fit agree)
+    first = pl.synth_frame(3, HW, DEV, seed=49)
+    first["vehicle_seeds"] = [11, 12, 13]
+    later = [_moved(first, f) for f in range(3)]
+    f0 = pipe.run_frame(first)
+    nt = torch.get_num_threads()
+    torch.set_num_threads(_host_threads())
+    try:
+        o0 = oracle.frame_pass(sds, lr.scene_cpu(first))
+        cpus = [lr.scene_cpu(sc) for sc in later]
+        refs = [oracle.later_frame_pass(sds, c, o0["state"]) for c in cpus]
+    finally:
+        torch.set_num_threads(nt)
+    assert not torch.equal(later[0]["frame"], later[1]["frame"]) and not np.array_equal(refs[0]["frame_icn"], refs[1]["frame_icn"])
+    return dict(sds=sds, pipe=pipe, first=first, later=later, f0=f0, o0=o0, cpus=cpus, refs=refs)
+
+
+# ------------------------------------------------------------------------------------------------ data movement
+def _per_frame_stages(pipe, scene, state):
+    """What `_later_local` builds for one frame in front of the networks, by its own calls."""
+    jobs = None if pipe.device_homography else pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
+    warped = pipe._warp_planes(scene, jobs)
+    _, geom = fo.mask_bbox_geom(scene["masks"])
+    icn_x = pu.icn_inputs_device(warped, scene["dst_sketch"], state["central"], geom, 256, 256)
+    _, vu_y = fo.vunet_inputs(scene["frame"], scene["masks"], scene["dst_sketch"], scene["dst_sketch"], geom, 256)
+    return {"warped": warped, "geom": geom, "icn_x": icn_x, "vu_y": vu_y}
+
+
+def _assert_stages(pipe, scenes, state, tag):
+    got = pipe._later_batch_stages(scenes, state)
+    want = [_per_frame_stages(pipe, sc, state) for sc in scenes]
+    assert got["warped"].any() and tuple(got["icn_x"].shape) == (len(scenes) * int(state["central"].shape[0]), 21, 256, 256)
+    for k in ("warped", "geom", "icn_x", "vu_y"):
+        ref = torch.cat([w[k] for w in want])
+        assert got[k].shape == ref.shape and got[k].dtype == ref.dtype, (tag, k)
+        assert torch.equal(got[k], ref), (tag, k)
+
+
+@pytest.mark.parametrize("F,V", [(2, 3), (3, 1), (1, 3)])
+def test_stages_equal_the_per_frame_path(env, F, V):
+    """Warped planes, crop rows, ICN input and VUnet shape input of the batch == the per-frame ones, concatenated frame-major:
+    F frames that differ in pose, image and masks, warped from ONE copy of the first frame's planes."""
+    pipe = env["pipe"]
+    assert pipe.device_homography is False
+    first = pl.synth_frame(V, HW, DEV, seed=50 + V)
+    first["vehicle_seeds"] = list(range(V))
+    state = pipe.run_frame(first)["state"]
+    scenes = []
+    for f in range(F):
+        sc = pl.synth_later_frame(first, f + 1)
+        sc["masks"] = torch.roll(first["masks"], shifts=(3 * f + 2, -4 * f - 1), dims=(1, 2))
+        sc["dst_sketch"] = torch.roll(first["dst_sketch"], shifts=(3 * f + 2, -4 * f - 1), dims=(1, 2))
+        sc["dst_vis"] = np.roll(first["dst_vis"], f, axis=0) if V > 1 else first["dst_vis"]       # other gates per frame
+        scenes.append(sc)
+    _assert_stages(pipe, scenes, state, (F, V))
+    if F > 1:
+        assert not torch.equal(*(pipe._later_batch_stages([sc], state)["warped"] for sc in scenes[:2]))
+
+
+def test_stages_with_device_homography_on_the_tie_free_scene(env):
+    """device_homography=True: the tables fitted for F * V rows feed the shared-source warp.  On the scene
+    tests/test_homography_cpu.py shows free of rounding ties (synth_frame seed 41, 2 vehicles, its first and its later pose) the
+    batch equals the per-frame path with the flag on AND with it off."""
+    pipe = env["pipe"]
+    first = pl.synth_frame(2, HW, DEV, seed=41)
+    first["vehicle_seeds"] = [11, 12]
+    g = np.random.default_rng(9)
+    later = dict(first)
+    later["masks"] = torch.roll(first["masks"], shifts=(5, -7), dims=(1, 2))
+    later["dst_sketch"] = torch.roll(first["dst_sketch"], shifts=(5, -7), dims=(1, 2))
+    later["dst_kp"] = [[np.int32(p + np.array([-7, 5]) + g.integers(-2, 3, p.shape)) for p in veh] for veh in first["dst_kp"]]
+    state = pipe.run_frame(first)["state"]
+    scenes = [later, first, later]
+    host = [_per_frame_stages(pipe, sc, state) for sc in scenes]
+    pipe.device_homography = True
+    try:
+        _assert_stages(pipe, scenes, state, "device_homography")
+        got = pipe._later_batch_stages(scenes, state)
+    finally:
+        pipe.device_homography = False
+    for k in ("warped", "geom", "icn_x", "vu_y"):
+        assert torch.equal(got[k], torch.cat([w[k] for w in host])), k
+
+
+# ------------------------------------------------------------------------------------------------ the batched paste kernel
+def _paste_case(F, V, H, W, R=32, seed=5, empty=None, clipped=None):
+    """F frames of V vehicles whose masks overlap in the middle of the frame (the vehicle order decides pixels there), a base
+    image per frame; `empty`: a (frame, vehicle) whose mask is empty; `clipped`: one whose crop window leaves the frame."""
+    g = np.random.default_rng(seed)
+    bases = g.integers(0, 256, (F, H, W, 3), dtype=np.uint8)
+    nets = g.integers(0, 256, (F * V, R, R, 3), dtype=np.uint8)
+    boxes_img = g.integers(0, 256, (F * V, R, R, 3), dtype=np.uint8)
+    masks = np.zeros((F * V, H, W), np.uint8)
+    geom, rects = np.zeros((F * V, 8), np.int32), np.zeros((F * V, 8), np.int32)
+    for f in range(F):
+        for v in range(V):
+            r = f * V + v
+            x0, y0 = W // 2 - 30 + 9 * v + int(g.integers(-3, 4)), H // 2 - 25 + 7 * v + 2 * f
+            bb = [x0, y0, x0 + int(g.integers(28, 45)), y0 + int(g.integers(22, 36))]
+            if (f, v) == clipped:
+                bb = [W - 30, -4, W + 6, 28]                                      # the square window pads on two sides
+            if (f, v) != empty:
+                masks[r, max(0, bb[1] - 3):bb[3] + 2, max(0, bb[0] - 2):min(W, bb[2] + 3)] = 1   # a little wider than the box
+            win, pb, pa = C.square_crop_geometry((H, W), bb)
+            geom[r] = [win[0], win[1], win[2], win[3], pb[0], pb[1], pa[0], pa[1]]
+            rects[r, :4] = [max(0, bb[0] - 9), max(0, bb[1] - 7), min(W - 1, bb[2] + 11), min(H - 1, bb[3] + 6)]
+    return dict(bases=bases, nets=nets, boxes_img=boxes_img, masks=masks, geom=geom, rects=rects, F=F, V=V)
+
+
+def _paste_both(c, boxes, order=None):
+    """(one launch for all frames, F calls of the existing paste); order: a permutation of the vehicles of every frame."""
+    F, V = c["F"], c["V"]
+    rows = np.arange(F * V) if order is None else np.concatenate([f * V + np.asarray(order) for f in range(F)])
+    t = {k: _d(c[k][rows]) for k in ("nets", "masks", "geom", "boxes_img", "rects")}
+    bases = [_d(c["bases"][f]) for f in range(F)]
+    box = dict(box_images=t["boxes_img"], box_geom=t["rects"]) if boxes else {}
+    got = pu.paste_back_frames_device(bases, t["nets"], t["geom"], t["masks"], **box)
+    want = []
+    for f in range(F):
+        sl = slice(f * V, (f + 1) * V)
+        bx = dict(box_images=t["boxes_img"][sl], box_geom=t["rects"][sl].contiguous()) if boxes else {}
+        want.append(pu.paste_back_device(bases[f], t["nets"][sl], t["geom"][sl].contiguous(), t["masks"][sl], **bx))
+    for f in range(F):                                                          # the bases are read, never written
+        assert np.array_equal(bases[f].cpu().numpy(), c["bases"][f])
+    return got, torch.stack(want)
+
+
+@pytest.mark.parametrize("boxes", [True, False], ids=["box_layers", "plain"])
+@pytest.mark.parametrize("F,V,H,W", [(3, 3, 120, 200), (2, 1, 90, 150), (1, 4, 77, 131)])
+def test_paste_frames_equals_the_per_frame_paste(F, V, H, W, boxes):
+    """fusg_paste_layers_frames_u8 == F calls of fusg_paste_layers_u8 / fusg_paste_back_u8, byte for byte: overlapping vehicles
+    whose order decides pixels, another base per frame, a vehicle with an empty mask, a crop clipped at the frame border, V = 1,
+    frame widths that are no multiple of 16 (200 = 12 * 16 + 8, 150, 131) and more than one block per frame."""
+    c = _paste_case(F, V, H, W, empty=(0, 1) if V > 1 else None, clipped=(F - 1, V - 1))
+    assert W % 16 and H * W > 256
+    assert c["geom"][(F - 1) * V + V - 1, 4:].any(), "the clipped crop pads"
+    if V > 1:
+        assert not c["masks"][1].any()
+    assert not np.array_equal(c["bases"][0], c["bases"][-1]) or F == 1
+    got, want = _paste_both(c, boxes)
+    assert tuple(got.shape) == (F, H, W, 3) and got.dtype == torch.uint8
+    assert torch.equal(got, want)
+    for f in range(F):                                                          # the layers really replaced pixels, the rest is the base
+        cover = c["masks"][f * V:(f + 1) * V].max(0).astype(bool)
+        if boxes:
+            for x0, y0, x1, y1 in c["rects"][f * V:(f + 1) * V, :4]:
+                cover[y0:y1, x0:x1] = True
+        a = got[f].cpu().numpy()
+        assert np.array_equal(a[~cover], c["bases"][f][~cover]) and not np.array_equal(a[cover], c["bases"][f][cover])
+
+
+@pytest.mark.parametrize("boxes", [True, False], ids=["box_layers", "plain"])
+def test_paste_frames_vehicle_order_decides_the_overlap(boxes):
+    c = _paste_case(3, 3, 120, 200)
+    for f in range(3):
+        m = c["masks"][f * 3:(f + 1) * 3].astype(bool)
+        assert (m[0] & m[1]).any() and (m[1] & m[2]).any(), "the overlap is not empty"
+    got, want = _paste_both(c, boxes)
+    rev, rev_want = _paste_both(c, boxes, order=[2, 1, 0])
+    assert torch.equal(got, want) and torch.equal(rev, rev_want)
+    for f in range(3):
+        assert not torch.equal(got[f], rev[f]), f                              # the same layers in another order: other pixels
+
+
+# ------------------------------------------------------------------------------------------------ end to end
+def test_batched_frames_match_the_oracle(env):
+    """F = 3, V = 3: every frame of the batch against oracle.frame_pass + oracle.later_frame_pass."""
+    pipe = env["pipe"]
+    got = pipe.run_later_frames_batched(env["later"], env["f0"]["state"])
+    assert isinstance(got, list) and len(got) == 3
+    for f, (g, ref, cpu) in enumerate(zip(got, env["refs"], env["cpus"])):
+        assert set(g) == set(KEYS)
+        assert tuple(g["icn_u8"].shape) == (3, 256, 256, 3) and tuple(g["frame_icn"].shape) == HW + (3,) and tuple(g["geom"].shape) == (3, 8)
+        _bars(g, ref, cpu, f"frame {f}")
+    assert not any(k[0] == "later_batch" for k in pipe._frame_plans)             # the eager form records nothing
+
+
+def test_background_is_the_base_of_its_own_frame(env):
+    """A 'background' on ONE scene of the batch: that frame's composite starts from it, the others from their frames."""
+    pipe = env["pipe"]
+    bg = torch.full_like(env["later"][1]["frame"], 77)
+    scenes = [env["later"][0], dict(env["later"][1], background=bg), env["later"][2]]
+    got = pipe.run_later_frames_batched(scenes, env["f0"]["state"])
+    _bars(got[0], env["refs"][0], env["cpus"][0], "frame 0 beside a background")
+    cover = env["cpus"][1]["masks"].max(0).astype(bool)
+    for k in ("frame_icn", "frame_vunet"):
+        a = got[1][k].cpu().numpy()
+        assert (a[~cover] == 77).all() and np.array_equal(a[cover], pipe.run_later_frames_batched(env["later"], env["f0"]["state"])[1][k].cpu().numpy()[cover]), k
+
+
+def test_replay_equals_eager_and_keeps_its_own_plan(env):
+    pipe, st = env["pipe"], env["f0"]["state"]
+    a = env["later"]
+    b = [env["later"][2], env["later"][0], env["later"][1]]                       # other scenes of the same (F, V)
+    pipe.run_later_frame(a[0], st, replay=True)                                   # the per-frame plan of 3 vehicles exists
+    before = {k: id(v) for k, v in pipe._frame_plans.items()}
+    key = ("later_batch", 3, 3, ops.PRECISION)
+    assert ("later", 3, ops.PRECISION) in before and key not in before
+    eager_a, eager_b = pipe.run_later_frames_batched(a, st), pipe.run_later_frames_batched(b, st)
+    r1 = pipe.run_later_frames_batched(a, st, replay=True)
+    plan = pipe._frame_plans[key]
+    keep = [{k: r1[f][k].clone() for k in KEYS} for f in range(3)]
+    r2 = pipe.run_later_frames_batched(b, st, replay=True)
+    r3 = pipe.run_later_frames_batched(a, st, replay=True)
+    assert pipe._frame_plans[key] is plan                                         # recorded once, replayed since
+    for f in range(3):
+        for k in KEYS:
+            assert torch.equal(r1[f][k], eager_a[f][k]) and torch.equal(r3[f][k], eager_a[f][k]), (f, k)
+            assert torch.equal(r2[f][k], eager_b[f][k]), (f, k)
+            assert torch.equal(r1[f][k], keep[f][k]), (f, k)                      # handed out as copies: later replays leave them
+    assert not torch.equal(r2[0]["frame_icn"], r1[0]["frame_icn"])
+    after = {k: id(v) for k, v in pipe._frame_plans.items() if k[0] != "later_batch"}
+    assert after == before                                                        # the other plans: none created, none dropped
+
+
+@pytest.mark.parametrize("max_batch,groups", [(3, 3), (6, 2)])
+def test_chunked_passes_meet_the_same_bars_in_scene_order(env, max_batch, groups):
+    """max_batch = V: one frame per pass; 2 * V: a group of two and a remainder of one (max_batch < V: tests/test_later_batch_cpu.py)."""
+    pipe, V = env["pipe"], 3
+    assert len(pl.later_batch_groups(3, V, max_batch)) == groups
+    calls = []
+    orig = pipe._run_later_batch
+    pipe._run_later_batch = lambda scenes, state, replay=False: (calls.append(len(scenes)), orig(scenes, state, replay))[1]
+    try:
+        got = pipe.run_later_frames_batched(env["later"], env["f0"]["state"], max_batch=max_batch)
+    finally:
+        del pipe._run_later_batch
+    assert calls == ([2, 1] if max_batch == 6 else [1, 1, 1])
+    assert len(got) == 3
+    for f, (g, ref, cpu) in enumerate(zip(got, env["refs"], env["cpus"])):        # frame f's result sits at position f
+        _bars(g, ref, cpu, f"max_batch {max_batch} frame {f}")
+
+
+def test_range_guard_redoes_the_whole_batch_in_fp32(env):
+    """An appearance code outside the split-fp16 range in the batch: the status word is raised once, and the results are those
+    of an exact-fp32 run of the same batch, bit for bit."""
+    pipe = env["pipe"]
+    hot = dict(env["f0"]["state"])
+    hot["appearance"] = [t.clone() for t in env["f0"]["state"]["appearance"]]
+    hot["appearance"][1][0, 0, 0, 0] = 6e4
+    with ops.precision("f32"):
+        f32 = pipe.run_later_frames_batched(env["later"], hot, check=None)
+    h16 = pipe.run_later_frames_batched(env["later"], env["f0"]["state"])
+    raised = []
+    orig = ops.range_exceeded
+    ops.range_exceeded = lambda *a, **k: (raised.append(orig(*a, **k)), raised[-1])[1]
+    try:
+        got = pipe.run_later_frames_batched(env["later"], hot)
+    finally:
+        ops.range_exceeded = orig
+    assert raised == [True]                                                       # one status word, read once, for the whole batch
+    for f in range(3):
+        for k in KEYS:
+            assert torch.equal(got[f][k], f32[f][k]), (f, k)
+    assert any(not torch.equal(got[f]["vunet_u8"], h16[f]["vunet_u8"]) for f in range(3))
+    assert not ops.range_exceeded(DEV) and not ops.range_exceeded(DEV, word=pipe.status_word())
+
+
+def test_edge_cases(env):
+    pipe, st, later = env["pipe"], env["f0"]["state"], env["later"]
+    assert pipe.run_later_frames_batched([], st) == []
+    with pytest.raises(ValueError, match="vehicle_seeds"):
+        pipe.run_later_frames_batched([later[0], {k: v for k, v in later[1].items() if k != "vehicle_seeds"}], st)
+    with pytest.raises(ValueError, match="vehicles"):
+        pipe.run_later_frames_batched([later[0], pl.synth_frame(1, HW, DEV, seed=43)], st)
+    with pytest.raises(ValueError, match="src_planes"):
+        pipe.run_later_frames_batched([later[0], dict(later[1], src_planes=later[1]["src_planes"].clone())], st)
+    H, W = HW
+    e = lambda *sh: torch.empty(sh, dtype=torch.uint8, device=DEV)                # noqa: E731
+    none = {"masks": e(0, H, W), "dst_sketch": e(0, H, W, 3), "src_planes": e(0, 5, H, W, 3), "src_kp": [], "dst_kp": [],
+            "src_vis": np.zeros((0, 5), np.uint8), "dst_vis": np.zeros((0, 5), np.uint8)}
+    st0 = {"appearance": [t[:0] for t in st["appearance"]], "central": st["central"][:0], "shard": (0, 0, 0), "sharded": False}
+    frames = [later[0]["frame"], later[1]["frame"]]
+    out = pipe.run_later_frames_batched([dict(none, frame=fr) for fr in frames], st0)
+    assert len(out) == 2
+    for o, fr in zip(out, frames):
+        assert tuple(o["icn_u8"].shape) == (0, 256, 256, 3) and tuple(o["vunet_u8"].shape) == (0, 256, 256, 3) and tuple(o["geom"].shape) == (0, 8)
+        assert torch.equal(o["frame_icn"], fr) and torch.equal(o["frame_vunet"], fr)
+
+
+def test_run_clip_frames_batched(env):
+    """run_clip_frames(batched=True) yields the first frame and the F future frames, each under the bars batched=False meets."""
+    pipe = env["pipe"]
+    clip = list(pipe.run_clip_frames(env["first"], env["later"], batched=True))
+    assert len(clip) == 4
+    for k in ("kp_idx", "icn_u8", "vunet_u8", "frame_icn", "frame_vunet"):
+        assert torch.equal(clip[0][k], env["f0"][k]), k
+    for f in range(3):
+        _bars(clip[1 + f], env["refs"][f], env["cpus"][f], f"clip frame {f}")
+    plain = list(pipe.run_clip_frames(env["first"], env["later"]))                # the default is the path of today
+    for f in range(3):
+        want = pipe.run_later_frame(env["later"][f], env["f0"]["state"])
+        for k in KEYS:
+            assert torch.equal(plain[1 + f][k], want[k]), (f, k)
+
+
+def test_a_geometry_mode_state_falls_back_to_the_frame_by_frame_driver():
+    from future_urban_scene_generation_amd import render as R
+    from test_gpu_render import _geometry_setup
+    pipe, _, scene = _geometry_setup(V=2)
+    out = pipe.run_frame(scene)
+    steps = R.trajectory_steps(np.c_[np.arange(6.0) * 0.8, 0.05 * np.arange(6.0) ** 2])
+    later = [{"frame": scene["frame"], "steps": [steps[n]] * 2, "vehicle_seeds": [900 + 10 * n + v for v in range(2)]} for n in (0, 1)]
+    want = list(pipe.run_later_frames(later, out["state"]))
+    got = pipe.run_later_frames_batched(later, out["state"])
+    assert len(got) == 2 and not any(k[0] == "later_batch" for k in pipe._frame_plans)
+    for a, b in zip(got, want):
+        assert a["skipped"] == b["skipped"]
+        for k in KEYS:
+            assert torch.equal(a[k], b[k]), k
+
+
+# ------------------------------------------------------------------------------------------------ inpainting
+@pytest.fixture(scope="module")
+def inpaint_env():
+    """A pipeline with all five networks, a first frame of 2 vehicles, 2 future frames with their own boxes (each reaching into the
+    other vehicle's mask) and the vehicle-serial reference of tests/later_inpaint_ref.py for both."""
+    ops.set_precision("f16x3")
+    sds = {n: synth_sd(n) for n in ("hg", "icn", "vunet", "edge", "inpaint")}
+    pipe = pl.VehiclePipeline(DEV, inpaint=True, state_dicts=sds)
+    first = pl.synth_frame(2, HW, DEV, seed=41, inpaint="masks")
+    first["vehicle_seeds"] = [11, 12]
+    f0 = pipe.run_frame(first)
+    frames = []
+    for f in range(2):
+        later = _moved(first, f)
+        masks = later["masks"].cpu().numpy()
+        dy, dx = 5 + 3 * f, -7 - 2 * f
+        boxes = lr.overlapping_boxes(masks, pl.synth_inpaint_boxes(np.asarray(first["bboxes"]).tolist(), HW, [(dx, dy)] * 2))
+        planes = pl.synth_det_masks(list(masks), boxes.tolist())
+        frames.append(dict(later=later, boxes=boxes, planes=planes,
+                           box_masks=dict(later, inpaint={"boxes": boxes, "box_masks": [m.to(DEV) for m in pl.synth_box_masks(planes, boxes)]})))
+    nt = torch.get_num_threads()
+    torch.set_num_threads(_host_threads())
+    try:
+        plain = {k: v for k, v in sds.items() if k in ("hg", "icn", "vunet")}
+        o0 = oracle.frame_pass(plain, lr.scene_cpu({k: v for k, v in first.items() if k != "inpaint"}))
+        for fr in frames:
+            fr["cpu"] = lr.scene_cpu(fr["later"])
+            fr["four"] = ops.inpaint_inputs_host(fr["cpu"]["frame"], fr["planes"].numpy(), fr["boxes"])
+            fr["ref"] = lr.later_inpaint_pass(sds, fr["cpu"], o0["state"], fr["four"], fr["boxes"])
+    finally:
+        torch.set_num_threads(nt)
+    return dict(pipe=pipe, first=first, f0=f0, frames=frames)
+
+
+def _inpaint_bars(got, fr, tag):
+    """The bars of test_later_frame_with_inpainting_matches_the_reference."""
+    ref, cpu = fr["ref"], fr["cpu"]
+    assert tuple(got["inpaint_u8"].shape) == (2, 256, 256, 3)
+    assert np.array_equal(got["geom"].cpu().numpy(), ref["geom"]), tag
+    for k in ("inpaint_u8", "vunet_u8"):
+        d = int(np.abs(got[k].cpu().numpy().astype(int) - ref[k].astype(int)).max())
+        print(f"{tag}: {k} max diff {d}")
+        record(f"later_batch_inpaint_{k}_max_diff", d)
+        assert d <= 1, (tag, k, d)
+    any_mask = cpu["masks"].max(0).astype(bool)
+    cover = any_mask.copy()
+    for x0, y0, x1, y1 in fr["boxes"]:
+        cover[y0:y1, x0:x1] = True
+    for k in ("frame_icn", "frame_vunet"):
+        a = got[k].cpu().numpy()
+        sv = oracle.ssim(a, ref[k])
+        d = int(np.abs(a.astype(int) - ref[k].astype(int))[~any_mask].max())
+        print(f"{tag}: {k} ssim {sv} max diff in boxes outside masks {d}")
+        record(f"later_batch_inpaint_{k}_ssim", sv, worst=min)
+        assert sv >= 0.999, (tag, k, sv)
+        assert np.array_equal(a[~cover], cpu["frame"][~cover]), (tag, k)
+        assert d <= 2, (tag, k, d)
+        x0, y0, x1, y1 = fr["boxes"][0]
+        assert not np.array_equal(a[y0:y1, x0:x1], cpu["frame"][y0:y1, x0:x1]), (tag, k)
+
+
+@pytest.mark.parametrize("form", ["box_masks", "given"])
+def test_inpainted_batch_matches_the_reference(inpaint_env, form):
+    """F = 2, V = 2 with scene['inpaint'] as detector masks in box coordinates and as the four given tensors: the merged boxes
+    within 1 LSB of the reference, the frames under the later-inpaint bars; EdgeConnect's batched inputs byte-equal to the
+    per-frame op's, each frame's rows built from ITS image."""
+    pipe, st, frames = inpaint_env["pipe"], inpaint_env["f0"]["state"], inpaint_env["frames"]
+    per_frame = [ops.inpaint_inputs_boxed(fr["later"]["frame"], fr["box_masks"]["inpaint"]["box_masks"], fr["boxes"]) for fr in frames]
+    if form == "box_masks":
+        scenes = [fr["box_masks"] for fr in frames]
+    else:
+        scenes = [dict(fr["later"], inpaint=dict(four, boxes=fr["boxes"])) for fr, four in zip(frames, per_frame)]
+    ec, join = pipe._inpaint_inputs_batch(scenes, 2, {})
+    join()
+    for k in ops.INPAINT_KEYS:
+        assert torch.equal(ec[k], torch.cat([four[k] for four in per_frame])), k
+    assert not torch.equal(ec["img"][:2], ec["img"][2:])
+    got = pipe.run_later_frames_batched(scenes, st)
+    assert len(got) == 2
+    for f, fr in enumerate(frames):
+        _inpaint_bars(got[f], fr, f"{form} frame {f}")
+    rep = [pipe.run_later_frames_batched(scenes, st, replay=True) for _ in range(2)]   # recorded, then replayed into the plan's inputs
+    assert ("later_batch", 2, 2, ops.PRECISION, "inpaint") in pipe._frame_plans
+    for r in rep:
+        for f in range(2):
+            for k in KEYS + ("inpaint_u8",):
+                assert torch.equal(r[f][k], got[f][k]), (f, k)
+
+
+def test_inpaint_presence_is_all_or_none(inpaint_env):
+    pipe, st, frames = inpaint_env["pipe"], inpaint_env["f0"]["state"], inpaint_env["frames"]
+    with pytest.raises(ValueError, match="inpaint"):
+        pipe.run_later_frames_batched([frames[0]["box_masks"], frames[1]["later"]], st)
+    with pytest.raises(ValueError, match="inpaint=True"):
+        pipe.run_later_frames_batched([frames[0]["box_masks"], dict(frames[1]["later"], inpaint={"boxes": frames[1]["boxes"]})], st)
+    got = pipe.run_later_frames_batched([fr["later"] for fr in frames], st)      # no scene carries the key: the plain pass
+    assert all("inpaint_u8" not in g for g in got)

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""GPU box, analysis tool: a clip's tail (F = 5 future frames, 720 x 1280, f16x3) frame by frame with one frame in flight
+(`run_later_frames(replay=True)`, the path of the parent commit) against ONE batched pass (`run_later_frames_batched`, replayed and
+eager), at 8 and 64 vehicles, with and without scene['inpaint'].  The arms alternate clip by clip in one process after a warm-up of
+every arm; each clip tail ends in a device synchronise; the medians go to --out (default profiles/later_batch_time.json).
+
+    python tools/later_batch_time.py                                  # the timing table
+    rocprofv3 --kernel-trace --stats -d DIR --output-format csv -- python tools/later_batch_time.py --arm batched_replay --vehicles 8
+    python tools/later_batch_time.py --fold DIR/.../*_kernel_stats.csv  # adds the batched arm's per-kernel split to --out
+
+(The profiler slows the host: the split is taken in a run of its own, the times never under it.)"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+F, HW = 5, (720, 1280)
+ARMS = ("frames_replay", "batched_replay", "batched_eager")
+
+
+def fold(args):
+    with open(args.fold) as f:
+        rows = list(csv.DictReader(f))
+    rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
+    total = sum(float(r["TotalDurationNs"]) for r in rows)
+    clips = args.warmup + args.reps
+    split = [{"kernel": r["Name"][:96], "calls_per_clip": int(r["Calls"]) / clips, "ms_per_clip": float(r["TotalDurationNs"]) / clips / 1e6,
+              "share": float(r["TotalDurationNs"]) / total} for r in rows[:args.top]]
+    rest = rows[args.top:]
+    split.append({"kernel": f"({len(rest)} others)", "calls_per_clip": sum(int(r["Calls"]) for r in rest) / clips,
+                  "ms_per_clip": sum(float(r["TotalDurationNs"]) for r in rest) / clips / 1e6,
+                  "share": sum(float(r["TotalDurationNs"]) for r in rest) / total})
+    with open(args.out) as f:
+        doc = json.load(f)
+    doc["batched_replay_kernel_split"] = {"vehicles": args.vehicles[0], "inpaint": bool(args.inpaint), "clips_profiled": clips,
+                                          "gpu_ms_per_clip_tail": total / clips / 1e6,
+                                          "launches_per_clip_tail": sum(int(r["Calls"]) for r in rows) / clips, "kernels": split}
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print(json.dumps(doc["batched_replay_kernel_split"], indent=1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "later_batch_time.json"))
+    ap.add_argument("--vehicles", type=int, nargs="+", default=[8, 64])
+    ap.add_argument("--inpaint", type=int, nargs="+", default=None, help="0 / 1; default both (with --arm: 0)")
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--arm", choices=ARMS, default=None, help="run this arm alone and write nothing (for a profiler)")
+    ap.add_argument("--fold", default=None, help="a rocprofv3 kernel_stats.csv of an --arm batched_replay run")
+    ap.add_argument("--top", type=int, default=14)
+    args = ap.parse_args()
+    if args.fold:
+        args.inpaint = (args.inpaint or [0])[0]
+        return fold(args)
+
+    import torch
+    from future_urban_scene_generation_amd import ops
+    from future_urban_scene_generation_amd.pipeline import VehiclePipeline, synth_frame, synth_later_frame
+    if not torch.cuda.is_available():
+        raise SystemExit("later_batch_time: needs a HIP device (nothing is measured without one)")
+    dev = torch.device("cuda:0")
+    torch.set_grad_enabled(False)
+    ops.set_precision("f16x3")
+    inpaints = [bool(i) for i in (args.inpaint if args.inpaint is not None else ([0] if args.arm else [0, 1]))]
+    table = []
+    for inp in inpaints:
+        pipe = VehiclePipeline(dev, inpaint=inp)
+        for V in args.vehicles:
+            scene = synth_frame(V, HW, dev, seed=3, inpaint="masks" if inp else False)
+            scene["vehicle_seeds"] = list(range(V))
+            laters = [synth_later_frame(scene, s, inpaint="box_masks" if inp else None) for s in range(1, F + 1)]
+            state = pipe.run_frame(scene, replay=True)["state"]
+            arms = {"frames_replay": lambda: list(pipe.run_later_frames(laters, state, replay=True)),
+                    "batched_replay": lambda: pipe.run_later_frames_batched(laters, state, replay=True),
+                    "batched_eager": lambda: pipe.run_later_frames_batched(laters, state, replay=False)}
+            names = [args.arm] if args.arm else list(ARMS)
+            ms = {n: [] for n in names}
+            for rep in range(args.warmup + args.reps):
+                for n in names:                                   # the arms alternate clip by clip
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    arms[n]()
+                    torch.cuda.synchronize()
+                    if rep >= args.warmup:
+                        ms[n].append((time.perf_counter() - t0) * 1e3)
+            row = {"vehicles": V, "frames": F, "frame_hw": list(HW), "inpaint": inp, "precision": "f16x3", "reps": args.reps}
+            for n in names:
+                med = statistics.median(ms[n])
+                row[n] = {"ms_per_clip_tail": med, "ms_per_frame": med / F, "min": min(ms[n]), "max": max(ms[n])}
+            if not args.arm:
+                row["batched_replay_over_frames_replay"] = row["batched_replay"]["ms_per_clip_tail"] / row["frames_replay"]["ms_per_clip_tail"]
+            print(json.dumps(row), flush=True)
+            table.append(row)
+            del laters, scene, state
+            pipe._frame_plans.clear()
+            torch.cuda.empty_cache()
+    if not args.arm:
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/later_batch_time.py", "device": torch.cuda.get_device_name(0), "table": table}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
