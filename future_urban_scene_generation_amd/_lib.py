@@ -125,6 +125,8 @@ _SIGS = {
     "fusg_find_homography_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "fusg_pose_geometry": (C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 11),
     "fusg_pose_geometry_host": (C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 10),
+    "fusg_later_gate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "fusg_later_gate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "fusg_inpaint_inputs": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [_TP] * 4 + [C.c_void_p] * 2),
     "fusg_inpaint_inputs_scratch_bytes": (C.c_int64, [C.c_int32] * 3),
     "fusg_inpaint_inputs_host": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [_TP] * 4 + [C.c_void_p]),

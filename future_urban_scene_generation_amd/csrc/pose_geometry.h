@@ -257,5 +257,28 @@ PG_FN void vehicle(const Args& a, int v) {
     a.jobs[v] = job;
 }
 
+// ---- the tail of a later frame's geometry stage (fusg_later_gate): what the frame driver decided on the host after reading the
+// plane counts and covered-pixel counts back.  A row is one (frame, vehicle); it has GATE_SLOTS = 8 slots of independent work, the
+// width of a paste box row, of which the first P <= 7 also own a plane.  The comparison is render.visible's float64 expression
+// (online_visibility.py:145-148) as it stands, one multiply and one compare - not an integer restatement: parity is with what the
+// per-frame path computes from the read-back counts.
+constexpr int GATE_SLOTS = 8;
+
+PG_FN void later_gate_slot(const int32_t* counts, const int32_t* covered, int P, long j, int s, uint8_t* dst_vis, int32_t* valid,
+                           int32_t* box_rows) {
+    const bool ok = covered[j] > 0;                                                    // an empty render: the reference's `except: break`
+    if (s < P) {
+        const int32_t* c = counts + (j * NVIS + s) * 2;                                // (absolute, occluded)
+        dst_vis[j * P + s] = (ok && (double)c[1] > 0.9 * (double)c[0]) ? 1 : 0;
+    }
+    if (s == 0) valid[j] = ok ? 1 : 0;
+    if (box_rows && !ok) box_rows[j * GATE_SLOTS + s] = 0;
+}
+
+PG_FN void later_gate_row(const int32_t* counts, const int32_t* covered, int P, long j, uint8_t* dst_vis, int32_t* valid,
+                          int32_t* box_rows) {
+    for (int s = 0; s < GATE_SLOTS; ++s) later_gate_slot(counts, covered, P, j, s, dst_vis, valid, box_rows);
+}
+
 }  // namespace pg
 }  // namespace fusg

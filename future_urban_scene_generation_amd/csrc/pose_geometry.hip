@@ -18,6 +18,15 @@ __global__ __launch_bounds__(PG_BLOCK) void pose_geometry_kernel(const pg::Args 
     if (v < a.V) pg::vehicle(a, v);
 }
 
+// fusg_later_gate: one thread per (row, slot), GATE_SLOTS = 8 slots per row - a block of 64 lanes holds 8 whole rows, so a
+// row's visibilities, its valid word and its box row are written by neighbouring lanes with ordinary stores.
+__global__ __launch_bounds__(PG_BLOCK) void later_gate_kernel(const int32_t* counts, const int32_t* covered, int J, int P,
+                                                              uint8_t* dst_vis, int32_t* valid, int32_t* box_rows) {
+    const int t = blockIdx.x * PG_BLOCK + threadIdx.x;
+    const int j = t / pg::GATE_SLOTS;
+    if (j < J) pg::later_gate_slot(counts, covered, P, j, t % pg::GATE_SLOTS, dst_vis, valid, box_rows);
+}
+
 }  // namespace fusg
 
 using namespace fusg;
@@ -80,5 +89,39 @@ extern "C" int fusg_pose_geometry_host(const float* rvec, const float* tvec, con
     const int rc = pose_geometry_check(a, "pose_geometry_host");
     if (rc != FUSG_OK) return rc;
     for (int v = 0; v < V; ++v) pg::vehicle(a, v);
+    return FUSG_OK;
+}
+
+// ---- the later-frame gate: plane counts + covered counts -> gated visibilities, valid words, gated box rows
+static int later_gate_check(const int32_t* counts, const int32_t* covered, int32_t J, int32_t P, const uint8_t* dst_vis,
+                            const int32_t* valid, const char* what) {
+    FUSG_CHECK(J >= 0 && J < (1 << 20), "%s: J %d (0 .. 2^20 - 1)", what, J);
+    FUSG_CHECK(P >= 1 && P <= pg::NVIS, "%s: P %d (1 .. %d planes)", what, P, pg::NVIS);
+    FUSG_CHECK(counts && covered && dst_vis && valid, "%s: counts, covered, dst_vis or valid is null", what);
+    return FUSG_OK;
+}
+
+static int later_gate_impl(const int32_t* counts, const int32_t* covered, int32_t J, int32_t P, uint8_t* dst_vis, int32_t* valid,
+                           int32_t* box_rows, void* stream) {
+    const unsigned blocks = (unsigned)(((long)J * pg::GATE_SLOTS + PG_BLOCK - 1) / PG_BLOCK);
+    hipLaunchKernelGGL(later_gate_kernel, dim3(blocks), dim3(PG_BLOCK), 0, (hipStream_t)stream, counts, covered, J, P, dst_vis, valid,
+                       box_rows);
+    FUSG_LAUNCH_CHECK("later_gate");
+    return FUSG_OK;
+}
+
+extern "C" int fusg_later_gate(const int32_t* counts, const int32_t* covered, int32_t J, int32_t P, uint8_t* dst_vis, int32_t* valid,
+                               int32_t* box_rows, void* stream) {
+    const int rc = later_gate_check(counts, covered, J, P, dst_vis, valid, "later_gate");
+    if (rc != FUSG_OK) return rc;
+    if (J == 0) return FUSG_OK;
+    return fusg::plan_dispatch(later_gate_impl, stream, counts, covered, J, P, dst_vis, valid, box_rows);
+}
+
+extern "C" int fusg_later_gate_host(const int32_t* counts, const int32_t* covered, int32_t J, int32_t P, uint8_t* dst_vis,
+                                    int32_t* valid, int32_t* box_rows) {
+    const int rc = later_gate_check(counts, covered, J, P, dst_vis, valid, "later_gate_host");
+    if (rc != FUSG_OK) return rc;
+    for (long j = 0; j < J; ++j) pg::later_gate_row(counts, covered, P, j, dst_vis, valid, box_rows);
     return FUSG_OK;
 }

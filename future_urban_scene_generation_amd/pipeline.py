@@ -204,6 +204,38 @@ def later_batch_seeds(seeds_per_frame: Sequence[Optional[Sequence[int]]], V: int
     return out
 
 
+def later_geometry_batch_rows(scenes: Sequence[Dict], vehicles: Sequence[int], device_pose: bool, device_homography: bool,
+                              inpaint: bool = False) -> Tuple[Optional[List[int]], bool]:
+    """What `run_later_frames_batched_geometry` checks before it issues anything, for F geometry-mode scenes ('steps', no 'masks')
+    and the first-frame indices `vehicles` of the state (pure Python).  The batched stage is the per-frame DEVICE path's
+    arithmetic row by row, so it needs a pipeline built with device_pose=True and device_homography=True; 'vehicle_seeds' and
+    'inpaint' list every first-frame vehicle like 'steps', and either every scene carries them or none does (`inpaint`: the
+    pipeline holds the inpainting networks - without them the key is ignored).  ValueError otherwise.  Returns (the seeds of
+    the F * V rows, frame-major, or None; whether the pass inpaints)."""
+    if not device_pose or not device_homography:
+        raise ValueError("run_later_frames_batched_geometry: a geometry-mode state is batched only by a pipeline built with "
+                         f"device_pose=True and device_homography=True (device_pose={bool(device_pose)}, "
+                         f"device_homography={bool(device_homography)}): the batched stage is that path's arithmetic, row by row")
+    veh = [int(v) for v in vehicles]
+    for f, sc in enumerate(scenes):
+        if "masks" in sc or sc.get("steps") is None:
+            raise ValueError(f"run_later_frames_batched_geometry: scene {f} is not a geometry-mode scene ('steps', no 'masks')")
+        for k in ("steps", "vehicle_seeds"):
+            if sc.get(k) is not None and veh and len(sc[k]) <= max(veh):
+                raise ValueError(f"run_later_frames_batched_geometry: scene {f} carries {len(sc[k])} {k!r} entries, the state's "
+                                 f"vehicles reach first-frame index {max(veh)}")
+    seeds = later_batch_seeds([None if sc.get("vehicle_seeds") is None else [sc["vehicle_seeds"][v] for v in veh] for sc in scenes],
+                              len(veh))
+    inps = [sc.get("inpaint") if inpaint else None for sc in scenes]
+    if any(i is not None for i in inps) and not all(i is not None for i in inps):
+        raise ValueError("run_later_frames_batched_geometry: either every scene of the batch carries 'inpaint' or none does "
+                         f"(frames without: {[f for f, i in enumerate(inps) if i is None]})")
+    for i in inps:
+        if i is not None:
+            inpaint_scene_form(i)                                 # (ValueError for a malformed entry, before anything is issued)
+    return seeds, inps[0] is not None if inps else False
+
+
 def _tensors(o):
     """Every tensor inside a nested dict / list / tuple, depth first."""
     if torch.is_tensor(o):
@@ -1612,14 +1644,51 @@ class VehiclePipeline:
         Returns a list of F dicts with `run_later_frame`'s keys and shapes, in scene order ('icn_u8', 'vunet_u8', 'geom',
         'frame_icn', 'frame_vunet' (+ 'inpaint_u8')); a frame's tensors are views into the pass's stacked results.  V = 0: F
         results of `run_later_frame`'s no-vehicle shape; F = 0: [].
-        Out of scope: a geometry-mode state (scenes without 'masks') and a sharded state (process group) go through
-        `run_later_frames`, frame by frame - the results of today."""
+        A geometry-mode state (scenes without 'masks') and a sharded state (process group) go through `run_later_frames`, frame
+        by frame - the results of today; `run_later_frames_batched_geometry` is the opt-in that batches a geometry-mode state
+        (this method's parameter list is pinned, so the flag lives on a sibling)."""
+        return self._later_frames_batched(scenes, state, replay, check, max_batch, False)
+
+    def run_later_frames_batched_geometry(self, scenes, state: Dict, replay: bool = False, check: Optional[str] = "sync",
+                                          max_batch: Optional[int] = None, batch_geometry: bool = True) -> list:
+        """`run_later_frames_batched` that also batches a GEOMETRY-MODE state (scenes with 'steps', no 'masks'; batch_geometry=False:
+        exactly `run_later_frames_batched`, the frame-by-frame fallback).  Frame by frame such a later frame blocks on a
+        device-to-host copy between its render and its plane warp (`render.vehicle_geometry_device`), because the visibilities
+        and the skip rule were decided on the host, and its networks run at batch "kept vehicles".  Here a group of
+        `later_batch_groups(F, V, max_batch)` frames is queued whole before anything is read: `render.later_geometry_batch_device`
+        (fusg_pose_geometry -> fusg_render_normals_u8 -> fusg_plane_visibility -> fusg_later_gate at F * V rows) ->
+        `plane_homographies_device` from device corner points and gated visibilities -> the shared-source plane warp -> crop rows
+        and both networks' inputs -> `_later_nets` at F * V -> Lab -> BGR -> the ordered paste of all frames; then ONE `ops.d2h`
+        of the stage's small packed buffer, from which the per-frame results are cut.  V = the state's vehicles, rows
+        frame-major, the plan of replay=True is the ("later_batch", F, V, precision[, "inpaint"]) plan a given-geometry batch of that
+        shape uses: its shape no longer depends on what rendered.
+        A vehicle whose render is empty (covered == 0, the reference's `except: break`) stays in the batch as an INERT row:
+        its gated visibilities are zero, so no plane is warped for it; its mask is empty, so its crop row is all zero, its network
+        inputs are black and nothing of it is pasted; with inpainting its box row is zeroed by the gate ("a skipped vehicle is not
+        inpainted").  Its network outputs are dropped from the result.
+        Needs a pipeline built with device_pose=True and device_homography=True (ValueError before any launch otherwise: those
+        are the paths whose per-row arithmetic this stage repeats, so it equals the per-frame device path byte for byte); a state
+        made without device copies uploads its host pose and corner points once.  'vehicle_seeds' and 'inpaint' list every
+        first-frame vehicle, like 'steps'; either every scene carries them or none does.  A sharded state keeps falling back; a
+        non-geometry state ignores the flag.  The range guard is `run_later_frames_batched`'s: one status word per group, a raised
+        word redoes the group in exact fp32.
+        Memory per row at H x W: 19 * H * W bytes (sketch 3, mask 1, warped planes 15) - 17.5 MB at 720 x 1280, 1.1 GB at 64 rows
+        (the given-geometry batch's 13.8 MB per row are the warped planes alone: its masks and sketches are the caller's).
+        Returns a list of F dicts with `run_later_frame`'s geometry-mode keys: 'icn_u8', 'vunet_u8', 'geom' (+ 'inpaint_u8') of the
+        kept vehicles in order, 'frame_icn', 'frame_vunet', 'geometry' ('masks', 'dst_sketch', 'dst_kp', 'dst_vis', 'kp3d' of
+        every vehicle of the state) and 'skipped'."""
+        return self._later_frames_batched(scenes, state, replay, check, max_batch, bool(batch_geometry))
+
+    def _later_frames_batched(self, scenes, state, replay, check, max_batch, batch_geometry) -> list:
         scenes = list(scenes)
         F = len(scenes)
         if F == 0:
             return []
-        if (not _one_rank(self.group) and state.get("sharded")) or any(self._is_geometry(sc, state) for sc in scenes):
+        geometry = any(self._is_geometry(sc, state) for sc in scenes)
+        if (not _one_rank(self.group) and state.get("sharded")) or (geometry and not batch_geometry):
             return list(self.run_later_frames(scenes, state, replay=replay))
+        if geometry:
+            return self._later_geometry_batched(scenes, state, replay, check, max_batch)
         V = int(state["central"].shape[0])
         for f, sc in enumerate(scenes):
             if int(sc["masks"].shape[0]) != V:
@@ -1647,28 +1716,36 @@ class VehiclePipeline:
         return self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay))
 
     @torch.no_grad()
-    def _later_batch_stages(self, scenes, state, icn_out=None) -> Dict:
+    def _later_batch_stages(self, scenes, state, icn_out=None, geo=None) -> Dict:
         """The data movement of a batched later pass in front of the networks, frame-major over the F scenes: 'warped' uint8
         [F * V, P, H, W, 3], 'masks' uint8 [F * V, H, W], 'geom' int32 [F * V, 8], 'icn_x' [F * V, 21, R, R] (icn_out: a recorded
         pass's buffer, written in place), 'vu_y' [F * V, 3, R, R].  Nothing here depends on the batch size: every row holds the
-        bytes `_later_local` builds for its frame."""
+        bytes `_later_local` builds for its frame.  geo (geometry mode, `_later_geometry_stage`): the masks, sketches, corner points
+        and visibilities come from the device stage instead of the scenes."""
         import numpy as np
 
         from . import frame_ops as fo
         from .warp_learn import planes_utils as pu
         F, R = len(scenes), 256
-        src_planes = scenes[0]["src_planes"]
-        kp = {k: [veh for sc in scenes for veh in sc[k]] for k in ("src_kp", "dst_kp")}
-        vis = {k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in scenes]) for k in ("src_vis", "dst_vis")}
         with torch.cuda.device(self.device):
-            if self.device_homography:
-                minv, index = pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
-                warped = pu.warp_planes_frames_fitted(src_planes, minv, index, F)              # :376-381
+            if geo is not None:
+                # geometry mode: masks, sketches, corner points and gated visibilities as the device stage left them
+                minv, index = pu.plane_homographies_device(geo["src_kp_d"], geo["tex_pts_d"], geo["src_vis_d"], geo["dst_vis_d"],
+                                                           nverts=geo["kp_nv_d"])
+                warped = pu.warp_planes_frames_fitted(geo["src_planes"], minv, index, F)       # :376-381
+                masks, sketch = geo["mask"], geo["sketch"]
             else:
-                jobs = pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
-                warped = pu.warp_planes_frames_batch(src_planes, jobs, F)
-            cat = lambda k: scenes[0][k] if F == 1 else torch.cat([sc[k] for sc in scenes])    # noqa: E731
-            masks, sketch = cat("masks"), cat("dst_sketch")
+                src_planes = scenes[0]["src_planes"]
+                kp = {k: [veh for sc in scenes for veh in sc[k]] for k in ("src_kp", "dst_kp")}
+                vis = {k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in scenes]) for k in ("src_vis", "dst_vis")}
+                if self.device_homography:
+                    minv, index = pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
+                    warped = pu.warp_planes_frames_fitted(src_planes, minv, index, F)          # :376-381
+                else:
+                    jobs = pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
+                    warped = pu.warp_planes_frames_batch(src_planes, jobs, F)
+                cat = lambda k: scenes[0][k] if F == 1 else torch.cat([sc[k] for sc in scenes])    # noqa: E731
+                masks, sketch = cat("masks"), cat("dst_sketch")
             _, geom = fo.mask_bbox_geom(masks)
             icn_x = pu.icn_inputs_device(warped, sketch, state["central"].repeat(F, 1, 1, 1), geom, R, R, out=icn_out)   # :385-387
             _, vu_y = fo.vunet_inputs(scenes[0]["frame"], masks, sketch, sketch, geom, R)      # :415-420 (y_tilde reads no frame)
@@ -1707,9 +1784,9 @@ class VehiclePipeline:
         return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
 
     @torch.no_grad()
-    def _later_batch_local(self, scenes, state, replay=False) -> Dict:
+    def _later_batch_local(self, scenes, state, replay=False, geo=None) -> Dict:
         """The per-(frame, vehicle) part of a batched later pass: glue, the networks at B = F * V, Lab -> BGR.  Returns 'icn_u8'
-        (BGR), 'vunet_u8', 'geom', 'masks' (+ 'inpaint_u8'), F * V rows each, frame-major."""
+        (BGR), 'vunet_u8', 'geom', 'masks' (+ 'inpaint_u8'), F * V rows each, frame-major.  geo: see `_later_batch_stages`."""
         from . import ops
         from .warp_learn import planes_utils as pu
         F, V = len(scenes), int(state["central"].shape[0])
@@ -1721,7 +1798,7 @@ class VehiclePipeline:
             cp = self._plan(pkey) if replay else None
             tgt = cp.inputs if cp is not None else {}            # a recorded pass's big inputs are written in place
             ec, ec_join = self._inpaint_inputs_batch(scenes, V, tgt) if inpaint else (None, None)
-            st = self._later_batch_stages(scenes, state, icn_out=tgt.get("icn_x"))
+            st = self._later_batch_stages(scenes, state, icn_out=tgt.get("icn_x"), geo=geo)
             nets_in = {"icn_x": st["icn_x"], "vu_y": st["vu_y"],
                        "app0": state["appearance"][0].repeat(F, 1, 1, 1), "app1": state["appearance"][1].repeat(F, 1, 1, 1)}
             if ec is not None:
@@ -1736,12 +1813,10 @@ class VehiclePipeline:
         return out
 
     @torch.no_grad()
-    def _later_batch_finish(self, scenes, out) -> list:
+    def _later_batch_finish(self, scenes, out, box_geom=None) -> list:
         """The frame-level part of a batched later pass: the ordered paste of all F frames, one launch per composite; then the
-        stacked results cut into `run_later_frame`'s dict per frame."""
-        import numpy as np
-
-        from . import ops
+        stacked results cut into `run_later_frame`'s dict per frame.  box_geom: the box rows already on the device (geometry mode:
+        uploaded in front of the stage, whose gate zeroes the rows of empty renders)."""
         from .warp_learn import planes_utils as pu
         F = len(scenes)
         V = int(out["geom"].shape[0]) // F
@@ -1751,28 +1826,130 @@ class VehiclePipeline:
             bases = [sc["frame"] if inpaint else sc.get("background", sc["frame"]) for sc in scenes]
             box = {}
             if inpaint:                                           # :340-350: every vehicle's inpainted box under its crop, in vehicle order
-                rows = np.zeros((F * V, 8), np.int32)
-                for f, sc in enumerate(scenes):
-                    rows[later_batch_slice(f, V), :4] = np.asarray(sc["inpaint"]["boxes"]).reshape(V, 4)
-                box = dict(box_images=out["inpaint_u8"], box_geom=ops.h2d(rows, self.device, torch.int32))
+                box = dict(box_images=out["inpaint_u8"], box_geom=box_geom if box_geom is not None else self._later_box_rows(scenes, V))
             frames = {k: pu.paste_back_frames_device(bases, out[c], out["geom"], out["masks"], **box)       # :393-410, :428-445
                       for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
         keys = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
         return [{**{k: out[k][later_batch_slice(f, V)] for k in keys}, "frame_icn": frames["frame_icn"][f],
                  "frame_vunet": frames["frame_vunet"][f]} for f in range(F)]
 
-    def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False, batched: bool = False):
+    def _later_box_rows(self, scenes, V: int) -> torch.Tensor:
+        """The paste box rows of F scenes' 'inpaint' boxes, frame-major: CUDA int32 [F * V, 8] = (x0, y0, x1, y1, 0, 0, 0, 0)."""
+        import numpy as np
+
+        from . import ops
+        rows = np.zeros((len(scenes) * V, 8), np.int32)
+        for f, sc in enumerate(scenes):
+            rows[later_batch_slice(f, V), :4] = np.asarray(sc["inpaint"]["boxes"]).reshape(V, 4)
+        return ops.h2d(rows, self.device, torch.int32)
+
+    # ---- the same for a geometry-mode state: the render, the visibilities and the skip rule stay on the device
+    def _later_geometry_batched(self, scenes, state, replay, check, max_batch) -> list:
+        """`run_later_frames_batched_geometry` for F geometry-mode scenes on one rank: validation, then one guarded pass per group."""
+        gs = state["geometry"]
+        veh = list(gs["vehicles"])
+        V = len(veh)
+        seeds, inpaint = later_geometry_batch_rows(scenes, veh, self.device_pose, self.device_homography, self.inpaint)
+        if int(state["central"].shape[0]) != V:
+            raise ValueError(f"run_later_frames_batched_geometry: the state holds {int(state['central'].shape[0])} crops for {V} vehicles")
+        if any(tuple(sc["frame"].shape) != tuple(scenes[0]["frame"].shape) for sc in scenes):
+            raise ValueError("run_later_frames_batched_geometry: the frames of a batch have one size")
+        if V == 0:
+            return list(self.run_later_frames(scenes, state, replay=replay))
+        # the rows' scenes: 'vehicle_seeds' and 'inpaint' list every first-frame vehicle and are selected to the state's
+        rows = []
+        for sc in scenes:
+            r = dict(sc)
+            if sc.get("vehicle_seeds") is not None:
+                r["vehicle_seeds"] = [sc["vehicle_seeds"][v] for v in veh]
+            if inpaint:
+                r["inpaint"] = self._select(sc["inpaint"], veh, list(sc["inpaint"].keys()))
+            elif "inpaint" in r:
+                del r["inpaint"]
+            rows.append(r)
+        out = []
+        for lo, hi in later_batch_groups(len(scenes), V, max_batch):
+            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
+            out.extend(self._guarded(self._run_later_geometry_batch, (rows[lo:hi], state, replay), check, rng))
+        return out
+
+    @torch.no_grad()
+    def _later_geometry_stage(self, scenes, state, box_rows=None) -> Dict:
+        """The device geometry of a group of F later frames for the V vehicles of `state` (`render.later_geometry_batch_device`) and
+        what the plane homographies need besides: the first frame's corner points and visibilities repeated per frame.  A state
+        made without device copies uploads its host pose, CAD indices and corner points once.  Nothing is read back."""
+        import numpy as np
+
+        from . import ops
+        from . import render as rd
+        from .warp_learn import planes_utils as pu
+        gs = state["geometry"]
+        F, V = len(scenes), len(gs["vehicles"])
+        veh = list(gs["vehicles"])
+        H, W = int(scenes[0]["frame"].shape[0]), int(scenes[0]["frame"].shape[1])
+        K = rd.intrinsic(gs["focals"], gs["centers"])
+        dev = self.device
+        with torch.cuda.device(dev):
+            pose_d, cad_d = gs.get("pose_d"), gs.get("cad_idx_d")
+            if pose_d is None:
+                prow = [[p[0], *np.asarray(p[1]).reshape(3), *np.asarray(p[2]).reshape(3)] for p in gs["pose"]]
+                pose_d = ops.h2d(np.asarray(prow, np.float32).reshape(V, 7), dev)
+                cad_d = ops.h2d(np.asarray(gs["cad_idx"], np.int64).reshape(V), dev)
+            src_kp_d, kp_nv_d = gs.get("src_kp_d"), gs.get("kp_nv_d")
+            if src_kp_d is None:
+                pts, nv = pu.pack_plane_points(gs["src_kp"], len(rd.TEXTURE_PLANES))
+                src_kp_d, kp_nv_d = ops.h2d(pts, dev), ops.h2d(np.ascontiguousarray(nv[0]), dev)
+            src_vis_d = ops.h2d((np.asarray(gs["src_vis"]).reshape(V, -1) != 0).astype(np.uint8), dev)
+            geo = rd.later_geometry_batch_device(self.cad_bank, (H, W), cad_d, pose_d, K, [[sc["steps"][v] for v in veh] for sc in scenes],
+                                                 box_rows=box_rows)
+            geo.update(src_planes=gs["src_planes"], src_kp_d=src_kp_d.repeat(F, 1, 1, 1).contiguous(),
+                       src_vis_d=src_vis_d.repeat(F, 1).contiguous(), kp_nv_d=kp_nv_d.contiguous())
+        return geo
+
+    @torch.no_grad()
+    def _run_later_geometry_batch(self, scenes, state, replay=False) -> list:
+        """One group of a geometry-mode batch: everything through the paste is queued, then the stage's small buffer is read back
+        ONCE and the per-frame results of `_geometry_later_frame` are cut from the stacked ones."""
+        from . import ops
+        gs = state["geometry"]
+        veh = list(gs["vehicles"])
+        F, V = len(scenes), len(veh)
+        inpaint = self._later_inpaint(scenes[0]) is not None
+        with torch.cuda.device(self.device):
+            box_rows = self._later_box_rows(scenes, V) if inpaint else None
+            geo = self._later_geometry_stage(scenes, state, box_rows)
+            frames = self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay, geo=geo), box_geom=box_rows)
+            host = geo["host"](ops.d2h(geo["buf"]))               # the one read-back of the group, behind the queued paste
+            keys = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
+            out = []
+            for f, res in enumerate(frames):
+                sl = later_batch_slice(f, V)
+                keep = [i for i in range(V) if host["covered"][sl][i] > 0]
+                if len(keep) < V:                                 # the inert rows' network outputs are dropped
+                    idx = torch.as_tensor(keep, dtype=torch.long, device=self.device)
+                    res = {**res, **{k: res[k].index_select(0, idx) for k in keys}}
+                res["geometry"] = {"masks": geo["mask"][sl], "dst_sketch": geo["sketch"][sl], "dst_kp": host["dst_kp"][sl],
+                                   "dst_vis": host["dst_vis"][sl], "kp3d": host["kp3d"][sl]}
+                kept = [veh[i] for i in keep]
+                res["skipped"] = [v for v in range(len(scenes[f]["steps"])) if v not in kept]
+                out.append(res)
+        return out
+
+    def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False, batched: bool = False,
+                        batch_geometry: bool = False):
         """A vehicle clip the reference's way (trajectory_inference.py:55-250 then :267-450): the first frame through
         `run_frame`, every future frame through `run_later_frame` with the first frame's state.  Generator of 1 + len(later_scenes)
         results.  Under a process group the whole clip is sharded by vehicle: a vehicle's six frames stay on one rank (frame by
         frame).  A geometry-mode clip (cad_bank, scenes without 'masks') goes through the same drivers.
         batched=True renders the future frames as batched passes (`run_later_frames_batched`) instead of one frame in flight:
-        the same sequence of results, each frame's within that method's bars of the frame-by-frame form."""
+        the same sequence of results, each frame's within that method's bars of the frame-by-frame form.  A geometry-mode clip
+        then still runs frame by frame unless batch_geometry=True (`run_later_frames_batched_geometry`: a pipeline built with
+        device_pose=True and device_homography=True)."""
         first = self.run_frame(first_scene, replay=replay)
         state = first["state"]
         yield first if len(first) > 1 else None
         if batched:
-            yield from self.run_later_frames_batched(list(later_scenes), state, replay=replay)
+            yield from self._later_frames_batched(list(later_scenes), state, replay, "sync", None, bool(batch_geometry))
             return
         yield from self.run_later_frames(later_scenes, state, replay=replay)       # one later frame in flight
 

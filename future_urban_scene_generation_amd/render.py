@@ -604,44 +604,68 @@ def vehicle_geometry_device(bank: CadBank, frame: torch.Tensor, cad_idx_d: torch
     V = int(cad_idx_d.shape[0])
     first = steps is None
     P = len(TEXTURE_PLANES)
-    lay, nbytes = _pg_layout(V, (("counts", np.int32, 14), ("covered", np.int32, 1), ("cad_idx", np.int64, 1)))
-    tdt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64,
-           np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
     with torch.cuda.device(dev):
-        buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        d = {k: buf[o:o + n * dt.itemsize].view(tdt[dt]) for k, (o, dt, n) in lay.items()}
-        r = {"sketch": torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev),
-             "mask": torch.zeros((V, H, W), dtype=torch.uint8, device=dev)}
         planes = torch.empty((V, P, H, W, 3), dtype=torch.uint8, device=dev)
-        if V:
-            if cad_idx_d.dtype != torch.int64 or not cad_idx_d.is_cuda:
-                raise ValueError("vehicle_geometry_device: cad_idx_d is a CUDA int64 [V]")
-            arr = bank.device_arrays(dev)
-            f32 = lambda t, sh: t.to(torch.float32).contiguous().view((V,) + sh)        # noqa: E731
-            if first:
-                ins = [f32(raw_d[0], (4, 3)), f32(raw_d[1], (4, 3)), f32(raw_d[2], (4,)), None, f32(kp_xy_d, (12, 2)), None]
-            else:
-                ins = [None, None, None, f32(pose_d, (7,)), None, ops.h2d(steps_array(steps), dev)]
-            cad_c = cad_idx_d.contiguous()
-            d["cad_idx"].copy_(cad_c)
-            Kc = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
-            ptr = lambda t: None if t is None else t.data_ptr()                           # noqa: E731
-            lib = L.lib()
-            L.check(lib.fusg_pose_geometry(*(ptr(t) for t in ins), cad_c.data_ptr(), arr["kp3d"].data_ptr(), arr["v_off"].data_ptr(),
-                                           arr["t_off"].data_ptr(), len(bank), Kc.ctypes.data, H, W, V,
-                                           *(d[k].data_ptr() for k in _PG_CALL), ops.stream_ptr()), "pose_geometry")
-            max_nv = bank.max_nv
-            ws = torch.empty((V * (16 + 40 * max_nv) + 15) // 16 * 2, dtype=torch.float64, device=dev)
-            L.check(lib.fusg_render_normals_u8(arr["verts"].data_ptr(), arr["normals"].data_ptr(), arr["verts"].shape[0],
-                                               arr["tris"].data_ptr(), arr["tris"].shape[0], d["jobs"].data_ptr(), V, max_nv, H, W,
-                                               ws.data_ptr(), ws.numel() * 8, r["sketch"].data_ptr(), r["mask"].data_ptr(), None,
-                                               d["covered"].data_ptr(), ops.stream_ptr()), "render_normals_u8")
-            L.check(lib.fusg_plane_visibility(d["vis_pts"].data_ptr(), d["vis_nv"].data_ptr(), d["nearer"].data_ptr(), V, H, W,
-                                              d["counts"].data_ptr(), ops.stream_ptr()), "plane_visibility")
-        host = ops.d2h(buf) if V else np.zeros(0, np.uint8)       # the one blocking copy of the stage
+        st = _device_stage(bank, (H, W), dev, cad_idx_d, K, raw_d=raw_d, pose_d=pose_d, kp_xy_d=kp_xy_d,
+                           steps_d=None if first or not V else ops.h2d(steps_array(steps), dev))
+        host = ops.d2h(st["buf"]) if V else np.zeros(0, np.uint8)       # the one blocking copy of the stage
         if V and first:                                           # queued after the read-back: it does not wait for the planes
-            pu.fill_planes_batch(frame, d["tex_pts"], d["tex_nv"], planes)
-    h = {k: host[o:o + n * dt.itemsize].view(dt) for k, (o, dt, n) in lay.items()}
+            pu.fill_planes_batch(frame, st["d"]["tex_pts"], st["d"]["tex_nv"], planes)
+    return _device_stage_result(bank, st, host, planes, first)
+
+
+_TORCH_DT = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64,
+             np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+_STAGE_EXTRA = (("counts", np.int32, 14), ("covered", np.int32, 1), ("cad_idx", np.int64, 1))
+
+
+def _device_stage(bank: CadBank, frame_hw: Tuple[int, int], dev, cad_idx_d: torch.Tensor, K: np.ndarray, raw_d=None, pose_d=None,
+                  kp_xy_d=None, steps_d=None, extra=()) -> Dict:
+    """The launches `vehicle_geometry_device` and `later_geometry_batch_device` share, for V rows on the current stream:
+    fusg_pose_geometry -> fusg_render_normals_u8 of the device jobs -> fusg_plane_visibility, every small result in ONE zeroed
+    buffer (`_pg_layout` + counts, covered, cad_idx + `extra`).  A first frame gives raw_d and kp_xy_d, a later frame pose_d and
+    steps_d (CUDA float64 [V, 4]).  Returns 'lay' / 'nbytes' (the layout), 'buf' (the buffer), 'd' (its parts as device views),
+    'r' ('sketch' uint8 [V, H, W, 3], 'mask' uint8 [V, H, W]) and 'V'.  Nothing is read back."""
+    H, W = frame_hw
+    V = int(cad_idx_d.shape[0])
+    first = steps_d is None and pose_d is None
+    lay, nbytes = _pg_layout(V, _STAGE_EXTRA + tuple(extra))
+    buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    d = {k: buf[o:o + n * dt.itemsize].view(_TORCH_DT[dt]) for k, (o, dt, n) in lay.items()}
+    r = {"sketch": torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev),
+         "mask": torch.zeros((V, H, W), dtype=torch.uint8, device=dev)}
+    if V:
+        if cad_idx_d.dtype != torch.int64 or not cad_idx_d.is_cuda:
+            raise ValueError("vehicle_geometry_device: cad_idx_d is a CUDA int64 [V]")
+        arr = bank.device_arrays(dev)
+        f32 = lambda t, sh: t.to(torch.float32).contiguous().view((V,) + sh)        # noqa: E731
+        if first:
+            ins = [f32(raw_d[0], (4, 3)), f32(raw_d[1], (4, 3)), f32(raw_d[2], (4,)), None, f32(kp_xy_d, (12, 2)), None]
+        else:
+            ins = [None, None, None, f32(pose_d, (7,)), None, steps_d]
+        cad_c = cad_idx_d.contiguous()
+        d["cad_idx"].copy_(cad_c)
+        Kc = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        ptr = lambda t: None if t is None else t.data_ptr()                           # noqa: E731
+        lib = L.lib()
+        L.check(lib.fusg_pose_geometry(*(ptr(t) for t in ins), cad_c.data_ptr(), arr["kp3d"].data_ptr(), arr["v_off"].data_ptr(),
+                                       arr["t_off"].data_ptr(), len(bank), Kc.ctypes.data, H, W, V,
+                                       *(d[k].data_ptr() for k in _PG_CALL), ops.stream_ptr()), "pose_geometry")
+        max_nv = bank.max_nv
+        ws = torch.empty((V * (16 + 40 * max_nv) + 15) // 16 * 2, dtype=torch.float64, device=dev)
+        L.check(lib.fusg_render_normals_u8(arr["verts"].data_ptr(), arr["normals"].data_ptr(), arr["verts"].shape[0],
+                                           arr["tris"].data_ptr(), arr["tris"].shape[0], d["jobs"].data_ptr(), V, max_nv, H, W,
+                                           ws.data_ptr(), ws.numel() * 8, r["sketch"].data_ptr(), r["mask"].data_ptr(), None,
+                                           d["covered"].data_ptr(), ops.stream_ptr()), "render_normals_u8")
+        L.check(lib.fusg_plane_visibility(d["vis_pts"].data_ptr(), d["vis_nv"].data_ptr(), d["nearer"].data_ptr(), V, H, W,
+                                          d["counts"].data_ptr(), ops.stream_ptr()), "plane_visibility")
+    return {"lay": lay, "nbytes": nbytes, "buf": buf, "d": d, "r": r, "V": V}
+
+
+def _device_stage_result(bank: CadBank, st: Dict, host: np.ndarray, planes: Optional[torch.Tensor], first: bool) -> Dict:
+    """`_device_stage`'s read-back bytes `host` -> `vehicle_geometry_device`'s result (IndexError for a cad_idx outside the bank)."""
+    V, d, r, P = st["V"], st["d"], st["r"], len(TEXTURE_PLANES)
+    h = {k: host[o:o + n * dt.itemsize].view(dt) for k, (o, dt, n) in st["lay"].items()}
     bad = np.flatnonzero(h["status"] != 0)
     if len(bad):
         raise IndexError(f"render: mesh {int(h['cad_idx'][bad[0]])} not in a bank of {len(bank)}")
@@ -656,6 +680,51 @@ def vehicle_geometry_device(bank: CadBank, frame: torch.Tensor, cad_idx_d: torch
     out.update(pose=h["pose"].reshape(V, 7).copy(), pose_d=d["pose"].view(V, 7), cad_idx=h["cad_idx"].copy(), status=h["status"].copy(),
                tex_pts_d=d["tex_pts"].view(V, P, pu.MAX_VERTS, 2), tex_nv_d=d["tex_nv"][:P] if V else d["tex_nv"])
     return out
+
+
+def later_geometry_batch_device(bank: CadBank, frame_hw: Tuple[int, int], cad_idx_d: torch.Tensor, pose_d: torch.Tensor, K: np.ndarray,
+                                steps_per_frame: Sequence[Sequence[Tuple[float, np.ndarray]]], box_rows: Optional[torch.Tensor] = None
+                                ) -> Dict:
+    """`vehicle_geometry_device`'s later-frame branch for the F frames of a clip at once, WITHOUT its read-back: F * V rows,
+    frame-major (row f * V + v = frame f, vehicle v: `pipeline.later_batch_row`).  cad_idx_d CUDA int64 [V] and pose_d CUDA
+    float32 [V, 7] (a first frame's) are repeated F times on the device; steps_per_frame[f] = (theta, tr) per vehicle, one
+    [F * V, 4] upload.  Order of work, all on the current stream: fusg_pose_geometry -> fusg_render_normals_u8 ->
+    fusg_plane_visibility -> fusg_later_gate, which turns the plane counts and covered counts into what the host decided after
+    the read-back: 'valid_d' int32 [F * V] (the render is not empty) and 'dst_vis_d' uint8 [F * V, 5], the visibilities with
+    the rows of an empty render zeroed - `plane_homographies_device` then gives such a row no job.  box_rows: CUDA int32
+    [F * V, 8] paste box rows, zeroed in place where the render is empty.
+    Returns the device tensors 'mask' uint8 [F * V, H, W], 'sketch' uint8 [F * V, H, W, 3], 'tex_pts_d' int32 [F * V, 5, 8, 2],
+    'tex_nv_d' int32 [5], 'dst_vis_d', 'valid_d'; 'buf', the one small packed buffer (`_pg_layout` + counts, covered, cad_idx,
+    the gate's outputs) to read back whenever the caller likes (`ops.d2h`), and 'host' = a function of the read-back bytes that
+    gives the host keys of `vehicle_geometry_device` ('dst_kp', 'dst_vis' = `visible(counts)`, UN-gated as the per-frame path
+    reports it, 'kp3d', 'covered', 'status', ...; IndexError for a cad_idx outside the bank) plus 'valid' (host int32 [F * V])."""
+    H, W = frame_hw
+    dev = cad_idx_d.device
+    V, F, P = int(cad_idx_d.shape[0]), len(steps_per_frame), len(TEXTURE_PLANES)
+    if any(len(s) != V for s in steps_per_frame):
+        raise ValueError(f"later_geometry_batch_device: every frame carries (theta, tr) for the {V} vehicles")
+    N = F * V
+    if box_rows is not None and (not box_rows.is_cuda or box_rows.dtype != torch.int32 or tuple(box_rows.shape) != (N, 8)
+                                 or not box_rows.is_contiguous()):
+        raise ValueError("later_geometry_batch_device: box_rows is a contiguous CUDA int32 [F * V, 8]")
+    with torch.cuda.device(dev):
+        steps_d = ops.h2d(np.concatenate([steps_array(s) for s in steps_per_frame]).reshape(N, 4), dev) if N else None
+        st = _device_stage(bank, (H, W), dev, cad_idx_d.repeat(F), K, pose_d=pose_d.to(torch.float32).reshape(V, 7).repeat(F, 1),
+                           steps_d=steps_d, extra=(("dst_vis", np.uint8, P), ("valid", np.int32, 1)))
+        d = st["d"]
+        if N:
+            L.check(L.lib().fusg_later_gate(d["counts"].data_ptr(), d["covered"].data_ptr(), N, P, d["dst_vis"].data_ptr(),
+                                            d["valid"].data_ptr(), None if box_rows is None else box_rows.data_ptr(),
+                                            ops.stream_ptr()), "later_gate")
+
+    def host(read: np.ndarray) -> Dict:
+        out = _device_stage_result(bank, st, read, None, False)
+        o, dt, n = st["lay"]["valid"]
+        out["valid"] = read[o:o + n * dt.itemsize].view(dt).copy()
+        return out
+
+    return {"mask": st["r"]["mask"], "sketch": st["r"]["sketch"], "tex_pts_d": d["tex_pts"].view(N, P, pu.MAX_VERTS, 2),
+            "tex_nv_d": d["tex_nv"][:P], "dst_vis_d": d["dst_vis"].view(N, P), "valid_d": d["valid"], "buf": st["buf"], "host": host}
 
 
 # ---------------------------------------------------------------------------------------------- trajectories

@@ -564,6 +564,24 @@ int fusg_pose_geometry_host(const float* rvec, const float* tvec, const float* e
                             double* extrinsic, double* kp3d, fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv,
                             int32_t* nearer, int32_t* tex_pts, int32_t* tex_nv, int32_t* status);
 
+/* ---- the later-frame gate (the tail of a geometry-mode later frame's device stage; like the pose geometry added without a
+ * version step: the entry points are new, nothing existing changed, and FUSG_VERSION 118 is what the suite pins) ------- */
+/* The tail of a later frame's geometry stage, without a read-back: for J (frame, vehicle) rows
+ *   valid[j]      = covered[j] > 0
+ *   dst_vis[j][p] = valid[j] && (double)counts[j][p][1] > 0.9 * (double)counts[j][p][0]      p < P <= 7
+ *   box_rows[j][0..7] = 0 where !valid[j]   (optional, in place; NULL: none)
+ * counts = DEVICE int32 [J][7][2] (fusg_plane_visibility: absolute, occluded), covered = DEVICE int32 [J]
+ * (fusg_render_normals_u8); DEVICE outputs dst_vis uint8 [J][P] (0 / 1: the dst_vis of fusg_plane_homographies), valid int32
+ * [J], box_rows int32 [J][8] (the box rows of fusg_paste_layers_frames_u8).  The comparison is render.visible's float64
+ * expression - one multiply, one compare, no contraction -, so an empty plane (0 > 0) is not visible.
+ * J = 0 launches nothing; NULL / P outside 1..7 / J < 0 (or >= 2^20): FUSG_ERR_INVALID before any launch.  One thread per
+ * (row, slot of 8), ordinary stores; bit-identical to the host twin (the same code). */
+int fusg_later_gate(const int32_t* counts, const int32_t* covered, int32_t J, int32_t P, uint8_t* dst_vis, int32_t* valid,
+                    int32_t* box_rows, void* stream);
+/* The same code on the CPU for HOST arrays (no GPU needed). */
+int fusg_later_gate_host(const int32_t* counts, const int32_t* covered, int32_t J, int32_t P, uint8_t* dst_vis, int32_t* valid,
+                         int32_t* box_rows);
+
 /* ---- EdgeConnect's inputs from a detector mask (create_inpaint_inputs_shape, utils/inpaint_utils.py:35-58; like the pose
  * geometry added without a version step: the entry points are new, nothing existing changed, and FUSG_VERSION 118 is what
  * the suite pins) ------------------------------------------------------------------------------------------------------ */

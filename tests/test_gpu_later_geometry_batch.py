@@ -1,0 +1,400 @@
+"""GPU: a geometry-mode clip's future frames as ONE batched, read-back-free pass (VehiclePipeline.run_later_frames_batched_geometry,
+render.later_geometry_batch_device, fusg_later_gate).  The device gate equals its host twin; the batched stage equals the
+per-frame device path (`_geometry_later_front`) byte for byte, with the vehicle whose render is empty kept as an inert row; the
+derived keys fed back as an explicit given-geometry batch of the same rows give the same bytes (the given-geometry batch is tied
+to the CPU oracle by tests/test_gpu_later_batch.py); one device-to-host copy per group."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from conftest import synth_sd                                              # noqa: E402
+from future_urban_scene_generation_amd import _lib as L                    # noqa: E402
+from future_urban_scene_generation_amd import ops                          # noqa: E402
+from future_urban_scene_generation_amd import pipeline as pl               # noqa: E402
+from future_urban_scene_generation_amd import render as R                  # noqa: E402
+from test_gpu_later_batch import _per_frame_stages                         # noqa: E402  (what `_later_local` builds for one frame)
+from test_later_gate_cpu import gate_cases, gate_host                      # noqa: E402
+
+DEV = "cuda:0"
+HW = (360, 640)
+KEYS = ("icn_u8", "vunet_u8", "geom", "frame_icn", "frame_vunet")
+F, V, INERT = 3, 3, (1, 1)                                                   # (frame, vehicle) moved behind the camera
+
+
+def _d(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+# ------------------------------------------------------------------------------------------------ 1. the gate kernel
+@pytest.mark.parametrize("boxes", [True, False], ids=["box_rows", "plain"])
+@pytest.mark.parametrize("J", [1, 64, 65, 200])
+def test_gate_equals_the_host_twin(J, boxes):
+    """One row; 64 and 65 rows (a block holds 8 rows of 8 slots: whole blocks, and one row into the next); 200 rows (25 blocks).
+    The rows are drawn from the CPU test's constructed counts so that ties, empty planes and covered = 0 rows all occur."""
+    lib = L.lib()
+    counts, covered = gate_cases()
+    pick = np.random.default_rng(J).permutation(len(counts))[:J]
+    counts, covered = np.ascontiguousarray(counts[pick]), np.ascontiguousarray(covered[pick])
+    if J > 1:
+        covered[:2] = (0, 5)
+    box = np.arange(1, J * 8 + 1, dtype=np.int32).reshape(J, 8) if boxes else None
+    for P in (5, 7):
+        want_vis, want_valid, want_box = gate_host(lib, counts, covered, P, box)
+        c_d, v_d = _d(counts), _d(covered)
+        vis = torch.full((J + 1, P), 9, dtype=torch.uint8, device=DEV)           # one row of guard behind each output
+        valid = torch.full((J + 1,), 9, dtype=torch.int32, device=DEV)
+        box_d = None if box is None else torch.cat([_d(box), torch.full((1, 8), 9, dtype=torch.int32, device=DEV)])
+        L.check(lib.fusg_later_gate(c_d.data_ptr(), v_d.data_ptr(), J, P, vis.data_ptr(), valid.data_ptr(),
+                                    None if box_d is None else box_d.data_ptr(), ops.stream_ptr()), "later_gate")
+        assert np.array_equal(vis[:J].cpu().numpy(), want_vis) and np.array_equal(valid[:J].cpu().numpy(), want_valid), (J, P)
+        assert (vis[J] == 9).all() and int(valid[J]) == 9
+        if boxes:
+            assert np.array_equal(box_d[:J].cpu().numpy(), want_box) and (box_d[J] == 9).all()
+            assert J == 1 or ((want_box[0] == 0).all() and (want_box[1] != 0).all())
+        if J >= 64:
+            assert want_vis.any() and not want_vis.all() and want_valid.any() and not want_valid.all()
+
+
+# ------------------------------------------------------------------------------------------------ the clip
+def _setup(n_vehicles, inpaint=False):
+    """tests/test_gpu_render.py's geometry-mode scene with the device paths on; with inpaint=True its bank and scene under a
+    pipeline that also holds the two EdgeConnect networks."""
+    from test_gpu_render import _geometry_setup
+    pipe, bank, scene = _geometry_setup(V=n_vehicles)
+    if inpaint:
+        sds = {n: synth_sd(n) for n in ("hg", "icn", "vunet", "edge", "inpaint")}
+        pipe = pl.VehiclePipeline(DEV, inpaint=True, state_dicts=sds, cad_bank=bank)
+    pipe.device_pose = pipe.device_homography = True
+    return pipe, bank, scene
+
+
+def _later_scenes(scene, first, frames, n_vehicles, inert):
+    """`frames` future frames along `trajectory_steps`, each on an image of its own; `inert` = (frame, vehicle) moved behind the
+    camera (the recipe of test_geometry_mode_run_frame_and_later_frames): that render is empty."""
+    steps = R.trajectory_steps(np.c_[np.arange(6.0) * 0.8, 0.05 * np.arange(6.0) ** 2])
+    E = [R.extrinsic_from_pose(p[1], p[2]) for p in first["pose"]]
+    later = []
+    for n in range(frames):
+        st = [steps[n]] * n_vehicles
+        if n == inert[0]:
+            st[inert[1]] = (steps[n][0], -200.0 * np.asarray(E[inert[1]][2, :3], np.float64))     # camera z axis in model coordinates
+        later.append({"frame": torch.roll(scene["frame"], shifts=37 * (n + 1), dims=1).contiguous(), "steps": st,
+                      "vehicle_seeds": [900 + 10 * n + v for v in range(n_vehicles)]})
+    return later
+
+
+def _explicit_scenes(later, got, first):
+    """The read-back 'geometry' of a batched result as explicit given-geometry scenes of the SAME rows: the inert vehicle stays
+    in as an empty-mask row with its dst_vis zeroed (what the device gate does to it)."""
+    g0 = first["geometry"]
+    out = []
+    for sc, res in zip(later, got):
+        g = res["geometry"]
+        vis = np.array(g["dst_vis"], np.uint8).copy()
+        vis[res["skipped"]] = 0
+        out.append({"frame": sc["frame"], "vehicle_seeds": sc["vehicle_seeds"], "masks": g["masks"], "dst_sketch": g["dst_sketch"],
+                    "dst_kp": g["dst_kp"], "dst_vis": vis, "src_planes": g0["src_planes"], "src_kp": g0["src_kp"], "src_vis": g0["src_vis"]})
+    return out
+
+
+def _kept(res, n_vehicles):
+    return [v for v in range(n_vehicles) if v not in res["skipped"]]
+
+
+def _same_as_explicit(got, ex, n_vehicles, tag, keys=("geom", "icn_u8", "vunet_u8")):
+    for f, (a, b) in enumerate(zip(got, ex)):
+        keep = torch.as_tensor(_kept(a, n_vehicles), device=DEV)
+        for k in keys:
+            assert a[k].shape[0] == len(keep) and torch.equal(a[k], b[k].index_select(0, keep)), (tag, f, k)
+        for k in ("frame_icn", "frame_vunet"):
+            assert torch.equal(a[k], b[k]), (tag, f, k)
+
+
+@pytest.fixture(scope="module")
+def env():
+    """One geometry-mode pipeline (device_pose and device_homography on), a first frame of 3 vehicles, its 3 future frames with
+    vehicle 1 of frame 1 behind the camera, and - computed once - the per-frame fronts, the batched result, the explicit scenes
+    built from it and their given-geometry batched result."""
+    pipe, bank, scene = _setup(V)
+    first = pipe.run_frame(scene)
+    assert first["skipped"] == [] and first["state"]["geometry"].get("pose_d") is not None
+    later = _later_scenes(scene, first, F, V, INERT)
+    state = first["state"]
+    fronts = [pipe._geometry_later_front(sc, state) for sc in later]
+    got = pipe.run_later_frames_batched_geometry(later, state)
+    explicit = _explicit_scenes(later, got, first)
+    sub = dict(state, geometry=None)
+    ex = pipe.run_later_frames_batched(explicit, sub)
+    return dict(pipe=pipe, bank=bank, scene=scene, first=first, later=later, state=state, fronts=fronts, got=got, explicit=explicit,
+                sub=sub, ex=ex)
+
+
+# ------------------------------------------------------------------------------------------------ 2. the stage
+def test_stage_equals_the_per_frame_path(env):
+    pipe, later, state, fronts = env["pipe"], env["later"], env["state"], env["fronts"]
+    geo = pipe._later_geometry_stage(later, state)
+    st = pipe._later_batch_stages(later, state, geo=geo)
+    host = geo["host"](ops.d2h(geo["buf"]))
+    assert tuple(geo["mask"].shape) == (F * V,) + HW and tuple(geo["sketch"].shape) == (F * V,) + HW + (3,)
+    assert tuple(st["icn_x"].shape) == (F * V, 21, 256, 256) and st["warped"].any()
+    gated, valid = geo["dst_vis_d"].cpu().numpy(), geo["valid_d"].cpu().numpy()
+    assert np.array_equal(valid, host["valid"]) and np.array_equal(host["status"], np.zeros(F * V, np.int32))
+    for f, fr in enumerate(fronts):
+        g, sl = fr["g"], pl.later_batch_slice(f, V)
+        assert fr["keep"] == [v for v in range(V) if (f, v) != INERT]
+        # every (f, v): the render, the corner points, the un-gated visibilities, the moved keypoints, the covered counts
+        assert torch.equal(geo["mask"][sl], g["masks"]) and torch.equal(geo["sketch"][sl], g["dst_sketch"]), f
+        assert np.array_equal(host["dst_vis"][sl], g["dst_vis"]) and host["dst_vis"].dtype == g["dst_vis"].dtype, f
+        assert np.array_equal(host["kp3d"][sl], g["kp3d"]) and host["kp3d"].dtype == g["kp3d"].dtype, f
+        assert np.array_equal(host["covered"][sl], g["covered"]), f
+        for v in range(V):
+            assert len(host["dst_kp"][sl][v]) == len(g["dst_kp"][v]) == 5
+            for a, b in zip(host["dst_kp"][sl][v], g["dst_kp"][v]):
+                assert a.dtype == b.dtype and np.array_equal(a, b), (f, v)
+        assert np.array_equal(valid[sl], (np.asarray(g["covered"]) > 0).astype(np.int32))
+        assert np.array_equal(gated[sl], np.asarray(g["dst_vis"]) * (np.asarray(g["covered"]) > 0)[:, None])
+        # every kept row: what `_later_local`'s stages build for that frame at batch "kept vehicles"
+        want = _per_frame_stages(pipe, fr["sub"], fr["sub_state"])
+        rows = torch.as_tensor([pl.later_batch_row(f, v, V) for v in fr["keep"]], device=DEV)
+        for k in ("warped", "geom", "icn_x", "vu_y"):
+            a = st[k].index_select(0, rows)
+            assert a.shape == want[k].shape and a.dtype == want[k].dtype and torch.equal(a, want[k]), (f, k)
+    # the inert row: nothing rendered, nothing gated in, nothing warped, an all-zero crop row
+    r = pl.later_batch_row(*INERT, V)
+    assert int(valid[r]) == 0 and int(host["covered"][r]) == 0 and not gated[r].any()
+    assert not geo["mask"][r].any() and not geo["sketch"][r].any() and not st["warped"][r].any() and not st["geom"][r].any()
+    assert valid.sum() == F * V - 1 and gated.any()
+
+
+def test_results_have_the_per_frame_shape(env):
+    """`run_later_frame`'s geometry-mode keys: the crops of the kept vehicles in order, 'geometry' of every vehicle, 'skipped'."""
+    pipe, got, fronts = env["pipe"], env["got"], env["fronts"]
+    assert isinstance(got, list) and len(got) == F
+    for f, (res, fr) in enumerate(zip(got, fronts)):
+        n = V - (1 if f == INERT[0] else 0)
+        assert set(res) == set(KEYS) | {"geometry", "skipped"}
+        assert res["skipped"] == ([INERT[1]] if f == INERT[0] else [])
+        assert res["skipped"] == pipe._geometry_later_assemble(fr, {})["skipped"]
+        assert tuple(res["icn_u8"].shape) == (n, 256, 256, 3) and tuple(res["vunet_u8"].shape) == (n, 256, 256, 3)
+        assert tuple(res["geom"].shape) == (n, 8) and tuple(res["frame_icn"].shape) == HW + (3,)
+        assert set(res["geometry"]) == {"masks", "dst_sketch", "dst_kp", "dst_vis", "kp3d"} == set(fr["geometry"])
+        assert torch.equal(res["geometry"]["masks"], fr["geometry"]["masks"]) and res["geometry"]["masks"].shape[0] == V
+        assert np.array_equal(res["geometry"]["dst_vis"], fr["geometry"]["dst_vis"])
+    assert not any(k[0] == "later_batch" for k in pipe._frame_plans)             # the eager form records nothing
+
+
+# ------------------------------------------------------------------------------------------------ 3. / 4. the explicit batch
+def test_derived_keys_fed_back_as_an_explicit_batch_give_the_same_bytes(env):
+    """The same rows at the same batch size through the given-geometry batched path: no tolerance."""
+    assert env["explicit"][INERT[0]]["dst_vis"][INERT[1]].sum() == 0 and not env["explicit"][INERT[0]]["masks"][INERT[1]].any()
+    assert all(tuple(e["icn_u8"].shape) == (V, 256, 256, 3) for e in env["ex"])
+    _same_as_explicit(env["got"], env["ex"], V, "explicit")
+    assert not torch.equal(env["got"][0]["frame_icn"], env["got"][1]["frame_icn"])
+
+
+def test_the_inert_row_is_harmless(env):
+    """The pass with the inert row leaves the status word clear (no fp32 redo), and no frame pixel outside the kept vehicles'
+    masks differs from the frame's base image."""
+    pipe, later, state = env["pipe"], env["later"], env["state"]
+    raised = []
+    orig = ops.range_exceeded
+    ops.range_exceeded = lambda *a, **k: (raised.append(orig(*a, **k)), raised[-1])[1]
+    try:
+        got = pipe.run_later_frames_batched_geometry(later, state)
+    finally:
+        ops.range_exceeded = orig
+    assert raised == [False]
+    assert not ops.range_exceeded(DEV) and not ops.range_exceeded(DEV, word=pipe.status_word())
+    for f, res in enumerate(got):
+        keep = torch.as_tensor(_kept(res, V), device=DEV)
+        cover = res["geometry"]["masks"].index_select(0, keep).max(0).values.bool()
+        assert cover.any() and not cover.all()
+        for k in ("frame_icn", "frame_vunet"):
+            assert torch.equal(res[k], env["got"][f][k]), (f, k)
+            assert torch.equal(res[k][~cover], later[f]["frame"][~cover]), (f, k)
+            assert not torch.equal(res[k][cover], later[f]["frame"][cover]), (f, k)
+
+
+# ------------------------------------------------------------------------------------------------ 5. replay
+def test_replay_equals_eager_and_shares_the_given_geometry_plan(env):
+    pipe, later, state = env["pipe"], env["later"], env["state"]
+    key = ("later_batch", F, V, ops.PRECISION)
+    assert not any(k[0] == "later_batch" for k in pipe._frame_plans)
+    r1 = pipe.run_later_frames_batched_geometry(later, state, replay=True)
+    assert [k for k in pipe._frame_plans if k[0] == "later_batch"] == [key]
+    plan = pipe._frame_plans[key]
+    r2 = pipe.run_later_frames_batched_geometry(later, state, replay=True)
+    ex = pipe.run_later_frames_batched(env["explicit"], env["sub"], replay=True)   # a given-geometry batch of the same shape
+    assert [k for k in pipe._frame_plans if k[0] == "later_batch"] == [key] and pipe._frame_plans[key] is plan
+    for f in range(F):
+        for k in KEYS:
+            assert torch.equal(r1[f][k], env["got"][f][k]) and torch.equal(r2[f][k], env["got"][f][k]), (f, k)
+        assert r1[f]["skipped"] == env["got"][f]["skipped"]
+    _same_as_explicit(env["got"], ex, V, "replayed explicit")
+    pipe._frame_plans.pop(key)
+
+
+# ------------------------------------------------------------------------------------------------ 6. chunking
+def test_chunked_groups_in_scene_order(env):
+    pipe, later, state = env["pipe"], env["later"], env["state"]
+    assert pl.later_batch_groups(F, V, 6) == [(0, 2), (2, 3)]
+    calls = []
+    orig = pipe._run_later_geometry_batch
+    pipe._run_later_geometry_batch = lambda scenes, st, replay=False: (calls.append(len(scenes)), orig(scenes, st, replay))[1]
+    try:
+        got = pipe.run_later_frames_batched_geometry(later, state, max_batch=6)
+    finally:
+        del pipe._run_later_geometry_batch
+    assert calls == [2, 1] and len(got) == F
+    ex = pipe.run_later_frames_batched(env["explicit"], env["sub"], max_batch=6)
+    _same_as_explicit(got, ex, V, "max_batch 6")
+    for f in range(F):
+        assert got[f]["skipped"] == env["got"][f]["skipped"]
+        assert torch.equal(got[f]["geometry"]["masks"], env["got"][f]["geometry"]["masks"])
+
+
+# ------------------------------------------------------------------------------------------------ 7. the read-back
+def test_one_read_back_per_group(env):
+    pipe, later, state = env["pipe"], env["later"], env["state"]
+    n = []
+    orig = ops.d2h
+    ops.d2h = lambda t: (n.append(int(t.numel())), orig(t))[1]
+    try:
+        pipe.run_later_frames_batched_geometry(later, state)
+        one = list(n)
+        del n[:]
+        pipe.run_later_frames_batched_geometry(later, state, max_batch=6)
+        two = list(n)
+        del n[:]
+        list(pipe.run_later_frames(later, state))
+        per_frame = list(n)
+    finally:
+        ops.d2h = orig
+    assert len(one) == 1 and len(two) == 2 and one[0] > two[0] > two[1]         # one per group, of its group's rows
+    assert len(per_frame) == F                                                  # the frame-by-frame path: one blocking copy per frame
+
+
+# ------------------------------------------------------------------------------------------------ 8. the range guard
+def test_range_guard_redoes_the_group_in_fp32(env):
+    """An appearance code outside the split-fp16 range: the status word is raised once, and the results are those of an
+    exact-fp32 run of the same batch, bit for bit (tests/test_gpu_later_batch.py's test of the given-geometry batch)."""
+    pipe, later = env["pipe"], env["later"]
+    hot = dict(env["state"])
+    hot["appearance"] = [t.clone() for t in env["state"]["appearance"]]
+    hot["appearance"][1][0, 0, 0, 0] = 6e4
+    with ops.precision("f32"):
+        f32 = pipe.run_later_frames_batched_geometry(later, hot, check=None)
+    raised = []
+    orig = ops.range_exceeded
+    ops.range_exceeded = lambda *a, **k: (raised.append(orig(*a, **k)), raised[-1])[1]
+    try:
+        got = pipe.run_later_frames_batched_geometry(later, hot)
+    finally:
+        ops.range_exceeded = orig
+    assert raised == [True]                                                       # one status word, read once, for the whole group
+    for f in range(F):
+        assert got[f]["skipped"] == f32[f]["skipped"]
+        for k in KEYS:
+            assert torch.equal(got[f][k], f32[f][k]), (f, k)
+    assert any(not torch.equal(got[f]["vunet_u8"], env["got"][f]["vunet_u8"]) for f in range(F))
+    assert not ops.range_exceeded(DEV) and not ops.range_exceeded(DEV, word=pipe.status_word())
+
+
+# ------------------------------------------------------------------------------------------------ 9. the clip driver
+def test_run_clip_frames(env):
+    pipe, scene, later = env["pipe"], env["scene"], env["later"]
+    clip = list(pipe.run_clip_frames(scene, later, batched=True, batch_geometry=True))
+    assert len(clip) == 1 + F
+    for k in ("kp_idx", "icn_u8", "vunet_u8", "frame_icn", "frame_vunet"):
+        assert torch.equal(clip[0][k], env["first"][k]), k
+    for f in range(F):
+        assert clip[1 + f]["skipped"] == env["got"][f]["skipped"]
+        for k in KEYS:
+            assert torch.equal(clip[1 + f][k], env["got"][f][k]), (f, k)
+    plain = list(pipe.run_clip_frames(scene, later, batched=True))               # batch_geometry=False: the fallback, unchanged
+    want = list(pipe.run_later_frames(later, env["state"]))
+    for f in range(F):
+        assert plain[1 + f]["skipped"] == want[f]["skipped"]
+        for k in KEYS:
+            assert torch.equal(plain[1 + f][k], want[f][k]), (f, k)
+    flagged = pipe.run_later_frames_batched_geometry(later, env["state"], batch_geometry=False)
+    for f in range(F):
+        for k in KEYS:
+            assert torch.equal(flagged[f][k], want[f][k]), (f, k)
+
+
+def test_a_state_without_device_copies_uploads_its_host_pose(env):
+    """A state made without device_pose holds host poses and corner points only: uploaded once, the same bytes."""
+    pipe, later = env["pipe"], env["later"]
+    gs = {k: v for k, v in env["state"]["geometry"].items() if k not in ("pose_d", "cad_idx_d", "src_kp_d", "kp_nv_d")}
+    got = pipe.run_later_frames_batched_geometry(later, dict(env["state"], geometry=gs))
+    for f in range(F):
+        assert got[f]["skipped"] == env["got"][f]["skipped"]
+        for k in KEYS:
+            assert torch.equal(got[f][k], env["got"][f][k]), (f, k)
+
+
+# ------------------------------------------------------------------------------------------------ 10. inpainting
+def test_inpainted_geometry_batch():
+    """2 vehicles, 2 frames, 'box_masks', vehicle 1 of frame 1 inert: frames and the kept rows' merged boxes equal the explicit
+    batched path with the inert row's box set to (0, 0, 0, 0); the inert vehicle's real box keeps the frame's pixels."""
+    nv, nf, inert = 2, 2, (1, 1)
+    pipe, bank, scene = _setup(nv, inpaint=True)
+    H, W = HW
+    boxes0 = np.asarray(pl.synth_inpaint_boxes(np.asarray(scene["bboxes"]).tolist(), HW), np.int64)
+
+    def inpaint_of(boxes):
+        planes = torch.zeros((len(boxes), 1, H, W), dtype=torch.uint8)
+        for v, (x0, y0, x1, y1) in enumerate(boxes):                            # a stand-in detection: the middle of the box
+            planes[v, 0, y0 + (y1 - y0) // 4:y1 - (y1 - y0) // 4, x0 + (x1 - x0) // 4:x1 - (x1 - x0) // 4] = 255
+        return {"boxes": boxes, "box_masks": [m.to(DEV) for m in pl.synth_box_masks(planes, boxes)]}
+
+    first = pipe.run_frame(dict(scene, inpaint=inpaint_of(boxes0)))
+    assert first["skipped"] == []
+    later = _later_scenes(scene, first, nf, nv, inert)
+    boxes = [boxes0 + np.array([2 * n + 1, n, 2 * n + 1, n]) * (boxes0[:, 2:3] < W - 8) for n in range(nf)]
+    for sc, b in zip(later, boxes):
+        sc["inpaint"] = inpaint_of(b)
+    state = first["state"]
+    got = pipe.run_later_frames_batched_geometry(later, state)
+    assert [g["skipped"] for g in got] == [[], [inert[1]]]
+    explicit = _explicit_scenes(later, got, first)
+    for f, (e, sc) in enumerate(zip(explicit, later)):
+        b, pieces = boxes[f].copy(), list(sc["inpaint"]["box_masks"])
+        if f == inert[0]:                                                        # the gate's doing, by hand
+            b[inert[1]] = 0
+            pieces[inert[1]] = torch.zeros((0, 0), dtype=torch.uint8, device=DEV)
+        e["inpaint"] = {"boxes": b, "box_masks": pieces}
+    ex = pipe.run_later_frames_batched(explicit, dict(state, geometry=None))
+    _same_as_explicit(got, ex, nv, "inpaint", keys=("geom", "icn_u8", "vunet_u8", "inpaint_u8"))
+    # the inert vehicle's real box, outside the other vehicle's mask and box, keeps the frame's pixels; a kept box does not
+    f, v = inert
+    x0, y0, x1, y1 = boxes[f][v]
+    free = torch.zeros((H, W), dtype=torch.bool, device=DEV)
+    free[y0:y1, x0:x1] = True
+    assert free.any()
+    for o in _kept(got[f], nv):
+        free[boxes[f][o][1]:boxes[f][o][3], boxes[f][o][0]:boxes[f][o][2]] = False
+        free &= ~got[f]["geometry"]["masks"][o].bool()
+    assert free.any()
+    for k in ("frame_icn", "frame_vunet"):
+        assert torch.equal(got[f][k][free], later[f]["frame"][free]), k
+    x0, y0, x1, y1 = boxes[0][1]
+    assert not torch.equal(got[0]["frame_icn"][y0:y1, x0:x1], later[0]["frame"][y0:y1, x0:x1])
+    # the same frames through the per-frame driver's rule: "a skipped vehicle is not inpainted"
+    per = pipe.run_later_frame(later[f], state)
+    assert per["skipped"] == got[f]["skipped"] and torch.equal(per["frame_icn"][free], got[f]["frame_icn"][free])
+    rep = pipe.run_later_frames_batched_geometry(later, state, replay=True)
+    assert ("later_batch", nf, nv, ops.PRECISION, "inpaint") in pipe._frame_plans
+    for f in range(nf):
+        for k in KEYS + ("inpaint_u8",):
+            assert torch.equal(rep[f][k], got[f][k]), (f, k)
