@@ -74,6 +74,7 @@ PRE_NONE, PRE_RELU, PRE_ELU, PRE_AFFINE_RELU, PRE_AFFINE = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_TANH01 = 0, 1, 2, 3, 4
 STORE_NORMAL, STORE_D2S, STORE_S2D = 0, 1, 2
 PREC_F32, PREC_F16X3, PREC_EMU_BF16, PREC_EMU_BF16X2, PREC_BF16 = 0, 1, 2, 3, 4
+MAX_FRAMES = 64                         # FUSG_MAX_FRAMES: frames per launch of the frame-indexed glue
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_128x32, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4, 5
 
 _TP = C.POINTER(Tensor)
@@ -114,6 +115,10 @@ _SIGS = {
     "fusg_crop_resize_u8": (C.c_int, [_TP, C.c_void_p, _TP, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fusg_vunet_inputs": (C.c_int, [_TP, _TP, _TP, _TP, C.c_void_p, _TP, _TP, C.c_void_p]),
     "fusg_mask_bbox_geom": (C.c_int, [_TP, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fusg_crop_resize_frames_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, _TP, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fusg_vunet_inputs_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _TP, _TP, _TP, C.c_void_p, _TP, _TP, C.c_void_p]),
+    "fusg_paste_layers_ragged_u8": (C.c_int, [_TP, _TP, C.c_void_p, _TP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _TP, C.c_void_p]),
     "fusg_keypoints_to_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "fusg_pnp_cpc": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p] * 4),
     "fusg_render_normals_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,

@@ -580,6 +580,82 @@ __global__ __launch_bounds__(256) void keypoints_to_frame_kernel(const int* idx,
     out[2 * i + 1] = (float)(fy * (double)(g[3] - g[1]) + (double)g[1] - (double)g[5]);
 }
 
+// ------------------------------------------------------------------------------------------------ frame-indexed glue
+// The three kernels above that read the frame, with the frame a property of the ROW (VehiclePipeline.run_frames_batched: the
+// first frames of several scenes as one pass).  FrameTab travels BY VALUE in the kernel arguments (~0.8 KB): the host has
+// checked every entry before the launch, which it could not do for a table in device memory.  Rows [rows[f], rows[f + 1]) read
+// image img[f] (dense u8 [H, W, 3]).  blockIdx.y = the row (the frame, for the paste), so the lookup is uniform per block; the
+// per-pixel arithmetic is the device functions of the one-frame kernels, so the bytes are theirs by construction.
+struct FrameTab { const unsigned char* img[FUSG_MAX_FRAMES]; int rows[FUSG_MAX_FRAMES + 1]; int n; };
+__device__ __forceinline__ int frame_of_row(const FrameTab& t, int row) {
+    int f = 0;
+    while (f + 1 < t.n && row >= t.rows[f + 1]) ++f;
+    return f;
+}
+
+__global__ __launch_bounds__(256) void crop_resize_frames_kernel(CropIn a, FrameTab t, long per_row) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= per_row) return;
+    const int v = blockIdx.y;
+    const int x = (int)(idx % a.out_w), y = (int)(idx / a.out_w);
+    const unsigned char* img = t.img[frame_of_row(t, v)];
+    const U8View& sv = a.src;                                          // the frames' common shape and dense strides
+    int rgb[3];
+    crop_resize_px(a.geom + v * 8, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(img, sv, px, py, c); }, rgb);
+    if (a.mode == 0) {
+        unsigned char* d = a.dst8.p + (long)v * a.dst8.sn + (long)y * a.dst8.sh + (long)x * a.dst8.sw;
+        d[0] = (unsigned char)rgb[0]; d[1] = (unsigned char)rgb[1]; d[2] = (unsigned char)rgb[2];
+        return;
+    }
+    float* d = a.dstf + (long)v * a.dsn + (long)y * a.dsh + (long)x * a.dsw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float f = (float)rgb[c] / 255.f;
+        d[c] = a.mode == 1 ? (f - a.mean[c]) / a.stdv[c] : f * 2.f - 1.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void vunet_inputs_frames_kernel(VuIn a, FrameTab t, long per_row) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= per_row) return;
+    const int v = blockIdx.y;
+    const int x = (int)(idx % a.out_w), y = (int)(idx / a.out_w);
+    const unsigned char* fr = t.img[frame_of_row(t, v)];
+    const int* g = a.geom + v * 8;
+    const unsigned char* mk = a.mask.p + (long)v * a.mask.sn;
+    const unsigned char* s1 = a.ssk.p + (long)v * a.ssk.sn;
+    const unsigned char* s2 = a.dsk.p + (long)v * a.dsk.sn;
+    int mf[3], ss[3], ds[3];
+    crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) {
+        if (!((unsigned)px < (unsigned)a.frame.w && (unsigned)py < (unsigned)a.frame.h)) return 0;
+        return mk[(long)py * a.mask.sh + (long)px * a.mask.sw] ? (int)fr[(long)py * a.frame.sh + (long)px * a.frame.sw + c] : 0;
+    }, mf);
+    crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(s1, a.ssk, px, py, c); }, ss);
+    crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(s2, a.dsk, px, py, c); }, ds);
+    if ((ss[0] | ss[1] | ss[2]) == 0) mf[0] = mf[1] = mf[2] = 255;
+    float* dx = a.x + (long)v * a.xsn + (long)y * a.xsh + (long)x * a.xsw;
+    float* dy = a.y + (long)v * a.ysn + (long)y * a.ysh + (long)x * a.ysw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        dx[c] = (float)mf[c] / 255.f * 2.f - 1.f;
+        dx[3 + c] = (float)ss[2 - c] / 255.f * 2.f - 1.f;
+        dy[c] = (float)ds[2 - c] / 255.f * 2.f - 1.f;
+    }
+}
+
+// blockIdx.y = frame f, whose layers are rows t.rows[f] .. t.rows[f + 1] - 1 (none: the frame is a copy of its base t.img[f])
+__global__ __launch_bounds__(256) void paste_ragged_kernel(PasteIn a, FrameTab t, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int f = blockIdx.y;
+    const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
+    unsigned char* d = a.frame.p + (long)f * a.frame.sn + (long)y * a.frame.sh + (long)x * a.frame.sw;
+    a.V = t.rows[f + 1] - t.rows[f];
+    if (paste_layers_px(a, t.rows[f], x, y, d)) return;
+    const unsigned char* b = t.img[f] + idx * 3;
+    d[0] = b[0]; d[1] = b[1]; d[2] = b[2];
+}
+
 }  // namespace fusg
 
 using namespace fusg;
@@ -809,4 +885,133 @@ static int keypoints_to_frame_impl(const int32_t* idx, const int32_t* geom, floa
 }
 extern "C" int fusg_keypoints_to_frame(const int32_t* idx, const int32_t* geom, float* out, int32_t vehicles, int32_t nkp, int32_t hm_w, int32_t hm_h, void* stream) {
     return fusg::plan_dispatch(keypoints_to_frame_impl, stream, idx, geom, out, vehicles, nkp, hm_w, hm_h);
+}
+
+// ---- frame-indexed glue: host side.  Both tables are HOST arrays, read (and checked) here, before anything is launched.
+static int frame_table(const char* what, const void* const* frames, const int32_t* frame_rows, int32_t n_frames, long rows, FrameTab& t) {
+    FUSG_CHECK(n_frames >= 1 && n_frames <= FUSG_MAX_FRAMES, "%s: n_frames = %d (1..%d)", what, n_frames, FUSG_MAX_FRAMES);
+    FUSG_CHECK(frames && frame_rows, "%s: a table is null (frames, frame_rows)", what);
+    memset(&t, 0, sizeof(t));
+    t.n = n_frames;
+    FUSG_CHECK(frame_rows[0] == 0, "%s: the row offsets start at %d, not at 0", what, frame_rows[0]);
+    for (int f = 0; f < n_frames; ++f) {
+        FUSG_CHECK(frames[f] != nullptr, "%s: frame %d is a null pointer", what, f);
+        FUSG_CHECK(frame_rows[f + 1] >= frame_rows[f], "%s: the row offsets decrease at frame %d (%d after %d)", what, f, frame_rows[f + 1],
+                   frame_rows[f]);
+        t.img[f] = (const unsigned char*)frames[f];
+        t.rows[f] = frame_rows[f];
+    }
+    t.rows[n_frames] = frame_rows[n_frames];
+    FUSG_CHECK((long)frame_rows[n_frames] == rows, "%s: the row offsets end at %d, the tensors hold %ld rows", what, frame_rows[n_frames], rows);
+    FUSG_CHECK(rows <= 65535, "%s: %ld rows (at most 65535 per launch)", what, rows);
+    return FUSG_OK;
+}
+
+static int crop_resize_frames_impl(FrameTab t, int32_t H, int32_t W, const int32_t* geom, const fusg_tensor* dst, int32_t mode, Norm3 nm,
+                                   void* stream) {
+    CropIn a;
+    memset(&a, 0, sizeof(a));
+    a.src = U8View{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
+    a.geom = geom; a.V = (int)dst->n; a.out_h = (int)dst->h; a.out_w = (int)dst->w; a.mode = mode;
+    if (mode == 0) a.dst8 = u8view(*dst);
+    else {
+        a.dstf = (float*)dst->data; a.dsn = dst->sn; a.dsh = dst->sh; a.dsw = dst->sw;
+        for (int c = 0; c < 3; ++c) { a.mean[c] = nm.m[c]; a.stdv[c] = nm.s[c]; }
+    }
+    const long per_row = (long)a.out_h * a.out_w;
+    hipLaunchKernelGGL(crop_resize_frames_kernel, dim3(blocks2d(per_row), (unsigned)a.V), dim3(256), 0, (hipStream_t)stream, a, t, per_row);
+    FUSG_LAUNCH_CHECK("crop_resize_frames_u8");
+    return FUSG_OK;
+}
+extern "C" int fusg_crop_resize_frames_u8(const void* const* frames, const int32_t* frame_rows, int32_t n_frames, int32_t H, int32_t W,
+                                          const int32_t* geom, const fusg_tensor* dst, int32_t mode, const float* mean3, const float* std3,
+                                          void* stream) {
+    const char* what = "crop_resize_frames_u8";
+    FUSG_CHECK(dst && dst->n >= 0, "%s: dst is null", what);
+    FrameTab t;
+    if (int rc = frame_table(what, frames, frame_rows, n_frames, dst->n, t)) return rc;
+    FUSG_CHECK(H >= 1 && W >= 1 && H < 32768 && W < 32768, "%s: frames of %d x %d", what, H, W);
+    FUSG_CHECK(mode >= 0 && mode <= 2, "%s: mode %d (0..2)", what, mode);
+    if (dst->n == 0) return FUSG_OK;
+    FUSG_CHECK(geom != nullptr && dst->h >= 1 && dst->w >= 1, "%s: geom is null or dst is empty", what);
+    Norm3 nm = {{0, 0, 0}, {1, 1, 1}, (mean3 && std3) ? 1 : 0};
+    if (mode == 0) FUSG_CHECK(is_u8_hwc(*dst, 3), "%s: mode 0 needs a u8 HWC destination", what);
+    else FUSG_CHECK(is_nhwc(*dst) && dst->c == 3, "%s: modes 1 / 2 need an NHWC-physical f32 destination of 3 channels", what);
+    if (mode == 1) {
+        FUSG_CHECK(nm.has, "%s: mode 1 needs mean / std (host arrays of 3)", what);
+        for (int c = 0; c < 3; ++c) { nm.m[c] = mean3[c]; nm.s[c] = std3[c]; }
+    }
+    for (int f = 0; f < n_frames; ++f) FUSG_CHECK(frames[f] != dst->data, "%s: not in place", what);
+    return fusg::plan_dispatch(crop_resize_frames_impl, stream, t, H, W, geom, dst, mode, nm);
+}
+
+static int vunet_inputs_frames_impl(FrameTab t, const fusg_tensor* masks, const fusg_tensor* src_sketch, const fusg_tensor* dst_sketch,
+                                    const int32_t* geom, const fusg_tensor* x, const fusg_tensor* y, void* stream) {
+    VuIn a;
+    const int H = (int)masks->h, W = (int)masks->w;
+    a.frame = U8View{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
+    a.ssk = u8view(*src_sketch); a.dsk = u8view(*dst_sketch);
+    a.mask = U8View{(unsigned char*)masks->data, masks->sn, masks->sh, masks->sw, (int)masks->n, H, W};
+    a.geom = geom; a.x = (float*)x->data; a.xsn = x->sn; a.xsh = x->sh; a.xsw = x->sw;
+    a.y = (float*)y->data; a.ysn = y->sn; a.ysh = y->sh; a.ysw = y->sw;
+    a.V = (int)masks->n; a.out_h = (int)x->h; a.out_w = (int)x->w;
+    const long per_row = (long)a.out_h * a.out_w;
+    hipLaunchKernelGGL(vunet_inputs_frames_kernel, dim3(blocks2d(per_row), (unsigned)a.V), dim3(256), 0, (hipStream_t)stream, a, t, per_row);
+    FUSG_LAUNCH_CHECK("vunet_inputs_frames");
+    return FUSG_OK;
+}
+extern "C" int fusg_vunet_inputs_frames(const void* const* frames, const int32_t* frame_rows, int32_t n_frames, const fusg_tensor* masks,
+                                        const fusg_tensor* src_sketch, const fusg_tensor* dst_sketch, const int32_t* geom,
+                                        const fusg_tensor* x, const fusg_tensor* y, void* stream) {
+    const char* what = "vunet_inputs_frames";
+    FUSG_CHECK(masks && src_sketch && dst_sketch && x && y && masks->n >= 0, "%s: a tensor is null", what);
+    FrameTab t;
+    if (int rc = frame_table(what, frames, frame_rows, n_frames, masks->n, t)) return rc;
+    FUSG_CHECK(src_sketch->n == masks->n && dst_sketch->n == masks->n && x->n == masks->n && y->n == masks->n,
+               "%s: %ld masks, %ld / %ld sketches, %ld / %ld outputs: the row counts differ", what, (long)masks->n, (long)src_sketch->n,
+               (long)dst_sketch->n, (long)x->n, (long)y->n);
+    if (masks->n == 0) return FUSG_OK;
+    FUSG_CHECK(geom != nullptr, "%s: geom is null", what);
+    FUSG_CHECK(is_u8_hwc(*src_sketch, 3) && is_u8_hwc(*dst_sketch, 3) && masks->data && masks->dtype == FUSG_U8 && masks->c == 1 &&
+               masks->h >= 1 && masks->w >= 1 && masks->h < 32768 && masks->w < 32768 && src_sketch->h == masks->h && src_sketch->w == masks->w &&
+               dst_sketch->h == masks->h && dst_sketch->w == masks->w, "%s: masks [rows, 1, H, W] u8 and sketches [rows] of the frames' size", what);
+    FUSG_CHECK(is_nhwc(*x) && is_nhwc(*y) && x->c == 6 && y->c == 3 && x->h == y->h && x->w == y->w,
+               "%s: x [rows, 6, h, w] and y [rows, 3, h, w] NHWC-physical f32", what);
+    return fusg::plan_dispatch(vunet_inputs_frames_impl, stream, t, masks, src_sketch, dst_sketch, geom, x, y);
+}
+
+static int paste_layers_ragged_u8_impl(FrameTab t, const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
+                                       const int32_t* rect_geom, const fusg_tensor* dst, void* stream) {
+    PasteIn a;
+    memset(&a, 0, sizeof(a));
+    a.frame = u8view(*dst); a.geom = geom;
+    if (t.rows[t.n] > 0) { a.net = u8view(*net); a.masks = u8view(*masks); }
+    if (rect && t.rows[t.n] > 0) { a.rect = u8view(*rect); a.rgeom = rect_geom; }
+    const long total = dst->h * dst->w;
+    hipLaunchKernelGGL(paste_ragged_kernel, dim3(blocks2d(total), (unsigned)t.n), dim3(256), 0, (hipStream_t)stream, a, t, total);
+    FUSG_LAUNCH_CHECK("paste_layers_ragged_u8");
+    return FUSG_OK;
+}
+extern "C" int fusg_paste_layers_ragged_u8(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
+                                           const int32_t* rect_geom, const void* const* bases, const int32_t* frame_rows, int32_t n_frames,
+                                           const fusg_tensor* dst, void* stream) {
+    const char* what = "paste_layers_ragged_u8";
+    FUSG_CHECK(net && masks && dst && net->n >= 0, "%s: a tensor is null", what);
+    FrameTab t;
+    if (int rc = frame_table(what, bases, frame_rows, n_frames, net->n, t)) return rc;
+    FUSG_CHECK(masks->n == net->n, "%s: %ld crops and %ld masks: the row counts differ", what, (long)net->n, (long)masks->n);
+    FUSG_CHECK((rect == nullptr) == (rect_geom == nullptr) && (!rect || rect->n == net->n),
+               "%s: the box images come with their rectangles, one per crop", what);
+    FUSG_CHECK(is_u8_hwc(*dst, 3) && dst->n == n_frames && dst->sw == 3 && dst->sh == 3 * dst->w, "%s: dst u8 [n_frames, H, W, 3], dense rows", what);
+    if (net->n > 0) {
+        FUSG_CHECK(geom != nullptr, "%s: geom is null", what);
+        FUSG_CHECK(is_u8_hwc(*net, 3) && masks->data && masks->dtype == FUSG_U8 && masks->c == 1 && masks->h == dst->h && masks->w == dst->w &&
+                   (!rect || is_u8_hwc(*rect, 3)), "%s: shapes (crops u8 HWC, masks [rows, 1, H, W] u8 of the frames' size)", what);
+    }
+    for (int f = 0; f < n_frames; ++f) {
+        const unsigned char* b = (const unsigned char*)bases[f];
+        const unsigned char* d0 = (const unsigned char*)dst->data;
+        FUSG_CHECK(b + 3 * dst->h * dst->w <= d0 || b >= d0 + dst->n * dst->sn, "%s: base %d overlaps dst (the bases are read only)", what, f);
+    }
+    return fusg::plan_dispatch(paste_layers_ragged_u8_impl, stream, t, net, masks, geom, rect, rect_geom, dst);
 }

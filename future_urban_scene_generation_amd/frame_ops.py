@@ -2,7 +2,8 @@
 frame and the networks in ``trajectory_inference.py:55-79, 200-228`` - box crops, the hourglass / CAD input, the central
 crop, the VUnet's inputs, mask bounding boxes and the keypoint coordinates the pose fit reads.  Thin wrappers over
 ``csrc/cvops.hip`` (``fusg_crop_resize_u8``, ``fusg_vunet_inputs``, ``fusg_mask_bbox_geom``,
-``fusg_keypoints_to_frame``); the resize is OpenCV's 8-bit INTER_LINEAR like the other uint8 steps (parity with OpenCV
+``fusg_keypoints_to_frame``, and the frame-indexed ``fusg_crop_resize_frames_u8`` / ``fusg_vunet_inputs_frames`` of
+``run_frames_batched``); the resize is OpenCV's 8-bit INTER_LINEAR like the other uint8 steps (parity with OpenCV
 itself unpinned, oracle/cv_host.py)."""
 from __future__ import annotations
 
@@ -102,6 +103,72 @@ def vunet_inputs(frame: torch.Tensor, masks: torch.Tensor, src_sketch: torch.Ten
         L.check(L.lib().fusg_vunet_inputs(C.byref(_u8desc(frame.contiguous()[None])), C.byref(ops.desc(masks.contiguous().view(V, 1, H, W))),
                                           C.byref(_u8desc(src_sketch.contiguous())), C.byref(_u8desc(dst_sketch.contiguous())),
                                           geom.data_ptr(), C.byref(ops.desc(x)), C.byref(ops.desc(y)), ops.stream_ptr()), "vunet_inputs")
+    return x, y
+
+
+def _frame_table(frames: Sequence[torch.Tensor], frame_rows: Sequence[int], rows: int, what: str):
+    """The two HOST tables of the frame-indexed kernels: (pointers of the F dense uint8 [H, W, 3] images, the F + 1 row offsets,
+    the contiguous images - referenced until the launch is queued -, (H, W)).  The library checks the tables' contents; this
+    checks what it cannot see: that every image really is uint8 [H, W, 3] of ONE size on one device."""
+    keep = [f.contiguous() for f in frames]
+    if not keep or len(keep) > L.MAX_FRAMES:
+        raise ValueError(f"{what}: {len(keep)} frames (1..{L.MAX_FRAMES} per launch)")
+    H, W = int(keep[0].shape[0]), int(keep[0].shape[1])
+    for f in keep:
+        ops._require_gpu(f, "frame")
+        if f.dtype != torch.uint8 or tuple(f.shape) != (H, W, 3) or f.device != keep[0].device:
+            raise ValueError(f"{what}: every frame is uint8 {(H, W, 3)} on {keep[0].device}, got {f.dtype} {tuple(f.shape)} on {f.device}")
+    offs = [int(r) for r in frame_rows]
+    if len(offs) != len(keep) + 1:
+        raise ValueError(f"{what}: {len(offs)} row offsets for {len(keep)} frames (one more than frames)")
+    ptrs = (C.c_void_p * len(keep))(*[f.data_ptr() for f in keep])
+    return ptrs, (C.c_int32 * len(offs))(*offs), keep, (H, W)
+
+
+def crop_resize_frames(frames: Sequence[torch.Tensor], frame_rows: Sequence[int], geom: torch.Tensor, out_hw: Tuple[int, int],
+                       mode: int = 0, mean: Optional[Sequence[float]] = None, std: Optional[Sequence[float]] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`crop_resize` for windows cut from F different images in ONE launch (fusg_crop_resize_frames_u8): frames = F CUDA uint8
+    [H, W, 3] images of one size; frame_rows = F + 1 host offsets, rows [frame_rows[f], frame_rows[f + 1]) of geom (int32
+    [rows, 8]) are windows of frame f.  Modes and `out` as in `crop_resize`; the bytes are those of F calls of it."""
+    rows = int(geom.shape[0])
+    ptrs, offs, keep, (H, W) = _frame_table(frames, frame_rows, rows, "crop_resize_frames")
+    assert geom.dtype == torch.int32 and geom.is_contiguous()
+    h, w = out_hw
+    dev = keep[0].device
+    with torch.cuda.device(dev):
+        if mode == 0:
+            out = torch.empty((rows, h, w, 3), dtype=torch.uint8, device=dev)
+            d = _u8desc(out)
+        else:
+            out = _into(out, rows, 3, h, w, dev)
+            d = ops.desc(out)
+        m = (C.c_float * 3)(*(mean if mean is not None else (0, 0, 0)))
+        s = (C.c_float * 3)(*(std if std is not None else (1, 1, 1)))
+        L.check(L.lib().fusg_crop_resize_frames_u8(ptrs, offs, len(keep), H, W, geom.data_ptr(), C.byref(d), int(mode),
+                                                   C.cast(m, C.c_void_p) if mean is not None else None,
+                                                   C.cast(s, C.c_void_p) if std is not None else None, ops.stream_ptr()),
+                "crop_resize_frames_u8")
+    return out
+
+
+def vunet_inputs_frames(frames: Sequence[torch.Tensor], frame_rows: Sequence[int], masks: torch.Tensor, src_sketch: torch.Tensor,
+                        dst_sketch: torch.Tensor, geom: torch.Tensor, res: int = 256,
+                        out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`vunet_inputs` for vehicles of F different frames in ONE launch (fusg_vunet_inputs_frames): rows [frame_rows[f],
+    frame_rows[f + 1]) of masks / sketches / geom belong to frames[f]."""
+    rows, H, W = masks.shape
+    ptrs, offs, keep, hw = _frame_table(frames, frame_rows, rows, "vunet_inputs_frames")
+    if hw != (H, W):
+        raise ValueError(f"vunet_inputs_frames: frames of {hw}, masks of {(H, W)}")
+    dev = keep[0].device
+    x = _into(out[0] if out else None, rows, 6, res, res, dev)
+    y = _into(out[1] if out else None, rows, 3, res, res, dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().fusg_vunet_inputs_frames(ptrs, offs, len(keep), C.byref(ops.desc(masks.contiguous().view(rows, 1, H, W))),
+                                                 C.byref(_u8desc(src_sketch.contiguous())), C.byref(_u8desc(dst_sketch.contiguous())),
+                                                 geom.data_ptr(), C.byref(ops.desc(x)), C.byref(ops.desc(y)), ops.stream_ptr()),
+                "vunet_inputs_frames")
     return x, y
 
 

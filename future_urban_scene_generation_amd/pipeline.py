@@ -204,6 +204,80 @@ def later_batch_seeds(seeds_per_frame: Sequence[Optional[Sequence[int]]], V: int
     return out
 
 
+# ---- `run_frames_batched`: the scene-major bookkeeping of a pass over the first frames of several scenes (pure Python)
+FRAME_BATCH_MAX_FRAMES = 64   # scenes per group: what one launch of the frame-indexed glue kernels takes (fusg.h FUSG_MAX_FRAMES)
+
+
+def frame_batch_groups(counts: Sequence[int], max_batch: Optional[int] = None,
+                       max_frames: int = FRAME_BATCH_MAX_FRAMES) -> List[Tuple[int, int]]:
+    """The passes of len(counts) scenes with counts[f] vehicles each: consecutive groups [lo, hi) packed greedily - a group is
+    closed when the next scene would push it over max_batch rows or over max_frames scenes.  A scene with more than max_batch
+    vehicles is a group of its own; every scene appears exactly once, in order.  max_batch None: LATER_MAX_BATCH."""
+    if max_batch is None:
+        max_batch = LATER_MAX_BATCH
+    if int(max_batch) < 1:
+        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
+    if int(max_frames) < 1:
+        raise ValueError(f"max_frames must be at least 1, got {max_frames}")
+    groups: List[Tuple[int, int]] = []
+    lo, rows = 0, 0
+    for f, c in enumerate(counts):
+        c = int(c)
+        if c < 0:
+            raise ValueError(f"scene {f} has {c} vehicles")
+        if f > lo and (rows + c > int(max_batch) or f - lo >= int(max_frames)):
+            groups.append((lo, f))
+            lo, rows = f, 0
+        rows += c
+    if len(counts) > lo:
+        groups.append((lo, len(counts)))
+    return groups
+
+
+def frame_batch_offsets(counts: Sequence[int]) -> List[int]:
+    """Row offsets of a group, scene-major: scene f's vehicles are rows offsets[f] .. offsets[f + 1] (len(counts) + 1 entries)."""
+    offs = [0]
+    for c in counts:
+        offs.append(offs[-1] + int(c))
+    return offs
+
+
+def frame_batch_pad(rows: int, max_batch: Optional[int] = None) -> int:
+    """The row count a group of `rows` vehicles is padded to for a recorded pass: the next of 4, 8, 16, 32, 64, ..., capped at
+    max_batch (default LATER_MAX_BATCH) - at most five shapes for the default, whatever the vehicle counts of a video.  A group
+    that already exceeds max_batch (one scene with more vehicles) keeps its own count; 0 stays 0."""
+    if max_batch is None:
+        max_batch = LATER_MAX_BATCH
+    rows, max_batch = int(rows), int(max_batch)
+    if rows <= 0:
+        return 0
+    if rows > max_batch:
+        return rows
+    p = 4
+    while p < rows:
+        p *= 2
+    return min(p, max_batch)
+
+
+def frame_batch_seeds(seeds_per_scene: Sequence[Optional[Sequence[int]]], counts: Sequence[int]) -> Optional[List[int]]:
+    """The scenes' 'vehicle_seeds' concatenated in row order (scene-major); None when no scene that has vehicles carries seeds;
+    ValueError when only some do, or a list is not as long as its scene has vehicles.  A scene without vehicles decides nothing."""
+    live = [f for f, c in enumerate(counts) if int(c) > 0]
+    have = [seeds_per_scene[f] is not None for f in live]
+    if any(have) and not all(have):
+        raise ValueError("run_frames_batched: either every scene that has vehicles carries 'vehicle_seeds' or none does "
+                         f"(scenes without: {[f for f, h in zip(live, have) if not h]})")
+    out: List[int] = []
+    for f in live:
+        sd = seeds_per_scene[f]
+        if sd is None:
+            continue
+        if len(sd) != int(counts[f]):
+            raise ValueError(f"run_frames_batched: scene {f} carries {len(sd)} vehicle_seeds for {int(counts[f])} vehicles")
+        out.extend(int(x) for x in sd)
+    return out if any(have) else None
+
+
 def later_geometry_batch_rows(scenes: Sequence[Dict], vehicles: Sequence[int], device_pose: bool, device_homography: bool,
                               inpaint: bool = False) -> Tuple[Optional[List[int]], bool]:
     """What `run_later_frames_batched_geometry` checks before it issues anything, for F geometry-mode scenes ('steps', no 'masks')
@@ -1934,6 +2008,267 @@ class VehiclePipeline:
                 res["skipped"] = [v for v in range(len(scenes[f]["steps"])) if v not in kept]
                 out.append(res)
         return out
+
+    # ------------------------------------------------------------------------------------------ first frames of several scenes
+    def run_frames_batched(self, scenes, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
+                           pad: Optional[bool] = None) -> list:
+        """`run_frame` for the first frames of SEVERAL scenes at once, with ragged vehicle counts V_f: a video frame usually
+        carries one to a few selected vehicles, and frame by frame each is a pass of ~300 dependent launches at batch V_f, the
+        worst regime the pass has.  The frames are independent of each other and the networks do not know which frame a row came
+        from, so everything between the uint8 frames and the composited frames is issued once for all sum(V_f) rows: the box
+        geometry rows (one upload), `frame_ops.crop_resize_frames` twice (box crop, hourglass input), the central crop, one plane
+        warp over the concatenated source planes (host-fitted jobs, or `device_homography`), `mask_bbox_geom`,
+        `icn_inputs_device`, `frame_ops.vunet_inputs_frames`, `_run` once, `lab2bgr`, `keypoints_to_frame`, the pose fit with
+        per-row focals and centers, and one ragged paste per composite (`paste_back_ragged_device`).  The three kernels that
+        read the frame take a table of frames and row offsets (fusg_crop_resize_frames_u8, fusg_vunet_inputs_frames,
+        fusg_paste_layers_ragged_u8); a group's read-back is ONE device-to-host copy of the raw pose fits.  Rows are
+        scene-major: scene f's vehicles are rows offsets[f] .. offsets[f + 1] (`frame_batch_offsets`).
+
+        scenes: a sequence of scenes as `run_frame` takes them on the given-geometry path, each with its own 'frame' (all of one
+        size: ValueError otherwise, before anything is launched) and its own vehicles; V_f = 0 is allowed.  Per scene
+        'background', 'vehicle_seeds', 'inpaint' (any of the three forms), 'kp3d' or 'kp3d_bank' (cad=True), 'focals' and
+        'centers' mean what they mean to `run_frame`.  Either every scene that has vehicles carries 'vehicle_seeds' or none does,
+        and with a pipeline built with inpaint=True the same holds for 'inpaint' (ValueError otherwise; where none does, the
+        refusal is `run_frame`'s own: such a pipeline's first frames need the key); EdgeConnect's inputs are built per scene from
+        its own image into its row slice, on the inpaint stream.
+        max_batch bounds the rows of a pass and FRAME_BATCH_MAX_FRAMES its scenes: consecutive scenes are packed greedily
+        (`frame_batch_groups`; default LATER_MAX_BATCH = 64 rows; a scene with more vehicles is a group of its own).
+        pad (None: pad when replay is on): the networks run at `frame_batch_pad(rows, max_batch)` rows - the next of 4, 8, 16,
+        32, 64 -, the padding rows of their inputs zero and their seeds 0; the glue writes the real rows and the outputs are cut
+        to them before the pose fit and the paste, so no kernel knows about padding.  replay=True: the networks are ONE
+        recorded plan per (padded rows, precision[, inpaint][, cad]), kept with the frame drivers' other plans under
+        ("frame_batch", padded_rows, ...) - at most five keys for the default max_batch whatever the counts of the video;
+        outputs are handed out as copies.  pad=True with replay=False is the eager pass over the same padded rows.
+        check: the range guard of `run` - one status word per group; raised, the group is redone in exact fp32 under the RNG
+        state it was issued with.
+        A batch's crops are not bit for bit those of per-frame passes of the same scenes: another batch size may route the
+        convolutions differently (the glue - crops, network inputs, paste - is byte-equal).
+        Memory: the scenes' per-vehicle tensors are concatenated - 19 * H * W bytes per row (source planes 15, sketch 3, mask 1;
+        17.5 MB at 720 x 1280) plus the warped planes' 15 * H * W, 2.0 GB for 64 rows at 720 x 1280.
+        Returns a list of `run_frame`'s dicts in scene order ('kp_idx', 'kp_xy', 'pose', 'icn_u8', 'vunet_u8', 'geom',
+        'frame_icn', 'frame_vunet' (+ 'inpaint_u8', 'cad_idx'), 'state' with that scene's rows of the appearance codes and central
+        crops, shard (0, V_f, V_f), sharded False - `run_later_frame` and `run_later_frames_batched` take it as they take
+        `run_frame`'s); per-vehicle tensors are views into the pass's stacked results.  A scene without vehicles gets
+        `run_frame`'s no-vehicle shape, its composites are its base.  [] -> [].
+        Geometry-mode scenes (a pipeline with cad_bank, scenes without 'masks') and a process group of more than one rank go
+        through `run_frames`, frame by frame - the results of today; a list that mixes geometry-mode and given-geometry scenes
+        is a ValueError."""
+        import numpy as np
+
+        from . import ops
+        from .utils.pnp_utils import select_and_flip
+        scenes = list(scenes)
+        if not scenes:
+            return []
+        geo = [self._is_geometry(sc) for sc in scenes]
+        if any(geo) and not all(geo):
+            raise ValueError("run_frames_batched: the list mixes geometry-mode scenes (no 'masks') and given-geometry scenes "
+                             f"(geometry-mode: {[f for f, g in enumerate(geo) if g]})")
+        if all(geo) or not _one_rank(self.group):
+            return list(self.run_frames(scenes, replay=replay))
+        sizes = {tuple(sc["frame"].shape) for sc in scenes}
+        if len(sizes) > 1:
+            raise ValueError(f"run_frames_batched: the frames of one call have one size, got {sorted(sizes)}")
+        counts = [int(np.asarray(sc["bboxes"]).reshape(-1, 4).shape[0]) for sc in scenes]
+        seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
+        if self.inpaint:
+            inps = [(f, sc.get("inpaint")) for f, (sc, c) in enumerate(zip(scenes, counts)) if c > 0]
+            if any(i is not None for _, i in inps) and not all(i is not None for _, i in inps):
+                raise ValueError("run_frames_batched: either every scene that has vehicles carries 'inpaint' or none does "
+                                 f"(scenes without: {[f for f, i in inps if i is None]})")
+            for _, i in inps:
+                inpaint_scene_form(i)                             # (ValueError for a malformed entry, before anything is issued)
+        if max_batch is None:
+            max_batch = LATER_MAX_BATCH
+        pad = bool(replay) if pad is None else bool(pad)
+        out = []
+        for lo, hi in frame_batch_groups(counts, max_batch):
+            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
+            rows = frame_batch_pad(sum(counts[lo:hi]), max_batch) if pad else None
+            res, raw = self._guarded(self._run_frame_batch, (scenes[lo:hi], replay, rows), check, rng)
+            if raw is not None:                                   # the group's one read-back: rvec | tvec | err of every row and start
+                raw = ops.d2h(raw)
+                rv, tv, er = raw[:, :12].reshape(-1, 4, 3), raw[:, 12:24].reshape(-1, 4, 3), raw[:, 24:28]
+            row = 0
+            for o in res:                                         # the reference's host epilogue of the pose fit, per row
+                n = int(o["kp_idx"].shape[0])
+                o["pose"] = [select_and_flip(rv[i], tv[i], er[i]) for i in range(row, row + n)]
+                row += n
+            out.extend(res)
+        return out
+
+    def _inpaint_inputs_ragged(self, scenes, offs, B: int, tgt) -> Tuple[Dict, object]:
+        """EdgeConnect's four inputs of a group of first frames, [B, c, R, R] each (B >= offs[-1]: the padding rows are zero):
+        scene f's rows offs[f] .. offs[f + 1] come from ITS image and boxes, as `_inpaint_inputs_batch` builds a later batch's -
+        all on the inpaint branch's stream, forked once; `tgt`: a recorded pass's input buffers, written in place."""
+        from . import ops
+        R, N = 256, offs[-1]
+
+        def build():
+            if tgt:
+                bufs = {k: tgt["ec_" + k] for k in ops.INPAINT_KEYS}
+                if B > N:
+                    for k in ops.INPAINT_KEYS:
+                        bufs[k][N:].zero_()
+            else:
+                bufs = {k: torch.zeros((B, 3 if k == "img" else 1, R, R), dtype=torch.float32, device=self.device) for k in ops.INPAINT_KEYS}
+            for f, sc in enumerate(scenes):
+                if offs[f + 1] == offs[f]:
+                    continue
+                inp = sc["inpaint"]
+                rows = {k: bufs[k][offs[f]:offs[f + 1]] for k in ops.INPAINT_KEYS}
+                if "box_masks" in inp:
+                    ops.inpaint_inputs_boxed(sc["frame"], inp["box_masks"], inp["boxes"], out=rows)
+                elif "det_masks" in inp:
+                    ops.inpaint_inputs(sc["frame"], inp["det_masks"], inp["boxes"], out=rows)
+                else:                                             # given
+                    for k in ops.INPAINT_KEYS:
+                        rows[k].copy_(inp[k])
+            return bufs
+
+        if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
+            return build(), (lambda: None)
+        st = self._streams.get("inpaint")
+        if st is None:
+            st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
+        ops.fork_to(st)
+        with torch.cuda.stream(st):
+            res = build()
+        return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
+
+    def _frame_batch_empty(self, scene) -> Dict:
+        """A scene without vehicles in `run_frames_batched`: `run_frame`'s no-vehicle shape (its composites are its base), and a
+        zero-vehicle 'state' the later-frame drivers take."""
+        inp = scene.get("inpaint") if self.inpaint else None     # (not asked for: only a scene that has vehicles needs the key)
+        o = self._no_vehicles(256, "kp_idx", "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if inp is not None else ()),
+                              *(("cad_idx",) if self.cad is not None else ()), "mu_app_0", "mu_app_1", "central")
+        o = self._frame_finish(scene, o)
+        o.pop("_pose_raw")
+        o["state"] = {"appearance": [o["mu_app_0"], o["mu_app_1"]], "central": o["central"], "shard": (0, 0, 0), "sharded": False}
+        return o
+
+    @torch.no_grad()
+    def _run_frame_batch(self, scenes, replay=False, rows=None):
+        """One group of `run_frames_batched`: (the scenes' `run_frame` dicts without 'pose', the raw pose fits of all rows packed
+        as float32 [N, 28] = rvec [4, 3] | tvec [4, 3] | err [4] on the device - None when no scene has a vehicle).  rows: the
+        row count the networks run at (>= N, the padding rows zero); None: N."""
+        import numpy as np
+
+        from . import frame_ops as fo
+        from . import ops
+        from .utils.pnp_utils import cpc_fit_device
+        from .warp_learn import planes_utils as pu
+        dev, R = self.device, 256
+        boxes = [np.asarray(sc["bboxes"]).reshape(-1, 4) for sc in scenes]
+        counts = [int(b.shape[0]) for b in boxes]
+        offs = frame_batch_offsets(counts)
+        N = offs[-1]
+        if N == 0:
+            return [self._frame_batch_empty(sc) for sc in scenes], None
+        B = N if rows is None else max(int(rows), N)
+        frames = [sc["frame"] for sc in scenes]
+        H, W, _ = frames[0].shape
+        live = [sc for sc, c in zip(scenes, counts) if c]
+        cat = lambda k: live[0][k] if len(live) == 1 else torch.cat([sc[k] for sc in live])       # noqa: E731
+        lst = lambda k: [veh for sc in live for veh in sc[k]]                                      # noqa: E731
+        vis = lambda k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in live])         # noqa: E731
+        with torch.cuda.device(dev):
+            inpaint = self.inpaint and live[0].get("inpaint") is not None
+            seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
+            if seeds is not None:
+                seeds = seeds + [0] * (B - N)
+            replay = replay and ops.RECORDER is None
+            pkey = ("frame_batch", B, ops.PRECISION) + (("inpaint",) if inpaint else ()) + (("cad",) if self.cad is not None else ())
+            cp = self._plan(pkey) if replay else None
+            tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
+
+            def buf(k, c):
+                """The networks' input `k` at B rows, its padding rows zero, and the view of its N real rows the glue writes."""
+                t = tgt.get(k)
+                if t is None:
+                    t = ops.nhwc_empty(B, c, R, R, dev, zero=True)
+                elif B > N:
+                    t[N:].zero_()
+                return t, t[:N]
+
+            merged = {"src_planes": cat("src_planes"), "src_kp": lst("src_kp"), "dst_kp": lst("dst_kp"),
+                      "src_vis": vis("src_vis"), "dst_vis": vis("dst_vis")}
+            masks, src_sketch, dst_sketch = cat("masks"), cat("src_sketch"), cat("dst_sketch")
+            # ---- host: the homography fits of every plane of every row, before any launch
+            jobs = None if self.device_homography else \
+                pu.warp_jobs_frame(merged["src_kp"], merged["dst_kp"], merged["src_vis"], merged["dst_vis"])
+            ec, ec_join = self._inpaint_inputs_ragged(scenes, offs, B, tgt) if inpaint else (None, None)
+            # ---- uint8 glue on the caller's stream, every step once for all rows
+            geom_box = ops.h2d([pu._geom_row(*pu.square_crop_geometry((H, W), bb)) for b in boxes for bb in b], dev, torch.int32)
+            img_bbox = fo.crop_resize_frames(frames, offs, geom_box, (R, R), 0)                # :58-60
+            hg_x, hg_rows = buf("hg_x", 3)
+            fo.crop_resize_frames(frames, offs, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD, out=hg_rows)   # :61-65
+            central = fo.central_crop(img_bbox)                                                # vehicle_utils.py:49-52
+            warped = self._warp_planes(merged, jobs)                                           # :171-175
+            _, geom = fo.mask_bbox_geom(masks)
+            icn_x, icn_rows = buf("icn_x", 3 * (int(warped.shape[1]) + 2))
+            pu.icn_inputs_device(warped, dst_sketch, central, geom, R, R, out=icn_rows)        # :179-180
+            (vu_x, vx_rows), (vu_y, vy_rows) = buf("vu_x", 6), buf("vu_y", 3)
+            fo.vunet_inputs_frames(frames, offs, masks, src_sketch, dst_sketch, geom, R, out=(vx_rows, vy_rows))   # :203-228
+            nets_in = {"hg_x": hg_x, "icn_x": icn_x, "vu_x": vu_x, "vu_y": vu_y}
+            if ec is not None:
+                ec_join()
+                nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
+            if replay:                                            # ('icn_u8' is consumed by lab2bgr below, before the next replay)
+                out = self._replay(pkey, nets_in, seeds, clone=("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"))
+            else:
+                out = self._run(nets_in, seeds)                                                # :75-79, :182, :230-234
+            out = {k: v[:N] for k, v in out.items()}             # the real rows: nothing below knows about padding
+            out["icn_u8"] = pu.lab2bgr(out["icn_u8"].contiguous())                             # to_image(from_LAB=True), :182
+            if "cad_logits" in out:
+                out["cad_idx"] = out.pop("cad_logits").argmax(1)                               # :69
+            # ---- keypoints -> frame pixels -> pose fit, with per-row focals and centers
+            out["kp_idx"] = out["kp_idx"].contiguous()
+            kp_xy = fo.keypoints_to_frame(out["kp_idx"], geom_box, (R // 4, R // 4))           # :95-97 (64 x 64 heat-maps)
+            per_row = lambda k: ops.h2d(np.concatenate([np.broadcast_to(np.asarray(sc[k], np.float32).reshape(-1, 2), (c, 2))   # noqa: E731
+                                                        for sc, c in zip(scenes, counts) if c]), dev)
+            banked = [self.cad is not None and sc.get("kp3d_bank") is not None for sc in live]
+            if all(banked):                                       # :82-88: the chosen CAD model's keypoints, one gather
+                banks, which = [], []
+                for sc, c in zip(live, [c for c in counts if c]):
+                    hit = [i for i, b in enumerate(banks) if b is sc["kp3d_bank"]]
+                    if not hit:
+                        banks.append(sc["kp3d_bank"])
+                    which += [hit[0] if hit else len(banks) - 1] * c
+                bank = ops.h2d(np.stack([np.asarray(b, np.float32) for b in banks]), dev)
+                kp3d = bank[ops.h2d(np.asarray(which, np.int64), dev), out["cad_idx"]]
+            elif not any(banked):
+                kp3d = ops.h2d(np.concatenate([np.asarray(sc["kp3d"], np.float32).reshape(-1, 12, 3) for sc in live]), dev)
+            else:
+                kp3d = torch.cat([ops.h2d(np.asarray(sc["kp3d_bank"], np.float32), dev)[out["cad_idx"][offs[f]:offs[f + 1]]] if
+                                  (self.cad is not None and sc.get("kp3d_bank") is not None) else
+                                  ops.h2d(np.asarray(sc["kp3d"], np.float32).reshape(-1, 12, 3), dev)
+                                  for f, sc in enumerate(scenes) if counts[f]])
+            rv, tv, er = cpc_fit_device(per_row("focals"), per_row("centers"), kp_xy, kp3d)   # :104-105
+            raw = torch.cat([rv.reshape(N, 12), tv.reshape(N, 12), er.reshape(N, 4)], 1)
+            # ---- one ragged paste per composite (:184-198, :236-250; :133-143: with --inpaint the composite starts from the frame)
+            bases = [sc["frame"] if (self.inpaint and sc.get("inpaint") is not None) else sc.get("background", sc["frame"]) for sc in scenes]
+            box = {}
+            if inpaint:
+                brow = np.zeros((N, 8), np.int32)
+                brow[:, :4] = np.concatenate([np.asarray(sc["inpaint"]["boxes"]).reshape(-1, 4) for sc in live])
+                box = dict(box_images=out["inpaint_u8"], box_geom=ops.h2d(brow, dev, torch.int32))
+            comp = {k: pu.paste_back_ragged_device(bases, offs, out[c], geom, masks, **box)
+                    for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+        keys = ("kp_idx", "icn_u8", "vunet_u8") + (("inpaint_u8",) if inpaint else ()) + (("cad_idx",) if "cad_idx" in out else ())
+        res = []
+        for f, c in enumerate(counts):
+            sl = slice(offs[f], offs[f + 1])
+            if c == 0:
+                o = self._frame_batch_empty(scenes[f])
+            else:
+                o = {k: out[k][sl] for k in keys}
+                o["geom"], o["kp_xy"] = geom[sl], kp_xy[sl]
+                o["state"] = {"appearance": [out["mu_app_0"][sl], out["mu_app_1"][sl]], "central": central[sl], "shard": (0, c, c),
+                              "sharded": False}
+            o["frame_icn"], o["frame_vunet"] = comp["frame_icn"][f], comp["frame_vunet"][f]
+            res.append(o)
+        return res, raw
 
     def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False, batched: bool = False,
                         batch_geometry: bool = False):

@@ -733,6 +733,42 @@ def paste_back_frames_device(bases: Sequence[torch.Tensor], net_images: torch.Te
     return out
 
 
+def paste_back_ragged_device(bases: Sequence[torch.Tensor], frame_rows: Sequence[int], net_images: torch.Tensor, geom: torch.Tensor,
+                             masks: torch.Tensor, box_images: Optional[torch.Tensor] = None,
+                             box_geom: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`paste_back_frames_device` with another number of layers per frame (fusg_paste_layers_ragged_u8): frame f's layers are rows
+    [frame_rows[f], frame_rows[f + 1]) of net_images [rows, h, w, 3], geom int32 [rows, 8], masks uint8 [rows, H, W] (and
+    box_images / box_geom), in row order; frame_rows = F + 1 host offsets from 0 to rows.  A frame without layers is a copy of its
+    base; the bases are read, never written.  At most L.MAX_FRAMES frames per launch.  -> uint8 [F, H, W, 3]."""
+    F = len(bases)
+    if F < 1 or F > L.MAX_FRAMES:
+        raise ValueError(f"paste_back_ragged_device: {F} frames (1..{L.MAX_FRAMES} per launch)")
+    keep = [b.contiguous() for b in bases]                        # referenced until the launch is queued
+    H, W = int(keep[0].shape[0]), int(keep[0].shape[1])
+    dev = keep[0].device
+    N = int(masks.shape[0])
+    if any(tuple(b.shape) != (H, W, 3) or b.dtype != torch.uint8 or b.device != dev for b in keep):
+        raise ValueError(f"paste_back_ragged_device: every base image is uint8 {(H, W, 3)} on {dev}")
+    offs = [int(r) for r in frame_rows]
+    if len(offs) != F + 1:
+        raise ValueError(f"paste_back_ragged_device: {len(offs)} row offsets for {F} frames (one more than frames)")
+    if tuple(masks.shape[1:]) != (H, W) or net_images.shape[0] != N or geom.dtype != torch.int32 or tuple(geom.shape) != (N, 8):
+        raise ValueError(f"paste_back_ragged_device: masks {tuple(masks.shape)}, {net_images.shape[0]} crops, geom {tuple(geom.shape)} "
+                         f"for frames of {(H, W)}")
+    if (box_images is None) != (box_geom is None) or (box_images is not None and (
+            box_images.shape[0] != N or box_geom.dtype != torch.int32 or tuple(box_geom.shape) != (N, 8))):
+        raise ValueError("paste_back_ragged_device: box_images [rows, h, w, 3] come with box_geom int32 [rows, 8]")
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    ptrs = (C.c_void_p * F)(*[b.data_ptr() for b in keep])
+    with torch.cuda.device(dev):
+        L.check(L.lib().fusg_paste_layers_ragged_u8(
+            C.byref(_u8desc(net_images.contiguous())), C.byref(ops.desc(masks.contiguous().view(N, 1, H, W))), geom.contiguous().data_ptr(),
+            C.byref(_u8desc(box_images.contiguous())) if box_images is not None else None,
+            box_geom.contiguous().data_ptr() if box_geom is not None else None, ptrs, (C.c_int32 * (F + 1))(*offs), F,
+            C.byref(_u8desc(out)), ops.stream_ptr()), "paste_layers_ragged_u8")
+    return out
+
+
 def paste_back(frame: Image, net_images: torch.Tensor, crop_infos: Sequence[dict], paste_masks: Image) -> Image:
     """The "revert and stitch" of trajectory_inference.py:184-198 for V vehicles in one launch: net_images [V, h, w, 3]
     uint8 (CUDA), their crop_infos (from get_icn_inputs) and paste masks [V, H, W] (bool / uint8; the reference's

@@ -451,6 +451,33 @@ int fusg_mask_bbox_geom(const fusg_tensor* masks, int32_t* bbox, int32_t* geom, 
 int fusg_keypoints_to_frame(const int32_t* idx, const int32_t* geom, float* out, int32_t vehicles, int32_t nkp,
                             int32_t hm_w, int32_t hm_h, void* stream);
 
+/* ---- frame-indexed glue (pipeline.VehiclePipeline.run_frames_batched: the first frames of several scenes as ONE pass; added
+ * without a version step: the entry points are new, nothing existing changed, and FUSG_VERSION 118 is what the suite pins).
+ * The three entry points above that read the frame, with the frame a property of the ROW.  Two HOST tables, read before the call
+ * returns and handed to the kernel by value: frames = n_frames pointers to dense u8 [H, W, 3] DEVICE images; frame_rows =
+ * n_frames + 1 non-decreasing offsets from 0 to `rows`, rows [frame_rows[f], frame_rows[f + 1]) read frame f.  Checked on the
+ * host before anything is launched: 1 <= n_frames <= FUSG_MAX_FRAMES, no null pointer, offsets monotone from 0 to rows, every
+ * row count equal, rect with rect_geom (a table in device memory could not be checked, and a wrong one is an out-of-bounds
+ * read).  The per-pixel arithmetic is that of the one-frame entry points: same bytes. */
+#define FUSG_MAX_FRAMES 64
+/* fusg_crop_resize_u8 for rows = dst->n windows cut from n_frames images of H x W; modes, mean3 / std3, geom (DEVICE int32
+ * [rows][8]) and dst as there.  rows == 0: no launch, returns 0. */
+int fusg_crop_resize_frames_u8(const void* const* frames, const int32_t* frame_rows, int32_t n_frames, int32_t H, int32_t W,
+                               const int32_t* geom, const fusg_tensor* dst, int32_t mode, const float* mean3, const float* std3,
+                               void* stream);
+/* fusg_vunet_inputs with the same tables: masks [rows, 1, H, W], src_sketch / dst_sketch [rows], geom [rows][8], x [rows, 6, h,
+ * w], y [rows, 3, h, w].  rows == 0: no launch, returns 0. */
+int fusg_vunet_inputs_frames(const void* const* frames, const int32_t* frame_rows, int32_t n_frames, const fusg_tensor* masks,
+                             const fusg_tensor* src_sketch, const fusg_tensor* dst_sketch, const int32_t* geom,
+                             const fusg_tensor* x, const fusg_tensor* y, void* stream);
+/* fusg_paste_layers_frames_u8 with another number of layers per frame: frame f's layers are rows [frame_rows[f], frame_rows[f +
+ * 1]) of net, masks, geom (and rect, rect_geom: both NULL for the plain paste), in row order, the last covering layer wins.
+ * bases = HOST table of n_frames DEVICE pointers, bases[f] = the dense u8 [H, W, 3] image frame f starts from (read only, must
+ * not overlap dst); dst u8 [n_frames, H, W, 3] is written whole; a frame without layers is a copy of its base. */
+int fusg_paste_layers_ragged_u8(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
+                                const int32_t* rect_geom, const void* const* bases, const int32_t* frame_rows, int32_t n_frames,
+                                const fusg_tensor* dst, void* stream);
+
 /* ---- pose fit ------------------------------------------------------------------------------- */
 /*
  * The reference's pose fit ("CamPoseCalib": Levenberg-Marquardt on a Rodrigues vector + translation, utils/cpc.py:45-139
