@@ -57,6 +57,17 @@ class BneckDesc(C.Structure):           # fusg_bneck_desc
                 ("status", C.c_void_p), ("planes", C.c_int32), ("exact_f32", C.c_int32)]
 
 
+class RespairDesc(C.Structure):         # fusg_respair_desc
+    _fields_ = [("x", Tensor), ("s1", Tensor), ("kb", Tensor), ("kc", Tensor),
+                ("w_in", C.c_void_p), ("bias_in", C.c_void_p),
+                ("wfragA", C.c_void_p), ("biasA", C.c_void_p), ("wscaleA", C.c_void_p),
+                ("wfragB", C.c_void_p), ("biasB", C.c_void_p), ("wscaleB", C.c_void_p),
+                ("wfrag_b", C.c_void_p), ("bias_b", C.c_void_p), ("wscale_b", C.c_void_p),
+                ("wfrag_c", C.c_void_p), ("bias_c", C.c_void_p), ("wscale_c", C.c_void_p),
+                ("status", C.c_void_p), ("channels", C.c_int32), ("entry", C.c_int32),
+                ("cin", C.c_int32), ("kpad_in", C.c_int32), ("tap_order", C.c_int32), ("_pad", C.c_int32)]
+
+
 class PackSpec(C.Structure):            # fusg_pack_spec
     _fields_ = [(n, C.c_int32) for n in ("cout", "cin", "kh", "kw", "c0", "stride", "pad", "dil", "upsample", "cin_pad")]
 
@@ -83,6 +94,7 @@ _SIGS = {
     "fusg_conv2d_plan": (C.c_int64, [C.POINTER(ConvDesc)]),
     "fusg_conv2d_route": (C.c_int, [C.POINTER(ConvDesc)]),
     "fusg_hg_bottleneck": (C.c_int, [C.POINTER(BneckDesc), C.c_void_p]),
+    "fusg_vunet_respair": (C.c_int, [C.POINTER(RespairDesc), C.c_void_p]),
     "fusg_chan_stats": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_void_p]),
     "fusg_in_finalize": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fusg_ln_finalize": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -163,6 +175,7 @@ _SIGS = {
     "fusg_sizeof_tensor": (C.c_int, []),
     "fusg_sizeof_conv_desc": (C.c_int, []),
     "fusg_sizeof_bneck_desc": (C.c_int, []),
+    "fusg_sizeof_respair_desc": (C.c_int, []),
     "fusg_prof_enable": (None, [C.c_int]),
     "fusg_prof_reset": (None, []),
     "fusg_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -194,7 +207,8 @@ def lib():
             fn.restype = res
             fn.argtypes = args
         if (h.fusg_sizeof_tensor() != C.sizeof(Tensor) or h.fusg_sizeof_conv_desc() != C.sizeof(ConvDesc)
-                or h.fusg_sizeof_bneck_desc() != C.sizeof(BneckDesc)):
+                or h.fusg_sizeof_bneck_desc() != C.sizeof(BneckDesc)
+                or h.fusg_sizeof_respair_desc() != C.sizeof(RespairDesc)):
             raise FusgUnavailable("libfusg.so struct layout differs from the ctypes mirror (stale build?)")
         _lib = h
     return _lib

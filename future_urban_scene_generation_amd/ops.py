@@ -603,11 +603,91 @@ def bottleneck(p: dict, x: torch.Tensor, res: Optional[torch.Tensor] = None, pre
     return out
 
 
+VU_RESPAIR = not _env_set("FUSG_NO_RESPAIR")      # the VUnet's 32-channel Residual pairs as one launch each (tests flip it)
+
+
+def respair_ok(res_a: ConvPlan, res_b: ConvPlan, nin_b: ConvPlan, nin_c: ConvPlan, x: torch.Tensor,
+               nin_in: Optional[ConvPlan] = None, precision: Optional[str] = None) -> bool:
+    """Can two Residuals (3x3 plans res_a, res_b), the skip NiNs of their outputs (nin_b, nin_c) and, in the entry form, the
+    few-channel NiN in front (nin_in, x = its input) run as ONE launch (fusg_vunet_respair)?  Split-fp16 only, 32 channels,
+    k3 pad 1 stride 1 from a single source, and only where fusg_conv2d would run every launch of the block on the halo
+    kernel (H % 8 == 0, W % 16 == 0, a grid large enough not to be split over K) and the entry NiN on the pointwise kernel:
+    the fused launch then writes their bytes.  Anything else runs unfused; so does everything with VU_RESPAIR off
+    (FUSG_NO_RESPAIR=1 at import)."""
+    prec = precision or PRECISION
+    if not VU_RESPAIR or prec != "f16x3" or not is_nhwc(x):
+        return False
+    for p in (res_a, res_b):
+        if not (p.cout == 32 and p.cout_pad == 32 and p.c0k == 32 and p.c1k == 0 and p.kh == 3 and p.kw == 3 and p.pad == 1
+                and p.pad_w < 0 and p.stride == 1 and p.dil == 1 and p.upsample == 0 and p.nphase == 1 and p.pad_mode == L.PAD_ZERO):
+            return False
+    for p in (nin_b, nin_c):
+        if not (p.cout == 32 and p.cout_pad == 32 and p.c0k == 32 and p.c1k == 0 and p.kh == 1 and p.kw == 1 and p.pad == 0
+                and p.stride == 1 and p.nphase == 1):
+            return False
+    b, c, h, w = x.shape
+    if nin_in is not None:
+        if not (nin_in.cout == 32 and nin_in.cout_pad == 32 and nin_in.c0k in (4, 8) and nin_in.c1k == 0 and nin_in.kh == 1
+                and nin_in.kw == 1 and nin_in.pad == 0 and nin_in.stride == 1 and nin_in.nphase == 1 and c == nin_in.c_split[0]):
+            return False
+    elif c != 32:
+        return False
+    # The fused launch sums as the HALO kernel does.  The router is asked what each launch it replaces would run on: small
+    # grids get a generic split-K launch (another order of summation), tiny images the small-image kernel - those stay unfused.
+    # The answer depends on the shapes and on the switches the router reads per call: asked once per such key.
+    key = (id(res_b), id(nin_b), id(nin_c), id(nin_in), b, c, h, w, x.stride(3), str(x.device),
+           _env_set("FUSG_NO_SMALL"), _env_set("FUSG_NO_POINTWISE"), _env_set("FUSG_SMALL_KSPLIT"))
+    memo = res_a.__dict__.setdefault("_respair_routes", {})
+    if key not in memo:
+        t32 = x if nin_in is None else nhwc_empty(b, 32, h, w, x.device)   # stands in for x0 / s0 / s1 (no launch reads it)
+        asks = [(res_a, t32, t32, 2), (res_b, t32, t32, 2), (nin_b, t32, None, 2), (nin_c, t32, None, 2)]
+        if nin_in is not None:
+            asks.append((nin_in, x, None, 7))
+        ok = True
+        for plan, src, res, family in asks:
+            d, _ = _conv_desc(plan, src, pre_op=L.PRE_ELU, res0=res, out=t32, precision=prec)
+            L.lib().fusg_conv2d_plan(C.byref(d))
+            ok = ok and L.lib().fusg_conv2d_route(C.byref(d)) == family
+        memo[key] = ok
+    return memo[key]
+
+
+def respair(res_a: ConvPlan, res_b: ConvPlan, nin_b: ConvPlan, nin_c: ConvPlan, x: torch.Tensor,
+            nin_in: Optional[ConvPlan] = None, tap_order: int = 0):
+    """(s1, kb, kc) of  x0 = nin_in(elu(x)) or x;  s0 = res_a(elu(x0)) + x0;  s1 = res_b(elu(s0)) + s0;  kb = nin_b(elu(s0));
+    kc = nin_c(elu(s1))  in one launch (fusg_vunet_respair) - the bytes of the five (four) `conv` launches it replaces.
+    tap_order: 0 = the summation order fusg_conv2d gives those launches at this grid size, 1 = taps in order (large grids),
+    2 = K split over the waves (small grids)."""
+    b, _, h, w = x.shape
+    s1, kb, kc = (nhwc_empty(b, 32, h, w, x.device) for _ in range(3))
+    d = L.RespairDesc()
+    d.x, d.s1, d.kb, d.kc = desc(x), desc(s1), desc(kb), desc(kc)
+    for key, plan in (("A", res_a), ("B", res_b), ("_b", nin_b), ("_c", nin_c)):
+        dev = plan.to(x.device).dev
+        if RECORDER is not None:
+            RECORDER.keep.append(dev)
+        assert dev.get("wfrag") is not None and dev["wfrag_order"] == 0, key
+        setattr(d, "wfrag" + key, dev["wfrag"].data_ptr())
+        setattr(d, "bias" + key, dev["bias"].data_ptr())
+        setattr(d, "wscale" + key, dev["wscale"].data_ptr())
+    if nin_in is not None:
+        dev = nin_in.to(x.device).dev
+        if RECORDER is not None:
+            RECORDER.keep.append(dev)
+        d.w_in, d.bias_in = dev["wpack"].data_ptr(), dev["bias"].data_ptr()
+        d.entry, d.cin, d.kpad_in = 1, nin_in.c0k, nin_in.k_pad
+    d.status = status_word(x.device).data_ptr()
+    d.channels = 32
+    d.tap_order = int(tap_order)
+    L.check(L.lib().fusg_vunet_respair(C.byref(d), stream_ptr()), "vunet_respair")
+    return s1, kb, kc
+
+
 def last_conv_kernel() -> int:
     """Kernel family of the last conv launch issued by this thread (fusg_last_conv_kernel): 0 generic fp32,
     1 generic split-fp16, 2 halo, 3 halo in parity-quadrant (stride-2) form, 4 tap-unit kernel (few-channel stems),
     5 halo in bf16 mode, 6 fused hourglass Bottleneck, 7 pointwise-from-few-channels streaming kernel, 8 small-image kernel,
-    9 halo in exact fp32, 10 tap-unit in exact fp32, 11 tap-unit in bf16 mode."""
+    9 halo in exact fp32, 10 tap-unit in exact fp32, 11 tap-unit in bf16 mode, 12 fused VUnet Residual pair (respair)."""
     return int(L.lib().fusg_last_conv_kernel())
 
 

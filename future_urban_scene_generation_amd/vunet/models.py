@@ -224,38 +224,16 @@ class Vunet_fix_res(FusedNet):
         # 'nearest' carry their tap sparsity (no fused ELU, no skip input: reference layers.py:140-152)
         return ops.conv(self._plans[name + self._UP_PLAN[self.up_mode]], x, store=L.STORE_D2S)
 
-    # ---- "fusion by cache blocking" of the high-resolution 32-channel blocks (round 4 experiment, FUSG_VU_SUBBATCH=n) ----
-    # The verdict's fused Residual -> Residual block would keep the intermediates of the 256 x 256 / 128 x 128 levels out of
-    # HBM.  The same traffic saving without a new kernel: run those levels depth-first over sub-batches of n images, so that
-    # every intermediate (67 MB per tensor at n = 8, 32 channels, 256 x 256) is consumed out of the 256 MiB Infinity Cache
-    # right after it was written, and the sub-batch temporaries are the same allocator blocks every time.  Same launches on
-    # slices: the results are bit-identical.  Measured: profiles/r04_ab_experiments.txt.
+    # ---- "fusion by cache blocking" of the high-resolution 32-channel decoder blocks (round 4 experiment, FUSG_VU_SUBBATCH=n) ----
+    # Run UpBlock 5_a and the EndBlock depth-first over sub-batches of n images, so that every intermediate (67 MB per tensor at
+    # n = 8, 32 channels, 256 x 256) is consumed out of the 256 MiB Infinity Cache right after it was written.  Same launches on
+    # slices: the results are bit-identical.  Measured: profiles/r04_ab_experiments.txt (no gain).  The encoder half of the
+    # experiment is gone: those two levels are one fused launch each (_respair), which keeps the intermediates in LDS.
     @staticmethod
     def _subbatch(b: int) -> int:
         import os
         n = int(os.environ.get("FUSG_VU_SUBBATCH", "0"))
         return n if 0 < n < b else 0
-
-    def _shape_encoder_top(self, x, n):
-        """forward_dec_up's first two levels (InitBlock at full resolution, DownBlock 1_a at half) over sub-batches of n."""
-        b, _, h, w = x.shape
-        dev = x.device
-        sb, sc = ops.nhwc_empty(b, 32, h, w, dev), ops.nhwc_empty(b, 32, h, w, dev)
-        ab, ac = ops.nhwc_empty(b, 32, h // 2, w // 2, dev), ops.nhwc_empty(b, 32, h // 2, w // 2, dev)
-        a1 = ops.nhwc_empty(b, 32, h // 2, w // 2, dev)
-        for lo in range(0, b, n):
-            hi = min(b, lo + n)
-            t = self._nin("shape_encoder_1.nin", x[lo:hi])
-            s0 = self._residual("shape_encoder_1.residual_0", t)
-            s1 = self._residual("shape_encoder_1.residual_1", s0)
-            self._nin("shape_skip_1_b", s0, out=sb[lo:hi])
-            self._nin("shape_skip_1_c", s1, out=sc[lo:hi])
-            d = ops.conv(self._plans["shape_encoder_1_a.down.down"], s1)
-            a0 = self._residual("shape_encoder_1_a.residual_0", d)
-            self._residual("shape_encoder_1_a.residual_1", a0, out=a1[lo:hi])
-            self._nin("shape_skip_1_a_b", a0, out=ab[lo:hi])
-            self._nin("shape_skip_1_a_c", a1[lo:hi], out=ac[lo:hi])
-        return a1, [sb, sc, ab, ac]
 
     def _shape_decoder_tail(self, x, skips, n):
         """forward_dec_down's last two blocks (UpBlock 5_a at half resolution, EndBlock at full) over sub-batches of n;
@@ -382,6 +360,33 @@ class Vunet_fix_res(FusedNet):
         s1 = x = self._residual(name + ".residual_1", x)
         return x, [s0, s1]
 
+    # ---- the 32-channel shape-encoder levels: both Residuals and both skip NiNs as ONE launch (ops.respair) where it applies
+    def _respair(self, name, skip, x, nin_in=None):
+        P = self._plans
+        plans = (P[name + ".residual_0.layers.2"], P[name + ".residual_1.layers.2"], P[skip + "_b.layers.1"], P[skip + "_c.layers.1"])
+        if not ops.respair_ok(*plans, x, nin_in=nin_in):
+            return None
+        s1, kb, kc = ops.respair(*plans, x, nin_in=nin_in)
+        return s1, [kb, kc]
+
+    def _init_block_skips(self, name, skip, x):
+        """InitBlock + the skip NiNs of its two Residual outputs -> (x, [skip_b, skip_c])."""
+        fused = self._respair(name, skip, x, nin_in=self._plans[name + ".nin.layers.1"])
+        if fused is not None:
+            return fused
+        x, sl = self._init_block(name, x)
+        return x, [self._nin(skip + "_b", sl[-2]), self._nin(skip + "_c", sl[-1])]
+
+    def _down_block_skips(self, name, skip, x):
+        """DownBlock + the skip NiNs of its two Residual outputs -> (x, [skip_b, skip_c]); the stride-2 conv stays its own launch."""
+        d = ops.conv(self._plans[name + ".down.down"], x)
+        fused = self._respair(name, skip, d)
+        if fused is not None:
+            return fused
+        s0 = self._residual(name + ".residual_0", d)
+        s1 = self._residual(name + ".residual_1", s0)
+        return s1, [self._nin(skip + "_b", s0), self._nin(skip + "_c", s1)]
+
     def _up_block(self, name, x, skip_a, skip_b):
         x = self._residual(name + ".residual_0", x, skip_a)
         x = self._residual(name + ".residual_1", x, skip_b)
@@ -426,15 +431,11 @@ class Vunet_fix_res(FusedNet):
         self._ensure(x)
         x = ops.as_nhwc(x)
         skips: List[torch.Tensor] = []
-        nsub = self._subbatch(x.shape[0]) if self.vunet_256 else 0
-        if nsub:
-            x, skips = self._shape_encoder_top(x, nsub)
-        else:
-            x, sl = self._init_block("shape_encoder_1", x)
-            skips += [self._nin("shape_skip_1_b", sl[-2]), self._nin("shape_skip_1_c", sl[-1])]
-            if self.vunet_256:
-                x, sl = self._down_block("shape_encoder_1_a", x)
-                skips += [self._nin("shape_skip_1_a_b", sl[-2]), self._nin("shape_skip_1_a_c", sl[-1])]
+        x, sk = self._init_block_skips("shape_encoder_1", "shape_skip_1", x)
+        skips += sk
+        if self.vunet_256:
+            x, sk = self._down_block_skips("shape_encoder_1_a", "shape_skip_1_a", x)
+            skips += sk
         for i in range(2, 7):
             x, sl = self._down_block(f"shape_encoder_{i}", x)
             skips += [self._nin(f"shape_skip_{i}_b", sl[-2]), self._nin(f"shape_skip_{i}_c", sl[-1])]

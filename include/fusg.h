@@ -264,6 +264,39 @@ typedef struct fusg_bneck_desc {
 } fusg_bneck_desc;
 int fusg_hg_bottleneck(const fusg_bneck_desc* d, void* stream);
 
+/*
+ * Two Residuals of the VUnet's 32-channel shape-encoder levels and the two skip NiNs that read them, in ONE launch
+ * (split-fp16 arithmetic, FUSG_PREC_F16X3; csrc/conv_respair.hip):
+ *   x0 = entry ? NiN_in(elu(u)) + bias_in : x
+ *   s0 = convA_3x3(elu(x0)) + biasA + x0,   s1 = convB_3x3(elu(s0)) + biasB + s0        (zero padding 1)
+ *   kb = conv_b_1x1(elu(s0)) + bias_b,      kc = conv_c_1x1(elu(s1)) + bias_c
+ * s1, kb and kc are written; x0 and s0 stay in the workgroup (vunet/models.py: InitBlock + shape_skip_1_b/c with entry = 1,
+ * the two Residuals of DownBlock 1_a + shape_skip_1_a_b/c with entry = 0).  The results are bit for bit those of the five
+ * (four) fusg_conv2d launches of the block.
+ * x: entry = 0: [n, 32, h, w]; entry = 1: u, [n, <= 8, h, w] as the few-channel pointwise launch takes it (w_in = that NiN's
+ * fusg_conv_desc.wpack with row pitch kpad_in, cin = its c0k, bias_in = its bias).  h % 8 == 0, w % 16 == 0.  All tensors
+ * NHWC-physical f32; no output may alias x or another output.
+ * Weights: the `wfrag` copy (wfrag_order 0), `bias` and `wscale` of the four 32 -> 32 convolutions.
+ * tap_order: which of the halo kernel's two summation orders the 3x3 convolutions follow - 0: the one fusg_conv2d gives the
+ * unfused launches at this grid size (K split over the waves on grids of at most 1024 patches), 1: taps in order, 2: split.
+ * Same range contract as F16X3 launches: *status = 1 when a staged operand (elu of x0, s0 or s1) is outside the split's range.
+ */
+typedef struct fusg_respair_desc {
+    fusg_tensor x, s1, kb, kc;
+    const float* w_in; const float* bias_in;                                /* entry NiN (entry = 1)      */
+    const void*  wfragA;  const float* biasA;  const float* wscaleA;        /* first Residual's 3x3       */
+    const void*  wfragB;  const float* biasB;  const float* wscaleB;        /* second Residual's 3x3      */
+    const void*  wfrag_b; const float* bias_b; const float* wscale_b;       /* skip NiN of s0             */
+    const void*  wfrag_c; const float* bias_c; const float* wscale_c;       /* skip NiN of s1             */
+    int32_t*     status;
+    int32_t      channels;       /* 32 */
+    int32_t      entry;
+    int32_t      cin, kpad_in;
+    int32_t      tap_order;
+    int32_t      _pad;
+} fusg_respair_desc;
+int fusg_vunet_respair(const fusg_respair_desc* d, void* stream);
+
 /* Load-time weight pre-packing on the HOST (no device work): everything fusg_conv_desc needs for one nn.Conv2d-style
  * filter weight[cout][cin][kh][kw] (torch layout, correlation form) whose input channels come from one source (c0 = cin)
  * or from two concatenated sources (the first c0 channels from src0: torch.cat([x, skip], 1) fused into the gather).
@@ -708,7 +741,8 @@ enum { FUSG_CONV_GENERIC_F32 = 0, FUSG_CONV_GENERIC_F16X3 = 1, FUSG_CONV_HALO = 
        FUSG_CONV_SMALL = 8 /* small output images (<= 64 pixels): latency-built split-fp16 kernel (csrc/conv_kernel_small.h) */,
        FUSG_CONV_HALO_F32 = 9 /* halo kernel in exact fp32 (v_mfma_f32_16x16x4_f32, fusg_conv_desc.wfrag_f32) */,
        FUSG_CONV_TAPUNIT_F32 = 10 /* few-channel stems in exact fp32 (csrc/conv_kernel_tapunit_f32.h; wfrag_order 2 + wfrag_f32) */,
-       FUSG_CONV_TAPUNIT_BF16 = 11 /* few-channel stems in single-pass bf16 (FUSG_PREC_BF16; wfrag_order 2 + wfrag_bf16) */ };
+       FUSG_CONV_TAPUNIT_BF16 = 11 /* few-channel stems in single-pass bf16 (FUSG_PREC_BF16; wfrag_order 2 + wfrag_bf16) */,
+       FUSG_CONV_RESPAIR = 12 /* fusg_vunet_respair */ };
 int         fusg_last_conv_kernel(void);
 const char* fusg_arch(void);                      /* "gfx950" */
 /* sizeof(fusg_tensor) / sizeof(fusg_conv_desc) as compiled, so that FFI bindings can verify their
@@ -716,6 +750,7 @@ const char* fusg_arch(void);                      /* "gfx950" */
 int         fusg_sizeof_tensor(void);
 int         fusg_sizeof_conv_desc(void);
 int         fusg_sizeof_bneck_desc(void);
+int         fusg_sizeof_respair_desc(void);
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline leg).
  * kind 0 = conv implicit-GEMM kernel.  Disabled by default; enabling makes launches record two
  * events each.  fusg_prof_read synchronises the recorded events and returns totals since reset. */
