@@ -95,6 +95,8 @@ _SIGS = {
     "fusg_conv2d_route": (C.c_int, [C.POINTER(ConvDesc)]),
     "fusg_hg_bottleneck": (C.c_int, [C.POINTER(BneckDesc), C.c_void_p]),
     "fusg_vunet_respair": (C.c_int, [C.POINTER(RespairDesc), C.c_void_p]),
+    "fusg_conv2d_entry_nin": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p]),
+    "fusg_conv2d_entry_nin_route": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
     "fusg_chan_stats": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_void_p]),
     "fusg_in_finalize": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fusg_ln_finalize": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -585,7 +585,7 @@ static hipError_t run_tapunit(const ConvK& k, const fusg_conv_desc& d, const Con
                                                                                          : launch_tapunit_32(h, grid, s, pk, r.unit, r.mode);
 }
 
-static hipError_t run_halo(const ConvK& k, const fusg_conv_desc& d, const ConvRoute& r, hipStream_t s, int pk) {
+static hipError_t run_halo(const ConvK& k, const fusg_conv_desc& d, const ConvRoute& r, hipStream_t s, int pk, const EntryK* en = nullptr) {
     HaloK h;
     memset(&h, 0, sizeof(h));
     h.c = k;
@@ -613,6 +613,9 @@ static hipError_t run_halo(const ConvK& k, const fusg_conv_desc& d, const ConvRo
         h.c.MT = (int)d.src0.n * d.tile_count;
     }
     const dim3 grid(h.c.MT * h.c.NT, 1, 1);
+    if (en)                                     // entry-NiN launches: the two forms entry_route admits
+        return r.bn == 128 && !r.ksw ? launch_halo_en_128(h, *en, grid, s)
+                                     : r.bn == 32 && r.ksw ? launch_halo_en_32k(h, *en, grid, s) : hipErrorInvalidValue;
     if (r.sp)
         return r.bn == 128 ? launch_halo_ts_128(h, grid, s, pk, r.mode, r.sp)
                            : r.bn == 64 ? (r.ksw ? launch_halo_ts_64k(h, grid, s, pk, r.mode, r.sp) : launch_halo_ts_64(h, grid, s, pk, r.mode, r.sp))
@@ -641,11 +644,13 @@ extern "C" int fusg_conv2d_route(const fusg_conv_desc* din) {
     return rc != FUSG_OK ? rc : r.family;
 }
 
-static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
+// `en`: source 0 is not read but computed by the entry NiN (fusg_conv2d_entry_nin below; the launch is a halo launch)
+static int conv2d_run(const fusg_conv_desc* din, const EntryK* en, void* stream) {
     fusg_conv_desc dd = *din;
     fusg_conv_desc* d = &dd;
     ConvRoute r;
     if (const int rc = route_conv(d, &r); rc != FUSG_OK) return rc;
+    FUSG_CHECK(!en || (r.family == FUSG_CONV_HALO && r.mode == 0 && r.sp == 0), "conv2d_entry_nin: not a split-fp16 halo launch");
     hipStream_t s = (hipStream_t)stream;
     const fusg_tensor& x0 = d->src0;
     const fusg_tensor& o = d->dst;
@@ -713,7 +718,7 @@ static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
             e = kGeneric[d->precision == FUSG_PREC_F16X3][d->tile](k, dim3(k.MT * k.NT, nphase, d->ksplit), s, pk,
                                                                    d->pad_mode != FUSG_PAD_ZERO || d->upsample != 0);
             break;
-        default:                  what = "conv2d halo launch"; e = run_halo(k, *d, r, s, pk); break;
+        default:                  what = "conv2d halo launch"; e = run_halo(k, *d, r, s, pk, en); break;
     }
     // K ranges over workgroups: the slab reduce (the generic kernels combine in-launch when given split-K counters)
     if (e == hipSuccess && k.ksplit > 1 && (r.family == FUSG_CONV_SMALL || k.counters == nullptr)) {
@@ -724,7 +729,63 @@ static int conv2d_impl(const fusg_conv_desc* din, void* stream) {
     }
     prof_end(0, s);
     if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return FUSG_ERR_LAUNCH; }
-    note_conv_kernel(r.family);
+    note_conv_kernel(en ? FUSG_CONV_HALO_ENTRY : r.family);
     return FUSG_OK;
 }
+static int conv2d_impl(const fusg_conv_desc* din, void* stream) { return conv2d_run(din, nullptr, stream); }
 extern "C" int fusg_conv2d(const fusg_conv_desc* din, void* stream) { return fusg::plan_dispatch(conv2d_impl, stream, din); }
+
+// ---- fusg_conv2d_entry_nin: a few-channel pointwise NiN and the 3x3 Residual that is its only reader, as one halo launch
+// Which form would run: 0 none (the pair stays two launches), 1 the 128-column tile (M split over the waves), 2 the 32-column
+// tile with K split over the waves - the form fusg_conv2d gives the Residual at this grid size, so that the sums keep their
+// order - or a negative FUSG_ERR_*.  Fills the halo launch's descriptor and the NiN's parameter block.
+static int entry_route(const fusg_conv_desc* res, const fusg_conv_desc* nin, fusg_conv_desc* dd, EntryK* en) {
+    FUSG_CHECK(res != nullptr && nin != nullptr, "conv2d_entry_nin: null descriptor");
+    const fusg_tensor& u = nin->src0;
+    const fusg_tensor& o = res->dst;
+    FUSG_CHECK(is_nhwc(u) && is_nhwc(o) && same_nhw(u, o) && o.data != u.data, "conv2d_entry_nin: u and dst must be distinct NHWC-physical f32 tensors with the same n, h, w");
+    // the NiN as the launch of its own that it would be (its output has dst's shape)
+    fusg_conv_desc nd = *nin;
+    nd.dst = o;
+    ConvRoute nr;
+    if (const int rc = route_conv(&nd, &nr); rc != FUSG_OK) return rc;
+    if (!(nr.family == FUSG_CONV_POINTWISE && nin->precision == FUSG_PREC_F16X3 && nin->pre_op == FUSG_PRE_ELU && nin->act == FUSG_ACT_NONE &&
+          !nin->res0.data && !nin->res1.data && nin->dst_c_off == 0 && nin->out_sy == 1 && nin->out_sx == 1 && nin->out_oy[0] == 0 &&
+          nin->out_ox[0] == 0 && nin->qh == u.h && nin->qw == u.w && nin->cout == nin->cout_pad && aligned16(nin->bias) && nin->k_pad >= nin->c0k))
+        return 0;
+    // the Residual: single-source k3 s1 p1 zero-padded ELU launch from the NiN's channels, its residual the NiN's output
+    if (!(res->precision == FUSG_PREC_F16X3 && res->pre_op == FUSG_PRE_ELU && res->act == FUSG_ACT_NONE && res->store_mode == FUSG_STORE_NORMAL &&
+          res->kh == 3 && res->kw == 3 && res->dil == 1 && res->pad_h == 1 && res->pad_w == 1 && res->stride == 1 && res->upsample == 0 &&
+          res->pad_mode == FUSG_PAD_ZERO && (res->nphase == 0 || res->nphase == 1) && !res->src1.data && !res->res1.data && !res->tile_list &&
+          !res->stats_out && res->tap_sparse == 0 && res->wfrag_order == 0 && res->dst_c_off == 0 && res->out_sy == 1 && res->out_sx == 1 &&
+          res->out_oy[0] == 0 && res->out_ox[0] == 0 && (res->q_oy | res->q_ox) == 0 && res->qh == o.h && res->qw == o.w &&
+          res->c0k == nin->cout && res->cout == res->c0k && res->cout_pad == res->cout && res->k_pad == 9 * res->c0k && o.c == res->cout &&
+          res->c0k == 128))                                    // (128 channels is what is built and tested)
+        return 0;
+    *dd = *res;
+    dd->src0 = o;                                              // x0's geometry; never read
+    dd->src1 = fusg_tensor{};
+    dd->res0 = fusg_tensor{};
+    ConvRoute r;
+    if (const int rc = route_conv(dd, &r); rc != FUSG_OK) return rc;
+    if (!(r.family == FUSG_CONV_HALO && r.mode == 0 && r.sp == 0 && !r.s2d && r.vec_epi)) return 0;
+    en->u = (const float*)u.data; en->usn = u.sn; en->ush = u.sh; en->usw = u.sw;
+    en->w_in = nin->wpack; en->b_in = nin->bias; en->cin = nin->c0k; en->kpad = nin->k_pad;
+    return r.bn == 128 && !r.ksw ? 1 : (r.bn == 32 && r.ksw ? 2 : 0);
+}
+static int entry_nin_impl(const fusg_conv_desc* res, const fusg_conv_desc* nin, void* stream) {
+    fusg_conv_desc dd;
+    EntryK en;
+    const int form = entry_route(res, nin, &dd, &en);
+    if (form < 0) return form;
+    if (form == 0) { set_error("conv2d_entry_nin: this pair does not fuse (fusg_conv2d_entry_nin_route == 0): run the two launches"); return FUSG_ERR_UNSUPPORTED; }
+    return conv2d_run(&dd, &en, stream);
+}
+extern "C" int fusg_conv2d_entry_nin(const fusg_conv_desc* res, const fusg_conv_desc* nin, void* stream) {
+    return fusg::plan_dispatch(entry_nin_impl, stream, res, nin);
+}
+extern "C" int fusg_conv2d_entry_nin_route(const fusg_conv_desc* res, const fusg_conv_desc* nin) {
+    fusg_conv_desc dd;
+    EntryK en;
+    return entry_route(res, nin, &dd, &en);
+}

@@ -93,6 +93,40 @@ struct HaloK {
     unsigned m_hw, m_nt, m_tpi, m_tx;
 };
 
+// Entry-NiN launches (conv_halo_en below, fusg_conv2d_entry_nin): the few-channel pointwise convolution that would have written
+// source 0.  u: its input, NHWC-physical fp32 with at most 8 channels (strides in elements); w_in / b_in: its fusg_conv_desc.wpack
+// (row pitch kpad) and bias; cin: its c0k (4 or 8).
+struct EntryK {
+    const float* u; long usn, ush, usw;
+    const float* w_in; const float* b_in;
+    int cin, kpad;
+};
+// first float of the entry-NiN region in dynamic LDS: behind the two halo images, 256-byte aligned
+__host__ __device__ inline int en_lds_floats(int HH, int RP) { return ((2 * HH * RP * (int)sizeof(_Float16) + 255) & ~255) / 4; }
+// conv_pointwise_small's chain for 4 output channels from the pixel's 8 (4) ELU'd inputs at `up`: k order 0, 4, 1, 5, 2, 6, 3, 7,
+// then fmaf(acc, 1, bias).  `two` false (at most 4 input channels): that kernel's k = 4 .. 7 steps are fmaf(0, 0, acc) with an acc that
+// is never -0 - identities, left out (as rp_nin of conv_respair.hip does).
+__device__ __forceinline__ f32x4 en_nin(const float* up, bool two, const f32x4 (&w)[8], const f32x4 bias) {
+    const f32x4 xa = *(const f32x4*)up;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (two) {
+        const f32x4 xb = *(const f32x4*)(up + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = fmaf(xb[e], w[4 + e][j], fmaf(xa[e], w[e][j], acc[j]));
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = fmaf(xa[e], w[e][j], acc[j]);
+    }
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = fmaf(acc[j], 1.f, bias[j]);
+    return v;
+}
+
 __device__ __forceinline__ void pix_offsets_yx(const ConvK& p, int b, int oy, int ox, PixOff& o) {
     long Y, X, cq = 0;
     if (p.store_mode == FUSG_STORE_D2S) { Y = 2 * oy; X = 2 * ox; }
@@ -152,13 +186,22 @@ constexpr unsigned tap_sparse_mask(int sp, int phase) {
 
 template <int TM, int TN, int WM, int WN, int PK, int NI, int MODE, int KS = 1>
 __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS)) void conv_halo_h3(const HaloK hk) {
-    constexpr int SP = 0;
+    constexpr int SP = 0, EN = 0;
+    const EntryK en = {};
 #include "conv_kernel_halo_body.inc"
 }
 // the tap-sparse sibling (SP = 1, 2): its own symbols, so the dense kernels above keep theirs
 template <int TM, int TN, int WM, int WN, int PK, int NI, int MODE, int KS, int SP>
 __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS)) void conv_halo_ts(const HaloK hk) {
     static_assert(SP != 0, "conv_halo_h3 is the dense kernel");
+    constexpr int EN = 0;
+    const EntryK en = {};
+#include "conv_kernel_halo_body.inc"
+}
+// the entry-NiN sibling (EN = 1): source 0 computed from `en.u`; the 3x3 ELU launch of the VUnet's InitBlock(6, 128) in its two forms
+template <int TM, int TN, int WM, int WN, int KS>
+__global__ __launch_bounds__(256, FUSG_HALO_WAVES) void conv_halo_en(const HaloK hk, const EntryK en) {
+    constexpr int PK = PK_ELU, NI = 6, MODE = 0, SP = 0, EN = 1;
 #include "conv_kernel_halo_body.inc"
 }
 
@@ -170,7 +213,8 @@ inline bool halo_fits(int HH, int HW) { return HH * HW * 8 <= 2560 && halo_lds_b
 
 // pick(ni): the instantiation for `ni` staged items per thread, or nullptr when there is none
 template <int TM, int TN, int WM, int WN, int KS, class Pick>
-hipError_t launch_halo_fn(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode, Pick pick) {      // mode: 0 split-fp16, 1 bf16, 2 exact fp32
+hipError_t launch_halo_fn(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode, Pick pick,       // mode: 0 split-fp16, 1 bf16, 2 exact fp32
+                          HaloK* prepared = nullptr, size_t* prepared_lds = nullptr) {                  // given: fill these instead of launching
     const int HP = k.HH * k.HW;
     size_t lds = halo_lds_bytes(k.HH, k.HW);
     size_t epi = (size_t)4 * TM * 32 * TN * 32 * sizeof(float);                                                     // epilogue detour (K split: the four partial tiles)
@@ -199,6 +243,7 @@ hipError_t launch_halo_fn(const HaloK& k, dim3 grid, hipStream_t s, int pk, int 
     kk.m_tpi = magic(ntiles, k.tiles_per_img);
     kk.m_tx = magic((long)k.tiles_per_img, k.tiles_x);
     if (!fits) return hipErrorInvalidValue;                    // > 2^32 / d tiles: not a shape this kernel is dispatched for
+    if (prepared) { *prepared = kk; *prepared_lds = lds; return hipSuccess; }
     return launch_kernel(fn, grid, lds, 96 * 1024 + TOUCH_LDS_BYTES, kk, s);
 }
 
@@ -236,6 +281,26 @@ hipError_t launch_halo_ts(const HaloK& k, dim3 grid, hipStream_t s, int pk, int 
     });
 }
 
+// entry-NiN launches: 3x3 dil 1 zero padding 1 (a 10 x 18 halo: 6 items per thread), split-fp16, ELU; the NiN's LDS region must fit
+// under the epilogue's detour.  Same LDS bytes, grid and reciprocals as the dense launch it stands for.
+template <int TM, int TN, int WM, int WN, int KS = 1>
+hipError_t launch_halo_en(const HaloK& k, const EntryK& en, dim3 grid, hipStream_t s) {
+    if (k.kh != 3 || k.kw != 3 || k.dil != 1 || k.pad_h != 1 || k.pad_w != 1 || k.s2d || k.c1k || k.tile_list || k.c.pad_mode != FUSG_PAD_ZERO ||
+        k.c.ups || !k.c.vec_epi)
+        return hipErrorInvalidValue;
+    const size_t need = ((size_t)en_lds_floats(k.HH, halo_row_pitch(k.HW)) + 6 * 32 * 8 + 9 * (size_t)k.c.C0) * sizeof(float);
+    if (need > (size_t)4 * TM * 32 * TN * 32 * sizeof(float)) return hipErrorInvalidValue;
+    HaloK kk;
+    size_t lds = 0;
+    const hipError_t e = launch_halo_fn<TM, TN, WM, WN, KS>(k, grid, s, PK_ELU, 0, [&](int ni) {
+        return ni == 6 ? (const void*)conv_halo_en<TM, TN, WM, WN, KS> : (const void*)nullptr; }, &kk, &lds);
+    if (e != hipSuccess) return e;
+    const void* fn = (const void*)conv_halo_en<TM, TN, WM, WN, KS>;
+    if (hipError_t e2 = ensure_dyn_lds(fn, 96 * 1024 + TOUCH_LDS_BYTES); e2 != hipSuccess) return e2;
+    void* args[] = {(void*)&kk, (void*)&en};
+    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+}
+
 hipError_t launch_halo_128(const HaloK&, dim3, hipStream_t, int, int);
 hipError_t launch_halo_64(const HaloK&, dim3, hipStream_t, int, int);
 hipError_t launch_halo_32(const HaloK&, dim3, hipStream_t, int, int);
@@ -247,5 +312,8 @@ hipError_t launch_halo_ts_64(const HaloK&, dim3, hipStream_t, int, int, int);
 hipError_t launch_halo_ts_32(const HaloK&, dim3, hipStream_t, int, int, int);
 hipError_t launch_halo_ts_32k(const HaloK&, dim3, hipStream_t, int, int, int);
 hipError_t launch_halo_ts_64k(const HaloK&, dim3, hipStream_t, int, int, int);
+// the entry-NiN siblings (conv_halo_en_*.hip): the two forms the VUnet's InitBlock(6, 128) launches
+hipError_t launch_halo_en_128(const HaloK&, const EntryK&, dim3, hipStream_t);
+hipError_t launch_halo_en_32k(const HaloK&, const EntryK&, dim3, hipStream_t);
 
 }  // namespace fusg

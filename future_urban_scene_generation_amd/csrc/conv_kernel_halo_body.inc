@@ -1,6 +1,9 @@
 // Body of the halo kernel (conv_kernel_halo.h), included once per kernel: conv_halo_h3 (SP = 0, the dense kernel - its text
 // is this file with every `if constexpr (SP != 0)` branch discarded, so its code does not depend on the sibling) and
 // conv_halo_ts (SP = 1, 2: tap-sparse).  In scope: TM, TN, WM, WN, PK, NI, MODE, KS, SP and the parameter block `hk`.
+// conv_halo_en (EN = 1, "entry NiN"): source 0 is not loaded but computed, x0 = b_in + sum_k w_in[k] elu(u[k]) from the <= 8
+// channels of `en.u` - conv_pointwise_small's fp32 chain - and the epilogue's residual is that chain again on the patch's own
+// pixels.  In scope then: EN and the parameter block `en` (EntryK); the other kernels see EN = 0 and an `en` nothing reads.
     constexpr bool BF = MODE == 1, F32 = MODE == 2;
     constexpr int CH = HALO_CH, HPITCH = HALO_PP;
     constexpr int CPP = CH / 4;                    // 16-byte fp32 items per halo pixel
@@ -75,6 +78,49 @@
     }
     const long img_pix0 = (long)b * p.H * p.W;
 
+    // ---- entry NiN: elu(u) of the halo's pixels ([NI * 32 pixels][8] fp32: the overrun items of the last pass read zeros), the NiN's
+    // weights [8][C0] and bias [C0] sit in LDS above the two halo images until the epilogue's detour takes the space
+    [[maybe_unused]] float* enU = (float*)smem_h + en_lds_floats(hk.HH, hk.RP);
+    [[maybe_unused]] float* enW = enU + NI * 32 * 8;
+    [[maybe_unused]] float* enB = enW + 8 * p.C0;
+    [[maybe_unused]] const bool en_two = en.cin > 4;           // u has a second 16-byte piece per pixel (wave-uniform)
+    if constexpr (EN != 0) {
+        static_assert(PK == PK_ELU && MODE == 0 && SP == 0 && TN == 1, "entry NiN: the split-fp16 ELU launch, one 32-column tile per wave");
+        for (int i = t; i < NI * 64; i += 256) {
+            const int pix = i >> 1, hf = i & 1;
+            const int hy = fdiv(pix, hk.m_hw), hx = pix - hy * hk.HW;
+            const int vy = oy0 - hk.pad_h + hy, vx = ox0 - hk.pad_w + hx;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (pix < HP && (unsigned)vy < (unsigned)p.Hv && (unsigned)vx < (unsigned)p.Wv && (hf == 0 || en_two)) {
+                v = *(const f32x4*)(en.u + b * en.usn + vy * en.ush + vx * en.usw + hf * 4);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) v[c] = elu1(v[c]);
+            }
+            *(f32x4*)(enU + i * 4) = v;
+        }
+        for (int n = t; n < p.C0; n += 256) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) enW[c * p.C0 + n] = c < en.cin ? en.w_in[(long)n * en.kpad + c] : 0.f;
+            enB[n] = en.b_in[n];
+        }
+        __syncthreads();
+    }
+    // x0 of the epilogue's rows (TMx * 32 rows from patch row index `rows0`, 4 columns from ncol_base per lane: epilogue_rows' map)
+    [[maybe_unused]] auto en_res = [&](auto tmc, ResRegs<decltype(tmc)::value, 1>& rr, int rows0, int ncol_base) __attribute__((always_inline)) {
+        const int n = ncol_base + (lane & 7) * 4;
+        f32x4 w[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) w[c] = *(const f32x4*)(enW + c * p.C0 + n);
+        const f32x4 bias = *(const f32x4*)(enB + n);
+#pragma unroll
+        for (int i = 0; i < decltype(tmc)::value; ++i)
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int r = rows0 + i * 32 + it * 8 + (lane >> 3);
+                rr.v[i][it] = en_nin(enU + (((r >> 4) + hk.pad_h) * hk.HW + (r & 15) + hk.pad_w) * 8, en_two, w, bias);
+            }
+    };
+
     // this wave's weight fragments: tiles (nt*BN/32 + wn*TN + j), j < TN
     constexpr int FPT = BF ? 2 : 4;                            // fragments (1 KiB) per 32-column tile: [ct] or [ct][hi|lo]
     const _Float16* wfr = hk.wfrag + ((long)(nt * (BN / 32) + wn * TN) * FPT * 64 + lane) * 8;
@@ -124,6 +170,21 @@
 
     // (q, cq) = quadrant and chunk within it of chunk cg in the quadrant form (the callers count them up: no division)
     auto halo_issue = [&](HSet& S, int cg, int q, int cq) __attribute__((always_inline)) {
+        if constexpr (EN != 0) {
+            // the chunk's 4 channels of this thread's items, computed where the loads would be issued: the chain runs beside the
+            // taps of the chunk before; a pixel outside the image is conv A's zero padding, not NiN(0) + bias
+            const int n0 = cg * CH + kc * 4;
+            f32x4 w[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) w[c] = *(const f32x4*)(enW + c * p.C0 + n0);
+            const f32x4 bias = *(const f32x4*)(enB + n0);
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                const f32x4 v = en_nin(enU + ((t + 256 * j) >> 3) * 8, en_two, w, bias);
+                S.r[j] = ((hvalid >> j) & 1u) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            return;
+        }
         const bool s1 = cg >= nch0;
         const float* base = s1 ? p.src1 : p.src0;
         const int Cs = s1 ? p.Cs1 : p.Cs0;
@@ -382,6 +443,8 @@
         // ---- K split: partial tiles -> LDS ([wave][128 rows][32 columns] fp32, over the halo images), summed in wave order by
         // the wave that finishes those rows: wave (wk, wn) takes rows 128 / KS * wk ... of column tile wn
         constexpr int RW = 128 / KS, TME = RW / 32;
+        [[maybe_unused]] ResRegs<TME, 1> rrk;                          // entry NiN: x0 of the rows this wave finishes, while its LDS is alive
+        if constexpr (EN != 0) en_res(std::integral_constant<int, TME>{}, rrk, RW * wk, nt * BN + wn * 32);
         __syncthreads();                                               // every wave is done with the halo images
         float* slabs = (float*)smem_h;
         float* mine = slabs + wave * (128 * 32);
@@ -410,6 +473,7 @@
         };
         if (p.vec_epi) {
             ResRegs<TME, 1> none;
+            if constexpr (EN != 0) epilogue_rows<TME, 1>(p, dstw, lane, nt * BN + wn * 32, pixk, statk, rrk, true); else
             epilogue_rows<TME, 1>(p, dstw, lane, nt * BN + wn * 32, pixk, statk, none, false);
         } else {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -460,7 +524,8 @@
             return;
         } else {
         ResRegs<TM, TN> rr;
-        const bool pre = p.res0 != nullptr;
+        const bool pre = EN != 0 || p.res0 != nullptr;
+        if constexpr (EN != 0) en_res(std::integral_constant<int, TM>{}, rr, wm * TM * 32, nt * BN + wn * TN * 32); else
         if (pre) res_prefetch<TM, TN>(p, lane, nt * BN + wn * TN * 32, pixfn, rr);     // in flight across the barrier and the LDS detour
         __syncthreads();
         float* wlds = (float*)smem_h + wave * (TM * 32 * TN * 32);

@@ -683,11 +683,74 @@ def respair(res_a: ConvPlan, res_b: ConvPlan, nin_b: ConvPlan, nin_c: ConvPlan, 
     return s1, kb, kc
 
 
+VU_ENTRY_NIN = not _env_set("FUSG_NO_ENTRY_NIN")  # the VUnet's 6 -> 128 entry NiN inside the Residual that reads it (tests flip it)
+
+
+def _entry_nin_descs(nin: ConvPlan, res: ConvPlan, u: torch.Tensor, out: torch.Tensor, precision: Optional[str] = None,
+                     ksplit: int = 0, plan: bool = True):
+    """The two descriptors fusg_conv2d_entry_nin takes: the NiN's on u and the Residual's.  x0 = nin(elu(u)) is never
+    materialised: `out`, which has its shape, stands in as the Residual's source (the library ignores src0 / res0 there)."""
+    dn, _ = _conv_desc(nin, u, pre_op=L.PRE_ELU, out=out, precision=precision)
+    dr, _ = _conv_desc(res, out, pre_op=L.PRE_ELU, out=out, precision=precision, ksplit=ksplit)
+    for d in (dn, dr) if plan else ():
+        L.lib().fusg_conv2d_plan(C.byref(d))
+    return dr, dn
+
+
+def entry_nin_form(nin: ConvPlan, res: ConvPlan, u: torch.Tensor, precision: Optional[str] = None, ksplit: int = 0) -> int:
+    """Which form of the halo kernel would run  res(elu(x0)) + x0,  x0 = nin(elu(u)),  as ONE launch (fusg_conv2d_entry_nin_route):
+    0 none - the pair stays two launches -, 1 the 128-column tile with the M split over the waves, 2 the 32-column tile with the K
+    split over the waves.  Fuses only in f16x3 on NHWC tensors, where the NiN is a k1 launch from at most 8 channels that
+    fusg_conv2d would put on the pointwise kernel and the Residual a single-source k3 s1 p1 zero-padded launch from the NiN's 128
+    channels that it would put on the halo kernel in one of those two forms - the fused launch then writes their bytes.  f32, bf16
+    and the range guard's fp32 redo keep the two launches.  ksplit: the Residual's, as ops.conv takes it (0: planned - small grids
+    then get a generic split-K launch and stay unfused).  Asked once per shape and per the switches the router reads per call."""
+    prec = precision or PRECISION
+    if prec != "f16x3" or not is_nhwc(u):
+        return 0
+    if not (nin.kh == 1 and nin.kw == 1 and nin.nphase == 1 and nin.c1k == 0 and nin.c0k <= 8 and res.kh == 3 and res.kw == 3
+            and res.nphase == 1 and res.c1k == 0 and res.c0k == nin.cout and res.cout == nin.cout and u.shape[1] == nin.c_split[0]):
+        return 0
+    b, c, h, w = u.shape
+    key = (id(nin), b, c, h, w, u.stride(3), str(u.device), int(ksplit),
+           _env_set("FUSG_NO_SMALL"), _env_set("FUSG_NO_POINTWISE"), _env_set("FUSG_SMALL_KSPLIT"))
+    memo = res.__dict__.setdefault("_entry_nin_routes", {})
+    if key not in memo:
+        # x0 / the output stand in as one 8 x 16 image whose descriptors are stretched to the real extents: the route reads
+        # shapes only, and a real stand-in would be a 1 GB allocation at B = 32
+        t = nhwc_empty(1, res.cout, 8, 16, u.device)
+        dr, dn = _entry_nin_descs(nin, res, u, t, prec, ksplit=ksplit, plan=False)
+        for tt in (dr.src0, dr.dst):
+            tt.n, tt.h, tt.w, tt.sh, tt.sn = b, h, w, w * tt.sw, h * w * tt.sw
+        dr.qh, dr.qw = res.out_hw(h, w)
+        for d in (dn, dr):
+            L.lib().fusg_conv2d_plan(C.byref(d))
+        memo[key] = max(0, int(L.lib().fusg_conv2d_entry_nin_route(C.byref(dr), C.byref(dn))))
+    return memo[key]
+
+
+def entry_nin_ok(nin: ConvPlan, res: ConvPlan, u: torch.Tensor, precision: Optional[str] = None) -> bool:
+    """Does `entry_nin` apply (see entry_nin_form)?  False with VU_ENTRY_NIN off (FUSG_NO_ENTRY_NIN=1 at import)."""
+    return VU_ENTRY_NIN and entry_nin_form(nin, res, u, precision) != 0
+
+
+def entry_nin(nin: ConvPlan, res: ConvPlan, u: torch.Tensor, out: Optional[torch.Tensor] = None, ksplit: int = 0) -> torch.Tensor:
+    """res(elu(x0)) + x0  with  x0 = nin(elu(u))  in one halo launch (fusg_conv2d_entry_nin) - the bytes of the two `conv`
+    launches it replaces; x0 is computed in the staging and never written.  Raises where entry_nin_form is 0."""
+    b, _, h, w = u.shape
+    if out is None:
+        out = nhwc_empty(b, res.cout, h, w, u.device)
+    dr, dn = _entry_nin_descs(nin, res, u, out, ksplit=ksplit)
+    L.check(L.lib().fusg_conv2d_entry_nin(C.byref(dr), C.byref(dn), stream_ptr()), "conv2d_entry_nin")
+    return out
+
+
 def last_conv_kernel() -> int:
     """Kernel family of the last conv launch issued by this thread (fusg_last_conv_kernel): 0 generic fp32,
     1 generic split-fp16, 2 halo, 3 halo in parity-quadrant (stride-2) form, 4 tap-unit kernel (few-channel stems),
     5 halo in bf16 mode, 6 fused hourglass Bottleneck, 7 pointwise-from-few-channels streaming kernel, 8 small-image kernel,
-    9 halo in exact fp32, 10 tap-unit in exact fp32, 11 tap-unit in bf16 mode, 12 fused VUnet Residual pair (respair)."""
+    9 halo in exact fp32, 10 tap-unit in exact fp32, 11 tap-unit in bf16 mode, 12 fused VUnet Residual pair (respair),
+    13 halo kernel with the entry NiN computed in its staging (entry_nin)."""
     return int(L.lib().fusg_last_conv_kernel())
 
 

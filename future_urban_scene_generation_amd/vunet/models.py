@@ -349,8 +349,14 @@ class Vunet_fix_res(FusedNet):
         return mu, z
 
     def _init_block(self, name, x):
-        x = self._nin(name + ".nin", x)
-        s0 = x = self._residual(name + ".residual_0", x)
+        # the entry NiN's output is read by residual_0 alone: where that pair qualifies (app_encoder_1: 6 -> 128) the NiN is
+        # computed inside residual_0's halo staging and never written (ops.entry_nin); else the two launches
+        nin, res = self._plans[name + ".nin.layers.1"], self._plans[name + ".residual_0.layers.2"]
+        if ops.entry_nin_ok(nin, res, x):
+            s0 = x = ops.entry_nin(nin, res, x)
+        else:
+            x = self._nin(name + ".nin", x)
+            s0 = x = self._residual(name + ".residual_0", x)
         s1 = x = self._residual(name + ".residual_1", x)
         return x, [s0, s1]
 

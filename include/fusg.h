@@ -297,6 +297,24 @@ typedef struct fusg_respair_desc {
 } fusg_respair_desc;
 int fusg_vunet_respair(const fusg_respair_desc* d, void* stream);
 
+/*
+ * The entry of the VUnet's InitBlock(6, 128) (vunet/models.py: app_encoder_1) as ONE halo launch (csrc/conv_kernel_halo.h,
+ * conv_halo_en; added without a version step: the entry points are new, nothing existing changed):
+ *   x0 = NiN(elu(u)) + bias_in          1x1 from at most 8 channels - never written
+ *   dst = conv3x3(elu(x0)) + bias + x0  zero padding 1
+ * `nin`: the descriptor of the NiN as fusg_conv2d would take it (src0 = u, FUSG_PRE_ELU, F16X3; its dst is ignored) - a launch
+ * the router puts on the pointwise kernel.  `res`: the descriptor of the 3x3 Residual as fusg_conv2d would take it (FUSG_PRE_ELU,
+ * F16X3, k3 stride 1 pad 1 dil 1, zero padding, one source of nin.cout = cout = 128 channels); its src0 and res0 are ignored -
+ * both are x0, whose shape is dst's.  The halo staging computes x0 with the pointwise kernel's fp32 chain, pixels outside the
+ * image are staged as zero, and the epilogue adds the same chain on the patch's own pixels: dst has the bytes of the two
+ * launches, and *res.status is raised as the Residual's own launch raises it.
+ * fusg_conv2d_entry_nin_route: 0 - this pair does not fuse (fusg_conv2d_entry_nin then returns FUSG_ERR_UNSUPPORTED); 1 - the
+ * 128-column tile, M split over the waves; 2 - the 32-column tile, K split over the waves: the form fusg_conv2d gives the
+ * Residual at this grid size (grids for which it picks another form stay two launches); negative: FUSG_ERR_*.  No device work.
+ */
+int fusg_conv2d_entry_nin(const fusg_conv_desc* res, const fusg_conv_desc* nin, void* stream);
+int fusg_conv2d_entry_nin_route(const fusg_conv_desc* res, const fusg_conv_desc* nin);
+
 /* Load-time weight pre-packing on the HOST (no device work): everything fusg_conv_desc needs for one nn.Conv2d-style
  * filter weight[cout][cin][kh][kw] (torch layout, correlation form) whose input channels come from one source (c0 = cin)
  * or from two concatenated sources (the first c0 channels from src0: torch.cat([x, skip], 1) fused into the gather).
@@ -742,7 +760,8 @@ enum { FUSG_CONV_GENERIC_F32 = 0, FUSG_CONV_GENERIC_F16X3 = 1, FUSG_CONV_HALO = 
        FUSG_CONV_HALO_F32 = 9 /* halo kernel in exact fp32 (v_mfma_f32_16x16x4_f32, fusg_conv_desc.wfrag_f32) */,
        FUSG_CONV_TAPUNIT_F32 = 10 /* few-channel stems in exact fp32 (csrc/conv_kernel_tapunit_f32.h; wfrag_order 2 + wfrag_f32) */,
        FUSG_CONV_TAPUNIT_BF16 = 11 /* few-channel stems in single-pass bf16 (FUSG_PREC_BF16; wfrag_order 2 + wfrag_bf16) */,
-       FUSG_CONV_RESPAIR = 12 /* fusg_vunet_respair */ };
+       FUSG_CONV_RESPAIR = 12 /* fusg_vunet_respair */,
+       FUSG_CONV_HALO_ENTRY = 13 /* fusg_conv2d_entry_nin: halo kernel with the entry NiN computed in its staging */ };
 int         fusg_last_conv_kernel(void);
 const char* fusg_arch(void);                      /* "gfx950" */
 /* sizeof(fusg_tensor) / sizeof(fusg_conv_desc) as compiled, so that FFI bindings can verify their
