@@ -593,6 +593,82 @@ __device__ __forceinline__ int frame_of_row(const FrameTab& t, int row) {
     return f;
 }
 
+// fill_poly_planes_batch_kernel with the frame a property of the JOB: blockIdx.y = job * n_planes + plane, and the table's rows
+// count jobs.  A frame without jobs is never looked up, so never read.  The loop is that kernel's, statement for statement (a
+// shared device function changed its instructions, tools/isa_digest.py): what one of the two learns, the other is taught.
+__global__ __launch_bounds__(256) void fill_poly_planes_frames_kernel(U8View frame, FrameTab t, const int* __restrict__ pts_xy,
+                                                                      const int* __restrict__ nverts, int n_planes, U8View dst,
+                                                                      long plane_bytes) {
+    __shared__ int spx[MAXV], spy[MAXV], snv;
+    const int q = blockIdx.y, tid = threadIdx.x;
+    frame.p = const_cast<unsigned char*>(t.img[frame_of_row(t, q / n_planes)]);       // uniform per block
+    if (tid < MAXV) {
+        spx[tid] = pts_xy[((long)q * MAXV + tid) * 2];
+        spy[tid] = pts_xy[((long)q * MAXV + tid) * 2 + 1];
+    }
+    if (tid == 0) {
+        const int n = nverts[q];
+        snv = n < 0 ? 0 : (n > MAXV ? MAXV : n);
+    }
+    __syncthreads();
+    const int nv = snv, W = dst.w, H = dst.h;
+    long bx0 = W, by0 = H, bx1 = -1, by1 = -1;
+    bool wide = false;
+    for (int i = 0; i < nv; ++i) {
+        const long x = spx[i], y = spy[i];
+        bx0 = x < bx0 ? x : bx0; bx1 = x > bx1 ? x : bx1; by0 = y < by0 ? y : by0; by1 = y > by1 ? y : by1;
+        wide = wide || x < -POLY_BOX_SAFE || x > POLY_BOX_SAFE || y < -POLY_BOX_SAFE || y > POLY_BOX_SAFE;
+    }
+    if (wide) { bx0 = 0; by0 = 0; bx1 = W - 1; by1 = H - 1; }
+    bx0 = bx0 < 0 ? 0 : bx0; by0 = by0 < 0 ? 0 : by0; bx1 = bx1 > W - 1 ? W - 1 : bx1; by1 = by1 > H - 1 ? H - 1 : by1;
+    const bool empty = bx0 > bx1 || by0 > by1;
+    unsigned char* d = dst.p + (long)q * dst.sn;
+    const long head = ((16 - (long)((unsigned long)d & 15)) & 15) < plane_bytes ? ((16 - (long)((unsigned long)d & 15)) & 15) : plane_bytes;
+    const long pieces = 1 + (plane_bytes - head + 15) / 16;
+    for (long k = (long)blockIdx.x * 256 + tid; k < pieces; k += (long)gridDim.x * 256) {
+        const long s = k == 0 ? 0 : head + 16 * (k - 1);
+        const long e0 = k == 0 ? head : s + 16;
+        const long e = e0 < plane_bytes ? e0 : plane_bytes;
+        if (s >= e) continue;
+        const long p0 = s / 3, p1 = (e - 1) / 3;
+        const long y0 = p0 / W, y1 = p1 / W;
+        bool zero = empty || y1 < by0 || y0 > by1;
+        if (!zero && y0 == y1) zero = p1 - y1 * W < bx0 || p0 - y0 * W > bx1;
+        unsigned char b[16];
+        if (zero) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) b[i] = 0;
+        } else {
+            unsigned in = 0;                                              // bit (pixel - p0): inside or on the outline
+            for (long p = p0; p <= p1; ++p) {
+                const long y = p / W, x = p - y * W;
+                if (x >= bx0 && x <= bx1 && y >= by0 && y <= by1 && poly_inside((int)x, (int)y, nv, spx, spy)) in |= 1u << (p - p0);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const long o = s + i, p = o / 3;
+                b[i] = 0;
+                if (o < e && ((in >> (p - p0)) & 1)) {
+                    const long y = p / W, x = p - y * W;
+                    b[i] = frame.p[y * frame.sh + x * frame.sw + (o - p * 3)];
+                }
+            }
+        }
+        if (e - s == 16 && k > 0) {                                       // 16-byte aligned by construction
+            uint4 v;
+            v.x = b[0] | (b[1] << 8) | (b[2] << 16) | ((unsigned)b[3] << 24);
+            v.y = b[4] | (b[5] << 8) | (b[6] << 16) | ((unsigned)b[7] << 24);
+            v.z = b[8] | (b[9] << 8) | (b[10] << 16) | ((unsigned)b[11] << 24);
+            v.w = b[12] | (b[13] << 8) | (b[14] << 16) | ((unsigned)b[15] << 24);
+            *reinterpret_cast<uint4*>(d + s) = v;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (s + i < e) d[s + i] = b[i];
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void crop_resize_frames_kernel(CropIn a, FrameTab t, long per_row) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= per_row) return;
@@ -905,6 +981,38 @@ static int frame_table(const char* what, const void* const* frames, const int32_
     FUSG_CHECK((long)frame_rows[n_frames] == rows, "%s: the row offsets end at %d, the tensors hold %ld rows", what, frame_rows[n_frames], rows);
     FUSG_CHECK(rows <= 65535, "%s: %ld rows (at most 65535 per launch)", what, rows);
     return FUSG_OK;
+}
+
+static int fill_poly_planes_frames_u8_impl(FrameTab t, int32_t H, int32_t W, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
+                                           int32_t n_planes, const fusg_tensor* dst, void* stream) {
+    const U8View frame{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
+    const long plane_bytes = 3 * dst->h * dst->w;
+    const long pieces = 1 + (plane_bytes + 15) / 16;
+    const unsigned bx = (unsigned)((pieces + 255) / 256);
+    hipLaunchKernelGGL(fill_poly_planes_frames_kernel, dim3(bx, (unsigned)(n_jobs * n_planes)), dim3(256), 0, (hipStream_t)stream, frame, t,
+                       (const int*)pts_xy, (const int*)nverts, (int)n_planes, u8view(*dst), plane_bytes);
+    FUSG_LAUNCH_CHECK("fill_poly_planes_frames_u8");
+    return FUSG_OK;
+}
+extern "C" int fusg_fill_poly_planes_frames_u8(const void* const* frames, const int32_t* frame_rows, int32_t n_frames, int32_t H, int32_t W,
+                                               const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs, int32_t n_planes,
+                                               const fusg_tensor* dst, void* stream) {
+    const char* what = "fill_poly_planes_frames_u8";
+    FUSG_CHECK(n_jobs >= 0, "%s: n_jobs = %d", what, n_jobs);
+    FrameTab t;
+    if (int rc = frame_table(what, frames, frame_rows, n_frames, n_jobs, t)) return rc;
+    FUSG_CHECK(pts_xy && nverts && dst, "%s: pts_xy, nverts or dst is null", what);
+    FUSG_CHECK(n_planes >= 1 && n_planes <= 8 && (long)n_jobs * n_planes <= 65535, "%s: arguments (1..8 planes, n_jobs * n_planes <= 65535)", what);
+    FUSG_CHECK(H >= 1 && W >= 1 && H < 32768 && W < 32768, "%s: frames of %d x %d", what, H, W);
+    if (n_jobs == 0) return FUSG_OK;
+    FUSG_CHECK(is_u8_hwc(*dst, 3) && dst->n == (long)n_jobs * n_planes && dst->h == H && dst->w == W && dst->sw == 3 && dst->sh == 3 * dst->w &&
+               dst->sn >= 3 * dst->h * dst->w, "%s: shapes (dst [n_jobs * n_planes] planes of H x W x 3, contiguous rows)", what);
+    for (int f = 0; f < n_frames; ++f) {
+        const unsigned char* b = (const unsigned char*)frames[f];
+        const unsigned char* d0 = (const unsigned char*)dst->data;
+        FUSG_CHECK(b + 3L * H * W <= d0 || b >= d0 + (dst->n - 1) * dst->sn + 3L * H * W, "%s: frame %d overlaps dst (the frames are read only)", what, f);
+    }
+    return fusg::plan_dispatch(fill_poly_planes_frames_u8_impl, stream, t, H, W, pts_xy, nverts, n_jobs, n_planes, dst);
 }
 
 static int crop_resize_frames_impl(FrameTab t, int32_t H, int32_t W, const int32_t* geom, const fusg_tensor* dst, int32_t mode, Norm3 nm,

@@ -310,6 +310,47 @@ def later_geometry_batch_rows(scenes: Sequence[Dict], vehicles: Sequence[int], d
     return seeds, inps[0] is not None if inps else False
 
 
+def frame_geometry_batch_rows(scenes: Sequence[Dict], device_pose: bool, device_homography: bool, inpaint: bool = False,
+                              classifier: bool = False) -> Tuple[List[int], Optional[List[int]], bool]:
+    """What `run_frames_batched_geometry` checks before it issues anything, for geometry-mode first frames ('frame', 'bboxes',
+    'focals', 'centers', no 'masks'; pure Python apart from reading the frames' shapes).  The batched stage is the per-frame DEVICE
+    path's arithmetic row by row, so it needs a pipeline built with device_pose=True and device_homography=True; the frames have
+    one size; either every scene that has vehicles carries 'vehicle_seeds' or none does, and with the inpainting networks
+    (`inpaint`) the same holds for 'inpaint'; without a CAD classifier every scene that has vehicles carries 'cad_idx' [V_f].
+    ValueError otherwise.  Returns (vehicles per scene, the seeds of all rows scene-major or None, whether the pass inpaints)."""
+    import numpy as np
+    if not device_pose or not device_homography:
+        raise ValueError("run_frames_batched_geometry: geometry-mode first frames are batched only by a pipeline built with "
+                         f"device_pose=True and device_homography=True (device_pose={bool(device_pose)}, "
+                         f"device_homography={bool(device_homography)}): the batched stage is that path's arithmetic, row by row")
+    for f, sc in enumerate(scenes):
+        if "masks" in sc:
+            raise ValueError(f"run_frames_batched_geometry: scene {f} is not a geometry-mode scene (it carries 'masks')")
+    sizes = {tuple(sc["frame"].shape) for sc in scenes}
+    if len(sizes) > 1:
+        raise ValueError(f"run_frames_batched_geometry: the frames of one call have one size, got {sorted(sizes)}")
+    counts = [int(np.asarray(sc["bboxes"]).reshape(-1, 4).shape[0]) for sc in scenes]
+    seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
+    live = [(f, sc) for f, (sc, c) in enumerate(zip(scenes, counts)) if c > 0]
+    has_inpaint = False
+    if inpaint:
+        inps = [(f, sc.get("inpaint")) for f, sc in live]
+        if any(i is not None for _, i in inps) and not all(i is not None for _, i in inps):
+            raise ValueError("run_frames_batched_geometry: either every scene that has vehicles carries 'inpaint' or none does "
+                             f"(scenes without: {[f for f, i in inps if i is None]})")
+        for _, i in inps:
+            inpaint_scene_form(i)                                 # (ValueError for a missing or malformed entry, before anything is issued)
+        has_inpaint = bool(inps)
+    if not classifier:
+        for f, sc in live:
+            if sc.get("cad_idx") is None:
+                raise ValueError(f"geometry mode: scene {f} needs 'cad_idx' [V] (or a pipeline built with cad=True)")
+            if int(np.asarray(sc["cad_idx"]).reshape(-1).shape[0]) != counts[f]:
+                raise ValueError(f"run_frames_batched_geometry: scene {f} carries {int(np.asarray(sc['cad_idx']).reshape(-1).shape[0])} "
+                                 f"'cad_idx' entries for {counts[f]} vehicles")
+    return counts, seeds, has_inpaint
+
+
 def _tensors(o):
     """Every tensor inside a nested dict / list / tuple, depth first."""
     if torch.is_tensor(o):
@@ -2096,6 +2137,206 @@ class VehiclePipeline:
                 row += n
             out.extend(res)
         return out
+
+    def run_frames_batched_geometry(self, scenes, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
+                                    pad: Optional[bool] = None, batch_geometry: bool = True) -> list:
+        """`run_frames_batched` for GEOMETRY-MODE first frames (a pipeline with cad_bank, scenes without 'masks': 'frame',
+        'bboxes', 'focals', 'centers' (+ 'cad_idx' [V_f] without a CAD classifier, optional 'background', 'inpaint',
+        'vehicle_seeds')): the first frames of several scenes as ONE pass per group, render included, with one device-to-host copy
+        per group where `run_frames` takes one blocking copy per frame between its render and its plane warp.  Rows are
+        scene-major (`frame_batch_offsets`); grouping and padding are `run_frames_batched`'s (`frame_batch_groups`,
+        `frame_batch_pad`, max_batch, pad), and each group is one range-guarded call: a raised status word redoes the group in
+        exact fp32 under the RNG state it was issued with.  Order of work per group, on the current stream:
+          1. the keypoint stage, eager, at the group's real N rows: `frame_ops.crop_resize_frames` (box crop, hourglass input),
+             hourglass (+ CAD classifier), `argmax_hw`, `keypoints_to_frame`, the pose fit with per-row focals and centers and the
+             bank's keypoints (an index outside the bank is clamped for the fit only).  It stays eager as in `_geometry_frame`: the
+             plan cache holds FRAME_PLANS plans, and a second plan per padded row count would evict the first;
+          2. `render.first_geometry_batch_device`: pose selection and geometry (one launch per camera), render, plane visibility,
+             the gate, the plane cut-outs of every row from its own frame (fusg_fill_poly_planes_frames_u8);
+          3. `plane_homographies_device` on the device corner points and gated visibilities -> `warp_planes_fitted` ->
+             `mask_bbox_geom` -> `icn_inputs_device` -> `frame_ops.vunet_inputs_frames` (-> `_inpaint_inputs_ragged`);
+          4. `_run` with the keypoints (and CAD logits) given, at N rows or the padded rows; replay=True: one recorded plan under
+             ("frame_batch", rows, precision, "kp_given"[, "inpaint"][, "cad"]);
+          5. `lab2bgr`, one ragged paste per composite with the gated box rows, then ONE `ops.d2h` of the stage's small buffer.
+        A vehicle whose render is empty stays in the batch as an INERT row: its visibilities are zero (no plane is warped for it),
+        its mask is empty (its crop is a zero row, nothing is pasted), its box row is zeroed (not inpainted into the frame), and
+        its network outputs are dropped from the result - it is listed in 'skipped'.
+        Returns, per scene, `run_frame`'s geometry-mode dict (`_geometry_frame`): 'kp_idx', 'kp_xy', 'pose' (+ 'cad_idx') of every
+        vehicle; 'icn_u8', 'vunet_u8', 'geom' (+ 'inpaint_u8') of the kept ones; 'frame_icn', 'frame_vunet'; 'geometry' (all ten
+        keys, every vehicle); 'skipped'; 'state' with state['geometry'] as `run_frame` builds it, which `run_later_frame` and
+        `run_later_frames_batched_geometry` take unchanged.  A scene without vehicles gets `run_frames_batched`'s no-vehicle
+        shape plus 'geometry' (zero rows) and 'skipped' == [].  A 'cad_idx' outside the bank raises IndexError after the read-back.
+        The batch's crops are not bit for bit those of per-frame passes where the batch sizes differ (see `run_frames_batched`);
+        the stage - render, cut-outs, corner points, poses - is the per-frame device path's, byte for byte.
+        Fallbacks, with the results of today: batch_geometry=False is `run_frames_batched` (whose geometry-mode branch is
+        `run_frames`); a list without geometry-mode scenes ignores the flag; a process group of more than one rank goes through
+        `run_frames`.  ValueError before anything is launched: a pipeline without device_pose=True and device_homography=True, a
+        list that mixes geometry-mode and given-geometry scenes, frames of different sizes, 'vehicle_seeds' or 'inpaint' present
+        for some scenes with vehicles and absent for others, no 'cad_idx' and no classifier.
+        Memory: 34 * H * W bytes per row (sketch 3, mask 1, planes 15, warped planes 15): 31 MB at 720 x 1280, 2.0 GB for 64 rows.
+        Without 'vehicle_seeds' the inert rows and the padding rows draw noise too, so the unseeded noise stream is not that of
+        per-frame passes over the kept vehicles."""
+        scenes = list(scenes)
+        if not scenes:
+            return []
+        geo = [self._is_geometry(sc) for sc in scenes]
+        if any(geo) and not all(geo):
+            raise ValueError("run_frames_batched_geometry: the list mixes geometry-mode scenes (no 'masks') and given-geometry scenes "
+                             f"(geometry-mode: {[f for f, g in enumerate(geo) if g]})")
+        if not batch_geometry or not any(geo):
+            return self.run_frames_batched(scenes, replay=replay, check=check, max_batch=max_batch, pad=pad)
+        if not _one_rank(self.group):
+            return list(self.run_frames(scenes, replay=replay))
+        counts, seeds, _ = frame_geometry_batch_rows(scenes, self.device_pose, self.device_homography, self.inpaint, self.cad is not None)
+        if max_batch is None:
+            max_batch = LATER_MAX_BATCH
+        pad = bool(replay) if pad is None else bool(pad)
+        out = []
+        for lo, hi in frame_batch_groups(counts, max_batch):
+            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
+            rows = frame_batch_pad(sum(counts[lo:hi]), max_batch) if pad else None
+            out.extend(self._guarded(self._run_frame_batch_geometry, (scenes[lo:hi], replay, rows), check, rng))
+        return out
+
+    @torch.no_grad()
+    def _run_frame_batch_geometry(self, scenes, replay=False, rows=None) -> list:
+        """One group of `run_frames_batched_geometry`: everything through the paste is queued, then the stage's small buffer is
+        read back ONCE and the per-scene results of `_geometry_frame` are cut from the stacked ones.  rows: the row count the
+        networks run at (>= N, the padding rows zero); None: N."""
+        import numpy as np
+
+        from . import frame_ops as fo
+        from . import ops
+        from . import render as rd
+        from .utils.pnp_utils import cpc_fit_device
+        from .warp_learn import planes_utils as pu
+        dev, bank, R = self.device, self.cad_bank, 256
+        boxes = [np.asarray(sc["bboxes"]).reshape(-1, 4) for sc in scenes]
+        counts = [int(b.shape[0]) for b in boxes]
+        offs = frame_batch_offsets(counts)
+        N = offs[-1]
+        frames = [sc["frame"] for sc in scenes]
+        H, W, _ = frames[0].shape
+        Ks = [rd.intrinsic(sc["focals"], sc["centers"]) for sc in scenes]
+        live = [sc for sc, c in zip(scenes, counts) if c]
+        inpaint = bool(N) and self.inpaint and live[0].get("inpaint") is not None
+        out = comp = kp_idx = kp_xy = cad_logits = cad_d = central = geom = None
+        with torch.cuda.device(dev):
+            if N == 0:                                            # no vehicle in the group: nothing is launched, nothing read back
+                cad_d = torch.zeros(0, dtype=torch.int64, device=dev)
+                geo = rd.first_geometry_batch_device(bank, frames, offs, cad_d, Ks, None, None)
+                host = geo["host"](np.zeros(0, np.uint8))
+            else:
+                B = N if rows is None else max(int(rows), N)
+                seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
+                if seeds is not None:
+                    seeds = seeds + [0] * (B - N)
+                replay = replay and ops.RECORDER is None
+                pkey = ("frame_batch", B, ops.PRECISION, "kp_given") + (("inpaint",) if inpaint else ()) + \
+                    (("cad",) if self.cad is not None else ())
+                cp = self._plan(pkey) if replay else None
+                tgt = cp.inputs if cp is not None else {}        # a recorded pass's inputs are written in place
+
+                def buf(k, c):
+                    """The networks' input `k` at B rows, its padding rows zero, and the view of its N real rows the glue writes."""
+                    t = tgt.get(k)
+                    if t is None:
+                        t = ops.nhwc_empty(B, c, R, R, dev, zero=True)
+                    elif B > N:
+                        t[N:].zero_()
+                    return t, t[:N]
+
+                def padded(t):
+                    """A per-row tensor of the keypoint stage at B rows, the padding rows zero."""
+                    if B == N:
+                        return t
+                    z = torch.zeros((B,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+                    z[:N].copy_(t)
+                    return z
+
+                ec, ec_join = self._inpaint_inputs_ragged(scenes, offs, B, tgt) if inpaint else (None, None)
+                # ---- 1. the keypoint stage, eager, at the N real rows
+                geom_box = ops.h2d([pu._geom_row(*pu.square_crop_geometry((H, W), bb)) for b in boxes for bb in b], dev, torch.int32)
+                img_bbox = fo.crop_resize_frames(frames, offs, geom_box, (R, R), 0)            # :58-60
+                hg_x, hg_rows = buf("hg_x", 3)
+                fo.crop_resize_frames(frames, offs, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD, out=hg_rows)   # :61-65
+                central = fo.central_crop(img_bbox)                                            # vehicle_utils.py:49-52
+                kp_idx = ops.argmax_hw(self.hg(hg_rows)["heatmaps"][-1])                       # :75-79
+                if self.cad is not None:
+                    cad_logits = self.cad(hg_rows)                                             # :66-69
+                    cad_d = cad_logits.argmax(1)
+                else:
+                    cad_d = ops.h2d(np.concatenate([np.asarray(sc["cad_idx"], np.int64).reshape(-1) for sc in live]), dev)
+                kp_xy = fo.keypoints_to_frame(kp_idx, geom_box, (R // 4, R // 4))              # :95-97
+                per_row = lambda k: ops.h2d(np.concatenate([np.broadcast_to(np.asarray(sc[k], np.float32).reshape(-1, 2), (c, 2))   # noqa: E731
+                                                            for sc, c in zip(scenes, counts) if c]), dev)
+                # (an index outside the bank is clamped for the fit only: fusg_pose_geometry flags it and the read-back raises)
+                kp3d_d = bank.device_arrays(dev)["kp3d"].index_select(0, cad_d.clamp(0, len(bank) - 1))
+                raw_d = cpc_fit_device(per_row("focals"), per_row("centers"), kp_xy, kp3d_d)   # :104-105
+                # ---- 2. pose, render, visibility, gate, plane cut-outs: nothing read back
+                box_rows = None
+                if inpaint:
+                    brow = np.zeros((N, 8), np.int32)
+                    brow[:, :4] = np.concatenate([np.asarray(sc["inpaint"]["boxes"]).reshape(-1, 4) for sc in live])
+                    box_rows = ops.h2d(brow, dev, torch.int32)
+                geo = rd.first_geometry_batch_device(bank, frames, offs, cad_d, Ks, raw_d, kp_xy, box_rows=box_rows)
+                # ---- 3. the glue, every step once for all rows
+                minv, index = pu.plane_homographies_device(geo["tex_pts_d"], geo["tex_pts_d"], geo["vis_d"], geo["vis_d"],
+                                                           nverts=geo["tex_nv_d"])
+                warped = pu.warp_planes_fitted(geo["planes"], minv, index)                     # :171-175
+                masks, sketch = geo["mask"], geo["sketch"]
+                _, geom = fo.mask_bbox_geom(masks)
+                icn_x, icn_rows = buf("icn_x", 3 * (int(warped.shape[1]) + 2))
+                pu.icn_inputs_device(warped, sketch, central, geom, R, R, out=icn_rows)        # :179-180
+                (vu_x, vx_rows), (vu_y, vy_rows) = buf("vu_x", 6), buf("vu_y", 3)
+                fo.vunet_inputs_frames(frames, offs, masks, sketch, sketch, geom, R, out=(vx_rows, vy_rows))   # :203-228
+                nets_in = {"hg_x": hg_x, "icn_x": icn_x, "vu_x": vu_x, "vu_y": vu_y, "kp_idx": padded(kp_idx)}
+                if cad_logits is not None:
+                    nets_in["cad_logits"] = padded(cad_logits)
+                if ec is not None:
+                    ec_join()
+                    nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
+                # ---- 4. the networks, the keypoints given
+                if replay:                                        # ('icn_u8' is consumed by lab2bgr below, before the next replay)
+                    out = self._replay(pkey, nets_in, seeds, clone=("vunet_u8", "inpaint_u8", "mu_app_0", "mu_app_1"))
+                else:
+                    out = self._run(nets_in, seeds)                                            # :182, :230-234
+                out = {k: v[:N] for k, v in out.items() if k not in ("kp_idx", "cad_logits")}
+                out["icn_u8"] = pu.lab2bgr(out["icn_u8"].contiguous())                         # to_image(from_LAB=True), :182
+                # ---- 5. one ragged paste per composite (:133-143: with --inpaint the composite starts from the frame)
+                bases = [sc["frame"] if (self.inpaint and sc.get("inpaint") is not None) else sc.get("background", sc["frame"])
+                         for sc in scenes]
+                box = dict(box_images=out["inpaint_u8"], box_geom=box_rows) if inpaint else {}
+                comp = {k: pu.paste_back_ragged_device(bases, offs, out[c], geom, masks, **box)
+                        for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+                host = geo["host"](ops.d2h(geo["buf"]))           # the one read-back of the group, behind the queued paste
+            # ---- the per-scene results of `_geometry_frame`, cut from the stacked ones
+            keys = ("icn_u8", "vunet_u8") + (("inpaint_u8",) if inpaint else ())
+            g_t = {"masks": geo["mask"], "src_sketch": geo["sketch"], "dst_sketch": geo["sketch"], "src_planes": geo["planes"]}
+            res = []
+            for f, (sc, c) in enumerate(zip(scenes, counts)):
+                sl = slice(offs[f], offs[f + 1])
+                cad_idx = host["cad_idx"][sl]
+                geometry = {**{k: t[sl] for k, t in g_t.items()}, **{k: host[k][sl] for k in ("src_kp", "dst_kp", "src_vis", "dst_vis")},
+                            "kp3d": bank.kp3d[cad_idx], "cad_idx": cad_idx}
+                keep = [v for v in range(c) if host["covered"][sl][v] > 0]
+                if c == 0:
+                    o = self._frame_batch_empty(sc)
+                else:
+                    idx = torch.as_tensor(keep, dtype=torch.long, device=dev)
+                    cut = (lambda t: t[sl]) if len(keep) == c else (lambda t: t[sl].index_select(0, idx))   # the inert rows are dropped
+                    o = {k: cut(out[k]) for k in keys}
+                    o["geom"], o["kp_idx"], o["kp_xy"] = cut(geom), kp_idx[sl], kp_xy[sl]
+                    o["state"] = {"appearance": [cut(out["mu_app_0"]), cut(out["mu_app_1"])], "central": cut(central),
+                                  "shard": (0, len(keep), len(keep)), "sharded": False}
+                if comp is not None:
+                    o["frame_icn"], o["frame_vunet"] = comp["frame_icn"][f], comp["frame_vunet"][f]
+                pose = self._pose_tuples(host["pose"][sl])
+                dev_keys = {"pose_d": geo["pose_d"][sl], "cad_idx_d": cad_d[sl], "src_kp_d": geo["tex_pts_d"][sl], "kp_nv_d": geo["tex_nv_d"]}
+                front = {"V": c, "pre": {"kp_idx": o["kp_idx"], "kp_xy": o["kp_xy"]}, "keep": keep, "pose": pose, "cad_idx": cad_idx,
+                         "geometry": geometry, "scene": sc, "dev": dev_keys}
+                res.append(self._geometry_assemble(front, o))
+        return res
 
     def _inpaint_inputs_ragged(self, scenes, offs, B: int, tgt) -> Tuple[Dict, object]:
         """EdgeConnect's four inputs of a group of first frames, [B, c, R, R] each (B >= offs[-1]: the padding rows are zero):

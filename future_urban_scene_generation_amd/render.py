@@ -620,12 +620,14 @@ _STAGE_EXTRA = (("counts", np.int32, 14), ("covered", np.int32, 1), ("cad_idx", 
 
 
 def _device_stage(bank: CadBank, frame_hw: Tuple[int, int], dev, cad_idx_d: torch.Tensor, K: np.ndarray, raw_d=None, pose_d=None,
-                  kp_xy_d=None, steps_d=None, extra=()) -> Dict:
+                  kp_xy_d=None, steps_d=None, extra=(), K_runs=None) -> Dict:
     """The launches `vehicle_geometry_device` and `later_geometry_batch_device` share, for V rows on the current stream:
     fusg_pose_geometry -> fusg_render_normals_u8 of the device jobs -> fusg_plane_visibility, every small result in ONE zeroed
     buffer (`_pg_layout` + counts, covered, cad_idx + `extra`).  A first frame gives raw_d and kp_xy_d, a later frame pose_d and
     steps_d (CUDA float64 [V, 4]).  Returns 'lay' / 'nbytes' (the layout), 'buf' (the buffer), 'd' (its parts as device views),
-    'r' ('sketch' uint8 [V, H, W, 3], 'mask' uint8 [V, H, W]) and 'V'.  Nothing is read back."""
+    'r' ('sketch' uint8 [V, H, W, 3], 'mask' uint8 [V, H, W]) and 'V'.  Nothing is read back.  K_runs (rows of several cameras):
+    [(lo, hi, K)] covering the rows in order - fusg_pose_geometry takes one host K, so it is launched once per run into the row
+    slices of the same buffers; None: one launch with `K`."""
     H, W = frame_hw
     V = int(cad_idx_d.shape[0])
     first = steps_d is None and pose_d is None
@@ -645,12 +647,15 @@ def _device_stage(bank: CadBank, frame_hw: Tuple[int, int], dev, cad_idx_d: torc
             ins = [None, None, None, f32(pose_d, (7,)), None, steps_d]
         cad_c = cad_idx_d.contiguous()
         d["cad_idx"].copy_(cad_c)
-        Kc = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
-        ptr = lambda t: None if t is None else t.data_ptr()                           # noqa: E731
         lib = L.lib()
-        L.check(lib.fusg_pose_geometry(*(ptr(t) for t in ins), cad_c.data_ptr(), arr["kp3d"].data_ptr(), arr["v_off"].data_ptr(),
-                                       arr["t_off"].data_ptr(), len(bank), Kc.ctypes.data, H, W, V,
-                                       *(d[k].data_ptr() for k in _PG_CALL), ops.stream_ptr()), "pose_geometry")
+        per = {name: n for name, _, n in _PG_OUT}
+        row = lambda t, lo: None if t is None else t.data_ptr() + lo * (t.numel() // V) * t.element_size()   # noqa: E731
+        for lo, hi, Kr in ([(0, V, K)] if K_runs is None else K_runs):
+            Kc = np.ascontiguousarray(np.asarray(Kr, np.float64).reshape(9))
+            L.check(lib.fusg_pose_geometry(*(row(t, lo) for t in ins), row(cad_c, lo), arr["kp3d"].data_ptr(), arr["v_off"].data_ptr(),
+                                           arr["t_off"].data_ptr(), len(bank), Kc.ctypes.data, H, W, hi - lo,
+                                           *(d[k].data_ptr() + lo * per[k] * d[k].element_size() for k in _PG_CALL), ops.stream_ptr()),
+                    "pose_geometry")
         max_nv = bank.max_nv
         ws = torch.empty((V * (16 + 40 * max_nv) + 15) // 16 * 2, dtype=torch.float64, device=dev)
         L.check(lib.fusg_render_normals_u8(arr["verts"].data_ptr(), arr["normals"].data_ptr(), arr["verts"].shape[0],
@@ -725,6 +730,69 @@ def later_geometry_batch_device(bank: CadBank, frame_hw: Tuple[int, int], cad_id
 
     return {"mask": st["r"]["mask"], "sketch": st["r"]["sketch"], "tex_pts_d": d["tex_pts"].view(N, P, pu.MAX_VERTS, 2),
             "tex_nv_d": d["tex_nv"][:P], "dst_vis_d": d["dst_vis"].view(N, P), "valid_d": d["valid"], "buf": st["buf"], "host": host}
+
+
+def camera_runs(Ks: Sequence[np.ndarray], offs: Sequence[int]) -> List[Tuple[int, int, np.ndarray]]:
+    """(row lo, row hi, K) per maximal run of consecutive scenes whose K has equal focals and centers, rows scene-major by the
+    offsets `offs`; runs without rows are dropped.  A one-camera video is one run."""
+    key = lambda K: tuple(float(np.asarray(K, np.float64)[i, j]) for i, j in ((0, 0), (1, 1), (0, 2), (1, 2)))   # noqa: E731
+    runs: List[Tuple[int, int, np.ndarray]] = []
+    for f, K in enumerate(Ks):
+        lo, hi = int(offs[f]), int(offs[f + 1])
+        if hi == lo:
+            continue
+        if runs and runs[-1][1] == lo and key(runs[-1][2]) == key(K):
+            runs[-1] = (runs[-1][0], hi, runs[-1][2])
+        else:
+            runs.append((lo, hi, np.asarray(K, np.float64)))
+    return runs
+
+
+def first_geometry_batch_device(bank: CadBank, frames: Sequence[torch.Tensor], offs: Sequence[int], cad_idx_d: torch.Tensor,
+                                Ks: Sequence[np.ndarray], raw_d, kp_xy_d: torch.Tensor, box_rows: Optional[torch.Tensor] = None) -> Dict:
+    """`vehicle_geometry_device`'s first-frame branch for the vehicles of SEVERAL scenes at once, WITHOUT its read-back: N =
+    offs[-1] rows, scene-major (rows offs[f] .. offs[f + 1] are scene f's vehicles, cut from frames[f]: CUDA uint8 [H, W, 3] of one
+    size).  cad_idx_d CUDA int64 [N]; raw_d = `cpc_fit_device`'s (rvec [N, 4, 3], tvec, err [N, 4]) and kp_xy_d float32 [N, 12, 2]
+    on the device; Ks[f] = scene f's 3 x 3 intrinsics (host).  Order of work, all on the current stream: fusg_pose_geometry once
+    per run of scenes with one camera (`camera_runs`) -> fusg_render_normals_u8 -> fusg_plane_visibility -> fusg_later_gate (on a
+    first frame src_vis = dst_vis, so its one gated table serves both; box_rows: CUDA int32 [N, 8] paste box rows, zeroed in place
+    where the render is empty) -> the plane cut-outs of every row from its own frame (`planes_utils.fill_planes_frames`).
+    Returns the device tensors 'mask' uint8 [N, H, W], 'sketch' uint8 [N, H, W, 3], 'planes' uint8 [N, 5, H, W, 3], 'tex_pts_d'
+    int32 [N, 5, 8, 2], 'tex_nv_d' int32 [5], 'vis_d' uint8 [N, 5] (gated), 'valid_d' int32 [N], 'pose_d' float32 [N, 7]; 'buf',
+    the one small packed buffer to read back whenever the caller likes (`ops.d2h`), and 'host' = a function of the read-back bytes
+    that gives the host keys of `vehicle_geometry_device` ('src_vis' = 'dst_vis' = `visible(counts)`, UN-gated as the per-frame
+    path reports it; 'src_planes' = 'planes'; IndexError for a cad_idx outside the bank) plus 'valid' (host int32 [N])."""
+    if len(frames) < 1 or len(offs) != len(frames) + 1 or len(Ks) != len(frames):
+        raise ValueError(f"first_geometry_batch_device: {len(frames)} frames, {len(offs)} offsets, {len(Ks)} intrinsics")
+    H, W = int(frames[0].shape[0]), int(frames[0].shape[1])
+    dev = frames[0].device
+    N, P = int(offs[-1]), len(TEXTURE_PLANES)
+    if int(cad_idx_d.shape[0]) != N:
+        raise ValueError(f"first_geometry_batch_device: {int(cad_idx_d.shape[0])} CAD indices for {N} rows")
+    if box_rows is not None and (not box_rows.is_cuda or box_rows.dtype != torch.int32 or tuple(box_rows.shape) != (N, 8)
+                                 or not box_rows.is_contiguous()):
+        raise ValueError("first_geometry_batch_device: box_rows is a contiguous CUDA int32 [N, 8]")
+    with torch.cuda.device(dev):
+        planes = torch.empty((N, P, H, W, 3), dtype=torch.uint8, device=dev)
+        runs = camera_runs(Ks, offs)
+        st = _device_stage(bank, (H, W), dev, cad_idx_d, runs[0][2] if runs else Ks[0], raw_d=raw_d, kp_xy_d=kp_xy_d,
+                           extra=(("dst_vis", np.uint8, P), ("valid", np.int32, 1)), K_runs=runs)
+        d = st["d"]
+        if N:
+            L.check(L.lib().fusg_later_gate(d["counts"].data_ptr(), d["covered"].data_ptr(), N, P, d["dst_vis"].data_ptr(),
+                                            d["valid"].data_ptr(), None if box_rows is None else box_rows.data_ptr(),
+                                            ops.stream_ptr()), "later_gate")
+            pu.fill_planes_frames(frames, offs, d["tex_pts"], d["tex_nv"], planes)
+
+    def host(read: np.ndarray) -> Dict:
+        out = _device_stage_result(bank, st, read, planes, True)
+        o, dt, n = st["lay"]["valid"]
+        out["valid"] = read[o:o + n * dt.itemsize].view(dt).copy()
+        return out
+
+    return {"mask": st["r"]["mask"], "sketch": st["r"]["sketch"], "planes": planes, "tex_pts_d": d["tex_pts"].view(N, P, pu.MAX_VERTS, 2),
+            "tex_nv_d": d["tex_nv"][:P] if N else d["tex_nv"], "vis_d": d["dst_vis"].view(N, P), "valid_d": d["valid"],
+            "pose_d": d["pose"].view(N, 7), "buf": st["buf"], "host": host}
 
 
 # ---------------------------------------------------------------------------------------------- trajectories

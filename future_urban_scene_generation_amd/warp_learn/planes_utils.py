@@ -289,6 +289,27 @@ def fill_planes_batch(image: torch.Tensor, pts: torch.Tensor, nverts: torch.Tens
     return out
 
 
+def fill_planes_frames(frames: Sequence[torch.Tensor], frame_rows: Sequence[int], pts: torch.Tensor, nverts: torch.Tensor,
+                       out: torch.Tensor) -> torch.Tensor:
+    """`fill_planes_batch` for vehicles of F different images in ONE launch (fusg_fill_poly_planes_frames_u8): frames = F CUDA
+    uint8 [H, W, 3] images of one size; frame_rows = F + 1 host offsets, vehicles [frame_rows[f], frame_rows[f + 1]) are cut from
+    frames[f]; pts, nverts and out as there.  The bytes are those of F calls of `fill_planes_batch`; a frame without vehicles
+    is not read."""
+    from ..frame_ops import _frame_table
+    V, P, H, W, _ = out.shape
+    ptrs, offs, keep, hw = _frame_table(frames, frame_rows, V, "fill_planes_frames")
+    if out.dtype != torch.uint8 or not out.is_contiguous() or hw != (H, W) or out.device != keep[0].device:
+        raise ValueError("fill_planes_frames: out must be a contiguous uint8 [V, P, H, W, 3] of the frames' size, on their device")
+    if pts.dtype != torch.int32 or nverts.dtype != torch.int32 or not (pts.is_contiguous() and nverts.is_contiguous()) or \
+            pts.numel() != V * P * MAX_VERTS * 2 or nverts.numel() != V * P or not (pts.is_cuda and nverts.is_cuda):
+        raise ValueError("fill_planes_frames: pts int32 [V, P, 8, 2] and nverts int32 [V, P], contiguous, on the device")
+    with torch.cuda.device(out.device):
+        L.check(L.lib().fusg_fill_poly_planes_frames_u8(ptrs, offs, len(keep), H, W, pts.data_ptr(), nverts.data_ptr(), V, P,
+                                                        C.byref(_u8desc(out.view(V * P, H, W, 3))), ops.stream_ptr()),
+                "fill_poly_planes_frames_u8")
+    return out
+
+
 def get_planes(image: Image, src_kpoint_dict, pascal_class: str, planes_visibility):
     """Reference signature (planes_utils.py:11-37): (planes [P, H, W, 3], polygon list, visibilities uint8 [P])."""
     img, as_np = _to_dev(image)

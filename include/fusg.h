@@ -529,6 +529,15 @@ int fusg_paste_layers_ragged_u8(const fusg_tensor* net, const fusg_tensor* masks
                                 const int32_t* rect_geom, const void* const* bases, const int32_t* frame_rows, int32_t n_frames,
                                 const fusg_tensor* dst, void* stream);
 
+/* fusg_fill_poly_planes_batch_u8 with the same tables, the rows being JOBS (VehiclePipeline.run_frames_batched_geometry; a new
+ * entry point, FUSG_VERSION stays 118): jobs [frame_rows[f], frame_rows[f + 1]) read frame f, dst[j * n_planes + p] =
+ * frames[frame of j] * fillPoly(polygon (j, p)).  pts_xy DEVICE int32 [n_jobs][n_planes][8][2], nverts DEVICE int32
+ * [n_jobs][n_planes], n_planes in 1..8, n_jobs * n_planes <= 65535, dst u8 [n_jobs * n_planes, H, W, 3] with contiguous rows,
+ * not overlapping a frame.  A frame without jobs is not read.  n_jobs == 0: no launch, returns 0. */
+int fusg_fill_poly_planes_frames_u8(const void* const* frames, const int32_t* frame_rows, int32_t n_frames, int32_t H, int32_t W,
+                                    const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs, int32_t n_planes,
+                                    const fusg_tensor* dst, void* stream);
+
 /* ---- pose fit ------------------------------------------------------------------------------- */
 /*
  * The reference's pose fit ("CamPoseCalib": Levenberg-Marquardt on a Rodrigues vector + translation, utils/cpc.py:45-139

@@ -1,0 +1,512 @@
+"""GPU: geometry-mode first frames of several scenes as ONE pass (VehiclePipeline.run_frames_batched_geometry,
+render.first_geometry_batch_device, fusg_fill_poly_planes_frames_u8).  The frame-indexed plane cut-outs equal the one-frame
+kernel byte for byte; the batched stage equals the per-frame device path (`_geometry_front`) row by row, with the vehicle whose
+render is empty kept as an inert row; slices of one scene give `run_frame`'s bits (the same batch sizes); the derived keys fed
+back as an explicit given-geometry batch of the same rows give the same bytes (that batch is tied to the CPU oracle by
+tests/test_gpu_frame_batch.py); against `run_frame` of the kept vehicles - another batch size - the bars of that file apply;
+one device-to-host copy per group, behind the queued paste."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import pose_geometry_cases as pc                                           # noqa: E402
+from conftest import synth_sd                                              # noqa: E402
+from future_urban_scene_generation_amd import _lib as L                    # noqa: E402
+from future_urban_scene_generation_amd import ops                          # noqa: E402
+from future_urban_scene_generation_amd import pipeline as pl               # noqa: E402
+from future_urban_scene_generation_amd import render as R                  # noqa: E402
+from future_urban_scene_generation_amd.warp_learn import planes_utils as pu   # noqa: E402
+from test_gpu_frame_batch import _bars                                     # noqa: E402
+from test_gpu_geometry_drivers import _with_empty_vehicle                  # noqa: E402
+from test_gpu_pose_geometry import POSE_BAR_ULP, pose_rows                 # noqa: E402
+
+DEV = "cuda:0"
+HW = (360, 640)
+V, EMPTY = 3, 1
+CROPS = ("icn_u8", "vunet_u8", "geom")
+KEYS = ("kp_idx", "kp_xy") + CROPS + ("frame_icn", "frame_vunet")
+G_TENSORS = ("masks", "src_sketch", "dst_sketch", "src_planes")
+G_ARRAYS = ("src_vis", "dst_vis", "kp3d", "cad_idx")
+G_LISTS = ("src_kp", "dst_kp")
+
+
+def _d(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+# ------------------------------------------------------------------------------------------------ 1. the kernel
+KH, KW, NP = 77, 131, 5                                                      # an odd W: plane starts are not 16-byte aligned
+
+
+def _kernel_polygons(n_jobs):
+    """Per job five polygons: inside the frame, partly off the frame on two sides, fully outside, nverts = 0, a triangle."""
+    pts = np.zeros((n_jobs, NP, 8, 2), np.int32)
+    nv = np.zeros((n_jobs, NP), np.int32)
+    for j in range(n_jobs):
+        s = 3 * j
+        polys = [[(20 + s, 10), (90 + s, 14), (100, 60 - s), (30, 66)],
+                 [(-25, -12 - s), (40 + s, -6), (55, 30), (22, 44 + s), (-9, 35)],
+                 [(KW + 5, 5), (KW + 60, 5), (KW + 60, 50 + s), (KW + 5, 50)],
+                 [],
+                 [(KW - 30 - s, KH - 25), (KW + 20, KH - 5), (KW - 40, KH + 30)]]
+        for p, poly in enumerate(polys):
+            nv[j, p] = len(poly)
+            for i, xy in enumerate(poly):
+                pts[j, p, i] = xy
+        pts[j, 3] = 7                                                        # nverts = 0: the points are not looked at
+    return pts, nv
+
+
+@pytest.mark.parametrize("counts", [[2, 0, 3], [1]], ids=["2-0-3", "1"])
+def test_fill_planes_frames_equals_fill_planes_batch_per_frame(counts):
+    g = np.random.default_rng(5)
+    frames = [_d(g.integers(1, 256, (KH, KW, 3), dtype=np.uint8)) for _ in counts]
+    offs = pl.frame_batch_offsets(counts)
+    n = offs[-1]
+    pts, nv = _kernel_polygons(n)
+    pts_d, nv_d = _d(pts), _d(nv)
+    full = torch.full((n + 1, NP, KH, KW, 3), 77, dtype=torch.uint8, device=DEV)       # one job of guard planes behind dst
+    out = pu.fill_planes_frames(frames, offs, pts_d, nv_d, full[:n])
+    assert (full[n] == 77).all()
+    assert (out.data_ptr() + KH * KW * 3) % 16 != 0                                     # plane 1 starts off a 16-byte address
+    for f, c in enumerate(counts):
+        sl = slice(offs[f], offs[f + 1])
+        want = torch.full((c, NP, KH, KW, 3), 13, dtype=torch.uint8, device=DEV)
+        pu.fill_planes_batch(frames[f], pts_d[sl].contiguous(), nv_d[sl].contiguous(), want)
+        assert torch.equal(out[sl], want), f
+    flat = out.flatten(2)
+    for j in range(n):
+        assert flat[j, 0].any() and flat[j, 1].any() and flat[j, 4].any() and not flat[j, 2].any() and not flat[j, 3].any(), j
+    if len(counts) == 1:
+        return
+    assert not torch.equal(out[0], out[2])
+    # a frame without jobs is not read: its table entry points at a small live buffer, the bytes are the same
+    small = torch.zeros(16, dtype=torch.uint8, device=DEV)
+    ptrs = (C.c_void_p * 3)(frames[0].data_ptr(), small.data_ptr(), frames[2].data_ptr())
+    again = torch.full_like(full, 99)
+    d = pu._u8desc(again[:n].view(n * NP, KH, KW, 3))
+    with torch.cuda.device(DEV):
+        L.check(L.lib().fusg_fill_poly_planes_frames_u8(ptrs, (C.c_int32 * 4)(*offs), 3, KH, KW, pts_d.data_ptr(), nv_d.data_ptr(), n, NP,
+                                                        C.byref(d), ops.stream_ptr()), "fill_poly_planes_frames_u8")
+    assert torch.equal(again[:n], out) and (again[n] == 99).all() and not small.any()
+
+
+# ------------------------------------------------------------------------------------------------ the scenes
+def _cut(scene, lo, hi, **extra):
+    """Vehicles [lo, hi) of a geometry-mode scene ('cad_idx' is per vehicle too)."""
+    return dict(pl.slice_scene(scene, lo, hi), cad_idx=np.asarray(scene["cad_idx"])[lo:hi], **extra)
+
+
+def _cat_lists(results, k):
+    return [v for r in results for v in r["geometry"][k]]
+
+
+def _same_lists(a, b, tag):
+    assert len(a) == len(b), tag
+    for pa, pb in zip(a, b):
+        assert len(pa) == len(pb) and all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(pa, pb)), tag
+
+
+@pytest.fixture(scope="module")
+def env():
+    """tests/test_gpu_render.py's geometry-mode pipeline with the device paths on and a bank that also holds the far-away copy
+    of vehicle EMPTY's model.  `scene`: 3 vehicles, all rendered; `scene_e`: the same with vehicle EMPTY's render empty; three
+    scenes with frames of their own (the low bits of the frame flipped: the same vehicles, other bytes) and counts 2 (one
+    inert), 0, 1; and - computed once - `run_frame` of each and the batched result of the three."""
+    from test_gpu_render import _geometry_setup
+    pipe, bank, scene = _geometry_setup(V=V)
+    pipe.device_pose = pipe.device_homography = True
+    scene_e = _with_empty_vehicle(pipe, bank, scene, EMPTY)
+    three = [_cut(scene_e, 0, 2),
+             _cut(scene, 0, 0, frame=scene["frame"] ^ 2),
+             _cut(scene, 2, 3, frame=scene["frame"] ^ 1)]
+    w = pipe.run_frame(scene)
+    assert w["skipped"] == []
+    refs = [pipe.run_frame(sc) for sc in three]
+    assert [r["skipped"] for r in refs] == [[EMPTY], [], []]
+    got = pipe.run_frames_batched_geometry(three)
+    return dict(pipe=pipe, bank=pipe.cad_bank, scene=scene, scene_e=scene_e, three=three, w=w, refs=refs, got=got)
+
+
+# ------------------------------------------------------------------------------------------------ 2. the stage
+def _fronts(pipe, scenes):
+    with torch.cuda.device(DEV):
+        return [pipe._geometry_front(sc, None) for sc in scenes]
+
+
+def _stage_of_fronts(pipe, scenes, fronts):
+    """`first_geometry_batch_device` fed the concatenated raw fits, keypoints and CAD indices of per-scene fronts."""
+    live = [f for f in fronts if f["V"]]
+    raw_d = tuple(torch.cat([f["raw_d"][i] for f in live]) for i in range(3))
+    kp_xy_d = torch.cat([f["pre"]["kp_xy"] for f in live])
+    cad_d = torch.cat([f["dev"]["cad_idx_d"] for f in live])
+    offs = pl.frame_batch_offsets([f["V"] for f in fronts])
+    Ks = [R.intrinsic(sc["focals"], sc["centers"]) for sc in scenes]
+    with torch.cuda.device(DEV):
+        geo = R.first_geometry_batch_device(pipe.cad_bank, [sc["frame"] for sc in scenes], offs, cad_d, Ks, raw_d, kp_xy_d)
+        host = geo["host"](ops.d2h(geo["buf"]))
+    return geo, host, offs
+
+
+def _stage_equals_fronts(geo, host, offs, fronts, inert_row):
+    N = offs[-1]
+    assert tuple(geo["mask"].shape) == (N,) + HW and tuple(geo["planes"].shape) == (N, 5) + HW + (3,)
+    gated, valid = geo["vis_d"].cpu().numpy(), geo["valid_d"].cpu().numpy()
+    assert np.array_equal(valid, host["valid"]) and np.array_equal(host["status"], np.zeros(N, np.int32))
+    for f, fr in enumerate(fronts):
+        g, sl = fr["g"], slice(offs[f], offs[f + 1])
+        for k, t in (("masks", geo["mask"]), ("src_sketch", geo["sketch"]), ("src_planes", geo["planes"]), ("tex_pts_d", geo["tex_pts_d"]),
+                     ("pose_d", geo["pose_d"])):
+            assert t[sl].shape == g[k].shape and torch.equal(t[sl], g[k]), (f, k)
+        assert np.array_equal(host["covered"][sl], g["covered"]) and np.array_equal(host["pose"][sl], g["pose"]), f
+        assert np.array_equal(host["src_vis"][sl], g["src_vis"]) and np.array_equal(host["counts"][sl], g["counts"]), f
+        _same_lists(host["src_kp"][sl], g["src_kp"], f)
+        kept = (np.asarray(g["covered"]) > 0)
+        assert np.array_equal(valid[sl], kept.astype(np.int32)), f
+        want = R.visible(g["counts"])[:, :5].astype(np.uint8) if fr["V"] else np.zeros((0, 5), np.uint8)
+        assert np.array_equal(gated[sl], want * kept[:, None]), f
+        if fr["V"]:
+            assert torch.equal(geo["tex_nv_d"], g["tex_nv_d"])
+    assert int(valid[inert_row]) == 0 and not gated[inert_row].any() and not geo["mask"][inert_row].any()
+    assert valid.sum() == N - 1 and gated.any() and geo["planes"].any()
+
+
+def test_stage_equals_the_per_frame_path(env, monkeypatch):
+    pipe, three = env["pipe"], env["three"]
+    fronts = _fronts(pipe, three)
+    assert [f["V"] for f in fronts] == [2, 0, 1] and [f["keep"] for f in fronts] == [[0], [], [0]]
+    lib = L.lib()
+    launches = []
+    real = lib.fusg_pose_geometry
+    monkeypatch.setattr(lib, "fusg_pose_geometry", lambda *a: (launches.append(int(a[14])), real(*a))[1])
+    geo, host, offs = _stage_of_fronts(pipe, three, fronts)
+    assert launches == [3]                                                        # one camera: one launch over all rows
+    _stage_equals_fronts(geo, host, offs, fronts, EMPTY)
+    assert not torch.equal(geo["planes"][0], geo["planes"][2])
+    # two cameras: scene 2 has other focals -> two launches into row slices of the same buffers, the same bytes as per scene
+    f0 = three[2]["focals"]
+    two = three[:2] + [dict(three[2], focals=(float(f0[0]) * 1.04, float(f0[1]) * 1.04))]
+    monkeypatch.setattr(lib, "fusg_pose_geometry", real)
+    fronts2 = _fronts(pipe, two)
+    assert not torch.equal(fronts2[2]["g"]["pose_d"], fronts[2]["g"]["pose_d"])
+    del launches[:]
+    monkeypatch.setattr(lib, "fusg_pose_geometry", lambda *a: (launches.append(int(a[14])), real(*a))[1])
+    geo2, host2, offs2 = _stage_of_fronts(pipe, two, fronts2)
+    assert launches == [2, 1]
+    _stage_equals_fronts(geo2, host2, offs2, fronts2, EMPTY)
+    assert torch.equal(geo2["mask"][:2], geo["mask"][:2]) and torch.equal(geo2["pose_d"][:2], geo["pose_d"][:2])
+
+
+# ------------------------------------------------------------------------------------------------ 3. bit equality
+def test_slices_of_one_scene_equal_run_frame_bit_for_bit(env):
+    """Scenes of 2, 0 and 1 vehicles that share a frame, eager and unpadded: the hourglass runs at 3 rows and the networks at 3
+    rows, as in `run_frame` of the 3 vehicles - every tensor equals it bit for bit."""
+    pipe, scene, w = env["pipe"], env["scene"], env["w"]
+    cuts = [(0, 2), (2, 2), (2, 3)]
+    got = pipe.run_frames_batched_geometry([_cut(scene, lo, hi) for lo, hi in cuts], pad=False)
+    assert len(got) == 3 and all(g["skipped"] == [] for g in got)
+    for k in ("kp_idx", "kp_xy") + CROPS:
+        assert torch.equal(torch.cat([g[k] for g in got]), w[k]), k
+    for k in G_TENSORS:
+        assert torch.equal(torch.cat([g["geometry"][k] for g in got]), w["geometry"][k]), k
+    for k in G_ARRAYS:
+        a = np.concatenate([np.asarray(g["geometry"][k]) for g in got])
+        assert a.dtype == np.asarray(w["geometry"][k]).dtype and np.array_equal(a, w["geometry"][k]), k
+    for k in G_LISTS:
+        _same_lists(_cat_lists(got, k), w["geometry"][k], k)
+    u = pc.ulp32(pose_rows([p for g in got for p in g["pose"]]), pose_rows(w["pose"]))
+    print(f"slices: pose ulp {u}")
+    assert u <= POSE_BAR_ULP
+    ws = w["state"]
+    assert torch.equal(torch.cat([g["state"]["central"] for g in got]), ws["central"])
+    for i in range(2):
+        assert torch.equal(torch.cat([g["state"]["appearance"][i] for g in got]), ws["appearance"][i]), i
+    for k in ("pose_d", "cad_idx_d", "src_kp_d", "src_planes"):
+        assert torch.equal(torch.cat([g["state"]["geometry"][k] for g in got]), ws["geometry"][k]), k
+    for g, (lo, hi) in zip(got, cuts):
+        n = hi - lo
+        sg = g["state"]["geometry"]
+        assert g["state"]["shard"] == (0, n, n) and g["state"]["sharded"] is False and sg["vehicles"] == list(range(n))
+        assert torch.equal(sg["kp_nv_d"], ws["geometry"]["kp_nv_d"]) or n == 0
+        assert np.array_equal(sg["cad_idx"], ws["geometry"]["cad_idx"][lo:hi]) and len(sg["pose"]) == n
+        assert set(g["geometry"]) == set(w["geometry"]) and len(g["geometry"]) == 10
+        assert set(g) == set(w) if n else set(g) >= set(KEYS) | {"pose", "geometry", "skipped", "state"}
+        for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8")):
+            if n:
+                want = pu.paste_back_device(scene["frame"], w[c][lo:hi], w["geom"][lo:hi].contiguous(), w["geometry"]["masks"][lo:hi])
+                assert torch.equal(g[k], want) and not torch.equal(g[k], scene["frame"]), k
+            else:
+                assert torch.equal(g[k], scene["frame"]), k
+    assert got[1]["pose"] == [] and got[1]["kp_idx"].shape[0] == 0 and got[1]["geometry"]["masks"].shape == (0,) + HW
+    assert not any(k[0] == "frame_batch" for k in pipe._frame_plans)               # the eager form records nothing
+
+
+# ------------------------------------------------------------------------------------------------ 4. the inert row
+def _explicit(scenes, got):
+    """The read-back 'geometry' of a batched result as explicit given-geometry scenes of the SAME rows: the inert vehicle stays
+    in as an empty-mask row with its visibilities zeroed (what the device gate does to it)."""
+    out = []
+    for sc, res in zip(scenes, got):
+        g = res["geometry"]
+        vis = np.array(g["src_vis"], np.uint8).copy()
+        vis[res["skipped"]] = 0
+        e = {k: sc[k] for k in ("frame", "bboxes", "focals", "centers", "vehicle_seeds")}
+        e.update({k: g[k] for k in G_TENSORS + G_LISTS}, src_vis=vis, dst_vis=vis, kp3d=g["kp3d"])
+        out.append(e)
+    return out
+
+
+def _kept_of(res, n):
+    return [v for v in range(n) if v not in res["skipped"]]
+
+
+def _same_as_explicit(got, ex, counts, tag, keys=CROPS):
+    for f, (a, b) in enumerate(zip(got, ex)):
+        keep = torch.as_tensor(_kept_of(a, counts[f]), dtype=torch.long, device=DEV)
+        for k in keys:
+            if counts[f] == 0 and k == "inpaint_u8":                                # a scene without vehicles carries no 'inpaint'
+                assert k not in a and k not in b
+                continue
+            assert a[k].shape[0] == len(keep) and torch.equal(a[k], b[k].index_select(0, keep)), (tag, f, k)
+        for k in ("frame_icn", "frame_vunet"):
+            assert torch.equal(a[k], b[k]), (tag, f, k)
+
+
+def test_the_inert_row(env):
+    pipe, three, got, refs = env["pipe"], env["three"], env["got"], env["refs"]
+    counts = [2, 0, 1]
+    for f, (a, b) in enumerate(zip(got, refs)):
+        assert a["skipped"] == b["skipped"] and torch.equal(a["kp_idx"], b["kp_idx"]) and torch.equal(a["kp_xy"], b["kp_xy"]), f
+        assert pc.ulp32(pose_rows(a["pose"]), pose_rows(b["pose"])) <= POSE_BAR_ULP if counts[f] else a["pose"] == []
+        assert set(a["geometry"]) == set(b["geometry"]) and len(a["geometry"]) == 10
+        for k in G_TENSORS:
+            assert torch.equal(a["geometry"][k], b["geometry"][k]), (f, k)
+        for k in G_ARRAYS:
+            assert np.array_equal(a["geometry"][k], b["geometry"][k]), (f, k)
+        for k in G_LISTS:
+            _same_lists(a["geometry"][k], b["geometry"][k], (f, k))
+        assert tuple(a["icn_u8"].shape) == (counts[f] - len(a["skipped"]), 256, 256, 3)
+    assert not got[0]["geometry"]["masks"][EMPTY].any() and got[0]["geometry"]["masks"][0].any()
+    # the same rows, at the same batch size, through the given-geometry batched path: no tolerance
+    explicit = _explicit(three, got)
+    assert explicit[0]["src_vis"][EMPTY].sum() == 0 and explicit[0]["src_vis"][0].sum() > 0
+    ex = pipe.run_frames_batched(explicit)
+    assert tuple(ex[0]["icn_u8"].shape) == (2, 256, 256, 3)
+    _same_as_explicit(got, ex, counts, "explicit")
+    assert torch.equal(got[1]["frame_icn"], three[1]["frame"]) and torch.equal(got[1]["frame_vunet"], three[1]["frame"])
+    # against `run_frame` of the kept vehicles the batch size differs: the project's bars
+    for f in (0, 2):
+        ref = {k: refs[f][k].cpu().numpy() for k in KEYS}
+        ref["pose"] = refs[f]["pose"]
+        keep = _kept_of(got[f], counts[f])
+        cpu = {"masks": got[f]["geometry"]["masks"].cpu().numpy()[keep], "frame": three[f]["frame"].cpu().numpy()}
+        _bars(got[f], ref, cpu, f"geometry batch scene {f}")
+
+
+# ------------------------------------------------------------------------------------------------ 5. one read-back
+def test_one_read_back_per_group_behind_the_paste(env, monkeypatch):
+    pipe, three = env["pipe"], env["three"]
+    lib = L.lib()
+    order = []
+    real_d2h = ops.d2h
+    monkeypatch.setattr(ops, "d2h", lambda t: (order.append("d2h"), real_d2h(t))[1])
+    for fn in ("fusg_fill_poly_planes_frames_u8", "fusg_paste_layers_ragged_u8"):
+        real = getattr(lib, fn)
+        monkeypatch.setattr(lib, fn, lambda *a, _r=real, _n=fn: (order.append(_n), _r(*a))[1])
+    cuts = ("fusg_fill_poly_planes_frames_u8",)
+    paste = ("fusg_paste_layers_ragged_u8",) * 2
+    pipe.run_frames_batched_geometry(three)
+    assert tuple(order) == cuts + paste + ("d2h",)                                # ONE copy per group, after the paste is queued
+    del order[:]
+    assert pl.frame_batch_groups([2, 0, 1], 2) == [(0, 2), (2, 3)]
+    pipe.run_frames_batched_geometry(three, max_batch=2)
+    assert tuple(order) == (cuts + paste + ("d2h",)) * 2
+    del order[:]
+    list(pipe.run_frames(three, replay=False))
+    assert order.count("d2h") >= 2 and "fusg_fill_poly_planes_frames_u8" not in order   # frame by frame: a blocking copy per frame with vehicles
+
+
+# ------------------------------------------------------------------------------------------------ 6. replay and padding
+def _same_results(a, b, tag):
+    assert len(a) == len(b)
+    for f, (x, y) in enumerate(zip(a, b)):
+        assert set(x) == set(y) and x["skipped"] == y["skipped"], (tag, f)
+        for k in KEYS:
+            assert torch.equal(x[k], y[k]), (tag, f, k)
+        assert np.array_equal(pose_rows(x["pose"]), pose_rows(y["pose"])) if x["pose"] else y["pose"] == []
+        assert torch.equal(x["state"]["central"], y["state"]["central"]), (tag, f)
+        assert all(torch.equal(p, q) for p, q in zip(x["state"]["appearance"], y["state"]["appearance"])), (tag, f)
+        for k in G_TENSORS:
+            assert torch.equal(x["geometry"][k], y["geometry"][k]), (tag, f, k)
+
+
+def test_replay_equals_the_padded_eager_pass_and_keeps_one_plan(env):
+    pipe, three, scene = env["pipe"], env["three"], env["scene"]
+    other = [_cut(scene, 0, 2), _cut(scene, 2, 3)]                                  # 3 rows again, nothing inert
+    pipe.run_frame(_cut(scene, 0, 2), replay=True)                                 # a per-frame plan exists
+    before = {k: id(v) for k, v in pipe._frame_plans.items() if k[0] != "frame_batch"}
+    assert before
+    key = ("frame_batch", 4, ops.PRECISION, "kp_given")
+    pipe._frame_plans.pop(key, None)
+    eager = [pipe.run_frames_batched_geometry(s, pad=True) for s in (three, other)]
+    assert not any(k[0] == "frame_batch" for k in pipe._frame_plans)               # pad=True alone records nothing
+    r0 = pipe.run_frames_batched_geometry(three, replay=True)
+    plan = pipe._frame_plans[key]
+    keep = [{k: r0[f][k].clone() for k in KEYS} for f in range(3)]
+    r1 = pipe.run_frames_batched_geometry(other, replay=True)
+    again = pipe.run_frames_batched_geometry(three, replay=True)
+    assert pipe._frame_plans[key] is plan                                         # recorded once, replayed since
+    assert [k for k in pipe._frame_plans if k[0] == "frame_batch"] == [key]
+    _same_results(r0, eager[0], "replay 0")
+    _same_results(again, eager[0], "replay again")
+    _same_results(r1, eager[1], "replay other")
+    for f in range(3):
+        for k in KEYS:
+            assert torch.equal(r0[f][k], keep[f][k]), (f, k)                      # handed out as copies: later replays leave them
+    assert {k: id(v) for k, v in pipe._frame_plans.items() if k[0] != "frame_batch"} == before
+    pipe._frame_plans.pop(key)
+
+
+# ------------------------------------------------------------------------------------------------ 7. the state
+def test_the_state_serves_the_later_frame_drivers(env):
+    """The state of a batched first frame is taken unchanged by the later-frame drivers.  Bit equality needs the appearance codes
+    of the same batch size, so the scene is the 3-vehicle one as a batch of its own against `run_frame` of it."""
+    pipe, scene, w = env["pipe"], env["scene"], env["w"]
+    got = pipe.run_frames_batched_geometry([scene], pad=False)[0]
+    steps = R.trajectory_steps(np.c_[np.arange(6.0) * 0.8, 0.05 * np.arange(6.0) ** 2])
+    later = [{"frame": torch.roll(scene["frame"], shifts=37 * (i + 1), dims=1).contiguous(), "steps": [steps[i]] * V,
+              "vehicle_seeds": [900 + 10 * i + v for v in range(V)]} for i in range(2)]
+    a = pipe.run_later_frames_batched_geometry(later, got["state"])
+    b = pipe.run_later_frames_batched_geometry(later, w["state"])
+    for x, y in zip(a, b):
+        assert x["skipped"] == y["skipped"] == []
+        for k in CROPS + ("frame_icn", "frame_vunet"):
+            assert torch.equal(x[k], y[k]), k
+    one = pipe.run_later_frame(later[0], got["state"])
+    want = pipe.run_later_frame(later[0], w["state"])
+    for k in CROPS + ("frame_icn", "frame_vunet"):
+        assert torch.equal(one[k], want[k]), k
+    # a state with an inert first-frame vehicle lists the kept vehicles only, as `run_frame`'s does
+    sg, rg = env["got"][0]["state"]["geometry"], env["refs"][0]["state"]["geometry"]
+    assert sg["vehicles"] == rg["vehicles"] == [0] and tuple(sg["pose_d"].shape) == (1, 7)
+    for k in ("pose_d", "cad_idx_d", "src_kp_d", "src_planes"):
+        assert torch.equal(sg[k], rg[k]), k
+    res = pipe.run_later_frames_batched_geometry([dict(l, steps=l["steps"][:2], vehicle_seeds=l["vehicle_seeds"][:2]) for l in later],
+                                                 env["got"][0]["state"])
+    assert len(res) == 2 and tuple(res[0]["icn_u8"].shape) == (1, 256, 256, 3)
+
+
+# ------------------------------------------------------------------------------------------------ 8. inpainting
+def test_inpainted_geometry_batch(env):
+    """2 + 1 vehicles with 'det_masks', vehicle EMPTY of scene 0 inert: its box is not pasted - outside every kept mask and kept
+    box the composites are the frame - and the kept rows equal the explicit given-geometry batch with that box set to zeros."""
+    bank, three = env["bank"], env["three"]
+    sds = {n: synth_sd(n) for n in ("hg", "icn", "vunet", "edge", "inpaint")}
+    pipe = pl.VehiclePipeline(DEV, inpaint=True, state_dicts=sds, cad_bank=bank)
+    pipe.device_pose = pipe.device_homography = True
+    H, W = HW
+
+    def inpaint_of(sc):
+        boxes = np.asarray(pl.synth_inpaint_boxes(np.asarray(sc["bboxes"]).tolist(), HW), np.int64).reshape(-1, 4)
+        det = torch.zeros((len(boxes), 1, H, W), dtype=torch.uint8, device=DEV)
+        for v, (x0, y0, x1, y1) in enumerate(boxes):                            # a stand-in detection: the middle of the box
+            det[v, 0, y0 + (y1 - y0) // 4:y1 - (y1 - y0) // 4, x0 + (x1 - x0) // 4:x1 - (x1 - x0) // 4] = 255
+        return {"boxes": boxes, "det_masks": det}
+
+    scenes = [dict(three[0], inpaint=inpaint_of(three[0])), three[1], dict(three[2], inpaint=inpaint_of(three[2]))]
+    got = pipe.run_frames_batched_geometry(scenes)
+    assert [g["skipped"] for g in got] == [[EMPTY], [], []]
+    assert tuple(got[0]["inpaint_u8"].shape) == (1, 256, 256, 3) and "inpaint_u8" not in got[1]
+    explicit = _explicit(scenes, got)
+    for e, sc in zip(explicit, scenes):                                          # the four tensors of the REAL boxes, given
+        if sc.get("inpaint") is not None:
+            with torch.cuda.device(DEV):
+                four = ops.inpaint_inputs(sc["frame"], sc["inpaint"]["det_masks"], sc["inpaint"]["boxes"])
+            e["inpaint"] = {"boxes": sc["inpaint"]["boxes"].copy(), **{k: four[k] for k in ops.INPAINT_KEYS}}
+    explicit[0]["inpaint"]["boxes"][EMPTY] = 0                                   # the gate's doing, by hand: that box is not pasted
+    ex = pipe.run_frames_batched(explicit)
+    _same_as_explicit(got, ex, [2, 0, 1], "inpaint", keys=CROPS + ("inpaint_u8",))
+    boxes = scenes[0]["inpaint"]["boxes"]
+    x0, y0, x1, y1 = boxes[EMPTY]
+    free = torch.ones((H, W), dtype=torch.bool, device=DEV)
+    for o in _kept_of(got[0], 2):
+        free[boxes[o][1]:boxes[o][3], boxes[o][0]:boxes[o][2]] = False
+        free &= ~got[0]["geometry"]["masks"][o].bool()
+    assert free[y0:y1, x0:x1].any()                                              # part of the inert box lies outside the kept one
+    kx0, ky0, kx1, ky1 = boxes[0]
+    for k in ("frame_icn", "frame_vunet"):
+        assert torch.equal(got[0][k][free], scenes[0]["frame"][free]), k
+        assert not torch.equal(got[0][k][ky0:ky1, kx0:kx1], scenes[0]["frame"][ky0:ky1, kx0:kx1]), k
+    per = pipe.run_frame(scenes[0])                                              # the per-frame rule: a skipped vehicle is not inpainted
+    assert per["skipped"] == [EMPTY] and torch.equal(per["frame_icn"][free], got[0]["frame_icn"][free])
+
+
+# ------------------------------------------------------------------------------------------------ 9. the range guard
+def test_range_guard_redoes_one_group_in_fp32(env):
+    """The status word raised behind the first of two groups: that group comes back as an exact-fp32 run of the same group, bit
+    for bit, the other stays split-fp16, and the word is clear afterwards."""
+    pipe, scene = env["pipe"], env["scene"]
+    scenes = [_cut(scene, 0, 2), _cut(scene, 2, 3)]
+    assert pl.frame_batch_groups([2, 1], 2) == [(0, 1), (1, 2)]
+    with ops.precision("f32"):
+        f32 = pipe.run_frames_batched_geometry(scenes[:1], check=None)
+    h16 = [pipe.run_frames_batched_geometry([sc])[0] for sc in scenes]
+    calls = {"n": 0}
+    orig = pipe._run_frame_batch_geometry
+
+    def flagged(sc, replay=False, rows=None):                                     # raise the status behind the 1st group only
+        out = orig(sc, replay, rows)
+        calls["n"] += 1
+        if calls["n"] == 1:
+            ops.status_word(DEV)[0] = 1
+        return out
+
+    pipe._run_frame_batch_geometry = flagged
+    try:
+        got = pipe.run_frames_batched_geometry(scenes, max_batch=2)
+    finally:
+        del pipe._run_frame_batch_geometry
+    assert calls["n"] == 3                                                        # group 0, its redo, group 1
+    for k in KEYS:
+        assert torch.equal(got[0][k], f32[0][k]), k
+        assert torch.equal(got[1][k], h16[1][k]), k
+    assert np.array_equal(pose_rows(got[0]["pose"]), pose_rows(f32[0]["pose"]))
+    assert any(not torch.equal(got[0][k], h16[0][k]) for k in ("icn_u8", "vunet_u8"))
+    assert not ops.range_exceeded(DEV) and not ops.range_exceeded(DEV, word=pipe.status_word())
+
+
+# ------------------------------------------------------------------------------------------------ 10. the fallbacks
+def test_fallbacks_are_run_frames(env):
+    pipe, three = env["pipe"], env["three"]
+    assert not any(k[0] == "frame_batch" for k in pipe._frame_plans)
+    want = list(pipe.run_frames(three, replay=False))
+    for tag, res in (("flag off", pipe.run_frames_batched_geometry(three, batch_geometry=False)),
+                     ("run_frames_batched", pipe.run_frames_batched(three))):
+        assert len(res) == 3
+        for f, (a, b) in enumerate(zip(res, want)):
+            assert a["skipped"] == b["skipped"], (tag, f)
+            for k in KEYS:
+                assert torch.equal(a[k], b[k]), (tag, f, k)
+    rep = pipe.run_frames_batched_geometry(three, replay=True, batch_geometry=False)
+    assert len(rep) == 3 and not any(k[0] == "frame_batch" for k in pipe._frame_plans)
+    # a list without geometry-mode scenes ignores the flag: the given-geometry batch
+    explicit = _explicit(three, env["got"])
+    a, b = pipe.run_frames_batched_geometry(explicit), pipe.run_frames_batched(explicit)
+    for f in range(3):
+        for k in KEYS:
+            assert torch.equal(a[f][k], b[f][k]), (f, k)
+    with pytest.raises(ValueError, match="mixes"):
+        pipe.run_frames_batched_geometry([three[0], explicit[2]])
+    # a 'cad_idx' outside the bank: IndexError after the read-back
+    with pytest.raises(IndexError, match="not in a bank"):
+        pipe.run_frames_batched_geometry([dict(three[2], cad_idx=np.array([len(pipe.cad_bank) + 3]))])
