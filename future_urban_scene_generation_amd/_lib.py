@@ -135,6 +135,7 @@ _SIGS = {
     "fusg_paste_layers_ragged_u8": (C.c_int, [_TP, _TP, C.c_void_p, _TP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _TP, C.c_void_p]),
     "fusg_fill_poly_planes_frames_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _TP,
                                                   C.c_void_p]),
+    "fusg_warp_perspective_clips_u8": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, _TP, C.c_void_p]),
     "fusg_keypoints_to_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "fusg_pnp_cpc": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p] * 4),
     "fusg_render_normals_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,

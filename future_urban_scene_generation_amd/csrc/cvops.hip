@@ -32,16 +32,12 @@ static inline unsigned blocks2d(long total) { return (unsigned)((total + 255) / 
 // job whose source is negative writes nothing (the empty rows of fusg_plane_homographies' fixed-size table).
 // src_mod > 0 (fusg_warp_perspective_frames_u8): the source image is index[2n] % src_mod - F frames' rows of a table fitted
 // for F * V vehicles all read ONE set of V * P source planes.
-__global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, const double* __restrict__ minv, U8View dst, long total,
-                                                                  const int* __restrict__ index, int src_mod) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int x = (int)(idx % dst.w);
-    const long r = idx / dst.w;
-    const int y = (int)(r % dst.h);
-    const int n = (int)(r / dst.h);
-    if (index && index[2 * n] < 0) return;
-    const double* M = minv + (long)n * 9;
+// warp_px: one destination pixel (x, y) of one job - M its inverse matrix, src_image() its source image (of src's shape and
+// strides), dst_px() the pixel's three bytes.  The ONE copy of the arithmetic: warp_perspective_u8_kernel and
+// warp_perspective_clips_u8_kernel differ only in how a thread finds its job's source and destination (the two callables, placed
+// where the one-stack kernel always had these statements).
+template <class SrcImage, class DstPx>
+__device__ __forceinline__ void warp_px(const double* M, const U8View& src, int x, int y, SrcImage src_image, DstPx dst_px) {
     const double X0 = M[0] * x + M[1] * y + M[2];
     const double Y0 = M[3] * x + M[4] * y + M[5];
     const double W0 = M[6] * x + M[7] * y + M[8];
@@ -55,12 +51,11 @@ __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, co
     const int ax = (int)(X & 31), ay = (int)(Y & 31);
     int w00 = (32 - ax) * (32 - ay) * 32, w01 = ax * (32 - ay) * 32, w10 = (32 - ax) * ay * 32, w11 = ax * ay * 32;
     if ((ax | ay) == 0) { w00 = 32767; w11 = 1; }
-    const int si = index ? index[2 * n] : n;
-    const unsigned char* s = src.p + (long)(src_mod > 0 ? si % src_mod : si) * src.sn;
+    const unsigned char* s = src_image();
     const bool y0ok = sy >= 0 && sy < src.h, y1ok = sy + 1 >= 0 && sy + 1 < src.h;
     const bool x0ok = sx >= 0 && sx < src.w, x1ok = sx + 1 >= 0 && sx + 1 < src.w;
     const unsigned char* p00 = s + sy * src.sh + sx * src.sw;
-    unsigned char* d = dst.p + (long)(index ? index[2 * n + 1] : n) * dst.sn + (long)y * dst.sh + (long)x * dst.sw;
+    unsigned char* d = dst_px();
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int v00 = (y0ok && x0ok) ? p00[c] : 0, v01 = (y0ok && x1ok) ? p00[src.sw + c] : 0;
@@ -69,6 +64,48 @@ __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, co
         const int o = (acc + (1 << 14)) >> 15;
         d[c] = (unsigned char)(o < 0 ? 0 : (o > 255 ? 255 : o));
     }
+}
+
+__global__ __launch_bounds__(256) void warp_perspective_u8_kernel(U8View src, const double* __restrict__ minv, U8View dst, long total,
+                                                                  const int* __restrict__ index, int src_mod) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int x = (int)(idx % dst.w);
+    const long r = idx / dst.w;
+    const int y = (int)(r % dst.h);
+    const int n = (int)(r / dst.h);
+    if (index && index[2 * n] < 0) return;
+    warp_px(minv + (long)n * 9, src, x, y,
+            [&]() -> const unsigned char* {
+                const int si = index ? index[2 * n] : n;
+                return src.p + (long)(src_mod > 0 ? si % src_mod : si) * src.sn;
+            },
+            [&]() { return dst.p + (long)(index ? index[2 * n + 1] : n) * dst.sn + (long)y * dst.sh + (long)x * dst.sw; });
+}
+
+// The same with the source stack a property of the DESTINATION image (VehiclePipeline.run_later_clips_batched: the future frames
+// of several clips as one pass, each clip's planes where its first frame left them).  ClipTab travels BY VALUE in the kernel
+// arguments (~1 KB), checked entry by entry on the host: clip c owns destination images [first[c], first[c + 1]) and reads its
+// own images[c] source planes at src[c] (dense u8 [images[c], H, W, 3]).  blockIdx.y = the job, so the clip lookup is uniform per
+// workgroup; job k reads image (index[2k] - first[c]) mod images[c] of its clip, which is inside that stack by construction.
+struct ClipTab { const unsigned char* src[FUSG_MAX_FRAMES]; int images[FUSG_MAX_FRAMES]; int first[FUSG_MAX_FRAMES + 1]; int n; };
+
+__global__ __launch_bounds__(256) void warp_perspective_clips_u8_kernel(ClipTab t, U8View src, const double* __restrict__ minv,
+                                                                        const int* __restrict__ index, U8View dst, int pixels) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= pixels) return;
+    const int k = blockIdx.y;
+    const int si = index[2 * k], di = index[2 * k + 1];
+    if (si < 0 || di < 0 || di >= dst.n) return;
+    int c = 0;
+    while (c + 1 < t.n && di >= t.first[c + 1]) ++c;                    // the clip whose range holds di: never an empty one
+    const int S = t.images[c];
+    if (S <= 0) return;
+    int m = (si - t.first[c]) % S;
+    m = m < 0 ? m + S : m;
+    const int x = idx % dst.w, y = idx / dst.w;
+    warp_px(minv + (long)k * 9, src, x, y, [&]() { return t.src[c] + (long)m * src.sn; },
+            [&]() { return dst.p + (long)di * dst.sn + (long)y * dst.sh + (long)x * dst.sw; });
 }
 
 // ------------------------------------------------------------------------------------------------ fillPoly planes
@@ -761,6 +798,59 @@ extern "C" int fusg_warp_perspective_frames_u8(const fusg_tensor* src, const dou
     FUSG_CHECK(src && dst && frames >= 1 && jobs >= 0 && src->n >= 1 && src->n <= 0x7fffffff / frames && dst->n == src->n * frames &&
                jobs <= dst->n, "warp_perspective_frames_u8: frames >= 1, dst holds frames * src->n images, at most one job per image");
     return fusg::plan_dispatch(warp_perspective_u8_impl, stream, src, minv, dst, index, jobs, (int32_t)src->n);
+}
+
+static int warp_perspective_clips_u8_impl(ClipTab t, int32_t H, int32_t W, const double* minv, const int32_t* index, int32_t jobs,
+                                          const fusg_tensor* dst, void* stream) {
+    const U8View src{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
+    const int pixels = H * W;
+    hipLaunchKernelGGL(warp_perspective_clips_u8_kernel, dim3(blocks2d(pixels), (unsigned)jobs), dim3(256), 0, (hipStream_t)stream, t, src,
+                       minv, (const int*)index, u8view(*dst), pixels);
+    FUSG_LAUNCH_CHECK("warp_perspective_clips_u8");
+    return FUSG_OK;
+}
+// srcs, src_images and dst_first are HOST tables, read (and checked) here, before anything is launched.
+extern "C" int fusg_warp_perspective_clips_u8(const void* const* srcs, const int32_t* src_images, const int32_t* dst_first,
+                                              int32_t n_clips, int32_t H, int32_t W, const double* minv, const int32_t* index,
+                                              int32_t jobs, const fusg_tensor* dst, void* stream) {
+    const char* what = "warp_perspective_clips_u8";
+    FUSG_CHECK(n_clips >= 1 && n_clips <= FUSG_MAX_FRAMES, "%s: n_clips = %d (1..%d)", what, n_clips, FUSG_MAX_FRAMES);
+    FUSG_CHECK(srcs && src_images && dst_first && dst, "%s: a table or dst is null (srcs, src_images, dst_first, dst)", what);
+    FUSG_CHECK(H >= 1 && W >= 1 && H < 32768 && W < 32768, "%s: planes of %d x %d", what, H, W);
+    FUSG_CHECK(jobs >= 0 && dst->n >= 0, "%s: jobs = %d, dst->n = %ld", what, jobs, (long)dst->n);
+    ClipTab t;
+    memset(&t, 0, sizeof(t));
+    t.n = n_clips;
+    FUSG_CHECK(dst_first[0] == 0, "%s: the destination offsets start at %d, not at 0", what, dst_first[0]);
+    for (int c = 0; c < n_clips; ++c) {
+        const int S = src_images[c];
+        const long cnt = (long)dst_first[c + 1] - dst_first[c];
+        FUSG_CHECK(S >= 0, "%s: clip %d has src_images = %d", what, c, S);
+        FUSG_CHECK(S == 0 || srcs[c] != nullptr, "%s: clip %d has %d source images and a null source pointer", what, c, S);
+        FUSG_CHECK(cnt >= 0, "%s: the destination offsets decrease at clip %d (%d after %d)", what, c, dst_first[c + 1], dst_first[c]);
+        FUSG_CHECK(S == 0 ? cnt == 0 : cnt % S == 0, "%s: clip %d owns %ld destination images, not a multiple of its %d source images",
+                   what, c, cnt, S);
+        t.src[c] = (const unsigned char*)srcs[c];
+        t.images[c] = S;
+        t.first[c] = dst_first[c];
+    }
+    t.first[n_clips] = dst_first[n_clips];
+    FUSG_CHECK((long)dst_first[n_clips] == (long)dst->n, "%s: the destination offsets end at %d, dst holds %ld images", what,
+               dst_first[n_clips], (long)dst->n);
+    FUSG_CHECK((long)jobs <= (long)dst->n, "%s: %d jobs for %ld destination images (at most one job per image)", what, jobs, (long)dst->n);
+    if (jobs == 0 || dst->n == 0) return FUSG_OK;
+    FUSG_CHECK(index != nullptr && minv != nullptr, "%s: a table is null (index, minv) with %d jobs", what, jobs);
+    FUSG_CHECK(jobs <= 65535, "%s: %d jobs (at most 65535 per launch)", what, jobs);
+    FUSG_CHECK(is_u8_hwc(*dst, 3) && dst->h == H && dst->w == W && dst->sw == 3 && dst->sh == 3L * W && dst->sn == 3L * H * W,
+               "%s: dst is dense u8 [n, H, W, 3] of %d x %d", what, H, W);
+    const unsigned char* d0 = (const unsigned char*)dst->data;
+    const unsigned char* d1 = d0 + dst->n * dst->sn;
+    for (int c = 0; c < n_clips; ++c) {
+        const unsigned char* b = t.src[c];
+        if (t.images[c] == 0) continue;
+        FUSG_CHECK(b + (long)t.images[c] * dst->sn <= d0 || b >= d1, "%s: clip %d's source planes overlap dst (in-place not supported)", what, c);
+    }
+    return fusg::plan_dispatch(warp_perspective_clips_u8_impl, stream, t, H, W, minv, index, jobs, dst);
 }
 
 extern "C" int fusg_fill_poly_planes_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t nplanes,

@@ -278,6 +278,88 @@ def frame_batch_seeds(seeds_per_scene: Sequence[Optional[Sequence[int]]], counts
     return out if any(have) else None
 
 
+# ---- `run_later_clips_batched`: the clip-major bookkeeping of a pass over the future frames of several clips (pure Python)
+def clip_batch_offsets(frames: Sequence[int], vehicles: Sequence[int]) -> List[int]:
+    """Row offsets of a group of clips with frames[c] future frames of vehicles[c] vehicles: clip c's rows are offsets[c] ..
+    offsets[c + 1], frames[c] * vehicles[c] of them (len(frames) + 1 entries)."""
+    if len(frames) != len(vehicles):
+        raise ValueError(f"{len(frames)} frame counts for {len(vehicles)} vehicle counts")
+    offs = [0]
+    for c, (F, V) in enumerate(zip(frames, vehicles)):
+        if int(F) < 0 or int(V) < 0:
+            raise ValueError(f"clip {c} has {F} frames of {V} vehicles")
+        offs.append(offs[-1] + int(F) * int(V))
+    return offs
+
+
+def clip_batch_row(offs: Sequence[int], vehicles: Sequence[int], c: int, f: int, v: int) -> int:
+    """The row of (clip c, frame f, vehicle v): clip-major, frame-major inside a clip (offs: `clip_batch_offsets`)."""
+    return int(offs[c]) + f * int(vehicles[c]) + v
+
+
+def clip_batch_frame_rows(frames: Sequence[int], vehicles: Sequence[int]) -> List[int]:
+    """The sum(frames) + 1 row offsets of the (clip, frame) frames in order - what the ragged paste takes: frame (c, f) owns
+    rows frame_rows[k] .. frame_rows[k + 1] with k = frames[0] + ... + frames[c - 1] + f."""
+    rows = [0]
+    for F, V in zip(frames, vehicles):
+        for _ in range(int(F)):
+            rows.append(rows[-1] + int(V))
+    return rows
+
+
+def clip_batch_seeds(seeds_per_clip: Sequence[Sequence[Optional[Sequence[int]]]], vehicles: Sequence[int]) -> Optional[List[int]]:
+    """The scenes' 'vehicle_seeds' (seeds_per_clip[c][f]: a list of vehicles[c], or None) concatenated in row order; None when
+    no scene that has vehicles carries seeds; ValueError naming the (clip, frame) offenders when only some do, or a list is not
+    as long as its clip has vehicles.  A scene without vehicles decides nothing."""
+    live = [(c, f) for c, sd in enumerate(seeds_per_clip) if int(vehicles[c]) > 0 for f in range(len(sd))]
+    have = [seeds_per_clip[c][f] is not None for c, f in live]
+    if any(have) and not all(have):
+        raise ValueError("run_later_clips_batched: either every scene that has vehicles carries 'vehicle_seeds' or none does "
+                         f"((clip, frame) without: {[cf for cf, h in zip(live, have) if not h]})")
+    if not any(have):
+        return None
+    out: List[int] = []
+    for c, f in live:
+        sd = seeds_per_clip[c][f]
+        if len(sd) != int(vehicles[c]):
+            raise ValueError(f"run_later_clips_batched: clip {c} frame {f} carries {len(sd)} vehicle_seeds for {int(vehicles[c])} vehicles")
+        out.extend(int(x) for x in sd)
+    return out
+
+
+def clip_batch_groups(frames: Sequence[int], vehicles: Sequence[int], max_batch: Optional[int] = None,
+                      max_frames: int = FRAME_BATCH_MAX_FRAMES) -> List[Tuple[int, int, bool]]:
+    """The passes of len(frames) clip tails: consecutive groups (lo, hi, oversized) of WHOLE clips packed greedily - a group is
+    closed when the next clip would push it over max_batch rows (frames[c] * vehicles[c] per clip; default LATER_MAX_BATCH), over
+    max_frames frames (what one ragged paste takes) or over max_frames clips (what one several-clip warp takes).  A clip that
+    alone exceeds a bound is a group of its own with oversized = True: it runs through the one-clip path
+    (`run_later_frames_batched`), which splits a clip by frames.  Every clip appears exactly once, in order."""
+    if max_batch is None:
+        max_batch = LATER_MAX_BATCH
+    if int(max_batch) < 1:
+        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
+    if int(max_frames) < 1:
+        raise ValueError(f"max_frames must be at least 1, got {max_frames}")
+    offs = clip_batch_offsets(frames, vehicles)                   # (ValueError for a negative count or lists of two lengths)
+    max_batch, max_frames = int(max_batch), int(max_frames)
+    groups: List[Tuple[int, int, bool]] = []
+    lo, rows, fr = 0, 0, 0
+    for c, F in enumerate(frames):
+        r, F = offs[c + 1] - offs[c], int(F)
+        big = r > max_batch or F > max_frames
+        if c > lo and (big or rows + r > max_batch or fr + F > max_frames or c - lo >= max_frames):
+            groups.append((lo, c, False))
+            lo, rows, fr = c, 0, 0
+        if big:
+            groups.append((c, c + 1, True))
+            lo, rows, fr = c + 1, 0, 0
+            continue
+        rows, fr = rows + r, fr + F
+    if len(frames) > lo:
+        groups.append((lo, len(frames), False))
+    return groups
+
+
 def later_geometry_batch_rows(scenes: Sequence[Dict], vehicles: Sequence[int], device_pose: bool, device_homography: bool,
                               inpaint: bool = False) -> Tuple[Optional[List[int]], bool]:
     """What `run_later_frames_batched_geometry` checks before it issues anything, for F geometry-mode scenes ('steps', no 'masks')
@@ -2510,6 +2592,228 @@ class VehiclePipeline:
             o["frame_icn"], o["frame_vunet"] = comp["frame_icn"][f], comp["frame_vunet"][f]
             res.append(o)
         return res, raw
+
+    # ------------------------------------------------------------------------------------------ future frames of several clips
+    def run_later_clips_batched(self, clips, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
+                                pad: Optional[bool] = None) -> list:
+        """`run_later_frames_batched` for the future frames of SEVERAL clips at once, with ragged F_c frames of V_c vehicles: every
+        selected frame of a video is a clip of 1 + 5 frames that usually carries one or two vehicles, so clip by clip each tail is
+        a pass of ~300 dependent launches at 5-10 rows.  The tails are independent of each other and `_later_nets` does not know
+        which clip or frame a row came from, so everything between the uint8 frames and the composited frames is issued once for
+        all sum(F_c * V_c) rows: the homography fits (host jobs, or `plane_homographies_device` over the concatenated corner
+        points), ONE plane warp whose source stack is a property of the destination row (fusg_warp_perspective_clips_u8: each
+        clip's planes stay where its first frame left them, passed by pointer - no torch.cat of source planes),
+        `mask_bbox_geom`, `icn_inputs_device` with each clip's central crops repeated per frame, `vunet_inputs`, the appearance
+        codes repeated per frame and concatenated, `_later_nets` once, `lab2bgr`, and one `paste_back_ragged_device` per
+        composite over all (clip, frame) frames, each from its own base.  Rows are clip-major, frame-major inside a clip: row
+        (c, f, v) = offsets[c] + f * V_c + v (`clip_batch_offsets`).
+
+        clips: a sequence of (later_scenes, state) pairs, each as `run_later_frames_batched` takes one: the F_c later scenes of
+        the clip (all sharing the first frame's 'src_planes' tensor; each its own 'frame', 'masks', 'dst_*', optional
+        'background', 'vehicle_seeds', 'inpaint') and the state of its first frame (`run_frame`'s or `run_frames_batched`'s).
+        F_c = 0 and V_c = 0 are allowed.  All frames of a call have one size.  Either every scene that has vehicles carries
+        'vehicle_seeds' or none does, and with a pipeline built with inpaint=True the same holds for 'inpaint' (any of the three
+        forms, per scene): each scene's EdgeConnect inputs are built from its own image into its row slice on the inpaint
+        stream, and the box rows go to the paste.  All of this is a ValueError before anything is launched, as are a scene whose
+        vehicle count differs from its state's, a clip whose scenes do not share one 'src_planes' tensor and a list that mixes
+        geometry-mode and given-geometry clips.
+        max_batch bounds the rows of a pass (default LATER_MAX_BATCH = 64), FRAME_BATCH_MAX_FRAMES its frames and clips:
+        consecutive WHOLE clips are packed greedily (`clip_batch_groups`); a clip that alone exceeds a bound goes through
+        `run_later_frames_batched` (which splits it by frames), with that method's results.
+        pad (None: pad when replay is on): the networks run at `frame_batch_pad(rows, max_batch)` rows - the next of 4, 8, 16,
+        32, 64 -, the padding rows of every input zero and their seeds 0; the outputs are cut to the real rows before `lab2bgr`
+        and the paste.  replay=True: the networks are ONE recorded plan per ("later_rows", padded_rows, precision[, "inpaint"]) -
+        at most five keys per video whatever its mix of F and V, apart from the ("later_batch", F, V, ...) plans of the one-clip
+        driver; outputs are handed out as copies.
+        check: the range guard of `run` - one status word per group; raised, the group is redone in exact fp32 under the RNG
+        state it was issued with.
+        A batch's crops are not bit for bit those of clip-by-clip passes: another batch size may route the convolutions
+        differently (the glue - warped planes, crop rows, network inputs, paste - is byte-equal).
+        Memory: the warped planes take 15 * H * W bytes per row (13.8 MB at 720 x 1280, 885 MB for 64 rows); the source planes
+        are not copied.
+        Returns one list per clip of `run_later_frame`'s dicts ('icn_u8', 'vunet_u8', 'geom', 'frame_icn', 'frame_vunet'
+        (+ 'inpaint_u8')), the keys and shapes `run_later_frames_batched` returns; tensors are views into the pass's stacked
+        results.  F_c = 0 -> []; V_c = 0 -> the no-vehicle shape, the composites equal to their base; [] -> [].
+        Geometry-mode states (scenes without 'masks') and sharded states (process group) go clip by clip through
+        `run_later_frames_batched` - the results of today."""
+        what = "run_later_clips_batched"
+        clips = [(list(scs), st) for scs, st in clips]
+        if not clips:
+            return []
+        geo = [any(self._is_geometry(sc, st) for sc in scs) for scs, st in clips]
+        given = [bool(scs) and not g for (scs, _), g in zip(clips, geo)]
+        if any(geo) and any(given):
+            raise ValueError(f"{what}: the list mixes geometry-mode clips (scenes without 'masks') and given-geometry clips "
+                             f"(geometry-mode: {[c for c, g in enumerate(geo) if g]})")
+        if any(geo) or (not _one_rank(self.group) and any(st.get("sharded") for _, st in clips)):
+            return [self._later_frames_batched(scs, st, replay, check, max_batch, False) for scs, st in clips]
+        sizes = {tuple(sc["frame"].shape) for scs, _ in clips for sc in scs}
+        if len(sizes) > 1:
+            raise ValueError(f"{what}: the frames of one call have one size, got {sorted(sizes)}")
+        frames = [len(scs) for scs, _ in clips]
+        vehicles = [int(st["central"].shape[0]) for _, st in clips]
+        for c, ((scs, _), V) in enumerate(zip(clips, vehicles)):
+            for f, sc in enumerate(scs):
+                if int(sc["masks"].shape[0]) != V:
+                    raise ValueError(f"{what}: the state of clip {c} holds {V} vehicles, its scene {f} {int(sc['masks'].shape[0])}")
+            if V and any(sc["src_planes"].data_ptr() != scs[0]["src_planes"].data_ptr() or sc["src_planes"].shape != scs[0]["src_planes"].shape
+                         for sc in scs):
+                raise ValueError(f"{what}: the scenes of clip {c} share the first frame's 'src_planes' (one tensor)")
+        seeds = clip_batch_seeds([[sc.get("vehicle_seeds") for sc in scs] for scs, _ in clips], vehicles)
+        inps = [((c, f), self._later_inpaint(sc)) for c, (scs, _) in enumerate(clips) if vehicles[c] for f, sc in enumerate(scs)]
+        if any(i is not None for _, i in inps) and not all(i is not None for _, i in inps):
+            raise ValueError(f"{what}: either every scene that has vehicles carries 'inpaint' or none does "
+                             f"((clip, frame) without: {[cf for cf, i in inps if i is None]})")
+        for _, i in inps:
+            if i is not None:
+                inpaint_scene_form(i)                             # (ValueError for a malformed entry, before anything is issued)
+        if max_batch is None:
+            max_batch = LATER_MAX_BATCH
+        pad = bool(replay) if pad is None else bool(pad)
+        out = []
+        for lo, hi, oversized in clip_batch_groups(frames, vehicles, max_batch):
+            if oversized:                                         # more rows or frames than a pass takes: the one-clip path splits by frames
+                out.append(self._later_frames_batched(clips[lo][0], clips[lo][1], replay, check, max_batch, False))
+                continue
+            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
+            rows = frame_batch_pad(sum(f * v for f, v in zip(frames[lo:hi], vehicles[lo:hi])), max_batch) if pad else None
+            out.extend(self._guarded(self._run_later_clips, (clips[lo:hi], replay, rows), check, rng))
+        return out
+
+    @torch.no_grad()
+    def _later_clips_stages(self, clips, icn_out=None, vu_out=None) -> Dict:
+        """The data movement of a several-clip later pass in front of the networks, clip-major over the (scenes, state) pairs and
+        frame-major inside a clip: 'warped' uint8 [N, P, H, W, 3], 'masks' uint8 [N, H, W], 'geom' int32 [N, 8], 'icn_x' [N, 21,
+        R, R], 'vu_y' [N, 3, R, R] for the N = sum(F_c * V_c) rows (icn_out / vu_out: the N real rows of a padded or recorded
+        pass's buffers, written in place).  Every row holds the bytes `_later_batch_stages` builds for its clip: a clip without
+        frames or without vehicles contributes no row.  At least one row."""
+        import numpy as np
+
+        from . import frame_ops as fo
+        from .warp_learn import planes_utils as pu
+        R = 256
+        live = [(list(scs), st) for scs, st in clips if len(scs) and int(st["central"].shape[0])]
+        scenes = [sc for scs, _ in live for sc in scs]
+        with torch.cuda.device(self.device):
+            planes = [scs[0]["src_planes"].contiguous() for scs, _ in live]       # by pointer: each clip's planes stay where they are
+            counts = [len(scs) for scs, _ in live]
+            kp = {k: [veh for sc in scenes for veh in sc[k]] for k in ("src_kp", "dst_kp")}
+            vis = {k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in scenes]) for k in ("src_vis", "dst_vis")}
+            if self.device_homography:
+                minv, index = pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
+                warped = pu.warp_planes_clips_fitted(planes, counts, minv, index)              # :376-381
+            else:
+                jobs = pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
+                warped = pu.warp_planes_clips_batch(planes, counts, jobs)
+            cat = lambda k: scenes[0][k] if len(scenes) == 1 else torch.cat([sc[k] for sc in scenes])    # noqa: E731
+            masks, sketch = cat("masks"), cat("dst_sketch")
+            _, geom = fo.mask_bbox_geom(masks)
+            central = [st["central"].repeat(len(scs), 1, 1, 1) for scs, st in live]
+            icn_x = pu.icn_inputs_device(warped, sketch, central[0] if len(central) == 1 else torch.cat(central), geom, R, R,
+                                         out=icn_out)                                          # :385-387
+            _, vu_y = fo.vunet_inputs(scenes[0]["frame"], masks, sketch, sketch, geom, R,      # :415-420 (y_tilde reads no frame)
+                                      out=None if vu_out is None else (None, vu_out))
+        return {"warped": warped, "masks": masks, "geom": geom, "icn_x": icn_x, "vu_y": vu_y}
+
+    @torch.no_grad()
+    def _run_later_clips(self, clips, replay=False, rows=None) -> list:
+        """One group of `run_later_clips_batched`: one list of `run_later_frame` dicts per clip.  rows: the row count the networks
+        run at (>= N, the padding rows zero); None: N."""
+        import numpy as np
+
+        from . import ops
+        from .warp_learn import planes_utils as pu
+        dev, R = self.device, 256
+        frames = [len(scs) for scs, _ in clips]
+        vehicles = [int(st["central"].shape[0]) for _, st in clips]
+        offs = clip_batch_offsets(frames, vehicles)
+        N = offs[-1]
+        if N == 0:
+            return [[self._run_later_frame(sc, st) for sc in scs] for scs, st in clips]
+        B = N if rows is None else max(int(rows), N)
+        scenes = [sc for scs, _ in clips for sc in scs]                           # the (clip, frame) frames, in order
+        frame_rows = clip_batch_frame_rows(frames, vehicles)
+        live = [(scs, st) for (scs, st), F, V in zip(clips, frames, vehicles) if F and V]
+        inpaint = self._later_inpaint(live[0][0][0]) is not None
+        seeds = clip_batch_seeds([[sc.get("vehicle_seeds") for sc in scs] for scs, _ in clips], vehicles)
+        if seeds is not None:
+            seeds = seeds + [0] * (B - N)
+        with torch.cuda.device(dev):
+            replay = replay and ops.RECORDER is None
+            pkey = ("later_rows", B, ops.PRECISION) + (("inpaint",) if inpaint else ())
+            cp = self._plan(pkey) if replay else None
+            tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
+
+            def buf(k, c):
+                """The networks' input `k` at B rows, its padding rows zero, and the view of its N real rows the glue writes."""
+                t = tgt.get(k)
+                if t is None:
+                    t = ops.nhwc_empty(B, c, R, R, dev, zero=True)
+                elif B > N:
+                    t[N:].zero_()
+                return t, t[:N]
+
+            def per_row(i):
+                """The clips' appearance code i repeated per frame, concatenated in row order, zero rows up to B."""
+                parts = [st["appearance"][i].repeat(len(scs), 1, 1, 1) for scs, st in live]
+                if B > N:
+                    parts.append(parts[0].new_zeros((B - N,) + tuple(parts[0].shape[1:])))
+                return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+            ec, ec_join = self._inpaint_inputs_ragged(scenes, frame_rows, B, tgt) if inpaint else (None, None)
+            if B > N or tgt:
+                (icn_x, icn_rows), (vu_y, vu_rows) = buf("icn_x", 21), buf("vu_y", 3)
+                st = self._later_clips_stages(clips, icn_out=icn_rows, vu_out=vu_rows)
+            else:
+                st = self._later_clips_stages(clips)
+                icn_x, vu_y = st["icn_x"], st["vu_y"]
+            geom, masks = st["geom"], st["masks"]
+            nets_in = {"icn_x": icn_x, "vu_y": vu_y, "app0": per_row(0), "app1": per_row(1)}
+            if ec is not None:
+                ec_join()
+                nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
+            if replay:
+                out = self._replay(pkey, nets_in, seeds, fn=self._later_nets)
+            else:
+                out = self._later_nets(nets_in, seeds)
+            out = {k: v[:N] for k, v in out.items()}             # the real rows: nothing below knows about padding
+            out["icn_u8"] = pu.lab2bgr(out["icn_u8"].contiguous())
+            # ---- one ragged paste per composite over all (clip, frame) frames (:340: with --inpaint the composite starts from the frame)
+            bases = [sc["frame"] if self._later_inpaint(sc) is not None else sc.get("background", sc["frame"]) for sc in scenes]
+            box = {}
+            if inpaint:                                           # :340-350: every vehicle's inpainted box under its crop, in vehicle order
+                brow = np.zeros((N, 8), np.int32)
+                brow[:, :4] = np.concatenate([np.asarray(sc["inpaint"]["boxes"]).reshape(-1, 4) for scs, _ in live for sc in scs])
+                box = dict(box_images=out["inpaint_u8"].contiguous(), box_geom=ops.h2d(brow, dev, torch.int32))
+            comp = {k: pu.paste_back_ragged_device(bases, frame_rows, out[c], geom, masks, **box)          # :393-410, :428-445
+                    for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+        keys = ("icn_u8", "vunet_u8") + (("inpaint_u8",) if inpaint else ())
+        res, k0 = [], 0
+        for c, (scs, _) in enumerate(clips):
+            one = []
+            for f, sc in enumerate(scs):
+                if vehicles[c] == 0:
+                    o = self._no_vehicles(R, "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if self._later_inpaint(sc) is not None else ()))
+                else:
+                    sl = slice(frame_rows[k0 + f], frame_rows[k0 + f + 1])
+                    o = {k: out[k][sl] for k in keys}
+                    o["geom"] = geom[sl]
+                o["frame_icn"], o["frame_vunet"] = comp["frame_icn"][k0 + f], comp["frame_vunet"][k0 + f]
+                one.append(o)
+            k0 += len(scs)
+            res.append(one)
+        return res
+
+    def run_clips_batched(self, clips, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
+                          pad: Optional[bool] = None) -> list:
+        """Whole clips of a video as batched passes: clips is a sequence of (first_scene, later_scenes) pairs; the first frames
+        go through `run_frames_batched`, all tails through `run_later_clips_batched` with the states it returned.  Returns, per
+        clip, [first_result, later_results...]."""
+        clips = [(first, list(later)) for first, later in clips]
+        firsts = self.run_frames_batched([first for first, _ in clips], replay=replay, check=check, max_batch=max_batch, pad=pad)
+        tails = self.run_later_clips_batched([(later, f["state"]) for (_, later), f in zip(clips, firsts)], replay=replay, check=check,
+                                             max_batch=max_batch, pad=pad)
+        return [[f] + t for f, t in zip(firsts, tails)]
 
     def run_clip_frames(self, first_scene: Dict, later_scenes, replay: bool = False, batched: bool = False,
                         batch_geometry: bool = False):

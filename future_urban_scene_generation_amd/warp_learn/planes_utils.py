@@ -585,6 +585,83 @@ def warp_planes_frames_fitted(src_planes: torch.Tensor, minv: torch.Tensor, inde
     return _warp_frames(flat, minv, index, n if V else 0, frames).view(frames * V, P, H, W, 3)
 
 
+def _clips_layout(what: str, src_planes_per_clip, frames_per_clip):
+    """What the several-clip warps check before any launch: (the clips' planes, [(F_c, V_c)], row offsets, P, H, W)."""
+    planes, frames = list(src_planes_per_clip), [int(f) for f in frames_per_clip]
+    if not 1 <= len(planes) <= L.MAX_FRAMES or len(frames) != len(planes):
+        raise ValueError(f"{what}: {len(planes)} clips with {len(frames)} frame counts (1..{L.MAX_FRAMES} clips per launch, one count each)")
+    first = planes[0]
+    if not isinstance(first, torch.Tensor) or first.dim() != 5:
+        raise ValueError(f"{what}: a clip's source planes are a CUDA uint8 tensor [V, P, H, W, 3]")
+    P, H, W = (int(x) for x in first.shape[1:4])
+    offs = [0]
+    for c, (t, f) in enumerate(zip(planes, frames)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 5 or t.dtype != torch.uint8 or t.device != first.device or \
+                tuple(t.shape[1:]) != (P, H, W, 3):
+            raise ValueError(f"{what}: clip {c}'s source planes are {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', None)}, "
+                             f"expected uint8 [V, {P}, {H}, {W}, 3] on {first.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: clip {c}'s source planes are not contiguous (they are passed by pointer, not copied)")
+        if f < 0:
+            raise ValueError(f"{what}: clip {c} has {f} frames")
+        offs.append(offs[-1] + f * int(t.shape[0]))
+    return planes, [(f, int(t.shape[0])) for t, f in zip(planes, frames)], offs, P, H, W
+
+
+def _warp_clips(planes, shape, offs, P: int, H: int, W: int, minv, index, jobs: int) -> torch.Tensor:
+    """fusg_warp_perspective_clips_u8: `jobs` rows of (minv, index) warp each clip's own planes into its rows of offs[-1] * P zeroed images."""
+    n = len(planes)
+    warped = torch.zeros((offs[-1] * P, H, W, 3), dtype=torch.uint8, device=planes[0].device)
+    if jobs:
+        srcs = (C.c_void_p * n)(*[t.data_ptr() if t.shape[0] else None for t in planes])
+        images = (C.c_int32 * n)(*[V * P for _, V in shape])
+        first = (C.c_int32 * (n + 1))(*[o * P for o in offs])
+        with torch.cuda.device(warped.device):
+            L.check(L.lib().fusg_warp_perspective_clips_u8(srcs, images, first, n, H, W, minv.data_ptr(), index.data_ptr(), int(jobs),
+                                                           C.byref(_u8desc(warped)), ops.stream_ptr()), "warp_perspective_clips_u8")
+    return warped.view(offs[-1], P, H, W, 3)
+
+
+def warp_planes_clips_batch(src_planes_per_clip, frames_per_clip, jobs_per_row) -> torch.Tensor:
+    """`warp_planes_frames_batch` for the future frames of SEVERAL clips in ONE launch, every clip's planes passed by pointer
+    (no copy of them is made): src_planes_per_clip[c] CUDA uint8 [V_c, P, H, W, 3] (contiguous), frames_per_clip[c] = F_c,
+    jobs_per_row[r] = warp_jobs(...) of row r - clip-major, frame-major inside a clip: r = offs[c] + f * V_c + v
+    -> [sum(F_c * V_c), P, H, W, 3], zeros where nothing is warped."""
+    planes, shape, offs, P, H, W = _clips_layout("warp_planes_clips_batch", src_planes_per_clip, frames_per_clip)
+    if len(jobs_per_row) != offs[-1]:
+        raise ValueError(f"warp_planes_clips_batch: {len(jobs_per_row)} job lists for {offs[-1]} rows ((frames, vehicles) per clip: {shape})")
+    src_idx, dst_idx, Hs = [], [], []
+    for c, (F, V) in enumerate(shape):
+        for r in range(offs[c], offs[c + 1]):
+            last = {}
+            for i, j, H12, _ in jobs_per_row[r]:                  # plane order: a later job on slot j overwrites an earlier one
+                last[j] = (i, H12)
+            for j, (i, H12) in last.items():
+                src_idx.append(offs[c] * P + ((r - offs[c]) % V) * P + i)
+                dst_idx.append(r * P + j)
+                Hs.append(H12)
+    minv_d = index = None
+    if Hs:
+        minv = np.linalg.inv(np.asarray(Hs, dtype=np.float64).reshape(len(Hs), 3, 3)).reshape(len(Hs), 9)
+        minv_d = ops.h2d(minv, planes[0].device)
+        index = ops.h2d(np.stack([src_idx, dst_idx], 1).astype(np.int32), planes[0].device)
+    return _warp_clips(planes, shape, offs, P, H, W, minv_d, index, len(Hs))
+
+
+def warp_planes_clips_fitted(src_planes_per_clip, frames_per_clip, minv: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """`warp_planes_frames_fitted` for the future frames of SEVERAL clips in ONE launch, every clip's planes passed by pointer:
+    minv / index are the tables `plane_homographies_device` fits for all rows of the call (clip-major, frame-major inside a
+    clip; the source corner points of a clip repeated per frame), whose source entries (row * P + i) the kernel folds back onto
+    the row's own clip's V_c * P planes.  -> [sum(F_c * V_c), P, H, W, 3]."""
+    planes, shape, offs, P, H, W = _clips_layout("warp_planes_clips_fitted", src_planes_per_clip, frames_per_clip)
+    n = offs[-1] * P
+    if not (isinstance(minv, torch.Tensor) and isinstance(index, torch.Tensor)) or minv.dtype != torch.float64 or \
+            index.dtype != torch.int32 or tuple(minv.shape) != (n, 9) or tuple(index.shape) != (n, 2) or \
+            not (minv.is_contiguous() and index.is_contiguous()) or minv.device != planes[0].device or index.device != planes[0].device:
+        raise ValueError(f"warp_planes_clips_fitted: minv float64 [{n}, 9] and index int32 [{n}, 2], contiguous, on the planes' device")
+    return _warp_clips(planes, shape, offs, P, H, W, minv, index, n)
+
+
 def warp_unwarp_planes(src_planes: Image, src_planes_kpoints: List[np.ndarray], dst_planes_kpoints: List[np.ndarray],
                        src_visibilities, dst_visibilities, pascal_class: str, pascal_texture_planes=pascal_texture_planes,
                        unwarp: bool = True):

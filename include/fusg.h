@@ -538,6 +538,22 @@ int fusg_fill_poly_planes_frames_u8(const void* const* frames, const int32_t* fr
                                     const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs, int32_t n_planes,
                                     const fusg_tensor* dst, void* stream);
 
+/* fusg_warp_perspective_frames_u8 with the source stack a property of the DESTINATION image (VehiclePipeline.
+ * run_later_clips_batched: the future frames of several clips as ONE pass; a new entry point, FUSG_VERSION stays 118).  Three HOST
+ * tables, read before the call returns and handed to the kernel by value: srcs[c] = DEVICE pointer to clip c's dense u8
+ * [src_images[c], H, W, 3] source planes; dst_first = n_clips + 1 non-decreasing offsets from 0 to dst->n, clip c owns destination
+ * images [dst_first[c], dst_first[c + 1]) - a multiple of src_images[c] (frames * planes), 0 where src_images[c] is 0.  minv
+ * (double [jobs][9]) and index (int32 [jobs][2]) are DEVICE tables as above: job k writes image d = index[2k + 1] of dst from image
+ * (index[2k] - dst_first[c]) mod src_images[c] (non-negative) of srcs[c], c the clip that owns d - so a table fitted for all rows
+ * of the call (source row * P + i) and a compact one (dst_first[c] + v * P + i) both address each clip's own planes.  A job with
+ * index[2k] < 0 or d outside [0, dst->n) writes nothing; images no job names are left untouched.  Checked on the host before
+ * anything is launched: 1 <= n_clips <= FUSG_MAX_FRAMES, no null source where src_images[c] > 0, src_images[c] >= 0, the offsets,
+ * dst dense u8 [n, H, W, 3] overlapping no source, jobs <= dst->n (and <= 65535), index and minv not NULL when jobs > 0.  jobs == 0
+ * or dst->n == 0: no launch, returns 0.  The per-pixel arithmetic is fusg_warp_perspective_u8's: same bytes. */
+int fusg_warp_perspective_clips_u8(const void* const* srcs, const int32_t* src_images, const int32_t* dst_first, int32_t n_clips,
+                                   int32_t H, int32_t W, const double* minv, const int32_t* index, int32_t jobs,
+                                   const fusg_tensor* dst, void* stream);
+
 /* ---- pose fit ------------------------------------------------------------------------------- */
 /*
  * The reference's pose fit ("CamPoseCalib": Levenberg-Marquardt on a Rodrigues vector + translation, utils/cpc.py:45-139

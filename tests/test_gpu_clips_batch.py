@@ -1,0 +1,444 @@
+"""GPU: the future frames of SEVERAL clips as one batched pass (VehiclePipeline.run_later_clips_batched,
+fusg_warp_perspective_clips_u8).  The kernel equals the per-clip kernel byte for byte; the data movement in front of the
+networks equals the one-clip stages; the rendered frames are compared with the vehicle-serial CPU oracle under the bars of
+tests/test_gpu_later_batch.py (not with clip-by-clip device passes: another batch size may route convolutions differently)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import later_inpaint_ref as lr                                             # noqa: E402
+import oracle                                                              # noqa: E402
+from conftest import synth_sd                                              # noqa: E402
+from future_urban_scene_generation_amd import ops                          # noqa: E402
+from future_urban_scene_generation_amd import pipeline as pl               # noqa: E402
+from future_urban_scene_generation_amd.warp_learn import planes_utils as pu   # noqa: E402
+from test_gpu_later_batch import _bars, _host_threads, _inpaint_bars, _moved, inpaint_env   # noqa: E402,F401
+
+DEV = "cuda:0"
+HW = (360, 640)
+KEYS = ("icn_u8", "vunet_u8", "geom", "frame_icn", "frame_vunet")
+
+
+def _d(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+# ------------------------------------------------------------------------------------------------ the kernel
+def _near_identity(g, n):
+    """n homographies near the identity: a little rotation, scale, shift and perspective."""
+    M = np.tile(np.eye(3), (n, 1, 1))
+    M[:, :2, :2] += g.normal(0, 0.04, (n, 2, 2))
+    M[:, :2, 2] = g.normal(0, 2.5, (n, 2))
+    M[:, 2, :2] = g.normal(0, 4e-4, (n, 2))
+    return M
+
+
+def _kernel_case(shape, P, H, W, seed=3, outside=None, holes=0.25):
+    """Clips of (V, F) with seeded random source planes and the FIXED-SIZE table `plane_homographies_device` would fit for all
+    rows of the call: entry r * P + j = (source r * P + i or -1, destination r * P + j).  outside: an entry whose matrix maps
+    wholly outside the image."""
+    g = np.random.default_rng(seed)
+    planes = [_d(g.integers(0, 256, (V, P, H, W, 3), dtype=np.uint8)) for V, _ in shape]
+    offs = pl.clip_batch_offsets([F for _, F in shape], [V for V, _ in shape])
+    n = offs[-1] * P
+    minv = _near_identity(g, n)
+    index = np.zeros((n, 2), np.int32)
+    for r in range(offs[-1]):
+        for j in range(P):
+            index[r * P + j] = (r * P + (j + r) % P, r * P + j)
+    index[g.random(n) < holes, 0] = -1
+    if outside is not None:
+        index[outside, 0] = (outside // P) * P
+        minv[outside] = np.array([[1, 0, 5000.0], [0, 1, -7000.0], [0, 0, 1]])
+    return planes, offs, minv.reshape(n, 9), index
+
+
+def _per_clip(shape, planes, offs, P, minv, index):
+    """fusg_warp_perspective_frames_u8 once per clip on that clip's slice of the table (sources and destinations re-based)."""
+    out = []
+    for c, (V, F) in enumerate(shape):
+        if V == 0 or F == 0:
+            continue
+        lo, hi = offs[c] * P, offs[c + 1] * P
+        idx = index[lo:hi].copy()
+        idx[:, 1] -= lo
+        idx[idx[:, 0] >= 0, 0] -= lo
+        out.append(pu.warp_planes_frames_fitted(planes[c], _d(minv[lo:hi]), _d(idx), F))
+    return torch.cat(out)
+
+
+SHAPE = [(2, 2), (0, 3), (1, 3), (3, 1)]                    # (V, F) per clip
+
+
+def test_clips_kernel_equals_the_per_clip_kernel():
+    """37 x 53: neither the row bytes (159) nor the pixel count (1961) is a multiple of the workgroup size; four clips, one without
+    vehicles; a fixed-size table with holes and one matrix that maps wholly outside."""
+    P, H, W = 5, 37, 53
+    assert (3 * W) % 256 and (H * W) % 256 and H * W > 256
+    planes, offs, minv, index = _kernel_case(SHAPE, P, H, W, outside=7)
+    assert offs == [0, 4, 4, 7, 10] and (index[:, 0] < 0).any() and index[7, 0] >= 0
+    frames = [F for _, F in SHAPE]
+    got = pu.warp_planes_clips_fitted(planes, frames, _d(minv), _d(index))
+    assert tuple(got.shape) == (10, P, H, W, 3) and got.dtype == torch.uint8
+    assert torch.equal(got, _per_clip(SHAPE, planes, offs, P, minv, index))
+    flat = got.view(10 * P, H, W, 3)
+    for k in range(10 * P):                                  # an image no job names stays zero, and so does the one mapped outside
+        if index[k, 0] < 0 or k == 7:
+            assert not flat[k].any(), k
+    assert sum(bool(flat[k].any()) for k in range(10 * P)) == int((index[:, 0] >= 0).sum()) - 1
+    # the compact form: only the real jobs, sources written dst_first[c] + v * P + i, in a shuffled order
+    g = np.random.default_rng(8)
+    keep = g.permutation(np.nonzero(index[:, 0] >= 0)[0])
+    cidx = index[keep].copy()
+    for k, (s, d) in enumerate(cidx):
+        c = max(c for c in range(len(SHAPE)) if offs[c] * P <= d and offs[c + 1] > offs[c])
+        V = SHAPE[c][0]
+        cidx[k, 0] = offs[c] * P + ((s // P - offs[c]) % V) * P + s % P
+    shape = [(F, V) for V, F in SHAPE]
+    again = pu._warp_clips(planes, shape, offs, P, H, W, _d(minv[keep]), _d(cidx), len(keep))
+    assert torch.equal(again, got)
+
+
+def test_clips_batch_wrapper_equals_the_per_clip_wrapper():
+    """`warp_planes_clips_batch` (host-fitted jobs, several jobs on one slot: the last wins) == `warp_planes_frames_batch` per clip."""
+    P, H, W = 5, 37, 53
+    g = np.random.default_rng(4)
+    planes = [_d(g.integers(0, 256, (V, P, H, W, 3), dtype=np.uint8)) for V, _ in SHAPE]
+    offs = pl.clip_batch_offsets([F for _, F in SHAPE], [V for V, _ in SHAPE])
+    jobs = []
+    for r in range(offs[-1]):
+        n = int(g.integers(0, 7))
+        Hs = _near_identity(g, n)
+        jobs.append([(int(g.integers(0, P)), int(g.integers(0, P)), Hs[k], None) for k in range(n)])
+    assert any(len({j for _, j, _, _ in row}) < len(row) for row in jobs) and any(not row for row in jobs)
+    got = pu.warp_planes_clips_batch(planes, [F for _, F in SHAPE], jobs)
+    want = torch.cat([pu.warp_planes_frames_batch(planes[c], jobs[offs[c]:offs[c + 1]], F) for c, (V, F) in enumerate(SHAPE) if V and F])
+    assert got.any() and torch.equal(got, want)
+
+
+def test_one_clip_equals_the_frames_kernel_and_64_clips_of_one_image():
+    P, H, W = 5, 37, 53
+    planes, offs, minv, index = _kernel_case([(2, 2)], P, H, W, seed=5)
+    got = pu.warp_planes_clips_fitted(planes, [2], _d(minv), _d(index))
+    assert got.any() and torch.equal(got, pu.warp_planes_frames_fitted(planes[0], _d(minv), _d(index), 2))
+    # FUSG_MAX_FRAMES clips of one vehicle, one frame, one plane, 8 x 8: every destination image reads ITS clip's only plane
+    shape = [(1, 1)] * 64
+    planes, offs, minv, index = _kernel_case(shape, 1, 8, 8, seed=6, holes=0.1)
+    got = pu.warp_planes_clips_fitted(planes, [1] * 64, _d(minv), _d(index))
+    want = pu.warp_planes_fitted(torch.cat(planes), _d(minv), _d(index))
+    assert got.any() and torch.equal(got, want)
+    assert len({bytes(got[r].cpu().numpy().tobytes()) for r in range(64)}) > 32
+    with pytest.raises(ValueError, match="clips"):
+        pu.warp_planes_clips_fitted(planes + planes[:1], [1] * 65, _d(minv), _d(index))
+
+
+# ------------------------------------------------------------------------------------------------ the pass
+@pytest.fixture(scope="module")
+def env():
+    """One pipeline; the scene of tests/test_gpu_later_batch.py (synth_frame seed 49, 3 vehicles, its `_moved` poses, whose fits
+    are well-posed for the oracle's per-plane solver) cut into two clips: A = vehicles 0-1 with later frames 0, 1; B = vehicle 2
+    with later frames 0, 1, 2 on a visibly different image, its frame 1 carrying a 'background'.  The oracle's first-frame state
+    and later frames of both clips are computed once, on at most 16 host threads."""
+    ops.set_precision("f16x3")
+    sds = {n: synth_sd(n) for n in ("hg", "icn", "vunet")}
+    pipe = pl.VehiclePipeline(DEV, state_dicts=sds)
+    first = pl.synth_frame(3, HW, DEV, seed=49)
+    first["vehicle_seeds"] = [11, 12, 13]
+    moved = [_moved(first, f) for f in range(3)]
+    other = lambda t: torch.flip(t, dims=(0,)).contiguous()                                   # noqa: E731
+    firsts = [pl.slice_scene(first, 0, 2), dict(pl.slice_scene(first, 2, 3), frame=other(first["frame"]))]
+    later = [[pl.slice_scene(moved[f], 0, 2) for f in (0, 1)],
+             [dict(pl.slice_scene(moved[f], 2, 3), frame=other(moved[f]["frame"])) for f in (0, 1, 2)]]
+    bg = torch.full_like(first["frame"], 77)
+    later[1][1]["background"] = bg
+    assert not torch.equal(later[0][0]["frame"], later[1][0]["frame"])
+    f0 = [pipe.run_frame(sc) for sc in firsts]
+    nt = torch.get_num_threads()
+    torch.set_num_threads(_host_threads())
+    try:
+        o0 = [oracle.frame_pass(sds, lr.scene_cpu(sc)) for sc in firsts]
+        cpus = [[lr.scene_cpu(sc) for sc in scs] for scs in later]
+        refs = [[oracle.later_frame_pass(sds, c, o["state"]) for c in cs] for cs, o in zip(cpus, o0)]
+    finally:
+        torch.set_num_threads(nt)
+    clips = [(scs, f["state"]) for scs, f in zip(later, f0)]
+    return dict(sds=sds, pipe=pipe, firsts=firsts, later=later, f0=f0, clips=clips, cpus=cpus, refs=refs, bg=bg.cpu().numpy())
+
+
+def _all_bars(env, got, tag):
+    assert len(got) == 2
+    for c, g in enumerate(got):
+        assert len(g) == len(env["later"][c]), (tag, c)
+        for f in range(len(g)):
+            assert set(g[f]) == set(KEYS)
+            V = 2 - c
+            assert tuple(g[f]["icn_u8"].shape) == (V, 256, 256, 3) and tuple(g[f]["geom"].shape) == (V, 8)
+            assert tuple(g[f]["frame_vunet"].shape) == HW + (3,)
+            cpu = env["cpus"][c][f]
+            _bars(g[f], env["refs"][c][f], cpu, f"{tag} clip {c} frame {f}", base=env["bg"] if "background" in cpu else None)
+
+
+def _equal(a, b, keys=KEYS):
+    assert len(a) == len(b)
+    for ca, cb in zip(a, b):
+        assert len(ca) == len(cb)
+        for x, y in zip(ca, cb):
+            for k in keys:
+                assert torch.equal(x[k], y[k]), k
+
+
+def _stage_scenes(pipe, V, F, seed):
+    first = pl.synth_frame(V, HW, DEV, seed=seed)
+    first["vehicle_seeds"] = list(range(V))
+    state = pipe.run_frame(first)["state"]
+    scenes = []
+    for f in range(F):
+        sc = pl.synth_later_frame(first, f + 1)
+        sc["frame"] = torch.roll(first["frame"], shifts=11 * (f + 1) + seed, dims=1).contiguous()
+        sc["masks"] = torch.roll(first["masks"], shifts=(3 * f + 2, -4 * f - 1), dims=(1, 2))
+        sc["dst_sketch"] = torch.roll(first["dst_sketch"], shifts=(3 * f + 2, -4 * f - 1), dims=(1, 2))
+        sc["dst_vis"] = np.roll(first["dst_vis"], f, axis=0) if V > 1 else first["dst_vis"]
+        scenes.append(sc)
+    return scenes, state
+
+
+def _assert_stages(pipe, clips, tag):
+    got = pipe._later_clips_stages(clips)
+    want = [pipe._later_batch_stages(scs, st) for scs, st in clips if len(scs) and int(st["central"].shape[0])]
+    assert got["warped"].any()
+    for k in ("warped", "geom", "icn_x", "vu_y"):
+        ref = torch.cat([w[k] for w in want])
+        assert got[k].shape == ref.shape and got[k].dtype == ref.dtype, (tag, k)
+        assert torch.equal(got[k], ref), (tag, k)
+    return got, want
+
+
+def test_stages_equal_the_one_clip_stages(env):
+    """Two clips that differ in F, V, frames and poses (and an empty tail between them): warped planes, crop rows and both
+    networks' inputs == `_later_batch_stages` per clip, concatenated."""
+    pipe = env["pipe"]
+    assert pipe.device_homography is False
+    a, b = _stage_scenes(pipe, 3, 2, 53), _stage_scenes(pipe, 1, 3, 51)
+    got, want = _assert_stages(pipe, [a, ([], b[1]), b], "host fits")
+    assert tuple(got["icn_x"].shape) == (9, 21, 256, 256) and not torch.equal(want[0]["warped"][:1], want[1]["warped"][:1])
+
+
+def test_stages_with_device_homography_on_the_tie_free_scene(env):
+    """device_homography=True: the table fitted for all rows of the call feeds the several-clip warp as it stands.  On the scene
+    free of rounding ties (synth_frame seed 41, 2 vehicles, its first and its later pose) the clips equal the one-clip stages
+    with the flag on AND with it off."""
+    pipe = env["pipe"]
+    first = pl.synth_frame(2, HW, DEV, seed=41)
+    first["vehicle_seeds"] = [11, 12]
+    g = np.random.default_rng(9)
+    later = dict(first)
+    later["masks"] = torch.roll(first["masks"], shifts=(5, -7), dims=(1, 2))
+    later["dst_sketch"] = torch.roll(first["dst_sketch"], shifts=(5, -7), dims=(1, 2))
+    later["dst_kp"] = [[np.int32(p + np.array([-7, 5]) + g.integers(-2, 3, p.shape)) for p in veh] for veh in first["dst_kp"]]
+    state = pipe.run_frame(first)["state"]
+    clips = [([later, first, later], state), ([first, later], state)]
+    host = [pipe._later_batch_stages(scs, st) for scs, st in clips]
+    pipe.device_homography = True
+    try:
+        got, _ = _assert_stages(pipe, clips, "device_homography")
+    finally:
+        pipe.device_homography = False
+    for k in ("warped", "geom", "icn_x", "vu_y"):
+        assert torch.equal(got[k], torch.cat([w[k] for w in host])), k
+
+
+def test_one_clip_eager_is_the_one_clip_driver_bit_for_bit(env):
+    """One clip, eager, pad off: the same inputs at the same batch size with the same per-row seeds - every key equal."""
+    pipe = env["pipe"]
+    for scs, st in env["clips"]:
+        got = pipe.run_later_clips_batched([(scs, st)])
+        want = pipe.run_later_frames_batched(scs, st)
+        _equal(got, [want])
+    assert not any(k[0] == "later_rows" for k in pipe._frame_plans)
+
+
+def test_several_clips_match_the_oracle(env):
+    """Clips A (2 vehicles x 2 frames) and B (1 vehicle x 3 frames) as ONE pass of 7 rows against oracle.frame_pass +
+    oracle.later_frame_pass per clip; B's frame 1 starts from its 'background', every other frame from its own image."""
+    pipe = env["pipe"]
+    calls = []
+    orig = pipe._later_nets
+    pipe._later_nets = lambda batch, seeds=None: (calls.append(int(batch["icn_x"].shape[0])), orig(batch, seeds))[1]
+    try:
+        got = pipe.run_later_clips_batched(env["clips"])
+    finally:
+        del pipe._later_nets
+    assert calls == [7]                                                           # the networks ran once, at 7 rows
+    _all_bars(env, got, "one pass")
+    assert not any(k[0] in ("later_rows", "later_batch") for k in pipe._frame_plans)          # the eager form records nothing
+    cover = env["cpus"][1][1]["masks"].max(0).astype(bool)
+    assert (got[1][1]["frame_icn"].cpu().numpy()[~cover] == 77).all()
+    assert not (got[1][0]["frame_icn"].cpu().numpy() == 77).all() and not (got[1][2]["frame_icn"].cpu().numpy()[~cover] == 77).all()
+
+
+def test_replay_equals_padded_eager_and_keeps_one_plan_per_padded_rows(env):
+    pipe, (A, B) = env["pipe"], env["clips"]
+    one = [A, B]                                                                  # 4 + 3 = 7 rows -> 8
+    two = [(B[0][:2], B[1]), A]                                                   # 2 + 4 = 6 rows -> 8
+    key = ("later_rows", 8, ops.PRECISION)
+    before = dict(pipe._frame_plans)
+    e1, e2 = pipe.run_later_clips_batched(one, pad=True), pipe.run_later_clips_batched(two, pad=True)
+    assert dict(pipe._frame_plans) == before and key not in before                # pad=True alone records nothing
+    _all_bars(env, e1, "padded")                                                  # the padded results meet the bars of the oracle test
+    assert [len(c) for c in e2] == [2, 2]
+    r1 = pipe.run_later_clips_batched(one, replay=True)
+    plan = pipe._frame_plans[key]
+    keep = [[{k: o[k].clone() for k in KEYS} for o in c] for c in r1]
+    r2 = pipe.run_later_clips_batched(two, replay=True)
+    r3 = pipe.run_later_clips_batched(one, replay=True)
+    assert pipe._frame_plans[key] is plan                                         # recorded once, replayed since - for other rows too
+    assert [k for k in pipe._frame_plans if k[0] == "later_rows"] == [key]
+    assert not any(k[0] == "later_batch" for k in pipe._frame_plans)
+    _equal(r1, e1), _equal(r3, e1), _equal(r2, e2)
+    _equal(r1, keep)                                                              # handed out as copies: later replays leave them
+
+
+def test_chunked_groups_meet_the_same_bars_in_clip_order(env):
+    pipe = env["pipe"]
+    assert pl.clip_batch_groups([2, 3], [2, 1], 4) == [(0, 1, False), (1, 2, False)]
+    calls = []
+    orig = pipe._run_later_clips
+    pipe._run_later_clips = lambda clips, replay=False, rows=None: (calls.append(len(clips)), orig(clips, replay, rows))[1]
+    try:
+        got = pipe.run_later_clips_batched(env["clips"], max_batch=4)
+    finally:
+        del pipe._run_later_clips
+    assert calls == [1, 1]
+    _all_bars(env, got, "max_batch 4")
+
+
+def test_range_guard_redoes_the_group_in_fp32(env):
+    """An appearance code outside the split-fp16 range in ONE clip of the group: the status word is raised once, and the results
+    of the whole group are those of an exact-fp32 run, bit for bit."""
+    pipe, (A, B) = env["pipe"], env["clips"]
+    hot = dict(B[1])
+    hot["appearance"] = [t.clone() for t in B[1]["appearance"]]
+    hot["appearance"][1][0, 0, 0, 0] = 6e4
+    clips = [A, (B[0], hot)]
+    with ops.precision("f32"):
+        f32 = pipe.run_later_clips_batched(clips, check=None)
+    h16 = pipe.run_later_clips_batched(env["clips"])
+    raised = []
+    orig = ops.range_exceeded
+    ops.range_exceeded = lambda *a, **k: (raised.append(orig(*a, **k)), raised[-1])[1]
+    try:
+        got = pipe.run_later_clips_batched(clips)
+    finally:
+        ops.range_exceeded = orig
+    assert raised == [True]                                                       # one status word, read once, for the whole group
+    _equal(got, f32)
+    assert any(not torch.equal(x["vunet_u8"], y["vunet_u8"]) for cx, cy in zip(got, h16) for x, y in zip(cx, cy))
+    assert not ops.range_exceeded(DEV) and not ops.range_exceeded(DEV, word=pipe.status_word())
+
+
+def test_edges_and_fallbacks(env):
+    pipe, (A, B) = env["pipe"], env["clips"]
+    assert pipe.run_later_clips_batched([]) == []
+    assert pipe.run_later_clips_batched([([], A[1])]) == [[]]
+    H, W = HW
+    e = lambda *sh: torch.empty(sh, dtype=torch.uint8, device=DEV)                # noqa: E731
+    none = {"masks": e(0, H, W), "dst_sketch": e(0, H, W, 3), "src_planes": e(0, 5, H, W, 3), "src_kp": [], "dst_kp": [],
+            "src_vis": np.zeros((0, 5), np.uint8), "dst_vis": np.zeros((0, 5), np.uint8)}
+    st0 = {"appearance": [t[:0] for t in A[1]["appearance"]], "central": A[1]["central"][:0], "shard": (0, 0, 0), "sharded": False}
+    frames = [B[0][0]["frame"], A[0][1]["frame"]]
+    empty = [dict(none, frame=frames[0]), dict(none, frame=frames[1], background=torch.full_like(frames[1], 9))]
+    got = pipe.run_later_clips_batched([A, ([], B[1]), (empty, st0), B])
+    assert [len(g) for g in got] == [2, 0, 2, 3]
+    _equal([got[0], got[3]], pipe.run_later_clips_batched([A, B]))                # the same 7 rows: the empty clips change nothing
+    for o, base in zip(got[2], (frames[0], torch.full_like(frames[1], 9))):       # V = 0 in the middle: the composite is its base
+        assert tuple(o["icn_u8"].shape) == (0, 256, 256, 3) and tuple(o["vunet_u8"].shape) == (0, 256, 256, 3) and tuple(o["geom"].shape) == (0, 8)
+        assert torch.equal(o["frame_icn"], base) and torch.equal(o["frame_vunet"], base)
+    only = pipe.run_later_clips_batched([(empty, st0)])                           # no row at all
+    assert torch.equal(only[0][1]["frame_icn"], torch.full_like(frames[1], 9)) and tuple(only[0][0]["geom"].shape) == (0, 8)
+    small = dict(A[0][1], frame=A[0][1]["frame"][:-8].contiguous())
+    with pytest.raises(ValueError, match="one size"):
+        pipe.run_later_clips_batched([([A[0][0], small], A[1]), B])
+    with pytest.raises(ValueError, match="vehicles"):
+        pipe.run_later_clips_batched([A, (A[0], B[1])])                           # 2 vehicles per scene, a state of 1
+    with pytest.raises(ValueError, match="src_planes"):
+        pipe.run_later_clips_batched([([A[0][0], dict(A[0][1], src_planes=A[0][1]["src_planes"].clone())], A[1]), B])
+    with pytest.raises(ValueError, match="vehicle_seeds"):
+        pipe.run_later_clips_batched([A, ([{k: v for k, v in sc.items() if k != "vehicle_seeds"} for sc in B[0]], B[1])])
+
+
+def test_run_clips_batched_is_first_frames_then_tails(env):
+    pipe = env["pipe"]
+    clips = list(zip(env["firsts"], env["later"]))
+    got = pipe.run_clips_batched(clips)
+    firsts = pipe.run_frames_batched(env["firsts"])
+    tails = pipe.run_later_clips_batched([(later, f["state"]) for later, f in zip(env["later"], firsts)])
+    assert [len(g) for g in got] == [3, 4]
+    for g, f, t in zip(got, firsts, tails):
+        for k in ("kp_idx", "icn_u8", "vunet_u8", "frame_icn", "frame_vunet"):
+            assert torch.equal(g[0][k], f[k]), k
+        assert "state" in g[0]
+        _equal([g[1:]], [t])
+
+
+def test_a_geometry_mode_state_falls_back_clip_by_clip(env):
+    from future_urban_scene_generation_amd import render as R
+    from test_gpu_render import _geometry_setup
+    pipe, _, scene = _geometry_setup(V=2)
+    out = pipe.run_frame(scene)
+    steps = R.trajectory_steps(np.c_[np.arange(6.0) * 0.8, 0.05 * np.arange(6.0) ** 2])
+    later = [{"frame": scene["frame"], "steps": [steps[n]] * 2, "vehicle_seeds": [900 + 10 * n + v for v in range(2)]} for n in (0, 1)]
+    want = list(pipe.run_later_frames(later, out["state"]))
+    got = pipe.run_later_clips_batched([(later, out["state"]), (later[:1], out["state"])])
+    assert [len(g) for g in got] == [2, 1] and not any(k[0] in ("later_rows", "later_batch") for k in pipe._frame_plans)
+    for a, b in zip(got[0] + got[1], want + want[:1]):
+        assert a["skipped"] == b["skipped"]
+        for k in KEYS:
+            assert torch.equal(a[k], b[k]), k
+    with pytest.raises(ValueError, match="mixes"):
+        pipe.run_later_clips_batched([(later, out["state"]), env["clips"][0]])
+
+
+# ------------------------------------------------------------------------------------------------ inpainting
+def test_inpainted_clips_match_the_reference(inpaint_env):  # noqa: F811
+    """Two clips of the same two vehicles, one frame each, whose scenes carry 'inpaint' in two different forms (detector masks in
+    box coordinates; the four given tensors): ONE pass of 4 rows under the bars of
+    tests/test_gpu_later_batch.py::test_inpainted_batch_matches_the_reference, EdgeConnect's inputs of each scene built from ITS
+    image; a partial 'inpaint' is refused before any launch."""
+    pipe, st, frames = inpaint_env["pipe"], inpaint_env["f0"]["state"], inpaint_env["frames"]
+    four = ops.inpaint_inputs_boxed(frames[1]["later"]["frame"], frames[1]["box_masks"]["inpaint"]["box_masks"], frames[1]["boxes"])
+    clips = [([frames[0]["box_masks"]], st), ([dict(frames[1]["later"], inpaint=dict(four, boxes=frames[1]["boxes"]))], st)]
+    calls = []
+    orig = pipe._later_nets
+    pipe._later_nets = lambda batch, seeds=None: (calls.append((int(batch["icn_x"].shape[0]), "ec_img" in batch)), orig(batch, seeds))[1]
+    try:
+        got = pipe.run_later_clips_batched(clips)
+    finally:
+        del pipe._later_nets
+    assert calls == [(4, True)] and [len(g) for g in got] == [1, 1]
+    for c, fr in enumerate(frames):
+        assert set(got[c][0]) == set(KEYS) | {"inpaint_u8"}
+        _inpaint_bars(got[c][0], fr, f"clip {c}")
+    rep = [pipe.run_later_clips_batched(clips, replay=True) for _ in range(2)]    # recorded, then replayed into the plan's inputs
+    assert ("later_rows", 4, ops.PRECISION, "inpaint") in pipe._frame_plans
+    for r in rep:
+        _equal(r, got, KEYS + ("inpaint_u8",))
+    launches = []
+    orig = pu.warp_planes_clips_batch
+    pu.warp_planes_clips_batch = lambda *a, **k: (launches.append(1), orig(*a, **k))[1]
+    try:
+        with pytest.raises(ValueError, match="inpaint"):
+            pipe.run_later_clips_batched([clips[0], ([frames[1]["later"]], st)])
+    finally:
+        pu.warp_planes_clips_batch = orig
+    assert not launches
+    plain = pipe.run_later_clips_batched([([fr["later"]], st) for fr in frames])  # no scene carries the key: the plain pass
+    assert all("inpaint_u8" not in g[0] for g in plain)
