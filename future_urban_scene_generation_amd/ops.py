@@ -413,7 +413,7 @@ def _conv_desc(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = No
         assert out is not None and plan.nphase == 1 and plan.pad_mode == L.PAD_ZERO and q_window is None
         qh, qw = int(q_size[0]), int(q_size[1])
     if q_window is not None:
-        assert out is not None and plan.nphase == 1 and store == L.STORE_NORMAL and not want_stats
+        assert out is not None and plan.nphase == 1 and store == L.STORE_NORMAL
         assert 0 <= q_window[0] and q_window[0] + q_window[2] <= qh and 0 <= q_window[1] and q_window[1] + q_window[3] <= qw
     if plan.nphase == 4:
         oc, oh, ow = plan.cout, 2 * qh, 2 * qw
@@ -526,11 +526,11 @@ def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *,
             d.splitk_counters_len = N_COUNTERS
     stats = None
     if want_stats:
-        # fused norm statistics when the launch qualifies (include/fusg.h, stats_out); else the caller falls
-        # back to the separate streaming pass
+        # fused norm statistics when the launch qualifies (include/fusg.h, stats_out: no tile list, no window origin
+        # either); else the caller falls back to the separate streaming pass
         if (d.ksplit <= 1 and plan.nphase == 1 and store == L.STORE_NORMAL and act == L.ACT_NONE and res0 is None
                 and res1 is None and (qh * qw) % 32 == 0 and plan.cout % 4 == 0 and out_c_off % 4 == 0 and is_nhwc(out)
-                and out.stride(3) % 4 == 0 and not _env_set("FUSG_NO_VEC_EPI")):
+                and out.stride(3) % 4 == 0 and not _env_set("FUSG_NO_VEC_EPI") and q_window is None and tiles is None):
             stats = torch.empty((b, qh * qw // 32, plan.cout, 2), device=x0.device, dtype=torch.float32)
             d.stats_out = stats.data_ptr()
     if stats_into is not None:
