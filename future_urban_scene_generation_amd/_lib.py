@@ -93,6 +93,9 @@ _SIGS = {
     "fusg_conv2d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "fusg_conv2d_plan": (C.c_int64, [C.POINTER(ConvDesc)]),
     "fusg_conv2d_route": (C.c_int, [C.POINTER(ConvDesc)]),
+    "fusg_set_route_batch": (C.c_int, [C.c_int32]),
+    "fusg_route_batch": (C.c_int32, []),
+    "fusg_conv2d_route_order": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32 * 4)]),
     "fusg_hg_bottleneck": (C.c_int, [C.POINTER(BneckDesc), C.c_void_p]),
     "fusg_vunet_respair": (C.c_int, [C.POINTER(RespairDesc), C.c_void_p]),
     "fusg_conv2d_entry_nin": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p]),
@@ -187,6 +190,9 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS.keys())
 
+# FUSG_ROUTE_BATCH=n (read once, here): the routing batch the library starts with (fusg_set_route_batch; ops.set_route_batch)
+ROUTE_BATCH_ENV = int(os.environ.get("FUSG_ROUTE_BATCH", "0") or 0)
+
 _lib = None
 
 
@@ -215,6 +221,8 @@ def lib():
                 or h.fusg_sizeof_bneck_desc() != C.sizeof(BneckDesc)
                 or h.fusg_sizeof_respair_desc() != C.sizeof(RespairDesc)):
             raise FusgUnavailable("libfusg.so struct layout differs from the ctypes mirror (stale build?)")
+        if ROUTE_BATCH_ENV and h.fusg_set_route_batch(ROUTE_BATCH_ENV) < 0:
+            raise FusgError(f"FUSG_ROUTE_BATCH={ROUTE_BATCH_ENV}: {h.fusg_last_error().decode()}")
         _lib = h
     return _lib
 

@@ -1,6 +1,7 @@
 // libfusg: error reporting, version, and the opt-in per-kernel HIP-event profiler.
 #include <stdarg.h>
 #include <stdlib.h>
+#include <atomic>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -47,6 +48,14 @@ const EnvSwitches& env_switches() {
     }();
     return sw;
 }
+
+// ---- routing batch: process-wide, overridden per thread while a recorded launch is re-issued ----
+static std::atomic<int32_t> g_route_batch{0};
+static thread_local int32_t g_route_replay = -1;           // >= 0: the value a recorded launch was recorded under
+
+int32_t route_batch_now() { return g_route_replay >= 0 ? g_route_replay : g_route_batch.load(std::memory_order_relaxed); }
+RouteBatchScope::RouteBatchScope(int32_t r) : prev(g_route_replay) { g_route_replay = r; }
+RouteBatchScope::~RouteBatchScope() { g_route_replay = prev; }
 
 // ---- profiler: event pairs recorded on the launch stream, resolved lazily in fusg_prof_read ----
 struct ProfKind {
@@ -107,6 +116,12 @@ extern "C" const char* fusg_arch(void) { return "gfx950"; }
 extern "C" int fusg_sizeof_tensor(void) { return (int)sizeof(fusg_tensor); }
 extern "C" int fusg_sizeof_conv_desc(void) { return (int)sizeof(fusg_conv_desc); }
 extern "C" int fusg_sizeof_bneck_desc(void) { return (int)sizeof(fusg_bneck_desc); }
+
+extern "C" int fusg_set_route_batch(int32_t n) {
+    FUSG_CHECK(n >= 0 && n <= (1 << 20), "set_route_batch: %d is outside 0 (off) .. 2^20", (int)n);
+    return (int)g_route_batch.exchange(n, std::memory_order_relaxed);
+}
+extern "C" int32_t fusg_route_batch(void) { return g_route_batch.load(std::memory_order_relaxed); }
 
 extern "C" void fusg_prof_enable(int on) { g_prof_on = on != 0; }
 

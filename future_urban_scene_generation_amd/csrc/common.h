@@ -61,6 +61,20 @@ hipError_t ensure_dyn_lds(const void* fn, int bytes);
 struct EnvSwitches { bool no_vec_epi, no_halo, no_touch, no_pointwise, no_ksplit; long halo_minwg; int halo_bn, small_maxhw; };
 const EnvSwitches& env_switches();
 
+// ---- routing batch (fusg_set_route_batch, api.hip) ---------------------------------------------------------------
+// route_n(n): the image count a routing DECISION sees for a launch of n images - the routing batch when one is set, else n
+// itself.  Sizes, grids and bounds never go through it.  While a recorded launch is re-issued the value is the one that was
+// in force when it was recorded (RouteBatchScope, plan_dispatch below), whatever the process-wide value is by then.
+int32_t route_batch_now();
+inline long route_n(long n) { const int32_t r = route_batch_now(); return r > 0 ? (long)r : n; }
+struct RouteBatchScope {
+    int32_t prev;
+    explicit RouteBatchScope(int32_t r);
+    ~RouteBatchScope();
+    RouteBatchScope(const RouteBatchScope&) = delete;
+    RouteBatchScope& operator=(const RouteBatchScope&) = delete;
+};
+
 // ---- recorded passes (plan.hip) ----------------------------------------------------------------------------------
 // While a fusg_plan is recording on this thread, every launching entry point appends a closure of itself - its
 // descriptors copied by value, its stream - to the plan before executing; fusg_plan_run replays the closures in order.
@@ -100,7 +114,9 @@ template <class... A>
 int plan_dispatch(int (*impl)(A..., void*), void* stream, A... a) {
     if (plan_recording()) {
         auto saved = std::make_shared<std::tuple<SavedArg<A>...>>(SavedArg<A>(a)...);
-        plan_append((hipStream_t)stream, [impl, saved](hipStream_t s) {
+        const int32_t rb = route_batch_now();              // a replay routes as the recording did
+        plan_append((hipStream_t)stream, [impl, saved, rb](hipStream_t s) {
+            RouteBatchScope scope(rb);
             return std::apply([&](const SavedArg<A>&... sv) { return impl(sv.get()..., (void*)s); }, *saved);
         });
     }

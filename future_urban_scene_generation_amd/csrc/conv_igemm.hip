@@ -218,8 +218,11 @@ static bool small_cfg(const fusg_conv_desc* d, int precision, SmallCfg* out) {
 
 // Tile, K split and workspace bytes.  Reads only shapes, so it also serves fusg_conv2d_plan on a bare descriptor.
 // `small` (may be NULL) receives the small kernel's configuration; small->ksplit == 0: the launch does not take it.
+// The tile and the K split are CHOSEN for route_n(n) images (the routing batch when one is set: common.h) and the workspace is
+// SIZED for the n images of the launch.
 static int64_t plan_impl(fusg_conv_desc* d, SmallCfg* small) {
     const long M = (long)d->src0.n * d->qh * d->qw;
+    const long Mr = route_n((long)d->src0.n) * d->qh * d->qw;      // what the choices below see
     const int nphase = d->nphase > 0 ? d->nphase : 1;
     SmallCfg sc;
     if (small_cfg(d, d->precision == FUSG_PREC_BF16 ? FUSG_PREC_F16X3 : d->precision, &sc)) {
@@ -233,8 +236,8 @@ static int64_t plan_impl(fusg_conv_desc* d, SmallCfg* small) {
         int bn = d->cout_pad >= 128 && d->cout_pad % 128 == 0 ? 128 : (d->cout_pad % 64 == 0 ? 64 : 32);
         int bm = 128;
         // small problems: prefer more, smaller tiles
-        long tiles = ((M + 127) / 128) * (d->cout_pad / bn) * nphase;
-        if (tiles < 256 && bn == 128) { bn = 64; tiles = ((M + 127) / 128) * (d->cout_pad / bn) * nphase; }
+        long tiles = ((Mr + 127) / 128) * (d->cout_pad / bn) * nphase;
+        if (tiles < 256 && bn == 128) { bn = 64; tiles = ((Mr + 127) / 128) * (d->cout_pad / bn) * nphase; }
         if (tiles < 256 && bn == 64) { bm = 64; }
         d->tile = bm == 128 ? (bn == 128 ? FUSG_TILE_128x128 : bn == 64 ? FUSG_TILE_128x64 : FUSG_TILE_128x32)
                             : FUSG_TILE_64x64;
@@ -245,7 +248,7 @@ static int64_t plan_impl(fusg_conv_desc* d, SmallCfg* small) {
             d->tile = bn == 128 ? FUSG_TILE_64x128 : FUSG_TILE_64x64;
     }
     const TileCfg tc = kTiles[d->tile];
-    const long tiles = ((M + tc.bm - 1) / tc.bm) * (d->cout_pad / tc.bn) * nphase;
+    const long tiles = ((Mr + tc.bm - 1) / tc.bm) * (d->cout_pad / tc.bn) * nphase;
     const int nk = d->k_pad / BK;
     if (d->ksplit <= 0) {
         int ks = 1;
@@ -492,7 +495,8 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
         // 130 -> 186 us, 64 -> 32 3x3 311 -> 351 us), conv time of the pass 23.9 -> 24.5 ms; round 4's bf16 128-column tile on a
         // 16 x 16 patch: 1.4x - 3x slower, profiles/r04_ab_experiments.txt.  Dropped.)
         if (halo_fits(r->HH, r->HW)) {
-            const long mt = (long)x0.n * (d->tile_list ? d->tile_count : tiles_per_img);
+            // (row tiles as the two choices below count them: of the routing batch when one is set)
+            const long mt = route_n((long)x0.n) * (d->tile_list ? d->tile_count : tiles_per_img);
             // pointwise layers are bound by their output stores, not by operand staging: the 64-column tile (a quarter of
             // the epilogue LDS, more resident workgroups) is 6-24 % faster there (hourglass 1x1s); k x k layers keep 128.
             // Small grids: narrower column tiles until the launch has enough workgroups to fill the chip.
@@ -642,6 +646,22 @@ extern "C" int fusg_conv2d_route(const fusg_conv_desc* din) {
     ConvRoute r;
     const int rc = route_conv(&d, &r);
     return rc != FUSG_OK ? rc : r.family;
+}
+
+extern "C" int fusg_conv2d_route_order(const fusg_conv_desc* din, int32_t out[4]) {
+    FUSG_CHECK(din != nullptr && out != nullptr, "conv2d_route_order: null argument");
+    fusg_conv_desc d = *din;
+    ConvRoute r;
+    if (const int rc = route_conv(&d, &r); rc != FUSG_OK) return rc;
+    const bool generic = r.family == FUSG_CONV_GENERIC_F32 || r.family == FUSG_CONV_GENERIC_F16X3;
+    const bool halo = r.family == FUSG_CONV_HALO || r.family == FUSG_CONV_HALO_S2D || r.family == FUSG_CONV_HALO_BF16 ||
+                      r.family == FUSG_CONV_HALO_F32;
+    const bool tapunit = r.family == FUSG_CONV_TAPUNIT || r.family == FUSG_CONV_TAPUNIT_F32 || r.family == FUSG_CONV_TAPUNIT_BF16;
+    out[0] = r.family;
+    out[1] = generic ? d.tile : (halo || tapunit ? r.bn : 0);
+    out[2] = r.family == FUSG_CONV_SMALL ? r.sc.ksplit : (generic ? d.ksplit : 1);
+    out[3] = halo && r.ksw ? 1 : 0;
+    return FUSG_OK;
 }
 
 // `en`: source 0 is not read but computed by the entry NiN (fusg_conv2d_entry_nin below; the launch is a halo launch)

@@ -478,7 +478,8 @@ static int respair_impl(const fusg_respair_desc* d, void* stream) {
     FUSG_CHECK(wgs < (1L << 31), "vunet_respair: grid");
     // the order of the 3x3 launches this replaces: route_conv gives a 32-column 3x3 halo launch of at most 1024 workgroups the K
     // split over the waves (conv_igemm.hip, ConvRoute::ksw)
-    const bool split = d->tap_order == 0 ? (!env_switches().no_ksplit && wgs <= 1024) : d->tap_order == 2;
+    // (tap_order 0 counts the patches of the routing batch when one is set, as route_conv does: common.h, route_n)
+    const bool split = d->tap_order == 0 ? (!env_switches().no_ksplit && route_n((long)k.B) * k.tiles_x * k.tiles_y <= 1024) : d->tap_order == 2;
     const void* fn = d->entry ? (split ? (const void*)vunet_respair_h3<32, true, true> : (const void*)vunet_respair_h3<32, true, false>)
                               : (split ? (const void*)vunet_respair_h3<32, false, true> : (const void*)vunet_respair_h3<32, false, false>);
     const size_t lds = respair_lds(d->entry != 0);

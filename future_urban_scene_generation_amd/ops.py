@@ -74,6 +74,48 @@ class precision:
         return False
 
 
+# ---- routing batch: a row's bits independent of its batch ---------------------------------------------------
+# Which kernel family a layer runs on, its tile and its K split - the order of its sums - depend on how many images share
+# the launch.  With a routing batch R > 0 every such decision, in the library (include/fusg.h, fusg_set_route_batch) and
+# here (`bottleneck_ok`, `_nchunk`, the memoised route questions), is made as if the launch held R images; sizes, grids and
+# bounds keep describing the real launch.  0 (the default) decides by the real batch.  Process-wide like PRECISION;
+# FUSG_ROUTE_BATCH=n in the environment sets the initial value (read once at import, applied when the library loads).
+ROUTE_BATCH = L.ROUTE_BATCH_ENV
+
+
+def set_route_batch(n: int) -> int:
+    """Set the routing batch (0 = off, at most 2**20); returns the previous value.  Not to be changed while another thread
+    issues launches."""
+    global ROUTE_BATCH
+    n = int(n)
+    prev = L.lib().fusg_set_route_batch(n)
+    if prev < 0:
+        raise ValueError(f"route batch {n}: {L.lib().fusg_last_error().decode()}")
+    ROUTE_BATCH = n
+    return int(prev)
+
+
+class route_batch:
+    """`with ops.route_batch(8):` - temporary routing batch (None leaves the current one in force)."""
+
+    def __init__(self, n: Optional[int]):
+        self.n = n
+
+    def __enter__(self):
+        self.prev = None if self.n is None else set_route_batch(self.n)
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev is not None:
+            set_route_batch(self.prev)
+        return False
+
+
+def _route_n(b: int) -> int:
+    """The image count a routing decision sees for a launch of b images."""
+    return ROUTE_BATCH if ROUTE_BATCH > 0 else int(b)
+
+
 # ---- range guard of the split-fp16 contraction --------------------------------------------------------------
 # An f16x3 launch that stages an operand with |x| >= 2^15 (or a non-finite one) cannot represent it and raises a
 # device-side status word instead of clamping (include/fusg.h, fusg_precision).  The word is caller-owned: one int32
@@ -561,8 +603,9 @@ def bottleneck_ok(p: dict, x: torch.Tensor, precision: Optional[str] = None) -> 
     # fused block, whose grid there is one workgroup per image walking 48 K-steps in series.  Measured (profiles/
     # r04_ab_experiments.txt [r04j], recorded-plan replay): with at most 8 images the three launches win - B = 8 1266 -> 1305
     # crops/s, B = 1 2.10 -> 2.03 ms per pass with levels < 32 unfused - from B = 16 up the fused block wins (B = 32: conv 23.5 ->
-    # 23.8 ms).  FUSG_BNECK_MINHW=n overrides (0 = always fused).
-    minhw = BNECK_MINHW if BNECK_MINHW is not None else (32 if x.shape[0] <= 8 and prec == "f16x3" else 0)
+    # 23.8 ms).  FUSG_BNECK_MINHW=n overrides (0 = always fused).  (The fused block and the three launches sum in different
+    # orders: the batch that decides is the routing batch when one is set.)
+    minhw = BNECK_MINHW if BNECK_MINHW is not None else (32 if _route_n(x.shape[0]) <= 8 and prec == "f16x3" else 0)
     return max(x.shape[2], x.shape[3]) >= minhw or _env_set("FUSG_NO_SMALL")
 
 
@@ -635,7 +678,7 @@ def respair_ok(res_a: ConvPlan, res_b: ConvPlan, nin_b: ConvPlan, nin_c: ConvPla
     # The fused launch sums as the HALO kernel does.  The router is asked what each launch it replaces would run on: small
     # grids get a generic split-K launch (another order of summation), tiny images the small-image kernel - those stay unfused.
     # The answer depends on the shapes and on the switches the router reads per call: asked once per such key.
-    key = (id(res_b), id(nin_b), id(nin_c), id(nin_in), b, c, h, w, x.stride(3), str(x.device),
+    key = (id(res_b), id(nin_b), id(nin_c), id(nin_in), b, c, h, w, x.stride(3), str(x.device), ROUTE_BATCH,
            _env_set("FUSG_NO_SMALL"), _env_set("FUSG_NO_POINTWISE"), _env_set("FUSG_SMALL_KSPLIT"))
     memo = res_a.__dict__.setdefault("_respair_routes", {})
     if key not in memo:
@@ -712,7 +755,7 @@ def entry_nin_form(nin: ConvPlan, res: ConvPlan, u: torch.Tensor, precision: Opt
             and res.nphase == 1 and res.c1k == 0 and res.c0k == nin.cout and res.cout == nin.cout and u.shape[1] == nin.c_split[0]):
         return 0
     b, c, h, w = u.shape
-    key = (id(nin), b, c, h, w, u.stride(3), str(u.device), int(ksplit),
+    key = (id(nin), b, c, h, w, u.stride(3), str(u.device), int(ksplit), ROUTE_BATCH,
            _env_set("FUSG_NO_SMALL"), _env_set("FUSG_NO_POINTWISE"), _env_set("FUSG_SMALL_KSPLIT"))
     memo = res.__dict__.setdefault("_entry_nin_routes", {})
     if key not in memo:
@@ -851,8 +894,9 @@ def conv_rowsplit(plan: ConvPlan, x0: torch.Tensor, *, pre_op: int = L.PRE_NONE,
 # normalisation
 # ---------------------------------------------------------------------------------------------
 def _nchunk(b: int, c: int, hw: int) -> int:
+    """Partial sums per image of the streamed statistics (their number fixes the order of the sums: by the routing batch)."""
     zg = (c // 4 + 63) // 64
-    want = max(1, 1024 // max(1, b * zg))
+    want = max(1, 1024 // max(1, _route_n(b) * zg))
     return int(max(1, min(want, max(1, hw // 64), 4096)))
 
 

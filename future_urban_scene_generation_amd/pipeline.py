@@ -465,7 +465,7 @@ class VehiclePipeline:
 
     def __init__(self, device, inpaint: bool = False, state_dicts: Optional[Dict[str, dict]] = None, seed: int = 0,
                  broadcast_src: Optional[int] = None, group=None, cad: bool = False, cad_bank=None,
-                 device_homography: bool = False, device_pose: bool = False):
+                 device_homography: bool = False, device_pose: bool = False, *, route_batch: Optional[int] = None):
         """state_dicts: checkpoints (the reference's keys) per network; a missing network gets the synthetic weights of
         `seed`; the VUnet is built in the configuration its checkpoint's keys show (`vunet.models.vunet_args_of`).  broadcast_src: with an initialised process group, only that rank needs to hold `state_dicts` (a real
         checkpoint read from disk on rank 0): they are distributed with `broadcast_state_dicts` first (north_star: RCCL
@@ -482,7 +482,20 @@ class VehiclePipeline:
         polygons, plane corner points - on the device (`render.vehicle_geometry_device`, fusg_pose_geometry) instead of in numpy
         between three read-backs (`render.vehicle_geometry`, the default): a frame's front stage then issues every launch through
         the plane cut-outs around ONE blocking device-to-host copy of the small results.  With device_homography as well the
-        corner points reach the homography fit as device tensors."""
+        corner points reach the homography fit as device tensors.
+        route_batch (keyword only): the routing batch (`ops.set_route_batch`) in force around every pass this pipeline issues - eager passes,
+        recordings and their replays, the range guard's fp32 redo; None: whatever the process has set (off by default).  Every
+        routing decision is then made as if the launch held `route_batch` images.  Contract: with route_batch set, one precision
+        and `vehicle_seeds` given, the network outputs of a row ('kp_idx', 'icn_u8', 'vunet_u8', 'inpaint_u8', the appearance
+        codes) are bit-identical whatever the batch size (1 ... 64), the row's position in the batch, the zero padding rows of
+        a padded replay and the driver (`run`, `run_frame`, `run_frames_batched`, `run_later_frames_batched`,
+        `run_later_clips_batched`).  One exception: a raised range status redoes the WHOLE pass in exact fp32, so a row's bits
+        still depend on whether a neighbour overflowed.  Without `vehicle_seeds` the VUnet's noise stays batch-shaped as in the
+        reference.  The recorded plans are kept per routing batch: a replay never mixes routings.  Pick a value near the typical
+        batch of a pass (the cost of a routing batch far from the real one)."""
+        if route_batch is not None and not 0 <= int(route_batch) <= (1 << 20):
+            raise ValueError(f"route_batch {route_batch} is outside 0 (off) .. 2**20")
+        self.route_batch = None if route_batch is None else int(route_batch)
         from .edgeconnect.models import EdgeModel, InpaintingModel
         from .stacked_hourglass.models import HourglassNet
         from .synth import synth_state_dict
@@ -654,20 +667,26 @@ class VehiclePipeline:
             self._status = ops.new_status_word(self.device)
         return self._status
 
+    def _routed(self):
+        """The context every pass of this pipeline is issued in: its routing batch (`route_batch`; None: the process's)."""
+        from . import ops
+        return ops.route_batch(self.route_batch)
+
     def _guarded(self, fn, args, check: str, rng_state):
         from . import ops
-        if not ops.range_guarded() or check is None:
-            return fn(*args)
-        word = self.status_word()
-        with ops.defer_range_check(), ops.status_scope(word):
-            out = fn(*args)
-        if check == "async":
-            return out
-        with torch.cuda.device(self.device):
-            hit = ops.range_exceeded(self.device, word=word)
-        if not hit:
-            return out
-        return _redo_f32(lambda: fn(*args), rng_state)
+        with self._routed():
+            if not ops.range_guarded() or check is None:
+                return fn(*args)
+            word = self.status_word()
+            with ops.defer_range_check(), ops.status_scope(word):
+                out = fn(*args)
+            if check == "async":
+                return out
+            with torch.cuda.device(self.device):
+                hit = ops.range_exceeded(self.device, word=word)
+            if not hit:
+                return out
+            return _redo_f32(lambda: fn(*args), rng_state)
 
     def finish(self) -> bool:
         """Synchronise the device and report (and clear) the range status of the passes issued with check="async":
@@ -1251,13 +1270,14 @@ class VehiclePipeline:
         pin = None
         if ops.range_guarded():
             word = (word or self.status_word)()
-            with ops.defer_range_check(), ops.status_scope(word):
+            with self._routed(), ops.defer_range_check(), ops.status_scope(word):
                 out = fn()
             pin = self._pins.pop() if self._pins else torch.zeros(1, dtype=torch.int32, pin_memory=True)
             pin.copy_(word[:1], non_blocking=True)
             word.zero_()
         else:
-            out = fn()
+            with self._routed():
+                out = fn()
         ev = torch.cuda.Event()
         ev.record()
         return out, (pin, ev)
@@ -1403,7 +1423,8 @@ class VehiclePipeline:
         local = t["local"]
         if self._status_raised(t["ticket"]):                      # (waits for this frame's launches only; the next frame's are already queued)
             # rare: this rank's shard again, in exact fp32 (before any collective)
-            local = _redo_f32(lambda: self._frame_local(t["sub"], False), t["rng"], restore=True)
+            with self._routed():
+                local = _redo_f32(lambda: self._frame_local(t["sub"], False), t["rng"], restore=True)
             torch.cuda.synchronize(self.device)
         main = torch.cuda.current_stream(self.device)
         if self._comm_stream is None:
@@ -1461,9 +1482,16 @@ class VehiclePipeline:
         out["state"] = state
         return out
 
+    def _plan_key(self, key):
+        """`key` as `_frame_plans` holds it: with a routing batch in force it gains ("route_batch", R), so a recording made
+        under one routing is never replayed under another; without one it is `key` itself."""
+        from . import ops
+        r = ops.ROUTE_BATCH if self.route_batch is None else self.route_batch
+        return tuple(key) + (("route_batch", r),) if r else key
+
     def _plan(self, key) -> Optional["CompiledPass"]:
-        """The recorded pass kept under `key`, unless a network's packed weights have changed since it was recorded."""
-        cp = self._frame_plans.get(key)
+        """The recorded pass kept under `key` (`_plan_key`), unless a network's packed weights have changed since it was recorded."""
+        cp = self._frame_plans.get(self._plan_key(key))
         return cp if cp is not None and [n.generation for n in self._nets] == cp.generations else None
 
     def _replay(self, key, nets_in, seeds, fn=None, clone=None) -> Dict:
@@ -1473,6 +1501,7 @@ class VehiclePipeline:
         of them) are handed out as copies."""
         cps = self._frame_plans
         cp = self._plan(key)
+        key = self._plan_key(key)
         if cp is None:
             cps.pop(key, None)
             while len(cps) >= FRAME_PLANS:
@@ -2897,6 +2926,16 @@ class CompiledPass:
         self.fn = fn if fn is not None else pipe._run                          # the pass being recorded
         self.precision = ops.PRECISION                                        # recorded into every conv descriptor
         self.keys = sorted(batch.keys())
+        with pipe._routed():
+            # the routing batch every recorded launch carries (fusg.h: a replay routes as the recording did); the fp32 redo
+            # of `run`, which is eager, is issued under it too
+            self.route_batch = ops.ROUTE_BATCH
+            self._record(batch, vehicle_seeds)
+
+    def _record(self, batch, vehicle_seeds):
+        from . import _lib as L
+        from . import ops
+        pipe = self.pipe
         with torch.cuda.device(self.device):
             pipe._guarded(self.fn, (batch, vehicle_seeds), None, None)        # warm-up: weight upload, workspaces, streams
             torch.cuda.synchronize(self.device)
@@ -2994,7 +3033,8 @@ class CompiledPass:
                 return out
             if not ops.range_exceeded(self.device, word=self.pipe.status_word()):
                 return out
-            return _redo_f32(lambda: self.fn(batch, vehicle_seeds), rng)
+            with ops.route_batch(self.route_batch):
+                return _redo_f32(lambda: self.fn(batch, vehicle_seeds), rng)
 
 
 def synth_clip(vehicles: int, frames: int, res: int, device, seed: int = 0) -> Dict[str, torch.Tensor]:

@@ -234,6 +234,30 @@ int64_t fusg_conv2d_plan(fusg_conv_desc* d);
 int  fusg_conv2d_route(const fusg_conv_desc* d);
 
 /*
+ * Routing batch (batch-invariant routing; added without a version step: the entry points are new, nothing existing changed
+ * and 0, the default, is the behaviour before them launch for launch).
+ * Which kernel family a convolution runs on, its tile and its K split - hence the order of its sums, hence its bits - depend
+ * on how many images share the launch.  With a routing batch R > 0 every such CHOICE is made as if the launch held R images,
+ * whatever it holds: the tile and ksplit of fusg_conv2d_plan, the column tile and the K split over the waves of the halo
+ * kernel (fusg_conv2d, fusg_conv2d_route, fusg_conv2d_entry_nin[_route]), and tap_order 0 of fusg_vunet_respair.  Grids,
+ * workspace bytes (the chosen ksplit times the REAL M) and every bounds check keep describing the real launch.  The arithmetic
+ * applied to one image then does not depend on its neighbours; R equal to the real batch is the default behaviour at that batch.
+ * fusg_hg_bottleneck and the small-image kernel sum per image whatever the grid and read no routing batch.
+ * The value is process-wide and read whenever a launch is planned or routed; a launch recorded into a fusg_plan is re-issued
+ * under the value it was recorded with.  Do not change it while another thread issues or plans launches.
+ * fusg_set_route_batch: n = 0 turns the mode off, 1 .. 2^20 sets it and the PREVIOUS value (>= 0) is returned; a negative or
+ * larger n changes nothing and returns FUSG_ERR_INVALID with a message.  fusg_route_batch: the current value.
+ */
+int     fusg_set_route_batch(int32_t n);
+int32_t fusg_route_batch(void);
+/* Dry run like fusg_conv2d_route (no launch, no device): what fixes the summation order of the launch fusg_conv2d would make
+ * of this descriptor - out = {family (FUSG_CONV_*), tile, ksplit, ksw}.  tile: the FUSG_TILE_* of the generic gathers, the
+ * column-tile width (128 / 64 / 32) of the halo and tap-unit kernels, 0 for the others; ksplit: K ranges over workgroups
+ * (generic gathers and the small-image kernel; 1 elsewhere); ksw: 1 when the halo kernel splits K over its waves.
+ * Returns FUSG_OK or the negative FUSG_ERR_* fusg_conv2d would return. */
+int  fusg_conv2d_route_order(const fusg_conv_desc* d, int32_t out[4]);
+
+/*
  * One pre-activation Bottleneck of the stacked hourglass in ONE launch (split-fp16 arithmetic, FUSG_PREC_F16X3):
  *   out = res + conv3_1x1( relu(bn3( conv2_3x3( relu(bn2( conv1_1x1( relu(bn1(x)) ))) ))) )
  * (stacked_hourglass/models.py:22-42; bn2 / bn3 are folded into conv1 / conv2 at pack time, bn1 is the per-channel
