@@ -159,10 +159,66 @@ def _box_masks_of(box_masks, keep):
     return (buf, np.asarray(offs, dtype=np.int64)[np.asarray(idx, dtype=np.int64)])
 
 
-# ---- `run_later_frames_batched`: the frame-major bookkeeping of a pass over F frames of V vehicles (pure Python)
+# ---- the batched frame drivers' bookkeeping (pure Python).  What every row layout shares stands here once - the bounds of a
+# group, the padded row count, "every scene carries a key or none does" - and the three layouts below (frame-major rows of one
+# clip, scene-major rows of several first frames, clip-major rows of several clip tails) supply their offsets and their labels.
 LATER_MAX_BATCH = 64     # rows per batched later pass: the largest batch the frame drivers run anyway (a frame of 64 vehicles)
+FRAME_BATCH_MAX_FRAMES = 64   # scenes per group: what one launch of the frame-indexed glue kernels takes (fusg.h FUSG_MAX_FRAMES)
 
 
+def _group_bounds(max_batch: Optional[int], max_frames: Optional[int] = None) -> Tuple[int, Optional[int]]:
+    """(max_batch, max_frames) of a `*_groups` function as ints; max_batch None: LATER_MAX_BATCH.  ValueError below 1."""
+    if max_batch is None:
+        max_batch = LATER_MAX_BATCH
+    if int(max_batch) < 1:
+        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
+    if max_frames is not None and int(max_frames) < 1:
+        raise ValueError(f"max_frames must be at least 1, got {max_frames}")
+    return int(max_batch), None if max_frames is None else int(max_frames)
+
+
+def _pad_defaults(replay: bool, max_batch: Optional[int], pad: Optional[bool]) -> Tuple[int, bool]:
+    """(max_batch, pad) of a padded driver: max_batch None is LATER_MAX_BATCH, pad None pads when replay is on."""
+    return LATER_MAX_BATCH if max_batch is None else max_batch, bool(replay) if pad is None else bool(pad)
+
+
+def _all_or_none(what: str, key: str, ids: Sequence, values: Sequence, scope: str, label: str) -> bool:
+    """Whether the scenes `ids` carry `key` (values[i] is not None): all of them or none - ValueError otherwise, raised in the
+    name of the entry point `what`, listing the `label` (frames, scenes, (clip, frame)) without it."""
+    have = [v is not None for v in values]
+    if any(have) and not all(have):
+        raise ValueError(f"{what}: either every scene {scope} carries {key!r} or none does "
+                         f"({label} without: {[i for i, h in zip(ids, have) if not h]})")
+    return any(have)
+
+
+def _batch_seeds(what: str, ids: Sequence, seeds: Sequence, counts: Sequence[int], scope: str, label: str, name,
+                 empty_counts: bool = False) -> Optional[List[int]]:
+    """The scenes' 'vehicle_seeds' concatenated in row order (seeds[i]: a list of counts[i], or None); None when no scene
+    carries seeds; ValueError (`_all_or_none`) when only some do, or when a list is not as long as its scene has vehicles
+    (name(id): how the message calls that scene).  A scene without vehicles decides nothing unless empty_counts."""
+    live = [(i, sd, int(n)) for i, sd, n in zip(ids, seeds, counts) if empty_counts or int(n) > 0]
+    if not _all_or_none(what, "vehicle_seeds", [i for i, _, _ in live], [sd for _, sd, _ in live], scope, label):
+        return None
+    out: List[int] = []
+    for i, sd, n in live:
+        if len(sd) != n:
+            raise ValueError(f"{what}: {name(i)} carries {len(sd)} vehicle_seeds for {n} vehicles")
+        out.extend(int(x) for x in sd)
+    return out
+
+
+def _batch_inpaint(what: str, ids: Sequence, inps: Sequence, scope: str, label: str, required: bool = False) -> bool:
+    """Whether the scenes `ids` carry 'inpaint' (all or none: `_all_or_none`), each entry checked with `inpaint_scene_form`
+    before anything is issued (ValueError for a malformed one; required: for a missing one too - a first frame's refusal)."""
+    has = _all_or_none(what, "inpaint", ids, inps, scope, label)
+    for i in inps:
+        if i is not None or required:
+            inpaint_scene_form(i)
+    return has
+
+
+# ---- `run_later_frames_batched`: frame-major rows of F frames of V vehicles
 def later_batch_row(f: int, v: int, V: int) -> int:
     """The row of (frame f, vehicle v) in a batched later pass: frame-major."""
     return f * V + v
@@ -177,55 +233,35 @@ def later_batch_groups(F: int, V: int, max_batch: Optional[int] = None) -> List[
     """The passes of F later frames of V vehicles: consecutive groups [lo, hi) of max(1, max_batch // V) frames, so that a
     pass holds at most max_batch rows - or one frame, where a single frame already has more (max_batch < V).  max_batch None:
     LATER_MAX_BATCH.  V = 0: one group (there is nothing to bound)."""
-    if max_batch is None:
-        max_batch = LATER_MAX_BATCH
-    if int(max_batch) < 1:
-        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
+    max_batch, _ = _group_bounds(max_batch)
     if F <= 0:
         return []
-    per = F if V == 0 else max(1, int(max_batch) // V)
+    per = F if V == 0 else max(1, max_batch // V)
     return [(lo, min(F, lo + per)) for lo in range(0, F, per)]
 
 
-def later_batch_seeds(seeds_per_frame: Sequence[Optional[Sequence[int]]], V: int) -> Optional[List[int]]:
+def later_batch_seeds(seeds_per_frame: Sequence[Optional[Sequence[int]]], V: int,
+                      what: str = "run_later_frames_batched") -> Optional[List[int]]:
     """The scenes' 'vehicle_seeds' (one list of V per frame, or None) concatenated in row order; None when no scene carries
-    seeds; ValueError when only some do, or a list is not V long."""
-    have = [s is not None for s in seeds_per_frame]
-    if not any(have):
-        return None
-    if not all(have):
-        raise ValueError("run_later_frames_batched: either every scene of the batch carries 'vehicle_seeds' or none does "
-                         f"(frames without: {[f for f, h in enumerate(have) if not h]})")
-    out: List[int] = []
-    for f, sd in enumerate(seeds_per_frame):
-        if len(sd) != V:
-            raise ValueError(f"run_later_frames_batched: frame {f} carries {len(sd)} vehicle_seeds for {V} vehicles")
-        out.extend(int(x) for x in sd)
-    return out
+    seeds; ValueError when only some do, or a list is not V long.  what: the entry point the messages name."""
+    F = len(seeds_per_frame)
+    return _batch_seeds(what, range(F), seeds_per_frame, [V] * F, "of the batch", "frames", lambda f: f"frame {f}", empty_counts=True)
 
 
-# ---- `run_frames_batched`: the scene-major bookkeeping of a pass over the first frames of several scenes (pure Python)
-FRAME_BATCH_MAX_FRAMES = 64   # scenes per group: what one launch of the frame-indexed glue kernels takes (fusg.h FUSG_MAX_FRAMES)
-
-
+# ---- `run_frames_batched`: scene-major rows of the first frames of several scenes
 def frame_batch_groups(counts: Sequence[int], max_batch: Optional[int] = None,
                        max_frames: int = FRAME_BATCH_MAX_FRAMES) -> List[Tuple[int, int]]:
     """The passes of len(counts) scenes with counts[f] vehicles each: consecutive groups [lo, hi) packed greedily - a group is
     closed when the next scene would push it over max_batch rows or over max_frames scenes.  A scene with more than max_batch
     vehicles is a group of its own; every scene appears exactly once, in order.  max_batch None: LATER_MAX_BATCH."""
-    if max_batch is None:
-        max_batch = LATER_MAX_BATCH
-    if int(max_batch) < 1:
-        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
-    if int(max_frames) < 1:
-        raise ValueError(f"max_frames must be at least 1, got {max_frames}")
+    max_batch, max_frames = _group_bounds(max_batch, max_frames)
     groups: List[Tuple[int, int]] = []
     lo, rows = 0, 0
     for f, c in enumerate(counts):
         c = int(c)
         if c < 0:
             raise ValueError(f"scene {f} has {c} vehicles")
-        if f > lo and (rows + c > int(max_batch) or f - lo >= int(max_frames)):
+        if f > lo and (rows + c > max_batch or f - lo >= max_frames):
             groups.append((lo, f))
             lo, rows = f, 0
         rows += c
@@ -259,26 +295,15 @@ def frame_batch_pad(rows: int, max_batch: Optional[int] = None) -> int:
     return min(p, max_batch)
 
 
-def frame_batch_seeds(seeds_per_scene: Sequence[Optional[Sequence[int]]], counts: Sequence[int]) -> Optional[List[int]]:
+def frame_batch_seeds(seeds_per_scene: Sequence[Optional[Sequence[int]]], counts: Sequence[int],
+                      what: str = "run_frames_batched") -> Optional[List[int]]:
     """The scenes' 'vehicle_seeds' concatenated in row order (scene-major); None when no scene that has vehicles carries seeds;
-    ValueError when only some do, or a list is not as long as its scene has vehicles.  A scene without vehicles decides nothing."""
-    live = [f for f, c in enumerate(counts) if int(c) > 0]
-    have = [seeds_per_scene[f] is not None for f in live]
-    if any(have) and not all(have):
-        raise ValueError("run_frames_batched: either every scene that has vehicles carries 'vehicle_seeds' or none does "
-                         f"(scenes without: {[f for f, h in zip(live, have) if not h]})")
-    out: List[int] = []
-    for f in live:
-        sd = seeds_per_scene[f]
-        if sd is None:
-            continue
-        if len(sd) != int(counts[f]):
-            raise ValueError(f"run_frames_batched: scene {f} carries {len(sd)} vehicle_seeds for {int(counts[f])} vehicles")
-        out.extend(int(x) for x in sd)
-    return out if any(have) else None
+    ValueError when only some do, or a list is not as long as its scene has vehicles.  A scene without vehicles decides nothing.
+    what: the entry point the messages name."""
+    return _batch_seeds(what, range(len(counts)), seeds_per_scene, counts, "that has vehicles", "scenes", lambda f: f"scene {f}")
 
 
-# ---- `run_later_clips_batched`: the clip-major bookkeeping of a pass over the future frames of several clips (pure Python)
+# ---- `run_later_clips_batched`: clip-major rows of the future frames of several clips
 def clip_batch_offsets(frames: Sequence[int], vehicles: Sequence[int]) -> List[int]:
     """Row offsets of a group of clips with frames[c] future frames of vehicles[c] vehicles: clip c's rows are offsets[c] ..
     offsets[c + 1], frames[c] * vehicles[c] of them (len(frames) + 1 entries)."""
@@ -307,24 +332,14 @@ def clip_batch_frame_rows(frames: Sequence[int], vehicles: Sequence[int]) -> Lis
     return rows
 
 
-def clip_batch_seeds(seeds_per_clip: Sequence[Sequence[Optional[Sequence[int]]]], vehicles: Sequence[int]) -> Optional[List[int]]:
+def clip_batch_seeds(seeds_per_clip: Sequence[Sequence[Optional[Sequence[int]]]], vehicles: Sequence[int],
+                     what: str = "run_later_clips_batched") -> Optional[List[int]]:
     """The scenes' 'vehicle_seeds' (seeds_per_clip[c][f]: a list of vehicles[c], or None) concatenated in row order; None when
     no scene that has vehicles carries seeds; ValueError naming the (clip, frame) offenders when only some do, or a list is not
-    as long as its clip has vehicles.  A scene without vehicles decides nothing."""
-    live = [(c, f) for c, sd in enumerate(seeds_per_clip) if int(vehicles[c]) > 0 for f in range(len(sd))]
-    have = [seeds_per_clip[c][f] is not None for c, f in live]
-    if any(have) and not all(have):
-        raise ValueError("run_later_clips_batched: either every scene that has vehicles carries 'vehicle_seeds' or none does "
-                         f"((clip, frame) without: {[cf for cf, h in zip(live, have) if not h]})")
-    if not any(have):
-        return None
-    out: List[int] = []
-    for c, f in live:
-        sd = seeds_per_clip[c][f]
-        if len(sd) != int(vehicles[c]):
-            raise ValueError(f"run_later_clips_batched: clip {c} frame {f} carries {len(sd)} vehicle_seeds for {int(vehicles[c])} vehicles")
-        out.extend(int(x) for x in sd)
-    return out
+    as long as its clip has vehicles.  A scene without vehicles decides nothing.  what: the entry point the messages name."""
+    ids = [(c, f) for c, sds in enumerate(seeds_per_clip) for f in range(len(sds))]
+    return _batch_seeds(what, ids, [seeds_per_clip[c][f] for c, f in ids], [vehicles[c] for c, _ in ids], "that has vehicles",
+                        "(clip, frame)", lambda cf: f"clip {cf[0]} frame {cf[1]}")
 
 
 def clip_batch_groups(frames: Sequence[int], vehicles: Sequence[int], max_batch: Optional[int] = None,
@@ -334,14 +349,8 @@ def clip_batch_groups(frames: Sequence[int], vehicles: Sequence[int], max_batch:
     max_frames frames (what one ragged paste takes) or over max_frames clips (what one several-clip warp takes).  A clip that
     alone exceeds a bound is a group of its own with oversized = True: it runs through the one-clip path
     (`run_later_frames_batched`), which splits a clip by frames.  Every clip appears exactly once, in order."""
-    if max_batch is None:
-        max_batch = LATER_MAX_BATCH
-    if int(max_batch) < 1:
-        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
-    if int(max_frames) < 1:
-        raise ValueError(f"max_frames must be at least 1, got {max_frames}")
+    max_batch, max_frames = _group_bounds(max_batch, max_frames)
     offs = clip_batch_offsets(frames, vehicles)                   # (ValueError for a negative count or lists of two lengths)
-    max_batch, max_frames = int(max_batch), int(max_frames)
     groups: List[Tuple[int, int, bool]] = []
     lo, rows, fr = 0, 0, 0
     for c, F in enumerate(frames):
@@ -368,28 +377,23 @@ def later_geometry_batch_rows(scenes: Sequence[Dict], vehicles: Sequence[int], d
     'inpaint' list every first-frame vehicle like 'steps', and either every scene carries them or none does (`inpaint`: the
     pipeline holds the inpainting networks - without them the key is ignored).  ValueError otherwise.  Returns (the seeds of
     the F * V rows, frame-major, or None; whether the pass inpaints)."""
+    what = "run_later_frames_batched_geometry"
     if not device_pose or not device_homography:
-        raise ValueError("run_later_frames_batched_geometry: a geometry-mode state is batched only by a pipeline built with "
+        raise ValueError(f"{what}: a geometry-mode state is batched only by a pipeline built with "
                          f"device_pose=True and device_homography=True (device_pose={bool(device_pose)}, "
                          f"device_homography={bool(device_homography)}): the batched stage is that path's arithmetic, row by row")
     veh = [int(v) for v in vehicles]
     for f, sc in enumerate(scenes):
         if "masks" in sc or sc.get("steps") is None:
-            raise ValueError(f"run_later_frames_batched_geometry: scene {f} is not a geometry-mode scene ('steps', no 'masks')")
+            raise ValueError(f"{what}: scene {f} is not a geometry-mode scene ('steps', no 'masks')")
         for k in ("steps", "vehicle_seeds"):
             if sc.get(k) is not None and veh and len(sc[k]) <= max(veh):
-                raise ValueError(f"run_later_frames_batched_geometry: scene {f} carries {len(sc[k])} {k!r} entries, the state's "
+                raise ValueError(f"{what}: scene {f} carries {len(sc[k])} {k!r} entries, the state's "
                                  f"vehicles reach first-frame index {max(veh)}")
     seeds = later_batch_seeds([None if sc.get("vehicle_seeds") is None else [sc["vehicle_seeds"][v] for v in veh] for sc in scenes],
-                              len(veh))
-    inps = [sc.get("inpaint") if inpaint else None for sc in scenes]
-    if any(i is not None for i in inps) and not all(i is not None for i in inps):
-        raise ValueError("run_later_frames_batched_geometry: either every scene of the batch carries 'inpaint' or none does "
-                         f"(frames without: {[f for f, i in enumerate(inps) if i is None]})")
-    for i in inps:
-        if i is not None:
-            inpaint_scene_form(i)                                 # (ValueError for a malformed entry, before anything is issued)
-    return seeds, inps[0] is not None if inps else False
+                              len(veh), what)
+    has = _batch_inpaint(what, range(len(scenes)), [sc.get("inpaint") if inpaint else None for sc in scenes], "of the batch", "frames")
+    return seeds, has
 
 
 def frame_geometry_batch_rows(scenes: Sequence[Dict], device_pose: bool, device_homography: bool, inpaint: bool = False,
@@ -412,17 +416,10 @@ def frame_geometry_batch_rows(scenes: Sequence[Dict], device_pose: bool, device_
     if len(sizes) > 1:
         raise ValueError(f"run_frames_batched_geometry: the frames of one call have one size, got {sorted(sizes)}")
     counts = [int(np.asarray(sc["bboxes"]).reshape(-1, 4).shape[0]) for sc in scenes]
-    seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
+    seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts, "run_frames_batched_geometry")
     live = [(f, sc) for f, (sc, c) in enumerate(zip(scenes, counts)) if c > 0]
-    has_inpaint = False
-    if inpaint:
-        inps = [(f, sc.get("inpaint")) for f, sc in live]
-        if any(i is not None for _, i in inps) and not all(i is not None for _, i in inps):
-            raise ValueError("run_frames_batched_geometry: either every scene that has vehicles carries 'inpaint' or none does "
-                             f"(scenes without: {[f for f, i in inps if i is None]})")
-        for _, i in inps:
-            inpaint_scene_form(i)                                 # (ValueError for a missing or malformed entry, before anything is issued)
-        has_inpaint = bool(inps)
+    has_inpaint = bool(inpaint) and _batch_inpaint("run_frames_batched_geometry", [f for f, _ in live], [sc.get("inpaint") for _, sc in live],
+                                             "that has vehicles", "scenes", required=True)
     if not classifier:
         for f, sc in live:
             if sc.get("cad_idx") is None:
@@ -1515,6 +1512,122 @@ class VehiclePipeline:
                 out[k] = out[k].clone()
         return out
 
+    # ---- the pass mechanics every frame driver shares, per-frame and batched.  Nothing here knows a row layout: a driver hands
+    # in its row offsets, its padded row count B and its paste function.  All of it runs INSIDE the guarded function, so the range
+    # guard's fp32 redo builds its own plan lookup and buffers (nothing of the first attempt is reused).
+    def _guarded_pass(self, fn, args, check, seeds):
+        """fn(*args) under the range guard (`_guarded`), with the host RNG state of now for its fp32 redo when the pass draws
+        global noise (no 'vehicle_seeds')."""
+        rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
+        return self._guarded(fn, args, check, rng)
+
+    def _pass_buffers(self, pkey, replay, B: int, N: int):
+        """How a pass of N real rows at B >= N network rows meets its recorded plan: (replay - off while another plan is being
+        recorded -, tgt = the inputs of the plan kept under pkey, written in place, or {}, buf).  buf(k, c) -> (the networks'
+        input `k` at B rows of c channels, its padding rows zero; the view of its N real rows the glue writes)."""
+        from . import ops
+        replay = replay and ops.RECORDER is None
+        cp = self._plan(pkey) if replay else None
+        tgt = cp.inputs if cp is not None else {}                 # a recorded pass's inputs are written in place
+
+        def buf(k, c):
+            t = tgt.get(k)
+            if t is None:
+                t = ops.nhwc_empty(B, c, 256, 256, self.device, zero=True)
+            elif B > N:
+                t[N:].zero_()
+            return t, t[:N]
+
+        return replay, tgt, buf
+
+    def _nets_pass(self, fn, pkey, replay, nets_in, seeds, N: Optional[int] = None, clone=None) -> Dict:
+        """The networks `fn` (`_run`, `_later_nets`) over nets_in - one replay of the plan under pkey (`_replay`; clone: the
+        outputs handed out as copies) or eagerly - and 'icn_u8' Lab -> BGR (consumed before the plan's next replay).  N: the real
+        rows of a padded pass - the seeds are padded with 0 to the inputs' rows and every output is cut to N, so nothing behind
+        knows about padding."""
+        from .warp_learn import planes_utils as pu
+        if N is not None and seeds is not None:
+            seeds = seeds + [0] * (int(nets_in["icn_x"].shape[0]) - N)
+        out = self._replay(pkey, nets_in, seeds, fn=fn, clone=clone) if replay else fn(nets_in, seeds)
+        if N is not None:
+            out = {k: v[:N] for k, v in out.items()}
+        out["icn_u8"] = pu.lab2bgr(out["icn_u8"] if N is None else out["icn_u8"].contiguous())     # to_image(from_LAB=True), :182
+        return out
+
+    def _on_inpaint_stream(self, build, tgt):
+        """build() -> EdgeConnect's four inputs, issued on the inpaint branch's stream, forked from the current one.  Returns (the
+        four tensors, join): join() makes the current stream wait for them (`tgt`: they are a recorded pass's own buffers)."""
+        from . import ops
+        if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
+            return build(), (lambda: None)
+        st = self._streams.get("inpaint")
+        if st is None:
+            st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
+        ops.fork_to(st)
+        with torch.cuda.stream(st):
+            res = build()
+        return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
+
+    def _inpaint_inputs_rows(self, scenes, offs, B: int, tgt) -> Tuple[Dict, object]:
+        """EdgeConnect's four inputs of a batch, [B, c, R, R] each (B >= offs[-1]: the padding rows are zero): scene f's rows
+        offs[f] .. offs[f + 1] come from ITS image and boxes (`ops.inpaint_inputs` / `inpaint_inputs_boxed`, or the scene's
+        given tensors copied in), all on the inpaint branch's stream, forked once; `tgt`: a recorded pass's input buffers,
+        written in place.  The offsets are the driver's: f * V for a clip's frames, `frame_batch_offsets` for first frames,
+        `clip_batch_frame_rows` for several clips.  Returns (the four tensors, join)."""
+        from . import ops
+        R, N = 256, offs[-1]
+
+        def build():
+            bufs = {k: tgt["ec_" + k] for k in ops.INPAINT_KEYS} if tgt else \
+                {k: torch.empty((B, 3 if k == "img" else 1, R, R), dtype=torch.float32, device=self.device) for k in ops.INPAINT_KEYS}
+            if B > N:                                             # (every real row is written below)
+                for k in ops.INPAINT_KEYS:
+                    bufs[k][N:].zero_()
+            for f, sc in enumerate(scenes):
+                if offs[f + 1] == offs[f]:
+                    continue
+                inp = sc["inpaint"]
+                rows = {k: bufs[k][offs[f]:offs[f + 1]] for k in ops.INPAINT_KEYS}
+                if "box_masks" in inp:
+                    ops.inpaint_inputs_boxed(sc["frame"], inp["box_masks"], inp["boxes"], out=rows)
+                elif "det_masks" in inp:
+                    ops.inpaint_inputs(sc["frame"], inp["det_masks"], inp["boxes"], out=rows)
+                else:                                             # given
+                    for k in ops.INPAINT_KEYS:
+                        rows[k].copy_(inp[k])
+            return bufs
+
+        return self._on_inpaint_stream(build, tgt)
+
+    def _box_rows(self, boxes) -> torch.Tensor:
+        """The paste box rows of the 'inpaint' boxes of a pass (a list of [n, 4] per scene, in row order): CUDA int32 [N, 8] =
+        (x0, y0, x1, y1, 0, 0, 0, 0), one upload."""
+        import numpy as np
+
+        from . import ops
+        boxes = np.concatenate([np.asarray(b).reshape(-1, 4) for b in boxes])
+        rows = np.zeros((boxes.shape[0], 8), np.int32)
+        rows[:, :4] = boxes
+        return ops.h2d(rows, self.device, torch.int32)
+
+    def _paste_base(self, scene) -> torch.Tensor:
+        """What a scene's composites start from: with inpainting the frame (:133-143, :340), else 'background' or the frame."""
+        inp = scene.get("inpaint") if self.inpaint else None
+        return scene["frame"] if inp is not None else scene.get("background", scene["frame"])
+
+    @staticmethod
+    def _composites(paste, out: Dict, box_geom=None) -> Dict:
+        """'frame_icn' and 'frame_vunet': paste(crops, **box) once per composite (:184-198, :236-250; :393-410, :428-445), the
+        driver's paste function closed over its bases, rows, crop rows and masks.  box_geom (`_box_rows`): with inpainting every
+        vehicle's inpainted box goes under its crop, in vehicle order (:130-145, :340-350)."""
+        box = {} if box_geom is None else dict(box_images=out["inpaint_u8"], box_geom=box_geom)
+        return {k: paste(out[c], **box) for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+
+    @staticmethod
+    def _cat_rows(scenes, k) -> torch.Tensor:
+        """The scenes' per-vehicle tensor `k` in row order (one scene: its own tensor, nothing copied)."""
+        return scenes[0][k] if len(scenes) == 1 else torch.cat([sc[k] for sc in scenes])
+
     @torch.no_grad()
     def _frame_local(self, scene, replay=False):
         """The per-vehicle part of a frame for the vehicles `scene` lists (all of them, or one rank's shard): glue, the
@@ -1537,10 +1650,8 @@ class VehiclePipeline:
                 # an empty shard still hands out a (zero-vehicle) state, so that `run_later_frame` takes part in the gathers
                 return self._no_vehicles(R, "kp_idx", "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if inp is not None else ()),
                                          *(("cad_idx",) if self.cad is not None else ()), "mu_app_0", "mu_app_1", "central")
-            replay = replay and ops.RECORDER is None
             pkey = (V, ops.PRECISION) + (("kp_given",) if scene.get("_hg") is not None else ())
-            cp = self._plan(pkey) if replay else None
-            tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
+            replay, tgt, _ = self._pass_buffers(pkey, replay, V, V)
             # ---- host: the homography fits of every plane of every vehicle (1.2 ms for 8 vehicles), before any launch
             jobs = None if self.device_homography else \
                 pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
@@ -1565,11 +1676,8 @@ class VehiclePipeline:
                 nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
             elif inp is not None:                                 # ... or given
                 nets_in.update(ec_img=inp["img"], ec_gray=inp["gray"], ec_edge=inp["edge"], ec_mask=inp["mask"])
-            if replay:                                            # ('icn_u8' is consumed by lab2bgr below, before the next replay)
-                out = self._replay(pkey, nets_in, seeds, clone=("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"))
-            else:
-                out = self._run(nets_in, seeds)                                                # :75-79, :182, :230-234
-            out["icn_u8"] = pu.lab2bgr(out["icn_u8"])                                          # to_image(from_LAB=True), :182
+            out = self._nets_pass(self._run, pkey, replay, nets_in, seeds,                     # :75-79, :182, :230-234
+                                  clone=("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"))
             out["geom"] = geom
             out["central"] = central
             if "cad_logits" in out:
@@ -1589,15 +1697,7 @@ class VehiclePipeline:
                 return ops.inpaint_inputs_boxed(frame, inp["box_masks"], inp["boxes"], out=out)
             return ops.inpaint_inputs(frame, inp["det_masks"], inp["boxes"], out=out)
 
-        if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
-            return build(), (lambda: None)
-        st = self._streams.get("inpaint")
-        if st is None:
-            st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
-        ops.fork_to(st)
-        with torch.cuda.stream(st):
-            res = build()
-        return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
+        return self._on_inpaint_stream(build, tgt)
 
     def _warp_planes(self, scene, jobs):
         """The source planes warped to the destination pose: from the host-fitted `jobs`, or (device_homography) from the
@@ -1634,7 +1734,7 @@ class VehiclePipeline:
         inp = scene.get("inpaint") if self.inpaint else None
         out = dict(out)
         with torch.cuda.device(dev):
-            back = frame if inp is not None else scene.get("background", frame)   # :133-143: with --inpaint the composite starts from the frame
+            back = self._paste_base(scene)
             if V == 0:
                 out["kp_xy"] = torch.empty((0, 12, 2), dtype=torch.float32, device=dev)
                 out["_pose_raw"] = tuple(torch.empty(sh, dtype=torch.float32, device=dev) for sh in ((0, 4, 3), (0, 4, 3), (0, 4)))
@@ -1653,12 +1753,8 @@ class VehiclePipeline:
                 out["_pose_raw"] = scene["_pose_raw"]
             else:
                 out["_pose_raw"] = cpc_fit_device(f32(scene["focals"]), f32(scene["centers"]), out["kp_xy"], kp3d)   # :104-105
-            box = {}
-            if inp is not None:
-                rows = [[int(b[0]), int(b[1]), int(b[2]), int(b[3]), 0, 0, 0, 0] for b in np.asarray(inp["boxes"]).reshape(-1, 4)]
-                box = dict(box_images=out["inpaint_u8"], box_geom=ops.h2d(rows, dev, torch.int32))
-            out["frame_icn"] = pu.paste_back_device(back, out["icn_u8"], out["geom"], scene["masks"], **box)       # :184-198
-            out["frame_vunet"] = pu.paste_back_device(back, out["vunet_u8"], out["geom"], scene["masks"], **box)   # :236-250
+            out.update(self._composites(lambda crops, **box: pu.paste_back_device(back, crops, out["geom"], scene["masks"], **box), out,
+                                        None if inp is None else self._box_rows([inp["boxes"]])))
             if "mu_app_0" in out:                                 # what `run_later_frame` renders these vehicles' future frames with
                 out["state"] = {"appearance": [out.pop("mu_app_0"), out.pop("mu_app_1")], "central": out.pop("central"),
                                 "shard": (0, V, V), "sharded": False}
@@ -1753,11 +1849,9 @@ class VehiclePipeline:
         with torch.cuda.device(dev):
             if V == 0:
                 return self._no_vehicles(R, "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if inp is not None else ()))
-            replay = replay and ops.RECORDER is None
             # (an inpaint marker in the key: the plans of scenes without 'inpaint' are the ones recorded before)
             pkey = ("later", V, ops.PRECISION) + (("inpaint",) if inp is not None else ())
-            cp = self._plan(pkey) if (replay and inp is not None) else None
-            tgt = cp.inputs if cp is not None else {}            # a recorded pass's EdgeConnect inputs are written in place
+            replay, tgt, _ = self._pass_buffers(pkey, replay, V, V)   # (tgt: only a recorded pass's EdgeConnect inputs are written in place)
             jobs = None if self.device_homography else \
                 pu.warp_jobs_frame(scene["src_kp"], scene["dst_kp"], scene["src_vis"], scene["dst_vis"])
             # ---- :326 from a detector mask: EdgeConnect's inputs of this frame's boxes, on the inpaint branch's stream
@@ -1773,35 +1867,23 @@ class VehiclePipeline:
                 nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
             elif inp is not None:                                 # given
                 nets_in.update(ec_img=inp["img"], ec_gray=inp["gray"], ec_edge=inp["edge"], ec_mask=inp["mask"])
-            if replay:
-                out = self._replay(pkey, nets_in, seeds, fn=self._later_nets)
-            else:
-                out = self._later_nets(nets_in, seeds)
-            out["icn_u8"] = pu.lab2bgr(out["icn_u8"])
+            out = self._nets_pass(self._later_nets, pkey, replay, nets_in, seeds)
             out["geom"] = geom
         return out
 
     @torch.no_grad()
     def _later_finish(self, scene, out):
         """The frame-level part of a later frame, on the rank that holds every vehicle's crops: the ordered paste."""
-        import numpy as np
-
-        from . import ops
         from .warp_learn import planes_utils as pu
-        frame = scene["frame"]
         out = dict(out)
         inp = self._later_inpaint(scene)
         with torch.cuda.device(self.device):
-            back = frame if inp is not None else scene.get("background", frame)   # :340: with --inpaint the composite starts from the frame
+            back = self._paste_base(scene)
             if int(scene["masks"].shape[0]) == 0:
                 out["frame_icn"], out["frame_vunet"] = back.clone(), back.clone()
                 return out
-            box = {}
-            if inp is not None:                                   # :340-350: every vehicle's inpainted box under its crop, in vehicle order
-                rows = [[int(b[0]), int(b[1]), int(b[2]), int(b[3]), 0, 0, 0, 0] for b in np.asarray(inp["boxes"]).reshape(-1, 4)]
-                box = dict(box_images=out["inpaint_u8"], box_geom=ops.h2d(rows, self.device, torch.int32))
-            out["frame_icn"] = pu.paste_back_device(back, out["icn_u8"], out["geom"], scene["masks"], **box)       # :393-410
-            out["frame_vunet"] = pu.paste_back_device(back, out["vunet_u8"], out["geom"], scene["masks"], **box)   # :428-445
+            out.update(self._composites(lambda crops, **box: pu.paste_back_device(back, crops, out["geom"], scene["masks"], **box), out,
+                                        None if inp is None else self._box_rows([inp["boxes"]])))
         return out
 
     def run_later_frames(self, scenes, state: Dict, replay: bool = False):
@@ -1920,23 +2002,14 @@ class VehiclePipeline:
             if int(sc["masks"].shape[0]) != V:
                 raise ValueError(f"run_later_frames_batched: the state holds {V} vehicles, scene {f} {int(sc['masks'].shape[0])}")
         seeds = later_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], V)
-        inps = [self._later_inpaint(sc) for sc in scenes]
-        if any(i is not None for i in inps) and not all(i is not None for i in inps):
-            raise ValueError("run_later_frames_batched: either every scene of the batch carries 'inpaint' or none does "
-                             f"(frames without: {[f for f, i in enumerate(inps) if i is None]})")
-        for i in inps:
-            if i is not None:
-                inpaint_scene_form(i)                             # (ValueError for a malformed entry, before anything is issued)
+        _batch_inpaint("run_later_frames_batched", range(F), [self._later_inpaint(sc) for sc in scenes], "of the batch", "frames")
         if V == 0:
             return [self._run_later_frame(sc, state) for sc in scenes]
         if any(sc["src_planes"].data_ptr() != scenes[0]["src_planes"].data_ptr() or sc["src_planes"].shape != scenes[0]["src_planes"].shape
                for sc in scenes):
             raise ValueError("run_later_frames_batched: the scenes of a batch share the first frame's 'src_planes' (one tensor)")
-        out = []
-        for lo, hi in later_batch_groups(F, V, max_batch):
-            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
-            out.extend(self._guarded(self._run_later_batch, (scenes[lo:hi], state, replay), check, rng))
-        return out
+        return [res for lo, hi in later_batch_groups(F, V, max_batch)
+                for res in self._guarded_pass(self._run_later_batch, (scenes[lo:hi], state, replay), check, seeds)]
 
     def _run_later_batch(self, scenes, state, replay=False) -> list:
         return self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay))
@@ -1948,11 +2021,8 @@ class VehiclePipeline:
         pass's buffer, written in place), 'vu_y' [F * V, 3, R, R].  Nothing here depends on the batch size: every row holds the
         bytes `_later_local` builds for its frame.  geo (geometry mode, `_later_geometry_stage`): the masks, sketches, corner points
         and visibilities come from the device stage instead of the scenes."""
-        import numpy as np
-
-        from . import frame_ops as fo
         from .warp_learn import planes_utils as pu
-        F, R = len(scenes), 256
+        F = len(scenes)
         with torch.cuda.device(self.device):
             if geo is not None:
                 # geometry mode: masks, sketches, corner points and gated visibilities as the device stage left them
@@ -1961,80 +2031,58 @@ class VehiclePipeline:
                 warped = pu.warp_planes_frames_fitted(geo["src_planes"], minv, index, F)       # :376-381
                 masks, sketch = geo["mask"], geo["sketch"]
             else:
-                src_planes = scenes[0]["src_planes"]
-                kp = {k: [veh for sc in scenes for veh in sc[k]] for k in ("src_kp", "dst_kp")}
-                vis = {k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in scenes]) for k in ("src_vis", "dst_vis")}
-                if self.device_homography:
-                    minv, index = pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
-                    warped = pu.warp_planes_frames_fitted(src_planes, minv, index, F)          # :376-381
-                else:
-                    jobs = pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
-                    warped = pu.warp_planes_frames_batch(src_planes, jobs, F)
-                cat = lambda k: scenes[0][k] if F == 1 else torch.cat([sc[k] for sc in scenes])    # noqa: E731
-                masks, sketch = cat("masks"), cat("dst_sketch")
-            _, geom = fo.mask_bbox_geom(masks)
-            icn_x = pu.icn_inputs_device(warped, sketch, state["central"].repeat(F, 1, 1, 1), geom, R, R, out=icn_out)   # :385-387
-            _, vu_y = fo.vunet_inputs(scenes[0]["frame"], masks, sketch, sketch, geom, R)      # :415-420 (y_tilde reads no frame)
+                src_planes, fit = scenes[0]["src_planes"], self._later_fits(scenes)
+                warped = pu.warp_planes_frames_fitted(src_planes, *fit, F) if self.device_homography else \
+                    pu.warp_planes_frames_batch(src_planes, fit, F)                            # :376-381
+                masks, sketch = self._cat_rows(scenes, "masks"), self._cat_rows(scenes, "dst_sketch")
+            return self._later_inputs(warped, masks, sketch, [(state["central"], F)], scenes[0]["frame"], icn_out)
+
+    def _later_fits(self, scenes):
+        """The plane homographies of the scenes' vehicles, in row order, from their host corner points and visibilities: the
+        (minv, index) tables one kernel fits (device_homography), or the host-fitted jobs - what the driver's warp takes."""
+        import numpy as np
+
+        from .warp_learn import planes_utils as pu
+        kp = {k: [veh for sc in scenes for veh in sc[k]] for k in ("src_kp", "dst_kp")}
+        vis = {k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in scenes]) for k in ("src_vis", "dst_vis")}
+        if self.device_homography:
+            return pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
+        return pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
+
+    def _later_inputs(self, warped, masks, sketch, central, frame, icn_out=None, vu_out=None) -> Dict:
+        """The stages of a later pass behind its warp, once for all rows: crop rows, the ICN's inputs with the first frame's
+        central crops - central: (crops [V, ...], frames) per clip, repeated per frame in row order -, the VUnet's y_tilde
+        (icn_out / vu_out: buffers written in place).  The dict `_later_batch_stages` and `_later_clips_stages` return."""
+        from . import frame_ops as fo
+        from .warp_learn import planes_utils as pu
+        R = 256
+        _, geom = fo.mask_bbox_geom(masks)
+        central = [c.repeat(n, 1, 1, 1) for c, n in central]
+        icn_x = pu.icn_inputs_device(warped, sketch, central[0] if len(central) == 1 else torch.cat(central), geom, R, R,
+                                     out=icn_out)                                              # :385-387
+        _, vu_y = fo.vunet_inputs(frame, masks, sketch, sketch, geom, R,                       # :415-420 (y_tilde reads no frame)
+                                  out=None if vu_out is None else (None, vu_out))
         return {"warped": warped, "masks": masks, "geom": geom, "icn_x": icn_x, "vu_y": vu_y}
-
-    def _inpaint_inputs_batch(self, scenes, V: int, tgt) -> Tuple[Dict, object]:
-        """EdgeConnect's four inputs of F frames, [F * V, c, R, R] each: frame f's V rows come from ITS image and boxes
-        (`ops.inpaint_inputs` / `inpaint_inputs_boxed`, or the scene's given tensors copied in), all on the inpaint branch's
-        stream, forked once; `tgt`: a recorded pass's input buffers, written in place.  Returns (the four tensors, join)."""
-        from . import ops
-        F, R = len(scenes), 256
-
-        def build():
-            bufs = {k: tgt["ec_" + k] for k in ops.INPAINT_KEYS} if tgt else \
-                {k: torch.empty((F * V, 3 if k == "img" else 1, R, R), dtype=torch.float32, device=self.device) for k in ops.INPAINT_KEYS}
-            for f, sc in enumerate(scenes):
-                inp, sl = sc["inpaint"], later_batch_slice(f, V)
-                rows = {k: bufs[k][sl] for k in ops.INPAINT_KEYS}
-                if "box_masks" in inp:
-                    ops.inpaint_inputs_boxed(sc["frame"], inp["box_masks"], inp["boxes"], out=rows)
-                elif "det_masks" in inp:
-                    ops.inpaint_inputs(sc["frame"], inp["det_masks"], inp["boxes"], out=rows)
-                else:                                             # given
-                    for k in ops.INPAINT_KEYS:
-                        rows[k].copy_(inp[k])
-            return bufs
-
-        if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
-            return build(), (lambda: None)
-        st = self._streams.get("inpaint")
-        if st is None:
-            st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
-        ops.fork_to(st)
-        with torch.cuda.stream(st):
-            res = build()
-        return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
 
     @torch.no_grad()
     def _later_batch_local(self, scenes, state, replay=False, geo=None) -> Dict:
         """The per-(frame, vehicle) part of a batched later pass: glue, the networks at B = F * V, Lab -> BGR.  Returns 'icn_u8'
         (BGR), 'vunet_u8', 'geom', 'masks' (+ 'inpaint_u8'), F * V rows each, frame-major.  geo: see `_later_batch_stages`."""
         from . import ops
-        from .warp_learn import planes_utils as pu
         F, V = len(scenes), int(state["central"].shape[0])
         inpaint = self._later_inpaint(scenes[0]) is not None
         seeds = later_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], V)
         with torch.cuda.device(self.device):
-            replay = replay and ops.RECORDER is None
             pkey = ("later_batch", F, V, ops.PRECISION) + (("inpaint",) if inpaint else ())
-            cp = self._plan(pkey) if replay else None
-            tgt = cp.inputs if cp is not None else {}            # a recorded pass's big inputs are written in place
-            ec, ec_join = self._inpaint_inputs_batch(scenes, V, tgt) if inpaint else (None, None)
+            replay, tgt, _ = self._pass_buffers(pkey, replay, F * V, F * V)
+            ec, ec_join = self._inpaint_inputs_rows(scenes, [f * V for f in range(F + 1)], F * V, tgt) if inpaint else (None, None)
             st = self._later_batch_stages(scenes, state, icn_out=tgt.get("icn_x"), geo=geo)
             nets_in = {"icn_x": st["icn_x"], "vu_y": st["vu_y"],
                        "app0": state["appearance"][0].repeat(F, 1, 1, 1), "app1": state["appearance"][1].repeat(F, 1, 1, 1)}
             if ec is not None:
                 ec_join()
                 nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
-            if replay:
-                out = self._replay(pkey, nets_in, seeds, fn=self._later_nets)
-            else:
-                out = self._later_nets(nets_in, seeds)
-            out["icn_u8"] = pu.lab2bgr(out["icn_u8"])
+            out = self._nets_pass(self._later_nets, pkey, replay, nets_in, seeds)
             out["geom"], out["masks"] = st["geom"], st["masks"]
         return out
 
@@ -2048,26 +2096,14 @@ class VehiclePipeline:
         V = int(out["geom"].shape[0]) // F
         inpaint = "inpaint_u8" in out
         with torch.cuda.device(self.device):
-            # :340: with --inpaint the composite starts from the frame
-            bases = [sc["frame"] if inpaint else sc.get("background", sc["frame"]) for sc in scenes]
-            box = {}
-            if inpaint:                                           # :340-350: every vehicle's inpainted box under its crop, in vehicle order
-                box = dict(box_images=out["inpaint_u8"], box_geom=box_geom if box_geom is not None else self._later_box_rows(scenes, V))
-            frames = {k: pu.paste_back_frames_device(bases, out[c], out["geom"], out["masks"], **box)       # :393-410, :428-445
-                      for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+            bases = [self._paste_base(sc) for sc in scenes]
+            if inpaint and box_geom is None:
+                box_geom = self._box_rows([sc["inpaint"]["boxes"] for sc in scenes])
+            frames = self._composites(lambda crops, **box: pu.paste_back_frames_device(bases, crops, out["geom"], out["masks"], **box),
+                                      out, box_geom if inpaint else None)
         keys = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
         return [{**{k: out[k][later_batch_slice(f, V)] for k in keys}, "frame_icn": frames["frame_icn"][f],
                  "frame_vunet": frames["frame_vunet"][f]} for f in range(F)]
-
-    def _later_box_rows(self, scenes, V: int) -> torch.Tensor:
-        """The paste box rows of F scenes' 'inpaint' boxes, frame-major: CUDA int32 [F * V, 8] = (x0, y0, x1, y1, 0, 0, 0, 0)."""
-        import numpy as np
-
-        from . import ops
-        rows = np.zeros((len(scenes) * V, 8), np.int32)
-        for f, sc in enumerate(scenes):
-            rows[later_batch_slice(f, V), :4] = np.asarray(sc["inpaint"]["boxes"]).reshape(V, 4)
-        return ops.h2d(rows, self.device, torch.int32)
 
     # ---- the same for a geometry-mode state: the render, the visibilities and the skip rule stay on the device
     def _later_geometry_batched(self, scenes, state, replay, check, max_batch) -> list:
@@ -2093,11 +2129,8 @@ class VehiclePipeline:
             elif "inpaint" in r:
                 del r["inpaint"]
             rows.append(r)
-        out = []
-        for lo, hi in later_batch_groups(len(scenes), V, max_batch):
-            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
-            out.extend(self._guarded(self._run_later_geometry_batch, (rows[lo:hi], state, replay), check, rng))
-        return out
+        return [res for lo, hi in later_batch_groups(len(scenes), V, max_batch)
+                for res in self._guarded_pass(self._run_later_geometry_batch, (rows[lo:hi], state, replay), check, seeds)]
 
     @torch.no_grad()
     def _later_geometry_stage(self, scenes, state, box_rows=None) -> Dict:
@@ -2142,7 +2175,7 @@ class VehiclePipeline:
         F, V = len(scenes), len(veh)
         inpaint = self._later_inpaint(scenes[0]) is not None
         with torch.cuda.device(self.device):
-            box_rows = self._later_box_rows(scenes, V) if inpaint else None
+            box_rows = self._box_rows([sc["inpaint"]["boxes"] for sc in scenes]) if inpaint else None
             geo = self._later_geometry_stage(scenes, state, box_rows)
             frames = self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay, geo=geo), box_geom=box_rows)
             host = geo["host"](ops.d2h(geo["buf"]))               # the one read-back of the group, behind the queued paste
@@ -2224,20 +2257,13 @@ class VehiclePipeline:
         counts = [int(np.asarray(sc["bboxes"]).reshape(-1, 4).shape[0]) for sc in scenes]
         seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
         if self.inpaint:
-            inps = [(f, sc.get("inpaint")) for f, (sc, c) in enumerate(zip(scenes, counts)) if c > 0]
-            if any(i is not None for _, i in inps) and not all(i is not None for _, i in inps):
-                raise ValueError("run_frames_batched: either every scene that has vehicles carries 'inpaint' or none does "
-                                 f"(scenes without: {[f for f, i in inps if i is None]})")
-            for _, i in inps:
-                inpaint_scene_form(i)                             # (ValueError for a malformed entry, before anything is issued)
-        if max_batch is None:
-            max_batch = LATER_MAX_BATCH
-        pad = bool(replay) if pad is None else bool(pad)
+            live = [f for f, c in enumerate(counts) if c > 0]
+            _batch_inpaint("run_frames_batched", live, [scenes[f].get("inpaint") for f in live], "that has vehicles", "scenes", required=True)
+        max_batch, pad = _pad_defaults(replay, max_batch, pad)
         out = []
         for lo, hi in frame_batch_groups(counts, max_batch):
-            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
             rows = frame_batch_pad(sum(counts[lo:hi]), max_batch) if pad else None
-            res, raw = self._guarded(self._run_frame_batch, (scenes[lo:hi], replay, rows), check, rng)
+            res, raw = self._guarded_pass(self._run_frame_batch, (scenes[lo:hi], replay, rows), check, seeds)
             if raw is not None:                                   # the group's one read-back: rvec | tvec | err of every row and start
                 raw = ops.d2h(raw)
                 rv, tv, er = raw[:, :12].reshape(-1, 4, 3), raw[:, 12:24].reshape(-1, 4, 3), raw[:, 24:28]
@@ -2265,7 +2291,7 @@ class VehiclePipeline:
           2. `render.first_geometry_batch_device`: pose selection and geometry (one launch per camera), render, plane visibility,
              the gate, the plane cut-outs of every row from its own frame (fusg_fill_poly_planes_frames_u8);
           3. `plane_homographies_device` on the device corner points and gated visibilities -> `warp_planes_fitted` ->
-             `mask_bbox_geom` -> `icn_inputs_device` -> `frame_ops.vunet_inputs_frames` (-> `_inpaint_inputs_ragged`);
+             `mask_bbox_geom` -> `icn_inputs_device` -> `frame_ops.vunet_inputs_frames` (-> `_inpaint_inputs_rows`);
           4. `_run` with the keypoints (and CAD logits) given, at N rows or the padded rows; replay=True: one recorded plan under
              ("frame_batch", rows, precision, "kp_given"[, "inpaint"][, "cad"]);
           5. `lab2bgr`, one ragged paste per composite with the gated box rows, then ONE `ops.d2h` of the stage's small buffer.
@@ -2299,14 +2325,11 @@ class VehiclePipeline:
         if not _one_rank(self.group):
             return list(self.run_frames(scenes, replay=replay))
         counts, seeds, _ = frame_geometry_batch_rows(scenes, self.device_pose, self.device_homography, self.inpaint, self.cad is not None)
-        if max_batch is None:
-            max_batch = LATER_MAX_BATCH
-        pad = bool(replay) if pad is None else bool(pad)
+        max_batch, pad = _pad_defaults(replay, max_batch, pad)
         out = []
         for lo, hi in frame_batch_groups(counts, max_batch):
-            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
             rows = frame_batch_pad(sum(counts[lo:hi]), max_batch) if pad else None
-            out.extend(self._guarded(self._run_frame_batch_geometry, (scenes[lo:hi], replay, rows), check, rng))
+            out.extend(self._guarded_pass(self._run_frame_batch_geometry, (scenes[lo:hi], replay, rows), check, seeds))
         return out
 
     @torch.no_grad()
@@ -2322,14 +2345,10 @@ class VehiclePipeline:
         from .utils.pnp_utils import cpc_fit_device
         from .warp_learn import planes_utils as pu
         dev, bank, R = self.device, self.cad_bank, 256
-        boxes = [np.asarray(sc["bboxes"]).reshape(-1, 4) for sc in scenes]
-        counts = [int(b.shape[0]) for b in boxes]
-        offs = frame_batch_offsets(counts)
+        boxes, counts, offs, live = self._frame_batch_rows(scenes)
         N = offs[-1]
         frames = [sc["frame"] for sc in scenes]
-        H, W, _ = frames[0].shape
         Ks = [rd.intrinsic(sc["focals"], sc["centers"]) for sc in scenes]
-        live = [sc for sc, c in zip(scenes, counts) if c]
         inpaint = bool(N) and self.inpaint and live[0].get("inpaint") is not None
         out = comp = kp_idx = kp_xy = cad_logits = cad_d = central = geom = None
         with torch.cuda.device(dev):
@@ -2340,22 +2359,9 @@ class VehiclePipeline:
             else:
                 B = N if rows is None else max(int(rows), N)
                 seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
-                if seeds is not None:
-                    seeds = seeds + [0] * (B - N)
-                replay = replay and ops.RECORDER is None
                 pkey = ("frame_batch", B, ops.PRECISION, "kp_given") + (("inpaint",) if inpaint else ()) + \
                     (("cad",) if self.cad is not None else ())
-                cp = self._plan(pkey) if replay else None
-                tgt = cp.inputs if cp is not None else {}        # a recorded pass's inputs are written in place
-
-                def buf(k, c):
-                    """The networks' input `k` at B rows, its padding rows zero, and the view of its N real rows the glue writes."""
-                    t = tgt.get(k)
-                    if t is None:
-                        t = ops.nhwc_empty(B, c, R, R, dev, zero=True)
-                    elif B > N:
-                        t[N:].zero_()
-                    return t, t[:N]
+                replay, tgt, buf = self._pass_buffers(pkey, replay, B, N)
 
                 def padded(t):
                     """A per-row tensor of the keypoint stage at B rows, the padding rows zero."""
@@ -2365,13 +2371,9 @@ class VehiclePipeline:
                     z[:N].copy_(t)
                     return z
 
-                ec, ec_join = self._inpaint_inputs_ragged(scenes, offs, B, tgt) if inpaint else (None, None)
+                ec, ec_join = self._inpaint_inputs_rows(scenes, offs, B, tgt) if inpaint else (None, None)
                 # ---- 1. the keypoint stage, eager, at the N real rows
-                geom_box = ops.h2d([pu._geom_row(*pu.square_crop_geometry((H, W), bb)) for b in boxes for bb in b], dev, torch.int32)
-                img_bbox = fo.crop_resize_frames(frames, offs, geom_box, (R, R), 0)            # :58-60
-                hg_x, hg_rows = buf("hg_x", 3)
-                fo.crop_resize_frames(frames, offs, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD, out=hg_rows)   # :61-65
-                central = fo.central_crop(img_bbox)                                            # vehicle_utils.py:49-52
+                geom_box, hg_x, hg_rows, central = self._frame_batch_crops(frames, offs, boxes, buf)
                 kp_idx = ops.argmax_hw(self.hg(hg_rows)["heatmaps"][-1])                       # :75-79
                 if self.cad is not None:
                     cad_logits = self.cad(hg_rows)                                             # :66-69
@@ -2379,17 +2381,12 @@ class VehiclePipeline:
                 else:
                     cad_d = ops.h2d(np.concatenate([np.asarray(sc["cad_idx"], np.int64).reshape(-1) for sc in live]), dev)
                 kp_xy = fo.keypoints_to_frame(kp_idx, geom_box, (R // 4, R // 4))              # :95-97
-                per_row = lambda k: ops.h2d(np.concatenate([np.broadcast_to(np.asarray(sc[k], np.float32).reshape(-1, 2), (c, 2))   # noqa: E731
-                                                            for sc, c in zip(scenes, counts) if c]), dev)
                 # (an index outside the bank is clamped for the fit only: fusg_pose_geometry flags it and the read-back raises)
                 kp3d_d = bank.device_arrays(dev)["kp3d"].index_select(0, cad_d.clamp(0, len(bank) - 1))
-                raw_d = cpc_fit_device(per_row("focals"), per_row("centers"), kp_xy, kp3d_d)   # :104-105
+                raw_d = cpc_fit_device(self._per_row(scenes, counts, "focals"), self._per_row(scenes, counts, "centers"), kp_xy,
+                                       kp3d_d)                                                 # :104-105
                 # ---- 2. pose, render, visibility, gate, plane cut-outs: nothing read back
-                box_rows = None
-                if inpaint:
-                    brow = np.zeros((N, 8), np.int32)
-                    brow[:, :4] = np.concatenate([np.asarray(sc["inpaint"]["boxes"]).reshape(-1, 4) for sc in live])
-                    box_rows = ops.h2d(brow, dev, torch.int32)
+                box_rows = self._box_rows([sc["inpaint"]["boxes"] for sc in live]) if inpaint else None
                 geo = rd.first_geometry_batch_device(bank, frames, offs, cad_d, Ks, raw_d, kp_xy, box_rows=box_rows)
                 # ---- 3. the glue, every step once for all rows
                 minv, index = pu.plane_homographies_device(geo["tex_pts_d"], geo["tex_pts_d"], geo["vis_d"], geo["vis_d"],
@@ -2407,19 +2404,13 @@ class VehiclePipeline:
                 if ec is not None:
                     ec_join()
                     nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
-                # ---- 4. the networks, the keypoints given
-                if replay:                                        # ('icn_u8' is consumed by lab2bgr below, before the next replay)
-                    out = self._replay(pkey, nets_in, seeds, clone=("vunet_u8", "inpaint_u8", "mu_app_0", "mu_app_1"))
-                else:
-                    out = self._run(nets_in, seeds)                                            # :182, :230-234
-                out = {k: v[:N] for k, v in out.items() if k not in ("kp_idx", "cad_logits")}
-                out["icn_u8"] = pu.lab2bgr(out["icn_u8"].contiguous())                         # to_image(from_LAB=True), :182
-                # ---- 5. one ragged paste per composite (:133-143: with --inpaint the composite starts from the frame)
-                bases = [sc["frame"] if (self.inpaint and sc.get("inpaint") is not None) else sc.get("background", sc["frame"])
-                         for sc in scenes]
-                box = dict(box_images=out["inpaint_u8"], box_geom=box_rows) if inpaint else {}
-                comp = {k: pu.paste_back_ragged_device(bases, offs, out[c], geom, masks, **box)
-                        for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+                # ---- 4. the networks, the keypoints given (their pass-through outputs are the keypoint stage's own)
+                out = self._nets_pass(self._run, pkey, replay, nets_in, seeds, N,              # :182, :230-234
+                                      clone=("vunet_u8", "inpaint_u8", "mu_app_0", "mu_app_1"))
+                # ---- 5. one ragged paste per composite
+                bases = [self._paste_base(sc) for sc in scenes]
+                comp = self._composites(lambda crops, **box: pu.paste_back_ragged_device(bases, offs, crops, geom, masks, **box), out,
+                                        box_rows)
                 host = geo["host"](ops.d2h(geo["buf"]))           # the one read-back of the group, behind the queued paste
             # ---- the per-scene results of `_geometry_frame`, cut from the stacked ones
             keys = ("icn_u8", "vunet_u8") + (("inpaint_u8",) if inpaint else ())
@@ -2449,44 +2440,36 @@ class VehiclePipeline:
                 res.append(self._geometry_assemble(front, o))
         return res
 
-    def _inpaint_inputs_ragged(self, scenes, offs, B: int, tgt) -> Tuple[Dict, object]:
-        """EdgeConnect's four inputs of a group of first frames, [B, c, R, R] each (B >= offs[-1]: the padding rows are zero):
-        scene f's rows offs[f] .. offs[f + 1] come from ITS image and boxes, as `_inpaint_inputs_batch` builds a later batch's -
-        all on the inpaint branch's stream, forked once; `tgt`: a recorded pass's input buffers, written in place."""
+    # ---- the front of a group of first frames, shared by the given-geometry and the geometry-mode group
+    @staticmethod
+    def _frame_batch_rows(scenes):
+        """The scene-major row layout of a group: (the scenes' boxes [V_f, 4], their vehicle counts, `frame_batch_offsets`, the
+        scenes that have vehicles)."""
+        import numpy as np
+        boxes = [np.asarray(sc["bboxes"]).reshape(-1, 4) for sc in scenes]
+        counts = [int(b.shape[0]) for b in boxes]
+        return boxes, counts, frame_batch_offsets(counts), [sc for sc, c in zip(scenes, counts) if c]
+
+    def _frame_batch_crops(self, frames, offs, boxes, buf):
+        """The box crops of every row from its own frame: (the box geometry rows - one upload -, the hourglass input at the
+        padded rows and the view of its real rows (`_pass_buffers`' buf), the central crops)."""
+        from . import frame_ops as fo
         from . import ops
-        R, N = 256, offs[-1]
+        from .warp_learn import planes_utils as pu
+        R, (H, W, _) = 256, frames[0].shape
+        geom_box = ops.h2d([pu._geom_row(*pu.square_crop_geometry((H, W), bb)) for b in boxes for bb in b], self.device, torch.int32)
+        img_bbox = fo.crop_resize_frames(frames, offs, geom_box, (R, R), 0)                    # :58-60
+        hg_x, hg_rows = buf("hg_x", 3)
+        fo.crop_resize_frames(frames, offs, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD, out=hg_rows)   # :61-65
+        return geom_box, hg_x, hg_rows, fo.central_crop(img_bbox)                              # vehicle_utils.py:49-52
 
-        def build():
-            if tgt:
-                bufs = {k: tgt["ec_" + k] for k in ops.INPAINT_KEYS}
-                if B > N:
-                    for k in ops.INPAINT_KEYS:
-                        bufs[k][N:].zero_()
-            else:
-                bufs = {k: torch.zeros((B, 3 if k == "img" else 1, R, R), dtype=torch.float32, device=self.device) for k in ops.INPAINT_KEYS}
-            for f, sc in enumerate(scenes):
-                if offs[f + 1] == offs[f]:
-                    continue
-                inp = sc["inpaint"]
-                rows = {k: bufs[k][offs[f]:offs[f + 1]] for k in ops.INPAINT_KEYS}
-                if "box_masks" in inp:
-                    ops.inpaint_inputs_boxed(sc["frame"], inp["box_masks"], inp["boxes"], out=rows)
-                elif "det_masks" in inp:
-                    ops.inpaint_inputs(sc["frame"], inp["det_masks"], inp["boxes"], out=rows)
-                else:                                             # given
-                    for k in ops.INPAINT_KEYS:
-                        rows[k].copy_(inp[k])
-            return bufs
+    def _per_row(self, scenes, counts, k) -> torch.Tensor:
+        """The scenes' 'focals' or 'centers' per row, float32 [N, 2] on the device (one upload): the pose fit's."""
+        import numpy as np
 
-        if os.environ.get("FUSG_STREAMS", "1") == "0" or self.device.type != "cuda":
-            return build(), (lambda: None)
-        st = self._streams.get("inpaint")
-        if st is None:
-            st = self._streams["inpaint"] = torch.cuda.Stream(device=self.device, priority=0)
-        ops.fork_to(st)
-        with torch.cuda.stream(st):
-            res = build()
-        return res, (lambda: ops.join_from(st, [] if tgt else list(res.values())))
+        from . import ops
+        return ops.h2d(np.concatenate([np.broadcast_to(np.asarray(sc[k], np.float32).reshape(-1, 2), (c, 2))
+                                       for sc, c in zip(scenes, counts) if c]), self.device)
 
     def _frame_batch_empty(self, scene) -> Dict:
         """A scene without vehicles in `run_frames_batched`: `run_frame`'s no-vehicle shape (its composites are its base), and a
@@ -2511,51 +2494,29 @@ class VehiclePipeline:
         from .utils.pnp_utils import cpc_fit_device
         from .warp_learn import planes_utils as pu
         dev, R = self.device, 256
-        boxes = [np.asarray(sc["bboxes"]).reshape(-1, 4) for sc in scenes]
-        counts = [int(b.shape[0]) for b in boxes]
-        offs = frame_batch_offsets(counts)
+        boxes, counts, offs, live = self._frame_batch_rows(scenes)
         N = offs[-1]
         if N == 0:
             return [self._frame_batch_empty(sc) for sc in scenes], None
         B = N if rows is None else max(int(rows), N)
         frames = [sc["frame"] for sc in scenes]
-        H, W, _ = frames[0].shape
-        live = [sc for sc, c in zip(scenes, counts) if c]
-        cat = lambda k: live[0][k] if len(live) == 1 else torch.cat([sc[k] for sc in live])       # noqa: E731
+        cat = lambda k: self._cat_rows(live, k)                                                    # noqa: E731
         lst = lambda k: [veh for sc in live for veh in sc[k]]                                      # noqa: E731
         vis = lambda k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in live])         # noqa: E731
         with torch.cuda.device(dev):
             inpaint = self.inpaint and live[0].get("inpaint") is not None
             seeds = frame_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], counts)
-            if seeds is not None:
-                seeds = seeds + [0] * (B - N)
-            replay = replay and ops.RECORDER is None
             pkey = ("frame_batch", B, ops.PRECISION) + (("inpaint",) if inpaint else ()) + (("cad",) if self.cad is not None else ())
-            cp = self._plan(pkey) if replay else None
-            tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
-
-            def buf(k, c):
-                """The networks' input `k` at B rows, its padding rows zero, and the view of its N real rows the glue writes."""
-                t = tgt.get(k)
-                if t is None:
-                    t = ops.nhwc_empty(B, c, R, R, dev, zero=True)
-                elif B > N:
-                    t[N:].zero_()
-                return t, t[:N]
-
+            replay, tgt, buf = self._pass_buffers(pkey, replay, B, N)
             merged = {"src_planes": cat("src_planes"), "src_kp": lst("src_kp"), "dst_kp": lst("dst_kp"),
                       "src_vis": vis("src_vis"), "dst_vis": vis("dst_vis")}
             masks, src_sketch, dst_sketch = cat("masks"), cat("src_sketch"), cat("dst_sketch")
             # ---- host: the homography fits of every plane of every row, before any launch
             jobs = None if self.device_homography else \
                 pu.warp_jobs_frame(merged["src_kp"], merged["dst_kp"], merged["src_vis"], merged["dst_vis"])
-            ec, ec_join = self._inpaint_inputs_ragged(scenes, offs, B, tgt) if inpaint else (None, None)
+            ec, ec_join = self._inpaint_inputs_rows(scenes, offs, B, tgt) if inpaint else (None, None)
             # ---- uint8 glue on the caller's stream, every step once for all rows
-            geom_box = ops.h2d([pu._geom_row(*pu.square_crop_geometry((H, W), bb)) for b in boxes for bb in b], dev, torch.int32)
-            img_bbox = fo.crop_resize_frames(frames, offs, geom_box, (R, R), 0)                # :58-60
-            hg_x, hg_rows = buf("hg_x", 3)
-            fo.crop_resize_frames(frames, offs, geom_box, (R, R), 1, fo.IMAGENET_MEAN, fo.IMAGENET_STD, out=hg_rows)   # :61-65
-            central = fo.central_crop(img_bbox)                                                # vehicle_utils.py:49-52
+            geom_box, hg_x, _, central = self._frame_batch_crops(frames, offs, boxes, buf)
             warped = self._warp_planes(merged, jobs)                                           # :171-175
             _, geom = fo.mask_bbox_geom(masks)
             icn_x, icn_rows = buf("icn_x", 3 * (int(warped.shape[1]) + 2))
@@ -2566,19 +2527,13 @@ class VehiclePipeline:
             if ec is not None:
                 ec_join()
                 nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
-            if replay:                                            # ('icn_u8' is consumed by lab2bgr below, before the next replay)
-                out = self._replay(pkey, nets_in, seeds, clone=("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"))
-            else:
-                out = self._run(nets_in, seeds)                                                # :75-79, :182, :230-234
-            out = {k: v[:N] for k, v in out.items()}             # the real rows: nothing below knows about padding
-            out["icn_u8"] = pu.lab2bgr(out["icn_u8"].contiguous())                             # to_image(from_LAB=True), :182
+            out = self._nets_pass(self._run, pkey, replay, nets_in, seeds, N,                  # :75-79, :182, :230-234
+                                  clone=("vunet_u8", "kp_idx", "inpaint_u8", "cad_logits", "mu_app_0", "mu_app_1"))
             if "cad_logits" in out:
                 out["cad_idx"] = out.pop("cad_logits").argmax(1)                               # :69
             # ---- keypoints -> frame pixels -> pose fit, with per-row focals and centers
             out["kp_idx"] = out["kp_idx"].contiguous()
             kp_xy = fo.keypoints_to_frame(out["kp_idx"], geom_box, (R // 4, R // 4))           # :95-97 (64 x 64 heat-maps)
-            per_row = lambda k: ops.h2d(np.concatenate([np.broadcast_to(np.asarray(sc[k], np.float32).reshape(-1, 2), (c, 2))   # noqa: E731
-                                                        for sc, c in zip(scenes, counts) if c]), dev)
             banked = [self.cad is not None and sc.get("kp3d_bank") is not None for sc in live]
             if all(banked):                                       # :82-88: the chosen CAD model's keypoints, one gather
                 banks, which = [], []
@@ -2596,17 +2551,13 @@ class VehiclePipeline:
                                   (self.cad is not None and sc.get("kp3d_bank") is not None) else
                                   ops.h2d(np.asarray(sc["kp3d"], np.float32).reshape(-1, 12, 3), dev)
                                   for f, sc in enumerate(scenes) if counts[f]])
-            rv, tv, er = cpc_fit_device(per_row("focals"), per_row("centers"), kp_xy, kp3d)   # :104-105
+            rv, tv, er = cpc_fit_device(self._per_row(scenes, counts, "focals"), self._per_row(scenes, counts, "centers"), kp_xy,
+                                        kp3d)                                                  # :104-105
             raw = torch.cat([rv.reshape(N, 12), tv.reshape(N, 12), er.reshape(N, 4)], 1)
-            # ---- one ragged paste per composite (:184-198, :236-250; :133-143: with --inpaint the composite starts from the frame)
-            bases = [sc["frame"] if (self.inpaint and sc.get("inpaint") is not None) else sc.get("background", sc["frame"]) for sc in scenes]
-            box = {}
-            if inpaint:
-                brow = np.zeros((N, 8), np.int32)
-                brow[:, :4] = np.concatenate([np.asarray(sc["inpaint"]["boxes"]).reshape(-1, 4) for sc in live])
-                box = dict(box_images=out["inpaint_u8"], box_geom=ops.h2d(brow, dev, torch.int32))
-            comp = {k: pu.paste_back_ragged_device(bases, offs, out[c], geom, masks, **box)
-                    for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+            # ---- one ragged paste per composite
+            bases = [self._paste_base(sc) for sc in scenes]
+            comp = self._composites(lambda crops, **box: pu.paste_back_ragged_device(bases, offs, crops, geom, masks, **box), out,
+                                    self._box_rows([sc["inpaint"]["boxes"] for sc in live]) if inpaint else None)
         keys = ("kp_idx", "icn_u8", "vunet_u8") + (("inpaint_u8",) if inpaint else ()) + (("cad_idx",) if "cad_idx" in out else ())
         res = []
         for f, c in enumerate(counts):
@@ -2689,24 +2640,16 @@ class VehiclePipeline:
                          for sc in scs):
                 raise ValueError(f"{what}: the scenes of clip {c} share the first frame's 'src_planes' (one tensor)")
         seeds = clip_batch_seeds([[sc.get("vehicle_seeds") for sc in scs] for scs, _ in clips], vehicles)
-        inps = [((c, f), self._later_inpaint(sc)) for c, (scs, _) in enumerate(clips) if vehicles[c] for f, sc in enumerate(scs)]
-        if any(i is not None for _, i in inps) and not all(i is not None for _, i in inps):
-            raise ValueError(f"{what}: either every scene that has vehicles carries 'inpaint' or none does "
-                             f"((clip, frame) without: {[cf for cf, i in inps if i is None]})")
-        for _, i in inps:
-            if i is not None:
-                inpaint_scene_form(i)                             # (ValueError for a malformed entry, before anything is issued)
-        if max_batch is None:
-            max_batch = LATER_MAX_BATCH
-        pad = bool(replay) if pad is None else bool(pad)
+        live = [(c, f) for c, (scs, _) in enumerate(clips) if vehicles[c] for f in range(len(scs))]
+        _batch_inpaint(what, live, [self._later_inpaint(clips[c][0][f]) for c, f in live], "that has vehicles", "(clip, frame)")
+        max_batch, pad = _pad_defaults(replay, max_batch, pad)
         out = []
         for lo, hi, oversized in clip_batch_groups(frames, vehicles, max_batch):
             if oversized:                                         # more rows or frames than a pass takes: the one-clip path splits by frames
                 out.append(self._later_frames_batched(clips[lo][0], clips[lo][1], replay, check, max_batch, False))
                 continue
-            rng = torch.get_rng_state() if (check == "sync" and seeds is None) else None
             rows = frame_batch_pad(sum(f * v for f, v in zip(frames[lo:hi], vehicles[lo:hi])), max_batch) if pad else None
-            out.extend(self._guarded(self._run_later_clips, (clips[lo:hi], replay, rows), check, rng))
+            out.extend(self._guarded_pass(self._run_later_clips, (clips[lo:hi], replay, rows), check, seeds))
         return out
 
     @torch.no_grad()
@@ -2716,40 +2659,23 @@ class VehiclePipeline:
         R, R], 'vu_y' [N, 3, R, R] for the N = sum(F_c * V_c) rows (icn_out / vu_out: the N real rows of a padded or recorded
         pass's buffers, written in place).  Every row holds the bytes `_later_batch_stages` builds for its clip: a clip without
         frames or without vehicles contributes no row.  At least one row."""
-        import numpy as np
-
-        from . import frame_ops as fo
         from .warp_learn import planes_utils as pu
-        R = 256
         live = [(list(scs), st) for scs, st in clips if len(scs) and int(st["central"].shape[0])]
         scenes = [sc for scs, _ in live for sc in scs]
         with torch.cuda.device(self.device):
             planes = [scs[0]["src_planes"].contiguous() for scs, _ in live]       # by pointer: each clip's planes stay where they are
             counts = [len(scs) for scs, _ in live]
-            kp = {k: [veh for sc in scenes for veh in sc[k]] for k in ("src_kp", "dst_kp")}
-            vis = {k: np.concatenate([np.asarray(sc[k]).reshape(-1, 5) for sc in scenes]) for k in ("src_vis", "dst_vis")}
-            if self.device_homography:
-                minv, index = pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
-                warped = pu.warp_planes_clips_fitted(planes, counts, minv, index)              # :376-381
-            else:
-                jobs = pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
-                warped = pu.warp_planes_clips_batch(planes, counts, jobs)
-            cat = lambda k: scenes[0][k] if len(scenes) == 1 else torch.cat([sc[k] for sc in scenes])    # noqa: E731
-            masks, sketch = cat("masks"), cat("dst_sketch")
-            _, geom = fo.mask_bbox_geom(masks)
-            central = [st["central"].repeat(len(scs), 1, 1, 1) for scs, st in live]
-            icn_x = pu.icn_inputs_device(warped, sketch, central[0] if len(central) == 1 else torch.cat(central), geom, R, R,
-                                         out=icn_out)                                          # :385-387
-            _, vu_y = fo.vunet_inputs(scenes[0]["frame"], masks, sketch, sketch, geom, R,      # :415-420 (y_tilde reads no frame)
-                                      out=None if vu_out is None else (None, vu_out))
-        return {"warped": warped, "masks": masks, "geom": geom, "icn_x": icn_x, "vu_y": vu_y}
+            fit = self._later_fits(scenes)
+            warped = pu.warp_planes_clips_fitted(planes, counts, *fit) if self.device_homography else \
+                pu.warp_planes_clips_batch(planes, counts, fit)                                # :376-381
+            masks, sketch = self._cat_rows(scenes, "masks"), self._cat_rows(scenes, "dst_sketch")
+            return self._later_inputs(warped, masks, sketch, [(st["central"], len(scs)) for scs, st in live], scenes[0]["frame"],
+                                      icn_out, vu_out)
 
     @torch.no_grad()
     def _run_later_clips(self, clips, replay=False, rows=None) -> list:
         """One group of `run_later_clips_batched`: one list of `run_later_frame` dicts per clip.  rows: the row count the networks
         run at (>= N, the padding rows zero); None: N."""
-        import numpy as np
-
         from . import ops
         from .warp_learn import planes_utils as pu
         dev, R = self.device, 256
@@ -2765,22 +2691,9 @@ class VehiclePipeline:
         live = [(scs, st) for (scs, st), F, V in zip(clips, frames, vehicles) if F and V]
         inpaint = self._later_inpaint(live[0][0][0]) is not None
         seeds = clip_batch_seeds([[sc.get("vehicle_seeds") for sc in scs] for scs, _ in clips], vehicles)
-        if seeds is not None:
-            seeds = seeds + [0] * (B - N)
         with torch.cuda.device(dev):
-            replay = replay and ops.RECORDER is None
             pkey = ("later_rows", B, ops.PRECISION) + (("inpaint",) if inpaint else ())
-            cp = self._plan(pkey) if replay else None
-            tgt = cp.inputs if cp is not None else {}            # a recorded pass's inputs are written in place
-
-            def buf(k, c):
-                """The networks' input `k` at B rows, its padding rows zero, and the view of its N real rows the glue writes."""
-                t = tgt.get(k)
-                if t is None:
-                    t = ops.nhwc_empty(B, c, R, R, dev, zero=True)
-                elif B > N:
-                    t[N:].zero_()
-                return t, t[:N]
+            replay, tgt, buf = self._pass_buffers(pkey, replay, B, N)
 
             def per_row(i):
                 """The clips' appearance code i repeated per frame, concatenated in row order, zero rows up to B."""
@@ -2789,7 +2702,7 @@ class VehiclePipeline:
                     parts.append(parts[0].new_zeros((B - N,) + tuple(parts[0].shape[1:])))
                 return parts[0] if len(parts) == 1 else torch.cat(parts)
 
-            ec, ec_join = self._inpaint_inputs_ragged(scenes, frame_rows, B, tgt) if inpaint else (None, None)
+            ec, ec_join = self._inpaint_inputs_rows(scenes, frame_rows, B, tgt) if inpaint else (None, None)
             if B > N or tgt:
                 (icn_x, icn_rows), (vu_y, vu_rows) = buf("icn_x", 21), buf("vu_y", 3)
                 st = self._later_clips_stages(clips, icn_out=icn_rows, vu_out=vu_rows)
@@ -2801,21 +2714,11 @@ class VehiclePipeline:
             if ec is not None:
                 ec_join()
                 nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
-            if replay:
-                out = self._replay(pkey, nets_in, seeds, fn=self._later_nets)
-            else:
-                out = self._later_nets(nets_in, seeds)
-            out = {k: v[:N] for k, v in out.items()}             # the real rows: nothing below knows about padding
-            out["icn_u8"] = pu.lab2bgr(out["icn_u8"].contiguous())
-            # ---- one ragged paste per composite over all (clip, frame) frames (:340: with --inpaint the composite starts from the frame)
-            bases = [sc["frame"] if self._later_inpaint(sc) is not None else sc.get("background", sc["frame"]) for sc in scenes]
-            box = {}
-            if inpaint:                                           # :340-350: every vehicle's inpainted box under its crop, in vehicle order
-                brow = np.zeros((N, 8), np.int32)
-                brow[:, :4] = np.concatenate([np.asarray(sc["inpaint"]["boxes"]).reshape(-1, 4) for scs, _ in live for sc in scs])
-                box = dict(box_images=out["inpaint_u8"].contiguous(), box_geom=ops.h2d(brow, dev, torch.int32))
-            comp = {k: pu.paste_back_ragged_device(bases, frame_rows, out[c], geom, masks, **box)          # :393-410, :428-445
-                    for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
+            out = self._nets_pass(self._later_nets, pkey, replay, nets_in, seeds, N)
+            # ---- one ragged paste per composite over all (clip, frame) frames
+            bases = [self._paste_base(sc) for sc in scenes]
+            comp = self._composites(lambda crops, **box: pu.paste_back_ragged_device(bases, frame_rows, crops, geom, masks, **box), out,
+                                    self._box_rows([sc["inpaint"]["boxes"] for scs, _ in live for sc in scs]) if inpaint else None)
         keys = ("icn_u8", "vunet_u8") + (("inpaint_u8",) if inpaint else ())
         res, k0 = [], 0
         for c, (scs, _) in enumerate(clips):

@@ -362,6 +362,29 @@ def test_replay_equals_the_padded_eager_pass_and_keeps_one_plan(env):
     assert {k: id(v) for k, v in pipe._frame_plans.items() if k[0] != "frame_batch"} == before
 
 
+def test_a_replay_zeroes_the_padding_row_an_earlier_group_filled(env):
+    """A group of 4 real rows replayed, then 3 real rows of other scenes under the same ("frame_batch", 4, ...) plan: the plan's
+    reused input buffers hold the first group's row 3, which the second group pads - every output of the second call equals the
+    padded eager pass of the same scenes, bit for bit."""
+    pipe, whole = env["pipe"], env["whole"]
+    key = ("frame_batch", 4, ops.PRECISION)
+    pipe._frame_plans.pop(key, None)
+    pipe.run_frames_batched([pl.slice_scene(whole, 0, 2), pl.slice_scene(whole, 2, 4)], replay=True)
+    plan = pipe._frame_plans[key]
+    scenes = [pl.slice_scene(whole, 4, 5), dict(pl.slice_scene(whole, 1, 3), frame=whole["frame"] ^ 1)]
+    got = pipe.run_frames_batched(scenes, replay=True)
+    assert pipe._frame_plans[key] is plan                                         # replayed, not recorded again
+    want = pipe.run_frames_batched(scenes, replay=False, pad=True)
+    assert len(got) == len(want) == 2
+    for a, b in zip(got, want):
+        assert set(a) == set(b)
+        for k in KEYS:
+            assert torch.equal(a[k], b[k]), k
+        assert _pose_equal(a["pose"], b["pose"])
+        assert torch.equal(a["state"]["central"], b["state"]["central"])
+        assert all(torch.equal(x, y) for x, y in zip(a["state"]["appearance"], b["state"]["appearance"]))
+
+
 def test_chunked_passes_meet_the_same_bars_in_scene_order(env):
     """6: counts (2, 1, 3) with max_batch 3: two groups, (2, 1) and (3); scene f's result sits at position f."""
     pipe, own = env["pipe"], env["own"]
@@ -498,7 +521,7 @@ def test_inpainted_batch_matches_the_oracle_and_builds_its_inputs_per_scene():
         sc["vehicle_seeds"] = [base + v for v in range(V)]
         scenes.append(sc)
     per_scene = [ops.inpaint_inputs_boxed(sc["frame"], sc["inpaint"]["box_masks"], sc["inpaint"]["boxes"]) for sc in scenes]
-    ec, join = pipe._inpaint_inputs_ragged(scenes, [0, 2, 3], 4, {})
+    ec, join = pipe._inpaint_inputs_rows(scenes, [0, 2, 3], 4, {})
     join()
     for k in ops.INPAINT_KEYS:
         assert torch.equal(ec[k][:3], torch.cat([four[k] for four in per_scene])), k

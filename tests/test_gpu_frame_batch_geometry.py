@@ -377,6 +377,22 @@ def test_replay_equals_the_padded_eager_pass_and_keeps_one_plan(env):
     pipe._frame_plans.pop(key)
 
 
+def test_a_replay_zeroes_the_padding_row_an_earlier_group_filled(env):
+    """A group of 4 real rows replayed, then 3 real rows of other scenes under the same ("frame_batch", 4, ..., "kp_given") plan:
+    the plan's reused input buffers hold the first group's row 3, which the second group pads - every output of the second call
+    equals the padded eager pass of the same scenes, bit for bit."""
+    pipe, scene = env["pipe"], env["scene"]
+    key = ("frame_batch", 4, ops.PRECISION, "kp_given")
+    pipe._frame_plans.pop(key, None)
+    pipe.run_frames_batched_geometry([_cut(scene, 0, 2), _cut(scene, 1, 3, frame=scene["frame"] ^ 1)], replay=True)
+    plan = pipe._frame_plans[key]
+    scenes = [_cut(scene, 2, 3, frame=scene["frame"] ^ 2), _cut(scene, 0, 2, frame=scene["frame"] ^ 3)]
+    got = pipe.run_frames_batched_geometry(scenes, replay=True)
+    assert pipe._frame_plans[key] is plan                                         # replayed, not recorded again
+    _same_results(got, pipe.run_frames_batched_geometry(scenes, replay=False, pad=True), "stale padding row")
+    pipe._frame_plans.pop(key)
+
+
 # ------------------------------------------------------------------------------------------------ 7. the state
 def test_the_state_serves_the_later_frame_drivers(env):
     """The state of a batched first frame is taken unchanged by the later-frame drivers.  Bit equality needs the appearance codes

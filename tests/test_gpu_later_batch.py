@@ -464,7 +464,7 @@ def test_inpainted_batch_matches_the_reference(inpaint_env, form):
         scenes = [fr["box_masks"] for fr in frames]
     else:
         scenes = [dict(fr["later"], inpaint=dict(four, boxes=fr["boxes"])) for fr, four in zip(frames, per_frame)]
-    ec, join = pipe._inpaint_inputs_batch(scenes, 2, {})
+    ec, join = pipe._inpaint_inputs_rows(scenes, [0, 2, 4], 4, {})
     join()
     for k in ops.INPAINT_KEYS:
         assert torch.equal(ec[k], torch.cat([four[k] for four in per_frame])), k

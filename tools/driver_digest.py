@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""GPU box, analysis tool: sha256 of every output tensor of the frame drivers on fixed synthetic scenes (360 x 640, f16x3, fixed
+seeds, 'vehicle_seeds' given), with and without an inpaint=True pipeline, replay False and True (True twice: the recording, then a
+replay into the plan's buffers).  It uses public entry points and `synth_*` only, so the same file runs on a checkout of another
+commit: two runs whose JSON is identical key for key computed the same bytes (a refactor of pipeline.py: nothing changed).
+
+    python tools/driver_digest.py --out digest.json                 # this tree
+    python tools/driver_digest.py --repo OTHER_CHECKOUT --out other.json
+    python tools/driver_digest.py --join parent=other.json tree=digest.json --out profiles/driver_refactor_digest.json
+
+--join keeps one sha256 per entry (driver / arguments / replay arm), folded from that entry's per-tensor digests."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+HW, F = (360, 640), 3
+
+
+def digest(o):
+    """Nested results -> the same nesting with a sha256 per tensor / array (dtype and shape hashed too); other leaves as text."""
+    import numpy as np
+    import torch
+    if torch.is_tensor(o):
+        o = o.detach().cpu().contiguous().numpy()
+    if isinstance(o, np.ndarray):
+        return hashlib.sha256(f"{o.dtype}{o.shape}".encode() + np.ascontiguousarray(o).tobytes()).hexdigest()
+    if isinstance(o, dict):
+        return {str(k): digest(v) for k, v in sorted(o.items(), key=lambda kv: str(kv[0]))}
+    if isinstance(o, (list, tuple)):
+        return [digest(v) for v in o]
+    return repr(o)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repo", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the built checkout to import")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--join", nargs="+", metavar="ARM=FILE", help="no GPU: merge digests into one file and say whether they are equal")
+    args = ap.parse_args()
+    if args.join:
+        # one line per entry: the sha256 of its per-tensor digests in canonical form (the per-tensor files locate a difference)
+        fold = lambda run: {k: hashlib.sha256(json.dumps(v, sort_keys=True).encode()).hexdigest() for k, v in run.items()}   # noqa: E731
+        arms = {a.split("=", 1)[0]: fold(json.load(open(a.split("=", 1)[1]))) for a in args.join}
+        first = next(iter(arms.values()))
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/driver_digest.py", "identical": all(v == first for v in arms.values()), **arms}, f, indent=1, sort_keys=True)
+        return
+    sys.path[:0] = [args.repo, os.path.join(args.repo, "tests")]
+    import numpy as np
+    import torch
+
+    import oracle
+    import render_ref as RR
+    from future_urban_scene_generation_amd import ops
+    from future_urban_scene_generation_amd import pipeline as pl
+    from future_urban_scene_generation_amd import render as R
+    print("driver_digest: the pipeline of", os.path.abspath(pl.__file__), flush=True)
+    dev = torch.device("cuda:0")
+    torch.set_grad_enabled(False)
+    ops.set_precision("f16x3")
+    out = {}
+
+    def rec(tag, fn):
+        """fn(replay) three times: eager, the recording, the replay."""
+        for name, replay in (("eager", False), ("replay_1", True), ("replay_2", True)):
+            out[f"{tag}/{name}"] = digest(fn(replay))
+            print(tag, name, flush=True)
+
+    for inpaint in (False, True):
+        pipe = pl.VehiclePipeline(dev, inpaint=inpaint)
+        form = "box_masks" if inpaint else None
+
+        def clip(V, seed, Fc=F):
+            """(first scene, Fc later scenes) of V vehicles; V = 0: a scene cut to none."""
+            sc = pl.synth_frame(max(V, 1), HW, dev, seed=seed, inpaint="masks" if inpaint else False)
+            sc["vehicle_seeds"] = [100 * seed + v for v in range(max(V, 1))]
+            later = [dict(pl.synth_later_frame(sc, s + 1, form), frame=torch.roll(sc["frame"], 37 * (s + 1), 1).contiguous())
+                     for s in range(Fc)]
+            return pl.slice_scene(sc, 0, V), [pl.slice_scene(sc_, 0, V) for sc_ in later]
+
+        tag = "inpaint" if inpaint else "plain"
+        first, later = clip(2, 3)
+        state = pipe.run_frame(first)["state"]
+        rec(f"{tag}/run_frame", lambda r: pipe.run_frame(first, replay=r))
+        rec(f"{tag}/run_later_frame", lambda r: pipe.run_later_frame(later[0], state, replay=r))
+        for mb in (64, 2):
+            rec(f"{tag}/run_later_frames_batched/max_batch_{mb}", lambda r: pipe.run_later_frames_batched(later, state, replay=r, max_batch=mb))
+        firsts = [clip(V, 10 + i)[0] for i, V in enumerate((2, 0, 1))]
+        for pad in (True, False):
+            rec(f"{tag}/run_frames_batched/pad_{pad}", lambda r: pipe.run_frames_batched(firsts, replay=r, pad=pad))
+        clips = []
+        for i, (Fc, V) in enumerate(((2, 2), (1, 1), (2, 0))):
+            f0, lat = clip(V, 20 + i, Fc)
+            clips.append((lat, pipe.run_frames_batched([f0])[0]["state"]))
+        rec(f"{tag}/run_later_clips_batched", lambda r: pipe.run_later_clips_batched(clips, replay=r))
+        del pipe
+
+    # ---- the geometry siblings: a CAD bank of boxes around well-posed keypoints of the first hourglass run (no reference data)
+    pipe = pl.VehiclePipeline(dev, device_pose=True, device_homography=True)
+    scenes, meshes = [], []
+    for f, V in enumerate((2, 0, 1)):
+        sc = pl.synth_frame(max(V, 1), HW, dev, seed=100 + f)
+        geo = {"frame": sc["frame"], "bboxes": sc["bboxes"][:V], "focals": sc["focals"], "centers": sc["centers"],
+               "cad_idx": len(meshes) + np.arange(V), "vehicle_seeds": [1000 * f + v for v in range(V)]}
+        if V:
+            kp3d = oracle.frame.well_posed_kp3d(pipe.run_frame(pl.slice_scene(sc, 0, V))["kp_xy"].cpu().numpy(), sc["focals"], sc["centers"], seed=2)
+            meshes += [(mv / R.SCALE, mt, k / R.SCALE) for k in kp3d for mv, mt in [RR.box_around(k, n=13)]]
+        scenes.append(geo)
+    pipe._frame_plans.clear()
+    pipe.cad_bank = R.CadBank(meshes)
+    rec("geometry/run_frames_batched_geometry", lambda r: pipe.run_frames_batched_geometry(scenes, replay=r))
+    state = pipe.run_frame(scenes[0])["state"]
+    steps = R.trajectory_steps(np.c_[np.arange(F + 1.0) * 0.8, 0.05 * np.arange(F + 1.0) ** 2])
+    laters = [{"frame": torch.roll(scenes[0]["frame"], 37 * (n + 1), 1).contiguous(), "steps": [steps[n]] * 2,
+               "vehicle_seeds": [1000 * (n + 1) + v for v in range(2)]} for n in range(F)]
+    rec("geometry/run_later_frames_batched_geometry", lambda r: pipe.run_later_frames_batched_geometry(laters, state, replay=r))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+
+
+if __name__ == "__main__":
+    main()
