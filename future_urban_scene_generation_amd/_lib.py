@@ -150,6 +150,8 @@ _SIGS = {
     "fusg_find_homography_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "fusg_pose_geometry": (C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 11),
     "fusg_pose_geometry_host": (C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 10),
+    "fusg_pose_geometry_clips": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 12),
+    "fusg_pose_geometry_clips_host": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 11),
     "fusg_later_gate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "fusg_later_gate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "fusg_inpaint_inputs": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [_TP] * 4 + [C.c_void_p] * 2),

@@ -180,12 +180,14 @@ PG_FN void texture_corners(const double kp2[NKP][2], int H, int W, int32_t* pts,
     }
 }
 
-// everything of vehicle v
-PG_FN void vehicle(const Args& a, int v) {
+// everything of vehicle v.  Its CAD index and, on a later frame, its pose are read at row `src` of cad_idx / pose_in: v itself for
+// fusg_pose_geometry, the vehicle's row in its clip's tables for fusg_pose_geometry_clips (clips_row below); steps and every output
+// are rows v.
+PG_FN void vehicle(const Args& a, int v, long src) {
     const bool later = a.steps != nullptr;
     float pose[7];
     if (later)
-        for (int j = 0; j < 7; ++j) pose[j] = a.pose_in[(long)v * 7 + j];
+        for (int j = 0; j < 7; ++j) pose[j] = a.pose_in[src * 7 + j];
     else
         select_and_flip(a.rvec + (long)v * 12, a.tvec + (long)v * 12, a.err + (long)v * 4, pose);
     for (int j = 0; j < 7; ++j) a.pose[(long)v * 7 + j] = pose[j];
@@ -202,7 +204,7 @@ PG_FN void vehicle(const Args& a, int v) {
     for (int j = 0; j < 12; ++j) a.extrinsic[(long)v * 12 + j] = (double)E32[j];
 
     // the CAD model: its keypoints and its slices of the bank
-    const int64_t m = a.cad_idx[v];
+    const int64_t m = a.cad_idx[src];
     const bool cad_ok = m >= 0 && m < (int64_t)a.n_cad;
     a.status[v] = cad_ok ? 0 : STATUS_BAD_CAD;
     float kp32[NKP][3];
@@ -255,6 +257,42 @@ PG_FN void vehicle(const Args& a, int v) {
     job.t_off = cad_ok ? a.bank_t_off[m] : 0;
     job.nt = cad_ok ? a.bank_t_off[m + 1] - a.bank_t_off[m] : 0;
     a.jobs[v] = job;
+}
+
+PG_FN void vehicle(const Args& a, int v) { vehicle(a, v, (long)v); }
+
+// ---- the later-frame branch for rows of SEVERAL clips (fusg_pose_geometry_clips): clip-major rows, frame-major inside a clip - row
+// row_first[c] + f * vehicles[c] + v is clip c, frame f, vehicle v.  The per-clip tables travel by value (three device pointers and
+// two ints per clip, 2.3 KB of the 4 KB kernel-argument space); the cameras do not fit beside them and are read from device memory.
+struct ClipsArgs {
+    const float* pose[FUSG_MAX_FRAMES];              // [V_c][7]
+    const int64_t* cad_idx[FUSG_MAX_FRAMES];         // [V_c]
+    const int32_t* src_pts[FUSG_MAX_FRAMES];         // [V_c][NTEX][MAXP][2]
+    int32_t vehicles[FUSG_MAX_FRAMES];
+    int32_t row_first[FUSG_MAX_FRAMES + 1];
+    int n_clips;
+    const double* steps;                             // [J][4]
+    const double* cams;                              // [n_clips][9], row-major K per clip
+    const float* bank_kp3d; const int32_t* bank_v_off; const int32_t* bank_t_off; int n_cad;
+    int H, W, J;
+    float* pose_out; double* extrinsic; double* kp3d; fusg_render_job* jobs;
+    int32_t* vis_pts; int32_t* vis_nv; int32_t* nearer; int32_t* tex_pts; int32_t* tex_nv; int32_t* status;
+    int32_t* src_pts_rows;                           // [J][NTEX][MAXP][2]
+};
+
+// row j: `vehicle` with its clip's pose table, CAD indices and camera, and the row's copy of its source corner points.  The host has
+// checked the offsets (0 .. J, non-decreasing, a clip's rows a multiple of its vehicles), so the scan ends and V > 0 here.
+PG_FN void clips_row(const ClipsArgs& t, int j) {
+    int c = 0;
+    while (j >= t.row_first[c + 1]) ++c;
+    const int v = (j - t.row_first[c]) % t.vehicles[c];
+    Args a{nullptr, nullptr, nullptr, t.pose[c], nullptr, t.steps, t.cad_idx[c], t.bank_kp3d, t.bank_v_off, t.bank_t_off, t.n_cad, {0},
+           t.H, t.W, t.J, t.pose_out, t.extrinsic, t.kp3d, t.jobs, t.vis_pts, t.vis_nv, t.nearer, t.tex_pts, t.tex_nv, t.status};
+    for (int i = 0; i < 9; ++i) a.K[i] = t.cams[(long)c * 9 + i];
+    vehicle(a, j, (long)v);
+    constexpr int NPTS = NTEX * MAXP * 2;
+    const int32_t* sp = t.src_pts[c] + (long)v * NPTS;
+    for (int i = 0; i < NPTS; ++i) t.src_pts_rows[(long)j * NPTS + i] = sp[i];
 }
 
 // ---- the tail of a later frame's geometry stage (fusg_later_gate): what the frame driver decided on the host after reading the

@@ -18,6 +18,12 @@ __global__ __launch_bounds__(PG_BLOCK) void pose_geometry_kernel(const pg::Args 
     if (v < a.V) pg::vehicle(a, v);
 }
 
+// fusg_pose_geometry_clips: one thread per row of several clips; the per-clip tables are kernel arguments, the cameras device memory.
+__global__ __launch_bounds__(PG_BLOCK) void pose_geometry_clips_kernel(const pg::ClipsArgs t) {
+    const int j = blockIdx.x * PG_BLOCK + threadIdx.x;
+    if (j < t.J) pg::clips_row(t, j);
+}
+
 // fusg_later_gate: one thread per (row, slot), GATE_SLOTS = 8 slots per row - a block of 64 lanes holds 8 whole rows, so a
 // row's visibilities, its valid word and its box row are written by neighbouring lanes with ordinary stores.
 __global__ __launch_bounds__(PG_BLOCK) void later_gate_kernel(const int32_t* counts, const int32_t* covered, int J, int P,
@@ -89,6 +95,88 @@ extern "C" int fusg_pose_geometry_host(const float* rvec, const float* tvec, con
     const int rc = pose_geometry_check(a, "pose_geometry_host");
     if (rc != FUSG_OK) return rc;
     for (int v = 0; v < V; ++v) pg::vehicle(a, v);
+    return FUSG_OK;
+}
+
+// ---- the later-frame branch for rows of several clips.  The five tables are HOST arrays, read and checked here, before anything is
+// launched; `what` names the entry point in the messages.  Returns FUSG_OK with t filled; t.J == 0: nothing to do.
+static int pose_geometry_clips_args(pg::ClipsArgs& t, const char* what, const float* const* poses, const int64_t* const* cad_idxs,
+                                    const int32_t* const* src_pts, const int32_t* vehicles, const int32_t* row_first, int32_t n_clips,
+                                    const double* steps, const double* cams, const float* bank_kp3d, const int32_t* bank_v_off,
+                                    const int32_t* bank_t_off, int32_t n_cad, int32_t H, int32_t W, int32_t J, float* pose,
+                                    double* extrinsic, double* kp3d, fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv,
+                                    int32_t* nearer, int32_t* tex_pts, int32_t* tex_nv, int32_t* status, int32_t* src_pts_rows) {
+    FUSG_CHECK(n_clips >= 1 && n_clips <= FUSG_MAX_FRAMES, "%s: n_clips = %d (1..%d)", what, n_clips, FUSG_MAX_FRAMES);
+    FUSG_CHECK(J >= 0 && J < (1 << 20), "%s: J %d (0 .. 2^20 - 1)", what, J);
+    FUSG_CHECK(poses && cad_idxs && src_pts && vehicles && row_first, "%s: a host table is null (poses, cad_idxs, src_pts, vehicles, row_first)",
+               what);
+    memset(&t, 0, sizeof(t));
+    FUSG_CHECK(row_first[0] == 0, "%s: the row offsets start at %d, not at 0", what, row_first[0]);
+    for (int c = 0; c < n_clips; ++c) {
+        const int V = vehicles[c];
+        const long cnt = (long)row_first[c + 1] - row_first[c];
+        FUSG_CHECK(V >= 0, "%s: clip %d has %d vehicles", what, c, V);
+        FUSG_CHECK(cnt >= 0, "%s: the row offsets decrease at clip %d (%d after %d)", what, c, row_first[c + 1], row_first[c]);
+        FUSG_CHECK(V == 0 ? cnt == 0 : cnt % V == 0, "%s: clip %d owns %ld rows, not a multiple of its %d vehicles", what, c, cnt, V);
+        FUSG_CHECK(cnt == 0 || (poses[c] && cad_idxs[c] && src_pts[c]), "%s: clip %d owns %ld rows and has a null table (pose, cad_idx, src_pts)",
+                   what, c, cnt);
+        t.pose[c] = poses[c];
+        t.cad_idx[c] = cad_idxs[c];
+        t.src_pts[c] = src_pts[c];
+        t.vehicles[c] = V;
+        t.row_first[c] = row_first[c];
+    }
+    for (int c = n_clips; c <= FUSG_MAX_FRAMES; ++c) t.row_first[c] = row_first[n_clips];
+    FUSG_CHECK(row_first[n_clips] == J, "%s: the row offsets end at %d, J is %d", what, row_first[n_clips], J);
+    t.n_clips = n_clips;
+    t.J = J;
+    if (J == 0) return FUSG_OK;
+    FUSG_CHECK(H >= 1 && W >= 1 && n_cad >= 1, "%s: H %d, W %d, n_cad %d must be positive", what, H, W, n_cad);
+    FUSG_CHECK(steps && cams && bank_kp3d && bank_v_off && bank_t_off, "%s: steps, cams or a bank table is null", what);
+    FUSG_CHECK(pose && extrinsic && kp3d && jobs && vis_pts && vis_nv && nearer && tex_pts && tex_nv && status && src_pts_rows,
+               "%s: an output pointer is null", what);
+    t.steps = steps; t.cams = cams;
+    t.bank_kp3d = bank_kp3d; t.bank_v_off = bank_v_off; t.bank_t_off = bank_t_off; t.n_cad = n_cad;
+    t.H = H; t.W = W;
+    t.pose_out = pose; t.extrinsic = extrinsic; t.kp3d = kp3d; t.jobs = jobs;
+    t.vis_pts = vis_pts; t.vis_nv = vis_nv; t.nearer = nearer; t.tex_pts = tex_pts; t.tex_nv = tex_nv; t.status = status;
+    t.src_pts_rows = src_pts_rows;
+    return FUSG_OK;
+}
+
+static int pose_geometry_clips_impl(pg::ClipsArgs t, void* stream) {
+    hipLaunchKernelGGL(pose_geometry_clips_kernel, dim3((unsigned)((t.J + PG_BLOCK - 1) / PG_BLOCK)), dim3(PG_BLOCK), 0, (hipStream_t)stream, t);
+    FUSG_LAUNCH_CHECK("pose_geometry_clips");
+    return FUSG_OK;
+}
+
+extern "C" int fusg_pose_geometry_clips(const float* const* poses, const int64_t* const* cad_idxs, const int32_t* const* src_pts,
+                                        const int32_t* vehicles, const int32_t* row_first, int32_t n_clips, const double* steps,
+                                        const double* cams, const float* bank_kp3d, const int32_t* bank_v_off, const int32_t* bank_t_off,
+                                        int32_t n_cad, int32_t H, int32_t W, int32_t J, float* pose, double* extrinsic, double* kp3d,
+                                        fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv, int32_t* nearer, int32_t* tex_pts,
+                                        int32_t* tex_nv, int32_t* status, int32_t* src_pts_rows, void* stream) {
+    pg::ClipsArgs t;
+    const int rc = pose_geometry_clips_args(t, "pose_geometry_clips", poses, cad_idxs, src_pts, vehicles, row_first, n_clips, steps, cams,
+                                            bank_kp3d, bank_v_off, bank_t_off, n_cad, H, W, J, pose, extrinsic, kp3d, jobs, vis_pts, vis_nv,
+                                            nearer, tex_pts, tex_nv, status, src_pts_rows);
+    if (rc != FUSG_OK || J == 0) return rc;
+    return fusg::plan_dispatch(pose_geometry_clips_impl, stream, t);
+}
+
+// ---- host twin: every pointer, the tables' entries included, is a HOST pointer (no GPU needed)
+extern "C" int fusg_pose_geometry_clips_host(const float* const* poses, const int64_t* const* cad_idxs, const int32_t* const* src_pts,
+                                             const int32_t* vehicles, const int32_t* row_first, int32_t n_clips, const double* steps,
+                                             const double* cams, const float* bank_kp3d, const int32_t* bank_v_off,
+                                             const int32_t* bank_t_off, int32_t n_cad, int32_t H, int32_t W, int32_t J, float* pose,
+                                             double* extrinsic, double* kp3d, fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv,
+                                             int32_t* nearer, int32_t* tex_pts, int32_t* tex_nv, int32_t* status, int32_t* src_pts_rows) {
+    pg::ClipsArgs t;
+    const int rc = pose_geometry_clips_args(t, "pose_geometry_clips_host", poses, cad_idxs, src_pts, vehicles, row_first, n_clips, steps, cams,
+                                            bank_kp3d, bank_v_off, bank_t_off, n_cad, H, W, J, pose, extrinsic, kp3d, jobs, vis_pts, vis_nv,
+                                            nearer, tex_pts, tex_nv, status, src_pts_rows);
+    if (rc != FUSG_OK) return rc;
+    for (int j = 0; j < J; ++j) pg::clips_row(t, j);
     return FUSG_OK;
 }
 

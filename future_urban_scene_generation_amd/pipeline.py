@@ -396,6 +396,47 @@ def later_geometry_batch_rows(scenes: Sequence[Dict], vehicles: Sequence[int], d
     return seeds, has
 
 
+def later_clips_geometry_batch_rows(clips: Sequence[Tuple[Sequence[Dict], Dict]], device_pose: bool, device_homography: bool,
+                                    inpaint: bool = False) -> Tuple[List[int], Optional[List[int]], bool]:
+    """What `run_later_clips_batched_geometry` checks before it issues anything, for (later_scenes, state) pairs of geometry-mode
+    clips (pure Python apart from reading the frames' shapes): `later_geometry_batch_rows`' demands clip by clip - a pipeline built
+    with device_pose=True and device_homography=True, scenes with 'steps' and without 'masks', 'steps' / 'vehicle_seeds' lists that
+    reach the state's highest first-frame index -, and over the whole list: every state is a geometry-mode one (no mix with
+    given-geometry clips), the frames have one size, and either every (clip, frame) whose clip has vehicles carries
+    'vehicle_seeds' / 'inpaint' (`inpaint`: the pipeline holds the inpainting networks - without them the key is ignored) or none
+    does.  ValueError otherwise.  Returns (vehicles per clip = the states' kept vehicles, the seeds of all rows - clip-major,
+    selected to the states' vehicles: `clip_batch_seeds` - or None, whether the pass inpaints)."""
+    what = "run_later_clips_batched_geometry"
+    if not device_pose or not device_homography:
+        raise ValueError(f"{what}: geometry-mode clips are batched only by a pipeline built with "
+                         f"device_pose=True and device_homography=True (device_pose={bool(device_pose)}, "
+                         f"device_homography={bool(device_homography)}): the batched stage is that path's arithmetic, row by row")
+    clips = [(list(scs), st) for scs, st in clips]
+    given = [c for c, (_, st) in enumerate(clips) if st.get("geometry") is None]
+    if given and len(given) < len(clips):
+        raise ValueError(f"{what}: the list mixes geometry-mode clips and given-geometry clips (given-geometry: {given})")
+    vehs = [[int(v) for v in (st.get("geometry") or {}).get("vehicles", [])] for _, st in clips]
+    for c, ((scs, _), veh) in enumerate(zip(clips, vehs)):
+        for f, sc in enumerate(scs):
+            if c in given or "masks" in sc or sc.get("steps") is None:
+                raise ValueError(f"{what}: clip {c} scene {f} is not a geometry-mode scene ('steps', no 'masks', the state of a "
+                                 "geometry-mode first frame)")
+            for k in ("steps", "vehicle_seeds"):
+                if sc.get(k) is not None and veh and len(sc[k]) <= max(veh):
+                    raise ValueError(f"{what}: clip {c} scene {f} carries {len(sc[k])} {k!r} entries, the state's "
+                                     f"vehicles reach first-frame index {max(veh)}")
+    sizes = {tuple(sc["frame"].shape) for scs, _ in clips for sc in scs}
+    if len(sizes) > 1:
+        raise ValueError(f"{what}: the frames of one call have one size, got {sorted(sizes)}")
+    vehicles = [len(veh) for veh in vehs]
+    seeds = clip_batch_seeds([[None if sc.get("vehicle_seeds") is None else [sc["vehicle_seeds"][v] for v in veh] for sc in scs]
+                              for (scs, _), veh in zip(clips, vehs)], vehicles, what)
+    live = [(c, f) for c, (scs, _) in enumerate(clips) if vehicles[c] for f in range(len(scs))]
+    has = _batch_inpaint(what, live, [clips[c][0][f].get("inpaint") if inpaint else None for c, f in live], "that has vehicles",
+                         "(clip, frame)")
+    return vehicles, seeds, has
+
+
 def frame_geometry_batch_rows(scenes: Sequence[Dict], device_pose: bool, device_homography: bool, inpaint: bool = False,
                               classifier: bool = False) -> Tuple[List[int], Optional[List[int]], bool]:
     """What `run_frames_batched_geometry` checks before it issues anything, for geometry-mode first frames ('frame', 'bboxes',
@@ -2118,7 +2159,13 @@ class VehiclePipeline:
             raise ValueError("run_later_frames_batched_geometry: the frames of a batch have one size")
         if V == 0:
             return list(self.run_later_frames(scenes, state, replay=replay))
-        # the rows' scenes: 'vehicle_seeds' and 'inpaint' list every first-frame vehicle and are selected to the state's
+        rows = self._geometry_row_scenes(scenes, veh, inpaint)
+        return [res for lo, hi in later_batch_groups(len(scenes), V, max_batch)
+                for res in self._guarded_pass(self._run_later_geometry_batch, (rows[lo:hi], state, replay), check, seeds)]
+
+    def _geometry_row_scenes(self, scenes, veh, inpaint: bool) -> list:
+        """The rows' scenes of a geometry-mode batch: 'vehicle_seeds' and 'inpaint' list every first-frame vehicle and are selected
+        to the state's vehicles `veh` (inpaint False: the key is dropped)."""
         rows = []
         for sc in scenes:
             r = dict(sc)
@@ -2129,8 +2176,28 @@ class VehiclePipeline:
             elif "inpaint" in r:
                 del r["inpaint"]
             rows.append(r)
-        return [res for lo, hi in later_batch_groups(len(scenes), V, max_batch)
-                for res in self._guarded_pass(self._run_later_geometry_batch, (rows[lo:hi], state, replay), check, seeds)]
+        return rows
+
+    def _geometry_state_device(self, gs: Dict) -> Dict:
+        """What a batched geometry stage reads of a first frame's state['geometry'], on the device: 'pose_d' float32 [V, 7],
+        'cad_idx_d' int64 [V], 'src_kp_d' int32 [V, 5, 8, 2], 'kp_nv_d' int32 [5].  A state made without device copies uploads its
+        host pose, CAD indices and corner points."""
+        import numpy as np
+
+        from . import ops
+        from . import render as rd
+        from .warp_learn import planes_utils as pu
+        dev, V = self.device, len(gs["vehicles"])
+        pose_d, cad_d = gs.get("pose_d"), gs.get("cad_idx_d")
+        if pose_d is None:
+            prow = [[p[0], *np.asarray(p[1]).reshape(3), *np.asarray(p[2]).reshape(3)] for p in gs["pose"]]
+            pose_d = ops.h2d(np.asarray(prow, np.float32).reshape(V, 7), dev)
+            cad_d = ops.h2d(np.asarray(gs["cad_idx"], np.int64).reshape(V), dev)
+        src_kp_d, kp_nv_d = gs.get("src_kp_d"), gs.get("kp_nv_d")
+        if src_kp_d is None:
+            pts, nv = pu.pack_plane_points(gs["src_kp"], len(rd.TEXTURE_PLANES))
+            src_kp_d, kp_nv_d = ops.h2d(pts, dev), ops.h2d(np.ascontiguousarray(nv[0]), dev)
+        return {"pose_d": pose_d, "cad_idx_d": cad_d, "src_kp_d": src_kp_d, "kp_nv_d": kp_nv_d}
 
     @torch.no_grad()
     def _later_geometry_stage(self, scenes, state, box_rows=None) -> Dict:
@@ -2141,7 +2208,6 @@ class VehiclePipeline:
 
         from . import ops
         from . import render as rd
-        from .warp_learn import planes_utils as pu
         gs = state["geometry"]
         F, V = len(scenes), len(gs["vehicles"])
         veh = list(gs["vehicles"])
@@ -2149,20 +2215,12 @@ class VehiclePipeline:
         K = rd.intrinsic(gs["focals"], gs["centers"])
         dev = self.device
         with torch.cuda.device(dev):
-            pose_d, cad_d = gs.get("pose_d"), gs.get("cad_idx_d")
-            if pose_d is None:
-                prow = [[p[0], *np.asarray(p[1]).reshape(3), *np.asarray(p[2]).reshape(3)] for p in gs["pose"]]
-                pose_d = ops.h2d(np.asarray(prow, np.float32).reshape(V, 7), dev)
-                cad_d = ops.h2d(np.asarray(gs["cad_idx"], np.int64).reshape(V), dev)
-            src_kp_d, kp_nv_d = gs.get("src_kp_d"), gs.get("kp_nv_d")
-            if src_kp_d is None:
-                pts, nv = pu.pack_plane_points(gs["src_kp"], len(rd.TEXTURE_PLANES))
-                src_kp_d, kp_nv_d = ops.h2d(pts, dev), ops.h2d(np.ascontiguousarray(nv[0]), dev)
+            sd = self._geometry_state_device(gs)
             src_vis_d = ops.h2d((np.asarray(gs["src_vis"]).reshape(V, -1) != 0).astype(np.uint8), dev)
-            geo = rd.later_geometry_batch_device(self.cad_bank, (H, W), cad_d, pose_d, K, [[sc["steps"][v] for v in veh] for sc in scenes],
-                                                 box_rows=box_rows)
-            geo.update(src_planes=gs["src_planes"], src_kp_d=src_kp_d.repeat(F, 1, 1, 1).contiguous(),
-                       src_vis_d=src_vis_d.repeat(F, 1).contiguous(), kp_nv_d=kp_nv_d.contiguous())
+            geo = rd.later_geometry_batch_device(self.cad_bank, (H, W), sd["cad_idx_d"], sd["pose_d"], K,
+                                                 [[sc["steps"][v] for v in veh] for sc in scenes], box_rows=box_rows)
+            geo.update(src_planes=gs["src_planes"], src_kp_d=sd["src_kp_d"].repeat(F, 1, 1, 1).contiguous(),
+                       src_vis_d=src_vis_d.repeat(F, 1).contiguous(), kp_nv_d=sd["kp_nv_d"].contiguous())
         return geo
 
     @torch.no_grad()
@@ -2172,27 +2230,30 @@ class VehiclePipeline:
         from . import ops
         gs = state["geometry"]
         veh = list(gs["vehicles"])
-        F, V = len(scenes), len(veh)
+        V = len(veh)
         inpaint = self._later_inpaint(scenes[0]) is not None
         with torch.cuda.device(self.device):
             box_rows = self._box_rows([sc["inpaint"]["boxes"] for sc in scenes]) if inpaint else None
             geo = self._later_geometry_stage(scenes, state, box_rows)
             frames = self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay, geo=geo), box_geom=box_rows)
             host = geo["host"](ops.d2h(geo["buf"]))               # the one read-back of the group, behind the queued paste
-            keys = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
-            out = []
-            for f, res in enumerate(frames):
-                sl = later_batch_slice(f, V)
-                keep = [i for i in range(V) if host["covered"][sl][i] > 0]
-                if len(keep) < V:                                 # the inert rows' network outputs are dropped
-                    idx = torch.as_tensor(keep, dtype=torch.long, device=self.device)
-                    res = {**res, **{k: res[k].index_select(0, idx) for k in keys}}
-                res["geometry"] = {"masks": geo["mask"][sl], "dst_sketch": geo["sketch"][sl], "dst_kp": host["dst_kp"][sl],
-                                   "dst_vis": host["dst_vis"][sl], "kp3d": host["kp3d"][sl]}
-                kept = [veh[i] for i in keep]
-                res["skipped"] = [v for v in range(len(scenes[f]["steps"])) if v not in kept]
-                out.append(res)
-        return out
+            return [self._geometry_cut(res, later_batch_slice(f, V), veh, scenes[f], geo, host, inpaint) for f, res in enumerate(frames)]
+
+    def _geometry_cut(self, res: Dict, sl: slice, veh, scene: Dict, geo: Dict, host: Dict, inpaint: bool) -> Dict:
+        """One frame of a batched geometry pass as `_geometry_later_frame` returns it: `res` holds the frame's rows `sl` of the
+        stacked results; the inert rows' network outputs are dropped, 'geometry' and 'skipped' come from the stage (`geo`) and
+        its read-back (`host`).  veh: the state's first-frame vehicle indices."""
+        V = len(veh)
+        keys = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
+        keep = [i for i in range(V) if host["covered"][sl][i] > 0]
+        if len(keep) < V:                                         # the inert rows' network outputs are dropped
+            idx = torch.as_tensor(keep, dtype=torch.long, device=self.device)
+            res = {**res, **{k: res[k].index_select(0, idx) for k in keys}}
+        res["geometry"] = {"masks": geo["mask"][sl], "dst_sketch": geo["sketch"][sl], "dst_kp": host["dst_kp"][sl],
+                           "dst_vis": host["dst_vis"][sl], "kp3d": host["kp3d"][sl]}
+        kept = [veh[i] for i in keep]
+        res["skipped"] = [v for v in range(len(scene["steps"])) if v not in kept]
+        return res
 
     # ------------------------------------------------------------------------------------------ first frames of several scenes
     def run_frames_batched(self, scenes, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
@@ -2615,7 +2676,8 @@ class VehiclePipeline:
         (+ 'inpaint_u8')), the keys and shapes `run_later_frames_batched` returns; tensors are views into the pass's stacked
         results.  F_c = 0 -> []; V_c = 0 -> the no-vehicle shape, the composites equal to their base; [] -> [].
         Geometry-mode states (scenes without 'masks') and sharded states (process group) go clip by clip through
-        `run_later_frames_batched` - the results of today."""
+        `run_later_frames_batched` - the results of today; `run_later_clips_batched_geometry` is the opt-in that batches
+        geometry-mode clips (this method's parameter list is pinned, so the flag lives on a sibling)."""
         what = "run_later_clips_batched"
         clips = [(list(scs), st) for scs, st in clips]
         if not clips:
@@ -2653,29 +2715,39 @@ class VehiclePipeline:
         return out
 
     @torch.no_grad()
-    def _later_clips_stages(self, clips, icn_out=None, vu_out=None) -> Dict:
+    def _later_clips_stages(self, clips, icn_out=None, vu_out=None, geo=None) -> Dict:
         """The data movement of a several-clip later pass in front of the networks, clip-major over the (scenes, state) pairs and
         frame-major inside a clip: 'warped' uint8 [N, P, H, W, 3], 'masks' uint8 [N, H, W], 'geom' int32 [N, 8], 'icn_x' [N, 21,
         R, R], 'vu_y' [N, 3, R, R] for the N = sum(F_c * V_c) rows (icn_out / vu_out: the N real rows of a padded or recorded
         pass's buffers, written in place).  Every row holds the bytes `_later_batch_stages` builds for its clip: a clip without
-        frames or without vehicles contributes no row.  At least one row."""
+        frames or without vehicles contributes no row.  At least one row.  geo (geometry mode, `_later_clips_geometry_stage`): the
+        masks, sketches, corner points and gated visibilities come from the device stage, the planes from the states."""
         from .warp_learn import planes_utils as pu
         live = [(list(scs), st) for scs, st in clips if len(scs) and int(st["central"].shape[0])]
         scenes = [sc for scs, _ in live for sc in scs]
         with torch.cuda.device(self.device):
-            planes = [scs[0]["src_planes"].contiguous() for scs, _ in live]       # by pointer: each clip's planes stay where they are
             counts = [len(scs) for scs, _ in live]
-            fit = self._later_fits(scenes)
-            warped = pu.warp_planes_clips_fitted(planes, counts, *fit) if self.device_homography else \
-                pu.warp_planes_clips_batch(planes, counts, fit)                                # :376-381
-            masks, sketch = self._cat_rows(scenes, "masks"), self._cat_rows(scenes, "dst_sketch")
+            if geo is not None:
+                planes = [st["geometry"]["src_planes"].contiguous() for _, st in live]    # by pointer, as below
+                minv, index = pu.plane_homographies_device(geo["src_kp_d"], geo["tex_pts_d"], geo["src_vis_d"], geo["dst_vis_d"],
+                                                           nverts=geo["kp_nv_d"])
+                warped = pu.warp_planes_clips_fitted(planes, counts, minv, index)              # :376-381
+                masks, sketch = geo["mask"], geo["sketch"]
+            else:
+                planes = [scs[0]["src_planes"].contiguous() for scs, _ in live]   # by pointer: each clip's planes stay where they are
+                fit = self._later_fits(scenes)
+                warped = pu.warp_planes_clips_fitted(planes, counts, *fit) if self.device_homography else \
+                    pu.warp_planes_clips_batch(planes, counts, fit)                            # :376-381
+                masks, sketch = self._cat_rows(scenes, "masks"), self._cat_rows(scenes, "dst_sketch")
             return self._later_inputs(warped, masks, sketch, [(st["central"], len(scs)) for scs, st in live], scenes[0]["frame"],
                                       icn_out, vu_out)
 
     @torch.no_grad()
-    def _run_later_clips(self, clips, replay=False, rows=None) -> list:
+    def _run_later_clips(self, clips, replay=False, rows=None, geometry=False) -> list:
         """One group of `run_later_clips_batched`: one list of `run_later_frame` dicts per clip.  rows: the row count the networks
-        run at (>= N, the padding rows zero); None: N."""
+        run at (>= N, the padding rows zero); None: N.  geometry: a group of `run_later_clips_batched_geometry` - the clips' scenes
+        carry 'steps' instead of masks, sketches and corner points, which come from the device stage
+        (`_later_clips_geometry_stage`), the results are `_geometry_later_frame`'s, cut after the stage's ONE read-back."""
         from . import ops
         from .warp_learn import planes_utils as pu
         dev, R = self.device, 256
@@ -2683,8 +2755,10 @@ class VehiclePipeline:
         vehicles = [int(st["central"].shape[0]) for _, st in clips]
         offs = clip_batch_offsets(frames, vehicles)
         N = offs[-1]
+        # (a geometry-mode scene of a clip without vehicles: the per-frame path, which launches nothing for it)
+        empty = (lambda sc, st: self._geometry_later_frame(sc, st, None, False)) if geometry else self._run_later_frame
         if N == 0:
-            return [[self._run_later_frame(sc, st) for sc in scs] for scs, st in clips]
+            return [[empty(sc, st) for sc in scs] for scs, st in clips]
         B = N if rows is None else max(int(rows), N)
         scenes = [sc for scs, _ in clips for sc in scs]                           # the (clip, frame) frames, in order
         frame_rows = clip_batch_frame_rows(frames, vehicles)
@@ -2703,11 +2777,14 @@ class VehiclePipeline:
                 return parts[0] if len(parts) == 1 else torch.cat(parts)
 
             ec, ec_join = self._inpaint_inputs_rows(scenes, frame_rows, B, tgt) if inpaint else (None, None)
+            # geometry mode: the box rows are uploaded in front of the stage, whose gate zeroes the rows of empty renders
+            box_rows = self._box_rows([sc["inpaint"]["boxes"] for scs, _ in live for sc in scs]) if inpaint and geometry else None
+            geo = self._later_clips_geometry_stage(live, box_rows) if geometry else None
             if B > N or tgt:
                 (icn_x, icn_rows), (vu_y, vu_rows) = buf("icn_x", 21), buf("vu_y", 3)
-                st = self._later_clips_stages(clips, icn_out=icn_rows, vu_out=vu_rows)
+                st = self._later_clips_stages(clips, icn_out=icn_rows, vu_out=vu_rows, geo=geo)
             else:
-                st = self._later_clips_stages(clips)
+                st = self._later_clips_stages(clips, geo=geo)
                 icn_x, vu_y = st["icn_x"], st["vu_y"]
             geom, masks = st["geom"], st["masks"]
             nets_in = {"icn_x": icn_x, "vu_y": vu_y, "app0": per_row(0), "app1": per_row(1)}
@@ -2717,24 +2794,111 @@ class VehiclePipeline:
             out = self._nets_pass(self._later_nets, pkey, replay, nets_in, seeds, N)
             # ---- one ragged paste per composite over all (clip, frame) frames
             bases = [self._paste_base(sc) for sc in scenes]
+            if inpaint and not geometry:
+                box_rows = self._box_rows([sc["inpaint"]["boxes"] for scs, _ in live for sc in scs])
             comp = self._composites(lambda crops, **box: pu.paste_back_ragged_device(bases, frame_rows, crops, geom, masks, **box), out,
-                                    self._box_rows([sc["inpaint"]["boxes"] for scs, _ in live for sc in scs]) if inpaint else None)
+                                    box_rows if inpaint else None)
+            # geometry mode: the one read-back of the group, behind the queued paste
+            host = geo["host"](ops.d2h(geo["buf"])) if geometry else None
         keys = ("icn_u8", "vunet_u8") + (("inpaint_u8",) if inpaint else ())
         res, k0 = [], 0
-        for c, (scs, _) in enumerate(clips):
+        for c, (scs, cst) in enumerate(clips):
             one = []
             for f, sc in enumerate(scs):
-                if vehicles[c] == 0:
+                if vehicles[c] == 0 and geometry:
+                    o = empty(sc, cst)
+                elif vehicles[c] == 0:
                     o = self._no_vehicles(R, "icn_u8", "vunet_u8", "geom", *(("inpaint_u8",) if self._later_inpaint(sc) is not None else ()))
                 else:
                     sl = slice(frame_rows[k0 + f], frame_rows[k0 + f + 1])
                     o = {k: out[k][sl] for k in keys}
                     o["geom"] = geom[sl]
                 o["frame_icn"], o["frame_vunet"] = comp["frame_icn"][k0 + f], comp["frame_vunet"][k0 + f]
+                if vehicles[c] and geometry:
+                    o = self._geometry_cut(o, sl, list(cst["geometry"]["vehicles"]), sc, geo, host, inpaint)
                 one.append(o)
             k0 += len(scs)
             res.append(one)
         return res
+
+    # ---- the same for geometry-mode clips: the render, the visibilities and the skip rule of ALL clips' rows stay on the device
+    def run_later_clips_batched_geometry(self, clips, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
+                                         pad: Optional[bool] = None, batch_geometry: bool = True) -> list:
+        """`run_later_clips_batched` that also batches GEOMETRY-MODE clips (states of geometry-mode first frames, scenes with
+        'steps' and no 'masks'; batch_geometry=False: exactly `run_later_clips_batched`, which takes such clips one by one).  Clip
+        by clip a geometry-mode video pays one pass of ~300 dependent launches at 5-10 rows and one blocking read-back per clip;
+        here a group of `clip_batch_groups` over (F_c, V_c = the state's kept vehicles) is queued whole before anything is read:
+        `render.later_geometry_clips_device` (ONE upload of every clip's steps, camera and source visibilities ->
+        fusg_pose_geometry_clips, each clip's pose table, CAD indices and source corner points passed by pointer ->
+        fusg_render_normals_u8 -> fusg_plane_visibility -> fusg_later_gate, once each for all rows) ->
+        `plane_homographies_device` over all rows -> the several-clip plane warp, each clip's state['geometry']['src_planes']
+        passed by pointer -> crop rows and both networks' inputs -> `_later_nets` once at N or the padded rows -> Lab -> BGR -> one
+        ragged paste per composite with the gated box rows; then ONE `ops.d2h` of the stage's small packed buffer, from which the
+        per-(clip, frame) results are cut.  Rows are clip-major, frame-major inside a clip (`clip_batch_offsets`).
+        A vehicle whose render is empty stays in the batch as an INERT row, exactly as in `run_later_frames_batched_geometry`;
+        'vehicle_seeds' and 'inpaint' list every first-frame vehicle, like 'steps', and are selected to the state's vehicles;
+        either every (clip, frame) whose clip has vehicles carries them or none does.  Needs a pipeline built with
+        device_pose=True and device_homography=True; all frames of a call have one size; every clip may have its own camera
+        (state['geometry'] 'focals' / 'centers').  All of this is a ValueError before anything is launched
+        (`later_clips_geometry_batch_rows`).  A state made without device copies uploads its host pose, CAD indices and corner
+        points once per call.
+        max_batch, pad, replay, check: `run_later_clips_batched`'s; the plan of replay=True is the ("later_rows", padded_rows,
+        precision[, "inpaint"]) plan a given-geometry group of that shape records - they share it.  A clip that alone exceeds a
+        bound goes through `run_later_frames_batched_geometry` (which splits it by frames).  Sharded states (process group) keep
+        going clip by clip; a given-geometry list ignores the flag.
+        Memory per row at H x W: 19 * H * W bytes (sketch 3, mask 1, warped planes 15) - 17.5 MB at 720 x 1280, 1.1 GB for 64 rows.
+        Returns one list per clip of `run_later_frames_batched_geometry`'s dicts ('icn_u8', 'vunet_u8', 'geom' (+ 'inpaint_u8') of
+        the kept vehicles, 'frame_icn', 'frame_vunet', 'geometry', 'skipped'); F_c = 0 -> []; V_c = 0 -> the no-vehicle shape."""
+        clips = [(list(scs), st) for scs, st in clips]
+        geo = [any(self._is_geometry(sc, st) for sc in scs) for scs, st in clips]
+        sharded = not _one_rank(self.group) and any(st.get("sharded") for _, st in clips)
+        if not batch_geometry or not any(geo) or sharded:
+            return self.run_later_clips_batched(clips, replay=replay, check=check, max_batch=max_batch, pad=pad)
+        vehicles, seeds, inpaint = later_clips_geometry_batch_rows(clips, self.device_pose, self.device_homography, self.inpaint)
+        frames = [len(scs) for scs, _ in clips]
+        for c, ((_, st), V) in enumerate(zip(clips, vehicles)):
+            if int(st["central"].shape[0]) != V:
+                raise ValueError(f"run_later_clips_batched_geometry: the state of clip {c} holds {int(st['central'].shape[0])} crops "
+                                 f"for {V} vehicles")
+        rows = [(self._geometry_row_scenes(scs, list(st["geometry"]["vehicles"]), inpaint), st) for scs, st in clips]
+        max_batch, pad = _pad_defaults(replay, max_batch, pad)
+        out = []
+        for lo, hi, oversized in clip_batch_groups(frames, vehicles, max_batch):
+            if oversized:                                         # more rows or frames than a pass takes: the one-clip path splits by frames
+                out.append(self._later_frames_batched(clips[lo][0], clips[lo][1], replay, check, max_batch, True))
+                continue
+            n = frame_batch_pad(sum(f * v for f, v in zip(frames[lo:hi], vehicles[lo:hi])), max_batch) if pad else None
+            out.extend(self._guarded_pass(self._run_later_clips, (rows[lo:hi], replay, n, True), check, seeds))
+        return out
+
+    @torch.no_grad()
+    def _later_clips_geometry_stage(self, live, box_rows=None) -> Dict:
+        """The device geometry of a group of geometry-mode clip tails (`render.later_geometry_clips_device`): live = the (scenes,
+        state) pairs that own rows, in order.  Nothing is read back."""
+        from . import render as rd
+        clips = []
+        for scs, st in live:
+            gs = st["geometry"]
+            veh = list(gs["vehicles"])
+            sd = self._geometry_state_device(gs)
+            clips.append({"cad_idx_d": sd["cad_idx_d"].contiguous(), "pose_d": sd["pose_d"].to(torch.float32).reshape(len(veh), 7).contiguous(),
+                          "src_kp_d": sd["src_kp_d"].contiguous(), "src_vis": gs["src_vis"], "cad_idx": gs["cad_idx"],
+                          "K": rd.intrinsic(gs["focals"], gs["centers"]),
+                          "steps_per_frame": [[sc["steps"][v] for v in veh] for sc in scs]})
+        frame = live[0][0][0]["frame"]
+        return rd.later_geometry_clips_device(self.cad_bank, (int(frame.shape[0]), int(frame.shape[1])), clips, box_rows=box_rows)
+
+    def run_clips_batched_geometry(self, clips, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
+                                   pad: Optional[bool] = None, batch_geometry: bool = True) -> list:
+        """`run_clips_batched` for geometry-mode clips: clips is a sequence of (first_scene, later_scenes) pairs; the first frames
+        go through `run_frames_batched_geometry`, all tails through `run_later_clips_batched_geometry` with the states it
+        returned (batch_geometry: both methods' flag).  Returns, per clip, [first_result, later_results...]."""
+        clips = [(first, list(later)) for first, later in clips]
+        firsts = self.run_frames_batched_geometry([first for first, _ in clips], replay=replay, check=check, max_batch=max_batch, pad=pad,
+                                                  batch_geometry=batch_geometry)
+        tails = self.run_later_clips_batched_geometry([(later, f["state"]) for (_, later), f in zip(clips, firsts)], replay=replay,
+                                                      check=check, max_batch=max_batch, pad=pad, batch_geometry=batch_geometry)
+        return [[f] + t for f, t in zip(firsts, tails)]
 
     def run_clips_batched(self, clips, replay: bool = False, check: Optional[str] = "sync", max_batch: Optional[int] = None,
                           pad: Optional[bool] = None) -> list:

@@ -543,14 +543,19 @@ _PG_OUT = (("jobs", np.uint8, JOB_DTYPE.itemsize), ("extrinsic", np.float64, 12)
 _PG_CALL = ("pose", "extrinsic", "kp3d", "jobs", "vis_pts", "vis_nv", "nearer", "tex_pts", "tex_nv", "status")   # the ABI's order
 
 
-def _pg_layout(V: int, extra=()) -> Tuple[Dict[str, Tuple[int, np.dtype, int]], int]:
-    """One buffer for every small per-vehicle array: name -> (byte offset, dtype, elements); each part 8-byte aligned."""
+def _pack_layout(parts) -> Tuple[Dict[str, Tuple[int, np.dtype, int]], int]:
+    """One buffer for several small arrays, parts = (name, dtype, elements): name -> (byte offset, dtype, elements) and the
+    buffer's bytes; each part 8-byte aligned."""
     lay, off = {}, 0
-    for name, dt, per in tuple(_PG_OUT) + tuple(extra):
-        n = V * per
+    for name, dt, n in parts:
         lay[name] = (off, np.dtype(dt), n)
         off += (n * np.dtype(dt).itemsize + 7) // 8 * 8
     return lay, off
+
+
+def _pg_layout(V: int, extra=()) -> Tuple[Dict[str, Tuple[int, np.dtype, int]], int]:
+    """One buffer for every small per-vehicle array: name -> (byte offset, dtype, elements); each part 8-byte aligned."""
+    return _pack_layout((name, dt, V * per) for name, dt, per in tuple(_PG_OUT) + tuple(extra))
 
 
 def pose_geometry_host(bank: CadBank, cad_idx, K: np.ndarray, frame_hw: Tuple[int, int], raw=None, kp_xy=None, pose=None,
@@ -575,6 +580,42 @@ def pose_geometry_host(bank: CadBank, cad_idx, K: np.ndarray, frame_hw: Tuple[in
               "nearer": (V, 7), "tex_pts": (V, len(_TEX_IDX), pu.MAX_VERTS, 2), "tex_nv": (V, len(_TEX_IDX)), "status": (V,)}
     res = {k: out[k].reshape(sh) for k, sh in shapes.items()}
     res["jobs"] = out["jobs"].view(JOB_DTYPE)
+    return res
+
+
+_PG_SHAPES = {"extrinsic": (12,), "kp3d": (12, 3), "pose": (7,), "vis_pts": (7, pu.MAX_VERTS, 2), "vis_nv": (7,), "nearer": (7,),
+              "tex_pts": (len(_TEX_IDX), pu.MAX_VERTS, 2), "tex_nv": (len(_TEX_IDX),), "status": ()}
+
+
+def pose_geometry_clips_host(bank: CadBank, frame_hw: Tuple[int, int], clips: Sequence[Dict]) -> Dict[str, np.ndarray]:
+    """fusg_pose_geometry_clips_host: the several-clip later-frame stage's per-row arithmetic on the CPU (no GPU needed), numpy in
+    and out.  clips[c] = {'pose' [V_c, 7], 'cad_idx' [V_c], 'src_pts' int32 [V_c, 5, 8, 2], 'K' 3 x 3, 'steps' [F_c * V_c, 4] (frame-
+    major)}; rows clip-major.  Returns fusg_pose_geometry's outputs by name at J = sum(F_c * V_c) rows ('jobs' as JOB_DTYPE) and
+    'src_pts_rows' int32 [J, 5, 8, 2]."""
+    import ctypes as C
+    H, W = frame_hw
+    n, P = len(clips), len(_TEX_IDX)
+    pose = [np.ascontiguousarray(np.asarray(cl["pose"], np.float32).reshape(-1, 7)) for cl in clips]
+    cad = [np.ascontiguousarray(np.asarray(cl["cad_idx"], np.int64).reshape(-1)) for cl in clips]
+    pts = [np.ascontiguousarray(np.asarray(cl["src_pts"], np.int32).reshape(-1, P, pu.MAX_VERTS, 2)) for cl in clips]
+    steps = [np.asarray(cl["steps"], np.float64).reshape(-1, 4) for cl in clips]
+    first = [0]
+    for s in steps:
+        first.append(first[-1] + s.shape[0])
+    J = first[-1]
+    steps_all = np.ascontiguousarray(np.concatenate(steps)) if n else np.zeros((0, 4))
+    cams = np.ascontiguousarray(np.concatenate([np.asarray(cl["K"], np.float64).reshape(9) for cl in clips])) if n else np.zeros(0)
+    tabs = [np.ascontiguousarray(bank.kp3d, dtype=np.float32), bank.v_off.astype(np.int32), bank.t_off.astype(np.int32)]
+    out = {name: np.zeros(J * per, dt) for name, dt, per in _PG_OUT}
+    rows = np.zeros((J, P, pu.MAX_VERTS, 2), np.int32)
+    tab = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])     # noqa: E731
+    L.check(L.lib().fusg_pose_geometry_clips_host(tab(pose), tab(cad), tab(pts), (C.c_int32 * max(n, 1))(*[len(a) for a in cad]),
+                                                  (C.c_int32 * (n + 1))(*first), n, steps_all.ctypes.data, cams.ctypes.data,
+                                                  *(a.ctypes.data for a in tabs), len(bank), H, W, J,
+                                                  *(out[k].ctypes.data for k in _PG_CALL), rows.ctypes.data), "pose_geometry_clips_host")
+    res = {k: out[k].reshape((J,) + sh) for k, sh in _PG_SHAPES.items()}
+    res["jobs"] = out["jobs"].view(JOB_DTYPE)
+    res["src_pts_rows"] = rows
     return res
 
 
@@ -631,11 +672,8 @@ def _device_stage(bank: CadBank, frame_hw: Tuple[int, int], dev, cad_idx_d: torc
     H, W = frame_hw
     V = int(cad_idx_d.shape[0])
     first = steps_d is None and pose_d is None
-    lay, nbytes = _pg_layout(V, _STAGE_EXTRA + tuple(extra))
-    buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    d = {k: buf[o:o + n * dt.itemsize].view(_TORCH_DT[dt]) for k, (o, dt, n) in lay.items()}
-    r = {"sketch": torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev),
-         "mask": torch.zeros((V, H, W), dtype=torch.uint8, device=dev)}
+    st = _stage_buffers(V, frame_hw, dev, extra)
+    d = st["d"]
     if V:
         if cad_idx_d.dtype != torch.int64 or not cad_idx_d.is_cuda:
             raise ValueError("vehicle_geometry_device: cad_idx_d is a CUDA int64 [V]")
@@ -656,15 +694,52 @@ def _device_stage(bank: CadBank, frame_hw: Tuple[int, int], dev, cad_idx_d: torc
                                            arr["t_off"].data_ptr(), len(bank), Kc.ctypes.data, H, W, hi - lo,
                                            *(d[k].data_ptr() + lo * per[k] * d[k].element_size() for k in _PG_CALL), ops.stream_ptr()),
                     "pose_geometry")
-        max_nv = bank.max_nv
-        ws = torch.empty((V * (16 + 40 * max_nv) + 15) // 16 * 2, dtype=torch.float64, device=dev)
-        L.check(lib.fusg_render_normals_u8(arr["verts"].data_ptr(), arr["normals"].data_ptr(), arr["verts"].shape[0],
-                                           arr["tris"].data_ptr(), arr["tris"].shape[0], d["jobs"].data_ptr(), V, max_nv, H, W,
-                                           ws.data_ptr(), ws.numel() * 8, r["sketch"].data_ptr(), r["mask"].data_ptr(), None,
-                                           d["covered"].data_ptr(), ops.stream_ptr()), "render_normals_u8")
-        L.check(lib.fusg_plane_visibility(d["vis_pts"].data_ptr(), d["vis_nv"].data_ptr(), d["nearer"].data_ptr(), V, H, W,
-                                          d["counts"].data_ptr(), ops.stream_ptr()), "plane_visibility")
+        _stage_render(bank, st, frame_hw, dev)
+    return st
+
+
+def _stage_buffers(V: int, frame_hw: Tuple[int, int], dev, extra=()) -> Dict:
+    """The buffers of a device stage of V rows, zeroed: `_device_stage`'s result before anything is launched."""
+    H, W = frame_hw
+    lay, nbytes = _pg_layout(V, _STAGE_EXTRA + tuple(extra))
+    buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    d = {k: buf[o:o + n * dt.itemsize].view(_TORCH_DT[dt]) for k, (o, dt, n) in lay.items()}
+    r = {"sketch": torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev),
+         "mask": torch.zeros((V, H, W), dtype=torch.uint8, device=dev)}
     return {"lay": lay, "nbytes": nbytes, "buf": buf, "d": d, "r": r, "V": V}
+
+
+def _stage_render(bank: CadBank, st: Dict, frame_hw: Tuple[int, int], dev) -> None:
+    """What follows the pose geometry in every device stage, for the V > 0 rows of `st` (`_stage_buffers`, its jobs and visibility
+    polygons written): fusg_render_normals_u8 of the device jobs -> fusg_plane_visibility, on the current stream."""
+    H, W = frame_hw
+    V, d, r = st["V"], st["d"], st["r"]
+    arr, lib = bank.device_arrays(dev), L.lib()
+    max_nv = bank.max_nv
+    ws = torch.empty((V * (16 + 40 * max_nv) + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    L.check(lib.fusg_render_normals_u8(arr["verts"].data_ptr(), arr["normals"].data_ptr(), arr["verts"].shape[0],
+                                       arr["tris"].data_ptr(), arr["tris"].shape[0], d["jobs"].data_ptr(), V, max_nv, H, W,
+                                       ws.data_ptr(), ws.numel() * 8, r["sketch"].data_ptr(), r["mask"].data_ptr(), None,
+                                       d["covered"].data_ptr(), ops.stream_ptr()), "render_normals_u8")
+    L.check(lib.fusg_plane_visibility(d["vis_pts"].data_ptr(), d["vis_nv"].data_ptr(), d["nearer"].data_ptr(), V, H, W,
+                                      d["counts"].data_ptr(), ops.stream_ptr()), "plane_visibility")
+
+
+def _stage_gate(st: Dict, box_rows: Optional[torch.Tensor]) -> None:
+    """fusg_later_gate over the V > 0 rows of a stage made with the extras 'dst_vis' and 'valid' (box_rows: zeroed in place where
+    the render is empty)."""
+    d = st["d"]
+    L.check(L.lib().fusg_later_gate(d["counts"].data_ptr(), d["covered"].data_ptr(), st["V"], len(TEXTURE_PLANES), d["dst_vis"].data_ptr(),
+                                    d["valid"].data_ptr(), None if box_rows is None else box_rows.data_ptr(), ops.stream_ptr()),
+            "later_gate")
+
+
+def _stage_host_valid(bank: CadBank, st: Dict, read: np.ndarray, planes: Optional[torch.Tensor], first: bool) -> Dict:
+    """`_device_stage_result` of a gated stage's read-back bytes plus 'valid' (host int32 [V])."""
+    out = _device_stage_result(bank, st, read, planes, first)
+    o, dt, n = st["lay"]["valid"]
+    out["valid"] = read[o:o + n * dt.itemsize].view(dt).copy()
+    return out
 
 
 def _device_stage_result(bank: CadBank, st: Dict, host: np.ndarray, planes: Optional[torch.Tensor], first: bool) -> Dict:
@@ -716,20 +791,95 @@ def later_geometry_batch_device(bank: CadBank, frame_hw: Tuple[int, int], cad_id
         steps_d = ops.h2d(np.concatenate([steps_array(s) for s in steps_per_frame]).reshape(N, 4), dev) if N else None
         st = _device_stage(bank, (H, W), dev, cad_idx_d.repeat(F), K, pose_d=pose_d.to(torch.float32).reshape(V, 7).repeat(F, 1),
                            steps_d=steps_d, extra=(("dst_vis", np.uint8, P), ("valid", np.int32, 1)))
-        d = st["d"]
         if N:
-            L.check(L.lib().fusg_later_gate(d["counts"].data_ptr(), d["covered"].data_ptr(), N, P, d["dst_vis"].data_ptr(),
-                                            d["valid"].data_ptr(), None if box_rows is None else box_rows.data_ptr(),
-                                            ops.stream_ptr()), "later_gate")
+            _stage_gate(st, box_rows)
+    return _later_stage_result(st, lambda read: _stage_host_valid(bank, st, read, None, False))
 
-    def host(read: np.ndarray) -> Dict:
-        out = _device_stage_result(bank, st, read, None, False)
-        o, dt, n = st["lay"]["valid"]
-        out["valid"] = read[o:o + n * dt.itemsize].view(dt).copy()
-        return out
 
+def _later_stage_result(st: Dict, host) -> Dict:
+    """What a gated later-frame stage of N rows hands its driver: `later_geometry_batch_device`'s keys."""
+    d, N, P = st["d"], st["V"], len(TEXTURE_PLANES)
     return {"mask": st["r"]["mask"], "sketch": st["r"]["sketch"], "tex_pts_d": d["tex_pts"].view(N, P, pu.MAX_VERTS, 2),
             "tex_nv_d": d["tex_nv"][:P], "dst_vis_d": d["dst_vis"].view(N, P), "valid_d": d["valid"], "buf": st["buf"], "host": host}
+
+
+def later_geometry_clips_device(bank: CadBank, frame_hw: Tuple[int, int], clips: Sequence[Dict],
+                                box_rows: Optional[torch.Tensor] = None) -> Dict:
+    """`later_geometry_batch_device` for the future frames of SEVERAL clips at once: J = sum(F_c * V_c) rows, clip-major and
+    frame-major inside a clip (row `pipeline.clip_batch_offsets`[c] + f * V_c + v = clip c, frame f, vehicle v).  clips[c] =
+    {'cad_idx_d' CUDA int64 [V_c], 'pose_d' CUDA float32 [V_c, 7], 'src_kp_d' CUDA int32 [V_c, 5, 8, 2] (the first frame's
+    corner points), 'src_vis' host [V_c, 5], 'K' the clip's 3 x 3 intrinsics (host), 'steps_per_frame' [F_c][V_c] of (theta, tr);
+    optional 'cad_idx' host int64 [V_c], what the host result reports (without it the device copy is read when 'host' is called)}.
+    At most `_lib.MAX_FRAMES` clips.  Nothing per clip is repeated or concatenated on the device: each clip's tables are passed
+    by pointer (fusg_pose_geometry_clips), and ONE upload carries everything the host knows - the steps of all rows, the
+    cameras, the source visibilities repeated per frame (`_pack_layout`).  Order of work, all on the current stream: that upload
+    -> fusg_pose_geometry_clips -> fusg_render_normals_u8 -> fusg_plane_visibility -> fusg_later_gate, once each at J rows;
+    nothing is read back.  box_rows: CUDA int32 [J, 8] paste box rows, zeroed in place where the render is empty.
+    Returns `later_geometry_batch_device`'s keys at J rows, and 'src_kp_d' int32 [J, 5, 8, 2] (each row's source corner points,
+    written by the same launch), 'src_vis_d' uint8 [J, 5] and 'kp_nv_d' int32 [5] as `plane_homographies_device` takes them."""
+    import ctypes as C
+    H, W = frame_hw
+    clips = list(clips)
+    n, P = len(clips), len(TEXTURE_PLANES)
+    if not 1 <= n <= L.MAX_FRAMES:
+        raise ValueError(f"later_geometry_clips_device: {n} clips (1..{L.MAX_FRAMES} per launch)")
+    dev = clips[0]["cad_idx_d"].device
+    veh, first, steps, vis = [], [0], [], []
+    for c, cl in enumerate(clips):
+        V = int(cl["cad_idx_d"].shape[0])
+        if any(len(s) != V for s in cl["steps_per_frame"]):
+            raise ValueError(f"later_geometry_clips_device: every frame of clip {c} carries (theta, tr) for its {V} vehicles")
+        for k, dt, sh in (("cad_idx_d", torch.int64, (V,)), ("pose_d", torch.float32, (V, 7)), ("src_kp_d", torch.int32, (V, P, pu.MAX_VERTS, 2))):
+            t = cl[k]
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == dt and tuple(t.shape) == sh and t.is_contiguous()):
+                raise ValueError(f"later_geometry_clips_device: clip {c}'s {k!r} is a contiguous CUDA {dt} {list(sh)} (it is passed "
+                                 "by pointer, not copied)")
+        F = len(cl["steps_per_frame"])
+        veh.append(V)
+        first.append(first[-1] + F * V)
+        if F * V:
+            steps.extend(steps_array(s) for s in cl["steps_per_frame"])
+            vis.append(np.tile((np.asarray(cl["src_vis"]).reshape(V, P) != 0).astype(np.uint8), (F, 1)))
+    J = first[-1]
+    if box_rows is not None and (not box_rows.is_cuda or box_rows.dtype != torch.int32 or tuple(box_rows.shape) != (J, 8)
+                                 or not box_rows.is_contiguous()):
+        raise ValueError("later_geometry_clips_device: box_rows is a contiguous CUDA int32 [J, 8]")
+    with torch.cuda.device(dev):
+        st = _stage_buffers(J, frame_hw, dev, (("dst_vis", np.uint8, P), ("valid", np.int32, 1), ("src_pts", np.int32, P * pu.MAX_VERTS * 2)))
+        d = st["d"]
+        up_lay, up_bytes = _pack_layout((("steps", np.float64, J * 4), ("cams", np.float64, n * 9), ("src_vis", np.uint8, J * P)))
+        up = {}
+        if J:
+            blob = np.zeros(up_bytes, np.uint8)
+            part = lambda k: blob[up_lay[k][0]:up_lay[k][0] + up_lay[k][2] * up_lay[k][1].itemsize].view(up_lay[k][1])   # noqa: E731
+            part("steps")[:] = np.concatenate(steps).reshape(-1)
+            part("cams")[:] = np.concatenate([np.asarray(cl["K"], np.float64).reshape(9) for cl in clips])
+            part("src_vis")[:] = np.concatenate(vis).reshape(-1)
+            blob_d = ops.h2d(blob, dev)                               # the one upload of the call
+            up = {k: blob_d[o:o + m * dt.itemsize].view(_TORCH_DT[dt]) for k, (o, dt, m) in up_lay.items()}
+            arr = bank.device_arrays(dev)
+            live = [first[c + 1] > first[c] for c in range(n)]
+            tab = lambda k: (C.c_void_p * n)(*[cl[k].data_ptr() if own else None for cl, own in zip(clips, live)])   # noqa: E731
+            L.check(L.lib().fusg_pose_geometry_clips(tab("pose_d"), tab("cad_idx_d"), tab("src_kp_d"), (C.c_int32 * n)(*veh),
+                                                     (C.c_int32 * (n + 1))(*first), n, up["steps"].data_ptr(), up["cams"].data_ptr(),
+                                                     arr["kp3d"].data_ptr(), arr["v_off"].data_ptr(), arr["t_off"].data_ptr(), len(bank),
+                                                     H, W, J, *(d[k].data_ptr() for k in _PG_CALL), d["src_pts"].data_ptr(),
+                                                     ops.stream_ptr()), "pose_geometry_clips")
+            _stage_render(bank, st, frame_hw, dev)
+            _stage_gate(st, box_rows)
+
+    def host(read: np.ndarray) -> Dict:
+        o, dt, m = st["lay"]["cad_idx"]                             # (the launch reads each clip's own table: the buffer's rows are filled here)
+        read = read.copy()
+        rows = [np.tile(np.asarray(cl["cad_idx"] if cl.get("cad_idx") is not None else ops.d2h(cl["cad_idx_d"]), np.int64).reshape(-1),
+                        len(cl["steps_per_frame"])) for cl in clips]
+        read[o:o + m * dt.itemsize].view(dt)[:] = np.concatenate(rows)
+        return _stage_host_valid(bank, st, read, None, False)
+
+    out = _later_stage_result(st, host)
+    out.update(src_kp_d=d["src_pts"].view(J, P, pu.MAX_VERTS, 2), src_vis_d=up["src_vis"].view(J, P) if J else d["dst_vis"].view(J, P),
+               kp_nv_d=d["tex_nv"][:P])
+    return out
 
 
 def camera_runs(Ks: Sequence[np.ndarray], offs: Sequence[int]) -> List[Tuple[int, int, np.ndarray]]:
@@ -779,16 +929,11 @@ def first_geometry_batch_device(bank: CadBank, frames: Sequence[torch.Tensor], o
                            extra=(("dst_vis", np.uint8, P), ("valid", np.int32, 1)), K_runs=runs)
         d = st["d"]
         if N:
-            L.check(L.lib().fusg_later_gate(d["counts"].data_ptr(), d["covered"].data_ptr(), N, P, d["dst_vis"].data_ptr(),
-                                            d["valid"].data_ptr(), None if box_rows is None else box_rows.data_ptr(),
-                                            ops.stream_ptr()), "later_gate")
+            _stage_gate(st, box_rows)
             pu.fill_planes_frames(frames, offs, d["tex_pts"], d["tex_nv"], planes)
 
     def host(read: np.ndarray) -> Dict:
-        out = _device_stage_result(bank, st, read, planes, True)
-        o, dt, n = st["lay"]["valid"]
-        out["valid"] = read[o:o + n * dt.itemsize].view(dt).copy()
-        return out
+        return _stage_host_valid(bank, st, read, planes, True)
 
     return {"mask": st["r"]["mask"], "sketch": st["r"]["sketch"], "planes": planes, "tex_pts_d": d["tex_pts"].view(N, P, pu.MAX_VERTS, 2),
             "tex_nv_d": d["tex_nv"][:P] if N else d["tex_nv"], "vis_d": d["dst_vis"].view(N, P), "valid_d": d["valid"],

@@ -691,6 +691,34 @@ int fusg_pose_geometry_host(const float* rvec, const float* tvec, const float* e
                             double* extrinsic, double* kp3d, fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv,
                             int32_t* nearer, int32_t* tex_pts, int32_t* tex_nv, int32_t* status);
 
+/* The later-frame branch of fusg_pose_geometry for J rows of SEVERAL clips in ONE launch (VehiclePipeline.
+ * run_later_clips_batched_geometry; new entry points, FUSG_VERSION stays 118).  Rows are clip-major, frame-major inside a clip: row
+ * row_first[c] + f * vehicles[c] + v is clip c, frame f, vehicle v.  Five HOST tables, read and checked before the call returns and
+ * handed to the kernel by value: poses[c] = DEVICE float32 [V_c][7] (a first frame's `pose`), cad_idxs[c] = DEVICE int64 [V_c],
+ * src_pts[c] = DEVICE int32 [V_c][5][8][2] (the first frame's texture-plane corner points), vehicles[c] = V_c, row_first = n_clips + 1
+ * non-decreasing offsets from 0 to J - clip c owns a multiple of V_c rows, 0 where V_c is 0.  DEVICE inputs: steps double [J][4] =
+ * (theta, tr) per row, cams double [n_clips][9] = the row-major intrinsics of each clip's camera (in device memory: the tables
+ * already take 2.3 KB of the 4 KB kernel-argument space), the bank as above.
+ * DEVICE outputs: those of fusg_pose_geometry at J rows, and src_pts_rows int32 [J][5][8][2] = each row's source corner points
+ * copied from its clip's table - the src_pts of fusg_plane_homographies for all rows.  A row is bit for bit what fusg_pose_geometry
+ * gives for that vehicle with its clip's K (the same code: csrc/pose_geometry.h).
+ * FUSG_ERR_INVALID before any launch: n_clips outside 1..FUSG_MAX_FRAMES, J outside 0 .. 2^20 - 1, a null host table, offsets that
+ * do not start at 0, decrease or do not end at J, a row count that is no multiple of V_c, a clip that owns rows with a null table
+ * entry; with J > 0 also a null device pointer or h, w, n_cad < 1.  J = 0 launches nothing.  One thread per row, ordinary stores. */
+int fusg_pose_geometry_clips(const float* const* poses, const int64_t* const* cad_idxs, const int32_t* const* src_pts,
+                             const int32_t* vehicles, const int32_t* row_first, int32_t n_clips, const double* steps,
+                             const double* cams, const float* bank_kp3d, const int32_t* bank_v_off, const int32_t* bank_t_off,
+                             int32_t n_cad, int32_t h, int32_t w, int32_t J, float* pose, double* extrinsic, double* kp3d,
+                             fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv, int32_t* nearer, int32_t* tex_pts,
+                             int32_t* tex_nv, int32_t* status, int32_t* src_pts_rows, void* stream);
+/* The same code on the CPU: every pointer, the tables' entries included, is a HOST pointer (no GPU needed). */
+int fusg_pose_geometry_clips_host(const float* const* poses, const int64_t* const* cad_idxs, const int32_t* const* src_pts,
+                                  const int32_t* vehicles, const int32_t* row_first, int32_t n_clips, const double* steps,
+                                  const double* cams, const float* bank_kp3d, const int32_t* bank_v_off, const int32_t* bank_t_off,
+                                  int32_t n_cad, int32_t h, int32_t w, int32_t J, float* pose, double* extrinsic, double* kp3d,
+                                  fusg_render_job* jobs, int32_t* vis_pts, int32_t* vis_nv, int32_t* nearer, int32_t* tex_pts,
+                                  int32_t* tex_nv, int32_t* status, int32_t* src_pts_rows);
+
 /* ---- the later-frame gate (the tail of a geometry-mode later frame's device stage; like the pose geometry added without a
  * version step: the entry points are new, nothing existing changed, and FUSG_VERSION 118 is what the suite pins) ------- */
 /* The tail of a later frame's geometry stage, without a read-back: for J (frame, vehicle) rows
