@@ -1665,6 +1665,21 @@ class VehiclePipeline:
         return {k: paste(out[c], **box) for k, c in (("frame_icn", "icn_u8"), ("frame_vunet", "vunet_u8"))}
 
     @staticmethod
+    def _paste_frames(bases, frame_rows, crops, geom, masks, box_images=None, box_geom=None) -> torch.Tensor:
+        """`paste_back_ragged_device` over any number of frames: consecutive chunks of at most `_lib.MAX_FRAMES` frames, one launch
+        each over the chunk's own rows, the composites concatenated.  Up to MAX_FRAMES frames it is that one launch."""
+        from . import _lib as L
+        from .warp_learn import planes_utils as pu
+        parts = []
+        for lo in range(0, len(bases), L.MAX_FRAMES):
+            hi = min(len(bases), lo + L.MAX_FRAMES)
+            r = slice(frame_rows[lo], frame_rows[hi])
+            parts.append(pu.paste_back_ragged_device(bases[lo:hi], [x - r.start for x in frame_rows[lo:hi + 1]], crops[r], geom[r], masks[r],
+                                                     None if box_images is None else box_images[r],
+                                                     None if box_geom is None else box_geom[r]))
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    @staticmethod
     def _cat_rows(scenes, k) -> torch.Tensor:
         """The scenes' per-vehicle tensor `k` in row order (one scene: its own tensor, nothing copied)."""
         return scenes[0][k] if len(scenes) == 1 else torch.cat([sc[k] for sc in scenes])
@@ -1970,10 +1985,11 @@ class VehiclePipeline:
         """`run_later_frame` for the F future frames of a clip at once: five of a clip's six frames are later frames of the SAME
         vehicles, and frame by frame each is a pass of ~300 dependent launches at batch V.  Here everything between the uint8
         frames and the composited uint8 frames is issued once for all F * V (frame, vehicle) pairs - one plane warp
-        (fusg_warp_perspective_frames_u8, from ONE copy of the first frame's planes), one mask_bbox_geom, icn_inputs and
-        vunet_inputs, `_later_nets` once at B = F * V, one lab2bgr and one ordered paste per composite for all F frames
-        (fusg_paste_layers_frames_u8).  Rows are frame-major: row f * V + v is frame f, vehicle v; the first frame's central
-        crops and appearance codes are repeated per frame, per-frame 'vehicle_seeds' concatenated in row order.
+        (fusg_warp_perspective_clips_u8, the first frame's planes passed by pointer, not copied), one mask_bbox_geom, icn_inputs
+        and vunet_inputs, `_later_nets` once at B = F * V, one lab2bgr and one ordered paste per composite for every 64 frames
+        (fusg_paste_layers_ragged_u8).  A group is run as the several-clip pass of ONE clip (`_run_later_clips`), whose rows
+        are these: frame-major, row f * V + v is frame f, vehicle v; the first frame's central crops and appearance codes
+        are repeated per frame, per-frame 'vehicle_seeds' concatenated in row order.
 
         scenes: a sequence of F later scenes as `run_later_frame` takes them (same vehicles and order as `state`; each its own
         'frame', 'masks', 'dst_*', optional 'background', 'vehicle_seeds', 'inpaint'); every scene's 'src_planes' is the first
@@ -1990,6 +2006,8 @@ class VehiclePipeline:
         pass each (`later_batch_groups`).  Default LATER_MAX_BATCH = 64 rows, the largest batch the frame drivers run anyway (a
         frame of 64 vehicles), so the networks' activations stay what that pass already needs; the warped planes take 5 * H * W
         * 3 bytes per row - 13.8 MB at 720 x 1280, 885 MB for 64 rows (553 MB for a clip tail of 5 frames of 8 vehicles).
+        One warp launch takes 65535 (row, plane) jobs: a max_batch that makes a group of more than 13107 rows at 5 planes is a
+        ValueError before anything is launched.
         Returns a list of F dicts with `run_later_frame`'s keys and shapes, in scene order ('icn_u8', 'vunet_u8', 'geom',
         'frame_icn', 'frame_vunet' (+ 'inpaint_u8')); a frame's tensors are views into the pass's stacked results.  V = 0: F
         results of `run_later_frame`'s no-vehicle shape; F = 0: [].
@@ -2004,10 +2022,12 @@ class VehiclePipeline:
         exactly `run_later_frames_batched`, the frame-by-frame fallback).  Frame by frame such a later frame blocks on a
         device-to-host copy between its render and its plane warp (`render.vehicle_geometry_device`), because the visibilities
         and the skip rule were decided on the host, and its networks run at batch "kept vehicles".  Here a group of
-        `later_batch_groups(F, V, max_batch)` frames is queued whole before anything is read: `render.later_geometry_batch_device`
-        (fusg_pose_geometry -> fusg_render_normals_u8 -> fusg_plane_visibility -> fusg_later_gate at F * V rows) ->
-        `plane_homographies_device` from device corner points and gated visibilities -> the shared-source plane warp -> crop rows
-        and both networks' inputs -> `_later_nets` at F * V -> Lab -> BGR -> the ordered paste of all frames; then ONE `ops.d2h`
+        `later_batch_groups(F, V, max_batch)` frames is queued whole before anything is read, as the several-clip pass of one
+        clip: `render.later_geometry_clips_device` (one upload of the steps, the camera and the source visibilities ->
+        fusg_pose_geometry_clips -> fusg_render_normals_u8 -> fusg_plane_visibility -> fusg_later_gate at F * V rows) ->
+        `plane_homographies_device` from device corner points and gated visibilities -> the plane warp
+        (fusg_warp_perspective_clips_u8, the state's planes passed by pointer) -> crop rows and both networks' inputs ->
+        `_later_nets` at F * V -> Lab -> BGR -> the ordered paste of all frames (fusg_paste_layers_ragged_u8); then ONE `ops.d2h`
         of the stage's small packed buffer, from which the per-frame results are cut.  V = the state's vehicles, rows
         frame-major, the plan of replay=True is the ("later_batch", F, V, precision[, "inpaint"]) plan a given-geometry batch of that
         shape uses: its shape no longer depends on what rendered.
@@ -2049,34 +2069,24 @@ class VehiclePipeline:
         if any(sc["src_planes"].data_ptr() != scenes[0]["src_planes"].data_ptr() or sc["src_planes"].shape != scenes[0]["src_planes"].shape
                for sc in scenes):
             raise ValueError("run_later_frames_batched: the scenes of a batch share the first frame's 'src_planes' (one tensor)")
-        return [res for lo, hi in later_batch_groups(F, V, max_batch)
-                for res in self._guarded_pass(self._run_later_batch, (scenes[lo:hi], state, replay), check, seeds)]
+        return self._later_one_clip_groups(scenes, state, replay, check, max_batch, seeds, False)
 
-    def _run_later_batch(self, scenes, state, replay=False) -> list:
-        return self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay))
-
-    @torch.no_grad()
-    def _later_batch_stages(self, scenes, state, icn_out=None, geo=None) -> Dict:
-        """The data movement of a batched later pass in front of the networks, frame-major over the F scenes: 'warped' uint8
-        [F * V, P, H, W, 3], 'masks' uint8 [F * V, H, W], 'geom' int32 [F * V, 8], 'icn_x' [F * V, 21, R, R] (icn_out: a recorded
-        pass's buffer, written in place), 'vu_y' [F * V, 3, R, R].  Nothing here depends on the batch size: every row holds the
-        bytes `_later_local` builds for its frame.  geo (geometry mode, `_later_geometry_stage`): the masks, sketches, corner points
-        and visibilities come from the device stage instead of the scenes."""
-        from .warp_learn import planes_utils as pu
-        F = len(scenes)
-        with torch.cuda.device(self.device):
-            if geo is not None:
-                # geometry mode: masks, sketches, corner points and gated visibilities as the device stage left them
-                minv, index = pu.plane_homographies_device(geo["src_kp_d"], geo["tex_pts_d"], geo["src_vis_d"], geo["dst_vis_d"],
-                                                           nverts=geo["kp_nv_d"])
-                warped = pu.warp_planes_frames_fitted(geo["src_planes"], minv, index, F)       # :376-381
-                masks, sketch = geo["mask"], geo["sketch"]
-            else:
-                src_planes, fit = scenes[0]["src_planes"], self._later_fits(scenes)
-                warped = pu.warp_planes_frames_fitted(src_planes, *fit, F) if self.device_homography else \
-                    pu.warp_planes_frames_batch(src_planes, fit, F)                            # :376-381
-                masks, sketch = self._cat_rows(scenes, "masks"), self._cat_rows(scenes, "dst_sketch")
-            return self._later_inputs(warped, masks, sketch, [(state["central"], F)], scenes[0]["frame"], icn_out)
+    def _later_one_clip_groups(self, scenes, state, replay, check, max_batch, seeds, geometry: bool) -> list:
+        """The validated later scenes of ONE clip with vehicles as guarded passes, one per group of `later_batch_groups`: each
+        group is `_run_later_clips` over a group of one clip - whose rows ARE the frame-major F * V rows -, unpadded, its plan
+        kept under the one-clip key ("later_batch", F, V, ...).  The several-clip warp takes at most 65535 (row, plane) jobs
+        per launch, so a group of more than 65535 // P rows (13107 at 5 planes; a max_batch far beyond anything the project
+        runs) is a ValueError before anything is launched."""
+        V = int(state["central"].shape[0])
+        P = int((state["geometry"] if geometry else scenes[0])["src_planes"].shape[1])
+        groups = later_batch_groups(len(scenes), V, max_batch)
+        rows = max(hi - lo for lo, hi in groups) * V
+        if rows * P > 65535:
+            raise ValueError(f"run_later_frames_batched{'_geometry' if geometry else ''}: a group of {rows} rows of {P} planes exceeds "
+                             f"the 65535 warp jobs of one launch (max_batch at most {65535 // P})")
+        return [res for lo, hi in groups
+                for res in self._guarded_pass(lambda *a: self._run_later_clips(*a)[0],
+                                              ([(scenes[lo:hi], state)], replay, None, geometry, ("later_batch", hi - lo, V)), check, seeds)]
 
     def _later_fits(self, scenes):
         """The plane homographies of the scenes' vehicles, in row order, from their host corner points and visibilities: the
@@ -2089,62 +2099,6 @@ class VehiclePipeline:
         if self.device_homography:
             return pu.plane_homographies_device(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"], self.device)
         return pu.warp_jobs_frame(kp["src_kp"], kp["dst_kp"], vis["src_vis"], vis["dst_vis"])
-
-    def _later_inputs(self, warped, masks, sketch, central, frame, icn_out=None, vu_out=None) -> Dict:
-        """The stages of a later pass behind its warp, once for all rows: crop rows, the ICN's inputs with the first frame's
-        central crops - central: (crops [V, ...], frames) per clip, repeated per frame in row order -, the VUnet's y_tilde
-        (icn_out / vu_out: buffers written in place).  The dict `_later_batch_stages` and `_later_clips_stages` return."""
-        from . import frame_ops as fo
-        from .warp_learn import planes_utils as pu
-        R = 256
-        _, geom = fo.mask_bbox_geom(masks)
-        central = [c.repeat(n, 1, 1, 1) for c, n in central]
-        icn_x = pu.icn_inputs_device(warped, sketch, central[0] if len(central) == 1 else torch.cat(central), geom, R, R,
-                                     out=icn_out)                                              # :385-387
-        _, vu_y = fo.vunet_inputs(frame, masks, sketch, sketch, geom, R,                       # :415-420 (y_tilde reads no frame)
-                                  out=None if vu_out is None else (None, vu_out))
-        return {"warped": warped, "masks": masks, "geom": geom, "icn_x": icn_x, "vu_y": vu_y}
-
-    @torch.no_grad()
-    def _later_batch_local(self, scenes, state, replay=False, geo=None) -> Dict:
-        """The per-(frame, vehicle) part of a batched later pass: glue, the networks at B = F * V, Lab -> BGR.  Returns 'icn_u8'
-        (BGR), 'vunet_u8', 'geom', 'masks' (+ 'inpaint_u8'), F * V rows each, frame-major.  geo: see `_later_batch_stages`."""
-        from . import ops
-        F, V = len(scenes), int(state["central"].shape[0])
-        inpaint = self._later_inpaint(scenes[0]) is not None
-        seeds = later_batch_seeds([sc.get("vehicle_seeds") for sc in scenes], V)
-        with torch.cuda.device(self.device):
-            pkey = ("later_batch", F, V, ops.PRECISION) + (("inpaint",) if inpaint else ())
-            replay, tgt, _ = self._pass_buffers(pkey, replay, F * V, F * V)
-            ec, ec_join = self._inpaint_inputs_rows(scenes, [f * V for f in range(F + 1)], F * V, tgt) if inpaint else (None, None)
-            st = self._later_batch_stages(scenes, state, icn_out=tgt.get("icn_x"), geo=geo)
-            nets_in = {"icn_x": st["icn_x"], "vu_y": st["vu_y"],
-                       "app0": state["appearance"][0].repeat(F, 1, 1, 1), "app1": state["appearance"][1].repeat(F, 1, 1, 1)}
-            if ec is not None:
-                ec_join()
-                nets_in.update({"ec_" + k: ec[k] for k in ops.INPAINT_KEYS})
-            out = self._nets_pass(self._later_nets, pkey, replay, nets_in, seeds)
-            out["geom"], out["masks"] = st["geom"], st["masks"]
-        return out
-
-    @torch.no_grad()
-    def _later_batch_finish(self, scenes, out, box_geom=None) -> list:
-        """The frame-level part of a batched later pass: the ordered paste of all F frames, one launch per composite; then the
-        stacked results cut into `run_later_frame`'s dict per frame.  box_geom: the box rows already on the device (geometry mode:
-        uploaded in front of the stage, whose gate zeroes the rows of empty renders)."""
-        from .warp_learn import planes_utils as pu
-        F = len(scenes)
-        V = int(out["geom"].shape[0]) // F
-        inpaint = "inpaint_u8" in out
-        with torch.cuda.device(self.device):
-            bases = [self._paste_base(sc) for sc in scenes]
-            if inpaint and box_geom is None:
-                box_geom = self._box_rows([sc["inpaint"]["boxes"] for sc in scenes])
-            frames = self._composites(lambda crops, **box: pu.paste_back_frames_device(bases, crops, out["geom"], out["masks"], **box),
-                                      out, box_geom if inpaint else None)
-        keys = ("icn_u8", "vunet_u8", "geom") + (("inpaint_u8",) if inpaint else ())
-        return [{**{k: out[k][later_batch_slice(f, V)] for k in keys}, "frame_icn": frames["frame_icn"][f],
-                 "frame_vunet": frames["frame_vunet"][f]} for f in range(F)]
 
     # ---- the same for a geometry-mode state: the render, the visibilities and the skip rule stay on the device
     def _later_geometry_batched(self, scenes, state, replay, check, max_batch) -> list:
@@ -2159,9 +2113,7 @@ class VehiclePipeline:
             raise ValueError("run_later_frames_batched_geometry: the frames of a batch have one size")
         if V == 0:
             return list(self.run_later_frames(scenes, state, replay=replay))
-        rows = self._geometry_row_scenes(scenes, veh, inpaint)
-        return [res for lo, hi in later_batch_groups(len(scenes), V, max_batch)
-                for res in self._guarded_pass(self._run_later_geometry_batch, (rows[lo:hi], state, replay), check, seeds)]
+        return self._later_one_clip_groups(self._geometry_row_scenes(scenes, veh, inpaint), state, replay, check, max_batch, seeds, True)
 
     def _geometry_row_scenes(self, scenes, veh, inpaint: bool) -> list:
         """The rows' scenes of a geometry-mode batch: 'vehicle_seeds' and 'inpaint' list every first-frame vehicle and are selected
@@ -2198,46 +2150,6 @@ class VehiclePipeline:
             pts, nv = pu.pack_plane_points(gs["src_kp"], len(rd.TEXTURE_PLANES))
             src_kp_d, kp_nv_d = ops.h2d(pts, dev), ops.h2d(np.ascontiguousarray(nv[0]), dev)
         return {"pose_d": pose_d, "cad_idx_d": cad_d, "src_kp_d": src_kp_d, "kp_nv_d": kp_nv_d}
-
-    @torch.no_grad()
-    def _later_geometry_stage(self, scenes, state, box_rows=None) -> Dict:
-        """The device geometry of a group of F later frames for the V vehicles of `state` (`render.later_geometry_batch_device`) and
-        what the plane homographies need besides: the first frame's corner points and visibilities repeated per frame.  A state
-        made without device copies uploads its host pose, CAD indices and corner points once.  Nothing is read back."""
-        import numpy as np
-
-        from . import ops
-        from . import render as rd
-        gs = state["geometry"]
-        F, V = len(scenes), len(gs["vehicles"])
-        veh = list(gs["vehicles"])
-        H, W = int(scenes[0]["frame"].shape[0]), int(scenes[0]["frame"].shape[1])
-        K = rd.intrinsic(gs["focals"], gs["centers"])
-        dev = self.device
-        with torch.cuda.device(dev):
-            sd = self._geometry_state_device(gs)
-            src_vis_d = ops.h2d((np.asarray(gs["src_vis"]).reshape(V, -1) != 0).astype(np.uint8), dev)
-            geo = rd.later_geometry_batch_device(self.cad_bank, (H, W), sd["cad_idx_d"], sd["pose_d"], K,
-                                                 [[sc["steps"][v] for v in veh] for sc in scenes], box_rows=box_rows)
-            geo.update(src_planes=gs["src_planes"], src_kp_d=sd["src_kp_d"].repeat(F, 1, 1, 1).contiguous(),
-                       src_vis_d=src_vis_d.repeat(F, 1).contiguous(), kp_nv_d=sd["kp_nv_d"].contiguous())
-        return geo
-
-    @torch.no_grad()
-    def _run_later_geometry_batch(self, scenes, state, replay=False) -> list:
-        """One group of a geometry-mode batch: everything through the paste is queued, then the stage's small buffer is read back
-        ONCE and the per-frame results of `_geometry_later_frame` are cut from the stacked ones."""
-        from . import ops
-        gs = state["geometry"]
-        veh = list(gs["vehicles"])
-        V = len(veh)
-        inpaint = self._later_inpaint(scenes[0]) is not None
-        with torch.cuda.device(self.device):
-            box_rows = self._box_rows([sc["inpaint"]["boxes"] for sc in scenes]) if inpaint else None
-            geo = self._later_geometry_stage(scenes, state, box_rows)
-            frames = self._later_batch_finish(scenes, self._later_batch_local(scenes, state, replay, geo=geo), box_geom=box_rows)
-            host = geo["host"](ops.d2h(geo["buf"]))               # the one read-back of the group, behind the queued paste
-            return [self._geometry_cut(res, later_batch_slice(f, V), veh, scenes[f], geo, host, inpaint) for f, res in enumerate(frames)]
 
     def _geometry_cut(self, res: Dict, sl: slice, veh, scene: Dict, geo: Dict, host: Dict, inpaint: bool) -> Dict:
         """One frame of a batched geometry pass as `_geometry_later_frame` returns it: `res` holds the frame's rows `sl` of the
@@ -2719,9 +2631,11 @@ class VehiclePipeline:
         """The data movement of a several-clip later pass in front of the networks, clip-major over the (scenes, state) pairs and
         frame-major inside a clip: 'warped' uint8 [N, P, H, W, 3], 'masks' uint8 [N, H, W], 'geom' int32 [N, 8], 'icn_x' [N, 21,
         R, R], 'vu_y' [N, 3, R, R] for the N = sum(F_c * V_c) rows (icn_out / vu_out: the N real rows of a padded or recorded
-        pass's buffers, written in place).  Every row holds the bytes `_later_batch_stages` builds for its clip: a clip without
-        frames or without vehicles contributes no row.  At least one row.  geo (geometry mode, `_later_clips_geometry_stage`): the
-        masks, sketches, corner points and gated visibilities come from the device stage, the planes from the states."""
+        pass's buffers, written in place).  Nothing here depends on the batch size: every row holds the bytes `_later_local`
+        builds for its frame; a clip without frames or without vehicles contributes no row.  At least one row.  geo (geometry
+        mode, `_later_clips_geometry_stage`): the masks, sketches, corner points and gated visibilities come from the device
+        stage, the planes from the states."""
+        from . import frame_ops as fo
         from .warp_learn import planes_utils as pu
         live = [(list(scs), st) for scs, st in clips if len(scs) and int(st["central"].shape[0])]
         scenes = [sc for scs, _ in live for sc in scs]
@@ -2739,17 +2653,26 @@ class VehiclePipeline:
                 warped = pu.warp_planes_clips_fitted(planes, counts, *fit) if self.device_homography else \
                     pu.warp_planes_clips_batch(planes, counts, fit)                            # :376-381
                 masks, sketch = self._cat_rows(scenes, "masks"), self._cat_rows(scenes, "dst_sketch")
-            return self._later_inputs(warped, masks, sketch, [(st["central"], len(scs)) for scs, st in live], scenes[0]["frame"],
-                                      icn_out, vu_out)
+            # ---- behind the warp, once for all rows: crop rows, the ICN's inputs with each clip's central crops repeated per frame
+            # in row order, the VUnet's y_tilde
+            R = 256
+            _, geom = fo.mask_bbox_geom(masks)
+            central = [st["central"].repeat(len(scs), 1, 1, 1) for scs, st in live]
+            icn_x = pu.icn_inputs_device(warped, sketch, central[0] if len(central) == 1 else torch.cat(central), geom, R, R,
+                                         out=icn_out)                                          # :385-387
+            _, vu_y = fo.vunet_inputs(scenes[0]["frame"], masks, sketch, sketch, geom, R,      # :415-420 (y_tilde reads no frame)
+                                      out=None if vu_out is None else (None, vu_out))
+            return {"warped": warped, "masks": masks, "geom": geom, "icn_x": icn_x, "vu_y": vu_y}
 
     @torch.no_grad()
-    def _run_later_clips(self, clips, replay=False, rows=None, geometry=False) -> list:
-        """One group of `run_later_clips_batched`: one list of `run_later_frame` dicts per clip.  rows: the row count the networks
-        run at (>= N, the padding rows zero); None: N.  geometry: a group of `run_later_clips_batched_geometry` - the clips' scenes
-        carry 'steps' instead of masks, sketches and corner points, which come from the device stage
-        (`_later_clips_geometry_stage`), the results are `_geometry_later_frame`'s, cut after the stage's ONE read-back."""
+    def _run_later_clips(self, clips, replay=False, rows=None, geometry=False, plan_key=None) -> list:
+        """One group of later frames - of `run_later_clips_batched`, or of the one-clip drivers, whose group is a list of one clip:
+        one list of `run_later_frame` dicts per clip.  rows: the row count the networks run at (>= N, the padding rows zero);
+        None: N.  geometry: a group of the geometry-mode drivers - the clips' scenes carry 'steps' instead of masks, sketches and
+        corner points, which come from the device stage (`_later_clips_geometry_stage`), the results are
+        `_geometry_later_frame`'s, cut after the stage's ONE read-back.  plan_key: what the recorded plan is kept under, in front
+        of the precision and the inpaint marker; None: ("later_rows", B)."""
         from . import ops
-        from .warp_learn import planes_utils as pu
         dev, R = self.device, 256
         frames = [len(scs) for scs, _ in clips]
         vehicles = [int(st["central"].shape[0]) for _, st in clips]
@@ -2766,7 +2689,7 @@ class VehiclePipeline:
         inpaint = self._later_inpaint(live[0][0][0]) is not None
         seeds = clip_batch_seeds([[sc.get("vehicle_seeds") for sc in scs] for scs, _ in clips], vehicles)
         with torch.cuda.device(dev):
-            pkey = ("later_rows", B, ops.PRECISION) + (("inpaint",) if inpaint else ())
+            pkey = tuple(plan_key or ("later_rows", B)) + (ops.PRECISION,) + (("inpaint",) if inpaint else ())
             replay, tgt, buf = self._pass_buffers(pkey, replay, B, N)
 
             def per_row(i):
@@ -2796,7 +2719,7 @@ class VehiclePipeline:
             bases = [self._paste_base(sc) for sc in scenes]
             if inpaint and not geometry:
                 box_rows = self._box_rows([sc["inpaint"]["boxes"] for scs, _ in live for sc in scs])
-            comp = self._composites(lambda crops, **box: pu.paste_back_ragged_device(bases, frame_rows, crops, geom, masks, **box), out,
+            comp = self._composites(lambda crops, **box: self._paste_frames(bases, frame_rows, crops, geom, masks, **box), out,
                                     box_rows if inpaint else None)
             # geometry mode: the one read-back of the group, behind the queued paste
             host = geo["host"](ops.d2h(geo["buf"])) if geometry else None

@@ -1,6 +1,6 @@
 """GPU: the future frames of SEVERAL clips as one batched pass (VehiclePipeline.run_later_clips_batched,
 fusg_warp_perspective_clips_u8).  The kernel equals the per-clip kernel byte for byte; the data movement in front of the
-networks equals the one-clip stages; the rendered frames are compared with the vehicle-serial CPU oracle under the bars of
+networks equals the per-frame stages; the rendered frames are compared with the vehicle-serial CPU oracle under the bars of
 tests/test_gpu_later_batch.py (not with clip-by-clip device passes: another batch size may route convolutions differently)."""
 import os
 import sys
@@ -21,7 +21,7 @@ from conftest import synth_sd                                              # noq
 from future_urban_scene_generation_amd import ops                          # noqa: E402
 from future_urban_scene_generation_amd import pipeline as pl               # noqa: E402
 from future_urban_scene_generation_amd.warp_learn import planes_utils as pu   # noqa: E402
-from test_gpu_later_batch import _bars, _host_threads, _inpaint_bars, _moved, inpaint_env   # noqa: E402,F401
+from test_gpu_later_batch import _bars, _host_threads, _inpaint_bars, _moved, _per_frame_stages, inpaint_env   # noqa: E402,F401
 
 DEV = "cuda:0"
 HW = (360, 640)
@@ -211,9 +211,14 @@ def _stage_scenes(pipe, V, F, seed):
     return scenes, state
 
 
+def _per_frame(pipe, clips):
+    """The per-frame path's own stages of every (clip, frame) that has vehicles, in row order."""
+    return [_per_frame_stages(pipe, sc, st) for scs, st in clips if int(st["central"].shape[0]) for sc in scs]
+
+
 def _assert_stages(pipe, clips, tag):
     got = pipe._later_clips_stages(clips)
-    want = [pipe._later_batch_stages(scs, st) for scs, st in clips if len(scs) and int(st["central"].shape[0])]
+    want = _per_frame(pipe, clips)
     assert got["warped"].any()
     for k in ("warped", "geom", "icn_x", "vu_y"):
         ref = torch.cat([w[k] for w in want])
@@ -224,17 +229,17 @@ def _assert_stages(pipe, clips, tag):
 
 def test_stages_equal_the_one_clip_stages(env):
     """Two clips that differ in F, V, frames and poses (and an empty tail between them): warped planes, crop rows and both
-    networks' inputs == `_later_batch_stages` per clip, concatenated."""
+    networks' inputs == the per-frame path's (`_per_frame_stages`) per (clip, frame), concatenated in row order."""
     pipe = env["pipe"]
     assert pipe.device_homography is False
     a, b = _stage_scenes(pipe, 3, 2, 53), _stage_scenes(pipe, 1, 3, 51)
     got, want = _assert_stages(pipe, [a, ([], b[1]), b], "host fits")
-    assert tuple(got["icn_x"].shape) == (9, 21, 256, 256) and not torch.equal(want[0]["warped"][:1], want[1]["warped"][:1])
+    assert tuple(got["icn_x"].shape) == (9, 21, 256, 256) and not torch.equal(want[0]["warped"][:1], want[2]["warped"][:1])
 
 
 def test_stages_with_device_homography_on_the_tie_free_scene(env):
     """device_homography=True: the table fitted for all rows of the call feeds the several-clip warp as it stands.  On the scene
-    free of rounding ties (synth_frame seed 41, 2 vehicles, its first and its later pose) the clips equal the one-clip stages
+    free of rounding ties (synth_frame seed 41, 2 vehicles, its first and its later pose) the clips equal the per-frame stages
     with the flag on AND with it off."""
     pipe = env["pipe"]
     first = pl.synth_frame(2, HW, DEV, seed=41)
@@ -246,7 +251,7 @@ def test_stages_with_device_homography_on_the_tie_free_scene(env):
     later["dst_kp"] = [[np.int32(p + np.array([-7, 5]) + g.integers(-2, 3, p.shape)) for p in veh] for veh in first["dst_kp"]]
     state = pipe.run_frame(first)["state"]
     clips = [([later, first, later], state), ([first, later], state)]
-    host = [pipe._later_batch_stages(scs, st) for scs, st in clips]
+    host = _per_frame(pipe, clips)
     pipe.device_homography = True
     try:
         got, _ = _assert_stages(pipe, clips, "device_homography")

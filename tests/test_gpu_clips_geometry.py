@@ -1,6 +1,6 @@
 """GPU: the future frames of SEVERAL geometry-mode clips as ONE batched, read-back-free pass
 (VehiclePipeline.run_later_clips_batched_geometry, render.later_geometry_clips_device, fusg_pose_geometry_clips).  The kernel equals
-its host twin byte for byte; the several-clip stage equals the one-clip stage (`_later_geometry_stage`) on each clip's rows, one
+its host twin byte for byte; the several-clip stage equals the one-clip stage (`render.later_geometry_batch_device`) on each clip's rows, one
 clip on a second camera and one row inert; the derived keys fed back as explicit given-geometry clips of the same rows give the
 same bytes (that path is tied to the CPU oracle by tests/test_gpu_clips_batch.py and tests/test_gpu_later_batch.py); one
 device-to-host copy per group; replay shares the given-geometry plan; the range guard; inpainting; whole clips."""
@@ -147,6 +147,19 @@ def _inert_row():
 
 
 # ------------------------------------------------------------------------------------------------ 2. the stage
+def _per_clip_stage(pipe, scs, st):
+    """The one-clip device stage of a clip's tail (`render.later_geometry_batch_device` at F * V rows, frame-major) and what the
+    plane homographies need besides: the state's source corner points and visibilities repeated F times."""
+    gs = st["geometry"]
+    veh, F = list(gs["vehicles"]), len(scs)
+    sd = pipe._geometry_state_device(gs)
+    one = R.later_geometry_batch_device(pipe.cad_bank, HW, sd["cad_idx_d"], sd["pose_d"], R.intrinsic(gs["focals"], gs["centers"]),
+                                        [[sc["steps"][v] for v in veh] for sc in scs])
+    vis = torch.from_numpy((np.asarray(gs["src_vis"]).reshape(len(veh), -1) != 0).astype(np.uint8)).to(DEV)
+    one.update(src_kp_d=sd["src_kp_d"].repeat(F, 1, 1, 1), src_vis_d=vis.repeat(F, 1), kp_nv_d=sd["kp_nv_d"])
+    return one
+
+
 def test_stage_equals_the_per_clip_stage(env):
     pipe, clips = env["pipe"], env["clips"]
     live = [(scs, st) for scs, st in clips if scs]
@@ -166,7 +179,7 @@ def test_stage_equals_the_per_clip_stage(env):
     for c, (scs, st) in enumerate(live):
         F, V = SHAPES[c]
         sl = slice(offs[c], offs[c + 1])
-        one = pipe._later_geometry_stage(scs, st)
+        one = _per_clip_stage(pipe, scs, st)
         h1 = one["host"](ops.d2h(one["buf"]))
         for k in ("mask", "sketch", "tex_pts_d", "dst_vis_d", "valid_d", "src_kp_d", "src_vis_d"):
             a = geo[k][sl]
@@ -299,12 +312,14 @@ def test_an_oversized_clip_goes_through_the_one_clip_method(env):
     assert pl.clip_batch_groups([2, 3], [2, 1], 3) == [(0, 1, True), (1, 2, False)]
     calls = []
     orig = pipe._run_later_clips
-    pipe._run_later_clips = lambda cl, *a: (calls.append(len(cl)), orig(cl, *a))[1]
+    pipe._run_later_clips = lambda cl, *a: (calls.append((len(cl[0][0]), a[3] if len(a) > 3 else None)), orig(cl, *a))[1]
     try:
         got = pipe.run_later_clips_batched_geometry([clips[0], clips[2]], max_batch=3)
     finally:
         del pipe._run_later_clips
-    assert calls == [1]                                           # clip 2 alone is a group; clip 0 (4 rows) is not one
+    # clip 0 (4 rows) is no group of the several-clip driver: the one-clip method splits it by frames, under its own plan key;
+    # clip 2 alone is a group of the several-clip driver, under the default key
+    assert calls == [(1, ("later_batch", 1, 2)), (1, ("later_batch", 1, 2)), (3, None)]
     want = pipe.run_later_frames_batched_geometry(*clips[0], max_batch=3)
     _same_clips([got[0]], [want], "oversized")
     _same_clips([got[1]], pipe.run_later_clips_batched_geometry([clips[2]]), "the clip behind it")

@@ -1,5 +1,5 @@
-"""GPU: a clip's future frames as ONE batched pass (VehiclePipeline.run_later_frames_batched, fusg_paste_layers_frames_u8,
-fusg_warp_perspective_frames_u8).  The data movement - warped planes, crop rows, both networks' inputs, EdgeConnect's inputs,
+"""GPU: a clip's future frames as ONE batched pass (VehiclePipeline.run_later_frames_batched, a group of one clip of the
+several-clip runner; the leaf fusg_paste_layers_frames_u8).  The data movement - warped planes, crop rows, both networks' inputs, EdgeConnect's inputs,
 the ordered paste - equals the per-frame path byte for byte; the rendered frames are compared with the vehicle-serial CPU
 oracle under the bars of tests/test_gpu_frame.py's later-frame test and tests/test_gpu_later_inpaint.py (not with the per-frame
 device path: a batch of 9 and a batch of 3 may route convolutions differently)."""
@@ -109,7 +109,7 @@ def _per_frame_stages(pipe, scene, state):
 
 
 def _assert_stages(pipe, scenes, state, tag):
-    got = pipe._later_batch_stages(scenes, state)
+    got = pipe._later_clips_stages([(scenes, state)])
     want = [_per_frame_stages(pipe, sc, state) for sc in scenes]
     assert got["warped"].any() and tuple(got["icn_x"].shape) == (len(scenes) * int(state["central"].shape[0]), 21, 256, 256)
     for k in ("warped", "geom", "icn_x", "vu_y"):
@@ -136,7 +136,7 @@ def test_stages_equal_the_per_frame_path(env, F, V):
         scenes.append(sc)
     _assert_stages(pipe, scenes, state, (F, V))
     if F > 1:
-        assert not torch.equal(*(pipe._later_batch_stages([sc], state)["warped"] for sc in scenes[:2]))
+        assert not torch.equal(*(pipe._later_clips_stages([([sc], state)])["warped"] for sc in scenes[:2]))
 
 
 def test_stages_with_device_homography_on_the_tie_free_scene(env):
@@ -157,7 +157,7 @@ def test_stages_with_device_homography_on_the_tie_free_scene(env):
     pipe.device_homography = True
     try:
         _assert_stages(pipe, scenes, state, "device_homography")
-        got = pipe._later_batch_stages(scenes, state)
+        got = pipe._later_clips_stages([(scenes, state)])
     finally:
         pipe.device_homography = False
     for k in ("warped", "geom", "icn_x", "vu_y"):
@@ -177,7 +177,7 @@ def _paste_case(F, V, H, W, R=32, seed=5, empty=None, clipped=None):
     for f in range(F):
         for v in range(V):
             r = f * V + v
-            x0, y0 = W // 2 - 30 + 9 * v + int(g.integers(-3, 4)), H // 2 - 25 + 7 * v + 2 * f
+            x0, y0 = W // 2 - 30 + 9 * v + int(g.integers(-3, 4)), H // 2 - 25 + 7 * v + 2 * (f % 5)
             bb = [x0, y0, x0 + int(g.integers(28, 45)), y0 + int(g.integers(22, 36))]
             if (f, v) == clipped:
                 bb = [W - 30, -4, W + 6, 28]                                      # the square window pads on two sides
@@ -244,6 +244,36 @@ def test_paste_frames_vehicle_order_decides_the_overlap(boxes):
         assert not torch.equal(got[f], rev[f]), f                              # the same layers in another order: other pixels
 
 
+@pytest.mark.parametrize("boxes", [True, False], ids=["box_layers", "plain"])
+@pytest.mark.parametrize("F", [65, 64])
+def test_chunked_ragged_paste_equals_one_frames_launch(F, boxes):
+    """The group runner's paste (`_paste_frames`: fusg_paste_layers_ragged_u8 over chunks of at most 64 frames) == ONE
+    fusg_paste_layers_frames_u8 launch over the same inputs, byte for byte: 65 frames of 1 vehicle at 37 x 53 (neither the row
+    bytes, 159, nor the pixel count, 1961, is a multiple of 256) are two launches, the second holding the frame whose crop
+    window leaves the image; one mask is empty.  64 frames are the single launch of before."""
+    H, W = 37, 53
+    assert (3 * W) % 256 and (H * W) % 256 and F * H * W > 256
+    c = _paste_case(F, 1, H, W, empty=(3, 0), clipped=(F - 1, 0))
+    assert not c["masks"][3].any() and c["masks"][2].any() and c["geom"][F - 1, 4:].any()
+    t = {k: _d(c[k]) for k in ("nets", "masks", "geom", "boxes_img", "rects")}
+    bases = [_d(c["bases"][f]) for f in range(F)]
+    box = dict(box_images=t["boxes_img"], box_geom=t["rects"]) if boxes else {}
+    launches = []
+    orig = pu.paste_back_ragged_device
+    pu.paste_back_ragged_device = lambda frames, *a, **k: (launches.append(len(frames)), orig(frames, *a, **k))[1]
+    try:
+        got = pl.VehiclePipeline._paste_frames(bases, list(range(F + 1)), t["nets"], t["geom"], t["masks"], **box)
+    finally:
+        pu.paste_back_ragged_device = orig
+    assert launches == ([64, 1] if F == 65 else [64])
+    want = pu.paste_back_frames_device(bases, t["nets"], t["geom"], t["masks"], **box)
+    assert tuple(got.shape) == (F, H, W, 3) and got.dtype == torch.uint8 and torch.equal(got, want)
+    for f in (0, F - 1):                                                        # layers were pasted in the first and in the last chunk
+        assert not np.array_equal(got[f].cpu().numpy(), c["bases"][f]), f
+    if not boxes:
+        assert np.array_equal(got[3].cpu().numpy(), c["bases"][3])              # the empty mask pastes nothing
+
+
 # ------------------------------------------------------------------------------------------------ end to end
 def test_batched_frames_match_the_oracle(env):
     """F = 3, V = 3: every frame of the batch against oracle.frame_pass + oracle.later_frame_pass."""
@@ -301,12 +331,12 @@ def test_chunked_passes_meet_the_same_bars_in_scene_order(env, max_batch, groups
     pipe, V = env["pipe"], 3
     assert len(pl.later_batch_groups(3, V, max_batch)) == groups
     calls = []
-    orig = pipe._run_later_batch
-    pipe._run_later_batch = lambda scenes, state, replay=False: (calls.append(len(scenes)), orig(scenes, state, replay))[1]
+    orig = pipe._run_later_clips
+    pipe._run_later_clips = lambda clips, *a: (calls.append(len(clips[0][0])), orig(clips, *a))[1]
     try:
         got = pipe.run_later_frames_batched(env["later"], env["f0"]["state"], max_batch=max_batch)
     finally:
-        del pipe._run_later_batch
+        del pipe._run_later_clips
     assert calls == ([2, 1] if max_batch == 6 else [1, 1, 1])
     assert len(got) == 3
     for f, (g, ref, cpu) in enumerate(zip(got, env["refs"], env["cpus"])):        # frame f's result sits at position f

@@ -1,5 +1,5 @@
 """GPU: a geometry-mode clip's future frames as ONE batched, read-back-free pass (VehiclePipeline.run_later_frames_batched_geometry,
-render.later_geometry_batch_device, fusg_later_gate).  The device gate equals its host twin; the batched stage equals the
+render.later_geometry_clips_device over one clip, fusg_later_gate).  The device gate equals its host twin; the batched stage equals the
 per-frame device path (`_geometry_later_front`) byte for byte, with the vehicle whose render is empty kept as an inert row; the
 derived keys fed back as an explicit given-geometry batch of the same rows give the same bytes (the given-geometry batch is tied
 to the CPU oracle by tests/test_gpu_later_batch.py); one device-to-host copy per group."""
@@ -141,8 +141,8 @@ def env():
 # ------------------------------------------------------------------------------------------------ 2. the stage
 def test_stage_equals_the_per_frame_path(env):
     pipe, later, state, fronts = env["pipe"], env["later"], env["state"], env["fronts"]
-    geo = pipe._later_geometry_stage(later, state)
-    st = pipe._later_batch_stages(later, state, geo=geo)
+    geo = pipe._later_clips_geometry_stage([(later, state)])
+    st = pipe._later_clips_stages([(later, state)], geo=geo)
     host = geo["host"](ops.d2h(geo["buf"]))
     assert tuple(geo["mask"].shape) == (F * V,) + HW and tuple(geo["sketch"].shape) == (F * V,) + HW + (3,)
     assert tuple(st["icn_x"].shape) == (F * V, 21, 256, 256) and st["warped"].any()
@@ -248,12 +248,12 @@ def test_chunked_groups_in_scene_order(env):
     pipe, later, state = env["pipe"], env["later"], env["state"]
     assert pl.later_batch_groups(F, V, 6) == [(0, 2), (2, 3)]
     calls = []
-    orig = pipe._run_later_geometry_batch
-    pipe._run_later_geometry_batch = lambda scenes, st, replay=False: (calls.append(len(scenes)), orig(scenes, st, replay))[1]
+    orig = pipe._run_later_clips
+    pipe._run_later_clips = lambda clips, *a: (calls.append(len(clips[0][0])), orig(clips, *a))[1]
     try:
         got = pipe.run_later_frames_batched_geometry(later, state, max_batch=6)
     finally:
-        del pipe._run_later_geometry_batch
+        del pipe._run_later_clips
     assert calls == [2, 1] and len(got) == F
     ex = pipe.run_later_frames_batched(env["explicit"], env["sub"], max_batch=6)
     _same_as_explicit(got, ex, V, "max_batch 6")

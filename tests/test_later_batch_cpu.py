@@ -144,3 +144,15 @@ def test_public_interface():
     assert sig.parameters["replay"].default is False and sig.parameters["check"].default == "sync" and sig.parameters["max_batch"].default is None
     clip = inspect.signature(pl.VehiclePipeline.run_clip_frames)
     assert clip.parameters["batched"].default is False and list(clip.parameters)[:4] == ["self", "first_scene", "later_scenes", "replay"]
+
+
+def test_one_group_runner():
+    """A group of later frames has ONE runner: the one-clip bodies are gone, and `_run_later_clips` takes the plan key its caller
+    records under (the one-clip drivers': ("later_batch", F, V), the several-clip default: ("later_rows", B))."""
+    for name in ("_run_later_batch", "_later_batch_stages", "_later_batch_local", "_later_batch_finish", "_later_geometry_stage",
+                 "_run_later_geometry_batch"):
+        assert not hasattr(pl.VehiclePipeline, name), name
+    sig = inspect.signature(pl.VehiclePipeline._run_later_clips)
+    assert list(sig.parameters) == ["self", "clips", "replay", "rows", "geometry", "plan_key"] and sig.parameters["plan_key"].default is None
+    src = inspect.getsource(pl.VehiclePipeline._later_one_clip_groups)
+    assert '"later_batch"' in src and "_run_later_clips" in src and '"later_rows"' in inspect.getsource(pl.VehiclePipeline._run_later_clips)

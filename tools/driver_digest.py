@@ -116,6 +116,35 @@ def main():
     laters = [{"frame": torch.roll(scenes[0]["frame"], 37 * (n + 1), 1).contiguous(), "steps": [steps[n]] * 2,
                "vehicle_seeds": [1000 * (n + 1) + v for v in range(2)]} for n in range(F)]
     rec("geometry/run_later_frames_batched_geometry", lambda r: pipe.run_later_frames_batched_geometry(laters, state, replay=r))
+    rec("geometry/run_later_frames_batched_geometry/max_batch_2",
+        lambda r: pipe.run_later_frames_batched_geometry(laters, state, replay=r, max_batch=2))          # one frame per group
+    # the inert-row and drop path: vehicle 1 of frame 1 moved behind the camera, its render is empty
+    first = pipe.run_frame(scenes[0])
+    behind = -200.0 * np.asarray(R.extrinsic_from_pose(first["pose"][1][1], first["pose"][1][2])[2, :3], np.float64)
+    inert = [dict(sc, steps=[steps[n], (steps[n][0], behind)]) if n == 1 else sc for n, sc in enumerate(laters)]
+    rec("geometry/run_later_frames_batched_geometry/inert", lambda r: pipe.run_later_frames_batched_geometry(inert, state, replay=r))
+    # clips of different (F, V), one of them without frames
+    state1 = pipe.run_frame(scenes[2])["state"]
+    tail1 = [{"frame": torch.roll(scenes[2]["frame"], 53 * (n + 1), 1).contiguous(), "steps": [steps[n]],
+              "vehicle_seeds": [2000 * (n + 1)]} for n in range(2)]
+    clips = [(inert, state), (tail1, state1), ([], state)]
+    rec("geometry/run_later_clips_batched_geometry", lambda r: pipe.run_later_clips_batched_geometry(clips, replay=r))
+    # the geometry tail with 'inpaint' box masks, the same inert row (its box row is zeroed by the gate)
+    bank = pipe.cad_bank
+    del pipe
+    pipe = pl.VehiclePipeline(dev, inpaint=True, device_pose=True, device_homography=True, cad_bank=bank)
+
+    def inpaint_of(shift):
+        boxes = np.asarray(pl.synth_inpaint_boxes(np.asarray(scenes[0]["bboxes"]).tolist(), HW), np.int64)
+        boxes = boxes + np.array([shift, 0, shift, 0]) * (boxes[:, 2:3] < HW[1] - 8)
+        planes = torch.zeros((len(boxes), 1) + HW, dtype=torch.uint8)
+        for v, (x0, y0, x1, y1) in enumerate(boxes):                              # a stand-in detection: the middle of the box
+            planes[v, 0, y0 + (y1 - y0) // 4:y1 - (y1 - y0) // 4, x0 + (x1 - x0) // 4:x1 - (x1 - x0) // 4] = 255
+        return {"boxes": boxes, "box_masks": [m.to(dev) for m in pl.synth_box_masks(planes, boxes)]}
+
+    state = pipe.run_frame(dict(scenes[0], inpaint=inpaint_of(0)))["state"]
+    boxed = [dict(sc, inpaint=inpaint_of(n + 1)) for n, sc in enumerate(inert)]
+    rec("geometry/inpaint/run_later_frames_batched_geometry", lambda r: pipe.run_later_frames_batched_geometry(boxed, state, replay=r))
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
 

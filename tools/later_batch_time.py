@@ -146,6 +146,8 @@ def main():
     ap.add_argument("--geometry", action="store_true", help="time a geometry-mode clip tail: frame by frame against the batched pass")
     ap.add_argument("--vehicles", type=int, nargs="+", default=[8, 64])
     ap.add_argument("--inpaint", type=int, nargs="+", default=None, help="0 / 1; default both (with --arm: 0)")
+    ap.add_argument("--seed", type=int, default=4, help="synth_frame's seed of the given-geometry table (seed 3 draws, at 64 vehicles, a "
+                    "plane whose host-fitted homography is singular: every arm raises LinAlgError on it)")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--arm", choices=ARMS, default=None, help="run this arm alone and write nothing (for a profiler)")
@@ -173,7 +175,7 @@ def main():
     for inp in inpaints:
         pipe = VehiclePipeline(dev, inpaint=inp)
         for V in args.vehicles:
-            scene = synth_frame(V, HW, dev, seed=3, inpaint="masks" if inp else False)
+            scene = synth_frame(V, HW, dev, seed=args.seed, inpaint="masks" if inp else False)
             scene["vehicle_seeds"] = list(range(V))
             laters = [synth_later_frame(scene, s, inpaint="box_masks" if inp else None) for s in range(1, F + 1)]
             state = pipe.run_frame(scene, replay=True)["state"]
