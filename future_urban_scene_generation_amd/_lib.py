@@ -68,6 +68,14 @@ class RespairDesc(C.Structure):         # fusg_respair_desc
                 ("cin", C.c_int32), ("kpad_in", C.c_int32), ("tap_order", C.c_int32), ("_pad", C.c_int32)]
 
 
+class HgHeadDesc(C.Structure):          # fusg_hg_head_desc
+    _fields_ = [("y_in", Tensor), ("x", Tensor), ("score", Tensor), ("dst", Tensor),
+                ("wfrag_fc", C.c_void_p), ("bias_fc", C.c_void_p), ("wscale_fc", C.c_void_p),
+                ("wfrag_score", C.c_void_p), ("bias_score", C.c_void_p), ("wscale_score", C.c_void_p),
+                ("wfrag_join", C.c_void_p), ("bias_join", C.c_void_p), ("wscale_join", C.c_void_p),
+                ("status", C.c_void_p), ("join", C.c_int32), ("_pad", C.c_int32)]
+
+
 class PackSpec(C.Structure):            # fusg_pack_spec
     _fields_ = [(n, C.c_int32) for n in ("cout", "cin", "kh", "kw", "c0", "stride", "pad", "dil", "upsample", "cin_pad")]
 
@@ -98,6 +106,7 @@ _SIGS = {
     "fusg_conv2d_route_order": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32 * 4)]),
     "fusg_hg_bottleneck": (C.c_int, [C.POINTER(BneckDesc), C.c_void_p]),
     "fusg_vunet_respair": (C.c_int, [C.POINTER(RespairDesc), C.c_void_p]),
+    "fusg_hg_head": (C.c_int, [C.POINTER(HgHeadDesc), C.c_void_p]),
     "fusg_conv2d_entry_nin": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p]),
     "fusg_conv2d_entry_nin_route": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
     "fusg_chan_stats": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -186,6 +195,7 @@ _SIGS = {
     "fusg_sizeof_conv_desc": (C.c_int, []),
     "fusg_sizeof_bneck_desc": (C.c_int, []),
     "fusg_sizeof_respair_desc": (C.c_int, []),
+    "fusg_sizeof_hg_head_desc": (C.c_int, []),
     "fusg_prof_enable": (None, [C.c_int]),
     "fusg_prof_reset": (None, []),
     "fusg_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -221,7 +231,8 @@ def lib():
             fn.argtypes = args
         if (h.fusg_sizeof_tensor() != C.sizeof(Tensor) or h.fusg_sizeof_conv_desc() != C.sizeof(ConvDesc)
                 or h.fusg_sizeof_bneck_desc() != C.sizeof(BneckDesc)
-                or h.fusg_sizeof_respair_desc() != C.sizeof(RespairDesc)):
+                or h.fusg_sizeof_respair_desc() != C.sizeof(RespairDesc)
+                or h.fusg_sizeof_hg_head_desc() != C.sizeof(HgHeadDesc)):
             raise FusgUnavailable("libfusg.so struct layout differs from the ctypes mirror (stale build?)")
         if ROUTE_BATCH_ENV and h.fusg_set_route_batch(ROUTE_BATCH_ENV) < 0:
             raise FusgError(f"FUSG_ROUTE_BATCH={ROUTE_BATCH_ENV}: {h.fusg_last_error().decode()}")

@@ -109,6 +109,12 @@ template <> struct SavedArg<const fusg_respair_desc*> {
     const fusg_respair_desc* get() const { return has ? &d : nullptr; }
 };
 
+template <> struct SavedArg<const fusg_hg_head_desc*> {
+    bool has; fusg_hg_head_desc d;
+    explicit SavedArg(const fusg_hg_head_desc* p) : has(p != nullptr), d(p ? *p : fusg_hg_head_desc{}) {}
+    const fusg_hg_head_desc* get() const { return has ? &d : nullptr; }
+};
+
 // run impl(args..., stream); when a plan is recording, remember the call first
 template <class... A>
 int plan_dispatch(int (*impl)(A..., void*), void* stream, A... a) {

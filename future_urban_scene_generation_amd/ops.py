@@ -788,12 +788,81 @@ def entry_nin(nin: ConvPlan, res: ConvPlan, u: torch.Tensor, out: Optional[torch
     return out
 
 
+HG_HEAD = not _env_set("FUSG_NO_HG_HEAD")         # the 1x1 head of an hourglass stack (fc, score, join) as one launch (tests flip it)
+
+
+def _k1(p: ConvPlan, c0k: int, c1k: int) -> bool:
+    return (p.kh == 1 and p.kw == 1 and p.pad == 0 and p.stride == 1 and p.dil == 1 and p.upsample == 0 and p.nphase == 1
+            and p.c0k == c0k and p.c1k == c1k)
+
+
+def hg_head_ok(fc: ConvPlan, score: ConvPlan, y_in: torch.Tensor, join: Optional[ConvPlan] = None,
+               x: Optional[torch.Tensor] = None, precision: Optional[str] = None) -> bool:
+    """Can  y = relu(fc(y_in));  s = score(y);  x' = x + join(cat[y, s])  (last stack: join None, stops after s) run as ONE launch
+    (fusg_hg_head)?  Split-fp16 only, 256 channels, at most 32 classes - in the join form the score plan is the one zero-padded to
+    32 output channels, its tensor the join's 32-channel source - and only where fusg_conv2d would run all three launches on the
+    halo kernel: the fused launch then writes their bytes.  Small maps, which the small-image kernel takes, and everything else
+    stay unfused; so does everything with HG_HEAD off (FUSG_NO_HG_HEAD=1 at import)."""
+    prec = precision or PRECISION
+    if not HG_HEAD or prec != "f16x3" or not is_nhwc(y_in) or y_in.shape[1] != 256:
+        return False
+    if not (_k1(fc, 256, 0) and fc.cout == 256 and _k1(score, 256, 0) and 1 <= score.cout <= 32 and score.cout_pad == 32):
+        return False
+    if join is not None:
+        if not (_k1(join, 256, 32) and join.cout == 256 and score.cout == 32 and x is not None and is_nhwc(x)
+                and x.shape == y_in.shape):
+            return False
+    b, c, h, w = y_in.shape
+    # The fused launch sums as the HALO kernel does: the router is asked what each launch it replaces would run on (as respair_ok
+    # does), once per shape and per the switches the router reads per call.
+    key = (id(score), id(join), b, h, w, y_in.stride(3), None if x is None else x.stride(3), str(y_in.device), ROUTE_BATCH,
+           _env_set("FUSG_NO_SMALL"), _env_set("FUSG_NO_POINTWISE"), _env_set("FUSG_SMALL_KSPLIT"))
+    memo = fc.__dict__.setdefault("_hg_head_routes", {})
+    if key not in memo:
+        s = nhwc_empty(b, score.cout, h, w, y_in.device)         # stands in for score; y_in for y and the outputs (no launch)
+        asks = [_conv_desc(fc, y_in, act=L.ACT_RELU, out=y_in, precision=prec)[0],
+                _conv_desc(score, y_in, out=s, precision=prec)[0]]
+        if join is not None:
+            asks.append(_conv_desc(join, y_in, s[:, :join.c_split[1]], res0=x, out=y_in, precision=prec)[0])
+        ok = True
+        for d in asks:
+            L.lib().fusg_conv2d_plan(C.byref(d))
+            ok = ok and L.lib().fusg_conv2d_route(C.byref(d)) == 2
+        memo[key] = ok
+    return memo[key]
+
+
+def hg_head(fc: ConvPlan, score: ConvPlan, y_in: torch.Tensor, join: Optional[ConvPlan] = None, x: Optional[torch.Tensor] = None):
+    """(s, x') of  y = relu(fc(y_in));  s = score(y);  x' = x + join(cat[y, s])  in one launch (fusg_hg_head) - the bytes of the
+    three `conv` launches it replaces; y is never written.  join None (the last stack): (s, None).  In the join form s has the
+    score plan's 32 channels, those past the classes exact zeros.  Raises where hg_head_ok is false."""
+    b, _, h, w = y_in.shape
+    s = nhwc_empty(b, score.cout, h, w, y_in.device)
+    out = None if join is None else nhwc_empty(b, join.cout, h, w, y_in.device)
+    d = L.HgHeadDesc()
+    d.y_in, d.x, d.score, d.dst = desc(y_in), desc(x if join is not None else None), desc(s), desc(out)
+    for key, plan in (("fc", fc), ("score", score), ("join", join)):
+        if plan is None:
+            continue
+        dev = plan.to(y_in.device).dev
+        if RECORDER is not None:
+            RECORDER.keep.append(dev)
+        assert dev.get("wfrag") is not None and dev["wfrag_order"] == 0, key
+        setattr(d, "wfrag_" + key, dev["wfrag"].data_ptr())
+        setattr(d, "bias_" + key, dev["bias"].data_ptr())
+        setattr(d, "wscale_" + key, dev["wscale"].data_ptr())
+    d.status = status_word(y_in.device).data_ptr()
+    d.join = 0 if join is None else 1
+    L.check(L.lib().fusg_hg_head(C.byref(d), stream_ptr()), "hg_head")
+    return s, out
+
+
 def last_conv_kernel() -> int:
     """Kernel family of the last conv launch issued by this thread (fusg_last_conv_kernel): 0 generic fp32,
     1 generic split-fp16, 2 halo, 3 halo in parity-quadrant (stride-2) form, 4 tap-unit kernel (few-channel stems),
     5 halo in bf16 mode, 6 fused hourglass Bottleneck, 7 pointwise-from-few-channels streaming kernel, 8 small-image kernel,
     9 halo in exact fp32, 10 tap-unit in exact fp32, 11 tap-unit in bf16 mode, 12 fused VUnet Residual pair (respair),
-    13 halo kernel with the entry NiN computed in its staging (entry_nin)."""
+    13 halo kernel with the entry NiN computed in its staging (entry_nin), 14 fused head of an hourglass stack (hg_head)."""
     return int(L.lib().fusg_last_conv_kernel())
 
 

@@ -12,7 +12,8 @@ Execution is a flat sequence of libfusg launches over NHWC activations:
   * residual adds (``out += residual``, ``x + fc_ + score_``) are conv epilogues;
   * max-pool and ``up1 + upsample(low3)`` are single HBM-bound kernels.
 A Bottleneck is therefore 3 launches (4 with a downsample conv) instead of 10 framework ops - and, on the
-split-fp16 path, ONE launch per block (fusg_hg_bottleneck, 64 or 128 planes: both intermediates stay in LDS).
+split-fp16 path, ONE launch per block (fusg_hg_bottleneck, 64 or 128 planes: both intermediates stay in LDS).  The 1x1 head
+that ends a stack (fc, score, and the join of fc_ + score_ with the residual) is one launch too on that path (fusg_hg_head).
 """
 from __future__ import annotations
 
@@ -193,8 +194,14 @@ class HourglassNet(FusedNet):
         for i in range(self.num_stacks):
             y = self._hourglass(P["hg"][i], 4, x)
             y = self._seq(P["res"][i], y)
-            y = ops.conv(P["fc"][i], y, act=L.ACT_RELU)
             last = i == self.num_stacks - 1
+            sp, jp = (P["score"][i], None) if last else (P["score32"][i], P["join"][i])
+            if ops.hg_head_ok(P["fc"][i], sp, y, jp, x):       # f16x3 on the halo kernel's maps: fc, score and join in one launch
+                score, xn = ops.hg_head(P["fc"][i], sp, y, jp, x)
+                heatmaps.append(ops.to_nchw(score[:, :self.num_classes]))
+                x = x if last else xn
+                continue
+            y = ops.conv(P["fc"][i], y, act=L.ACT_RELU)
             joined = not last and ops.halo_precision() and y.shape[1] % 32 == 0 and self.num_classes <= 32
             # (for the joined form the score map is the first num_classes channels of a 32-channel launch whose other
             # channels are exact zeros: a 32-channel source of the next launch)

@@ -339,6 +339,31 @@ int fusg_vunet_respair(const fusg_respair_desc* d, void* stream);
 int fusg_conv2d_entry_nin(const fusg_conv_desc* res, const fusg_conv_desc* nin, void* stream);
 int fusg_conv2d_entry_nin_route(const fusg_conv_desc* res, const fusg_conv_desc* nin);
 
+/*
+ * The 1x1 head that ends a stack of the hourglass in ONE launch (split-fp16 arithmetic, FUSG_PREC_F16X3; csrc/conv_hghead.hip;
+ * added without a version step: the entry points are new, nothing existing changed, and FUSG_VERSION 118 is what the suite pins):
+ *   y     = relu(fc_1x1(y_in) + bias_fc)            256 -> 256 (the fc BatchNorm folded at pack time) - never written
+ *   score = score_1x1(y) + bias_score               256 -> cout_pad 32; channels [0, score.c) are written
+ *   dst   = x + join_1x1(cat[y, score]) + bias_join 288 -> 256                                    (join = 1 only)
+ * (stacked_hourglass/models.py: fc, score, and x + fc_(y) + score_(score) as one two-source convolution.)  join = 1 wants
+ * score.c == 32 - the score filter zero-padded to 32 output channels, so that the launch writes the padding as exact zeros on
+ * every call and `score` is the join's 32-channel second source; join = 0 (the last stack) stops after score.
+ * Weights: the `wfrag` copy (fusg_conv_desc.wfrag, wfrag_order 0) of each convolution, their `bias` [cout_pad] and `wscale`
+ * [cout_pad] arrays.  y_in, x, dst: NHWC-physical f32 [n, 256, h, w]; score [n, <= 32, h, w].  score and dst have the bytes of
+ * the three fusg_conv2d launches on the halo kernel (a 1x1 launch has one summation order there at every batch size).  Same range
+ * contract as F16X3 launches: *status = 1 when a staged operand (y_in, y, or score in the join form) is outside the split's range.
+ */
+typedef struct fusg_hg_head_desc {
+    fusg_tensor y_in, x, score, dst;
+    const void*  wfrag_fc;    const float* bias_fc;    const float* wscale_fc;
+    const void*  wfrag_score; const float* bias_score; const float* wscale_score;
+    const void*  wfrag_join;  const float* bias_join;  const float* wscale_join;    /* join = 1 */
+    int32_t*     status;
+    int32_t      join;
+    int32_t      _pad;
+} fusg_hg_head_desc;
+int fusg_hg_head(const fusg_hg_head_desc* d, void* stream);
+
 /* Load-time weight pre-packing on the HOST (no device work): everything fusg_conv_desc needs for one nn.Conv2d-style
  * filter weight[cout][cin][kh][kw] (torch layout, correlation form) whose input channels come from one source (c0 = cin)
  * or from two concatenated sources (the first c0 channels from src0: torch.cat([x, skip], 1) fused into the gather).
@@ -838,7 +863,8 @@ enum { FUSG_CONV_GENERIC_F32 = 0, FUSG_CONV_GENERIC_F16X3 = 1, FUSG_CONV_HALO = 
        FUSG_CONV_TAPUNIT_F32 = 10 /* few-channel stems in exact fp32 (csrc/conv_kernel_tapunit_f32.h; wfrag_order 2 + wfrag_f32) */,
        FUSG_CONV_TAPUNIT_BF16 = 11 /* few-channel stems in single-pass bf16 (FUSG_PREC_BF16; wfrag_order 2 + wfrag_bf16) */,
        FUSG_CONV_RESPAIR = 12 /* fusg_vunet_respair */,
-       FUSG_CONV_HALO_ENTRY = 13 /* fusg_conv2d_entry_nin: halo kernel with the entry NiN computed in its staging */ };
+       FUSG_CONV_HALO_ENTRY = 13 /* fusg_conv2d_entry_nin: halo kernel with the entry NiN computed in its staging */,
+       FUSG_CONV_HG_HEAD = 14 /* fusg_hg_head */ };
 int         fusg_last_conv_kernel(void);
 const char* fusg_arch(void);                      /* "gfx950" */
 /* sizeof(fusg_tensor) / sizeof(fusg_conv_desc) as compiled, so that FFI bindings can verify their
@@ -847,6 +873,7 @@ int         fusg_sizeof_tensor(void);
 int         fusg_sizeof_conv_desc(void);
 int         fusg_sizeof_bneck_desc(void);
 int         fusg_sizeof_respair_desc(void);
+int         fusg_sizeof_hg_head_desc(void);
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline leg).
  * kind 0 = conv implicit-GEMM kernel.  Disabled by default; enabling makes launches record two
  * events each.  fusg_prof_read synchronises the recorded events and returns totals since reset. */
