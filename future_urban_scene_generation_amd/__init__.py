@@ -29,10 +29,12 @@ _ALIASES = {
 #   pnp:          the pose fit (cpc_rodr_4_angles).  north_star keeps PnP host-side; the device fit itself is pinned to the
 #                 reference's CPC_R, its cv2.Rodrigues epilogue is not.
 _OPT_IN_ALIASES = {"planes_utils": {"warp_learn.planes_utils": "future_urban_scene_generation_amd.warp_learn.planes_utils"},
-                   "pnp": {"utils.pnp_utils": "future_urban_scene_generation_amd.utils.pnp_utils"}}
+                   "pnp": {"utils.pnp_utils": "future_urban_scene_generation_amd.utils.pnp_utils"},
+                   # metrics: PSNR / EdgeAccuracy from device counts (exact) - same values up to the reference's float32 sums
+                   "metrics": {"edgeconnect.metrics": "future_urban_scene_generation_amd.edgeconnect.metrics"}}
 
 
-def install(names=None, planes_utils=None, pnp=None) -> None:
+def install(names=None, planes_utils=None, pnp=None, metrics=None) -> None:
     """Register the drop-in modules in ``sys.modules`` under the reference's import names.
 
     By default only the four network packages are replaced; ``warp_learn``, ``edgeconnect`` and ``utils`` keep resolving
@@ -40,17 +42,22 @@ def install(names=None, planes_utils=None, pnp=None) -> None:
     ``planes_utils=True`` (or FUSG_DROPIN_PLANES_UTILS=1) additionally routes ``from warp_learn.planes_utils import
     to_image, warp_unwarp_planes`` (trajectory_inference.py:28-29) to the device versions; ``pnp=True`` (or
     FUSG_DROPIN_PNP=1) routes ``from utils.pnp_utils import cpc_rodr_4_angles`` (:25) to the device pose fit - both
-    explicit, because their parity with OpenCV is unpinned."""
+    explicit, because their parity with OpenCV is unpinned.  ``metrics=True`` (or FUSG_DROPIN_METRICS=1) routes ``from
+    edgeconnect.metrics import PSNR, EdgeAccuracy`` to the device-counting versions."""
     import os
     if planes_utils is None:
         planes_utils = os.environ.get("FUSG_DROPIN_PLANES_UTILS") == "1"
     if pnp is None:
         pnp = os.environ.get("FUSG_DROPIN_PNP") == "1"
+    if metrics is None:
+        metrics = os.environ.get("FUSG_DROPIN_METRICS") == "1"
     aliases = dict(_ALIASES)
     if planes_utils:
         aliases.update(_OPT_IN_ALIASES["planes_utils"])
     if pnp:
         aliases.update(_OPT_IN_ALIASES["pnp"])
+    if metrics:
+        aliases.update(_OPT_IN_ALIASES["metrics"])
     for alias, target in aliases.items():
         if names is not None and alias.split(".")[0] not in names:
             continue

@@ -170,6 +170,12 @@ _SIGS = {
                                   + [C.c_void_p] * 2),
     "fusg_inpaint_inputs_boxed_host": (C.c_int, [_TP, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [_TP] * 4
                                        + [C.c_void_p]),
+    "fusg_image_metrics_u8": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fusg_image_metrics_scratch_bytes": (C.c_int64, [C.c_int32] * 4),
+    "fusg_image_metrics_host": (C.c_int, [_TP, _TP, C.c_void_p]),
+    "fusg_edge_counts": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p, C.c_void_p]),
+    "fusg_edge_counts_host": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p]),
+    "fusg_sq_diff_sum_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

@@ -1370,6 +1370,88 @@ def inpaint_inputs_boxed_host(frame, box_masks, boxes, sigma: float = 2.0, gauss
 
 
 # ---------------------------------------------------------------------------------------------
+# per-image quality metrics (csrc/metrics.h): SSIM / PSNR / difference counts of uint8 crops, EdgeAccuracy's counts
+# ---------------------------------------------------------------------------------------------
+IMAGE_METRIC_COLUMNS = ("ssim", "mse", "psnr", "max_abs", "n_diff", "sse")
+
+
+def _image_pair(a, b, u8, what: str) -> None:
+    if a.dtype != u8 or b.dtype != u8 or len(a.shape) != 4 or len(b.shape) != 4:
+        raise ValueError(f"{what}: a and b must be uint8 [B, H, W, C], got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+
+
+def image_metrics_u8(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The float64 [B, 6] table (`IMAGE_METRIC_COLUMNS`) of two CUDA uint8 [B, H, W, C] batches of any strides, on the device:
+    two launches on the current stream, no host synchronisation (fusg_image_metrics_u8; SSIM as the test oracle defines it)."""
+    _require_gpu(a, "a")
+    _require_gpu(b, "b")
+    _image_pair(a, b, torch.uint8, "image_metrics_u8")
+    B, H, W, Cn = a.shape
+    with torch.cuda.device(a.device):
+        out = torch.empty((B, len(IMAGE_METRIC_COLUMNS)), dtype=torch.float64, device=a.device)
+        lib = L.lib()
+        nbytes = int(lib.fusg_image_metrics_scratch_bytes(B, H, W, Cn))
+        scratch = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=a.device)
+        L.check(lib.fusg_image_metrics_u8(C.byref(desc(a.permute(0, 3, 1, 2))), C.byref(desc(b.permute(0, 3, 1, 2))), out.data_ptr(),
+                                          scratch.data_ptr(), stream_ptr()), "image_metrics_u8")
+        if RECORDER is not None:
+            RECORDER.keep.append(scratch)
+    return out
+
+
+def image_metrics_host(a, b) -> _np.ndarray:
+    """`image_metrics_u8` on the CPU by the same code in the same order of sums (fusg_image_metrics_host; no GPU needed):
+    numpy uint8 [B, H, W, C] in, float64 [B, 6] out."""
+    a, b = _np.asarray(a), _np.asarray(b)
+    _image_pair(a, b, _np.uint8, "image_metrics_host")
+    out = _np.zeros((a.shape[0], len(IMAGE_METRIC_COLUMNS)), dtype=_np.float64)
+    L.check(L.lib().fusg_image_metrics_host(C.byref(_np_desc(a.transpose(0, 3, 1, 2), L.U8)), C.byref(_np_desc(b.transpose(0, 3, 1, 2), L.U8)),
+                                            out.ctypes.data), "image_metrics_host")
+    return out
+
+
+def _edge_pair(x, y, f32, what: str) -> None:
+    if x.dtype != f32 or y.dtype != f32 or len(x.shape) != 4 or len(y.shape) != 4:
+        raise ValueError(f"{what}: x and y must be float32 [B, 1, H, W], got {x.dtype} {tuple(x.shape)} and {y.dtype} {tuple(y.shape)}")
+
+
+def edge_counts(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
+    """int64 [B, 3] on the device = per row #(x > threshold), #(y > threshold), #(both) of two CUDA float32 [B, 1, H, W] edge
+    maps (labels, outputs): the counts behind EdgeAccuracy, exact, one launch, no host synchronisation."""
+    _require_gpu(x, "x")
+    _require_gpu(y, "y")
+    _edge_pair(x, y, torch.float32, "edge_counts")
+    with torch.cuda.device(x.device):
+        out = torch.empty((x.shape[0], 3), dtype=torch.int64, device=x.device)
+        L.check(L.lib().fusg_edge_counts(C.byref(desc(x)), C.byref(desc(y)), float(threshold), out.data_ptr(), stream_ptr()), "edge_counts")
+    return out
+
+
+def edge_counts_host(x, y, threshold: float = 0.5) -> _np.ndarray:
+    """`edge_counts` on the CPU (fusg_edge_counts_host): numpy float32 [B, 1, H, W] in, int64 [B, 3] out."""
+    x, y = _np.asarray(x), _np.asarray(y)
+    _edge_pair(x, y, _np.float32, "edge_counts_host")
+    out = _np.zeros((x.shape[0], 3), dtype=_np.int64)
+    L.check(L.lib().fusg_edge_counts_host(C.byref(_np_desc(x, L.F32)), C.byref(_np_desc(y, L.F32)), float(threshold), out.ctypes.data),
+            "edge_counts_host")
+    return out
+
+
+def sq_diff_sum(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """0-d float64 device tensor = sum((a - b)^2) of two CUDA float tensors of one shape, added in float64 in a fixed order
+    (fusg_sq_diff_sum_f32: two launches, no host synchronisation)."""
+    _require_gpu(a, "a")
+    _require_gpu(b, "b")
+    if a.shape != b.shape:
+        raise ValueError(f"sq_diff_sum: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    a, b = a.to(torch.float32).contiguous(), b.to(torch.float32).contiguous()
+    with torch.cuda.device(a.device):
+        out = torch.empty((257,), dtype=torch.float64, device=a.device)
+        L.check(L.lib().fusg_sq_diff_sum_f32(a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), stream_ptr()), "sq_diff_sum")
+    return out[0]
+
+
+# ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------
 def prof_enable(on: bool) -> None:

@@ -748,6 +748,68 @@ class VehiclePipeline:
         rng = torch.get_rng_state() if (vehicle_seeds is None and check == "sync") else None
         return self._guarded(self._run, (batch, vehicle_seeds), check, rng)
 
+    # ------------------------------------------------------------------------------------------ quality of one pass against another
+    COMPARED_IMAGES = ("icn_u8", "vunet_u8", "inpaint_u8")
+
+    def compare_outputs(self, a: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor]) -> Dict:
+        """Per-row quality of two output dicts of `run` (or of a frame driver) against each other, measured on the device
+        (`ops.image_metrics_u8`: SSIM as the project's quality bars define it, PSNR, difference counts) and read back in ONE
+        `ops.d2h`.  Compared: every key of `COMPARED_IMAGES` both dicts hold as uint8 [N, R, R, 3] of one shape, and 'kp_idx'.
+        Returns {key: {'ssim' float64 [N], 'psnr' float64 [N], 'max_abs' int64 [N], 'n_diff' int64 [N]}, 'kp_equal' int64 [N]
+        (equal keypoints per row, with 'kp_idx' in both), 'worst': {key: {'ssim': the smallest, 'max_abs': the largest, 'row':
+        the row of the smallest ssim}}} as numpy arrays / Python scalars."""
+        import numpy as np
+        from . import ops
+
+        def is_image(t):
+            return torch.is_tensor(t) and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[-1] == 3
+
+        keys = [k for k in self.COMPARED_IMAGES if is_image(a.get(k)) and is_image(b.get(k)) and a[k].shape == b[k].shape]
+        kp = "kp_idx" in a and "kp_idx" in b and a["kp_idx"].shape == b["kp_idx"].shape
+        if not keys and not kp:
+            raise ValueError("compare_outputs: the two dicts share no uint8 [N, R, R, 3] image and no 'kp_idx'")
+        N = int((a[keys[0]] if keys else a["kp_idx"]).shape[0])
+        ncol = len(ops.IMAGE_METRIC_COLUMNS)
+        with torch.cuda.device(self.device):
+            cols = [ops.image_metrics_u8(a[k], b[k]) for k in keys]
+            if kp:                                                # the indices themselves (exact in float64): compared on the host
+                cols += [a["kp_idx"].reshape(N, -1).to(torch.float64), b["kp_idx"].reshape(N, -1).to(torch.float64)]
+            host = ops.d2h(torch.cat(cols, dim=1))
+        col = {n: i for i, n in enumerate(ops.IMAGE_METRIC_COLUMNS)}
+        res: Dict = {"worst": {}}
+        for i, k in enumerate(keys):
+            t = host[:, i * ncol:(i + 1) * ncol]
+            res[k] = {"ssim": t[:, col["ssim"]].copy(), "psnr": t[:, col["psnr"]].copy(),
+                      "max_abs": t[:, col["max_abs"]].astype(np.int64), "n_diff": t[:, col["n_diff"]].astype(np.int64)}
+            if N:
+                row = int(np.argmin(res[k]["ssim"]))
+                res["worst"][k] = {"ssim": float(res[k]["ssim"][row]), "max_abs": int(res[k]["max_abs"].max()), "row": row}
+        if kp:
+            n_kp = (host.shape[1] - len(keys) * ncol) // 2
+            ka, kb = host[:, len(keys) * ncol:len(keys) * ncol + n_kp], host[:, len(keys) * ncol + n_kp:]
+            res["kp_equal"] = (ka == kb).sum(axis=1).astype(np.int64)
+        return res
+
+    def compare_precisions(self, batch: Dict[str, torch.Tensor], vehicle_seeds: Sequence[int], precision: str = "bf16",
+                           against: str = "f16x3", check: Optional[str] = "sync") -> Dict:
+        """`run(batch, vehicle_seeds)` once under `against` and once under `precision` (`ops.precision`, restored afterwards;
+        this pipeline's routing batch in force around both), then `compare_outputs` of the two: what a faster arithmetic costs
+        on the caller's own weights and crops, in the unit the quality bars are stated in.  The acceptance recipe for bf16:
+        `rep = pipe.compare_precisions(batch, seeds, "bf16"); assert rep["worst"]["icn_u8"]["ssim"] >= 0.999`.
+        vehicle_seeds is required: without it the two passes draw different VUnet noise and the comparison means nothing."""
+        from . import ops
+        if vehicle_seeds is None:
+            raise ValueError("compare_precisions: vehicle_seeds is required (without seeds the two passes draw different noise)")
+        for p in (precision, against):
+            if p not in ops._PREC:
+                raise ValueError(f"compare_precisions: precision must be one of {list(ops._PREC)}, got {p!r}")
+        with self._routed():
+            with ops.precision(against):
+                ref = self.run(batch, vehicle_seeds, check)
+            with ops.precision(precision):
+                out = self.run(batch, vehicle_seeds, check)
+            return self.compare_outputs(out, ref)
+
     def _no_vehicles(self, R: int, *keys) -> Dict[str, torch.Tensor]:
         """The named per-vehicle outputs for zero vehicles (a frame without vehicles, a rank whose shard is empty)."""
         u8 = ((0, R, R, 3), torch.uint8)

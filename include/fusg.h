@@ -809,6 +809,35 @@ int fusg_inpaint_inputs_boxed_host(const fusg_tensor* frame, const void* box_mas
                                    int32_t max_box_h, int32_t max_box_w, const fusg_tensor* img, const fusg_tensor* gray,
                                    const fusg_tensor* edge, const fusg_tensor* mask, void* scratch);
 
+/* ---- per-image quality metrics (the quantity the project's quality bars are stated in, for the product's user; added
+ * without a version step: the entry points are new, nothing existing changed, and FUSG_VERSION 118 is what the suite pins) */
+/* a, b: u8 [B, C, H, W] descriptors of any strides (the NHWC layout of the pipeline's uint8 crops included), the same
+ * shape, C in 1..4, H and W in 11..32767, B < 65536.  out: DEVICE float64 [B][6]; row r =
+ *   0 ssim     mean SSIM of image r over its channels and its (H - 10) x (W - 10) valid positions: 11 x 11 Gaussian window
+ *              of sigma 1.5 (outer product of the normalised 1-D taps), K1 = 0.01, K2 = 0.03, data range 255
+ *   1 mse      sse / (H W C)
+ *   2 psnr     10 log10(255^2 / mse) dB, +inf when sse = 0
+ *   3 max_abs  largest |a - b|               4 n_diff  number of differing values        5 sse  sum of (a - b)^2
+ * Columns 3..5 are exact integers.  The window sums and everything behind them are float64 (csrc/metrics.h says why).
+ * scratch: DEVICE, 16-byte aligned, the bytes the size query returns; it holds nothing between calls.  Two launches (a tile
+ * kernel, then one wave per image), no atomics: a row is bit-identical from run to run and does not depend on B or on the
+ * row's position.  A wrong dtype, C, H < 11, W < 11 or two different shapes: FUSG_ERR_INVALID before any launch; B = 0
+ * launches nothing. */
+int fusg_image_metrics_u8(const fusg_tensor* a, const fusg_tensor* b, double* out, void* scratch, void* stream);
+/* Bytes of scratch for B images of H x W x C; -1 for arguments fusg_image_metrics_u8 would refuse. */
+int64_t fusg_image_metrics_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+/* The same code on the CPU, sums in the kernel's order: a, b and out are HOST pointers, no GPU and no scratch needed. */
+int fusg_image_metrics_host(const fusg_tensor* a, const fusg_tensor* b, double* out);
+/* The counts behind EdgeConnect's EdgeAccuracy: x (labels), y (outputs) f32 [B, 1, H, W] descriptors of any strides, the
+ * same shape, H and W in 1..32767; out: DEVICE int64 [B][3] = #(x > threshold), #(y > threshold), #(both), exact.  One
+ * workgroup per row, no atomics.  B = 0 launches nothing; anything else wrong: FUSG_ERR_INVALID before any launch. */
+int fusg_edge_counts(const fusg_tensor* x, const fusg_tensor* y, float threshold, int64_t* out, void* stream);
+/* The same on HOST pointers. */
+int fusg_edge_counts_host(const fusg_tensor* x, const fusg_tensor* y, float threshold, int64_t* out);
+/* out[0] = the sum over i < n of ((double)a[i] - (double)b[i])^2 for two dense DEVICE float arrays (PSNR of float tensors);
+ * out: DEVICE float64 [257] - out[1..256] hold the per-workgroup partials, added in a fixed order by a second launch. */
+int fusg_sq_diff_sum_f32(const float* a, const float* b, int64_t n, double* out, void* stream);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)
