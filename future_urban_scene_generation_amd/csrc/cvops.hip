@@ -15,12 +15,19 @@
 namespace fusg {
 
 struct U8View { unsigned char* p; long sn, sh, sw; int n, h, w; };
+static inline bool frame_size_ok(long h, long w) { return h >= 1 && w >= 1 && h < 32768 && w < 32768; }     // pixel coordinates fit 16 bits
 static inline bool is_u8_hwc(const fusg_tensor& t, int c) {
-    return t.data && t.dtype == FUSG_U8 && t.c == c && t.sc == 1 && t.sw >= c && t.sh >= t.w * t.sw && t.n >= 1 && t.h >= 1 && t.w >= 1 &&
-           t.h < 32768 && t.w < 32768;
+    return t.data && t.dtype == FUSG_U8 && t.c == c && t.sc == 1 && t.sw >= c && t.sh >= t.w * t.sw && t.n >= 1 && frame_size_ok(t.h, t.w);
 }
 static inline U8View u8view(const fusg_tensor& t) {
     return U8View{(unsigned char*)t.data, t.sn, t.sh, t.sw, (int)t.n, (int)t.h, (int)t.w};
+}
+// shape and strides of the dense u8 [H, W, 3] images that the frame and clip tables point to (the pointer comes from the table)
+static inline U8View dense_hwc3(int H, int W) { return U8View{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W}; }
+// the `bytes` read-only bytes at img lie apart from dst's images, the last of which extends `last` bytes
+static inline bool apart_from_dst(const void* img, long bytes, const fusg_tensor& dst, long last) {
+    const unsigned char *b = (const unsigned char*)img, *d0 = (const unsigned char*)dst.data;
+    return b + bytes <= d0 || b >= d0 + (dst.n - 1) * dst.sn + last;
 }
 static inline unsigned blocks2d(long total) { return (unsigned)((total + 255) / 256); }
 
@@ -133,10 +140,12 @@ __global__ __launch_bounds__(256) void fill_poly_planes_kernel(U8View frame, Pol
 // piece are written byte by byte.  A piece outside the polygon's frame-clipped vertex box is zeros without a frame read or a
 // membership test (poly_inside is true only inside that box); inside, each of its <= 6 pixels takes poly_inside once and reads
 // the frame where it is true.  blockIdx.y = job * n_planes + plane; no atomics, no ordering: every byte is written once.
+// fill_poly_plane_pieces is the ONE copy of that loop: plane q = blockIdx.y of dst cut out of `frame`, whose pointer the calling
+// kernel has resolved (as warp_px's callers do).
 constexpr long POLY_BOX_SAFE = 1L << 29;     // beyond this on_line's int arithmetic may wrap: such a polygon gets the whole frame as box
 
-__global__ __launch_bounds__(256) void fill_poly_planes_batch_kernel(U8View frame, const int* __restrict__ pts_xy,
-                                                                     const int* __restrict__ nverts, U8View dst, long plane_bytes) {
+__device__ __forceinline__ void fill_poly_plane_pieces(const U8View& frame, const int* __restrict__ pts_xy, const int* __restrict__ nverts,
+                                                       const U8View& dst, long plane_bytes) {
     __shared__ int spx[MAXV], spy[MAXV], snv;
     const int q = blockIdx.y, tid = threadIdx.x;
     if (tid < MAXV) {
@@ -204,6 +213,29 @@ __global__ __launch_bounds__(256) void fill_poly_planes_batch_kernel(U8View fram
                 if (s + i < e) d[s + i] = b[i];
         }
     }
+}
+__global__ __launch_bounds__(256) void fill_poly_planes_batch_kernel(U8View frame, const int* __restrict__ pts_xy,
+                                                                     const int* __restrict__ nverts, U8View dst, long plane_bytes) {
+    fill_poly_plane_pieces(frame, pts_xy, nverts, dst, plane_bytes);
+}
+
+// Frame-indexed launches (VehiclePipeline.run_frames_batched: the first frames of several scenes as one pass).  FrameTab travels
+// BY VALUE in the kernel arguments (~0.8 KB): the host has checked every entry before the launch, which it could not do for a
+// table in device memory.  Rows [rows[f], rows[f + 1]) read image img[f].  blockIdx.y = the row (the frame, for the paste), so
+// the lookup is uniform per block.
+struct FrameTab { const unsigned char* img[FUSG_MAX_FRAMES]; int rows[FUSG_MAX_FRAMES + 1]; int n; };
+__device__ __forceinline__ int frame_of_row(const FrameTab& t, int row) {
+    int f = 0;
+    while (f + 1 < t.n && row >= t.rows[f + 1]) ++f;
+    return f;
+}
+// the cut-outs with the frame a property of the JOB: t's rows count jobs, `frame` = the frames' common shape and dense strides.
+// A frame without jobs is never looked up, so never read.
+__global__ __launch_bounds__(256) void fill_poly_planes_frames_kernel(U8View frame, FrameTab t, const int* __restrict__ pts_xy,
+                                                                      const int* __restrict__ nverts, int n_planes, U8View dst,
+                                                                      long plane_bytes) {
+    frame.p = const_cast<unsigned char*>(t.img[frame_of_row(t, blockIdx.y / n_planes)]);       // uniform per block
+    fill_poly_plane_pieces(frame, pts_xy, nverts, dst, plane_bytes);
 }
 
 // ------------------------------------------------------------------------------------------------ resize + Lab
@@ -420,18 +452,30 @@ __global__ __launch_bounds__(256) void paste_back_kernel(PasteIn a, long total) 
     const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
     paste_layers_px(a, 0, x, y, a.frame.p + (long)y * a.frame.sh + (long)x * a.frame.sw);
 }
+// Composite pixel idx of frame f of a.frame: the last of the layers v0 .. v0 + a.V - 1 that covers it, or the pixel of the
+// frame's own base image (dense [H, W, 3]) - every pixel is written.  The ONE copy behind both several-frame kernels.
+__device__ __forceinline__ void paste_frame_px(const PasteIn& a, int f, int v0, const unsigned char* base, long idx) {
+    const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
+    unsigned char* d = a.frame.p + (long)f * a.frame.sn + (long)y * a.frame.sh + (long)x * a.frame.sw;
+    if (paste_layers_px(a, v0, x, y, d)) return;
+    const unsigned char* b = base + idx * 3;
+    d[0] = b[0]; d[1] = b[1]; d[2] = b[2];
+}
 // F frames in one launch (fusg_paste_layers_frames_u8): blockIdx.y = frame f, whose layers are rows f * V .. f * V + V - 1 of
-// the stacked crops, masks and rows; a.frame = the F composites, every pixel of which is written - the layer that covers it,
-// or the pixel of the frame's own base image bases[f] (dense [H, W, 3]).
+// the stacked crops, masks and rows; the bases are a DEVICE table, so F goes up to 65535.
 __global__ __launch_bounds__(256) void paste_frames_kernel(PasteIn a, const unsigned char* const* __restrict__ bases, long total) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int f = blockIdx.y;
-    const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
-    unsigned char* d = a.frame.p + (long)f * a.frame.sn + (long)y * a.frame.sh + (long)x * a.frame.sw;
-    if (paste_layers_px(a, f * a.V, x, y, d)) return;
-    const unsigned char* b = bases[f] + idx * 3;
-    d[0] = b[0]; d[1] = b[1]; d[2] = b[2];
+    paste_frame_px(a, f, f * a.V, bases[f], idx);
+}
+// blockIdx.y = frame f, whose layers are rows t.rows[f] .. t.rows[f + 1] - 1 (none: the frame is a copy of its base t.img[f])
+__global__ __launch_bounds__(256) void paste_ragged_kernel(PasteIn a, FrameTab t, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int f = blockIdx.y;
+    a.V = t.rows[f + 1] - t.rows[f];
+    paste_frame_px(a, f, t.rows[f], t.img[f], idx);
 }
 
 
@@ -467,14 +511,9 @@ __device__ __forceinline__ void crop_resize_px(const int* g, int out_w, int out_
 // output uint8 HWC (mode 0), ToTensor + normalize (mode 1: (v/255 - mean) / std, trajectory_inference.py:61-64) or
 // to_tensor (mode 2: v/255*2 - 1, utils/misc_utils.py:35-49) as f32 NHWC-physical.
 struct CropIn { U8View src; const int* geom; U8View dst8; float* dstf; long dsn, dsh, dsw; int V, out_h, out_w, mode, src_per_v; float mean[3], stdv[3]; };
-__global__ __launch_bounds__(256) void crop_resize_kernel(CropIn a, long total) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int x = (int)(idx % a.out_w);
-    long r = idx / a.out_w;
-    const int y = (int)(r % a.out_h);
-    const int v = (int)(r / a.out_h);
-    const unsigned char* img = a.src.p + (a.src_per_v ? (long)v * a.src.sn : 0);
+// crop_resize_row_px: output pixel (x, y) of window v, cut from `img` (of a.src's shape and strides), stored in a.mode's form.
+// The ONE copy of the arithmetic and of the store: the two kernels differ only in how a thread finds its window and its image.
+__device__ __forceinline__ void crop_resize_row_px(const CropIn& a, const unsigned char* img, int v, int x, int y) {
     const U8View& sv = a.src;
     int rgb[3];
     crop_resize_px(a.geom + v * 8, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(img, sv, px, py, c); }, rgb);
@@ -490,19 +529,31 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(CropIn a, long total) 
         d[c] = a.mode == 1 ? (f - a.mean[c]) / a.stdv[c] : f * 2.f - 1.f;
     }
 }
-
-// The VUnet's inputs (trajectory_inference.py:203-228): x = cat[to_tensor(masked frame crop), to_tensor(src sketch
-// crop, channels reversed)], y_tilde = to_tensor(dst sketch crop, channels reversed); all three crops use the square
-// window of the vehicle mask's bounding box, resized to out_w x out_h; masked-frame pixels whose (resized) src sketch
-// is all zero become 255.
-struct VuIn { U8View frame, mask, ssk, dsk; const int* geom; float* x; long xsn, xsh, xsw; float* y; long ysn, ysh, ysw; int V, out_h, out_w; };
-__global__ __launch_bounds__(256) void vunet_inputs_kernel(VuIn a, long total) {
+__global__ __launch_bounds__(256) void crop_resize_kernel(CropIn a, long total) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int x = (int)(idx % a.out_w);
     long r = idx / a.out_w;
     const int y = (int)(r % a.out_h);
     const int v = (int)(r / a.out_h);
+    crop_resize_row_px(a, a.src.p + (a.src_per_v ? (long)v * a.src.sn : 0), v, x, y);
+}
+// the image a property of the ROW: blockIdx.y = the window, a.src = the frames' common shape and dense strides
+__global__ __launch_bounds__(256) void crop_resize_frames_kernel(CropIn a, FrameTab t, long per_row) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= per_row) return;
+    const int v = blockIdx.y;
+    crop_resize_row_px(a, t.img[frame_of_row(t, v)], v, (int)(idx % a.out_w), (int)(idx / a.out_w));
+}
+
+// The VUnet's inputs (trajectory_inference.py:203-228): x = cat[to_tensor(masked frame crop), to_tensor(src sketch
+// crop, channels reversed)], y_tilde = to_tensor(dst sketch crop, channels reversed); all three crops use the square
+// window of the vehicle mask's bounding box, resized to out_w x out_h; masked-frame pixels whose (resized) src sketch
+// is all zero become 255.
+struct VuIn { U8View frame, mask, ssk, dsk; const int* geom; float* x; long xsn, xsh, xsw; float* y; long ysn, ysh, ysw; int V, out_h, out_w; };
+// vunet_inputs_row_px: pixel (x, y) of row v's three crops, the masked one cut from frame image `fr` (of a.frame's shape and
+// strides).  The ONE copy of the arithmetic: the two kernels differ only in how a thread finds its row and its frame.
+__device__ __forceinline__ void vunet_inputs_row_px(const VuIn& a, const unsigned char* fr, int v, int x, int y) {
     const int* g = a.geom + v * 8;
     const unsigned char* mk = a.mask.p + (long)v * a.mask.sn;
     const unsigned char* s1 = a.ssk.p + (long)v * a.ssk.sn;
@@ -510,7 +561,7 @@ __global__ __launch_bounds__(256) void vunet_inputs_kernel(VuIn a, long total) {
     int mf[3], ss[3], ds[3];
     crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) {
         if (!((unsigned)px < (unsigned)a.frame.w && (unsigned)py < (unsigned)a.frame.h)) return 0;
-        return mk[(long)py * a.mask.sh + (long)px * a.mask.sw] ? (int)a.frame.p[(long)py * a.frame.sh + (long)px * a.frame.sw + c] : 0;
+        return mk[(long)py * a.mask.sh + (long)px * a.mask.sw] ? (int)fr[(long)py * a.frame.sh + (long)px * a.frame.sw + c] : 0;
     }, mf);
     crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(s1, a.ssk, px, py, c); }, ss);
     crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(s2, a.dsk, px, py, c); }, ds);
@@ -523,6 +574,21 @@ __global__ __launch_bounds__(256) void vunet_inputs_kernel(VuIn a, long total) {
         dx[3 + c] = (float)ss[2 - c] / 255.f * 2.f - 1.f;
         dy[c] = (float)ds[2 - c] / 255.f * 2.f - 1.f;
     }
+}
+__global__ __launch_bounds__(256) void vunet_inputs_kernel(VuIn a, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int x = (int)(idx % a.out_w);
+    long r = idx / a.out_w;
+    const int y = (int)(r % a.out_h);
+    vunet_inputs_row_px(a, a.frame.p, (int)(r / a.out_h), x, y);
+}
+// the frame a property of the ROW: blockIdx.y = the row, a.frame = the frames' common shape and dense strides
+__global__ __launch_bounds__(256) void vunet_inputs_frames_kernel(VuIn a, FrameTab t, long per_row) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= per_row) return;
+    const int v = blockIdx.y;
+    vunet_inputs_row_px(a, t.img[frame_of_row(t, v)], v, (int)(idx % a.out_w), (int)(idx / a.out_w));
 }
 
 // Bounding box of the non-zero pixels of V masks (np.nonzero + min / max, warp_learn/models.py:333-336,
@@ -617,158 +683,6 @@ __global__ __launch_bounds__(256) void keypoints_to_frame_kernel(const int* idx,
     out[2 * i + 1] = (float)(fy * (double)(g[3] - g[1]) + (double)g[1] - (double)g[5]);
 }
 
-// ------------------------------------------------------------------------------------------------ frame-indexed glue
-// The three kernels above that read the frame, with the frame a property of the ROW (VehiclePipeline.run_frames_batched: the
-// first frames of several scenes as one pass).  FrameTab travels BY VALUE in the kernel arguments (~0.8 KB): the host has
-// checked every entry before the launch, which it could not do for a table in device memory.  Rows [rows[f], rows[f + 1]) read
-// image img[f] (dense u8 [H, W, 3]).  blockIdx.y = the row (the frame, for the paste), so the lookup is uniform per block; the
-// per-pixel arithmetic is the device functions of the one-frame kernels, so the bytes are theirs by construction.
-struct FrameTab { const unsigned char* img[FUSG_MAX_FRAMES]; int rows[FUSG_MAX_FRAMES + 1]; int n; };
-__device__ __forceinline__ int frame_of_row(const FrameTab& t, int row) {
-    int f = 0;
-    while (f + 1 < t.n && row >= t.rows[f + 1]) ++f;
-    return f;
-}
-
-// fill_poly_planes_batch_kernel with the frame a property of the JOB: blockIdx.y = job * n_planes + plane, and the table's rows
-// count jobs.  A frame without jobs is never looked up, so never read.  The loop is that kernel's, statement for statement (a
-// shared device function changed its instructions, tools/isa_digest.py): what one of the two learns, the other is taught.
-__global__ __launch_bounds__(256) void fill_poly_planes_frames_kernel(U8View frame, FrameTab t, const int* __restrict__ pts_xy,
-                                                                      const int* __restrict__ nverts, int n_planes, U8View dst,
-                                                                      long plane_bytes) {
-    __shared__ int spx[MAXV], spy[MAXV], snv;
-    const int q = blockIdx.y, tid = threadIdx.x;
-    frame.p = const_cast<unsigned char*>(t.img[frame_of_row(t, q / n_planes)]);       // uniform per block
-    if (tid < MAXV) {
-        spx[tid] = pts_xy[((long)q * MAXV + tid) * 2];
-        spy[tid] = pts_xy[((long)q * MAXV + tid) * 2 + 1];
-    }
-    if (tid == 0) {
-        const int n = nverts[q];
-        snv = n < 0 ? 0 : (n > MAXV ? MAXV : n);
-    }
-    __syncthreads();
-    const int nv = snv, W = dst.w, H = dst.h;
-    long bx0 = W, by0 = H, bx1 = -1, by1 = -1;
-    bool wide = false;
-    for (int i = 0; i < nv; ++i) {
-        const long x = spx[i], y = spy[i];
-        bx0 = x < bx0 ? x : bx0; bx1 = x > bx1 ? x : bx1; by0 = y < by0 ? y : by0; by1 = y > by1 ? y : by1;
-        wide = wide || x < -POLY_BOX_SAFE || x > POLY_BOX_SAFE || y < -POLY_BOX_SAFE || y > POLY_BOX_SAFE;
-    }
-    if (wide) { bx0 = 0; by0 = 0; bx1 = W - 1; by1 = H - 1; }
-    bx0 = bx0 < 0 ? 0 : bx0; by0 = by0 < 0 ? 0 : by0; bx1 = bx1 > W - 1 ? W - 1 : bx1; by1 = by1 > H - 1 ? H - 1 : by1;
-    const bool empty = bx0 > bx1 || by0 > by1;
-    unsigned char* d = dst.p + (long)q * dst.sn;
-    const long head = ((16 - (long)((unsigned long)d & 15)) & 15) < plane_bytes ? ((16 - (long)((unsigned long)d & 15)) & 15) : plane_bytes;
-    const long pieces = 1 + (plane_bytes - head + 15) / 16;
-    for (long k = (long)blockIdx.x * 256 + tid; k < pieces; k += (long)gridDim.x * 256) {
-        const long s = k == 0 ? 0 : head + 16 * (k - 1);
-        const long e0 = k == 0 ? head : s + 16;
-        const long e = e0 < plane_bytes ? e0 : plane_bytes;
-        if (s >= e) continue;
-        const long p0 = s / 3, p1 = (e - 1) / 3;
-        const long y0 = p0 / W, y1 = p1 / W;
-        bool zero = empty || y1 < by0 || y0 > by1;
-        if (!zero && y0 == y1) zero = p1 - y1 * W < bx0 || p0 - y0 * W > bx1;
-        unsigned char b[16];
-        if (zero) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) b[i] = 0;
-        } else {
-            unsigned in = 0;                                              // bit (pixel - p0): inside or on the outline
-            for (long p = p0; p <= p1; ++p) {
-                const long y = p / W, x = p - y * W;
-                if (x >= bx0 && x <= bx1 && y >= by0 && y <= by1 && poly_inside((int)x, (int)y, nv, spx, spy)) in |= 1u << (p - p0);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const long o = s + i, p = o / 3;
-                b[i] = 0;
-                if (o < e && ((in >> (p - p0)) & 1)) {
-                    const long y = p / W, x = p - y * W;
-                    b[i] = frame.p[y * frame.sh + x * frame.sw + (o - p * 3)];
-                }
-            }
-        }
-        if (e - s == 16 && k > 0) {                                       // 16-byte aligned by construction
-            uint4 v;
-            v.x = b[0] | (b[1] << 8) | (b[2] << 16) | ((unsigned)b[3] << 24);
-            v.y = b[4] | (b[5] << 8) | (b[6] << 16) | ((unsigned)b[7] << 24);
-            v.z = b[8] | (b[9] << 8) | (b[10] << 16) | ((unsigned)b[11] << 24);
-            v.w = b[12] | (b[13] << 8) | (b[14] << 16) | ((unsigned)b[15] << 24);
-            *reinterpret_cast<uint4*>(d + s) = v;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (s + i < e) d[s + i] = b[i];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void crop_resize_frames_kernel(CropIn a, FrameTab t, long per_row) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= per_row) return;
-    const int v = blockIdx.y;
-    const int x = (int)(idx % a.out_w), y = (int)(idx / a.out_w);
-    const unsigned char* img = t.img[frame_of_row(t, v)];
-    const U8View& sv = a.src;                                          // the frames' common shape and dense strides
-    int rgb[3];
-    crop_resize_px(a.geom + v * 8, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(img, sv, px, py, c); }, rgb);
-    if (a.mode == 0) {
-        unsigned char* d = a.dst8.p + (long)v * a.dst8.sn + (long)y * a.dst8.sh + (long)x * a.dst8.sw;
-        d[0] = (unsigned char)rgb[0]; d[1] = (unsigned char)rgb[1]; d[2] = (unsigned char)rgb[2];
-        return;
-    }
-    float* d = a.dstf + (long)v * a.dsn + (long)y * a.dsh + (long)x * a.dsw;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float f = (float)rgb[c] / 255.f;
-        d[c] = a.mode == 1 ? (f - a.mean[c]) / a.stdv[c] : f * 2.f - 1.f;
-    }
-}
-
-__global__ __launch_bounds__(256) void vunet_inputs_frames_kernel(VuIn a, FrameTab t, long per_row) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= per_row) return;
-    const int v = blockIdx.y;
-    const int x = (int)(idx % a.out_w), y = (int)(idx / a.out_w);
-    const unsigned char* fr = t.img[frame_of_row(t, v)];
-    const int* g = a.geom + v * 8;
-    const unsigned char* mk = a.mask.p + (long)v * a.mask.sn;
-    const unsigned char* s1 = a.ssk.p + (long)v * a.ssk.sn;
-    const unsigned char* s2 = a.dsk.p + (long)v * a.dsk.sn;
-    int mf[3], ss[3], ds[3];
-    crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) {
-        if (!((unsigned)px < (unsigned)a.frame.w && (unsigned)py < (unsigned)a.frame.h)) return 0;
-        return mk[(long)py * a.mask.sh + (long)px * a.mask.sw] ? (int)fr[(long)py * a.frame.sh + (long)px * a.frame.sw + c] : 0;
-    }, mf);
-    crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(s1, a.ssk, px, py, c); }, ss);
-    crop_resize_px(g, a.out_w, a.out_h, x, y, [&](int px, int py, int c) { return crop_fetch(s2, a.dsk, px, py, c); }, ds);
-    if ((ss[0] | ss[1] | ss[2]) == 0) mf[0] = mf[1] = mf[2] = 255;
-    float* dx = a.x + (long)v * a.xsn + (long)y * a.xsh + (long)x * a.xsw;
-    float* dy = a.y + (long)v * a.ysn + (long)y * a.ysh + (long)x * a.ysw;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        dx[c] = (float)mf[c] / 255.f * 2.f - 1.f;
-        dx[3 + c] = (float)ss[2 - c] / 255.f * 2.f - 1.f;
-        dy[c] = (float)ds[2 - c] / 255.f * 2.f - 1.f;
-    }
-}
-
-// blockIdx.y = frame f, whose layers are rows t.rows[f] .. t.rows[f + 1] - 1 (none: the frame is a copy of its base t.img[f])
-__global__ __launch_bounds__(256) void paste_ragged_kernel(PasteIn a, FrameTab t, long total) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int f = blockIdx.y;
-    const int x = (int)(idx % a.frame.w), y = (int)(idx / a.frame.w);
-    unsigned char* d = a.frame.p + (long)f * a.frame.sn + (long)y * a.frame.sh + (long)x * a.frame.sw;
-    a.V = t.rows[f + 1] - t.rows[f];
-    if (paste_layers_px(a, t.rows[f], x, y, d)) return;
-    const unsigned char* b = t.img[f] + idx * 3;
-    d[0] = b[0]; d[1] = b[1]; d[2] = b[2];
-}
-
 }  // namespace fusg
 
 using namespace fusg;
@@ -802,7 +716,7 @@ extern "C" int fusg_warp_perspective_frames_u8(const fusg_tensor* src, const dou
 
 static int warp_perspective_clips_u8_impl(ClipTab t, int32_t H, int32_t W, const double* minv, const int32_t* index, int32_t jobs,
                                           const fusg_tensor* dst, void* stream) {
-    const U8View src{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
+    const U8View src = dense_hwc3(H, W);
     const int pixels = H * W;
     hipLaunchKernelGGL(warp_perspective_clips_u8_kernel, dim3(blocks2d(pixels), (unsigned)jobs), dim3(256), 0, (hipStream_t)stream, t, src,
                        minv, (const int*)index, u8view(*dst), pixels);
@@ -816,7 +730,7 @@ extern "C" int fusg_warp_perspective_clips_u8(const void* const* srcs, const int
     const char* what = "warp_perspective_clips_u8";
     FUSG_CHECK(n_clips >= 1 && n_clips <= FUSG_MAX_FRAMES, "%s: n_clips = %d (1..%d)", what, n_clips, FUSG_MAX_FRAMES);
     FUSG_CHECK(srcs && src_images && dst_first && dst, "%s: a table or dst is null (srcs, src_images, dst_first, dst)", what);
-    FUSG_CHECK(H >= 1 && W >= 1 && H < 32768 && W < 32768, "%s: planes of %d x %d", what, H, W);
+    FUSG_CHECK(frame_size_ok(H, W), "%s: planes of %d x %d", what, H, W);
     FUSG_CHECK(jobs >= 0 && dst->n >= 0, "%s: jobs = %d, dst->n = %ld", what, jobs, (long)dst->n);
     ClipTab t;
     memset(&t, 0, sizeof(t));
@@ -843,13 +757,9 @@ extern "C" int fusg_warp_perspective_clips_u8(const void* const* srcs, const int
     FUSG_CHECK(jobs <= 65535, "%s: %d jobs (at most 65535 per launch)", what, jobs);
     FUSG_CHECK(is_u8_hwc(*dst, 3) && dst->h == H && dst->w == W && dst->sw == 3 && dst->sh == 3L * W && dst->sn == 3L * H * W,
                "%s: dst is dense u8 [n, H, W, 3] of %d x %d", what, H, W);
-    const unsigned char* d0 = (const unsigned char*)dst->data;
-    const unsigned char* d1 = d0 + dst->n * dst->sn;
-    for (int c = 0; c < n_clips; ++c) {
-        const unsigned char* b = t.src[c];
-        if (t.images[c] == 0) continue;
-        FUSG_CHECK(b + (long)t.images[c] * dst->sn <= d0 || b >= d1, "%s: clip %d's source planes overlap dst (in-place not supported)", what, c);
-    }
+    for (int c = 0; c < n_clips; ++c)
+        FUSG_CHECK(t.images[c] == 0 || apart_from_dst(t.src[c], (long)t.images[c] * dst->sn, *dst, dst->sn),
+                   "%s: clip %d's source planes overlap dst (in-place not supported)", what, c);
     return fusg::plan_dispatch(warp_perspective_clips_u8_impl, stream, t, H, W, minv, index, jobs, dst);
 }
 
@@ -870,25 +780,33 @@ extern "C" int fusg_fill_poly_planes_u8(const fusg_tensor* frame, const int32_t*
     return FUSG_OK;
 }
 
-static int fill_poly_planes_batch_u8_impl(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
-                                          int32_t n_planes, const fusg_tensor* dst, void* stream) {
+// The launch of both device-polygon entries.  frame.p set: every job reads that one frame, through its own strides (its
+// pointer stays a kernel argument: read through a table of one frame, the same loop took 5 % longer at 64 vehicles,
+// profiles/glue_kernels_time_table_of_one.json); else `frame` = the frames' shape and strides and t says which job reads which frame.
+static int fill_poly_planes_jobs_impl(const char* what, U8View frame, FrameTab t, const int32_t* pts_xy, const int32_t* nverts,
+                                      int32_t n_jobs, int32_t n_planes, const fusg_tensor* dst, void* stream) {
+    const long plane_bytes = 3 * dst->h * dst->w;
+    const long pieces = 1 + (plane_bytes + 15) / 16;
+    const dim3 grid((unsigned)((pieces + 255) / 256), (unsigned)(n_jobs * n_planes));
+    if (frame.p)
+        hipLaunchKernelGGL(fill_poly_planes_batch_kernel, grid, dim3(256), 0, (hipStream_t)stream, frame, (const int*)pts_xy,
+                           (const int*)nverts, u8view(*dst), plane_bytes);
+    else
+        hipLaunchKernelGGL(fill_poly_planes_frames_kernel, grid, dim3(256), 0, (hipStream_t)stream, frame, t, (const int*)pts_xy,
+                           (const int*)nverts, (int)n_planes, u8view(*dst), plane_bytes);
+    FUSG_LAUNCH_CHECK(what);
+    return FUSG_OK;
+}
+extern "C" int fusg_fill_poly_planes_batch_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
+                                              int32_t n_planes, const fusg_tensor* dst, void* stream) {
     FUSG_CHECK(frame && dst && pts_xy && nverts && n_jobs >= 0 && n_planes >= 1 && n_planes <= 8 && (long)n_jobs * n_planes <= 65535,
                "fill_poly_planes_batch_u8: arguments (1..8 planes, n_jobs * n_planes <= 65535)");
     if (n_jobs == 0) return FUSG_OK;
     FUSG_CHECK(is_u8_hwc(*frame, 3) && is_u8_hwc(*dst, 3) && frame->n == 1 && dst->n == (long)n_jobs * n_planes && frame->h == dst->h &&
                frame->w == dst->w && dst->sw == 3 && dst->sh == 3 * dst->w && dst->sn >= 3 * dst->h * dst->w,
                "fill_poly_planes_batch_u8: shapes (dst [n_jobs * n_planes] planes of contiguous rows)");
-    const long plane_bytes = 3 * dst->h * dst->w;
-    const long pieces = 1 + (plane_bytes + 15) / 16;
-    const unsigned bx = (unsigned)((pieces + 255) / 256);
-    hipLaunchKernelGGL(fill_poly_planes_batch_kernel, dim3(bx, (unsigned)(n_jobs * n_planes)), dim3(256), 0, (hipStream_t)stream,
-                       u8view(*frame), (const int*)pts_xy, (const int*)nverts, u8view(*dst), plane_bytes);
-    FUSG_LAUNCH_CHECK("fill_poly_planes_batch_u8");
-    return FUSG_OK;
-}
-extern "C" int fusg_fill_poly_planes_batch_u8(const fusg_tensor* frame, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
-                                              int32_t n_planes, const fusg_tensor* dst, void* stream) {
-    return fusg::plan_dispatch(fill_poly_planes_batch_u8_impl, stream, frame, pts_xy, nverts, n_jobs, n_planes, dst);
+    return fusg::plan_dispatch(fill_poly_planes_jobs_impl, stream, "fill_poly_planes_batch_u8", u8view(*frame), FrameTab{}, pts_xy, nverts,
+                               n_jobs, n_planes, dst);
 }
 
 static int icn_inputs_impl(const fusg_tensor* sketch, const fusg_tensor* central, const fusg_tensor* planes, const int32_t* geom,
@@ -921,16 +839,25 @@ static int lab2bgr_u8_impl(const fusg_tensor* src, const fusg_tensor* dst, void*
 }
 extern "C" int fusg_lab2bgr_u8(const fusg_tensor* src, const fusg_tensor* dst, void* stream) { return fusg::plan_dispatch(lab2bgr_u8_impl, stream, src, dst); }
 
+// The kernel arguments of every paste entry: V layers per frame (the ragged kernel sets its own per frame) onto `frame`; a
+// launch without layers passes no crops, so none of their fields is looked at.
+static PasteIn paste_in(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
+                        const int32_t* rect_geom, const fusg_tensor& frame, int V) {
+    PasteIn a;
+    memset(&a, 0, sizeof(a));
+    a.frame = u8view(frame); a.geom = geom; a.V = V;
+    if (net) { a.net = u8view(*net); a.masks = u8view(*masks); }
+    if (net && rect) { a.rect = u8view(*rect); a.rgeom = rect_geom; }
+    return a;
+}
+
 static int paste_layers_u8_impl(const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
                                 const int32_t* rect_geom, const fusg_tensor* frame, void* stream) {
     FUSG_CHECK(net && masks && geom && frame && is_u8_hwc(*net, 3) && is_u8_hwc(*frame, 3) && frame->n == 1 && masks->data &&
                masks->dtype == FUSG_U8 && masks->c == 1 && masks->n == net->n && masks->h == frame->h && masks->w == frame->w, "paste_back_u8: shapes");
     FUSG_CHECK((rect == nullptr) == (rect_geom == nullptr) && (!rect || (is_u8_hwc(*rect, 3) && rect->n == net->n)),
                "paste_layers_u8: the box images come with their rectangles, one per vehicle");
-    PasteIn a;
-    memset(&a, 0, sizeof(a));
-    a.net = u8view(*net); a.masks = u8view(*masks); a.frame = u8view(*frame); a.geom = geom; a.V = (int)net->n;
-    if (rect) { a.rect = u8view(*rect); a.rgeom = rect_geom; }
+    const PasteIn a = paste_in(net, masks, geom, rect, rect_geom, *frame, (int)net->n);
     const long total = frame->h * frame->w;
     hipLaunchKernelGGL(paste_back_kernel, dim3(blocks2d(total)), dim3(256), 0, (hipStream_t)stream, a, total);
     FUSG_LAUNCH_CHECK("paste_back_u8");
@@ -954,10 +881,7 @@ static int paste_layers_frames_u8_impl(const fusg_tensor* net, const fusg_tensor
                (long)net->n, (long)masks->n, frames);
     FUSG_CHECK((rect == nullptr) == (rect_geom == nullptr) && (!rect || (is_u8_hwc(*rect, 3) && rect->n == net->n)),
                "paste_layers_frames_u8: the box images come with their rectangles, one per crop");
-    PasteIn a;
-    memset(&a, 0, sizeof(a));
-    a.net = u8view(*net); a.masks = u8view(*masks); a.frame = u8view(*dst); a.geom = geom; a.V = (int)(net->n / frames);
-    if (rect) { a.rect = u8view(*rect); a.rgeom = rect_geom; }
+    const PasteIn a = paste_in(net, masks, geom, rect, rect_geom, *dst, (int)(net->n / frames));
     const long total = dst->h * dst->w;
     hipLaunchKernelGGL(paste_frames_kernel, dim3(blocks2d(total), (unsigned)frames), dim3(256), 0, (hipStream_t)stream, a,
                        (const unsigned char* const*)bases, total);
@@ -971,33 +895,48 @@ extern "C" int fusg_paste_layers_frames_u8(const fusg_tensor* net, const fusg_te
 }
 
 struct Norm3 { float m[3], s[3]; int has; };      // mode 1's mean / std, captured by value (host arrays at the ABI)
+static Norm3 norm3(const float* mean3, const float* std3) {
+    Norm3 nm = {{0, 0, 0}, {1, 1, 1}, (mean3 && std3) ? 1 : 0};
+    if (nm.has) for (int c = 0; c < 3; ++c) { nm.m[c] = mean3[c]; nm.s[c] = std3[c]; }
+    return nm;
+}
+// The kernel arguments of both crop entries, checked by the caller: dst's rows are windows of images of src's shape and strides.
+static CropIn crop_in(const U8View& src, int src_per_v, const int32_t* geom, const fusg_tensor& dst, int mode, const Norm3& nm) {
+    CropIn a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.src_per_v = src_per_v; a.geom = geom; a.V = (int)dst.n; a.out_h = (int)dst.h; a.out_w = (int)dst.w; a.mode = mode;
+    if (mode == 0) a.dst8 = u8view(dst);
+    else {
+        a.dstf = (float*)dst.data; a.dsn = dst.sn; a.dsh = dst.sh; a.dsw = dst.sw;
+        for (int c = 0; c < 3; ++c) { a.mean[c] = nm.m[c]; a.stdv[c] = nm.s[c]; }
+    }
+    return a;
+}
 static int crop_resize_impl(const fusg_tensor* src, const int32_t* geom, const fusg_tensor* dst, int32_t mode, Norm3 nm, void* stream) {
     FUSG_CHECK(src && geom && dst && is_u8_hwc(*src, 3), "crop_resize_u8: u8 HWC source of 3 channels");
     FUSG_CHECK(mode >= 0 && mode <= 2 && (src->n == 1 || src->n == dst->n) && dst->n >= 1 && dst->h >= 1 && dst->w >= 1, "crop_resize_u8: mode / batch");
-    CropIn a;
-    memset(&a, 0, sizeof(a));
-    a.src = u8view(*src); a.geom = geom; a.V = (int)dst->n; a.out_h = (int)dst->h; a.out_w = (int)dst->w; a.mode = mode;
-    a.src_per_v = src->n == 1 ? 0 : 1;
-    if (mode == 0) {
-        FUSG_CHECK(is_u8_hwc(*dst, 3) && dst->data != src->data, "crop_resize_u8: mode 0 needs a u8 HWC destination (not in place)");
-        a.dst8 = u8view(*dst);
-    } else {
-        FUSG_CHECK(is_nhwc(*dst) && dst->c == 3, "crop_resize_u8: modes 1 / 2 need an NHWC-physical f32 destination of 3 channels");
-        a.dstf = (float*)dst->data; a.dsn = dst->sn; a.dsh = dst->sh; a.dsw = dst->sw;
-        if (mode == 1) {
-            FUSG_CHECK(nm.has, "crop_resize_u8: mode 1 needs mean / std (host arrays of 3)");
-            for (int c = 0; c < 3; ++c) { a.mean[c] = nm.m[c]; a.stdv[c] = nm.s[c]; }
-        }
-    }
+    if (mode == 0) FUSG_CHECK(is_u8_hwc(*dst, 3) && dst->data != src->data, "crop_resize_u8: mode 0 needs a u8 HWC destination (not in place)");
+    else FUSG_CHECK(is_nhwc(*dst) && dst->c == 3, "crop_resize_u8: modes 1 / 2 need an NHWC-physical f32 destination of 3 channels");
+    FUSG_CHECK(mode != 1 || nm.has, "crop_resize_u8: mode 1 needs mean / std (host arrays of 3)");
+    const CropIn a = crop_in(u8view(*src), src->n == 1 ? 0 : 1, geom, *dst, mode, nm);
     const long total = (long)a.V * a.out_h * a.out_w;
     hipLaunchKernelGGL(crop_resize_kernel, dim3(blocks2d(total)), dim3(256), 0, (hipStream_t)stream, a, total);
     FUSG_LAUNCH_CHECK("crop_resize_u8");
     return FUSG_OK;
 }
 extern "C" int fusg_crop_resize_u8(const fusg_tensor* src, const int32_t* geom, const fusg_tensor* dst, int32_t mode, const float* mean3, const float* std3, void* stream) {
-    Norm3 nm = {{0, 0, 0}, {1, 1, 1}, (mean3 && std3) ? 1 : 0};
-    if (nm.has) for (int c = 0; c < 3; ++c) { nm.m[c] = mean3[c]; nm.s[c] = std3[c]; }
-    return fusg::plan_dispatch(crop_resize_impl, stream, src, geom, dst, mode, nm);
+    return fusg::plan_dispatch(crop_resize_impl, stream, src, geom, dst, mode, norm3(mean3, std3));
+}
+
+// The kernel arguments of both VUnet-input entries, checked by the caller: `frame` = the frame image(s)' shape and strides.
+static VuIn vu_in(const U8View& frame, const fusg_tensor& masks, const fusg_tensor& src_sketch, const fusg_tensor& dst_sketch,
+                  const int32_t* geom, const fusg_tensor& x, const fusg_tensor& y) {
+    VuIn a;
+    a.frame = frame; a.mask = u8view(masks); a.ssk = u8view(src_sketch); a.dsk = u8view(dst_sketch);
+    a.geom = geom; a.x = (float*)x.data; a.xsn = x.sn; a.xsh = x.sh; a.xsw = x.sw;
+    a.y = (float*)y.data; a.ysn = y.sn; a.ysh = y.sh; a.ysw = y.sw;
+    a.V = (int)masks.n; a.out_h = (int)x.h; a.out_w = (int)x.w;
+    return a;
 }
 
 static int vunet_inputs_impl(const fusg_tensor* frame, const fusg_tensor* masks, const fusg_tensor* src_sketch, const fusg_tensor* dst_sketch,
@@ -1009,12 +948,7 @@ static int vunet_inputs_impl(const fusg_tensor* frame, const fusg_tensor* masks,
                "vunet_inputs: masks [V, 1, H, W] u8 and sketches of the frame's size");
     FUSG_CHECK(is_nhwc(*x) && is_nhwc(*y) && x->c == 6 && y->c == 3 && x->n == masks->n && y->n == masks->n && x->h == y->h && x->w == y->w,
                "vunet_inputs: x [V, 6, h, w] and y [V, 3, h, w] NHWC-physical f32");
-    VuIn a;
-    a.frame = u8view(*frame); a.ssk = u8view(*src_sketch); a.dsk = u8view(*dst_sketch);
-    a.mask = U8View{(unsigned char*)masks->data, masks->sn, masks->sh, masks->sw, (int)masks->n, (int)masks->h, (int)masks->w};
-    a.geom = geom; a.x = (float*)x->data; a.xsn = x->sn; a.xsh = x->sh; a.xsw = x->sw;
-    a.y = (float*)y->data; a.ysn = y->sn; a.ysh = y->sh; a.ysw = y->sw;
-    a.V = (int)masks->n; a.out_h = (int)x->h; a.out_w = (int)x->w;
+    const VuIn a = vu_in(u8view(*frame), *masks, *src_sketch, *dst_sketch, geom, *x, *y);
     const long total = (long)a.V * a.out_h * a.out_w;
     hipLaunchKernelGGL(vunet_inputs_kernel, dim3(blocks2d(total)), dim3(256), 0, (hipStream_t)stream, a, total);
     FUSG_LAUNCH_CHECK("vunet_inputs");
@@ -1026,8 +960,7 @@ extern "C" int fusg_vunet_inputs(const fusg_tensor* frame, const fusg_tensor* ma
 }
 
 static int mask_bbox_geom_impl(const fusg_tensor* masks, int32_t* bbox, int32_t* geom, void* stream) {
-    FUSG_CHECK(masks && bbox && geom && masks->data && masks->dtype == FUSG_U8 && masks->c == 1 && masks->n >= 1 && masks->h >= 1 && masks->w >= 1 &&
-               masks->h < 32768 && masks->w < 32768, "mask_bbox_geom: masks [V, 1, H, W] u8");
+    FUSG_CHECK(masks && bbox && geom && masks->data && masks->dtype == FUSG_U8 && masks->c == 1 && masks->n >= 1 && frame_size_ok(masks->h, masks->w), "mask_bbox_geom: masks [V, 1, H, W] u8");
     const int V = (int)masks->n;
     U8View m{(unsigned char*)masks->data, masks->sn, masks->sh, masks->sw, V, (int)masks->h, (int)masks->w};
     hipStream_t s = (hipStream_t)stream;
@@ -1073,17 +1006,6 @@ static int frame_table(const char* what, const void* const* frames, const int32_
     return FUSG_OK;
 }
 
-static int fill_poly_planes_frames_u8_impl(FrameTab t, int32_t H, int32_t W, const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs,
-                                           int32_t n_planes, const fusg_tensor* dst, void* stream) {
-    const U8View frame{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
-    const long plane_bytes = 3 * dst->h * dst->w;
-    const long pieces = 1 + (plane_bytes + 15) / 16;
-    const unsigned bx = (unsigned)((pieces + 255) / 256);
-    hipLaunchKernelGGL(fill_poly_planes_frames_kernel, dim3(bx, (unsigned)(n_jobs * n_planes)), dim3(256), 0, (hipStream_t)stream, frame, t,
-                       (const int*)pts_xy, (const int*)nverts, (int)n_planes, u8view(*dst), plane_bytes);
-    FUSG_LAUNCH_CHECK("fill_poly_planes_frames_u8");
-    return FUSG_OK;
-}
 extern "C" int fusg_fill_poly_planes_frames_u8(const void* const* frames, const int32_t* frame_rows, int32_t n_frames, int32_t H, int32_t W,
                                                const int32_t* pts_xy, const int32_t* nverts, int32_t n_jobs, int32_t n_planes,
                                                const fusg_tensor* dst, void* stream) {
@@ -1093,29 +1015,18 @@ extern "C" int fusg_fill_poly_planes_frames_u8(const void* const* frames, const 
     if (int rc = frame_table(what, frames, frame_rows, n_frames, n_jobs, t)) return rc;
     FUSG_CHECK(pts_xy && nverts && dst, "%s: pts_xy, nverts or dst is null", what);
     FUSG_CHECK(n_planes >= 1 && n_planes <= 8 && (long)n_jobs * n_planes <= 65535, "%s: arguments (1..8 planes, n_jobs * n_planes <= 65535)", what);
-    FUSG_CHECK(H >= 1 && W >= 1 && H < 32768 && W < 32768, "%s: frames of %d x %d", what, H, W);
+    FUSG_CHECK(frame_size_ok(H, W), "%s: frames of %d x %d", what, H, W);
     if (n_jobs == 0) return FUSG_OK;
     FUSG_CHECK(is_u8_hwc(*dst, 3) && dst->n == (long)n_jobs * n_planes && dst->h == H && dst->w == W && dst->sw == 3 && dst->sh == 3 * dst->w &&
                dst->sn >= 3 * dst->h * dst->w, "%s: shapes (dst [n_jobs * n_planes] planes of H x W x 3, contiguous rows)", what);
-    for (int f = 0; f < n_frames; ++f) {
-        const unsigned char* b = (const unsigned char*)frames[f];
-        const unsigned char* d0 = (const unsigned char*)dst->data;
-        FUSG_CHECK(b + 3L * H * W <= d0 || b >= d0 + (dst->n - 1) * dst->sn + 3L * H * W, "%s: frame %d overlaps dst (the frames are read only)", what, f);
-    }
-    return fusg::plan_dispatch(fill_poly_planes_frames_u8_impl, stream, t, H, W, pts_xy, nverts, n_jobs, n_planes, dst);
+    for (int f = 0; f < n_frames; ++f)
+        FUSG_CHECK(apart_from_dst(frames[f], 3L * H * W, *dst, 3L * H * W), "%s: frame %d overlaps dst (the frames are read only)", what, f);
+    return fusg::plan_dispatch(fill_poly_planes_jobs_impl, stream, what, dense_hwc3(H, W), t, pts_xy, nverts, n_jobs, n_planes, dst);
 }
 
 static int crop_resize_frames_impl(FrameTab t, int32_t H, int32_t W, const int32_t* geom, const fusg_tensor* dst, int32_t mode, Norm3 nm,
                                    void* stream) {
-    CropIn a;
-    memset(&a, 0, sizeof(a));
-    a.src = U8View{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
-    a.geom = geom; a.V = (int)dst->n; a.out_h = (int)dst->h; a.out_w = (int)dst->w; a.mode = mode;
-    if (mode == 0) a.dst8 = u8view(*dst);
-    else {
-        a.dstf = (float*)dst->data; a.dsn = dst->sn; a.dsh = dst->sh; a.dsw = dst->sw;
-        for (int c = 0; c < 3; ++c) { a.mean[c] = nm.m[c]; a.stdv[c] = nm.s[c]; }
-    }
+    const CropIn a = crop_in(dense_hwc3(H, W), 0, geom, *dst, mode, nm);
     const long per_row = (long)a.out_h * a.out_w;
     hipLaunchKernelGGL(crop_resize_frames_kernel, dim3(blocks2d(per_row), (unsigned)a.V), dim3(256), 0, (hipStream_t)stream, a, t, per_row);
     FUSG_LAUNCH_CHECK("crop_resize_frames_u8");
@@ -1128,31 +1039,21 @@ extern "C" int fusg_crop_resize_frames_u8(const void* const* frames, const int32
     FUSG_CHECK(dst && dst->n >= 0, "%s: dst is null", what);
     FrameTab t;
     if (int rc = frame_table(what, frames, frame_rows, n_frames, dst->n, t)) return rc;
-    FUSG_CHECK(H >= 1 && W >= 1 && H < 32768 && W < 32768, "%s: frames of %d x %d", what, H, W);
+    FUSG_CHECK(frame_size_ok(H, W), "%s: frames of %d x %d", what, H, W);
     FUSG_CHECK(mode >= 0 && mode <= 2, "%s: mode %d (0..2)", what, mode);
     if (dst->n == 0) return FUSG_OK;
     FUSG_CHECK(geom != nullptr && dst->h >= 1 && dst->w >= 1, "%s: geom is null or dst is empty", what);
-    Norm3 nm = {{0, 0, 0}, {1, 1, 1}, (mean3 && std3) ? 1 : 0};
+    const Norm3 nm = norm3(mean3, std3);
     if (mode == 0) FUSG_CHECK(is_u8_hwc(*dst, 3), "%s: mode 0 needs a u8 HWC destination", what);
     else FUSG_CHECK(is_nhwc(*dst) && dst->c == 3, "%s: modes 1 / 2 need an NHWC-physical f32 destination of 3 channels", what);
-    if (mode == 1) {
-        FUSG_CHECK(nm.has, "%s: mode 1 needs mean / std (host arrays of 3)", what);
-        for (int c = 0; c < 3; ++c) { nm.m[c] = mean3[c]; nm.s[c] = std3[c]; }
-    }
+    FUSG_CHECK(mode != 1 || nm.has, "%s: mode 1 needs mean / std (host arrays of 3)", what);
     for (int f = 0; f < n_frames; ++f) FUSG_CHECK(frames[f] != dst->data, "%s: not in place", what);
     return fusg::plan_dispatch(crop_resize_frames_impl, stream, t, H, W, geom, dst, mode, nm);
 }
 
 static int vunet_inputs_frames_impl(FrameTab t, const fusg_tensor* masks, const fusg_tensor* src_sketch, const fusg_tensor* dst_sketch,
                                     const int32_t* geom, const fusg_tensor* x, const fusg_tensor* y, void* stream) {
-    VuIn a;
-    const int H = (int)masks->h, W = (int)masks->w;
-    a.frame = U8View{nullptr, (long)H * W * 3, (long)W * 3, 3, 1, H, W};
-    a.ssk = u8view(*src_sketch); a.dsk = u8view(*dst_sketch);
-    a.mask = U8View{(unsigned char*)masks->data, masks->sn, masks->sh, masks->sw, (int)masks->n, H, W};
-    a.geom = geom; a.x = (float*)x->data; a.xsn = x->sn; a.xsh = x->sh; a.xsw = x->sw;
-    a.y = (float*)y->data; a.ysn = y->sn; a.ysh = y->sh; a.ysw = y->sw;
-    a.V = (int)masks->n; a.out_h = (int)x->h; a.out_w = (int)x->w;
+    const VuIn a = vu_in(dense_hwc3((int)masks->h, (int)masks->w), *masks, *src_sketch, *dst_sketch, geom, *x, *y);
     const long per_row = (long)a.out_h * a.out_w;
     hipLaunchKernelGGL(vunet_inputs_frames_kernel, dim3(blocks2d(per_row), (unsigned)a.V), dim3(256), 0, (hipStream_t)stream, a, t, per_row);
     FUSG_LAUNCH_CHECK("vunet_inputs_frames");
@@ -1171,7 +1072,7 @@ extern "C" int fusg_vunet_inputs_frames(const void* const* frames, const int32_t
     if (masks->n == 0) return FUSG_OK;
     FUSG_CHECK(geom != nullptr, "%s: geom is null", what);
     FUSG_CHECK(is_u8_hwc(*src_sketch, 3) && is_u8_hwc(*dst_sketch, 3) && masks->data && masks->dtype == FUSG_U8 && masks->c == 1 &&
-               masks->h >= 1 && masks->w >= 1 && masks->h < 32768 && masks->w < 32768 && src_sketch->h == masks->h && src_sketch->w == masks->w &&
+               frame_size_ok(masks->h, masks->w) && src_sketch->h == masks->h && src_sketch->w == masks->w &&
                dst_sketch->h == masks->h && dst_sketch->w == masks->w, "%s: masks [rows, 1, H, W] u8 and sketches [rows] of the frames' size", what);
     FUSG_CHECK(is_nhwc(*x) && is_nhwc(*y) && x->c == 6 && y->c == 3 && x->h == y->h && x->w == y->w,
                "%s: x [rows, 6, h, w] and y [rows, 3, h, w] NHWC-physical f32", what);
@@ -1180,11 +1081,7 @@ extern "C" int fusg_vunet_inputs_frames(const void* const* frames, const int32_t
 
 static int paste_layers_ragged_u8_impl(FrameTab t, const fusg_tensor* net, const fusg_tensor* masks, const int32_t* geom, const fusg_tensor* rect,
                                        const int32_t* rect_geom, const fusg_tensor* dst, void* stream) {
-    PasteIn a;
-    memset(&a, 0, sizeof(a));
-    a.frame = u8view(*dst); a.geom = geom;
-    if (t.rows[t.n] > 0) { a.net = u8view(*net); a.masks = u8view(*masks); }
-    if (rect && t.rows[t.n] > 0) { a.rect = u8view(*rect); a.rgeom = rect_geom; }
+    const PasteIn a = paste_in(t.rows[t.n] > 0 ? net : nullptr, masks, geom, rect, rect_geom, *dst, 0);
     const long total = dst->h * dst->w;
     hipLaunchKernelGGL(paste_ragged_kernel, dim3(blocks2d(total), (unsigned)t.n), dim3(256), 0, (hipStream_t)stream, a, t, total);
     FUSG_LAUNCH_CHECK("paste_layers_ragged_u8");
@@ -1206,10 +1103,7 @@ extern "C" int fusg_paste_layers_ragged_u8(const fusg_tensor* net, const fusg_te
         FUSG_CHECK(is_u8_hwc(*net, 3) && masks->data && masks->dtype == FUSG_U8 && masks->c == 1 && masks->h == dst->h && masks->w == dst->w &&
                    (!rect || is_u8_hwc(*rect, 3)), "%s: shapes (crops u8 HWC, masks [rows, 1, H, W] u8 of the frames' size)", what);
     }
-    for (int f = 0; f < n_frames; ++f) {
-        const unsigned char* b = (const unsigned char*)bases[f];
-        const unsigned char* d0 = (const unsigned char*)dst->data;
-        FUSG_CHECK(b + 3 * dst->h * dst->w <= d0 || b >= d0 + dst->n * dst->sn, "%s: base %d overlaps dst (the bases are read only)", what, f);
-    }
+    for (int f = 0; f < n_frames; ++f)
+        FUSG_CHECK(apart_from_dst(bases[f], 3 * dst->h * dst->w, *dst, dst->sn), "%s: base %d overlaps dst (the bases are read only)", what, f);
     return fusg::plan_dispatch(paste_layers_ragged_u8_impl, stream, t, net, masks, geom, rect, rect_geom, dst);
 }

@@ -37,6 +37,22 @@ def _into(out: Optional[torch.Tensor], b: int, c: int, h: int, w: int, dev) -> t
     return out
 
 
+def _crop_dst(out: Optional[torch.Tensor], rows: int, out_hw: Tuple[int, int], mode: int, mean, std, dev):
+    """The destination of both crop wrappers and the arguments that follow `geom` in both library calls: (out - a fresh uint8
+    [rows, h, w, 3] in mode 0, else `out` or a fresh float32 NHWC-physical [rows, 3, h, w] -, (dst descriptor, mode, mean3,
+    std3, stream)); mean3 / std3 are host float arrays, None where not given."""
+    h, w = out_hw
+    if mode == 0:
+        out = torch.empty((rows, h, w, 3), dtype=torch.uint8, device=dev)
+        d = _u8desc(out)
+    else:
+        out = _into(out, rows, 3, h, w, dev)
+        d = ops.desc(out)
+    m = (C.c_float * 3)(*mean) if mean is not None else None
+    s = (C.c_float * 3)(*std) if std is not None else None
+    return out, (C.byref(d), int(mode), m, s, ops.stream_ptr())
+
+
 def crop_resize(src: torch.Tensor, geom: torch.Tensor, out_hw: Tuple[int, int], mode: int = 0,
                 mean: Optional[Sequence[float]] = None, std: Optional[Sequence[float]] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -48,20 +64,9 @@ def crop_resize(src: torch.Tensor, geom: torch.Tensor, out_hw: Tuple[int, int], 
         src = src[None]
     V = int(geom.shape[0])
     assert src.dtype == torch.uint8 and src.shape[0] in (1, V) and geom.dtype == torch.int32 and geom.is_contiguous()
-    h, w = out_hw
-    dev = src.device
-    with torch.cuda.device(dev):
-        if mode == 0:
-            out = torch.empty((V, h, w, 3), dtype=torch.uint8, device=dev)
-            d = _u8desc(out)
-        else:
-            out = _into(out, V, 3, h, w, dev)
-            d = ops.desc(out)
-        m = (C.c_float * 3)(*(mean if mean is not None else (0, 0, 0)))
-        s = (C.c_float * 3)(*(std if std is not None else (1, 1, 1)))
-        L.check(L.lib().fusg_crop_resize_u8(C.byref(_u8desc(src.contiguous())), geom.data_ptr(), C.byref(d), int(mode),
-                                            C.cast(m, C.c_void_p) if mean is not None else None,
-                                            C.cast(s, C.c_void_p) if std is not None else None, ops.stream_ptr()), "crop_resize_u8")
+    with torch.cuda.device(src.device):
+        out, tail = _crop_dst(out, V, out_hw, mode, mean, std, src.device)
+        L.check(L.lib().fusg_crop_resize_u8(C.byref(_u8desc(src.contiguous())), geom.data_ptr(), *tail), "crop_resize_u8")
     return out
 
 
@@ -134,21 +139,9 @@ def crop_resize_frames(frames: Sequence[torch.Tensor], frame_rows: Sequence[int]
     rows = int(geom.shape[0])
     ptrs, offs, keep, (H, W) = _frame_table(frames, frame_rows, rows, "crop_resize_frames")
     assert geom.dtype == torch.int32 and geom.is_contiguous()
-    h, w = out_hw
-    dev = keep[0].device
-    with torch.cuda.device(dev):
-        if mode == 0:
-            out = torch.empty((rows, h, w, 3), dtype=torch.uint8, device=dev)
-            d = _u8desc(out)
-        else:
-            out = _into(out, rows, 3, h, w, dev)
-            d = ops.desc(out)
-        m = (C.c_float * 3)(*(mean if mean is not None else (0, 0, 0)))
-        s = (C.c_float * 3)(*(std if std is not None else (1, 1, 1)))
-        L.check(L.lib().fusg_crop_resize_frames_u8(ptrs, offs, len(keep), H, W, geom.data_ptr(), C.byref(d), int(mode),
-                                                   C.cast(m, C.c_void_p) if mean is not None else None,
-                                                   C.cast(s, C.c_void_p) if std is not None else None, ops.stream_ptr()),
-                "crop_resize_frames_u8")
+    with torch.cuda.device(keep[0].device):
+        out, tail = _crop_dst(out, rows, out_hw, mode, mean, std, keep[0].device)
+        L.check(L.lib().fusg_crop_resize_frames_u8(ptrs, offs, len(keep), H, W, geom.data_ptr(), *tail), "crop_resize_frames_u8")
     return out
 
 

@@ -393,24 +393,46 @@ def warp_planes_batch(src_planes: torch.Tensor, jobs_per_vehicle) -> torch.Tenso
     V, P, H, W, _ = src_planes.shape
     flat = src_planes.reshape(V * P, H, W, 3)
     warped = torch.zeros_like(flat)
-    src_idx, dst_idx, Hs = [], [], []
-    for v, jobs in enumerate(jobs_per_vehicle):
-        last = {}
-        for k, (i, j, H12, _) in enumerate(jobs):                 # plane order: a later job on slot j overwrites an earlier one
-            last[j] = (i, H12)
-        for j, (i, H12) in last.items():
-            src_idx.append(v * P + i)
-            dst_idx.append(v * P + j)
-            Hs.append(H12)
-    if Hs:                                                        # every job reads its plane and writes its slot in place
+    minv_d, index, n = _job_tables(jobs_per_vehicle, P, _stack_starts([(1, V)], [0], P), flat.device)
+    if n:                                                         # every job reads its plane and writes its slot in place
         flat = flat.contiguous()
-        minv = np.linalg.inv(np.asarray(Hs, dtype=np.float64).reshape(len(Hs), 3, 3)).reshape(len(Hs), 9)   # LAPACK getrf/getri per matrix, as one call
-        minv_d = ops.h2d(minv, flat.device)
-        index = ops.h2d(np.stack([src_idx, dst_idx], 1).astype(np.int32), flat.device)
         with torch.cuda.device(flat.device):
-            L.check(L.lib().fusg_warp_perspective_indexed_u8(C.byref(_u8desc(flat)), minv_d.data_ptr(), index.data_ptr(), len(Hs),
+            L.check(L.lib().fusg_warp_perspective_indexed_u8(C.byref(_u8desc(flat)), minv_d.data_ptr(), index.data_ptr(), n,
                                                              C.byref(_u8desc(warped)), ops.stream_ptr()), "warp_perspective_indexed_u8")
     return warped.view(V, P, H, W, 3)
+
+
+def _stack_starts(shape, offs, P: int) -> List[int]:
+    """Row -> first source image of the row's plane stack.  Rows are clip-major and frame-major inside a clip (clip c of
+    shape[c] = (F, V) starts at row offs[c]); every frame of a clip reads the clip's own V stacks of P planes, which start at
+    image offs[c] * P.  A clip's tail is the one clip [(F, V)], a frame's vehicles the one frame [(1, V)]."""
+    return [(offs[c] + k % V) * P for c, (F, V) in enumerate(shape) for k in range(F * V)]
+
+
+def _job_table_host(jobs_per_row, P: int, src_first: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+    """The ONE job table of the three `warp_planes_*_batch` forms, on the host: jobs_per_row[r] = warp_jobs(...) of row r, whose
+    destination stack starts at image r * P and whose source stack at image src_first[r] - the forms differ only in that mapping.
+    In a row a later job on slot j overwrites an earlier one (plane order): the last job per slot is kept, slots in the order they
+    were first written.  -> (minv float64 [n, 9]: inverses of the kept H12s, index int32 [n, 2]: (source, destination) image)."""
+    idx, Hs = [], []
+    for r, jobs in enumerate(jobs_per_row):
+        last = {}
+        for i, j, H12, _ in jobs:
+            last[j] = (i, H12)
+        for j, (i, H12) in last.items():
+            idx.append((src_first[r] + i, r * P + j))
+            Hs.append(H12)
+    n = len(Hs)
+    minv = np.linalg.inv(np.asarray(Hs, dtype=np.float64).reshape(n, 3, 3)).reshape(n, 9)      # LAPACK getrf/getri per matrix, as one call
+    return minv, np.asarray(idx, dtype=np.int32).reshape(n, 2)
+
+
+def _job_tables(jobs_per_row, P: int, src_first: Sequence[int], device):
+    """`_job_table_host` uploaded: (minv_d, index, n_jobs), or (None, None, 0) when no row has a job."""
+    minv, index = _job_table_host(jobs_per_row, P, src_first)
+    if not len(index):
+        return None, None, 0
+    return ops.h2d(minv, device), ops.h2d(index, device), len(index)
 
 
 # ---------------------------------------------------------------------------------------------- device homographies
@@ -555,21 +577,8 @@ def warp_planes_frames_batch(src_planes: torch.Tensor, jobs_per_row, frames: int
     if frames < 1 or len(jobs_per_row) != frames * V:
         raise ValueError(f"warp_planes_frames_batch: {len(jobs_per_row)} job lists for {frames} frames of {V} vehicles")
     flat = src_planes.reshape(V * P, H, W, 3).contiguous()
-    src_idx, dst_idx, Hs = [], [], []
-    for r, jobs in enumerate(jobs_per_row):
-        last = {}
-        for i, j, H12, _ in jobs:                                 # plane order: a later job on slot j overwrites an earlier one
-            last[j] = (i, H12)
-        for j, (i, H12) in last.items():
-            src_idx.append((r % V) * P + i)
-            dst_idx.append(r * P + j)
-            Hs.append(H12)
-    minv_d = index = None
-    if Hs:
-        minv = np.linalg.inv(np.asarray(Hs, dtype=np.float64).reshape(len(Hs), 3, 3)).reshape(len(Hs), 9)
-        minv_d = ops.h2d(minv, flat.device)
-        index = ops.h2d(np.stack([src_idx, dst_idx], 1).astype(np.int32), flat.device)
-    return _warp_frames(flat, minv_d, index, len(Hs), frames).view(frames * V, P, H, W, 3)
+    minv_d, index, n = _job_tables(jobs_per_row, P, _stack_starts([(frames, V)], [0], P), flat.device)
+    return _warp_frames(flat, minv_d, index, n, frames).view(frames * V, P, H, W, 3)
 
 
 def warp_planes_frames_fitted(src_planes: torch.Tensor, minv: torch.Tensor, index: torch.Tensor, frames: int) -> torch.Tensor:
@@ -630,22 +639,8 @@ def warp_planes_clips_batch(src_planes_per_clip, frames_per_clip, jobs_per_row) 
     planes, shape, offs, P, H, W = _clips_layout("warp_planes_clips_batch", src_planes_per_clip, frames_per_clip)
     if len(jobs_per_row) != offs[-1]:
         raise ValueError(f"warp_planes_clips_batch: {len(jobs_per_row)} job lists for {offs[-1]} rows ((frames, vehicles) per clip: {shape})")
-    src_idx, dst_idx, Hs = [], [], []
-    for c, (F, V) in enumerate(shape):
-        for r in range(offs[c], offs[c + 1]):
-            last = {}
-            for i, j, H12, _ in jobs_per_row[r]:                  # plane order: a later job on slot j overwrites an earlier one
-                last[j] = (i, H12)
-            for j, (i, H12) in last.items():
-                src_idx.append(offs[c] * P + ((r - offs[c]) % V) * P + i)
-                dst_idx.append(r * P + j)
-                Hs.append(H12)
-    minv_d = index = None
-    if Hs:
-        minv = np.linalg.inv(np.asarray(Hs, dtype=np.float64).reshape(len(Hs), 3, 3)).reshape(len(Hs), 9)
-        minv_d = ops.h2d(minv, planes[0].device)
-        index = ops.h2d(np.stack([src_idx, dst_idx], 1).astype(np.int32), planes[0].device)
-    return _warp_clips(planes, shape, offs, P, H, W, minv_d, index, len(Hs))
+    minv_d, index, n = _job_tables(jobs_per_row, P, _stack_starts(shape, offs, P), planes[0].device)
+    return _warp_clips(planes, shape, offs, P, H, W, minv_d, index, n)
 
 
 def warp_planes_clips_fitted(src_planes_per_clip, frames_per_clip, minv: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
@@ -801,6 +796,22 @@ def paste_back_device(frame: torch.Tensor, net_images: torch.Tensor, geom: torch
     return fr
 
 
+def _check_paste(what: str, bases, hw, dev, net_images, geom, masks, box_images, box_geom, rows: str, bad_rows: bool, counts: str):
+    """What both several-frame paste wrappers check before the launch, under the wrapper's name: the bases (uint8 [H, W, 3] on
+    dev), one crop and one int32 geom row per mask (`bad_rows`: the wrapper's own condition on the masks, `counts`: its message),
+    box_images paired with box_geom (`rows`: its name for the row count).  -> the contiguous bases, kept until the launch is queued."""
+    N, (H, W) = int(masks.shape[0]), hw
+    keep = [b.contiguous() for b in bases]
+    if any(tuple(b.shape) != (H, W, 3) or b.dtype != torch.uint8 or b.device != dev for b in keep):
+        raise ValueError(f"{what}: every base image is uint8 {(H, W, 3)} on {dev}")
+    if bad_rows or net_images.shape[0] != N or geom.dtype != torch.int32 or tuple(geom.shape) != (N, 8):
+        raise ValueError(f"{what}: {counts}")
+    if (box_images is None) != (box_geom is None) or (box_images is not None and (
+            box_images.shape[0] != N or box_geom.dtype != torch.int32 or tuple(box_geom.shape) != (N, 8))):
+        raise ValueError(f"{what}: box_images [{rows}, h, w, 3] come with box_geom int32 [{rows}, 8]")
+    return keep
+
+
 def paste_back_frames_device(bases: Sequence[torch.Tensor], net_images: torch.Tensor, geom: torch.Tensor, masks: torch.Tensor,
                              box_images: Optional[torch.Tensor] = None, box_geom: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`paste_back_device` for F frames in ONE launch (fusg_paste_layers_frames_u8): bases = F CUDA uint8 [H, W, 3] images, the
@@ -812,14 +823,8 @@ def paste_back_frames_device(bases: Sequence[torch.Tensor], net_images: torch.Te
         raise ValueError("paste_back_frames_device: at least one frame")
     N, H, W = masks.shape
     dev = masks.device
-    keep = [b.contiguous() for b in bases]                        # referenced until the launch is queued
-    if any(tuple(b.shape) != (H, W, 3) or b.dtype != torch.uint8 or b.device != dev for b in keep):
-        raise ValueError(f"paste_back_frames_device: every base image is uint8 {(H, W, 3)} on {dev}")
-    if N % F or net_images.shape[0] != N or geom.dtype != torch.int32 or tuple(geom.shape) != (N, 8):
-        raise ValueError(f"paste_back_frames_device: {N} masks, {net_images.shape[0]} crops, geom {tuple(geom.shape)} for {F} frames")
-    if (box_images is None) != (box_geom is None) or (box_images is not None and (
-            box_images.shape[0] != N or box_geom.dtype != torch.int32 or tuple(box_geom.shape) != (N, 8))):
-        raise ValueError("paste_back_frames_device: box_images [F * V, h, w, 3] come with box_geom int32 [F * V, 8]")
+    keep = _check_paste("paste_back_frames_device", bases, (H, W), dev, net_images, geom, masks, box_images, box_geom, "F * V",
+                        N % F != 0, f"{N} masks, {net_images.shape[0]} crops, geom {tuple(geom.shape)} for {F} frames")
     out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
     table = ops.h2d(np.asarray([b.data_ptr() for b in keep], dtype=np.int64), dev)
     with torch.cuda.device(dev):
@@ -841,21 +846,15 @@ def paste_back_ragged_device(bases: Sequence[torch.Tensor], frame_rows: Sequence
     F = len(bases)
     if F < 1 or F > L.MAX_FRAMES:
         raise ValueError(f"paste_back_ragged_device: {F} frames (1..{L.MAX_FRAMES} per launch)")
-    keep = [b.contiguous() for b in bases]                        # referenced until the launch is queued
-    H, W = int(keep[0].shape[0]), int(keep[0].shape[1])
-    dev = keep[0].device
+    H, W = int(bases[0].shape[0]), int(bases[0].shape[1])
+    dev = bases[0].device
     N = int(masks.shape[0])
-    if any(tuple(b.shape) != (H, W, 3) or b.dtype != torch.uint8 or b.device != dev for b in keep):
-        raise ValueError(f"paste_back_ragged_device: every base image is uint8 {(H, W, 3)} on {dev}")
     offs = [int(r) for r in frame_rows]
     if len(offs) != F + 1:
         raise ValueError(f"paste_back_ragged_device: {len(offs)} row offsets for {F} frames (one more than frames)")
-    if tuple(masks.shape[1:]) != (H, W) or net_images.shape[0] != N or geom.dtype != torch.int32 or tuple(geom.shape) != (N, 8):
-        raise ValueError(f"paste_back_ragged_device: masks {tuple(masks.shape)}, {net_images.shape[0]} crops, geom {tuple(geom.shape)} "
-                         f"for frames of {(H, W)}")
-    if (box_images is None) != (box_geom is None) or (box_images is not None and (
-            box_images.shape[0] != N or box_geom.dtype != torch.int32 or tuple(box_geom.shape) != (N, 8))):
-        raise ValueError("paste_back_ragged_device: box_images [rows, h, w, 3] come with box_geom int32 [rows, 8]")
+    keep = _check_paste("paste_back_ragged_device", bases, (H, W), dev, net_images, geom, masks, box_images, box_geom, "rows",
+                        tuple(masks.shape[1:]) != (H, W),
+                        f"masks {tuple(masks.shape)}, {net_images.shape[0]} crops, geom {tuple(geom.shape)} for frames of {(H, W)}")
     out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
     ptrs = (C.c_void_p * F)(*[b.data_ptr() for b in keep])
     with torch.cuda.device(dev):
