@@ -176,6 +176,13 @@ _SIGS = {
     "fusg_edge_counts": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p, C.c_void_p]),
     "fusg_edge_counts_host": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p]),
     "fusg_sq_diff_sum_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "fusg_gram_f32": (C.c_int, [_TP, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fusg_gram_scratch_bytes": (C.c_int64, [C.c_int32] * 4),
+    "fusg_gram_chunk_pixels": (C.c_int32, [C.c_int32, C.c_int64]),
+    "fusg_gram_f32_host": (C.c_int, [_TP, C.c_void_p]),
+    "fusg_abs_diff_rows_f32": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fusg_abs_diff_rows_scratch_bytes": (C.c_int64, [C.c_int32] * 4),
+    "fusg_abs_diff_rows_f32_host": (C.c_int, [_TP, _TP, C.c_void_p]),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

@@ -1451,6 +1451,103 @@ def sq_diff_sum(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out[0]
 
 
+# ---- feature-space distances (csrc/perceptual.hip; edgeconnect/loss.py) ----------------------------------------------------
+def gram_chunk(c: int, hw: int) -> int:
+    """Pixels per chunk of `gram` for a C-channel activation of H W = hw pixels (fusg_gram_chunk_pixels): inside a chunk an
+    entry is one fp32 fmaf chain, so this is the n of the entry's error bound.  A function of (C, H W) only."""
+    k = int(L.lib().fusg_gram_chunk_pixels(int(c), int(hw)))
+    if k < 0:
+        raise ValueError(f"gram_chunk: C = {c} must be in 1..1024 and H W = {hw} in 1..2^24")
+    return k
+
+
+def _scratch(device, nbytes: int) -> torch.Tensor:
+    """Scratch of one call from the caching allocator (kept alive by a recording pass, which replays its address)."""
+    s = torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+    if RECORDER is not None:
+        RECORDER.keep.append(s)
+    return s
+
+
+def gram(x: torch.Tensor) -> torch.Tensor:
+    """float32 [B, C, C] on the device: out[b] = x[b] x[b]^T / (H W C) over the pixels of a CUDA float32 [B, C, H, W]
+    activation in the NHWC-physical layout (channel stride 1; anything else is converted by `as_nhwc`) - StyleLoss.compute_gram.
+    Exact-fp32 matrix instruction, exactly symmetric, two launches, no atomics, no host synchronisation (fusg_gram_f32)."""
+    _require_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"gram: x must be float32 [B, C, H, W], got {x.dtype} {tuple(x.shape)}")
+    B, Cn, H, W = x.shape
+    with torch.cuda.device(x.device):
+        if Cn > 1 and x.stride(1) != 1:
+            x = as_nhwc(x)
+        lib = L.lib()
+        nbytes = int(lib.fusg_gram_scratch_bytes(B, Cn, H, W))
+        if nbytes < 0:
+            raise ValueError(f"gram: {tuple(x.shape)}: C must be in 1..1024, H W in 1..2^24, B < 65536")
+        out = torch.empty((B, Cn, Cn), dtype=torch.float32, device=x.device)
+        L.check(lib.fusg_gram_f32(C.byref(desc(x)), out.data_ptr(), _scratch(x.device, nbytes).data_ptr(), stream_ptr()), "gram")
+    return out
+
+
+def gram_host(x) -> _np.ndarray:
+    """`gram` on the CPU in the same order of sums (fusg_gram_f32_host; no GPU needed): numpy float32 [B, C, H, W] in - any
+    strides with channel stride 1, a plain array is converted - float32 [B, C, C] out."""
+    x = _np.asarray(x)
+    if x.ndim != 4 or x.dtype != _np.float32:
+        raise ValueError(f"gram_host: x must be float32 [B, C, H, W], got {x.dtype} {x.shape}")
+    if x.shape[1] > 1 and x.strides[1] != x.itemsize:
+        x = _np.ascontiguousarray(x.transpose(0, 2, 3, 1)).transpose(0, 3, 1, 2)
+    out = _np.zeros((x.shape[0], x.shape[1], x.shape[1]), dtype=_np.float32)
+    L.check(L.lib().fusg_gram_f32_host(C.byref(_np_desc(x, L.F32)), out.ctypes.data), "gram_host")
+    return out
+
+
+def _as4d(t):
+    """[B, ...] as [B, C, H, W] for the row-wise kernels: [B, n] -> [B, n, 1, 1], [B, m, n] -> [B, 1, m, n] (views)."""
+    if len(t.shape) == 4:
+        return t
+    if len(t.shape) == 3:
+        return t[:, None]
+    if len(t.shape) == 2:
+        return t[:, :, None, None]
+    raise ValueError(f"expected a [B, ...] tensor of 2 to 4 dimensions, got {tuple(t.shape)}")
+
+
+def abs_diff_rows(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 [B] on the device: out[r] = sum |a[r] - b[r]| in float64 of two CUDA float32 tensors of one shape [B, ...] and
+    any strides (2 to 4 dimensions; only logical elements are read).  Two launches, a fixed order of sums, no atomics, no host
+    synchronisation (fusg_abs_diff_rows_f32).  out: a contiguous float64 [B] to write to (a row of a table)."""
+    _require_gpu(a, "a")
+    _require_gpu(b, "b")
+    if a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(f"abs_diff_rows: a and b must be float32 of one shape, got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+    a, b = _as4d(a), _as4d(b)
+    with torch.cuda.device(a.device):
+        lib = L.lib()
+        nbytes = int(lib.fusg_abs_diff_rows_scratch_bytes(*a.shape))
+        if nbytes < 0:
+            raise ValueError(f"abs_diff_rows: {tuple(a.shape)}: a row must hold 1..2^31 - 1 elements, B < 65536")
+        if out is None:
+            out = torch.empty((a.shape[0],), dtype=torch.float64, device=a.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (a.shape[0],) or not out.is_contiguous() or out.device != a.device:
+            raise ValueError(f"abs_diff_rows: out must be a contiguous float64 [{a.shape[0]}] on {a.device}")
+        L.check(lib.fusg_abs_diff_rows_f32(C.byref(desc(a)), C.byref(desc(b)), out.data_ptr(), _scratch(a.device, nbytes).data_ptr(),
+                                           stream_ptr()), "abs_diff_rows")
+    return out
+
+
+def abs_diff_rows_host(a, b) -> _np.ndarray:
+    """`abs_diff_rows` on the CPU in the same order of sums (fusg_abs_diff_rows_f32_host): numpy float32 in, float64 [B] out."""
+    a, b = _np.asarray(a), _np.asarray(b)
+    if a.shape != b.shape or a.dtype != _np.float32 or b.dtype != _np.float32:
+        raise ValueError(f"abs_diff_rows_host: a and b must be float32 of one shape, got {a.dtype} {a.shape} and {b.dtype} {b.shape}")
+    a, b = _as4d(a), _as4d(b)
+    out = _np.zeros((a.shape[0],), dtype=_np.float64)
+    L.check(L.lib().fusg_abs_diff_rows_f32_host(C.byref(_np_desc(a, L.F32)), C.byref(_np_desc(b, L.F32)), out.ctypes.data),
+            "abs_diff_rows_host")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------

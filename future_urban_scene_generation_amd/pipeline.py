@@ -15,11 +15,14 @@ import json
 import os
 from argparse import Namespace
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-_REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if TYPE_CHECKING:
+    from .edgeconnect.loss import VGG19
+
+_REPO =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def shard_range(n_items: int, rank: int, world: int) -> Tuple[int, int]:
@@ -751,13 +754,18 @@ class VehiclePipeline:
     # ------------------------------------------------------------------------------------------ quality of one pass against another
     COMPARED_IMAGES = ("icn_u8", "vunet_u8", "inpaint_u8")
 
-    def compare_outputs(self, a: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor]) -> Dict:
+    def compare_outputs(self, a: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], *, features: Optional[VGG19] = None) -> Dict:
         """Per-row quality of two output dicts of `run` (or of a frame driver) against each other, measured on the device
         (`ops.image_metrics_u8`: SSIM as the project's quality bars define it, PSNR, difference counts) and read back in ONE
         `ops.d2h`.  Compared: every key of `COMPARED_IMAGES` both dicts hold as uint8 [N, R, R, 3] of one shape, and 'kp_idx'.
         Returns {key: {'ssim' float64 [N], 'psnr' float64 [N], 'max_abs' int64 [N], 'n_diff' int64 [N]}, 'kp_equal' int64 [N]
         (equal keypoints per row, with 'kp_idx' in both), 'worst': {key: {'ssim': the smallest, 'max_abs': the largest, 'row':
-        the row of the smallest ssim}}} as numpy arrays / Python scalars."""
+        the row of the smallest ssim}}} as numpy arrays / Python scalars.
+        features: an `edgeconnect.loss.VGG19` (the user's torchvision checkpoint loaded into it, on this device).  With it every
+        compared image key also gets 'perceptual' (sum of the five PerceptualLoss terms) and 'style' (sum of the four StyleLoss
+        terms) as float64 [N] (`edgeconnect.loss.feature_distances` on the crops / 255, same read-back; NaN where the split-fp16
+        range guard fired), and 'worst'[key] gains 'perceptual': {'value': the largest, 'row': its row}.  R must be a
+        multiple of 16."""
         import numpy as np
         from . import ops
 
@@ -772,6 +780,10 @@ class VehiclePipeline:
         ncol = len(ops.IMAGE_METRIC_COLUMNS)
         with torch.cuda.device(self.device):
             cols = [ops.image_metrics_u8(a[k], b[k]) for k in keys]
+            if features is not None:
+                from .edgeconnect.loss import FEATURE_DISTANCE_COLUMNS, PERCEPTUAL_TAPS, feature_distances
+                nfeat, nperc = len(FEATURE_DISTANCE_COLUMNS), len(PERCEPTUAL_TAPS)
+                cols += [feature_distances(features, a[k], b[k]) for k in keys]
             if kp:                                                # the indices themselves (exact in float64): compared on the host
                 cols += [a["kp_idx"].reshape(N, -1).to(torch.float64), b["kp_idx"].reshape(N, -1).to(torch.float64)]
             host = ops.d2h(torch.cat(cols, dim=1))
@@ -784,19 +796,30 @@ class VehiclePipeline:
             if N:
                 row = int(np.argmin(res[k]["ssim"]))
                 res["worst"][k] = {"ssim": float(res[k]["ssim"][row]), "max_abs": int(res[k]["max_abs"].max()), "row": row}
+        n_img = len(keys) * ncol                                  # columns ahead of the keypoints
+        if features is not None:
+            for i, k in enumerate(keys):
+                t = host[:, n_img + i * nfeat:n_img + (i + 1) * nfeat]
+                res[k]["perceptual"], res[k]["style"] = t[:, :nperc].sum(axis=1), t[:, nperc:].sum(axis=1)
+                if N:
+                    row = int(np.argmax(res[k]["perceptual"]))
+                    res["worst"][k]["perceptual"] = {"value": float(res[k]["perceptual"][row]), "row": row}
+            n_img += len(keys) * nfeat
         if kp:
-            n_kp = (host.shape[1] - len(keys) * ncol) // 2
-            ka, kb = host[:, len(keys) * ncol:len(keys) * ncol + n_kp], host[:, len(keys) * ncol + n_kp:]
+            n_kp = (host.shape[1] - n_img) // 2
+            ka, kb = host[:, n_img:n_img + n_kp], host[:, n_img + n_kp:]
             res["kp_equal"] = (ka == kb).sum(axis=1).astype(np.int64)
         return res
 
     def compare_precisions(self, batch: Dict[str, torch.Tensor], vehicle_seeds: Sequence[int], precision: str = "bf16",
-                           against: str = "f16x3", check: Optional[str] = "sync") -> Dict:
+                           against: str = "f16x3", check: Optional[str] = "sync", *, features: Optional[VGG19] = None) -> Dict:
         """`run(batch, vehicle_seeds)` once under `against` and once under `precision` (`ops.precision`, restored afterwards;
         this pipeline's routing batch in force around both), then `compare_outputs` of the two: what a faster arithmetic costs
         on the caller's own weights and crops, in the unit the quality bars are stated in.  The acceptance recipe for bf16:
         `rep = pipe.compare_precisions(batch, seeds, "bf16"); assert rep["worst"]["icn_u8"]["ssim"] >= 0.999`.
-        vehicle_seeds is required: without it the two passes draw different VUnet noise and the comparison means nothing."""
+        vehicle_seeds is required: without it the two passes draw different VUnet noise and the comparison means nothing.
+        features: as in `compare_outputs` (the feature-space distances of the two passes' crops, measured at the ambient
+        precision, not at `precision`)."""
         from . import ops
         if vehicle_seeds is None:
             raise ValueError("compare_precisions: vehicle_seeds is required (without seeds the two passes draw different noise)")
@@ -808,7 +831,7 @@ class VehiclePipeline:
                 ref = self.run(batch, vehicle_seeds, check)
             with ops.precision(precision):
                 out = self.run(batch, vehicle_seeds, check)
-            return self.compare_outputs(out, ref)
+            return self.compare_outputs(out, ref) if features is None else self.compare_outputs(out, ref, features=features)
 
     def _no_vehicles(self, R: int, *keys) -> Dict[str, torch.Tensor]:
         """The named per-vehicle outputs for zero vehicles (a frame without vehicles, a rank whose shard is empty)."""

@@ -838,6 +838,36 @@ int fusg_edge_counts_host(const fusg_tensor* x, const fusg_tensor* y, float thre
  * out: DEVICE float64 [257] - out[1..256] hold the per-workgroup partials, added in a fixed order by a second launch. */
 int fusg_sq_diff_sum_f32(const float* a, const float* b, int64_t n, double* out, void* stream);
 
+/* ---- feature-space distances (EdgeConnect's PerceptualLoss / StyleLoss, forward only; new entry points, FUSG_VERSION stays
+ * 118 as for the metrics above) */
+/* The Gram matrix of an activation over its pixels: x is an f32 [B, C, H, W] descriptor with channel stride 1 (the NHWC-
+ * physical layout, any channel pitch >= C, a channel-slice view of a wider buffer included; padding channels are never
+ * read), C in 1..1024, H W in 1..2^24, B < 65536.  out: DEVICE float32 [B][C][C],
+ *   out[b][i][j] = (sum over the pixels p of x[b, i, p] x[b, j, p]) / (H W C)        (StyleLoss.compute_gram)
+ * exactly symmetric.  The products run on the exact-fp32 matrix instruction: inside a chunk of fusg_gram_chunk_pixels(C, H W)
+ * pixels an entry is one fp32 fmaf chain in pixel order; the chunk partials (fp32, in scratch) are added in ascending order
+ * in float64, scaled and rounded once by a second launch.  An entry is within (gamma_n + 2u) sum_p |x_i x_j| / (H W C) of
+ * exact arithmetic, u = 2^-24, n the chunk size.  scratch: DEVICE, 16-byte aligned, the bytes the size query returns; it
+ * holds nothing between calls.  Two launches, no atomics: a row's bits do not depend on B, on the row's position or on the
+ * run.  A wrong dtype, a channel stride other than 1 or a size out of range: FUSG_ERR_INVALID before any launch; B = 0
+ * launches nothing.  Bit-identical to the host twin. */
+int fusg_gram_f32(const fusg_tensor* x, float* out, void* scratch, void* stream);
+/* Bytes of scratch for a [B, C, H, W] activation; -1 for sizes fusg_gram_f32 would refuse. */
+int64_t fusg_gram_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+/* Pixels per chunk: a function of C and H W only (csrc/perceptual.h states the rule); -1 for sizes out of range. */
+int32_t fusg_gram_chunk_pixels(int32_t C, int64_t HW);
+/* The same sums in the same order on the CPU: x and out are HOST pointers, no GPU and no scratch needed. */
+int fusg_gram_f32_host(const fusg_tensor* x, float* out);
+/* out[r] = the sum over row r of |(double)a - (double)b|: a, b f32 [B, C, H, W] descriptors of one shape and any strides
+ * (only the C H W logical elements of a row are read), C H W < 2^31, B < 65536; out: DEVICE float64 [B].  Two launches -
+ * float64 partials per workgroup into scratch (DEVICE, 16-byte aligned, the size query's bytes), then one fixed-order add
+ * per row - no atomics, a row's bits independent of B.  B = 0 launches nothing; anything else wrong: FUSG_ERR_INVALID
+ * before any launch.  Bit-identical to the host twin. */
+int fusg_abs_diff_rows_f32(const fusg_tensor* a, const fusg_tensor* b, double* out, void* scratch, void* stream);
+int64_t fusg_abs_diff_rows_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+/* The same on HOST pointers. */
+int fusg_abs_diff_rows_f32_host(const fusg_tensor* a, const fusg_tensor* b, double* out);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)
