@@ -67,7 +67,10 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const float* __restrict__
         const f32x4 c = *(const f32x4*)(s + (long)W * xCs), d = *(const f32x4*)(s + (long)W * xCs + xCs);
         f32x4 m;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) m[k] = fmaxf(fmaxf(a[k], bb[k]), fmaxf(c[k], d[k]));
+        for (int k = 0; k < 4; ++k) {             // fmaxf drops a NaN operand; F.max_pool2d hands it on
+            const bool nan = a[k] != a[k] || bb[k] != bb[k] || c[k] != c[k] || d[k] != d[k];
+            m[k] = nan ? NAN : fmaxf(fmaxf(a[k], bb[k]), fmaxf(c[k], d[k]));
+        }
         *(f32x4*)(dst + ((b * Ho + oy) * (long)Wo + ox) * dCs + q * 4) = m;
     }
 }
@@ -428,8 +431,14 @@ static int hshift_sum_impl(const fusg_tensor* t, const float* bias, int32_t kw, 
     FUSG_CHECK(t && dst && bias && is_nhwc(*t) && dst->data && dst->dtype == FUSG_F32 && same_nhw(*t, *dst), "hshift_sum: tensors");
     FUSG_CHECK(kw >= 1 && kw <= 15 && pad >= 0 && pad < dst->w && dst->c * kw <= t->c, "hshift_sum: kw %d pad %d cout %ld tc %ld", kw, pad, (long)dst->c, (long)t->c);
     FUSG_CHECK(act >= 0 && act <= FUSG_ACT_TANH01 && (pad_mode == 0 || pad_mode == 1), "hshift_sum: act/pad_mode");
+    // the taps reach pad pixels to the left and kw-1-pad to the right: the window holds its own pixel, and a reflected
+    // overshoot has to land inside the row (2W-2-xx >= 0) like the left one does (pad < W)
+    const int reach = kw - 1 - pad;
+    FUSG_CHECK(reach >= 0 && (pad_mode == 0 || reach < dst->w), "hshift_sum: kw %d pad %d does not fit W %ld (pad_mode %d)", kw, pad,
+               (long)dst->w, pad_mode);
     const long total = dst->n * dst->h * dst->w;
-    if (t->sw % 4 == 0 && t->sw <= 32 && pad <= 16 && dst->w > 2 * pad && (((uintptr_t)t->data) & 15) == 0) {
+    // the LDS tile holds a segment's 256 pixels +- pad: a window reaching further right than pad goes the direct way
+    if (t->sw % 4 == 0 && t->sw <= 32 && pad <= 16 && reach <= pad && dst->w > 2 * pad && (((uintptr_t)t->data) & 15) == 0) {
         const int segs = (int)((dst->w + 255) / 256);
         const long nblk = dst->n * dst->h * segs;
         FUSG_CHECK(nblk < (1L << 31), "hshift_sum: grid too large");

@@ -422,7 +422,8 @@ int fusg_ln_finalize_slots(const float* slots, int32_t batch, int32_t nslots, in
  * edgeconnect/networks.py:198-199). */
 int fusg_affine_act(const fusg_tensor* x, const float* scale, const float* shift, int64_t bstride,
                     int32_t act, const fusg_tensor* res, const fusg_tensor* dst, void* stream);
-/* F.max_pool2d(x, 2, stride=2) (stacked_hourglass/models.py:72,149).  NHWC-physical. */
+/* F.max_pool2d(x, 2, stride=2) (stacked_hourglass/models.py:72,149), a NaN in the window included: the
+ * result is then NaN.  NHWC-physical. */
 int fusg_maxpool2(const fusg_tensor* x, const fusg_tensor* dst, void* stream);
 /* dst = up1 + nearest_upsample2(low) (stacked_hourglass/models.py:81-82).  NHWC-physical. */
 int fusg_upsample2_add(const fusg_tensor* low, const fusg_tensor* up1, const fusg_tensor* dst, void* stream);
@@ -445,11 +446,16 @@ int fusg_ec_inputs(const fusg_tensor* images, const fusg_tensor* edges, const fu
  * (kw x fewer MFMA flops than padding cout to 32), then
  *   dst[b, co, y, x] = act(bias[co] + sum_kx t[b, co*kw + kx, y, pad_x(x + kx - pad)])
  * with zero / reflect handling of the horizontal border.  t NHWC-physical, dst any strides.
+ * The taps are added in fp32 in ascending kx, starting from the bias.  Accepted: 1 <= kw <= 15, 0 <= pad < W,
+ * cout*kw <= t.c, and a window that holds its own pixel and fits the row: kw - 1 - pad >= 0, and with reflect
+ * padding kw - 1 - pad < W (the right overshoot reflects inside the row like the left one); anything else is
+ * FUSG_ERR_INVALID.  A window reaching further right than left (kw - 1 > 2*pad) is served by the direct kernel.
  * Used for the 7x7 heads (warp_learn/models.py:182-183; edgeconnect/networks.py:72-73,123-124). */
 int fusg_hshift_sum(const fusg_tensor* t, const float* bias, int32_t kw, int32_t pad, int32_t pad_mode,
                     int32_t act, const fusg_tensor* dst, void* stream);
 /* Row-major first-occurrence argmax over H*W per (b, c) -> idx[b*C + c] = y*W + x (int32).
- * Integer contract of get_maxima (utils/keypoint_utils.py:85-88). */
+ * Integer contract of get_maxima (utils/keypoint_utils.py:85-88).  A map of equal values (all -inf included)
+ * gives 0.  Unspecified for a map that holds a NaN. */
 int fusg_argmax_hw(const fusg_tensor* x, int32_t* idx, void* stream);
 /* to_image(from_LAB=False) quantiser (warp_learn/planes_utils.py:111-114):
  * u8[b,y,x,c] = trunc(clip((x+1)/2*255, 0, 255)).  dst is a U8 tensor described as NCHW extents
