@@ -90,7 +90,7 @@ class PackSizes(C.Structure):           # fusg_pack_sizes
 F32, U8, I32 = 0, 1, 2
 PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = 0, 1, 2
 PRE_NONE, PRE_RELU, PRE_ELU, PRE_AFFINE_RELU, PRE_AFFINE = 0, 1, 2, 3, 4
-ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_TANH01 = 0, 1, 2, 3, 4
+ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_TANH01, ACT_LEAKY02 = 0, 1, 2, 3, 4, 5
 STORE_NORMAL, STORE_D2S, STORE_S2D = 0, 1, 2
 PREC_F32, PREC_F16X3, PREC_EMU_BF16, PREC_EMU_BF16X2, PREC_BF16 = 0, 1, 2, 3, 4
 MAX_FRAMES = 64                         # FUSG_MAX_FRAMES: frames per launch of the frame-indexed glue
@@ -183,6 +183,14 @@ _SIGS = {
     "fusg_abs_diff_rows_f32": (C.c_int, [_TP, _TP, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fusg_abs_diff_rows_scratch_bytes": (C.c_int64, [C.c_int32] * 4),
     "fusg_abs_diff_rows_f32_host": (C.c_int, [_TP, _TP, C.c_void_p]),
+    "fusg_avgpool3s2_f32": (C.c_int, [_TP, _TP, C.c_void_p]),
+    "fusg_avgpool3s2_f32_host": (C.c_int, [_TP, _TP]),
+    "fusg_mask_mul_f32": (C.c_int, [_TP, _TP, _TP, C.c_void_p]),
+    "fusg_gan_terms_rows_f32": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fusg_gan_terms_scratch_bytes": (C.c_int64, [C.c_int32] * 4),
+    "fusg_gan_terms_columns": (C.c_int32, []),
+    "fusg_gan_terms_chunk": (C.c_int64, [C.c_int64]),
+    "fusg_gan_terms_rows_f32_host": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p]),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

@@ -336,7 +336,7 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
     FUSG_CHECK(d->pad_mode == FUSG_PAD_ZERO || d->pad_mode == FUSG_PAD_REFLECT || d->pad_mode == FUSG_PAD_REPLICATE, "conv2d: pad_mode");
     FUSG_CHECK(!d->tile_list || (d->tile_count > 0 && !d->stats_out), "conv2d: tile_list needs tile_count > 0 and no stats_out");
     FUSG_CHECK(d->pre_op >= 0 && d->pre_op <= FUSG_PRE_AFFINE, "conv2d: pre_op");
-    FUSG_CHECK(d->act >= 0 && d->act <= FUSG_ACT_TANH01, "conv2d: act");
+    FUSG_CHECK(d->act >= 0 && d->act <= FUSG_ACT_LEAKY02, "conv2d: act");
     if (d->pre_op >= FUSG_PRE_AFFINE_RELU) {
         FUSG_CHECK(d->pre_scale && d->pre_shift && ((((uintptr_t)d->pre_scale) | ((uintptr_t)d->pre_shift)) & 15) == 0 &&
                    d->pre_bstride % 4 == 0, "conv2d: affine pre-op needs 16B-aligned scale/shift");

@@ -97,6 +97,7 @@ __device__ __forceinline__ float act_apply(float v, int act) {
         case FUSG_ACT_TANH: return tanhf(v);
         case FUSG_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case FUSG_ACT_TANH01: return (tanhf(v) + 1.f) / 2.f;
+        case FUSG_ACT_LEAKY02: return v > 0.f ? v : 0.2f * v;        // a NaN stays a NaN, as in nn.LeakyReLU
         default: return v;
     }
 }

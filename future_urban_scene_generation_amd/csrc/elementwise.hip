@@ -25,6 +25,7 @@ __device__ __forceinline__ float act1(float v, int act) {
         case FUSG_ACT_TANH: return tanhf(v);
         case FUSG_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case FUSG_ACT_TANH01: return (tanhf(v) + 1.f) / 2.f;
+        case FUSG_ACT_LEAKY02: return v > 0.f ? v : 0.2f * v;        // a NaN stays a NaN, as in nn.LeakyReLU
         default: return v;
     }
 }
@@ -134,6 +135,17 @@ __global__ __launch_bounds__(256) void add4d_kernel(T4 a, T4 bt, T4 d, long tota
     ((float*)d.p)[b * d.sn + c * d.sc + y * d.sh + x * d.sw] =
         ((const float*)a.p)[b * a.sn + c * a.sc + y * a.sh + x * a.sw] +
         ((const float*)bt.p)[b * bt.sn + c * bt.sc + y * bt.sh + x * bt.sw];
+}
+
+// dst[b, c, y, x] = x[b, c, y, x] * m[b, 0, y, x]; one thread per element of dst, channel fastest
+__global__ __launch_bounds__(256) void mask_mul_kernel(T4 a, T4 m, T4 d, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long c = i % d.c; long r = i / d.c;
+    const long x = r % d.w; r /= d.w;
+    const long y = r % d.h; const long b = r / d.h;
+    ((float*)d.p)[b * d.sn + c * d.sc + y * d.sh + x * d.sw] =
+        ((const float*)a.p)[b * a.sn + c * a.sc + y * a.sh + x * a.sw] * ((const float*)m.p)[b * m.sn + y * m.sh + x * m.sw];
 }
 
 // SpaceToDepth(2): dst[b, (2i+j)*C + c, h, w] = x[b, c, 2h+i, 2w+j]; thread per (dst pixel, quadrant, float4)
@@ -316,7 +328,7 @@ static int affine_act_impl(const fusg_tensor* x, const float* scale, const float
     if (scale) FUSG_CHECK(((((uintptr_t)scale) | ((uintptr_t)shift)) & 15) == 0 && bstride % 4 == 0, "affine_act: misaligned scale/shift");
     const bool hr = res && res->data;
     if (hr) FUSG_CHECK(is_nhwc(*res) && same_shape(*x, *res), "affine_act: residual must match x");
-    FUSG_CHECK(act >= 0 && act <= FUSG_ACT_TANH01, "affine_act: act");
+    FUSG_CHECK(act >= 0 && act <= FUSG_ACT_LEAKY02, "affine_act: act");
     const int C4 = (int)(x->c / 4);
     const long total = x->n * x->h * x->w * C4;
     unsigned nb = blocks_for(total);
@@ -388,6 +400,18 @@ static int add4d_impl(const fusg_tensor* a, const fusg_tensor* b, const fusg_ten
 }
 extern "C" int fusg_add4d(const fusg_tensor* a, const fusg_tensor* b, const fusg_tensor* dst, void* stream) { return fusg::plan_dispatch(add4d_impl, stream, a, b, dst); }
 
+static int mask_mul_impl(const fusg_tensor* x, const fusg_tensor* m, const fusg_tensor* dst, void* stream) {
+    FUSG_CHECK(x && m && dst && x->data && m->data && dst->data && same_shape(*x, *dst) && same_nhw(*x, *m) && m->c == 1 &&
+               x->dtype == FUSG_F32 && m->dtype == FUSG_F32 && dst->dtype == FUSG_F32, "mask_mul: x/dst [B,C,H,W] and m [B,1,H,W], f32");
+    const long total = dst->n * dst->h * dst->w * dst->c;
+    if (total == 0) return FUSG_OK;
+    FUSG_CHECK(total < (1L << 31) * 256, "mask_mul: too many elements");
+    hipLaunchKernelGGL(mask_mul_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, view(*x), view(*m), view(*dst), total);
+    FUSG_LAUNCH_CHECK("mask_mul");
+    return FUSG_OK;
+}
+extern "C" int fusg_mask_mul_f32(const fusg_tensor* x, const fusg_tensor* m, const fusg_tensor* dst, void* stream) { return fusg::plan_dispatch(mask_mul_impl, stream, x, m, dst); }
+
 static int space_to_depth2_impl(const fusg_tensor* x, const fusg_tensor* dst, void* stream) {
     FUSG_CHECK(x && dst && is_nhwc(*x) && is_nhwc(*dst) && x->c % 4 == 0 && dst->c == 4 * x->c && x->h == 2 * dst->h &&
                x->w == 2 * dst->w && x->n == dst->n, "space_to_depth2: shapes");
@@ -430,7 +454,7 @@ static int hshift_sum_impl(const fusg_tensor* t, const float* bias, int32_t kw, 
                                const fusg_tensor* dst, void* stream) {
     FUSG_CHECK(t && dst && bias && is_nhwc(*t) && dst->data && dst->dtype == FUSG_F32 && same_nhw(*t, *dst), "hshift_sum: tensors");
     FUSG_CHECK(kw >= 1 && kw <= 15 && pad >= 0 && pad < dst->w && dst->c * kw <= t->c, "hshift_sum: kw %d pad %d cout %ld tc %ld", kw, pad, (long)dst->c, (long)t->c);
-    FUSG_CHECK(act >= 0 && act <= FUSG_ACT_TANH01 && (pad_mode == 0 || pad_mode == 1), "hshift_sum: act/pad_mode");
+    FUSG_CHECK(act >= 0 && act <= FUSG_ACT_LEAKY02 && (pad_mode == 0 || pad_mode == 1), "hshift_sum: act/pad_mode");
     // the taps reach pad pixels to the left and kw-1-pad to the right: the window holds its own pixel, and a reflected
     // overshoot has to land inside the row (2W-2-xx >= 0) like the left one does (pad < W)
     const int reach = kw - 1 - pad;

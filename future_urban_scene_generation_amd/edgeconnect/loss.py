@@ -1,7 +1,8 @@
 """Drop-in for the reference's ``edgeconnect.loss``, forward only: ``VGG19`` (the sixteen ReLU taps of VGG-19 configuration
 E), ``PerceptualLoss(weights)`` (L1 distance of the activations at relu1_1, 2_1, 3_1, 4_1, 5_1) and ``StyleLoss()`` (L1
 distance of the Gram matrices of relu2_2, 3_4, 4_4, 5_2), with the reference's constructor arguments, ``state_dict`` keys and
-call signatures.  ``AdversarialLoss`` belongs to training and raises on construction.
+call signatures.  ``AdversarialLoss`` belongs to training and raises on construction; ``AdversarialScore`` computes its values
+forward only, and ``feature_matching`` the discriminator feature-matching sum.
 
 ``VGG19`` holds the ``features`` weights of a torchvision ``vgg19`` under the reference's names (``relu1_1.0.weight`` ...
 ``relu5_4.34.bias``); ``load_torchvision(sd)`` takes a torchvision state dict (``features.N.*``).  Nothing is downloaded:
@@ -241,8 +242,55 @@ class StyleLoss(_FeatureLoss):
 
 
 class AdversarialLoss(nn.Module):
-    """Training only: this library is forward-only evaluation."""
+    """Training only: this library is forward-only evaluation.  The VALUES of the reference's objective are
+    `AdversarialScore`."""
 
     def __init__(self, type="nsgan", target_real_label=1.0, target_fake_label=0.0):
         raise NotImplementedError("AdversarialLoss belongs to training (discriminators, backward passes), which this "
-                                  "forward-only library does not provide")
+                                  "forward-only library does not provide; AdversarialScore computes the same values forward only")
+
+
+class AdversarialScore(nn.Module):
+    """The reference ``AdversarialLoss``'s values (loss.py:6-42), forward only: ``type`` 'nsgan' (BCELoss), 'lsgan' (MSELoss) or
+    'hinge', called as ``score(outputs, is_real, is_disc=None)``; a 0-d float32 device tensor computed from the float64 columns of
+    ``ops.gan_terms`` without a host synchronisation.  'nsgan' expects probabilities (a discriminator built with
+    ``use_sigmoid=True``): for values outside [0, 1] nn.BCELoss raises, this returns NaN."""
+
+    def __init__(self, type="nsgan", target_real_label=1.0, target_fake_label=0.0):
+        super().__init__()
+        if type not in ("nsgan", "lsgan", "hinge"):
+            raise ValueError(f"AdversarialScore: type must be 'nsgan', 'lsgan' or 'hinge', got {type!r}")
+        self.type = type
+        self.register_buffer("real_label", torch.tensor(target_real_label))
+        self.register_buffer("fake_label", torch.tensor(target_fake_label))
+        self._labels = (float(torch.tensor(target_fake_label, dtype=torch.float32)), float(torch.tensor(target_real_label, dtype=torch.float32)))
+
+    def value64(self, outputs: torch.Tensor, is_real, is_disc=None) -> torch.Tensor:
+        """The value as a 0-d float64 device tensor (what `__call__` rounds to float32)."""
+        t = ops.gan_terms(outputs.detach(), self._labels[1 if is_real else 0])
+        n = t[:, 0].sum()
+        if self.type == "hinge":
+            if is_disc:
+                return t[:, 4 if is_real else 3].sum() / n     # relu(1 - x) for real, relu(1 + x) for fake
+            return -(t[:, 1].sum() / n)
+        return t[:, 5 if self.type == "nsgan" else 2].sum() / n
+
+    def __call__(self, outputs, is_real, is_disc=None):
+        return self.value64(outputs, is_real, is_disc).to(torch.float32)
+
+
+def feature_matching64(feats_a: Sequence[torch.Tensor], feats_b: Sequence[torch.Tensor]) -> torch.Tensor:
+    """sum_i L1Loss(a_i, b_i) as a 0-d float64 device tensor: one `ops.abs_diff_rows` per pair, no host synchronisation."""
+    if len(feats_a) != len(feats_b) or not len(feats_a):
+        raise ValueError(f"feature_matching: {len(feats_a)} and {len(feats_b)} feature maps")
+    total = None
+    for a, b in zip(feats_a, feats_b):
+        v = ops.abs_diff_rows(a.detach(), b.detach()).sum() / float(a.numel())
+        total = v if total is None else total + v
+    return total
+
+
+def feature_matching(feats_a: Sequence[torch.Tensor], feats_b: Sequence[torch.Tensor]) -> torch.Tensor:
+    """EdgeConnect's feature-matching term before its weight (models.py:115-117): sum_i L1Loss(a_i, b_i) over two lists of
+    discriminator feature maps, a 0-d float32 device tensor."""
+    return feature_matching64(feats_a, feats_b).to(torch.float32)

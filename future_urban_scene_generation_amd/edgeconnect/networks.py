@@ -4,7 +4,8 @@ Public surface kept (edgeconnect/networks.py:37-135): ``InpaintGenerator(residua
 init_weights=True)``, ``EdgeGenerator(residual_blocks=8, use_spectral_norm=True, init_weights=True)``
 with the reference's ``state_dict`` schema (``encoder.{1,4,7}``, ``middle.{i}.conv_block.{1,5}``,
 ``decoder.{0,3,7}``; spectral-normed convs expose ``weight_orig / weight_u / weight_v``).
-``Discriminator`` is training-only in the reference and is not provided.
+``Discriminator(in_channels, use_sigmoid=True, use_spectral_norm=True, init_weights=True)`` (networks.py:138-181) is
+provided forward only, for the validation terms of ``EdgeModel.evaluate`` / ``InpaintingModel.evaluate``.
 
 Execution: spectral norm is folded once at pack time (eval mode does no power iteration); the
 dilated / reflect-padded 3x3 convs, the zero-padded 4x4 stride-2 convs and the two
@@ -134,13 +135,79 @@ class EdgeGenerator(_Generator):
         super().__init__(3, 1, residual_blocks, spectral=use_spectral_norm, final_act=L.ACT_SIGMOID)
 
 
-class Discriminator(nn.Module):
-    """Name kept importable for `from edgeconnect.networks import InpaintGenerator, EdgeGenerator, Discriminator`
-    (reference edgeconnect/models.py:5).  The PatchGAN discriminator (reference networks.py:138-181) is used only by
-    the training half of EdgeModel / InpaintingModel (models.py:62, 154: adversarial loss), which is outside the
-    inference hot path: constructing it here is an error rather than a silent CPU module."""
+class Discriminator(FusedNet):
+    """The PatchGAN discriminator (reference networks.py:138-181), forward only: ``Discriminator(in_channels, use_sigmoid=True,
+    use_spectral_norm=True, init_weights=True)`` with the reference's ``state_dict`` schema - ``conv{1..5}.0.{weight_orig,
+    weight_u, weight_v}`` (``weight, bias`` without spectral norm) and the reference's alias: ``conv1`` and ``features`` are
+    ONE module, so ``features.0.*`` appears too and shares storage with ``conv1.0.*``.
+
+    ``forward(x)`` returns ``(outputs, [conv1, ..., conv5])`` as logical NCHW views of NHWC-physical tensors: conv1 - conv4
+    after LeakyReLU(0.2) (the reference's activation is in place, so that is what it hands out), conv5 raw, outputs
+    ``sigmoid(conv5)`` or conv5 itself.  Five ``ops.conv`` launches with the activation in the epilogue (spectral norm folded
+    at pack time) and one ``ops.affine_act`` for the sigmoid."""
 
     def __init__(self, in_channels, use_sigmoid=True, use_spectral_norm=True, init_weights=True):
         super().__init__()
-        raise NotImplementedError("edgeconnect.networks.Discriminator belongs to EdgeConnect's training half, which the "
-                                  "MI355X inference path does not provide (SURVEY.md §2 row 8)")
+        self.in_channels, self.use_sigmoid, self.use_spectral_norm = in_channels, use_sigmoid, use_spectral_norm
+        sn, I = use_spectral_norm, nn.Identity
+        self.conv1 = self.features = nn.Sequential(_holder(in_channels, 64, 4, sn, bias=not sn), I())
+        self.conv2 = nn.Sequential(_holder(64, 128, 4, sn, bias=not sn), I())
+        self.conv3 = nn.Sequential(_holder(128, 256, 4, sn, bias=not sn), I())
+        self.conv4 = nn.Sequential(_holder(256, 512, 4, sn, bias=not sn), I())
+        self.conv5 = nn.Sequential(_holder(512, 1, 4, sn, bias=not sn))
+
+    init_weights = _Generator.init_weights
+
+    def _build_plans(self, device) -> dict:
+        wb = _Generator._wb
+        return {"conv1": pack.pack_conv(*wb(self.conv1[0]), stride=2, pad=1).to(device),
+                "conv2": pack.pack_conv(*wb(self.conv2[0]), stride=2, pad=1).to(device),
+                "conv3": pack.pack_conv(*wb(self.conv3[0]), stride=2, pad=1).to(device),
+                "conv4": pack.pack_conv(*wb(self.conv4[0]), stride=1, pad=1).to(device),
+                "conv5": pack.pack_conv(*wb(self.conv5[0]), stride=1, pad=1).to(device)}
+
+    @staticmethod
+    def _whole_k(x: torch.Tensor) -> int:
+        """How a stride-2 4 x 4 conv of x is launched.  1: K whole, where the halo kernel's parity-quadrant form qualifies (output
+        grid a multiple of its 8 x 16-pixel patch) - a split-K launch does not use it, and on one image the planner would split.
+        2: the same on a copy of x widened by 16 zero columns, where only the output's width misses the patch by half of one
+        (8, 24, ... columns: 8 x 8 outputs at 64 x 64 inputs).  0: the planner's choice."""
+        _, c, h, w = x.shape
+        if not (ops.halo_precision() and c % 32 == 0 and h % 2 == 0 and w % 2 == 0 and (h // 2) % 8 == 0):
+            return 0
+        return {0: 1, 8: 2}.get((w // 2) % 16, 0)
+
+    def _stride2(self, plan, x: torch.Tensor) -> torch.Tensor:
+        """LeakyReLU(conv(x)) of a stride-2 layer by the route `_whole_k` names."""
+        how = self._whole_k(x)
+        if how != 2:
+            return ops.conv(plan, x, act=L.ACT_LEAKY02, ksplit=how)
+        # Zero columns to the right of the image are what the conv's own zero padding reads there, so output columns
+        # 0 .. w / 2 - 1 of the widened launch are the layer's: one launch on the quadrant form plus two strided copies.
+        b, c, h, w = x.shape
+        wide = ops.nhwc_empty(b, c, h, w + 16, x.device, zero=True)
+        if ops.RECORDER is not None:
+            ops.RECORDER.keep.append(wide)
+        ops.copy4d(x, wide[:, :, :, :w])
+        y = ops.conv(plan, wide, act=L.ACT_LEAKY02, ksplit=1)
+        out = ops.nhwc_empty(b, plan.cout, h // 2, w // 2, x.device)
+        return ops.copy4d(y[:, :, :, :w // 2], out)
+
+    def _run(self, x_nhwc: torch.Tensor):
+        P, LK = self._plans, L.ACT_LEAKY02
+        c1 = ops.conv(P["conv1"], x_nhwc, act=LK)
+        c2 = self._stride2(P["conv2"], c1)
+        c3 = self._stride2(P["conv3"], c2)
+        c4 = ops.conv(P["conv4"], c3, act=LK)
+        c5 = ops.conv(P["conv5"], c4)
+        outputs = c5
+        if self.use_sigmoid:
+            outputs = ops.affine_act(ops.pitch_view(c5), None, None, L.ACT_SIGMOID)[:, :1]
+        return outputs, [c1, c2, c3, c4, c5]
+
+    @entry_point
+    def forward(self, x: torch.Tensor):
+        self._ensure(x)
+        if x.dim() != 4 or x.shape[1] != self.in_channels or x.shape[2] // 8 < 3 or x.shape[3] // 8 < 3:
+            raise ValueError(f"Discriminator expects [B,{self.in_channels},H,W] with H,W >= 24, got {tuple(x.shape)}")
+        return self._run(ops.as_nhwc(x.detach()))

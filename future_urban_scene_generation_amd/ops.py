@@ -332,6 +332,13 @@ def nhwc_empty(b: int, c: int, h: int, w: int, device, dtype=torch.float32, zero
     return t
 
 
+def pitch_view(t: torch.Tensor) -> torch.Tensor:
+    """An NHWC-physical tensor widened to its whole channel pitch (a view: the padding channels hold whatever the buffer
+    does), for the float4 elementwise kernels on a tensor whose channel count is no multiple of 4."""
+    b, c, h, w = t.shape
+    return t if c == t.stride(3) else t.as_strided((b, t.stride(3), h, w), t.stride(), t.storage_offset())
+
+
 def is_nhwc(t: torch.Tensor) -> bool:
     if t.dim() != 4 or t.dtype != torch.float32 or not t.is_cuda:
         return False
@@ -1545,6 +1552,107 @@ def abs_diff_rows_host(a, b) -> _np.ndarray:
     out = _np.zeros((a.shape[0],), dtype=_np.float64)
     L.check(L.lib().fusg_abs_diff_rows_f32_host(C.byref(_np_desc(a, L.F32)), C.byref(_np_desc(b, L.F32)), out.ctypes.data),
             "abs_diff_rows_host")
+    return out
+
+
+# ---- discriminator glue and GAN terms (csrc/gan_terms.hip, elementwise.hip; edgeconnect/networks.py, warp_learn/models.py) -----
+GAN_TERM_COLUMNS = ("n", "sum", "sq", "relu_plus", "relu_minus", "bce")
+
+
+def avgpool3s2(x: torch.Tensor) -> torch.Tensor:
+    """nn.AvgPool2d(3, stride=2, padding=1, count_include_pad=False) of an NHWC-physical float32 [B, C, H, W] (anything else is
+    converted by `as_nhwc`): [B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1], NHWC-physical (fusg_avgpool3s2_f32)."""
+    _require_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"avgpool3s2: x must be float32 [B, C, H, W], got {x.dtype} {tuple(x.shape)}")
+    with torch.cuda.device(x.device):
+        if not is_nhwc(x):
+            x = as_nhwc(x)
+        b, c, h, w = x.shape
+        # (padding channels are not written: zero them when there are any, for a consumer conv that reads whole quads)
+        out = nhwc_empty(b, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1, x.device, zero=c % 4 != 0)
+        L.check(L.lib().fusg_avgpool3s2_f32(C.byref(desc(x)), C.byref(desc(out)), stream_ptr()), "avgpool3s2")
+    return out
+
+
+def _np_nhwc(x: _np.ndarray) -> _np.ndarray:
+    """A float32 [B, C, H, W] numpy array as a logical view over a dense NHWC copy."""
+    return _np.array(x.transpose(0, 2, 3, 1), order="C", copy=True).transpose(0, 3, 1, 2)
+
+
+def avgpool3s2_host(x) -> _np.ndarray:
+    """`avgpool3s2` on the CPU in the same order of sums (fusg_avgpool3s2_f32_host): numpy float32 [B, C, H, W] in and out."""
+    x = _np.asarray(x)
+    if x.ndim != 4 or x.dtype != _np.float32:
+        raise ValueError(f"avgpool3s2_host: x must be float32 [B, C, H, W], got {x.dtype} {x.shape}")
+    x = _np_nhwc(x)
+    b, c, h, w = x.shape
+    out = _np.zeros((b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=_np.float32).transpose(0, 3, 1, 2)
+    L.check(L.lib().fusg_avgpool3s2_f32_host(C.byref(_np_desc(x, L.F32)), C.byref(_np_desc(out, L.F32))), "avgpool3s2_host")
+    return out
+
+
+def mask_mul(x: torch.Tensor, m: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, C, H, W] * m [B, 1, H, W], float32 through any strides (fusg_mask_mul_f32); out: an NHWC-physical tensor unless given."""
+    _require_gpu(x, "x")
+    _require_gpu(m, "m")
+    if (x.dim() != 4 or m.dim() != 4 or x.dtype != torch.float32 or m.dtype != torch.float32 or m.shape[1] != 1
+            or (m.shape[0],) + tuple(m.shape[2:]) != (x.shape[0],) + tuple(x.shape[2:])):
+        raise ValueError(f"mask_mul: x must be float32 [B, C, H, W] and m float32 [B, 1, H, W], got {tuple(x.shape)} and {tuple(m.shape)}")
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = nhwc_empty(*x.shape, x.device)
+        L.check(L.lib().fusg_mask_mul_f32(C.byref(desc(x)), C.byref(desc(m)), C.byref(desc(out)), stream_ptr()), "mask_mul")
+    return out
+
+
+def gan_terms_chunk(n: int) -> int:
+    """Elements per (row, chunk) workgroup of `gan_terms` for a row of n elements: a function of n only."""
+    return int(L.lib().fusg_gan_terms_chunk(int(n)))
+
+
+def gan_terms(pred: torch.Tensor, label: float = 1.0, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 [B, 6] on the device, columns `GAN_TERM_COLUMNS`: per row of a CUDA float32 [B, C, H, W] `pred` (any strides)
+    n, sum x, sum (m x - m label)^2, sum relu(1 + x), sum relu(1 - x) and the BCE sum against `label` with nn.BCELoss's clamp
+    at -100.  The BCE column is NaN for a row with an x outside [0, 1]: pick the columns that mean something for `pred`.
+    mask: float32 [B, 1, Hm, Wm], sampled as `F.interpolate(mask, size=(H, W))` samples (nearest), used in the squared column
+    only.  Two launches, a fixed order of float64 sums, no atomics, no host synchronisation (fusg_gan_terms_rows_f32)."""
+    _require_gpu(pred, "pred")
+    if pred.dim() != 4 or pred.dtype != torch.float32:
+        raise ValueError(f"gan_terms: pred must be float32 [B, C, H, W], got {pred.dtype} {tuple(pred.shape)}")
+    if mask is not None:
+        _require_gpu(mask, "mask")
+        if mask.dim() != 4 or mask.dtype != torch.float32 or mask.shape[0] != pred.shape[0] or mask.shape[1] != 1:
+            raise ValueError(f"gan_terms: mask must be float32 [{pred.shape[0]}, 1, Hm, Wm], got {mask.dtype} {tuple(mask.shape)}")
+    nc = len(GAN_TERM_COLUMNS)
+    with torch.cuda.device(pred.device):
+        lib = L.lib()
+        nbytes = int(lib.fusg_gan_terms_scratch_bytes(*pred.shape))
+        if nbytes < 0:
+            raise ValueError(f"gan_terms: {tuple(pred.shape)}: a row must hold 1..2^31 - 1 elements, B < 65536")
+        if out is None:
+            out = torch.empty((pred.shape[0], nc), dtype=torch.float64, device=pred.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (pred.shape[0], nc) or not out.is_contiguous() or out.device != pred.device:
+            raise ValueError(f"gan_terms: out must be a contiguous float64 [{pred.shape[0]}, {nc}] on {pred.device}")
+        L.check(lib.fusg_gan_terms_rows_f32(C.byref(desc(pred)), C.byref(desc(mask)) if mask is not None else None, float(label),
+                                            out.data_ptr(), _scratch(pred.device, nbytes).data_ptr(), stream_ptr()), "gan_terms")
+    return out
+
+
+def gan_terms_host(pred, label: float = 1.0, mask=None) -> _np.ndarray:
+    """`gan_terms` on the CPU in the same order of sums (fusg_gan_terms_rows_f32_host): numpy float32 in (any strides), float64
+    [B, 6] out."""
+    pred = _np.asarray(pred)
+    if pred.ndim != 4 or pred.dtype != _np.float32:
+        raise ValueError(f"gan_terms_host: pred must be float32 [B, C, H, W], got {pred.dtype} {pred.shape}")
+    md = None
+    if mask is not None:
+        mask = _np.asarray(mask)
+        if mask.ndim != 4 or mask.dtype != _np.float32 or mask.shape[0] != pred.shape[0] or mask.shape[1] != 1:
+            raise ValueError(f"gan_terms_host: mask must be float32 [{pred.shape[0]}, 1, Hm, Wm], got {mask.dtype} {mask.shape}")
+        md = C.byref(_np_desc(mask, L.F32))
+    out = _np.zeros((pred.shape[0], len(GAN_TERM_COLUMNS)), dtype=_np.float64)
+    L.check(L.lib().fusg_gan_terms_rows_f32_host(C.byref(_np_desc(pred, L.F32)), md, float(label), out.ctypes.data), "gan_terms_host")
     return out
 
 

@@ -18,7 +18,8 @@ import torch
 
 # Per-net gains chosen so that activations stay O(1) through the whole depth with random weights
 # (otherwise tanh saturates / images turn constant and SSIM against the reference is meaningless).
-_CONV_GAIN = {"hg": 0.7, "icn": 1.4, "vunet": 0.7, "edge": 1.4, "inpaint": 1.4, "vgg": 1.4142135}
+_CONV_GAIN = {"hg": 0.7, "icn": 1.4, "vunet": 0.7, "edge": 1.4, "inpaint": 1.4, "vgg": 1.4142135,
+              "edge_dis": 1.4, "inpaint_dis": 1.4, "icn_dis": 1.4}
 
 
 def _gen(net: str, key: str, seed: int) -> torch.Generator:
@@ -37,7 +38,7 @@ def _uniform(shape, lo, hi, g):
 
 def synth_state_dict(net: str, schema: Mapping[str, Tuple[Sequence[int], str]], seed: int = 0
                      ) -> "OrderedDict[str, torch.Tensor]":
-    """Build a full state_dict for ``net`` in {'hg','icn','vunet','edge','inpaint','vgg'}.
+    """Build a full state_dict for ``net`` in {'hg','icn','vunet','edge','inpaint','vgg','edge_dis','inpaint_dis','icn_dis'}.
 
     ``schema`` maps state_dict key -> (shape, dtype-name), in state_dict order (the reference's
     own schema is shipped in the package, schemas/schema_*.json; the HIP-backed modules expose the
@@ -108,6 +109,11 @@ def synth_state_dict(net: str, schema: Mapping[str, Tuple[Sequence[int], str]], 
                 u = torch.nn.functional.normalize(wm.mv(v), dim=0)
             out[key] = u
             out[prefix + ".weight_v"] = v
+    # EdgeConnect's Discriminator registers one module under two names (conv1 and features): the aliased keys hold the same
+    # tensors - left to their own draws, load_state_dict would silently let the later key win
+    for key in keys:
+        if key.startswith("features.") and "conv1." + key[len("features."):] in out:
+            out[key] = out["conv1." + key[len("features."):]]
     for key in keys:
         assert out[key] is not None and tuple(out[key].shape) == tuple(schema[key][0]), key
     return out

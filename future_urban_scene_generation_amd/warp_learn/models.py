@@ -11,10 +11,14 @@ address mapping; ``InstanceNorm -> ReLU -> conv`` chains never materialise the n
 staging its tile); the decoder's ``nearest-upsample -> 5x5 conv`` reads the low-resolution tensor
 directly (upsample folded into the gather), its custom LayerNorm (unbiased std, eps on std)
 becomes the next conv's per-(b,c) affine prologue, and ``x + IN(conv(.))`` is one elementwise pass.
+
+``D_NLayersMulti(input_nc, ndf=64, n_layers=2, num_D=2)`` and ``GANLoss(target_real_label=1.0, target_fake_label=0.0)``
+(warp_learn/models.py:211-320) are provided forward only: the multi-scale PatchGAN critic with the reference's schema
+(``model_{i}.{0,2,5,8}.{weight,bias}`` at the defaults) and the sum over scales of its MSE objective.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -185,6 +189,109 @@ class G_Resnet(FusedNet):
         if image.dim() != 4 or image.shape[1] != self.input_nc or image.shape[2] % 4 or image.shape[3] % 4:
             raise ValueError(f"G_Resnet expects [B,{self.input_nc},H,W] with H,W multiples of 4, got {tuple(image.shape)}")
         return self._decode(P, self._encode(P, image))
+
+
+class D_NLayersMulti(FusedNet):
+    """The ICN's multi-scale PatchGAN critic (reference models.py:211-259), forward only.  Scale i > 0 has
+    ``round(ndf / 2**i)`` base channels and sees the input after i count-excluding 3 x 3 stride-2 average pools.
+    Per scale: the stride-2 stem with LeakyReLU(0.2) in its epilogue; per normed layer ``ops.conv_in`` (InstanceNorm statistics
+    from the conv) and one ``ops.affine_act`` applying norm + LeakyReLU; the final 1-channel conv.  ``forward`` returns the
+    reference's list of logit maps; ``features`` every map of every scale."""
+
+    def __init__(self, input_nc, ndf=64, n_layers=2, num_D=2):
+        super().__init__()
+        self.input_nc, self.ndf, self.n_layers, self.num_D = input_nc, ndf, n_layers, num_D
+        for i in range(num_D):
+            self.add_module("model_%d" % i, nn.Sequential(*self.get_layers(input_nc, int(round(ndf / (2 ** i))), n_layers)))
+
+    @staticmethod
+    def get_layers(input_nc, ndf=64, n_layers=3):
+        """Parameter holders in the reference's slots (conv, [norm], LeakyReLU): each ConvP carries its stride."""
+        I = nn.Identity
+
+        def cv(cin, cout, stride):
+            m = ConvP(cin, cout, 4)
+            m.stride = stride
+            return m
+        seq = [cv(input_nc, ndf, 2), I()]
+        nf = 1
+        for n in range(1, n_layers):
+            prev, nf = nf, min(2 ** n, 8)
+            seq += [cv(ndf * prev, ndf * nf, 2), I(), I()]
+        prev, nf = nf, min(2 ** n_layers, 8)
+        seq += [cv(ndf * prev, ndf * nf, 1), I(), I()]
+        seq += [cv(ndf * nf, 1, 1)]
+        return seq
+
+    def _build_plans(self, device) -> dict:
+        P = {}
+        for i in range(self.num_D):
+            P[i] = [pack.pack_conv(m.weight, m.bias, stride=m.stride, pad=1).to(device)
+                    for m in getattr(self, "model_%d" % i) if isinstance(m, ConvP)]
+        return P
+
+    @staticmethod
+    def _scale(plans, x: torch.Tensor) -> List[torch.Tensor]:
+        y = ops.conv(plans[0], x, act=L.ACT_LEAKY02)
+        maps = [y]
+        for p in plans[1:-1]:
+            c, st = ops.conv_in(p, y)
+            y = ops.affine_act(c, st[0], st[1], L.ACT_LEAKY02)
+            maps.append(y)
+        maps.append(ops.conv(plans[-1], y))
+        return maps
+
+    def _run(self, x: torch.Tensor) -> List[List[torch.Tensor]]:
+        P = self._ensure(x)
+        if x.dim() != 4 or x.shape[1] != self.input_nc:
+            raise ValueError(f"D_NLayersMulti expects [B,{self.input_nc},H,W], got {tuple(x.shape)}")
+        h, w = x.shape[2:]
+        for _ in range(self.num_D - 1):
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        if (h >> self.n_layers) < 3 or (w >> self.n_layers) < 3:
+            raise ValueError(f"D_NLayersMulti: {tuple(x.shape)} leaves the last scale's logit map empty")
+        down = ops.as_nhwc(x.detach())
+        out = []
+        for i in range(self.num_D):
+            out.append(self._scale(P[i], down))
+            if i != self.num_D - 1:
+                down = ops.avgpool3s2(down)
+        return out
+
+    @entry_point
+    def features(self, input: torch.Tensor) -> List[List[torch.Tensor]]:
+        """Per scale: [stem, normed layers ..., logits], each after its LeakyReLU (the reference's is in place) but the logits."""
+        return self._run(input)
+
+    @entry_point
+    def forward(self, input: torch.Tensor) -> List[torch.Tensor]:
+        return [maps[-1] for maps in self._run(input)]
+
+
+class GANLoss(nn.Module):
+    """The reference's least-squares objective (models.py:262-320), forward only: the sum over the scales of
+    ``MSELoss(prediction [* mask], label [* mask])`` as a 0-d float32 device tensor, from ``ops.gan_terms``' squared column (the
+    mask is sampled inside the kernel as ``F.interpolate(mask, size=prediction.shape[2:])`` samples it).  ``do_smooth`` draws
+    ``torch.rand(1)`` from the CPU generator exactly as the reference does.  No host synchronisation."""
+
+    def __init__(self, target_real_label=1.0, target_fake_label=0.0):
+        super().__init__()
+        self.register_buffer("real_label", torch.tensor(target_real_label))
+        self.register_buffer("fake_label", torch.tensor(target_fake_label))
+        self._labels = (torch.tensor(target_fake_label).to(torch.float32), torch.tensor(target_real_label).to(torch.float32))
+
+    def __call__(self, predictions, target_is_real: bool, do_smooth: bool = False, mask: Optional[torch.Tensor] = None):
+        total = None
+        for prediction in predictions:
+            label = self._labels[1 if target_is_real else 0]
+            if do_smooth:
+                label = label + (torch.rand(1) - 0.5) / 2.0           # [-0.25, 0.25], float32 like the reference's tensor
+            if mask is not None:
+                mask = mask.detach().to(prediction.device, torch.float32)
+            t = ops.gan_terms(prediction.detach(), float(label), mask)
+            mse = t[:, 2].sum() / t[:, 0].sum()
+            total = mse if total is None else total + mse
+        return total.to(torch.float32)
 
 
 def get_icn_inputs(planes, sketch_normal, sketch_mask, central_crop, icn_w: int, icn_h: int):

@@ -68,7 +68,8 @@ typedef enum fusg_pre_op {
 
 typedef enum fusg_act {
     FUSG_ACT_NONE = 0, FUSG_ACT_RELU = 1, FUSG_ACT_TANH = 2, FUSG_ACT_SIGMOID = 3,
-    FUSG_ACT_TANH01 = 4        /* (tanh(x)+1)/2, edgeconnect/networks.py:83 */
+    FUSG_ACT_TANH01 = 4,       /* (tanh(x)+1)/2, edgeconnect/networks.py:83 */
+    FUSG_ACT_LEAKY02 = 5       /* v > 0 ? v : 0.2f v - nn.LeakyReLU(0.2), the discriminators'; a NaN stays a NaN */
 } fusg_act;
 
 typedef enum fusg_store_mode {
@@ -873,6 +874,36 @@ int fusg_abs_diff_rows_f32(const fusg_tensor* a, const fusg_tensor* b, double* o
 int64_t fusg_abs_diff_rows_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
 /* The same on HOST pointers. */
 int fusg_abs_diff_rows_f32_host(const fusg_tensor* a, const fusg_tensor* b, double* out);
+
+/* ---- discriminator glue and GAN terms (EdgeConnect's Discriminator / AdversarialLoss, Warp&Learn's D_NLayersMulti / GANLoss,
+ * forward only; new entry points, FUSG_VERSION stays 118 as above) */
+/* nn.AvgPool2d(3, stride=2, padding=1, count_include_pad=False): src, dst NHWC-physical f32 (channel stride 1, any channel
+ * pitch that is a multiple of 4, a channel-slice view included; padding channels are neither read into a result nor written),
+ * any H, W >= 1, dst [B, C, (H - 1) / 2 + 1, (W - 1) / 2 + 1].  The taps inside the image are added to +0 in fp32 in raster
+ * order and divided once by their number.  Bit-identical to the host twin (HOST pointers, the same layout). */
+int fusg_avgpool3s2_f32(const fusg_tensor* src, const fusg_tensor* dst, void* stream);
+int fusg_avgpool3s2_f32_host(const fusg_tensor* src, const fusg_tensor* dst);
+/* dst[b, c, y, x] = x[b, c, y, x] * m[b, 0, y, x]: f32 descriptors of any strides, x and dst of one shape, m [B, 1, H, W]. */
+int fusg_mask_mul_f32(const fusg_tensor* x, const fusg_tensor* m, const fusg_tensor* dst, void* stream);
+/* Per-row sums behind the GAN objectives.  pred: f32 [B, C, H, W] through any strides (only logical elements are read),
+ * C H W < 2^31, B < 65536; out: DEVICE float64 [B][fusg_gan_terms_columns() = 6], per row over its elements x (each widened
+ * to float64, order (y, x, c)):
+ *   0 n   1 sum x   2 sum (m x - m label)^2   3 sum relu(1 + x)   4 sum relu(1 - x)
+ *   5 sum -[label max(log x, -100) + (1 - label) max(log(1 - x), -100)]     (nn.BCELoss's clamp)
+ * Column 5 is NaN for a row holding an x outside [0, 1] (logits, not probabilities): the caller picks the columns that mean
+ * something for its pred.  mask: NULL (or data NULL: m = 1) or f32 [B, 1, Hm, Wm], sampled as F.interpolate(mask,
+ * size=(H, W)) samples in its default nearest mode - source index min((int)floorf(dst * ((float)Hm / (float)H)), Hm - 1) -
+ * and used in column 2 only.  Two launches: float64 partials per (row, chunk) workgroup into scratch (DEVICE, 16-byte
+ * aligned, the size query's bytes; chunk boundaries - fusg_gan_terms_chunk(n) elements each - depend on the row's element
+ * count only), then one fixed-order add per row.  No atomics; a row's bits do not depend on B.  B = 0 launches nothing;
+ * anything else wrong: FUSG_ERR_INVALID before any launch.  Bit-identical to the host twin: the logarithm is the library's
+ * own float64 routine on both sides (csrc/gan_terms.h), a few ulp from the exact value. */
+int fusg_gan_terms_rows_f32(const fusg_tensor* pred, const fusg_tensor* mask, float label, double* out, void* scratch, void* stream);
+int64_t fusg_gan_terms_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int32_t fusg_gan_terms_columns(void);
+int64_t fusg_gan_terms_chunk(int64_t n);
+/* The same on HOST pointers. */
+int fusg_gan_terms_rows_f32_host(const fusg_tensor* pred, const fusg_tensor* mask, float label, double* out);
 
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
