@@ -191,6 +191,8 @@ _SIGS = {
     "fusg_gan_terms_columns": (C.c_int32, []),
     "fusg_gan_terms_chunk": (C.c_int64, [C.c_int64]),
     "fusg_gan_terms_rows_f32_host": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p]),
+    "fusg_background_median_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 3),
+    "fusg_background_median_host": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 2),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

@@ -1657,6 +1657,111 @@ def gan_terms_host(pred, label: float = 1.0, mask=None) -> _np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------
+# background frame (csrc/background.h): the per-pixel lower median of the frames in which no tracker box covers the pixel
+# ---------------------------------------------------------------------------------------------
+BACKGROUND_MAX_FRAMES = 64
+BACKGROUND_MAX_BOXES = 64           # per frame
+BACKGROUND_MAX_DIM = 32767          # H, W and the margin
+
+
+def _background_frames(frames, u8, what: str):
+    """The T frames as a list, checked: uint8 [H, W, 3], dense, one shape, T, H and W inside the limits."""
+    if not isinstance(frames, (list, tuple)):
+        if not hasattr(frames, "shape") or len(frames.shape) != 4:
+            raise ValueError(f"{what}: frames must be a sequence of uint8 [H, W, 3] images or one [T, H, W, 3] stack")
+        frames = [frames[t] for t in range(frames.shape[0])]
+    T = len(frames)
+    if not 1 <= T <= BACKGROUND_MAX_FRAMES:
+        raise ValueError(f"{what}: {T} frames (1..{BACKGROUND_MAX_FRAMES})")
+    for t, f in enumerate(frames):
+        if not hasattr(f, "shape") or f.dtype != u8 or len(f.shape) != 3 or f.shape[2] != 3:
+            raise ValueError(f"{what}: frame {t} must be uint8 [H, W, 3], got {getattr(f, 'dtype', type(f))} {tuple(getattr(f, 'shape', ()))}")
+        if tuple(f.shape) != tuple(frames[0].shape):
+            raise ValueError(f"{what}: frame {t} is {tuple(f.shape)}, frame 0 is {tuple(frames[0].shape)}")
+        if not (f.is_contiguous() if isinstance(f, torch.Tensor) else f.flags.c_contiguous):
+            raise ValueError(f"{what}: frame {t} is not contiguous")
+    H, W = int(frames[0].shape[0]), int(frames[0].shape[1])
+    if not (1 <= H <= BACKGROUND_MAX_DIM and 1 <= W <= BACKGROUND_MAX_DIM):
+        raise ValueError(f"{what}: frames of {H} x {W} (H and W in 1..{BACKGROUND_MAX_DIM})")
+    return list(frames), T, H, W
+
+
+def _background_args(T: int, boxes, margin, min_valid, what: str):
+    """(flat int32 [N, 4] boxes, int32 [T + 1] offsets, margin, min_valid), checked against the limits."""
+    margin, min_valid = int(margin), int(min_valid)
+    if not 0 <= margin <= BACKGROUND_MAX_DIM:
+        raise ValueError(f"{what}: margin = {margin} (0..{BACKGROUND_MAX_DIM})")
+    if not 1 <= min_valid <= T:
+        raise ValueError(f"{what}: min_valid = {min_valid} (1..T = {T})")
+    offs = _np.zeros((T + 1,), dtype=_np.int32)
+    if boxes is None:
+        return _np.zeros((0, 4), dtype=_np.int32), offs, margin, min_valid
+    if len(boxes) != T:
+        raise ValueError(f"{what}: {len(boxes)} box lists for {T} frames")
+    rows = []
+    for t, b in enumerate(boxes):
+        b = _np.asarray(b)
+        if b.size and (b.dtype.kind not in "iu" or b.size % 4 or (b.ndim > 1 and b.shape[-1] != 4)):
+            raise ValueError(f"{what}: the boxes of frame {t} must be an integer [n, 4] array, got {b.dtype} {b.shape}")
+        b = b.reshape(-1, 4).astype(_np.int64)
+        if b.shape[0] > BACKGROUND_MAX_BOXES:
+            raise ValueError(f"{what}: frame {t} has {b.shape[0]} boxes (at most {BACKGROUND_MAX_BOXES})")
+        if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
+            raise ValueError(f"{what}: a box of frame {t} does not fit int32")
+        rows.append(b.astype(_np.int32))
+        offs[t + 1] = offs[t] + b.shape[0]
+    return _np.ascontiguousarray(_np.concatenate(rows, axis=0)), offs, margin, min_valid
+
+
+def background_median(frames, boxes=None, margin: int = 0, min_valid: int = 1, out=None):
+    """(bg uint8 [H, W, 3], count uint8 [H, W]) on the device: per pixel and channel the lower median (rank (m - 1) // 2, always a
+    value that occurred) over the frames in which no box, grown by `margin` on every side, covers the pixel; `count` is the
+    number of those frames, and a pixel with count < min_valid took all T frames instead.  frames: a sequence of T <= 64 CUDA
+    uint8 [H, W, 3] tensors (separate allocations are fine) or one [T, H, W, 3] tensor; boxes: None or T host int arrays
+    [nb_t, 4] of (x0, y0, x1, y1), both ends inclusive, at most 64 per frame.  out: an optional (bg, count) pair to write into.
+    One launch on the current stream, no atomics, no host synchronisation (fusg_background_median_u8)."""
+    what = "background_median"
+    frames, T, H, W = _background_frames(frames, torch.uint8, what)
+    dev = frames[0].device
+    for t, f in enumerate(frames):
+        if f.device != dev:
+            raise ValueError(f"{what}: frame {t} is on {f.device}, frame 0 on {dev}")
+    flat, offs, margin, min_valid = _background_args(T, boxes, margin, min_valid, what)
+    _require_gpu(frames[0], "frames")
+    if out is not None:
+        bg, count = out
+        for name, o, shape in (("bg", bg, (H, W, 3)), ("count", count, (H, W))):
+            if o.dtype != torch.uint8 or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev:
+                raise ValueError(f"{what}: out's {name} must be a contiguous uint8 {shape} tensor on {dev}")
+    with torch.cuda.device(dev):
+        if out is None:
+            bg = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+            count = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        dbox = h2d(flat, dev) if flat.shape[0] else None
+        ptrs = (C.c_void_p * T)(*[f.data_ptr() for f in frames])
+        L.check(L.lib().fusg_background_median_u8(ptrs, T, H, W, dbox.data_ptr() if dbox is not None else None, offs.ctypes.data, margin,
+                                                  min_valid, bg.data_ptr(), count.data_ptr(), stream_ptr()), what)
+        if RECORDER is not None and dbox is not None:
+            RECORDER.keep.append(dbox)
+    return bg, count
+
+
+def background_median_host(frames, boxes=None, margin: int = 0, min_valid: int = 1):
+    """`background_median` on the CPU by the same code (fusg_background_median_host; no GPU needed): numpy uint8 frames in,
+    (bg, count) numpy arrays out."""
+    what = "background_median_host"
+    frames = [_np.asarray(f) for f in frames] if isinstance(frames, (list, tuple)) else _np.asarray(frames)
+    frames, T, H, W = _background_frames(frames, _np.uint8, what)
+    flat, offs, margin, min_valid = _background_args(T, boxes, margin, min_valid, what)
+    bg = _np.zeros((H, W, 3), dtype=_np.uint8)
+    count = _np.zeros((H, W), dtype=_np.uint8)
+    ptrs = (C.c_void_p * T)(*[f.ctypes.data for f in frames])
+    L.check(L.lib().fusg_background_median_host(ptrs, T, H, W, flat.ctypes.data if flat.shape[0] else None, offs.ctypes.data, margin,
+                                                min_valid, bg.ctypes.data, count.ctypes.data), what)
+    return bg, count
+
+
+# ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------
 def prof_enable(on: bool) -> None:

@@ -1742,6 +1742,31 @@ class VehiclePipeline:
         return scene["frame"] if inp is not None else scene.get("background", scene["frame"])
 
     @staticmethod
+    def background_indices(n: int, max_frames: int = 64) -> List[int]:
+        """The scenes `estimate_background` samples out of n: all of them up to max_frames, else (i * n) // max_frames."""
+        if n < 1 or not 1 <= max_frames <= 64:
+            raise ValueError(f"estimate_background: {n} scenes, max_frames = {max_frames} (at least one scene, max_frames in 1..64)")
+        return list(range(n)) if n <= max_frames else [(i * n) // max_frames for i in range(max_frames)]
+
+    def estimate_background(self, scenes, max_frames: int = 64, margin: int = 8, min_valid: Optional[int] = None) -> Dict:
+        """The 'background' the default mode's composites start from (`_paste_base`; the reference reads background_frame.png,
+        trajectory_inference.py:42-53, and has no code that makes it), estimated from the video itself: per pixel and channel the
+        lower median over the sampled frames in which no detector box, grown by `margin`, covers the pixel (`ops.background_median`:
+        one launch, nothing read back).  scenes: `run_frames`-style, 'frame' uint8 [H, W, 3] (CUDA) and 'bboxes' int [V, 4] (host).
+        min_valid=None: max(1, T // 8) of the T sampled frames; a pixel that fewer frames see takes all T.  Returns 'background'
+        uint8 [H, W, 3] and 'count' uint8 [H, W] on the device (count < min_valid marks the fallback pixels), 'frames' (the indices
+        used) and 'min_valid'.  Nothing is put into the scenes: the caller sets scene['background']."""
+        import numpy as np
+
+        from . import ops
+        idx = self.background_indices(len(scenes), max_frames)
+        T = len(idx)
+        mv = max(1, T // 8) if min_valid is None else int(min_valid)
+        boxes = [np.asarray(scenes[i]["bboxes"]).reshape(-1, 4) for i in idx]
+        bg, count = ops.background_median([scenes[i]["frame"] for i in idx], boxes, margin=margin, min_valid=mv)
+        return {"background": bg, "count": count, "frames": idx, "min_valid": mv}
+
+    @staticmethod
     def _composites(paste, out: Dict, box_geom=None) -> Dict:
         """'frame_icn' and 'frame_vunet': paste(crops, **box) once per composite (:184-198, :236-250; :393-410, :428-445), the
         driver's paste function closed over its bases, rows, crop rows and masks.  box_geom (`_box_rows`): with inpainting every

@@ -905,6 +905,27 @@ int64_t fusg_gan_terms_chunk(int64_t n);
 /* The same on HOST pointers. */
 int fusg_gan_terms_rows_f32_host(const fusg_tensor* pred, const fusg_tensor* mask, float label, double* out);
 
+/* ---- background frame (what the default mode's composites start from - scene['background'] - estimated from the video's own
+ * frames; new entry points, FUSG_VERSION stays 118 as above) */
+/* bg[y, x, c] = the LOWER median - rank (m - 1) / 2 of the m samples in ascending order, always a value that occurred - of
+ * channel c of pixel (x, y) over the frames in which no box covers the pixel; count[y, x] = n, the number of those frames.
+ * Frame t covers (x, y) if one of its boxes has x0 - margin <= x <= x1 + margin and y0 - margin <= y <= y1 + margin (both ends
+ * inclusive; a box may reach outside the frame; one with x1 < x0 or y1 < y0 covers nothing).  A pixel with n < min_valid takes
+ * all T frames instead (the fallback: the caller sees it as count < min_valid).  csrc/background.h states the arithmetic.
+ * frame_ptrs: HOST table of T DEVICE pointers to dense u8 [H, W, 3] frames (separate allocations; 4-byte aligned ones are
+ * read as dwords); box_offs: HOST int32 [T + 1], frame t's boxes are rows [box_offs[t], box_offs[t + 1]) of boxes, a DEVICE
+ * int32 [box_offs[T]][4] table of (x0, y0, x1, y1) with any values (box_offs NULL: no boxes; boxes may then be NULL).  bg: DEVICE
+ * u8 [H, W, 3], count: DEVICE u8 [H, W], both dense and written whole, nothing outside them.  Both HOST tables are read before
+ * the call returns.  Checked on the host before anything is launched (FUSG_ERR_INVALID): T in 1..64, H and W in 1..32767,
+ * margin in 0..32767, min_valid in 1..T, at most 64 boxes per frame, offsets from 0, no null frame.  One launch (two when 3 H W
+ * is not a multiple of 4: the last bytes), no atomics, no scratch memory: a pixel's bytes depend on its own samples and boxes
+ * only, not on H, W, T's bucket or the launch.  Bit-identical to the host twin. */
+int fusg_background_median_u8(const void* const* frame_ptrs, int32_t T, int32_t H, int32_t W, const int32_t* boxes,
+                              const int32_t* box_offs, int32_t margin, int32_t min_valid, uint8_t* bg, uint8_t* count, void* stream);
+/* The same code on the CPU: every pointer (the frames, boxes, bg and count included) is a HOST pointer, no GPU needed. */
+int fusg_background_median_host(const void* const* frame_ptrs, int32_t T, int32_t H, int32_t W, const int32_t* boxes,
+                                const int32_t* box_offs, int32_t margin, int32_t min_valid, uint8_t* bg, uint8_t* count);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)
