@@ -56,7 +56,7 @@ hipError_t ensure_dyn_lds(const void* fn, int bytes);
 
 // Development switches, read from the environment ONCE (first use): FUSG_NO_VEC_EPI, FUSG_NO_HALO, FUSG_NO_TOUCH,
 // FUSG_NO_POINTWISE, FUSG_NO_KSPLIT, FUSG_HALO_MINWG, FUSG_HALO_BN, FUSG_SMALL_MAXHW (tools/README.md).  (api.hip)
-// The per-call switches (FUSG_NO_SMALL, FUSG_NO_POINTWISE, FUSG_NO_F32_HALO, FUSG_NO_BF16_TAPUNIT, FUSG_SMALL_KSPLIT) are
+// The per-call switches (FUSG_NO_SMALL, FUSG_NO_POINTWISE, FUSG_NO_F32_HALO, FUSG_NO_BF16_TAPUNIT, FUSG_SMALL_KSPLIT, FUSG_NO_HALO_COLMAJOR) are
 // read by the conv router on every call instead (conv_igemm.hip).
 struct EnvSwitches { bool no_vec_epi, no_halo, no_touch, no_pointwise, no_ksplit; long halo_minwg; int halo_bn, small_maxhw; };
 const EnvSwitches& env_switches();

@@ -5,7 +5,10 @@
 // 24.28 -> 23.54 ms, 1383 -> 1424 crops/s; the bf16 mode does not care (18.16 vs 18.19 ms).
 #include "conv_kernel_halo.h"
 namespace fusg {
-hipError_t launch_halo_128(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode) { return launch_halo<4,1,1,4>(k, grid, s, pk, mode); }
+// Dense 3x3 dil 1 split-fp16 launches walk a chunk's taps column-major when `colmajor` allows it (conv_kernel_halo.h, CM).
+hipError_t launch_halo_128(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode, bool colmajor) {
+    return launch_halo<4,1,1,4>(k, grid, s, pk, mode, colmajor);
+}
 }  // namespace fusg
 #ifdef FUSG_HALO_STAMPS
 extern "C" int fusg_debug_halo_stamps(unsigned long long* out) {

@@ -305,6 +305,7 @@ struct ConvRoute {
     bool ksw;                   // halo: K split over the waves (the 64k / 32k instantiations)
     bool s2d;                   // halo: parity-quadrant form
     int sp;                     // halo: tap-sparse pattern the launch skips by (fusg_conv_desc.tap_sparse), 0 = dense
+    bool cm;                    // halo: a chunk's taps column-major (conv_kernel_halo.h, CM) - another summation order
     int HH, HW;                 // halo / tap-unit: halo extent in (virtual) input pixels
     int RP, unit;               // tap-unit: LDS pitch of a halo row, channels per K unit
 };
@@ -344,6 +345,7 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
     const int nphase = d->nphase > 0 ? d->nphase : 1;
     FUSG_CHECK(nphase == 1 || nphase == 4, "conv2d: nphase %d", nphase);
     r->sp = 0;
+    r->cm = false;
     if (d->tap_sparse != 0) {
         // the patterns describe ONE weight form (include/fusg.h): anything else would run dense weights that are not the layer
         if (!((d->tap_sparse == 1 || d->tap_sparse == 2) && d->kh == 3 && d->kw == 3 && d->pad_h == 1 && d->pad_w == 1 &&
@@ -512,6 +514,10 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
             r->mode = f32_frag ? 2 : (bf ? 1 : 0);
             // tap-sparse weights: the sibling instantiations skip the dead taps (bf16 has none: it runs the dense weights)
             r->sp = r->mode != 1 ? d->tap_sparse : 0;
+            // dense 3x3 dil 1 split-fp16 launches of the 128-column tile: the taps of a chunk column-major (each staged row read
+            // once per tap column).  (FUSG_NO_HALO_COLMAJOR, read per call, keeps the tap-major order: tests and the A/B compare the two)
+            r->cm = r->bn == 128 && !r->ksw && r->mode == 0 && r->sp == 0 && !s2d && d->kh == 3 && d->kw == 3 && d->dil == 1 &&
+                    getenv("FUSG_NO_HALO_COLMAJOR") == nullptr;
             r->family = f32_frag ? FUSG_CONV_HALO_F32 : bf ? FUSG_CONV_HALO_BF16 : (s2d ? FUSG_CONV_HALO_S2D : FUSG_CONV_HALO);
             return FUSG_OK;
         }
@@ -618,13 +624,13 @@ static hipError_t run_halo(const ConvK& k, const fusg_conv_desc& d, const ConvRo
     }
     const dim3 grid(h.c.MT * h.c.NT, 1, 1);
     if (en)                                     // entry-NiN launches: the two forms entry_route admits
-        return r.bn == 128 && !r.ksw ? launch_halo_en_128(h, *en, grid, s)
+        return r.bn == 128 && !r.ksw ? launch_halo_en_128(h, *en, grid, s, r.cm)
                                      : r.bn == 32 && r.ksw ? launch_halo_en_32k(h, *en, grid, s) : hipErrorInvalidValue;
     if (r.sp)
         return r.bn == 128 ? launch_halo_ts_128(h, grid, s, pk, r.mode, r.sp)
                            : r.bn == 64 ? (r.ksw ? launch_halo_ts_64k(h, grid, s, pk, r.mode, r.sp) : launch_halo_ts_64(h, grid, s, pk, r.mode, r.sp))
                                         : (r.ksw ? launch_halo_ts_32k(h, grid, s, pk, r.mode, r.sp) : launch_halo_ts_32(h, grid, s, pk, r.mode, r.sp));
-    return r.bn == 128 ? launch_halo_128(h, grid, s, pk, r.mode)
+    return r.bn == 128 ? launch_halo_128(h, grid, s, pk, r.mode, r.cm)
                        : r.bn == 64 ? (r.ksw ? launch_halo_64k(h, grid, s, pk, r.mode) : launch_halo_64(h, grid, s, pk, r.mode))
                                     : (r.ksw ? launch_halo_32k(h, grid, s, pk, r.mode) : launch_halo_32(h, grid, s, pk, r.mode));
 }
@@ -660,7 +666,7 @@ extern "C" int fusg_conv2d_route_order(const fusg_conv_desc* din, int32_t out[4]
     out[0] = r.family;
     out[1] = generic ? d.tile : (halo || tapunit ? r.bn : 0);
     out[2] = r.family == FUSG_CONV_SMALL ? r.sc.ksplit : (generic ? d.ksplit : 1);
-    out[3] = halo && r.ksw ? 1 : 0;
+    out[3] = halo && r.ksw ? 1 : (halo && r.cm ? 2 : 0);       // K split over the waves / column-major taps / neither
     return FUSG_OK;
 }
 

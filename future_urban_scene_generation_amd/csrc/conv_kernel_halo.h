@@ -28,6 +28,9 @@
 //
 // Loop nest: source -> 32-channel chunk -> tap;  K index of a (chunk, tap) weight tile in the packed
 // panel = tap * Ctot + channel (same panels as the generic kernel, no re-packing).
+// Summation order of an accumulator: (chunk, ky, kx, term) with term = (ah wh, ah wl, al wh 2^-11) - except in the column-major
+// instantiations (CM below: the 128-column tile's dense 3x3 dil 1 split-fp16 launches), where it is (chunk, kx, ky, term).  Which of
+// the two a launch takes depends on its descriptor and tile alone (fusg_conv2d_route_order reports it), never on the batch.
 #pragma once
 #include "conv_kernel_h3.h"
 #ifndef FUSG_HALO_WAVES
@@ -184,7 +187,17 @@ constexpr unsigned tap_sparse_mask(int sp, int phase) {
     return m;
 }
 
-template <int TM, int TN, int WM, int WN, int PK, int NI, int MODE, int KS = 1>
+// CM = 1 ("column-major taps", the 3x3 dil 1 launches of the 128-column tile in split-fp16 mode): within a chunk the taps are
+// walked kx-outer.  The A fragment of output row i at tap (ky, kx) is the fragment of staged halo row i + ky at column shift kx,
+// so for a fixed kx the three ky taps touch only 10 distinct halo rows: their (hi, lo) fragments are read from LDS ONCE into
+// registers (20 ds_read_b128) and the three taps issue from them - 60 reads per chunk instead of 144.  Weights keep their
+// pipeline (one tap ahead, two fragment sets) and their packed layout; only the order in which a chunk's nine slabs are
+// visited changes.  Per accumulator the summation order is (chunk, kx, ky, term) instead of (chunk, ky, kx, term): a CM launch
+// is deterministic and batch-invariant, but not bit-identical to the tap-major (CM = 0) launch of the same layer.
+// launch_halo / launch_halo_en pick the variant on the host (halo_colmajor_ok); the kernel carries no run-time flag.
+constexpr bool halo_colmajor_tile(int tm, int ks) { return tm == 4 && ks == 1; }
+
+template <int TM, int TN, int WM, int WN, int PK, int NI, int MODE, int KS = 1, int CM = 0>
 __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS)) void conv_halo_h3(const HaloK hk) {
     constexpr int SP = 0, EN = 0;
     const EntryK en = {};
@@ -194,12 +207,12 @@ __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS))
 template <int TM, int TN, int WM, int WN, int PK, int NI, int MODE, int KS, int SP>
 __global__ __launch_bounds__(256, halo_waves_mode(TM, TN, WM, PK, NI, MODE, KS)) void conv_halo_ts(const HaloK hk) {
     static_assert(SP != 0, "conv_halo_h3 is the dense kernel");
-    constexpr int EN = 0;
+    constexpr int EN = 0, CM = 0;
     const EntryK en = {};
 #include "conv_kernel_halo_body.inc"
 }
 // the entry-NiN sibling (EN = 1): source 0 computed from `en.u`; the 3x3 ELU launch of the VUnet's InitBlock(6, 128) in its two forms
-template <int TM, int TN, int WM, int WN, int KS>
+template <int TM, int TN, int WM, int WN, int KS, int CM = 0>
 __global__ __launch_bounds__(256, FUSG_HALO_WAVES) void conv_halo_en(const HaloK hk, const EntryK en) {
     constexpr int PK = PK_ELU, NI = 6, MODE = 0, SP = 0, EN = 1;
 #include "conv_kernel_halo_body.inc"
@@ -247,11 +260,20 @@ hipError_t launch_halo_fn(const HaloK& k, dim3 grid, hipStream_t s, int pk, int 
     return launch_kernel(fn, grid, lds, 96 * 1024 + TOUCH_LDS_BYTES, kk, s);
 }
 
+// Does this launch qualify for the column-major tap order (CM above)?  Dense 3x3, dil 1, split-fp16, not the quadrant form.
+inline bool halo_colmajor_ok(const HaloK& k, int mode) { return mode == 0 && k.kh == 3 && k.kw == 3 && k.dil == 1 && !k.s2d; }
+
+// colmajor: the caller allows the column-major variant (conv_igemm.hip: on unless FUSG_NO_HALO_COLMAJOR is set)
 template <int TM, int TN, int WM, int WN, int KS = 1>
-hipError_t launch_halo(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode) {
-    return launch_halo_fn<TM, TN, WM, WN, KS>(k, grid, s, pk, mode, [pk, mode](int ni) {
-        return pick_pk(pk, [ni, mode](auto pkc) {
+hipError_t launch_halo(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode, bool colmajor = false) {
+    const bool cm = colmajor && halo_colmajor_tile(TM, KS) && halo_colmajor_ok(k, mode);
+    return launch_halo_fn<TM, TN, WM, WN, KS>(k, grid, s, pk, mode, [pk, mode, cm](int ni) {
+        return pick_pk(pk, [ni, mode, cm](auto pkc) {
             constexpr int PK = decltype(pkc)::value;
+            (void)cm;
+            if constexpr (halo_colmajor_tile(TM, KS)) {            // (a 10 x 18 halo: 6 items per thread)
+                if (cm) return ni <= 6 ? (const void*)conv_halo_h3<TM, TN, WM, WN, PK, 6, 0, KS, 1> : (const void*)nullptr;
+            }
             auto by_ni = [ni](auto mdc) {
                 constexpr int MD = decltype(mdc)::value;
                 return ni <= 6 ? (const void*)conv_halo_h3<TM, TN, WM, WN, PK, 6, MD, KS>
@@ -284,7 +306,7 @@ hipError_t launch_halo_ts(const HaloK& k, dim3 grid, hipStream_t s, int pk, int 
 // entry-NiN launches: 3x3 dil 1 zero padding 1 (a 10 x 18 halo: 6 items per thread), split-fp16, ELU; the NiN's LDS region must fit
 // under the epilogue's detour.  Same LDS bytes, grid and reciprocals as the dense launch it stands for.
 template <int TM, int TN, int WM, int WN, int KS = 1>
-hipError_t launch_halo_en(const HaloK& k, const EntryK& en, dim3 grid, hipStream_t s) {
+hipError_t launch_halo_en(const HaloK& k, const EntryK& en, dim3 grid, hipStream_t s, bool colmajor = false) {
     if (k.kh != 3 || k.kw != 3 || k.dil != 1 || k.pad_h != 1 || k.pad_w != 1 || k.s2d || k.c1k || k.tile_list || k.c.pad_mode != FUSG_PAD_ZERO ||
         k.c.ups || !k.c.vec_epi)
         return hipErrorInvalidValue;
@@ -292,16 +314,19 @@ hipError_t launch_halo_en(const HaloK& k, const EntryK& en, dim3 grid, hipStream
     if (need > (size_t)4 * TM * 32 * TN * 32 * sizeof(float)) return hipErrorInvalidValue;
     HaloK kk;
     size_t lds = 0;
-    const hipError_t e = launch_halo_fn<TM, TN, WM, WN, KS>(k, grid, s, PK_ELU, 0, [&](int ni) {
-        return ni == 6 ? (const void*)conv_halo_en<TM, TN, WM, WN, KS> : (const void*)nullptr; }, &kk, &lds);
-    if (e != hipSuccess) return e;
     const void* fn = (const void*)conv_halo_en<TM, TN, WM, WN, KS>;
+    if constexpr (halo_colmajor_tile(TM, KS)) {                    // (the checks above are halo_colmajor_ok's)
+        if (colmajor) fn = (const void*)conv_halo_en<TM, TN, WM, WN, KS, 1>;
+    }
+    const hipError_t e = launch_halo_fn<TM, TN, WM, WN, KS>(k, grid, s, PK_ELU, 0, [&](int ni) {
+        return ni == 6 ? fn : (const void*)nullptr; }, &kk, &lds);
+    if (e != hipSuccess) return e;
     if (hipError_t e2 = ensure_dyn_lds(fn, 96 * 1024 + TOUCH_LDS_BYTES); e2 != hipSuccess) return e2;
     void* args[] = {(void*)&kk, (void*)&en};
     return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
 }
 
-hipError_t launch_halo_128(const HaloK&, dim3, hipStream_t, int, int);
+hipError_t launch_halo_128(const HaloK&, dim3, hipStream_t, int, int, bool colmajor);   // colmajor: launch_halo's
 hipError_t launch_halo_64(const HaloK&, dim3, hipStream_t, int, int);
 hipError_t launch_halo_32(const HaloK&, dim3, hipStream_t, int, int);
 hipError_t launch_halo_32k(const HaloK&, dim3, hipStream_t, int, int);      // K split over the four waves
@@ -313,7 +338,7 @@ hipError_t launch_halo_ts_32(const HaloK&, dim3, hipStream_t, int, int, int);
 hipError_t launch_halo_ts_32k(const HaloK&, dim3, hipStream_t, int, int, int);
 hipError_t launch_halo_ts_64k(const HaloK&, dim3, hipStream_t, int, int, int);
 // the entry-NiN siblings (conv_halo_en_*.hip): the two forms the VUnet's InitBlock(6, 128) launches
-hipError_t launch_halo_en_128(const HaloK&, const EntryK&, dim3, hipStream_t);
+hipError_t launch_halo_en_128(const HaloK&, const EntryK&, dim3, hipStream_t, bool colmajor);
 hipError_t launch_halo_en_32k(const HaloK&, const EntryK&, dim3, hipStream_t);
 
 }  // namespace fusg

@@ -387,6 +387,87 @@
                 __syncthreads();
             }
         }
+    } else if constexpr (CM != 0) {
+    // ---- column-major taps (dense 3x3, dil 1, split-fp16, the wave owns all eight patch rows): a step is a tap COLUMN of a
+    // chunk.  Its ten halo-row fragments (hi, lo) at column shift kx are read once; row group i of tap ky uses fragment i + ky.
+    // Weights: as in the tap-major loop one tap ahead through bfA / bfB - a column is three taps, so the two sets change roles
+    // from one column to the next.  Slab of (ky, kx, chunk) = (3 ky + kx) * tapstride + chunk * wstep: the packed layout's.
+    static_assert(TM == 4 && WM == 1 && KS == 1 && SP == 0 && MODE == 0, "column-major taps: the split-fp16 M-whole wide tile");
+    halo_issue(hA, 0, 0, 0);
+    b_load(bfA, wfr);
+    halo_commit(hA);
+    __syncthreads();
+    int cgc = 0, kxc = 0;
+    // The fragments live in eight register slots, halo row r in slot r % 8: row 0 is dead after the ky = 0 tap and row 1 after
+    // the ky = 1 tap, so rows 8 and 9 take their slots - the A operands keep the 64 registers of the tap-major loop
+    // (DESIGN.md 4.1g: resource figures, and the ten-slot form that was dropped).
+    auto tap_mfma = [&](auto kyc, const h8 (&ah)[8], const h8 (&al)[8], const BFrag& F) __attribute__((always_inline)) {
+        constexpr int KY = decltype(kyc)::value;
+        h8 bs[TN][2];
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) bs[j][ct] = scale_m11(F.f[j][ct][0]);       // wh * 2^-11: B operand of the al' term
+        // term-major order, as in compute()
+#pragma unroll
+        for (int term = 0; term < 3; ++term)
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct)
+                        acc[i][2 * j + ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                            term == 2 ? al[(i + KY) & 7] : ah[(i + KY) & 7], term == 0 ? F.f[j][ct][0] : term == 1 ? F.f[j][ct][1] : bs[j][ct],
+                            acc[i][2 * j + ct], 0, 0, 0);
+    };
+    auto one_column = [&](BFrag& F0, BFrag& F1) __attribute__((always_inline)) {      // F0: holds the column's ky = 0 weights
+        if (kxc == 0) {
+            FUSG_HSTAMP(1 + 3 * cgc);
+            if (cgc + 1 < nch) halo_issue(hA, cgc + 1, 0, 0);      // in flight during all taps of this chunk
+        }
+        const _Float16* wcol = wfr + (long)kxc * tapstride + (long)cgc * wstep;     // slab (ky 0, kxc) of this chunk
+        b_load(F1, wcol + 3 * tapstride);
+        const int hx = (lane & 15) + kxc;
+        const int toff = hx * HPITCH + (((lane >> 4) ^ (((hx >> 2) & 1) << 1)) << 3);
+        h8 ah[8], al[8];
+        auto a_row = [&](auto slotc, int r) __attribute__((always_inline)) {        // halo row r -> slot r % 8
+            ah[decltype(slotc)::value] = *(const h8*)(Ah + r * hk.RP + toff);
+            al[decltype(slotc)::value] = *(const h8*)(Al + r * hk.RP + toff);
+        };
+        a_row(std::integral_constant<int, 0>{}, 0); a_row(std::integral_constant<int, 1>{}, 1);
+        a_row(std::integral_constant<int, 2>{}, 2); a_row(std::integral_constant<int, 3>{}, 3);
+        a_row(std::integral_constant<int, 4>{}, 4); a_row(std::integral_constant<int, 5>{}, 5);
+        a_row(std::integral_constant<int, 6>{}, 6); a_row(std::integral_constant<int, 7>{}, 7);
+        tap_mfma(std::integral_constant<int, 0>{}, ah, al, F0);
+        // (the barriers keep the scheduler from hoisting the two late rows above the tap that frees their slots: DESIGN.md 4.1g)
+        __builtin_amdgcn_sched_barrier(0);
+        a_row(std::integral_constant<int, 0>{}, 8);
+        b_load(F0, wcol + 6 * tapstride);
+        tap_mfma(std::integral_constant<int, 1>{}, ah, al, F1);
+        __builtin_amdgcn_sched_barrier(0);
+        a_row(std::integral_constant<int, 1>{}, 9);
+        // the next column's first tap: (ky 0, kxc + 1) of this chunk, or tap 0 of the next chunk
+        if (kxc < 2) b_load(F1, wcol + tapstride);
+        else if (cgc + 1 < nch) b_load(F1, wfr + (long)(cgc + 1) * wstep);
+        tap_mfma(std::integral_constant<int, 2>{}, ah, al, F0);
+        if (++kxc == 3) {
+            FUSG_HSTAMP(2 + 3 * cgc);
+            kxc = 0;
+            if (++cgc < nch) {
+                __syncthreads();                                   // every wave is done with the old halo
+                halo_commit(hA);
+                __syncthreads();
+            }
+            FUSG_HSTAMP(3 * cgc);
+        }
+    };
+    for (;;) {
+        one_column(bfA, bfB);
+        if (cgc >= nch) break;
+        one_column(bfB, bfA);
+        if (cgc >= nch) break;
+    }
     } else {
     // ---- prologue: halo of chunk 0 and the first weight fragments
     // (Tried in round 3 and left off: weights TWO steps ahead through a ring of three fragment sets for the short steps -

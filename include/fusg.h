@@ -254,7 +254,9 @@ int32_t fusg_route_batch(void);
 /* Dry run like fusg_conv2d_route (no launch, no device): what fixes the summation order of the launch fusg_conv2d would make
  * of this descriptor - out = {family (FUSG_CONV_*), tile, ksplit, ksw}.  tile: the FUSG_TILE_* of the generic gathers, the
  * column-tile width (128 / 64 / 32) of the halo and tap-unit kernels, 0 for the others; ksplit: K ranges over workgroups
- * (generic gathers and the small-image kernel; 1 elsewhere); ksw: 1 when the halo kernel splits K over its waves.
+ * (generic gathers and the small-image kernel; 1 elsewhere); ksw: 1 when the halo kernel splits K over its waves, 2 when
+ * its 128-column tile walks a chunk's 3x3 taps column-major (the FUSG_NO_HALO_COLMAJOR environment switch, read per call,
+ * keeps them tap-major: 0).
  * Returns FUSG_OK or the negative FUSG_ERR_* fusg_conv2d would return. */
 int  fusg_conv2d_route_order(const fusg_conv_desc* d, int32_t out[4]);
 
