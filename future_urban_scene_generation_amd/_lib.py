@@ -92,7 +92,8 @@ PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = 0, 1, 2
 PRE_NONE, PRE_RELU, PRE_ELU, PRE_AFFINE_RELU, PRE_AFFINE = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_TANH01, ACT_LEAKY02 = 0, 1, 2, 3, 4, 5
 STORE_NORMAL, STORE_D2S, STORE_S2D = 0, 1, 2
-PREC_F32, PREC_F16X3, PREC_EMU_BF16, PREC_EMU_BF16X2, PREC_BF16 = 0, 1, 2, 3, 4
+PREC_F32, PREC_F16X3, PREC_EMU_BF16, PREC_EMU_BF16X2, PREC_BF16, PREC_F16 = 0, 1, 2, 3, 4, 5
+CONV_HALO_F16, CONV_TAPUNIT_F16 = 15, 16   # FUSG_CONV_*: the two families of the single-pass fp16 mode (ops.last_conv_kernel)
 MAX_FRAMES = 64                         # FUSG_MAX_FRAMES: frames per launch of the frame-indexed glue
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_128x32, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4, 5
 

@@ -12,7 +12,7 @@ Execution: 16 fused 3x3 conv + ReLU launches (tap-unit kernel for the 3-channel 
 max-pool launches, and the classifier as three more convolution launches: ``AdaptiveAvgPool2d((7, 7))`` followed by
 ``Linear(25088, 4096)`` is one linear map of the s x s x 512 feature map (s = H / 32), folded at pack time into an
 s x s "valid" convolution; the other two Linear layers are 1 x 1 convolutions on a 1 x 1 image.  The logits decide an
-integer (the CAD index), so like the hourglass this network keeps the fp32-class path under ``precision="bf16"``.
+integer (the CAD index), so like the hourglass this network keeps the fp32-class path under ``precision="bf16"`` and ``precision="f16"``.
 """
 from __future__ import annotations
 
@@ -92,7 +92,7 @@ class VGG19Classifier(FusedNet):
 
     @entry_point
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if ops.PRECISION == "bf16":                            # an argmax decides the CAD model: fp32-class path only
+        if ops.PRECISION in ("bf16", "f16"):                   # an argmax decides the CAD model: fp32-class path only
             with ops.precision("f16x3"):
                 return self._forward(x)
         return self._forward(x)

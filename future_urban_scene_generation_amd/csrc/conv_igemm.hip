@@ -225,7 +225,7 @@ static int64_t plan_impl(fusg_conv_desc* d, SmallCfg* small) {
     const long Mr = route_n((long)d->src0.n) * d->qh * d->qw;      // what the choices below see
     const int nphase = d->nphase > 0 ? d->nphase : 1;
     SmallCfg sc;
-    if (small_cfg(d, d->precision == FUSG_PREC_BF16 ? FUSG_PREC_F16X3 : d->precision, &sc)) {
+    if (small_cfg(d, d->precision == FUSG_PREC_BF16 || d->precision == FUSG_PREC_F16 ? FUSG_PREC_F16X3 : d->precision, &sc)) {
         d->tile = FUSG_TILE_128x32;
         d->ksplit = sc.ksplit;
         if (small) *small = sc;
@@ -300,7 +300,7 @@ struct ConvRoute {
     int family;                 // FUSG_CONV_*
     int vec_epi;                // 16-byte epilogue accesses (ConvK::vec_epi)
     SmallCfg sc;                // FUSG_CONV_SMALL: its configuration (plan_impl)
-    int mode;                   // halo / tap-unit arithmetic: 0 split-fp16, 1 bf16, 2 exact fp32
+    int mode;                   // halo / tap-unit arithmetic: 0 split-fp16, 1 bf16, 2 exact fp32, 3 single-pass fp16
     int bn;                     // halo / tap-unit: column-tile width
     bool ksw;                   // halo: K split over the waves (the 64k / 32k instantiations)
     bool s2d;                   // halo: parity-quadrant form
@@ -311,12 +311,15 @@ struct ConvRoute {
 };
 
 // Validation and the family choice of fusg_conv2d - no HIP call, no allocation.  `d` is the caller's descriptor, copied: it
-// leaves planned (tile, ksplit) and with the arithmetic that runs (FUSG_PREC_BF16 -> F16X3).  Returns FUSG_OK or the error
+// leaves planned (tile, ksplit) and with the arithmetic that runs (FUSG_PREC_BF16, FUSG_PREC_F16 -> F16X3).  Returns FUSG_OK or the error
 // fusg_conv2d reports (the workspace and split-K counters, the caller's allocations, are checked by the launch).
 static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
     // FUSG_PREC_BF16: single-pass bf16 on the halo / tap-unit kernels where the layer qualifies, F16X3 everywhere else
     const bool want_bf16 = d->precision == FUSG_PREC_BF16;
     if (want_bf16) d->precision = FUSG_PREC_F16X3;
+    // FUSG_PREC_F16: the same rule with one fp16 product on the `hi` fragments of `wfrag` (mode 3) where bf16 takes mode 1
+    const bool want_f16 = d->precision == FUSG_PREC_F16;
+    if (want_f16) d->precision = FUSG_PREC_F16X3;
     const fusg_tensor& x0 = d->src0;
     FUSG_CHECK(is_nhwc(x0), "conv2d: src0 must be NHWC-physical f32 (sc=1, Cs%%4=0, 16B aligned)");
     const bool has1 = d->src1.data != nullptr;
@@ -464,10 +467,12 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
         if (nunits <= (f32 ? 320 : 160) && lds <= 80 * 1024 && r->HH * r->HW * (d->c0k / 4) <= 256 * 8) {
             // FUSG_PREC_BF16: the stem in single-pass bf16 too (wfrag_bf16 in the tap-unit form, pack.py: frag_tapunit_bf16)
             r->mode = f32 ? 2 : (want_bf16 && aligned16(d->wfrag_bf16) && getenv("FUSG_NO_BF16_TAPUNIT") == nullptr ? 1 : 0);
+            // FUSG_PREC_F16: the stem in single-pass fp16 (FUSG_NO_F16_TAPUNIT, read per call, keeps the split-fp16 kernel)
+            if (!f32 && want_f16 && getenv("FUSG_NO_F16_TAPUNIT") == nullptr) r->mode = 3;
             // thin split-fp16 / bf16 layers (a handful of k-steps: the launch is a stream of output stores) run 24-45 % faster on
             // the 64-column tile: its 16 KiB epilogue detour leaves room for more resident workgroups than the 128-column one
             r->bn = column_tile(d->cout_pad, !f32 && nsteps <= 4 ? 64 : 128);
-            r->family = f32 ? FUSG_CONV_TAPUNIT_F32 : r->mode ? FUSG_CONV_TAPUNIT_BF16 : FUSG_CONV_TAPUNIT;
+            r->family = f32 ? FUSG_CONV_TAPUNIT_F32 : r->mode == 3 ? FUSG_CONV_TAPUNIT_F16 : r->mode ? FUSG_CONV_TAPUNIT_BF16 : FUSG_CONV_TAPUNIT;
             return FUSG_OK;
         }
     }
@@ -511,14 +516,17 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
             r->ksw = !s2d && !d->tile_list && !env_switches().no_ksplit && mt * (d->cout_pad / r->bn) <= 1024 &&
                      ((r->bn == 32 && ntaps >= 4) || (r->bn == 64 && ntaps >= 2));
             const bool bf = want_bf16 && aligned16(d->wfrag_bf16);
-            r->mode = f32_frag ? 2 : (bf ? 1 : 0);
-            // tap-sparse weights: the sibling instantiations skip the dead taps (bf16 has none: it runs the dense weights)
-            r->sp = r->mode != 1 ? d->tap_sparse : 0;
+            const bool f16 = want_f16 && !f32_frag;                  // (aligned16(d->wfrag) holds on this route)
+            r->mode = f32_frag ? 2 : (bf ? 1 : f16 ? 3 : 0);
+            // tap-sparse weights: the sibling instantiations skip the dead taps (bf16 and single-pass fp16 have none: they run the
+            // dense kernel on the same weights, whose dead blocks are zeros)
+            r->sp = r->mode != 1 && r->mode != 3 ? d->tap_sparse : 0;
             // dense 3x3 dil 1 split-fp16 launches of the 128-column tile: the taps of a chunk column-major (each staged row read
             // once per tap column).  (FUSG_NO_HALO_COLMAJOR, read per call, keeps the tap-major order: tests and the A/B compare the two)
             r->cm = r->bn == 128 && !r->ksw && r->mode == 0 && r->sp == 0 && !s2d && d->kh == 3 && d->kw == 3 && d->dil == 1 &&
                     getenv("FUSG_NO_HALO_COLMAJOR") == nullptr;
-            r->family = f32_frag ? FUSG_CONV_HALO_F32 : bf ? FUSG_CONV_HALO_BF16 : (s2d ? FUSG_CONV_HALO_S2D : FUSG_CONV_HALO);
+            r->family = f32_frag ? FUSG_CONV_HALO_F32 : bf ? FUSG_CONV_HALO_BF16 : f16 ? FUSG_CONV_HALO_F16
+                                                                               : (s2d ? FUSG_CONV_HALO_S2D : FUSG_CONV_HALO);
             return FUSG_OK;
         }
     }
@@ -575,7 +583,7 @@ template <class H> static dim3 tapunit_block(H& h, const ConvK& k, const fusg_co
     h.tiles_x = d.qw / 16; h.tiles_per_img = (d.qh / 8) * h.tiles_x;
     h.c.MT = (int)d.src0.n * h.tiles_per_img; h.c.NT = d.cout_pad / r.bn;
     h.c.ksplit = 1;
-    if (r.mode != 0) { h.c.wscale = nullptr; h.c.status = nullptr; }
+    if (r.mode != 0 && r.mode != 3) { h.c.wscale = nullptr; h.c.status = nullptr; }       // (single-pass fp16 keeps the scales and the guard)
     return dim3(h.c.MT * h.c.NT, 1, 1);
 }
 
@@ -602,7 +610,7 @@ static hipError_t run_halo(const ConvK& k, const fusg_conv_desc& d, const ConvRo
     h.kh = d.kh; h.kw = d.kw; h.dil = d.dil; h.pad_h = d.pad_h; h.pad_w = d.pad_w;
     h.c1k = d.k_pad / (d.kh * d.kw) - d.c0k;
     h.wfrag = (const _Float16*)(r.mode == 1 ? d.wfrag_bf16 : r.mode == 2 ? d.wfrag_f32 : d.wfrag);
-    if (r.mode != 0) { h.c.wscale = nullptr; h.c.status = nullptr; }
+    if (r.mode != 0 && r.mode != 3) { h.c.wscale = nullptr; h.c.status = nullptr; }       // (single-pass fp16 keeps the scales and the guard)
     h.nt32 = d.cout_pad / 32;
     h.c.NT = d.cout_pad / r.bn;
     h.c.ksplit = 1;
@@ -661,8 +669,9 @@ extern "C" int fusg_conv2d_route_order(const fusg_conv_desc* din, int32_t out[4]
     if (const int rc = route_conv(&d, &r); rc != FUSG_OK) return rc;
     const bool generic = r.family == FUSG_CONV_GENERIC_F32 || r.family == FUSG_CONV_GENERIC_F16X3;
     const bool halo = r.family == FUSG_CONV_HALO || r.family == FUSG_CONV_HALO_S2D || r.family == FUSG_CONV_HALO_BF16 ||
-                      r.family == FUSG_CONV_HALO_F32;
-    const bool tapunit = r.family == FUSG_CONV_TAPUNIT || r.family == FUSG_CONV_TAPUNIT_F32 || r.family == FUSG_CONV_TAPUNIT_BF16;
+                      r.family == FUSG_CONV_HALO_F32 || r.family == FUSG_CONV_HALO_F16;
+    const bool tapunit = r.family == FUSG_CONV_TAPUNIT || r.family == FUSG_CONV_TAPUNIT_F32 || r.family == FUSG_CONV_TAPUNIT_BF16 ||
+                         r.family == FUSG_CONV_TAPUNIT_F16;
     out[0] = r.family;
     out[1] = generic ? d.tile : (halo || tapunit ? r.bn : 0);
     out[2] = r.family == FUSG_CONV_SMALL ? r.sc.ksplit : (generic ? d.ksplit : 1);
@@ -736,7 +745,7 @@ static int conv2d_run(const fusg_conv_desc* din, const EntryK* en, void* stream)
     switch (r.family) {
         case FUSG_CONV_SMALL:     what = "conv2d small-image launch"; e = run_small(k, *d, r.sc, s, pk); break;
         case FUSG_CONV_POINTWISE: what = "conv2d pointwise launch"; e = run_pointwise(k, *d, s); break;
-        case FUSG_CONV_TAPUNIT_F32: case FUSG_CONV_TAPUNIT: case FUSG_CONV_TAPUNIT_BF16:
+        case FUSG_CONV_TAPUNIT_F32: case FUSG_CONV_TAPUNIT: case FUSG_CONV_TAPUNIT_BF16: case FUSG_CONV_TAPUNIT_F16:
             what = r.mode == 2 ? "conv2d fp32 tap-unit launch" : "conv2d tap-unit launch";
             e = run_tapunit(k, *d, r, s, pk);
             break;

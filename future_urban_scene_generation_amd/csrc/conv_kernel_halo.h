@@ -55,6 +55,11 @@ namespace fusg {
 // wave load per fragment, the same 4 KiB per 32-column tile and step as the split-fp16 mode.  The matrix pipe is 16x slower
 // per FLOP than in fp16, so neither LDS nor the weight stream matters here (16 KiB of reads per 4096 MFMA cycles and wave).
 // K runs chunk-major here and tap-major in the generic fp32 kernel: the two agree to fp32 rounding, not bit for bit.
+// MODE 3 (FUSG_PREC_F16): MODE 1's loop in fp16 - ONE fp16 product per (a, w) pair, the first of the split-fp16 mode's three: operands
+// rounded to fp16 (ties to even) while the halo is staged, one LDS image, v_mfma_f32_16x16x32_f16 with fp32 accumulation.  The weights
+// are the `hi` fragments of the split-fp16 copy (hi = RTN_fp16(w s_n), the `lo` fragments are skipped), so the epilogue multiplies by
+// 1 / s_n and the launch keeps the split's range guard: every staged |a| feeds amax, report_range raises the status at 2^15.  11
+// significant bits per operand instead of bf16's 8, at the same matrix rate and the same operand bytes.
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 
@@ -79,6 +84,7 @@ struct HaloK {
     int c1k;                    // K-channels of src1 (0 if absent)
     const _Float16* wfrag;      // f16x3: [tap][chunk][cout_pad/32][16-column half][hi|lo][64 lanes][8] halves
                                 // bf16:  [tap][chunk][cout_pad/32][16-column half][64 lanes][8] bf16
+                                // f16 (MODE 3): the f16x3 copy, of which only the `hi` fragments are read
     const int* tile_list;       // optional: patch indices (within an image) to compute; MT = B * tile_count
     int tile_count;
     // Stride-2 k3/k4 pad-1 layers as four stride-1 convolutions of the parity sub-images x[2Y+i, 2X+j] (q = 2i+j):
@@ -156,7 +162,7 @@ constexpr int halo_waves(int, int) { return FUSG_HALO_WAVES; }
 // fragments, and ~60 bookkeeping instructions per step - so those launches ran at an MFMA-pipe busy of 0.22-0.30
 // (profiles/r03_pmc_narrow_layers.txt); here a step is 48 MFMAs like on the 128-column tile, every wave fetches different
 // weight fragments, and the per-step overhead is paid a quarter as often.  It pays on small grids only (conv_igemm.hip).
-// bf16 mode: THREE (FUSG_BF16_OCC=4: four) waves per SIMD.  A bf16 step is 16 MFMAs = 256 cycles of matrix pipe per wave and ~1000 cycles of
+// bf16 mode (and the single-pass fp16 mode, MODE 3, which has its loop): THREE (FUSG_BF16_OCC=4: four) waves per SIMD.  A bf16 step is 16 MFMAs = 256 cycles of matrix pipe per wave and ~1000 cycles of
 // wave time (tools/halo_stamps.py: the gaps are the step's own instruction stream and, once per chunk, the wait behind the next chunk's halo
 // gather - loads return in order); two waves per SIMD leave the pipe half idle inside the taps, a third fills it.  Needs <= 168 VGPRs (the
 // instantiations that would spill keep two waves) and the epilogue's LDS detour in two halves (32 KiB per workgroup instead of 64).
@@ -164,11 +170,15 @@ constexpr int halo_waves(int, int) { return FUSG_HALO_WAVES; }
 #define FUSG_BF16_OCC 3
 #endif
 constexpr bool halo_bf16_dense(int tm, int wm, int pk, int ni, int mode, int ks) {
-    return FUSG_BF16_OCC > 2 && mode == 1 && ks == 1 && 32 * tm * wm == 128 &&
-           !(tm == 4 && ((pk == PK_AFFINE && ni >= 8) || (pk == PK_NONE && ni >= 10)));      // (these spill at 168 registers)
+    return FUSG_BF16_OCC > 2 && (mode == 1 || mode == 3) && ks == 1 && 32 * tm * wm == 128 &&
+           !(tm == 4 && ((pk == PK_AFFINE && ni >= 8) || (pk == PK_NONE && ni >= 10))) &&    // (these spill at 168 registers)
+           // (MODE 3 carries the range guard's running maximum, one register more than MODE 1: these two then spill as well)
+           !(mode == 3 && ni >= 10 && ((tm == 4 && pk == PK_ELU) || (tm == 2 && pk == PK_AFFINE)));
 }
+// (K split, MODE 3, affine, 8 items: two registers over 168 when left at two waves - asked to stay where its MODE 1 sibling is)
 constexpr int halo_waves_mode(int tm, int tn, int wm, int pk, int ni, int mode, int ks) {
-    return halo_bf16_dense(tm, wm, pk, ni, mode, ks) ? FUSG_BF16_OCC : halo_waves(tm, tn);
+    return halo_bf16_dense(tm, wm, pk, ni, mode, ks) ? FUSG_BF16_OCC
+         : (mode == 3 && ks == 4 && pk == PK_AFFINE && ni == 8 && FUSG_HALO_WAVES < 3) ? 3 : halo_waves(tm, tn);
 }
 // Tap-sparse launches (fusg_conv_desc.tap_sparse, SP below): the dense-equivalent 3x3 / 4 C_out DepthToSpace form of a 2x
 // upsampling layer.  Output channel block [ph * C_out, +C_out) is phase ph = 2 py + px of the 2x2 output cell, and a phase
@@ -226,7 +236,7 @@ inline bool halo_fits(int HH, int HW) { return HH * HW * 8 <= 2560 && halo_lds_b
 
 // pick(ni): the instantiation for `ni` staged items per thread, or nullptr when there is none
 template <int TM, int TN, int WM, int WN, int KS, class Pick>
-hipError_t launch_halo_fn(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode, Pick pick,       // mode: 0 split-fp16, 1 bf16, 2 exact fp32
+hipError_t launch_halo_fn(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mode, Pick pick,       // mode: 0 split-fp16, 1 bf16, 2 exact fp32, 3 single-pass fp16
                           HaloK* prepared = nullptr, size_t* prepared_lds = nullptr) {                  // given: fill these instead of launching
     const int HP = k.HH * k.HW;
     size_t lds = halo_lds_bytes(k.HH, k.HW);
@@ -280,7 +290,8 @@ hipError_t launch_halo(const HaloK& k, dim3 grid, hipStream_t s, int pk, int mod
                      : ni <= 8 ? (const void*)conv_halo_h3<TM, TN, WM, WN, PK, 8, MD, KS>
                                : (const void*)conv_halo_h3<TM, TN, WM, WN, PK, 10, MD, KS>;
             };
-            return mode == 2 ? by_ni(std::integral_constant<int, 2>{}) : mode == 1 ? by_ni(std::integral_constant<int, 1>{})
+            return mode == 3 ? by_ni(std::integral_constant<int, 3>{})
+                 : mode == 2 ? by_ni(std::integral_constant<int, 2>{}) : mode == 1 ? by_ni(std::integral_constant<int, 1>{})
                                                                                    : by_ni(std::integral_constant<int, 0>{});
         });
     });

@@ -4,7 +4,8 @@
 // conv_halo_en (EN = 1, "entry NiN"): source 0 is not loaded but computed, x0 = b_in + sum_k w_in[k] elu(u[k]) from the <= 8
 // channels of `en.u` - conv_pointwise_small's fp32 chain - and the epilogue's residual is that chain again on the patch's own
 // pixels.  In scope then: EN and the parameter block `en` (EntryK); the other kernels see EN = 0 and an `en` nothing reads.
-    constexpr bool BF = MODE == 1, F32 = MODE == 2;
+    constexpr bool BF = MODE == 1, F32 = MODE == 2, F16 = MODE == 3;
+    constexpr bool ONE = BF || F16;                // one product per operand pair: one LDS image, one weight fragment per 16 columns
     constexpr int CH = HALO_CH, HPITCH = HALO_PP;
     constexpr int CPP = CH / 4;                    // 16-byte fp32 items per halo pixel
     constexpr int LOGC = 3;
@@ -122,7 +123,7 @@
     };
 
     // this wave's weight fragments: tiles (nt*BN/32 + wn*TN + j), j < TN
-    constexpr int FPT = BF ? 2 : 4;                            // fragments (1 KiB) per 32-column tile: [ct] or [ct][hi|lo]
+    constexpr int FPT = BF ? 2 : 4;                            // fragments (1 KiB) per 32-column tile: [ct] or [ct][hi|lo] (MODE 3 reads the hi ones)
     const _Float16* wfr = hk.wfrag + ((long)(nt * (BN / 32) + wn * TN) * FPT * 64 + lane) * 8;
     const long wstep = (long)hk.nt32 * FPT * 64 * 8;          // 16-bit elements per (tap, chunk) slab
     const float vfloor = relu_floor<PK>(p);
@@ -222,6 +223,16 @@
                 }
                 const bf4 hb = __builtin_convertvector(v, bf4);
                 if ((hexist >> j) & 1u) *(bf4*)(Ah + hoff[j]) = hb;
+            } else if constexpr (F16) {
+                // MODE 1's NaN rule (fmaxf under a fused ReLU, propagation elsewhere); the split's amax, taken after the floor
+                if (vfloor == 0.f) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v[c] = __builtin_fmaxf(v[c], 0.f);
+                }
+                asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v[0]), "v"(v[1]));
+                asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v[2]), "v"(v[3]));
+                const h4 hh = __builtin_convertvector(v, h4);      // v_cvt_f16_f32: round to nearest, ties to even
+                if ((hexist >> j) & 1u) *(h4*)(Ah + hoff[j]) = hh;
             } else {
                 h4 hi, lo;
                 if constexpr (PK == PK_ELU) split4<false>(v, vfloor, hi, lo, amax); else split4(v, vfloor, hi, lo, amax);
@@ -232,7 +243,7 @@
             }
         }
     };
-    struct BFrag { h8 f[TN][2][BF ? 1 : 2]; };        // [32-column tile][16-column half][hi, lo] (bf16: one fragment)
+    struct BFrag { h8 f[TN][2][ONE ? 1 : 2]; };       // [32-column tile][16-column half][hi, lo] (bf16, single-pass fp16: one fragment)
     BFrag bfA, bfB;
     auto b_load = [&](BFrag& F, const _Float16* base) __attribute__((always_inline)) {            // base: this wave column's part of one (tap, chunk) slab
 #pragma unroll
@@ -240,7 +251,7 @@
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-                for (int hl = 0; hl < (BF ? 1 : 2); ++hl)
+                for (int hl = 0; hl < (ONE ? 1 : 2); ++hl)
                     F.f[j][ct][hl] = *(const h8*)(base + ((j * 2 + ct) * (BF ? 1 : 2) + hl) * 512);
     };
 
@@ -292,6 +303,17 @@
                     for (int ct = 0; ct < 2; ++ct)
                         acc[i][2 * j + ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[i], __builtin_bit_cast(bf8, F.f[j][ct][0]),
                                                                                        acc[i][2 * j + ct], 0, 0, 0);
+        } else if constexpr (F16) {
+            h8 ah[2 * TM];
+#pragma unroll
+            for (int i = 0; i < 2 * TM; ++i) ah[i] = *(const h8*)(Ah + abase[i] + toff);
+#pragma unroll
+            for (int i = 0; i < 2 * TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct)
+                        acc[i][2 * j + ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], F.f[j][ct][0], acc[i][2 * j + ct], 0, 0, 0);
         } else {
             h8 ah[2 * TM], al[2 * TM], bs[TN][2];
 #pragma unroll

@@ -13,6 +13,9 @@
 // MODE 1 (round 4, FUSG_PREC_BF16: the stems of BASELINE configs[4]'s "bf16 MFMA conv path"): the same kernel with ONE bf16 product per
 // operand pair - activations rounded to bf16 while they are staged (one LDS image), weights pre-rounded (pack.py: frag_tapunit_bf16,
 // [step][cout_pad/32][64 lanes][8]), v_mfma_f32_32x32x16_bf16, no weight scales, no range status.
+// MODE 3 (FUSG_PREC_F16): MODE 1's loop in fp16 - activations rounded to fp16 (ties to even) while they are staged (one LDS image), ONE
+// product per operand pair on v_mfma_f32_32x32x16_f16 against the `hi` fragments of the split-fp16 weights (the `lo` fragments are skipped),
+// so the launch keeps the weight scales and the split's range status.
 #pragma once
 #include "conv_kernel_halo.h"
 
@@ -33,7 +36,8 @@ struct TapUnitK {
 
 template <int TM, int TN, int WM, int WN, int PK, int U, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
-    constexpr bool BF = MODE == 1;
+    constexpr bool BF = MODE == 1, F16 = MODE == 3;
+    constexpr bool ONE = BF || F16;                                // one product per operand pair: one LDS image, one weight fragment
     const ConvK& p = hk.c;
     constexpr int BM = 32 * TM * WM;
     constexpr int BN = 32 * TN * WN;
@@ -108,6 +112,14 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
                     for (int c = 0; c < 4; ++c) v[c] = __builtin_fmaxf(v[c], 0.f);
                 }
                 *(bf4*)(Ah + hoff[j]) = __builtin_convertvector(v, bf4);
+            } else if constexpr (F16) {
+                if (vfloor == 0.f) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v[c] = __builtin_fmaxf(v[c], 0.f);
+                }
+                asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v[0]), "v"(v[1]));
+                asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v[2]), "v"(v[3]));
+                *(h4*)(Ah + hoff[j]) = __builtin_convertvector(v, h4);     // round to nearest, ties to even
             } else {
                 h4 hi, lo;
                 if constexpr (PK == PK_ELU) split4<false>(v, vfloor, hi, lo, amax); else split4(v, vfloor, hi, lo, amax);
@@ -120,6 +132,7 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
 
     // this wave's weight fragments: column tiles (nt*BN/32 + wn*TN + j), j < TN
     constexpr int FPT = BF ? 1 : 2;                                // fragments per 32-column tile and k-step: [hi | lo] or one bf16
+    constexpr int FLD = ONE ? 1 : 2;                               // of which a step loads: MODE 3 reads the hi fragment only
     const _Float16* wfr = hk.wfrag + ((long)(nt * (BN / 32) + wn * TN) * FPT * 64 + lane) * 8;
     const long wstep = (long)hk.nt32 * FPT * 64 * 8;               // 16-bit elements per k-step slab
 
@@ -139,13 +152,13 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
     }
     const int g = lane >> 5;
 
-    struct BFrag { h8 f[TN][FPT]; };
+    struct BFrag { h8 f[TN][FLD]; };
     auto b_load = [&](BFrag& F, int step) {
         const _Float16* base = wfr + (long)step * wstep;
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int hl = 0; hl < FPT; ++hl) F.f[j][hl] = *(const h8*)(base + (j * FPT + hl) * 512);
+            for (int hl = 0; hl < FLD; ++hl) F.f[j][hl] = *(const h8*)(base + (j * FPT + hl) * 512);
     };
     BFrag bfA, bfB;
     b_load(bfA, 0);
@@ -163,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 ah[i] = live ? *(const h8*)(Ah + abase[i] + off) : zero8;
-                if constexpr (!BF) al[i] = live ? *(const h8*)(Al + abase[i] + off) : zero8;
+                if constexpr (!ONE) al[i] = live ? *(const h8*)(Al + abase[i] + off) : zero8;
             }
         } else {
             const int j = step * 4, last = hk.nunits - 1;
@@ -176,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
             for (int i = 0; i < TM; ++i) {
                 const h4 a0 = l0 ? *(const h4*)(Ah + abase[i] + oa) : zero4, a1 = l1 ? *(const h4*)(Ah + abase[i] + ob) : zero4;
                 ah[i] = h8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-                if constexpr (!BF) {
+                if constexpr (!ONE) {
                     const h4 c0 = l0 ? *(const h4*)(Al + abase[i] + oa) : zero4, c1 = l1 ? *(const h4*)(Al + abase[i] + ob) : zero4;
                     al[i] = h8{c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
                 }
@@ -188,6 +201,12 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, ah[i]), __builtin_bit_cast(bf8, F.f[j][0]), acc[i][j], 0, 0, 0);
+        } else if constexpr (F16) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], F.f[j][0], acc[i][j], 0, 0, 0);
         } else {
             h8 bs[TN];                                             // wh * 2^-11: B operand of the al' term
 #pragma unroll
@@ -199,7 +218,7 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 2 ? al[i] : ah[i],
-                                                                           term == 0 ? F.f[j][0] : term == 1 ? F.f[j][FPT - 1] : bs[j],
+                                                                           term == 0 ? F.f[j][0] : term == 1 ? F.f[j][FLD - 1] : bs[j],
                                                                            acc[i][j], 0, 0, 0);
         }
     };
@@ -254,13 +273,14 @@ __global__ __launch_bounds__(256, 2) void conv_tapunit_h3(const TapUnitK hk) {
 inline size_t tapunit_lds_bytes(int HH, int RP) { return (size_t)2 * HH * RP * sizeof(_Float16); }
 
 template <int TM, int TN, int WM, int WN>
-hipError_t launch_tapunit(const TapUnitK& k, dim3 grid, hipStream_t s, int pk, int unit, int mode) {       // mode: 0 split-fp16, 1 bf16
+hipError_t launch_tapunit(const TapUnitK& k, dim3 grid, hipStream_t s, int pk, int unit, int mode) {       // mode: 0 split-fp16, 1 bf16, 3 single-pass fp16
     size_t lds = tapunit_lds_bytes(k.HH, k.RP);
     if (lds < (size_t)4 * TM * 32 * TN * 32 * sizeof(float)) lds = (size_t)4 * TM * 32 * TN * 32 * sizeof(float);   // epilogue detour
     if (lds > 80 * 1024) return hipErrorInvalidValue;
     const void* fn = pick_pk(pk, [unit, mode](auto pkc) {
         constexpr int PK = decltype(pkc)::value;
-        return mode == 1 ? (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 8, 1> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 4, 1>)
+        return mode == 3 ? (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 8, 3> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 4, 3>)
+             : mode == 1 ? (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 8, 1> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 4, 1>)
                          : (unit == 8 ? (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 8, 0> : (const void*)conv_tapunit_h3<TM, TN, WM, WN, PK, 4, 0>);
     });
     return launch_kernel(fn, grid, lds, 80 * 1024, k, s);

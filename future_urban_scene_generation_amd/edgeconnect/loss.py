@@ -12,7 +12,7 @@ with torchvision's own module stays unpinned like the CAD classifier's (DESIGN.m
 Execution: the CAD classifier's convolutions (3 x 3 + fused ReLU, the tap-unit stem, ``ops.maxpool2``), the Gram matrix by
 ``ops.gram`` (exact-fp32 matrix instruction, contraction over pixels) and every L1 sum by ``ops.abs_diff_rows`` (float64, per
 row).  ``feature_distances`` is the per-row form both losses are means of; it never synchronises with the host.  Under
-``precision="bf16"`` the convolutions run f16x3, as ``VGG19Classifier.forward`` does: a measure must not be noisier than what
+``precision="bf16"`` and ``precision="f16"`` the convolutions run f16x3, as ``VGG19Classifier.forward`` does: a measure must not be noisier than what
 it measures.  No autograd: inputs are detached.
 """
 from __future__ import annotations
@@ -102,8 +102,8 @@ class VGG19(FusedNet):
             raise ValueError(f"VGG19 expects a float tensor, got {x.dtype}")
 
     def _run(self, x: torch.Tensor, last: str, keep: Sequence[str]) -> "OrderedDict[str, torch.Tensor]":
-        """The taps in `keep` up to `last`, NHWC-physical, convolutions at the current precision (bf16 -> f16x3)."""
-        if ops.PRECISION == "bf16":
+        """The taps in `keep` up to `last`, NHWC-physical, convolutions at the current precision (bf16, f16 -> f16x3)."""
+        if ops.PRECISION in ("bf16", "f16"):
             with ops.precision("f16x3"):
                 return self._run(x, last, keep)
         P = self._ensure(x)

@@ -117,7 +117,7 @@ def entry_point(fn):
     the CURRENT HIP device and ops.stream_ptr() returns the current device's stream, so the call is executed with
     the module's device made current (a model on 'cuda:1' works without torch.cuda.set_device(1)).
 
-    Range guard: with the split-fp16 contraction (ops.PRECISION == "f16x3") a launch that meets an operand outside
+    Range guard: with the split-fp16 contraction (ops.range_guarded(): "f16x3", and "bf16" / "f16", whose launches keep it) a launch that meets an operand outside
     the split's range raises a device-side status word instead of saturating; this wrapper reads the word after the
     call (one 4-byte read = one stream synchronisation, which the reference's callers do anyway when they `.cpu()`
     the result) and, when it is set, repeats the call in exact fp32 with the CPU generators rewound and list

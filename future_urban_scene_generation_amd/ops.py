@@ -33,6 +33,9 @@ def _env_set(name: str) -> bool:
 _PREC = {"f32": L.PREC_F32, "f16x3": L.PREC_F16X3,
          # BASELINE configs[4]: single-pass bf16 MFMA on the halo-kernel layers, f16x3 elsewhere (include/fusg.h)
          "bf16": L.PREC_BF16,
+         # single-pass fp16 on the halo and tap-unit layers (f16x3's first product of three: 11 significant bits per operand, the
+         # split's weight scales and range guard), f16x3 elsewhere (include/fusg.h)
+         "f16": L.PREC_F16,
          # evidence paths (include/fusg.h): operands rounded to 8 / 16 significant bits on the exact-fp32 kernel
          "emu_bf16": L.PREC_EMU_BF16, "emu_bf16x2": L.PREC_EMU_BF16X2}
 _EMU_BITS = {"emu_bf16": 8, "emu_bf16x2": 16}
@@ -131,13 +134,14 @@ _GUARD = {"depth": 0, "deferred": 0}
 
 def range_guarded() -> bool:
     """Do launches of the current precision use the fp16 split (and hence its range status)?  f16x3 does everywhere;
-    bf16 does on the layers that do not run on the halo kernel (and the hourglass keeps f16x3 under it)."""
-    return PRECISION in ("f16x3", "bf16")
+    bf16 does on the layers that do not run on the halo kernel (and the hourglass keeps f16x3 under it); f16 does everywhere
+    too - its single-pass launches keep the split's status word."""
+    return PRECISION in ("f16x3", "bf16", "f16")
 
 
 def halo_precision() -> bool:
     """Does the current precision route qualifying layers to the halo kernel?  (f32: its exact-fp32 mode, round 4.)"""
-    return PRECISION in ("f16x3", "bf16") or (PRECISION == "f32" and not _env_set("FUSG_NO_F32_HALO"))
+    return PRECISION in ("f16x3", "bf16", "f16") or (PRECISION == "f32" and not _env_set("FUSG_NO_F32_HALO"))
 
 
 def new_status_word(device) -> torch.Tensor:
@@ -869,7 +873,8 @@ def last_conv_kernel() -> int:
     1 generic split-fp16, 2 halo, 3 halo in parity-quadrant (stride-2) form, 4 tap-unit kernel (few-channel stems),
     5 halo in bf16 mode, 6 fused hourglass Bottleneck, 7 pointwise-from-few-channels streaming kernel, 8 small-image kernel,
     9 halo in exact fp32, 10 tap-unit in exact fp32, 11 tap-unit in bf16 mode, 12 fused VUnet Residual pair (respair),
-    13 halo kernel with the entry NiN computed in its staging (entry_nin), 14 fused head of an hourglass stack (hg_head)."""
+    13 halo kernel with the entry NiN computed in its staging (entry_nin), 14 fused head of an hourglass stack (hg_head),
+    15 halo in single-pass fp16 mode, 16 tap-unit in single-pass fp16 mode."""
     return int(L.lib().fusg_last_conv_kernel())
 
 
@@ -911,7 +916,7 @@ def conv_up2(exact: ConvPlan, phases, x: torch.Tensor, *, pre_op: int = L.PRE_NO
     b, c, h, w = x.shape
     out = nhwc_empty(b, exact.cout, 2 * h, 2 * w, x.device)
     # split-K launches do not use the halo kernel: keep K whole where the phase launches qualify for it
-    halo = (((precision or PRECISION) in ("f16x3", "bf16") or ((precision or PRECISION) == "f32" and not _env_set("FUSG_NO_F32_HALO")))
+    halo = (((precision or PRECISION) in ("f16x3", "bf16", "f16") or ((precision or PRECISION) == "f32" and not _env_set("FUSG_NO_F32_HALO")))
             and c % 32 == 0 and h % 8 == 0 and w % 16 == 0 and _os.environ.get("FUSG_NO_HALO") is None)
     if isinstance(phases, ConvPlan):                               # all four phases in one launch, DepthToSpace store
         conv(phases, x, out=out, store=L.STORE_D2S, pre_op=pre_op, pre=pre, pre_bstride=pre_bstride,

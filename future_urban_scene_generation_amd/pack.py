@@ -139,6 +139,15 @@ def split_f16x3(wpack: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return torch.stack([hi, lo], dim=1), (1.0 / s).to(torch.float32)
 
 
+def f16_mode_weights(wpack: torch.Tensor) -> torch.Tensor:
+    """[nphase, cout_pad, k_pad] f32 -> the weights the single-pass fp16 mode (precision "f16": the halo kernel's MODE 3, the
+    tap-unit kernel's too) multiplies with, as float32 of the same shape: `split_f16x3`'s hi / s[n] = RTN_fp16(w s[n]) / s[n] per
+    output channel n.  The kernels read the `hi` fragments of the f16x3 copy and the epilogue multiplies by 1 / s[n]; s[n] is a
+    power of two, so the value is exact in float32 - w rounded to 11 significant bits at the scale of its channel's largest."""
+    wsplit, inv_s = split_f16x3(wpack)
+    return wsplit[:, 0].to(torch.float32) * inv_s[None, :, None]
+
+
 def frag_f16x3(wsplit: torch.Tensor, plan: "ConvPlan") -> Optional[torch.Tensor]:
     """MFMA-fragment order of the split weights for the halo kernel (csrc/conv_kernel_halo.h):
     [tap][chunk32][cout_pad/32][16-column half][hi|lo][lane 64][8 halves], lane = (k >> 3) * 16 + column, i.e. exactly

@@ -816,7 +816,8 @@ class VehiclePipeline:
         """`run(batch, vehicle_seeds)` once under `against` and once under `precision` (`ops.precision`, restored afterwards;
         this pipeline's routing batch in force around both), then `compare_outputs` of the two: what a faster arithmetic costs
         on the caller's own weights and crops, in the unit the quality bars are stated in.  The acceptance recipe for bf16:
-        `rep = pipe.compare_precisions(batch, seeds, "bf16"); assert rep["worst"]["icn_u8"]["ssim"] >= 0.999`.
+        `rep = pipe.compare_precisions(batch, seeds, "bf16"); assert rep["worst"]["icn_u8"]["ssim"] >= 0.999`; the same
+        recipe with "f16" measures the single-pass fp16 mode (11 significant bits per operand where bf16 keeps 8).
         vehicle_seeds is required: without it the two passes draw different VUnet noise and the comparison means nothing.
         features: as in `compare_outputs` (the feature-space distances of the two passes' crops, measured at the ambient
         precision, not at `precision`)."""

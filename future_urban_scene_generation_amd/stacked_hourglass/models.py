@@ -174,9 +174,10 @@ class HourglassNet(FusedNet):
 
     @entry_point
     def forward(self, x: torch.Tensor) -> Dict[str, List[torch.Tensor]]:
-        if ops.PRECISION == "bf16":
+        if ops.PRECISION in ("bf16", "f16"):
             # the heat-map argmax is an integer contract (utils/keypoint_utils.py:85-88): single-pass bf16 moves 1 of 12
             # keypoints on the fixtures (tests::test_reduced_precision_evidence), so this network keeps the fp32-class path
+            # (under the single-pass fp16 mode too: an argmax must not be noisier than the default)
             with ops.precision("f16x3"):
                 return self._forward(x)
         return self._forward(x)

@@ -95,9 +95,17 @@ typedef enum fusg_store_mode {
  *        FLOPs) contract in ONE bf16 product per operand pair on v_mfma_f32_16x16x32_bf16 (operands rounded to bf16 as
  *        they are staged, weights from `wfrag_bf16`, fp32 accumulation); every other launch runs as F16X3, whose
  *        fields must be given too.  Measured: SSIM >= 0.9997 on every image output of the path, keypoint argmax NOT
- *        bit-exact - the hourglass module keeps F16X3 under this setting. */
+ *        bit-exact - the hourglass module keeps F16X3 under this setting.
+ * F16:   single-pass fp16, between F16X3 and BF16: launches that qualify for the halo or the tap-unit kernel contract in ONE fp16
+ *        product per operand pair - the first of F16X3's three: a' = RTN_fp16(pre_op(a)) rounded as it is staged (ties to even),
+ *        w' = RTN_fp16(w * s[n]) = the `hi` half of the split weights, acc += a' * w' on v_mfma_f32_16x16x32_f16 in fp32,
+ *        out = act(fmaf(acc, wscale[n], bias[n])).  11 significant bits per operand where BF16 keeps 8, at BF16's matrix rate and
+ *        operand bytes, from the F16X3 fields alone: no weight copy of its own.  F16X3's range guard holds unchanged (every staged
+ *        operand after the pre-op and a fused ReLU's floor; |a| >= 2^15 or non-finite sets *status; nothing is clamped).  Every
+ *        other launch runs as F16X3, bit for bit.  Added without a version step: two enum values, no layout change, and
+ *        FUSG_VERSION 118 is what the suite pins. */
 typedef enum fusg_precision { FUSG_PREC_F32 = 0, FUSG_PREC_F16X3 = 1, FUSG_PREC_EMU_BF16 = 2, FUSG_PREC_EMU_BF16X2 = 3,
-                              FUSG_PREC_BF16 = 4 } fusg_precision;
+                              FUSG_PREC_BF16 = 4, FUSG_PREC_F16 = 5 } fusg_precision;
 
 typedef enum fusg_tile {       /* workgroup tile (output pixels x output channels); 0 = auto */
     FUSG_TILE_AUTO = 0, FUSG_TILE_128x128 = 1, FUSG_TILE_128x64 = 2, FUSG_TILE_128x32 = 3,
@@ -167,7 +175,9 @@ typedef struct fusg_conv_desc {
     /* Halo kernel only: the (hi, lo) fp16 weights again, in MFMA-fragment order
      * [tap][chunk32][cout_pad/32][16-column half][hi|lo][64 lanes][8 halves], lane = (k >> 3) * 16 + column
      * (pack.py: frag_f16x3) = the B operand of v_mfma_f32_16x16x32_f16, so that a fragment is one contiguous
-     * 1 KiB wave load.  NULL disables the halo kernel. */
+     * 1 KiB wave load.  NULL disables the halo kernel.
+     * FUSG_PREC_F16 (the halo kernel's MODE 3, the tap-unit kernel's too) reads only the `hi` fragments of this copy, in either
+     * order's layout, and skips the `lo` ones; a tap-sparse copy then runs dense (its dead blocks are zeros: the same bytes). */
     const void*    wfrag;
     /* Optional fused normalisation statistics of the conv OUTPUT (bias included): per image and per
      * 32-pixel slot (slot order is kernel-defined; finalisation is order-independent) the mean and the
@@ -973,7 +983,7 @@ int         fusg_version(void);
 const char* fusg_last_error(void);
 /* Kernel family of this thread's last fusg_conv2d launch (tests assert that the intended path ran):
  * 0 generic fp32, 1 generic split-fp16, 2 halo, 3 halo in parity-quadrant form (stride 2), 4 tap-unit kernel
- * (few-channel stems), 5 halo kernel in single-pass bf16; -1 none yet. */
+ * (few-channel stems), 5 halo kernel in single-pass bf16, 15 / 16 halo / tap-unit kernel in single-pass fp16; -1 none yet. */
 enum { FUSG_CONV_GENERIC_F32 = 0, FUSG_CONV_GENERIC_F16X3 = 1, FUSG_CONV_HALO = 2, FUSG_CONV_HALO_S2D = 3,
        FUSG_CONV_TAPUNIT = 4, FUSG_CONV_HALO_BF16 = 5, FUSG_CONV_BNECK = 6 /* fusg_hg_bottleneck */,
        FUSG_CONV_POINTWISE = 7 /* 1x1 from <= 8 channels: streaming fp32 FMA kernel, no matrix cores */,
@@ -983,7 +993,9 @@ enum { FUSG_CONV_GENERIC_F32 = 0, FUSG_CONV_GENERIC_F16X3 = 1, FUSG_CONV_HALO = 
        FUSG_CONV_TAPUNIT_BF16 = 11 /* few-channel stems in single-pass bf16 (FUSG_PREC_BF16; wfrag_order 2 + wfrag_bf16) */,
        FUSG_CONV_RESPAIR = 12 /* fusg_vunet_respair */,
        FUSG_CONV_HALO_ENTRY = 13 /* fusg_conv2d_entry_nin: halo kernel with the entry NiN computed in its staging */,
-       FUSG_CONV_HG_HEAD = 14 /* fusg_hg_head */ };
+       FUSG_CONV_HG_HEAD = 14 /* fusg_hg_head */,
+       FUSG_CONV_HALO_F16 = 15 /* halo kernel in single-pass fp16 (FUSG_PREC_F16: one product on the `hi` fragments of wfrag) */,
+       FUSG_CONV_TAPUNIT_F16 = 16 /* few-channel stems in single-pass fp16 (FUSG_PREC_F16; wfrag_order 2, `hi` fragments of wfrag) */ };
 int         fusg_last_conv_kernel(void);
 const char* fusg_arch(void);                      /* "gfx950" */
 /* sizeof(fusg_tensor) / sizeof(fusg_conv_desc) as compiled, so that FFI bindings can verify their
