@@ -194,6 +194,15 @@ _SIGS = {
     "fusg_gan_terms_rows_f32_host": (C.c_int, [_TP, _TP, C.c_float, C.c_void_p]),
     "fusg_background_median_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 3),
     "fusg_background_median_host": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 2),
+    "fusg_foreground_masks_u8": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32] * 8
+                                 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
+    "fusg_foreground_masks_scratch_bytes": (C.c_int64, [C.c_int32] * 3),
+    "fusg_foreground_masks_host": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32] * 8
+                                   + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "fusg_erase_boxes_u8": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 2 + [C.c_int32]
+                            + [C.c_void_p] * 2),
+    "fusg_erase_boxes_host": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 2 + [C.c_int32]
+                              + [C.c_void_p]),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

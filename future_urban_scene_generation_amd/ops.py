@@ -1767,6 +1767,214 @@ def background_median_host(frames, boxes=None, margin: int = 0, min_valid: int =
 
 
 # ---------------------------------------------------------------------------------------------
+# vehicle masks from the estimated background (csrc/foreground.h) and the erase that uses them
+# ---------------------------------------------------------------------------------------------
+FOREGROUND_LIMITS = {"thr": 254, "open_r": 3, "close_r": 7, "grow": 15}
+FOREGROUND_STATS = ("n_f0", "n_seed", "n_mask", "flags")
+FOREGROUND_FALLBACK, FOREGROUND_BORDER, FOREGROUND_REFUSED = 1, 2, 4
+
+
+def _box_table(boxes, n, H, W, what: str, name: str, inside: bool) -> _np.ndarray:
+    """An integer [n, 4] host table as int32; inside: every row a half-open rectangle of the W x H frame, as `_inpaint_args` asks."""
+    b = _np.asarray(boxes)
+    if b.size and (b.dtype.kind not in "iu" or b.size % 4 or (b.ndim > 1 and b.shape[-1] != 4)):
+        raise ValueError(f"{what}: {name} must be an integer [n, 4] array, got {b.dtype} {b.shape}")
+    b = b.reshape(-1, 4).astype(_np.int64)
+    if n is not None and b.shape[0] != n:
+        raise ValueError(f"{what}: {b.shape[0]} {name} for {n} boxes")
+    if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
+        raise ValueError(f"{what}: a row of {name} does not fit int32")
+    if inside:
+        bad = (b[:, 0] < 0) | (b[:, 1] < 0) | (b[:, 2] < b[:, 0]) | (b[:, 3] < b[:, 1]) | (b[:, 2] > W) | (b[:, 3] > H)
+        if bad.any():
+            v = int(_np.nonzero(bad)[0][0])
+            raise ValueError(f"{what}: box {v} = {b[v].tolist()} leaves the {W} x {H} frame (x0, y0, x1, y1, half-open)")
+    return _np.ascontiguousarray(b.astype(_np.int32))
+
+
+def _foreground_args(frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box, offs, u8, what):
+    """What both forms of `foreground_masks` check before anything is touched -> (frames, backgrounds, H, W, boxes int32 [n, 4],
+    cores int32 [n, 4], offsets int64 [n], the bytes the masks take, frame_rows int32 [F + 1], the five parameters, max_box)."""
+    if hasattr(frames, "shape") and len(frames.shape) == 3:
+        frames = [frames]
+    frames, F, H, W = _background_frames(frames, u8, what)
+    if hasattr(background, "shape") and len(background.shape) == 3:
+        background = [background] * F
+    if hasattr(background, "shape") and len(background.shape) != 4:
+        raise ValueError(f"{what}: background must be uint8 [H, W, 3], or one per frame")
+    bgs = [background[f] for f in range(len(background))]
+    if len(bgs) != F:
+        raise ValueError(f"{what}: {len(bgs)} backgrounds for {F} frames")
+    for f, g in enumerate(bgs):
+        if not hasattr(g, "shape") or g.dtype != u8 or tuple(g.shape) != (H, W, 3):
+            raise ValueError(f"{what}: background {f} must be uint8 {(H, W, 3)}, got {getattr(g, 'dtype', type(g))} {tuple(getattr(g, 'shape', ()))}")
+        if not (g.is_contiguous() if isinstance(g, torch.Tensor) else g.flags.c_contiguous):
+            raise ValueError(f"{what}: background {f} is not contiguous")
+    par = []
+    for name, v in (("thr", thr), ("open_r", open_r), ("close_r", close_r), ("grow", grow)):
+        if int(v) != v or not 0 <= int(v) <= FOREGROUND_LIMITS[name]:
+            raise ValueError(f"{what}: {name} = {v} (0..{FOREGROUND_LIMITS[name]})")
+        par.append(int(v))
+    par.append(1 if fallback else 0)
+    bx = _box_table(boxes, None, H, W, what, "boxes", True)
+    n = bx.shape[0]
+    cr = _box_table(cores, n, H, W, what, "cores", False)
+    if frame_rows is None:
+        if F != 1:
+            raise ValueError(f"{what}: {F} frames need frame_rows (int [{F + 1}], from 0 to the number of boxes)")
+        rows = _np.asarray([0, n], dtype=_np.int32)
+    else:
+        rows = _np.asarray(frame_rows, dtype=_np.int64).reshape(-1)
+        if rows.shape[0] != F + 1 or rows[0] != 0 or rows[-1] != n or (_np.diff(rows) < 0).any():
+            raise ValueError(f"{what}: frame_rows = {rows.tolist()} must be {F + 1} non-decreasing offsets from 0 to the {n} boxes")
+        rows = rows.astype(_np.int32)
+    hw = (bx[:, 3] - bx[:, 1]).astype(_np.int64) * (bx[:, 2] - bx[:, 0]).astype(_np.int64)
+    if offs is None:
+        offs = _np.zeros(n, dtype=_np.int64)
+        offs[1:] = _np.cumsum(hw)[:-1]
+    else:
+        offs = _np.ascontiguousarray(_np.asarray(offs, dtype=_np.int64).reshape(-1))
+        if offs.shape[0] != n:
+            raise ValueError(f"{what}: {offs.shape[0]} offsets for {n} boxes")
+    if max_box is None:
+        max_box = (int((bx[:, 3] - bx[:, 1]).max()), int((bx[:, 2] - bx[:, 0]).max())) if n else (0, 0)
+    mb = (int(max_box[0]), int(max_box[1]))
+    if not (0 <= mb[0] <= BACKGROUND_MAX_DIM and 0 <= mb[1] <= BACKGROUND_MAX_DIM):
+        raise ValueError(f"{what}: max_box = {mb} (0..{BACKGROUND_MAX_DIM})")
+    return frames, bgs, H, W, bx, cr, offs, int(hw.sum()), _np.ascontiguousarray(rows), par, mb
+
+
+def foreground_masks(frames, background, boxes, cores, thr: int = 24, open_r: int = 1, close_r: int = 3, grow: int = 0,
+                     fallback: bool = True, frame_rows=None, max_box=None, out=None):
+    """Every box's vehicle mask from the background, on the device (fusg_foreground_masks_u8, one launch on the current stream, one
+    workgroup per box, nothing read back; csrc/foreground.h states the definition): inside the box, max_c |frame - background| >
+    thr, opened by the (2 open_r + 1)^2 square, closed by the (2 close_r + 1)^2 square without eating back from the box edge, the
+    part 4-connected to the core kept, its enclosed holes filled, grown by `grow`; an empty seed gives the core rectangle
+    (fallback) or nothing.  The defaults 24 / 1 / 3 are untried on real video.
+    frames: one CUDA uint8 [H, W, 3] frame, or a sequence / stack of up to 64 with frame_rows (int [F + 1]: boxes [frame_rows[f],
+    frame_rows[f + 1]) read frame f); background: one [H, W, 3] for all frames or one per frame; boxes, cores: host int [n, 4]
+    (x0, y0, x1, y1) half-open, frame coordinates - the boxes checked as `inpaint_inputs` checks them, the cores free (clipped to
+    their box); both uploaded without a synchronisation.  max_box = (h, w): the bound the launch is sized for (default: the largest
+    box; a box that exceeds it is refused and flagged).  out = (buffer CUDA uint8 [m], host int64 offsets [n]) to write into
+    (default: a fresh buffer, the offsets the running sum of h w).
+    -> ((buffer uint8 [m], offsets int64 [n]) on the device - what `inpaint_inputs_boxed` takes as box_masks -, stats int32 [n, 4]
+    on the device: `FOREGROUND_STATS`, flags = 1 fallback taken | 2 touches the box border | 4 refused, bytes not written)."""
+    what = "foreground_masks"
+    frames, bgs, H, W, bx, cr, offs, nbytes, rows, par, mb = _foreground_args(
+        frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box,
+        None if out is None else out[1], torch.uint8, what)
+    dev = frames[0].device
+    for t in frames + bgs:
+        if t.device != dev:
+            raise ValueError(f"{what}: a frame or background is on {t.device}, frame 0 on {dev}")
+    if out is not None and (not torch.is_tensor(out[0]) or out[0].dtype != torch.uint8 or out[0].dim() != 1 or not out[0].is_contiguous()
+                            or out[0].device != dev):
+        raise ValueError(f"{what}: out's buffer must be a contiguous uint8 [m] tensor on {dev}")
+    _require_gpu(frames[0], "frames")
+    n, F = bx.shape[0], len(frames)
+    with torch.cuda.device(dev):
+        buf = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if out is None else out[0]
+        stats = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        if n == 0:
+            return (buf, torch.empty((0,), dtype=torch.int64, device=dev)), stats
+        tab = h2d(_np.concatenate([bx, cr]), dev)                 # one copy for both tables
+        off_d = h2d(offs, dev, torch.int64)
+        lib = L.lib()
+        sb = int(lib.fusg_foreground_masks_scratch_bytes(n, mb[0], mb[1]))
+        scratch = torch.empty((sb,), dtype=torch.uint8, device=dev) if sb > 0 else None
+        fp = (C.c_void_p * F)(*[f.data_ptr() for f in frames])
+        gp = (C.c_void_p * F)(*[g.data_ptr() for g in bgs])
+        L.check(lib.fusg_foreground_masks_u8(fp, gp, rows.ctypes.data, F, H, W, tab[:n].data_ptr(), tab[n:].data_ptr(), off_d.data_ptr(), n,
+                                             *par, mb[0], mb[1], buf.data_ptr() if buf.numel() else None, int(buf.numel()),
+                                             stats.data_ptr(), scratch.data_ptr() if scratch is not None else None, stream_ptr()), what)
+        if RECORDER is not None:
+            RECORDER.keep.extend(t for t in (tab, off_d, scratch) if t is not None)
+    return (buf, off_d), stats
+
+
+def foreground_masks_host(frames, background, boxes, cores, thr: int = 24, open_r: int = 1, close_r: int = 3, grow: int = 0,
+                          fallback: bool = True, frame_rows=None, max_box=None, out=None):
+    """`foreground_masks` on the CPU by the same code (fusg_foreground_masks_host; no GPU needed): numpy uint8 images in,
+    ((buffer uint8 [m], offsets int64 [n]), stats int32 [n, 4]) numpy arrays out."""
+    what = "foreground_masks_host"
+    as_np = lambda x: [_np.asarray(f) for f in x] if isinstance(x, (list, tuple)) else _np.asarray(x)  # noqa: E731
+    frames, bgs, H, W, bx, cr, offs, nbytes, rows, par, mb = _foreground_args(
+        as_np(frames), as_np(background), boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box,
+        None if out is None else out[1], _np.uint8, what)
+    if out is not None and (not isinstance(out[0], _np.ndarray) or out[0].dtype != _np.uint8 or out[0].ndim != 1
+                            or not out[0].flags.c_contiguous):
+        raise ValueError(f"{what}: out's buffer must be a contiguous uint8 [m] array")
+    n, F = bx.shape[0], len(frames)
+    buf = _np.zeros((nbytes,), dtype=_np.uint8) if out is None else out[0]
+    stats = _np.zeros((n, 4), dtype=_np.int32)
+    if n == 0:
+        return (buf, offs), stats
+    fp = (C.c_void_p * F)(*[f.ctypes.data for f in frames])
+    gp = (C.c_void_p * F)(*[g.ctypes.data for g in bgs])
+    L.check(L.lib().fusg_foreground_masks_host(fp, gp, rows.ctypes.data, F, H, W, bx.ctypes.data, cr.ctypes.data, offs.ctypes.data, n, *par,
+                                               mb[0], mb[1], buf.ctypes.data if buf.size else None, int(buf.size), stats.ctypes.data), what)
+    return (buf, offs), stats
+
+
+def _erase_args(frame, background, box_masks, boxes, u8, what):
+    """Shared by both forms of `erase_to_background`: -> (H, W, boxes int32 [n, 4], buffer, offsets)."""
+    for name, a in (("frame", frame), ("background", background)):
+        if not hasattr(a, "shape") or a.dtype != u8 or len(a.shape) != 3 or a.shape[2] != 3:
+            raise ValueError(f"{what}: {name} must be uint8 [H, W, 3], got {getattr(a, 'dtype', type(a))} {tuple(getattr(a, 'shape', ()))}")
+        if not (a.is_contiguous() if isinstance(a, torch.Tensor) else a.flags.c_contiguous):
+            raise ValueError(f"{what}: {name} is not contiguous")
+    if tuple(background.shape) != tuple(frame.shape):
+        raise ValueError(f"{what}: background is {tuple(background.shape)}, the frame {tuple(frame.shape)}")
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    if not (1 <= H <= BACKGROUND_MAX_DIM and 1 <= W <= BACKGROUND_MAX_DIM):
+        raise ValueError(f"{what}: frames of {H} x {W} (H and W in 1..{BACKGROUND_MAX_DIM})")
+    if not _is_packed_pair(box_masks) or box_masks[0].dtype != u8:
+        raise ValueError(f"{what}: box_masks must be a packed (uint8 buffer [m], int64 offsets [n]) pair, as `foreground_masks` returns it")
+    bx = _box_table(boxes, int(box_masks[1].shape[0]), H, W, what, "boxes", True)
+    return H, W, bx, box_masks[0], box_masks[1]
+
+
+def erase_to_background(frame: torch.Tensor, background: torch.Tensor, box_masks, boxes, out=None) -> torch.Tensor:
+    """The frame with the masked pixels of every box replaced by the background (fusg_erase_boxes_u8, two launches on the current
+    stream): a compositing base that keeps the rest of the traffic.  frame, background CUDA uint8 [H, W, 3]; box_masks = the
+    packed (buffer, offsets) pair of `foreground_masks` (offsets on the device or host); boxes host int [n, 4].  -> uint8 [H, W,
+    3] (out: a buffer to write into, not overlapping the inputs)."""
+    what = "erase_to_background"
+    H, W, bx, buf, offs = _erase_args(frame, background, box_masks, boxes, torch.uint8, what)
+    dev = frame.device
+    if not torch.is_tensor(buf) or buf.device != dev or background.device != dev or not buf.is_contiguous():
+        raise ValueError(f"{what}: the frame, the background and the mask buffer must be contiguous tensors on one device")
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"{what}: out must be a contiguous uint8 {(H, W, 3)} tensor on {dev}")
+    _require_gpu(frame, "frame")
+    n = bx.shape[0]
+    with torch.cuda.device(dev):
+        dst = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
+        off_d = offs.to(torch.int64).contiguous() if (torch.is_tensor(offs) and offs.is_cuda) else h2d(_np.asarray(offs, dtype=_np.int64), dev)
+        bx_d = h2d(bx, dev) if n else None
+        L.check(L.lib().fusg_erase_boxes_u8(frame.data_ptr(), background.data_ptr(), H, W, buf.data_ptr() if buf.numel() else None,
+                                            int(buf.numel()), off_d.data_ptr() if n else None, bx_d.data_ptr() if n else None, n,
+                                            dst.data_ptr(), stream_ptr()), what)
+        if RECORDER is not None:
+            RECORDER.keep.extend(t for t in (off_d, bx_d) if t is not None)
+    return dst
+
+
+def erase_to_background_host(frame, background, box_masks, boxes) -> _np.ndarray:
+    """`erase_to_background` on the CPU by the same code (fusg_erase_boxes_host): numpy in and out."""
+    what = "erase_to_background_host"
+    frame, background = _np.asarray(frame), _np.asarray(background)
+    if isinstance(box_masks, tuple) and len(box_masks) == 2:
+        box_masks = (_np.ascontiguousarray(box_masks[0]), _np.ascontiguousarray(box_masks[1], dtype=_np.int64))
+    H, W, bx, buf, offs = _erase_args(frame, background, box_masks, boxes, _np.uint8, what)
+    n = bx.shape[0]
+    dst = _np.zeros((H, W, 3), dtype=_np.uint8)
+    L.check(L.lib().fusg_erase_boxes_host(frame.ctypes.data, background.ctypes.data, H, W, buf.ctypes.data if buf.size else None, int(buf.size),
+                                          offs.ctypes.data if n else None, bx.ctypes.data if n else None, n, dst.ctypes.data), what)
+    return dst
+
+
+# ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------
 def prof_enable(on: bool) -> None:

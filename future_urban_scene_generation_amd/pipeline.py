@@ -1767,6 +1767,30 @@ class VehiclePipeline:
         bg, count = ops.background_median([scenes[i]["frame"] for i in idx], boxes, margin=margin, min_valid=mv)
         return {"background": bg, "count": count, "frames": idx, "min_valid": mv}
 
+    def foreground_inpaint(self, scene, background, core_frac: float = 0.5, **params) -> Dict:
+        """scene['inpaint'] without a detector: {'boxes', 'box_masks', 'stats'} for the caller to assign.  boxes = `inpaint_box_rule`
+        of every scene['bboxes'] row (the reference's bbox_new_img); box_masks = each vehicle's mask as what differs from
+        `background` (uint8 [H, W, 3] on the device, e.g. `estimate_background`'s) inside that box and hangs together with the
+        tracker box's core - the box shrunk about its centre to core_frac of its width and height (`ops.foreground_masks`, one
+        launch, nothing read back; params: thr, open_r, close_r, grow, fallback - defaults untried on real video) - in the packed
+        (buffer, offsets) form `ops.inpaint_inputs_boxed` takes; stats int32 [V, 4] stays on the device.  Nothing is put into the scene."""
+        import numpy as np
+
+        from . import ops
+        frame = scene["frame"]
+        tb = np.asarray(scene["bboxes"], dtype=np.int64).reshape(-1, 4)
+        boxes = inpaint_box_rule(tb, (int(frame.shape[0]), int(frame.shape[1])))
+        box_masks, stats = ops.foreground_masks(frame, background, boxes, foreground_cores(tb, core_frac), **params)
+        return {"boxes": boxes, "box_masks": box_masks, "stats": stats}
+
+    def erase_vehicles(self, scene, background, grow: int = 4, **params) -> torch.Tensor:
+        """A third compositing base, uint8 [H, W, 3]: the scene's frame with only its own vehicles (scene['bboxes']) replaced by
+        `background` inside their masks (`foreground_inpaint`'s, grown by `grow` pixels), the rest of the traffic kept.  Two more
+        launches, nothing read back; the caller passes it as that scene's scene['background'].  Nothing is put into the scene."""
+        from . import ops
+        inp = self.foreground_inpaint(scene, background, grow=grow, **params)
+        return ops.erase_to_background(scene["frame"], background, inp["box_masks"], inp["boxes"])
+
     @staticmethod
     def _composites(paste, out: Dict, box_geom=None) -> Dict:
         """'frame_icn' and 'frame_vunet': paste(crops, **box) once per composite (:184-198, :236-250; :393-410, :428-445), the
@@ -3273,6 +3297,38 @@ def synth_inpaint_boxes(bboxes, frame_hw, shift=None) -> list:
         bx0, by0 = max(0, int(cx - bw / 2)), max(0, int(cy - bh / 2))
         boxes.append([bx0, by0, max(bx0 + 2, min(W - 1, int(cx + bw / 2))), max(by0 + 2, min(H - 1, int(cy + bh / 2)))])
     return boxes
+
+
+def inpaint_box_rule(bboxes, frame_hw):
+    """bbox_new_img of every tracker box (x0, y0, x1, y1) by the reference's own rule (utils/inpaint_utils.py:22-23:
+    BoundingBox(..., scale=1.3, bounds=(0, W - 1, 0, H - 1)), utils/bounding_box.py): each side moves out by int(1.3 w - w) // 2
+    (resp. h), then the box is clipped to 0 .. W - 1 and 0 .. H - 1 -> int64 [V, 4], half-open.  `synth_inpaint_boxes` above is the
+    synthetic scenes' stand-in (a centre shift, a minimum extent of 2): it rounds differently by up to a pixel and is kept as it
+    is, since the recorded outputs of the synthetic passes depend on it."""
+    import numpy as np
+    H, W = frame_hw
+    b = np.asarray(bboxes, dtype=np.int64).reshape(-1, 4)
+    out = np.zeros_like(b)
+    for v, (x0, y0, x1, y1) in enumerate(b.tolist()):
+        w, h = x1 - x0, y1 - y0
+        dw, dh = int(w * 1.3 - w) // 2, int(h * 1.3 - h) // 2
+        out[v] = (max(0, x0 - dw), max(0, y0 - dh), min(W - 1, x1 + dw), min(H - 1, y1 + dh))
+    return out
+
+
+def foreground_cores(bboxes, core_frac: float = 0.5):
+    """Every tracker box (x0, y0, x1, y1) shrunk about its centre to core_frac of its width and height, in integers: the core is
+    floor(core_frac * w + 0.5) wide, and (w - that) // 2 comes off both sides (likewise h) -> int64 [V, 4]."""
+    import numpy as np
+    if not 0.0 < core_frac <= 1.0:
+        raise ValueError(f"foreground_cores: core_frac = {core_frac} (0 < core_frac <= 1)")
+    b = np.asarray(bboxes, dtype=np.int64).reshape(-1, 4)
+    out = np.zeros_like(b)
+    for v, (x0, y0, x1, y1) in enumerate(b.tolist()):
+        w, h = x1 - x0, y1 - y0
+        mx, my = (w - int(core_frac * w + 0.5)) // 2, (h - int(core_frac * h + 0.5)) // 2
+        out[v] = (x0 + mx, y0 + my, x1 - mx, y1 - my)
+    return out
 
 
 def synth_box_masks(masks: torch.Tensor, boxes, dtype=torch.uint8) -> list:

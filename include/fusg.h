@@ -938,6 +938,45 @@ int fusg_background_median_u8(const void* const* frame_ptrs, int32_t T, int32_t 
 int fusg_background_median_host(const void* const* frame_ptrs, int32_t T, int32_t H, int32_t W, const int32_t* boxes,
                                 const int32_t* box_offs, int32_t margin, int32_t min_valid, uint8_t* bg, uint8_t* count);
 
+/* ---- vehicle masks from the estimated background (what scene['inpaint']['box_masks'] takes without a detector, and a third
+ * compositing base: the frame with the selected vehicles replaced by background; new entry points, FUSG_VERSION stays 118) */
+/* Per box b = (x0, y0, x1, y1), half-open, of n: inside the box, threshold max_c |frame - background| > thr, open by the
+ * (2 open_r + 1)^2 square (outside = 0), close by the (2 close_r + 1)^2 square (dilation outside = 0, erosion outside = 1),
+ * keep what is 4-connected to the part inside the core rectangle cores[b] (frame coordinates, clipped to the box), fill the
+ * holes that do not open to the box border, dilate by the (2 grow + 1)^2 square cut at the box.  An empty seed gives an empty
+ * mask, or with fallback != 0 the clipped core rectangle.  csrc/foreground.h states the definition step by step.
+ * In frame-indexed form: frames / backgrounds = HOST tables of n_frames <= FUSG_MAX_FRAMES DEVICE pointers to dense u8 [H, W, 3]
+ * images (the same pointer may repeat), frame_rows = HOST int32 [n_frames + 1], non-decreasing from 0 to n: boxes
+ * [frame_rows[f], frame_rows[f + 1]) read frame f and background f.  boxes, cores: DEVICE int32 [n][4]; offsets: DEVICE int64 [n].
+ * mask: DEVICE u8 [mask_len]; box b's mask is row-major [h][w] from mask[offsets[b]], 255 or 0 - the packed form
+ * fusg_inpaint_inputs_boxed takes.  stats: DEVICE int32 [n][4] = n_F0, n_seed, n_mask, flags (1 fallback taken, 2 the mask
+ * touches the box border, 4 the box was refused).  max_box_h / max_box_w bound the box extents of the call: up to
+ * fusg_foreground_masks_scratch_bytes() == 0 the bit planes of a box live in LDS and scratch may be NULL, above it in scratch
+ * (DEVICE, 4-byte aligned, that many bytes; it holds nothing between calls).  The boxes live on the device, so a box that leaves
+ * the frame, exceeds the bound or whose h w bytes would leave the mask buffer is REFUSED there: flags = 4, the other stats 0, its
+ * mask bytes not written, nothing of it read.  Checked on the host before any launch (FUSG_ERR_INVALID): the tables, H and W in
+ * 1..32767, thr 0..254, open_r 0..3, close_r 0..7, grow 0..15, max_box 0..32767, mask_len >= 0.  n == 0: no launch, returns 0.
+ * One launch, one workgroup per box, no atomics; bit-identical to the host twin. */
+int fusg_foreground_masks_u8(const void* const* frames, const void* const* backgrounds, const int32_t* frame_rows, int32_t n_frames,
+                             int32_t H, int32_t W, const int32_t* boxes, const int32_t* cores, const int64_t* offsets, int32_t n,
+                             int32_t thr, int32_t open_r, int32_t close_r, int32_t grow, int32_t fallback, int32_t max_box_h,
+                             int32_t max_box_w, uint8_t* mask, int64_t mask_len, int32_t* stats, void* scratch, void* stream);
+/* Bytes of scratch for n_boxes boxes of at most max_box_h x max_box_w: 0 while the planes fit LDS; -1 for a bad argument. */
+int64_t fusg_foreground_masks_scratch_bytes(int32_t n_boxes, int32_t max_box_h, int32_t max_box_w);
+/* The same code on the CPU: every pointer is a HOST pointer, no GPU and no scratch needed.  A refused box is flagged as above. */
+int fusg_foreground_masks_host(const void* const* frames, const void* const* backgrounds, const int32_t* frame_rows, int32_t n_frames,
+                               int32_t H, int32_t W, const int32_t* boxes, const int32_t* cores, const int64_t* offsets, int32_t n,
+                               int32_t thr, int32_t open_r, int32_t close_r, int32_t grow, int32_t fallback, int32_t max_box_h,
+                               int32_t max_box_w, uint8_t* mask, int64_t mask_len, int32_t* stats);
+/* dst = frame, then dst = background at every pixel of a box whose mask byte (mask, offsets, boxes: the packed form above) is
+ * non-zero.  frame, background, dst: DEVICE dense u8 [H, W, 3]; dst is written whole and must not overlap the inputs.  Boxes
+ * may overlap (every write stores the same background byte); a box that leaves the frame or whose mask would leave the buffer is
+ * skipped.  Two launches, no atomics; n == 0 copies the frame. */
+int fusg_erase_boxes_u8(const uint8_t* frame, const uint8_t* background, int32_t H, int32_t W, const uint8_t* mask, int64_t mask_len,
+                        const int64_t* offsets, const int32_t* boxes, int32_t n, uint8_t* dst, void* stream);
+int fusg_erase_boxes_host(const uint8_t* frame, const uint8_t* background, int32_t H, int32_t W, const uint8_t* mask,
+                          int64_t mask_len, const int64_t* offsets, const int32_t* boxes, int32_t n, uint8_t* dst);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)
