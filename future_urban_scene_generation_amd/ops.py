@@ -1975,6 +1975,114 @@ def erase_to_background_host(frame, background, box_masks, boxes) -> _np.ndarray
 
 
 # ---------------------------------------------------------------------------------------------
+# vehicle boxes from the estimated background, on a cell grid (csrc/foreground_boxes.h)
+# ---------------------------------------------------------------------------------------------
+FOREGROUND_BOXES_MAX = 64           # K: boxes per frame, the background median's limit
+FOREGROUND_BOXES_COMPONENTS = 256   # components examined per frame
+FOREGROUND_BOXES_STATS = ("n_kept", "n_examined", "n_p", "flags")
+FOREGROUND_BOXES_OVERFLOW, FOREGROUND_BOXES_TRUNCATED = 1, 2
+
+
+def _foreground_boxes_args(frames, backgrounds, thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, max_boxes, roi, u8, what):
+    """What both forms of `foreground_boxes` check themselves - the images and that every parameter is an integer; the ranges are
+    the library's to refuse -> (frames, backgrounds, T, H, W, the eleven int32 parameters with K in place, roi int32 [4])."""
+    if hasattr(frames, "shape") and len(frames.shape) == 3:
+        frames = [frames]
+    frames, T, H, W = _background_frames(frames, u8, what)
+    if hasattr(backgrounds, "shape") and len(backgrounds.shape) == 3:
+        backgrounds = [backgrounds] * T
+    if hasattr(backgrounds, "shape") and len(backgrounds.shape) != 4:
+        raise ValueError(f"{what}: backgrounds must be uint8 [H, W, 3], or one per frame")
+    bgs = [backgrounds[f] for f in range(len(backgrounds))]
+    if len(bgs) != T:
+        raise ValueError(f"{what}: {len(bgs)} backgrounds for {T} frames")
+    for f, g in enumerate(bgs):
+        if not hasattr(g, "shape") or g.dtype != u8 or tuple(g.shape) != (H, W, 3):
+            raise ValueError(f"{what}: background {f} must be uint8 {(H, W, 3)}, got {getattr(g, 'dtype', type(g))} {tuple(getattr(g, 'shape', ()))}")
+        if not (g.is_contiguous() if isinstance(g, torch.Tensor) else g.flags.c_contiguous):
+            raise ValueError(f"{what}: background {f} is not contiguous")
+    par = []
+    for name, v in (("thr", thr), ("cell", cell), ("min_count", min_count), ("open_r", open_r), ("close_r", close_r),
+                    ("min_area", min_area), ("min_w", min_w), ("min_h", min_h), ("max_boxes", max_boxes)):
+        if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError(f"{what}: {name} = {v} must be an integer")
+        par.append(int(v))
+    r = _np.asarray((0, 0, W, H) if roi is None else roi)
+    if r.dtype.kind not in "iu" or r.shape != (4,) or r.min() < -2 ** 31 or r.max() >= 2 ** 31:
+        raise ValueError(f"{what}: roi must be four integers (x0, y0, x1, y1), half-open, got {roi}")
+    return frames, bgs, T, H, W, par, _np.ascontiguousarray(r.astype(_np.int32))
+
+
+def foreground_boxes(frames, backgrounds, thr: int = 24, cell: int = 8, min_count: int = 16, open_r: int = 0, close_r: int = 1,
+                     min_area: int = 400, min_w: int = 12, min_h: int = 12, max_boxes: int = 64, roi=None, out=None):
+    """Vehicle boxes of every frame from the background, on the device (fusg_foreground_boxes_u8: two launches on the current
+    stream, nothing read back; csrc/foreground_boxes.h states the definition): a pixel counts when max_c |frame - background| >
+    thr inside roi; a cell x cell cell (4, 8 or 16) is on with >= min_count such pixels; the cell grid is opened by the
+    (2 open_r + 1)^2 square and closed by the (2 close_r + 1)^2 one without eating back from the frame edge; each 4-connected
+    component, in the raster order of its first cell (the first 256 are looked at), is kept when it has >= min_area such pixels
+    and its pixel-tight box is >= min_w wide and >= min_h high.  The defaults are tried on synthetic scenes only.
+    frames: one CUDA uint8 [H, W, 3] frame, or a sequence / stack of up to 64; backgrounds: one [H, W, 3] for all frames or one
+    per frame; roi = (x0, y0, x1, y1) half-open, default the frame; out = (boxes, box_stats, stats) to write into.
+    -> (boxes int32 [T, K, 4] half-open (x0, y0, x1, y1), box_stats int32 [T, K, 2] = (area, n_cells), stats int32 [T, 4] =
+    `FOREGROUND_BOXES_STATS`, flags 1 = more than K = max_boxes were kept, 2 = more than 256 components) on the device; the rows
+    from min(n_kept, K) on are zeros."""
+    what = "foreground_boxes"
+    frames, bgs, T, H, W, par, r = _foreground_boxes_args(frames, backgrounds, thr, cell, min_count, open_r, close_r, min_area, min_w, min_h,
+                                                          max_boxes, roi, torch.uint8, what)
+    dev = frames[0].device
+    for t in frames + bgs:
+        if t.device != dev:
+            raise ValueError(f"{what}: a frame or background is on {t.device}, frame 0 on {dev}")
+    _require_gpu(frames[0], "frames")
+    K = par[-1]
+    if not 1 <= K <= FOREGROUND_BOXES_MAX:
+        raise ValueError(f"{what}: max_boxes = {K} (1..{FOREGROUND_BOXES_MAX})")
+    shapes = ((T, K, 4), (T, K, 2), (T, 4))
+    if out is not None:
+        for o, s in zip(out, shapes):
+            if not torch.is_tensor(o) or o.dtype != torch.int32 or tuple(o.shape) != s or not o.is_contiguous() or o.device != dev:
+                raise ValueError(f"{what}: out must be contiguous int32 tensors of {shapes} on {dev}")
+    with torch.cuda.device(dev):
+        lib = L.lib()
+        sb = int(lib.fusg_foreground_boxes_scratch_bytes(T, H, W, par[1]))
+        if sb < 0:
+            raise ValueError(f"{what}: cell = {par[1]} (4, 8 or 16)")
+        boxes, box_stats, stats = out if out is not None else [torch.empty(s, dtype=torch.int32, device=dev) for s in shapes]
+        scratch = torch.empty((sb // 4,), dtype=torch.int32, device=dev)
+        fp = (C.c_void_p * T)(*[f.data_ptr() for f in frames])
+        gp = (C.c_void_p * T)(*[g.data_ptr() for g in bgs])
+        L.check(lib.fusg_foreground_boxes_u8(fp, gp, T, H, W, *par[:8], r.ctypes.data, K, boxes.data_ptr(), box_stats.data_ptr(),
+                                             stats.data_ptr(), scratch.data_ptr(), stream_ptr()), what)
+        if RECORDER is not None:
+            RECORDER.keep.append(scratch)
+    return boxes, box_stats, stats
+
+
+def foreground_boxes_host(frames, backgrounds, thr: int = 24, cell: int = 8, min_count: int = 16, open_r: int = 0, close_r: int = 1,
+                          min_area: int = 400, min_w: int = 12, min_h: int = 12, max_boxes: int = 64, roi=None, out=None):
+    """`foreground_boxes` on the CPU by the same code (fusg_foreground_boxes_host; no GPU needed): numpy uint8 images in, (boxes,
+    box_stats, stats) int32 numpy arrays out."""
+    what = "foreground_boxes_host"
+    as_np = lambda x: [_np.asarray(f) for f in x] if isinstance(x, (list, tuple)) else _np.asarray(x)  # noqa: E731
+    frames, bgs, T, H, W, par, r = _foreground_boxes_args(as_np(frames), as_np(backgrounds), thr, cell, min_count, open_r, close_r, min_area,
+                                                          min_w, min_h, max_boxes, roi, _np.uint8, what)
+    K = par[-1]
+    if not 1 <= K <= FOREGROUND_BOXES_MAX:
+        raise ValueError(f"{what}: max_boxes = {K} (1..{FOREGROUND_BOXES_MAX})")
+    shapes = ((T, K, 4), (T, K, 2), (T, 4))
+    if out is not None:
+        for o, s in zip(out, shapes):
+            if not isinstance(o, _np.ndarray) or o.dtype != _np.int32 or o.shape != s or not o.flags.c_contiguous:
+                raise ValueError(f"{what}: out must be contiguous int32 arrays of {shapes}")
+    boxes, box_stats, stats = out if out is not None else [_np.zeros(s, dtype=_np.int32) for s in shapes]
+    fp = (C.c_void_p * T)(*[f.ctypes.data for f in frames])
+    gp = (C.c_void_p * T)(*[g.ctypes.data for g in bgs])
+    L.check(L.lib().fusg_foreground_boxes_host(fp, gp, T, H, W, *par[:8], r.ctypes.data, K, boxes.ctypes.data, box_stats.ctypes.data,
+                                               stats.ctypes.data), what)
+    return boxes, box_stats, stats
+
+
+# ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------
 def prof_enable(on: bool) -> None:

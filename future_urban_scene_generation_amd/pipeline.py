@@ -1791,6 +1791,62 @@ class VehiclePipeline:
         inp = self.foreground_inpaint(scene, background, grow=grow, **params)
         return ops.erase_to_background(scene["frame"], background, inp["box_masks"], inp["boxes"])
 
+    def detect_vehicles(self, scenes, background, **params) -> list:
+        """scene['bboxes'] without a tracker's detector: per scene {'bboxes' int64 [V_f, 4] (x0, y0, x1, y1) half-open and
+        pixel-tight, 'area' int64 [V_f], 'stats' int32 [4] = `ops.FOREGROUND_BOXES_STATS`} on the host, for the caller to assign.
+        A vehicle is a 4-connected blob of grid cells in which the frame differs from `background` (uint8 [H, W, 3] on the device,
+        e.g. `estimate_background`'s, or one per scene) - `ops.foreground_boxes`, two launches per 64 scenes, and ONE `ops.d2h`
+        for all of them (params: thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, max_boxes, roi - defaults tried on
+        synthetic scenes only).  Boxes are per frame: nothing links them across frames, and the read-back is the only way the
+        boxes reach `foreground_inpaint`.  Nothing is put into the scenes."""
+        from . import ops
+        frames = [s["frame"] for s in scenes]
+        if not frames:
+            return []
+        one = hasattr(background, "shape") and len(background.shape) == 3
+        rows = []
+        for a in range(0, len(frames), ops.BACKGROUND_MAX_FRAMES):
+            b = min(len(frames), a + ops.BACKGROUND_MAX_FRAMES)
+            boxes, box_stats, stats = ops.foreground_boxes(frames[a:b], background if one else [background[f] for f in range(a, b)], **params)
+            rows.append(torch.cat([boxes.view(b - a, -1), box_stats.view(b - a, -1), stats], dim=1))
+        return self._detected_rows(ops.d2h(rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)))
+
+    @staticmethod
+    def _detected_rows(table) -> list:
+        """`detect_vehicles`' read-back, int32 [T, 6 K + 4] = per frame K boxes, K (area, n_cells) and the four stats -> the rows
+        of each frame that hold a box (the first min(n_kept, K))."""
+        import numpy as np
+        K = (table.shape[1] - 4) // 6
+        out = []
+        for row in table:
+            v = min(int(row[6 * K]), K)
+            out.append({"bboxes": row[:4 * K].reshape(K, 4)[:v].astype(np.int64), "area": row[4 * K:6 * K].reshape(K, 2)[:v, 0].astype(np.int64),
+                        "stats": row[6 * K:].copy()})
+        return out
+
+    def bootstrap_background(self, scenes, max_frames: int = 64, margin: int = 8, rounds: int = 1, min_valid: Optional[int] = None,
+                             **params) -> Dict:
+        """`estimate_background` for a video that comes without boxes: the median of the sampled frames with no boxes, then `rounds`
+        times `detect_vehicles` on those frames against it and the median again with the boxes found (grown by `margin`) kept out.
+        A vehicle that stands through the sampled frames but changes its look is baked into the first median and marked
+        (count < min_valid) by the second; one that never changes is background to both.  params go to `detect_vehicles`.
+        Returns `estimate_background`'s dict plus 'bboxes': the last round's int64 [V_f, 4] half-open boxes per sampled frame.
+        Nothing is put into the scenes."""
+        import numpy as np
+
+        from . import ops
+        idx = self.background_indices(len(scenes), max_frames)
+        T = len(idx)
+        mv = max(1, T // 8) if min_valid is None else int(min_valid)
+        sampled = [scenes[i] for i in idx]
+        frames = [s["frame"] for s in sampled]
+        bg, count = ops.background_median(frames, None, margin=margin, min_valid=mv)
+        found = [np.zeros((0, 4), dtype=np.int64) for _ in idx]
+        for _ in range(int(rounds)):
+            found = [d["bboxes"] for d in self.detect_vehicles(sampled, bg, **params)]
+            bg, count = ops.background_median(frames, [b - np.asarray([0, 0, 1, 1]) for b in found], margin=margin, min_valid=mv)   # inclusive ends
+        return {"background": bg, "count": count, "frames": idx, "min_valid": mv, "bboxes": found}
+
     @staticmethod
     def _composites(paste, out: Dict, box_geom=None) -> Dict:
         """'frame_icn' and 'frame_vunet': paste(crops, **box) once per composite (:184-198, :236-250; :393-410, :428-445), the

@@ -977,6 +977,37 @@ int fusg_erase_boxes_u8(const uint8_t* frame, const uint8_t* background, int32_t
 int fusg_erase_boxes_host(const uint8_t* frame, const uint8_t* background, int32_t H, int32_t W, const uint8_t* mask,
                           int64_t mask_len, const int64_t* offsets, const int32_t* boxes, int32_t n, uint8_t* dst);
 
+/* ---- vehicle boxes from the estimated background (what scene['bboxes'] takes without a tracker's detector; new entry points,
+ * FUSG_VERSION stays 118) */
+/* Per frame f of T: P = max_c |frame - background| > thr inside the half-open pixel rectangle roi4 = (x0, y0, x1, y1); the frame
+ * is cut into cell x cell cells (partial at the right and lower edge), a cell is on when it holds >= min_count P pixels; the
+ * cell grid is opened by the (2 open_r + 1)^2 square (outside = 0) and closed by the (2 close_r + 1)^2 square (dilation
+ * outside = 0, erosion outside = 1); its 4-connected components, ordered by their first cell in raster order, are examined, the
+ * first 256 of them; a component's area is the number of P pixels in its cells and its box the pixel-tight, half-open rectangle
+ * around them; it is kept if area >= min_area, box width >= min_w and box height >= min_h.  csrc/foreground_boxes.h states the
+ * definition step by step.
+ * frames / backgrounds = HOST tables of T <= FUSG_MAX_FRAMES DEVICE pointers to dense u8 [H, W, 3] images, read before the call
+ * returns (the same pointer may repeat).  Outputs, DEVICE int32, each written whole: boxes [T][K][4] and box_stats [T][K][2] =
+ * (area, n_cells) hold the first K kept components in order and zeros from row min(n_kept, K) on; stats [T][4] = n_kept,
+ * n_examined, n_P (the frame's P pixels), flags (1 OVERFLOW: n_kept > K; 2 TRUNCATED: more than 256 components, the rest
+ * ignored).  scratch: DEVICE, 4-byte aligned, fusg_foreground_boxes_scratch_bytes() bytes (one 32-bit record per cell and
+ * frame); every call writes all of it before reading it, it holds nothing between calls.
+ * Checked on the host before any launch (FUSG_ERR_INVALID): T in 1..FUSG_MAX_FRAMES, no null pointer, H and W in 1..32767, thr
+ * 0..254, cell 4, 8 or 16, min_count 1..cell^2, open_r 0..3, close_r 0..7, min_area, min_w, min_h >= 1, K 1..64, roi inside the
+ * frame and not inverted, and the grid's two bit planes of ceil(H / cell) * ceil(ceil(W / cell) / 32) words within 64 KiB of
+ * LDS less 512 bytes - else the message says to raise cell.  Two launches (a cell pass over the images, one workgroup per frame
+ * for the rest), no atomics, no floating point; bit-identical to the host twin; recorded and replayed by a fusg_plan. */
+int fusg_foreground_boxes_u8(const void* const* frames, const void* const* backgrounds, int32_t T, int32_t H, int32_t W, int32_t thr,
+                             int32_t cell, int32_t min_count, int32_t open_r, int32_t close_r, int32_t min_area, int32_t min_w,
+                             int32_t min_h, const int32_t* roi4, int32_t K, int32_t* boxes, int32_t* box_stats, int32_t* stats,
+                             void* scratch, void* stream);
+/* Bytes of scratch for T frames of H x W at this cell size: 4 T ceil(H / cell) ceil(W / cell); -1 for a bad argument. */
+int64_t fusg_foreground_boxes_scratch_bytes(int32_t T, int32_t H, int32_t W, int32_t cell);
+/* The same code on the CPU: every pointer is a HOST pointer, no GPU and no scratch needed. */
+int fusg_foreground_boxes_host(const void* const* frames, const void* const* backgrounds, int32_t T, int32_t H, int32_t W, int32_t thr,
+                               int32_t cell, int32_t min_count, int32_t open_r, int32_t close_r, int32_t min_area, int32_t min_w,
+                               int32_t min_h, const int32_t* roi4, int32_t K, int32_t* boxes, int32_t* box_stats, int32_t* stats);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)

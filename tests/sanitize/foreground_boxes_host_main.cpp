@@ -1,0 +1,145 @@
+// Stand-alone sanitizer program for the host twin of the foreground boxes (csrc/foreground_boxes.hip, fusg_foreground_boxes_host:
+// the header's per-frame code on one thread).  CPU only - it never touches a GPU:
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//       -Xarch_host -fno-sanitize-recover=undefined tests/sanitize/foreground_boxes_host_main.cpp \
+//       future_urban_scene_generation_amd/csrc/foreground_boxes.hip -o foreground_boxes_asan && ./foreground_boxes_asan
+// Frames of exactly H x W pixels (widths that put the grid on both sides of a word seam and leave partial cells, heights 1, 2,
+// 37), every cell size, radii at 0 and at their largest (3 / 7), an roi that is the frame, cuts cells or is empty, and output
+// tables of exactly K rows, so that any access outside an image or a table is one outside an exactly-sized heap buffer.  Every
+// frame's n_P equals the count made here, the kept boxes lie inside the roi and are not empty, their areas add up to no more
+// than n_P, the rows past the last box are zeros; a checkerboard of cells is truncated at 256; bad arguments are refused.
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <functional>
+#include <vector>
+#include <hip/hip_runtime.h>
+#include "../../include/fusg.h"
+
+namespace fusg {                                    // what the translation unit expects of the rest of the library
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    std::fputc('\n', stderr);
+}
+bool plan_recording() { return false; }
+void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
+int32_t route_batch_now() { return 0; }
+struct RouteBatchScope {
+    int32_t prev;
+    explicit RouteBatchScope(int32_t r);
+    ~RouteBatchScope();
+};
+RouteBatchScope::RouteBatchScope(int32_t) : prev(0) {}
+RouteBatchScope::~RouteBatchScope() {}
+}  // namespace fusg
+
+static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
+
+// a background, and a frame that differs from it by 60 on one channel in blocks of 6 x 6 with some single pixels flipped
+static void images(int H, int W, uint32_t seed, std::vector<uint8_t>& fr, std::vector<uint8_t>& bg) {
+    fr.assign((size_t)H * W * 3, 0);
+    bg.assign((size_t)H * W * 3, 0);
+    std::vector<uint8_t> coarse((size_t)(H / 6 + 1) * (W / 6 + 1));
+    for (auto& c : coarse) c = rnd(seed) % 10 < 4;
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            bool on = coarse[(size_t)(y / 6) * (W / 6 + 1) + x / 6] != 0;
+            if (rnd(seed) % 32 == 0) on = !on;
+            for (int c = 0; c < 3; ++c) {
+                const uint8_t b = (uint8_t)(10 + rnd(seed) % 90);
+                bg[((size_t)y * W + x) * 3 + c] = b;
+                fr[((size_t)y * W + x) * 3 + c] = (uint8_t)(b + (on && c == 1 ? 60 : rnd(seed) % 5));
+            }
+        }
+}
+
+static long count_p(const std::vector<uint8_t>& fr, const std::vector<uint8_t>& bg, int W, const int32_t* roi, int thr) {
+    long n = 0;
+    for (int y = roi[1]; y < roi[3]; ++y)
+        for (int x = roi[0]; x < roi[2]; ++x) {
+            int m = 0;
+            for (int c = 0; c < 3; ++c) {
+                const int d = (int)fr[((size_t)y * W + x) * 3 + c] - (int)bg[((size_t)y * W + x) * 3 + c];
+                m = (d < 0 ? -d : d) > m ? (d < 0 ? -d : d) : m;
+            }
+            n += m > thr;
+        }
+    return n;
+}
+
+int main() {
+    long total_boxes = 0, total_p = 0;
+    const int radii[3][2] = {{0, 0}, {1, 1}, {3, 7}};
+    for (int W : {1, 3, 70, 129, 133, 260, 515})
+        for (int H : {1, 2, 37})
+            for (int cell : {4, 8, 16})
+                for (const auto& r : radii)
+                    for (int q = 0; q < 3; ++q) {
+                        std::vector<uint8_t> fr, bg;
+                        images(H, W, (uint32_t)(W * 131 + H * 7 + cell), fr, bg);
+                        const int32_t rois[3][4] = {{0, 0, W, H}, {W / 3, H / 3, W - W / 4, H - H / 5}, {W / 2, 0, W / 2, H}};
+                        const int32_t* roi = rois[q];
+                        const int K = 1 + (W + H + q) % 5;
+                        const void* fp[2] = {fr.data(), fr.data()};
+                        const void* gp[2] = {bg.data(), bg.data()};
+                        std::vector<int32_t> boxes((size_t)2 * K * 4, -7), bstats((size_t)2 * K * 2, -7), stats(8, -7);
+                        if (fusg_foreground_boxes_host(fp, gp, 2, H, W, 24, cell, cell, r[0], r[1], 1, 1, 1, roi, K, boxes.data(), bstats.data(),
+                                                       stats.data()) != FUSG_OK) return 1;
+                        const long np = count_p(fr, bg, W, roi, 24);
+                        for (int f = 0; f < 2; ++f) {
+                            const int32_t* st = stats.data() + 4 * f;
+                            if (st[2] != np || st[0] < 0 || st[0] > st[1] || st[1] > 256) return 2;
+                            if (((st[3] & 1) != 0) != (st[0] > K) || (st[3] & ~3)) return 3;
+                            const int used = st[0] < K ? st[0] : K;
+                            long area = 0;
+                            for (int k = 0; k < K; ++k) {
+                                const int32_t* b = boxes.data() + ((size_t)f * K + k) * 4;
+                                const int32_t* s = bstats.data() + ((size_t)f * K + k) * 2;
+                                if (k >= used) {
+                                    if (b[0] || b[1] || b[2] || b[3] || s[0] || s[1]) return 4;
+                                    continue;
+                                }
+                                if (b[0] < roi[0] || b[1] < roi[1] || b[2] > roi[2] || b[3] > roi[3] || b[2] <= b[0] || b[3] <= b[1]) return 5;
+                                if (s[0] < 1 || s[1] < 1 || s[0] > (long)(b[2] - b[0]) * (b[3] - b[1])) return 6;
+                                area += s[0];
+                            }
+                            if (area > np) return 7;
+                            total_boxes += used;
+                        }
+                        if (boxes[0] != boxes[(size_t)K * 4] || stats[0] != stats[4]) return 8;   // the same frame twice
+                        total_p += np;
+                    }
+    // 96 x 96, every other 4 x 4 cell on: 288 components, 256 examined, K = 64 written
+    {
+        const int H = 96, W = 96, K = 64;
+        std::vector<uint8_t> bg((size_t)H * W * 3, 50), fr(bg);
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x)
+                if (((y / 4) + (x / 4)) % 2 == 0) fr[((size_t)y * W + x) * 3 + 2] = 150;
+        const void* fp[1] = {fr.data()};
+        const void* gp[1] = {bg.data()};
+        const int32_t roi[4] = {0, 0, W, H};
+        std::vector<int32_t> boxes((size_t)K * 4, -7), bstats((size_t)K * 2, -7), stats(4, -7);
+        if (fusg_foreground_boxes_host(fp, gp, 1, H, W, 24, 4, 16, 0, 0, 1, 1, 1, roi, K, boxes.data(), bstats.data(), stats.data()) != FUSG_OK)
+            return 9;
+        if (stats[0] != 256 || stats[1] != 256 || stats[2] != 288 * 16 || stats[3] != 3) return 10;
+        if (boxes[4] != 8 || boxes[5] != 0 || boxes[6] != 12 || boxes[7] != 4 || bstats[2] != 16 || bstats[3] != 1) return 11;
+        // bad arguments
+        const int32_t bad_roi[4] = {0, 0, W + 1, H};
+        auto call = [&](int T, int cell, int mc, int op, int cl, int ma, int k, const int32_t* r) {
+            return fusg_foreground_boxes_host(fp, gp, T, H, W, 24, cell, mc, op, cl, ma, 1, 1, r, k, boxes.data(), bstats.data(), stats.data());
+        };
+        if (call(0, 4, 16, 0, 0, 1, K, roi) != FUSG_ERR_INVALID || call(1, 5, 16, 0, 0, 1, K, roi) != FUSG_ERR_INVALID) return 12;
+        if (call(1, 4, 17, 0, 0, 1, K, roi) != FUSG_ERR_INVALID || call(1, 4, 16, 4, 0, 1, K, roi) != FUSG_ERR_INVALID) return 13;
+        if (call(1, 4, 16, 0, 8, 1, K, roi) != FUSG_ERR_INVALID || call(1, 4, 16, 0, 0, 0, K, roi) != FUSG_ERR_INVALID) return 14;
+        if (call(1, 4, 16, 0, 0, 1, 65, roi) != FUSG_ERR_INVALID || call(1, 4, 16, 0, 0, 1, K, bad_roi) != FUSG_ERR_INVALID) return 15;
+        if (call(1, 4, 16, 0, 0, 1, K, nullptr) != FUSG_ERR_INVALID) return 16;
+        if (fusg_foreground_boxes_host(fp, gp, 1, 4 * 255, 4 * 1024, 24, 4, 16, 0, 0, 1, 1, 1, roi, K, boxes.data(), bstats.data(), stats.data())
+            != FUSG_ERR_INVALID) return 17;                               // the grid leaves the LDS budget: refused before a pixel is read
+    }
+    std::printf("boxes %ld, differing pixels %ld\n", total_boxes, total_p);
+    return total_boxes > 0 && total_p > 0 ? 0 : 20;
+}
