@@ -85,7 +85,7 @@ typedef enum fusg_store_mode {
  *        (wscale), so every operand in fp16's normal range [2^-14, 2^15) keeps >= 22 significant bits: the
  *        error against fp64 is at or below that of an fp32 fmaf chain for operand scales 1e-4 .. 1e4
  *        (tools/emu_split.py, tests/test_gpu_ops.py::test_f16x3_scale_sweep).  3 MFMA passes at the fp16 rate.
- *        Nothing is clamped: a launch that stages an operand with |x| >= 2^15 (or a non-finite one) sets
+ *        Nothing is clamped: a launch that stages an operand with |x| >= 2^15 (or an infinity) sets
  *        *status = 1 and its output is unspecified; the caller must then redo the work with F32.
  * EMU_BF16 / EMU_BF16X2: evidence paths, not production: the F32 kernel with every staged activation rounded to 8 / 16
  *        significant bits (the caller passes weights rounded the same way in `wpack`): products of such operands are
@@ -100,9 +100,11 @@ typedef enum fusg_store_mode {
  *        product per operand pair - the first of F16X3's three: a' = RTN_fp16(pre_op(a)) rounded as it is staged (ties to even),
  *        w' = RTN_fp16(w * s[n]) = the `hi` half of the split weights, acc += a' * w' on v_mfma_f32_16x16x32_f16 in fp32,
  *        out = act(fmaf(acc, wscale[n], bias[n])).  11 significant bits per operand where BF16 keeps 8, at BF16's matrix rate and
- *        operand bytes, from the F16X3 fields alone: no weight copy of its own.  F16X3's range guard holds unchanged (every staged
- *        operand after the pre-op and a fused ReLU's floor; |a| >= 2^15 or non-finite sets *status; nothing is clamped).  Every
- *        other launch runs as F16X3, bit for bit.  Added without a version step: two enum values, no layout change, and
+ *        operand bytes, from the F16X3 fields alone: no weight copy of its own.  Activations are staged unscaled, so the 11 bits
+ *        hold for staged |a| >= 2^-14; below that a' is an fp16 subnormal (gradual underflow, never flushed): an absolute 2^-25.
+ *        F16X3's range guard holds unchanged (every staged operand after the pre-op and a fused ReLU's floor; |a| >= 2^15 or an
+ *        infinity sets *status; nothing is clamped), and so does its NaN rule: a NaN reaches the output, or is zeroed by a fused
+ *        ReLU without raising *status (csrc/conv_kernel_h3.h).  Every other launch runs as F16X3, bit for bit.  Added without a version step: two enum values, no layout change, and
  *        FUSG_VERSION 118 is what the suite pins. */
 typedef enum fusg_precision { FUSG_PREC_F32 = 0, FUSG_PREC_F16X3 = 1, FUSG_PREC_EMU_BF16 = 2, FUSG_PREC_EMU_BF16X2 = 3,
                               FUSG_PREC_BF16 = 4, FUSG_PREC_F16 = 5 } fusg_precision;

@@ -151,6 +151,64 @@ def make_plan(c: Case, w: torch.Tensor, b: torch.Tensor) -> pack.ConvPlan:
                          dil=c.dil, pad_mode=c.pm, upsample=c.ups, nphase=1, flops_per_pixel=2.0 * c.cout * c.K, pad_w=c.pad_w)
 
 
+# ---- the keywords of a case's ops.conv launch: ONE copy, for the GPU launch and for the router's dry run on CPU tensors ----
+SENTINEL = 1234.5        # what every output buffer of the tests' own holds before the launch
+GUARD = 64               # fp32 elements on each side of a "misaligned" output (a padded column, a pixel's channels past the end)
+
+
+def launch_kwargs(c: Case, B: int, device, prec: str, pre=None, pre_bstride: int = 0, res=(), ksplit: Optional[int] = None,
+                  tile: int = L.TILE_AUTO):
+    """(kw, guard) of ops.conv(plan, x0, x1, **kw) for the case at batch B: `pre` the (scale, shift) of an affine pre-op in the K
+    layout, `res` the residuals.  Output buffers of its own are filled with SENTINEL.  `guard` is None except for a "misaligned"
+    output: then the flat buffer the output lies in, GUARD + 1 sentinels before it (an odd count: the output starts 4 bytes off
+    16-byte alignment) and GUARD after it - `guard_elements` takes them back out after the launch."""
+    from future_urban_scene_generation_amd import ops
+    ho, wo = c.full_hw()
+    kw = dict(pre_op=PRE[c.pre], act=c.act, precision=prec, ksplit=c.ksplit if ksplit is None else ksplit, tile=tile)
+    if pre is not None:
+        kw.update(pre=pre, pre_bstride=pre_bstride)
+    for i, r in enumerate(res):
+        kw["res%d" % i] = r
+    out = guard = None
+    if c.out == "nchw":
+        kw["nchw_out"] = True
+    elif c.out == "slice":
+        out = ops.nhwc_empty(B, c.out_c_off + c.cout + 4, ho, wo, device)
+        kw.update(out=out, out_c_off=c.out_c_off)
+    elif c.out == "misaligned":
+        n = B * ho * wo * c.cout
+        guard = torch.empty(GUARD + 1 + n + GUARD, device=device)
+        out = guard[GUARD + 1:GUARD + 1 + n].view(B, ho, wo, c.cout).permute(0, 3, 1, 2)
+        assert out.data_ptr() % 16 != 0
+        kw["out"] = out
+    if c.qwin:
+        out = ops.nhwc_empty(B, c.cout, ho, wo, device)
+        kw.update(out=out, q_window=c.qwin)
+    if guard is not None:
+        guard.fill_(SENTINEL)
+    elif out is not None:
+        out.fill_(SENTINEL)
+    return kw, guard
+
+
+def guard_elements(guard: torch.Tensor) -> torch.Tensor:
+    """The elements before and after the misaligned output inside `guard` (launch_kwargs), float64 on the CPU."""
+    g = guard.cpu().double()
+    return torch.cat([g[:GUARD + 1], g[-GUARD:]])
+
+
+def d2s(t: torch.Tensor) -> torch.Tensor:
+    """DepthToSpace(2), DCR order, of an NCHW-logical tensor: out[b, c, 2h + i, 2w + j] = in[b, (2i + j) C + c, h, w]."""
+    b, c4, h, w = t.shape
+    return t.reshape(b, 2, 2, c4 // 4, h, w).permute(0, 3, 4, 1, 5, 2).reshape(b, c4 // 4, 2 * h, 2 * w)
+
+
+def s2d(t: torch.Tensor) -> torch.Tensor:
+    """SpaceToDepth(2), the inverse of d2s."""
+    b, c, h, w = t.shape
+    return t.reshape(b, c, h // 2, 2, w // 2, 2).permute(0, 3, 5, 1, 2, 4).reshape(b, 4 * c, h // 2, w // 2)
+
+
 def inputs(c: Case) -> dict:
     """Seeded CPU float32 operands of the case: x0, x1, w, b, the pre-op's (scale, shift) per logical channel ([cin] or
     [B, cin]) and the residuals (output-shaped)."""

@@ -36,8 +36,11 @@ BAR_CHAN = 2.0 ** -18           # streaming path, both forms (against the pivot-
 BAR_WRAPPER = 2.0 ** -20        # the wrappers' nchunk against the direct ABI at nchunk = 1
 EPS = float(np.float32(1e-5))   # the C ABI takes eps as a float
 
+HALO_F16, TAPUNIT_F16 = L.CONV_HALO_F16, L.CONV_TAPUNIT_F16      # the single-pass fp16 mode ("f16": tests/f16_cases.py)
 STAT_FAMILIES = (cs.GEN_F32, cs.GEN_F16X3, cs.HALO, cs.HALO_S2D, cs.HALO_F32, cs.HALO_BF16, cs.TAPUNIT, cs.TAPUNIT_F32,
-                 cs.TAPUNIT_BF16)
+                 cs.TAPUNIT_BF16, HALO_F16, TAPUNIT_F16)
+# "f16" is carried explicitly by the rows that run it (conv_sweep.PRECISIONS indexes the edge table's `expect` triplets)
+PRECISIONS_F16 = cs.PRECISIONS + ("f16",)
 NO_STAT_FAMILIES = (cs.POINTWISE, cs.SMALL)       # the router keeps a launch with stats_out off these
 # a launch with statistics routes as one with these two families switched off
 STATS_ENV = {"FUSG_NO_SMALL": "1", "FUSG_NO_POINTWISE": "1"}
@@ -76,7 +79,10 @@ def qualifies(c: Case, *, ksplit: int = 1, prec: str = "f32", store: int = L.STO
 
 
 def predict_stats_family(c: Case, prec: str, tile: int = 0) -> int:
-    """The family of the case launched with statistics and ksplit = 1."""
+    """The family of the case launched with statistics and ksplit = 1.  ("f16" routes as "bf16" does, onto its own families.)"""
+    if prec == "f16":
+        fam = predict_family(c, "bf16", env=STATS_ENV, ksplit=1, tile=tile)
+        return {cs.HALO_BF16: HALO_F16, cs.TAPUNIT_BF16: TAPUNIT_F16}.get(fam, fam)
     return predict_family(c, prec, env=STATS_ENV, ksplit=1, tile=tile)
 
 
@@ -140,6 +146,7 @@ def _added():
              StatCase(replace(g, tag="st_gen_large", sx=1e3, sw=1e3), precs=("f32", "f16x3")),
              StatCase(replace(g, tag="st_gen_b1", B=1), precs=("f32", "f16x3")),
              StatCase(replace(g, tag="st_gen_slice8", out="slice", out_c_off=8), precs=("f32", "f16x3"))]
+    n_generic = len(rows)
     # halo kernels.  The launcher's rule for the in-workgroup K split (csrc/conv_igemm.hip, conv2d's halo branch):
     #     r->bn  = column_tile(cout_pad, ntaps == 1 ? 64 : 128, mt, halo_minwg)   // halved while mt * cout_pad / bn < 512
     #     r->ksw = !s2d && !d->tile_list && !no_ksplit && mt * (cout_pad / r->bn) <= 1024 &&
@@ -170,6 +177,9 @@ def _added():
              StatCase(t7, "bias50"), StatCase(t7, "zero_ch"), StatCase(t3, "bias50"), StatCase(t3, "zero_ch"),
              StatCase(replace(t7, tag="st_tap_7x7_small", sx=1e-3, sw=1e-3)), StatCase(replace(t7, tag="st_tap_7x7_large", sx=1e3, sw=1e3)),
              StatCase(replace(t3, tag="st_tap_3x3_slice4", out="slice", out_c_off=4))]
+    # the halo and tap-unit rows run under the single-pass fp16 mode too (families 15 / 16: `epilogue_vec16` per half with
+    # `stath` on the tile that leaves in two halves, the K-split `statk`)
+    rows[n_generic:] = [replace(r, precs=PRECISIONS_F16) for r in rows[n_generic:]]
     return rows
 
 
@@ -186,7 +196,7 @@ def halo_takes_ksplit(c: Case, prec: str) -> Optional[bool]:
     """Does the launch (a halo family, default switches, grids of < 512 workgroups: column tile 32) take the in-workgroup
     K-split epilogue?  None: not a halo family."""
     fam = predict_stats_family(c, prec)
-    if fam not in (cs.HALO, cs.HALO_S2D, cs.HALO_F32, cs.HALO_BF16):
+    if fam not in (cs.HALO, cs.HALO_S2D, cs.HALO_F32, cs.HALO_BF16, HALO_F16):
         return None
     s2d = c.stride == 2
     return (not s2d) and c.kh * c.kw >= 4

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 from future_urban_scene_generation_amd import _lib as L          # noqa: E402
 from future_urban_scene_generation_amd import ops                 # noqa: E402
 
-SENTINEL = 1234.5
+SENTINEL = cs.SENTINEL
 PER_CALL = ("FUSG_NO_SMALL", "FUSG_NO_POINTWISE", "FUSG_NO_F32_HALO", "FUSG_NO_BF16_TAPUNIT", "FUSG_SMALL_KSPLIT")
 HALO_FAMILIES = (cs.HALO, cs.HALO_S2D, cs.HALO_BF16, cs.HALO_F32)
 
@@ -91,34 +91,15 @@ def _prepare(c: cs.Case, sample=None):
 def _launch(c: cs.Case, S: dict, prec: str, env=None, ksplit=None, tile=L.TILE_AUTO):
     """One ops.conv launch of the case -> (result in the reference's layout, float64 on the CPU; family; what it wrote
     outside the result, which must be untouched)."""
-    B = S["B"]
-    ho, wo = c.full_hw()
-    kw = dict(pre_op=cs.PRE[c.pre], act=c.act, precision=prec, ksplit=c.ksplit if ksplit is None else ksplit, tile=tile)
-    if "pre" in S:
-        kw.update(pre=S["pre"], pre_bstride=S["pre_bstride"])
-    for i, r in enumerate(S["res"]):
-        kw["res%d" % i] = r
-    out = None
-    if c.out == "nchw":
-        kw["nchw_out"] = True
-    elif c.out == "slice":
-        out = ops.nhwc_empty(B, c.out_c_off + c.cout + 4, ho, wo, dev())
-        out.fill_(SENTINEL)
-        kw.update(out=out, out_c_off=c.out_c_off)
-    elif c.out == "misaligned":
-        buf = torch.full((B * ho * wo * c.cout + 1,), SENTINEL, device=dev())
-        out = buf[1:].view(B, ho, wo, c.cout).permute(0, 3, 1, 2)
-        assert out.data_ptr() % 16 != 0
-        kw["out"] = out
-    if c.qwin:
-        out = ops.nhwc_empty(B, c.cout, ho, wo, dev())
-        out.fill_(SENTINEL)
-        kw.update(out=out, q_window=c.qwin)
+    kw, guard = cs.launch_kwargs(c, S["B"], dev(), prec, pre=S.get("pre"), pre_bstride=S.get("pre_bstride", 0), res=S["res"],
+                                 ksplit=ksplit, tile=tile)
     with _env(env):
         y = ops.conv(S["plan"], S["x0"], S["x1"], **kw)
         fam = ops.last_conv_kernel()
     y = y.cpu().double()
     rest = torch.empty(0, dtype=torch.float64)
+    if guard is not None:                                  # a misaligned output: the sentinels on both sides of it
+        rest = cs.guard_elements(guard)
     if c.out == "slice":
         rest = torch.cat([y[:, :c.out_c_off].flatten(), y[:, c.out_c_off + c.cout:].flatten()])
         y = y[:, c.out_c_off:c.out_c_off + c.cout]

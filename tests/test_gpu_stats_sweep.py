@@ -28,7 +28,7 @@ SENTINEL = 1234.5
 FIRST, TAIL = 3, 2
 NAME = {cs.GEN_F32: "gen_f32", cs.GEN_F16X3: "gen_f16x3", cs.HALO: "halo", cs.HALO_S2D: "halo_s2d", cs.HALO_F32: "halo_f32",
         cs.HALO_BF16: "halo_bf16", cs.TAPUNIT: "tapunit", cs.TAPUNIT_F32: "tapunit_f32", cs.TAPUNIT_BF16: "tapunit_bf16",
-        cs.POINTWISE: "pointwise", cs.SMALL: "small"}
+        cs.POINTWISE: "pointwise", cs.SMALL: "small", ss.HALO_F16: "halo_f16", ss.TAPUNIT_F16: "tapunit_f16"}
 PER_CALL = ("FUSG_NO_SMALL", "FUSG_NO_POINTWISE", "FUSG_NO_F32_HALO", "FUSG_NO_BF16_TAPUNIT", "FUSG_SMALL_KSPLIT")
 
 
@@ -264,7 +264,7 @@ def test_fused_stats_cover_every_family():
             run_fused(sc, prec)
     want = {(cs.GEN_F32, "f32"), (cs.GEN_F16X3, "f16x3"), (cs.GEN_F16X3, "bf16"), (cs.HALO, "f16x3"), (cs.HALO_S2D, "f16x3"),
             (cs.HALO_F32, "f32"), (cs.HALO_BF16, "bf16"), (cs.TAPUNIT, "f16x3"), (cs.TAPUNIT_F32, "f32"),
-            (cs.TAPUNIT_BF16, "bf16")}
+            (cs.TAPUNIT_BF16, "bf16"), (ss.HALO_F16, "f16"), (ss.TAPUNIT_F16, "f16")}
     assert want <= set(OBS), want - set(OBS)
     assert not any(f in ss.NO_STAT_FAMILIES for f, _ in OBS)
     for (fam, prec), o in sorted(OBS.items()):
@@ -275,12 +275,12 @@ def test_fused_stats_cover_every_family():
         assert o["mean"] <= ss.BAR_MEAN and o["var"] <= ss.BAR_VAR, (fam, prec, o)
     for prec, fam in (("f32", cs.GEN_F32), ("f16x3", cs.GEN_F16X3)):
         assert {1, 2, 3, 4, 5} <= OBS[(fam, prec)]["tiles"], OBS[(fam, prec)]["tiles"]
-    for key in ((cs.HALO, "f16x3"), (cs.HALO_F32, "f32"), (cs.HALO_BF16, "bf16")):
+    for key in ((cs.HALO, "f16x3"), (cs.HALO_F32, "f32"), (cs.HALO_BF16, "bf16"), (ss.HALO_F16, "f16")):
         assert {True, False} <= OBS[key]["ksw"], (key, OBS[key]["ksw"])
 
 
 # ---- the wide column tiles of the halo body: a switch cached per process, so a fresh child process ------------------------
-HALO_FAMILIES = (cs.HALO, cs.HALO_S2D, cs.HALO_F32, cs.HALO_BF16)
+HALO_FAMILIES = (cs.HALO, cs.HALO_S2D, cs.HALO_F32, cs.HALO_BF16, ss.HALO_F16)
 
 
 def halo_pairs():
@@ -313,7 +313,7 @@ def test_halo_stats_on_the_wide_column_tiles():
         with open(out) as f:
             res = json.load(f)
     assert not res["fails"], "\n".join(res["fails"])
-    assert {"halo/f16x3", "halo_s2d/f16x3", "halo_f32/f32", "halo_bf16/bf16"} <= set(res["obs"]), sorted(res["obs"])
+    assert {"halo/f16x3", "halo_s2d/f16x3", "halo_f32/f32", "halo_bf16/bf16", "halo_f16/f16"} <= set(res["obs"]), sorted(res["obs"])
     for k, o in res["obs"].items():
         record(f"stats_mean_wide_{k.replace('/', '_')}", o["mean"])
         record(f"stats_var_wide_{k.replace('/', '_')}", o["var"])

@@ -1,6 +1,8 @@
 """VUnet UpSample modes 'nearest' and 'conv2d_t' on the MI355X: the one-launch dense-equivalent form (pack.py) against the
 float64 torch op with the conv sweep's comparator and bar, the tap-sparse halo instantiations against the dense launch
-(byte for byte), their routing, the two reference fixtures, a recorded pass, and a guard on UpSample('subpixel')."""
+(byte for byte), their routing, the two reference fixtures, a recorded pass, and a guard on UpSample('subpixel').  Under the
+single-pass modes ("bf16", "f16") the router runs the dense kernel on the tap-sparse weights: those launches are held to the
+operand-rounded reference of the dense-equivalent weights."""
 import ctypes as C
 import json
 from argparse import Namespace
@@ -28,11 +30,12 @@ PRECS = ("f16x3", "f32")
 SHAPES = {"halo_128": (128, 128, 8, 16), "four_phase": (64, 32, 16, 16), "generic": (32, 32, 5, 7)}
 HALO_FAMILY = {"f16x3": cs.HALO, "f32": cs.HALO_F32}
 GENERIC_FAMILY = {"f16x3": cs.GEN_F16X3, "f32": cs.GEN_F32}
+SINGLE_PASS = {"bf16": (cs.HALO_BF16, cs.BAR_BF16), "f16": (L.CONV_HALO_F16, (1 + 2.0 ** -11) ** 2 - 1)}   # family, operand-rounding bound
 _CACHE = {}
 
 
-def _layer(mode, shape):
-    """(plan, x [2, c_in, H, W], float64 reference, comparator's denominator) of one layer, computed once."""
+def _layer_all(mode, shape):
+    """(plan, x [2, c_in, H, W], float64 reference, comparator's denominator, weight, bias) of one layer, computed once."""
     key = (mode, shape)
     if key not in _CACHE:
         cin, cout, h, w = SHAPES[shape]
@@ -48,8 +51,12 @@ def _layer(mode, shape):
             op = lambda xx, ww, bb: F.conv_transpose2d(xx, ww, bb, stride=2, padding=1, output_padding=1)            # noqa: E731
         ref = op(x.double(), wt.double(), b.double())
         den = op(x.double().abs(), wt.double().abs(), b.double().abs())
-        _CACHE[key] = (plan, x, ref, den)
+        _CACHE[key] = (plan, x, ref, den, wt, b)
     return _CACHE[key]
+
+
+def _layer(mode, shape):
+    return _layer_all(mode, shape)[:4]
 
 
 def _launch(plan, x, prec, tap_sparse=None):
@@ -71,6 +78,37 @@ def test_layer_against_float64(mode, shape, prec):
     record(f"{mode}_{shape}_{prec}_norm_err", err)
     print(f"{mode} {shape} {prec}: family {fam} norm_err {err:.3e} (bar {cs.bar(fam):.3e})")
     assert tuple(got.shape) == tuple(ref.shape) and err <= cs.bar(fam)
+
+
+@pytest.mark.parametrize("prec", list(SINGLE_PASS))
+@pytest.mark.parametrize("shape", ["halo_128", "four_phase"])
+@pytest.mark.parametrize("mode", MODES)
+def test_layer_single_pass_against_the_operand_rounded_reference(mode, shape, prec):
+    """Under "bf16" / "f16" the halo shapes take family 5 / 15: the DENSE kernel, with a DepthToSpace store, on the tap-sparse
+    weights.  Held to that arithmetic - activations and the dense-equivalent weights rounded as the mode rounds them, exact
+    products and sums - at BAR_FP32, and to the float64 torch op at the mode's operand-rounding bound; the launch with the
+    pattern set is the launch with pattern 0, bit for bit."""
+    plan, x, ref, den, wt, b = _layer_all(mode, shape)
+    wd = (pack.up2_nearest_dense_weight if mode == "nearest" else pack.transpose_k3s2p1op1_dense_weight)(wt.float())
+    if prec == "bf16":
+        xr, wr = x.bfloat16().double(), wd.bfloat16().double()
+    else:
+        xr, wr = x.half().double(), pack.f16_mode_weights(wd.reshape(1, wd.shape[0], -1)).reshape(wd.shape).double()
+    b4 = b.repeat(4).double()
+    own = cs.d2s(F.conv2d(xr, wr, b4, padding=1))
+    own_den = cs.d2s(F.conv2d(xr.abs(), wr.abs(), b4.abs(), padding=1))
+    family, bound = SINGLE_PASS[prec]
+    got, fam = _launch(plan, x, prec)
+    dense, fd = _launch(plan, x, prec, tap_sparse=0)
+    assert not ops.range_exceeded(DEV)
+    assert fam == fd == family, (fam, fd)
+    assert torch.equal(got, dense)
+    e_own, e_exact = cs.norm_err(got, own, own_den), cs.norm_err(got, ref, den)
+    record(f"{mode}_{shape}_{prec}_operands_err", e_own)
+    record(f"{mode}_{shape}_{prec}_norm_err", e_exact)
+    print(f"{mode} {shape} {prec}: family {fam}, {e_own:.3e} from its own arithmetic (bar {cs.BAR_FP32:.3e}), {e_exact:.3e} from float64")
+    assert tuple(got.shape) == tuple(ref.shape) and e_own <= cs.BAR_FP32 and e_exact <= bound
+    assert cs.norm_err(own, ref, den) > 10 * cs.BAR_FP32       # (and that reference does tell the mode from f16x3)
 
 
 @pytest.mark.parametrize("prec", PRECS)

@@ -16,7 +16,7 @@ L = cs.L
 def test_every_family_and_precision_has_a_case():
     want = {(cs.GEN_F32, "f32"), (cs.GEN_F16X3, "f16x3"), (cs.GEN_F16X3, "bf16"), (cs.HALO, "f16x3"), (cs.HALO_S2D, "f16x3"),
             (cs.HALO_F32, "f32"), (cs.HALO_BF16, "bf16"), (cs.TAPUNIT, "f16x3"), (cs.TAPUNIT_F32, "f32"),
-            (cs.TAPUNIT_BF16, "bf16")}
+            (cs.TAPUNIT_BF16, "bf16"), (ss.HALO_F16, "f16"), (ss.TAPUNIT_F16, "f16")}
     seen, variants, tiles = set(), {}, set()
     for sc in ss.stat_cases():
         assert ss.qualifies(sc.case, ksplit=1), sc.tag
@@ -37,8 +37,9 @@ def test_every_family_and_precision_has_a_case():
         assert {"plain", "bias50", "zero_ch", "small", "large"} <= variants[fam], (fam, variants[fam])
     # both epilogues of the halo body, at every precision; an out slice and a single image per family group
     ks = {(ss.halo_takes_ksplit(sc.case, p), p) for sc in ss.stat_cases() for p in sc.precs}
-    assert {(k, p) for k in (True, False) for p in cs.PRECISIONS} <= ks
-    for fams in ((cs.GEN_F32, cs.GEN_F16X3), (cs.HALO, cs.HALO_F32, cs.HALO_BF16), (cs.TAPUNIT, cs.TAPUNIT_F32, cs.TAPUNIT_BF16)):
+    assert {(k, p) for k in (True, False) for p in ss.PRECISIONS_F16} <= ks
+    for fams in ((cs.GEN_F32, cs.GEN_F16X3), (cs.HALO, cs.HALO_F32, cs.HALO_BF16, ss.HALO_F16),
+                 (cs.TAPUNIT, cs.TAPUNIT_F32, cs.TAPUNIT_BF16, ss.TAPUNIT_F16)):
         rows = [sc for sc in ss.stat_cases() if ss.predict_stats_family(sc.case, sc.precs[-1], sc.tile) in fams]
         assert any(sc.case.out == "slice" and sc.case.out_c_off % 4 == 0 for sc in rows), fams
         assert any(sc.case.B == 1 for sc in rows), fams
