@@ -206,6 +206,9 @@ _SIGS = {
     "fusg_foreground_boxes_u8": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 11 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     "fusg_foreground_boxes_scratch_bytes": (C.c_int64, [C.c_int32] * 4),
     "fusg_foreground_boxes_host": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 11 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3),
+    "fusg_link_boxes": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 7 + [C.c_void_p] * 5),
+    "fusg_link_boxes_host": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 7 + [C.c_void_p] * 4),
+    "fusg_link_boxes_state_words": (C.c_int32, []),
     "fusg_plan_create": (C.c_void_p, []),
     "fusg_plan_destroy": (None, [C.c_void_p]),
     "fusg_plan_begin": (C.c_int, [C.c_void_p]),

@@ -2083,6 +2083,130 @@ def foreground_boxes_host(frames, backgrounds, thr: int = 24, cell: int = 8, min
 
 
 # ---------------------------------------------------------------------------------------------
+# the boxes of successive frames linked into trajectories (csrc/track_boxes.h)
+# ---------------------------------------------------------------------------------------------
+LINK_BOXES_STATS = ("n_tracks", "n_live", "n_linked", "flags")
+LINK_BOXES_BAD_BOX, LINK_BOXES_TRACKS_FULL, LINK_BOXES_LIVE_FULL, LINK_BOXES_ORDER, LINK_BOXES_BAD_STATE = 1, 2, 4, 8, 16
+LINK_BOXES_LIVE_MAX = 128           # live tracks per video
+LINK_BOXES_MAX_VIDEOS = 64          # videos (workgroups) per call
+LINK_BOXES_STATE_WORDS = 8 + 128 * 13
+
+
+def _link_boxes_args(boxes, stats, iou, max_gap, predict, max_tracks, t0, lib_t, what):
+    """What both forms of `link_boxes` check themselves - the tables' shapes and types and that every parameter is an integer;
+    the ranges are the library's to refuse -> (boxes and stats as ONE table each, one video?, S, K, first int32 [S + 1], t0 int32
+    [S], the five int32 parameters)."""
+    is_t = (lambda x: torch.is_tensor(x)) if lib_t is torch else (lambda x: isinstance(x, _np.ndarray))
+    one = is_t(boxes)
+    bl, sl = ([boxes], [stats]) if one else (list(boxes), list(stats))
+    S = len(bl)
+    if S < 1 or len(sl) != S:
+        raise ValueError(f"{what}: {S} box tables and {len(sl)} stats tables (one pair per video, at least one)")
+    i32 = torch.int32 if lib_t is torch else _np.int32
+    K = None
+    for s, (b, st) in enumerate(zip(bl, sl)):
+        if not is_t(b) or not is_t(st) or b.dtype != i32 or st.dtype != i32 or len(b.shape) != 3 or b.shape[2] != 4 \
+                or tuple(st.shape) != (b.shape[0], 4):
+            raise ValueError(f"{what}: video {s} must be int32 boxes [T, K, 4] and int32 stats [T, 4] (ops.foreground_boxes' tables), got "
+                             f"{getattr(b, 'dtype', type(b))} {tuple(getattr(b, 'shape', ()))} and {getattr(st, 'dtype', type(st))} "
+                             f"{tuple(getattr(st, 'shape', ()))}")
+        K = int(b.shape[1]) if K is None else K
+        if int(b.shape[1]) != K:
+            raise ValueError(f"{what}: video {s} has K = {int(b.shape[1])} boxes per frame, video 0 has {K}")
+    first = _np.zeros((S + 1,), dtype=_np.int64)
+    first[1:] = _np.cumsum([int(b.shape[0]) for b in bl])
+    if first[-1] >= 2 ** 31:
+        raise ValueError(f"{what}: {int(first[-1])} frames in all")
+    par = []
+    if not isinstance(iou, (tuple, list)) or len(iou) != 2:
+        raise ValueError(f"{what}: iou must be a pair of integers (numerator, denominator), got {iou}")
+    for name, v in (("iou[0]", iou[0]), ("iou[1]", iou[1]), ("max_gap", max_gap), ("predict", predict), ("max_tracks", max_tracks)):
+        if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError(f"{what}: {name} = {v} must be an integer")
+        par.append(int(v))
+    t0a = _np.asarray([t0] * S if _np.ndim(t0) == 0 else t0)
+    if t0a.dtype.kind not in "iu" or t0a.shape != (S,) or t0a.min() < -2 ** 31 or t0a.max() >= 2 ** 31:
+        raise ValueError(f"{what}: t0 must be an integer, or one per video, got {t0}")
+    cat = (lambda x: x[0] if len(x) == 1 else torch.cat(x)) if lib_t is torch else (lambda x: x[0] if len(x) == 1 else _np.concatenate(x))
+    return cat(bl), cat(sl), one, S, K, _np.ascontiguousarray(first.astype(_np.int32)), _np.ascontiguousarray(t0a.astype(_np.int32)), par
+
+
+def _link_boxes_split(ids, tracks, stats, state, one, first):
+    """`link_boxes`' tables in the caller's form: one video without the leading axis, several with ids as one view per video."""
+    if one:
+        return ids, tracks[0], stats[0], state[0]
+    return [ids[first[s]:first[s + 1]] for s in range(len(first) - 1)], tracks, stats, state
+
+
+def link_boxes(boxes, stats, iou=(3, 10), max_gap: int = 2, predict: int = 1, max_tracks: int = 1024, state=None, t0=0, out=None):
+    """The boxes of successive frames linked into trajectories, on the device (fusg_link_boxes: one launch on the current stream,
+    one workgroup per video, nothing read back; csrc/track_boxes.h states the definition): a track is live while it was seen
+    within the last max_gap + 1 frames; its expected box is its last one, with predict = 1 moved on by its centre's velocity; in a
+    frame the pairs (live track, box) whose intersection over union is at least iou = (numerator, denominator) are matched best
+    first, ties to the smaller track id and then the smaller box index; a matched box takes its track's id, the others found new
+    tracks.  The defaults are tried on synthetic scenes only.
+    boxes, stats: `foreground_boxes`' int32 [T, K, 4] and [T, 4] of ONE video's successive frames, or a list of such pairs' halves
+    for several videos (ragged, the same K, at most 64).  t0: the frame index of the first frame (one for all or one per video).
+    state: None to start the videos, or the state an earlier call returned to go on after its last frame (then pass that call's
+    tracks in out too: the rows of tracks that have died are not written again).  out = (ids [frames, K], tracks [S, max_tracks,
+    4], stats [S, 4]) to write into.
+    -> (ids int32 [T, K], -1 where there is no box or none could be given; tracks int32 [max_tracks, 4] = (first_t, last_t, hits,
+    0); stats int32 [4] = `LINK_BOXES_STATS`, flags `LINK_BOXES_*`; state int32 [`LINK_BOXES_STATE_WORDS`]) on the device - for a
+    list, ids is a list of views and the others gain a leading axis S."""
+    what = "link_boxes"
+    b, st, one, S, K, first, t0a, par = _link_boxes_args(boxes, stats, iou, max_gap, predict, max_tracks, t0, torch, what)
+    dev = b.device
+    _require_gpu(b, "boxes")
+    if st.device != dev:
+        raise ValueError(f"{what}: stats is on {st.device}, boxes on {dev}")
+    N, F = par[4], int(first[-1])
+    if not 1 <= N <= 2 ** 20:
+        raise ValueError(f"{what}: max_tracks = {N} (1..{2 ** 20})")
+    shapes = ((F, K), (S, N, 4), (S, 4))
+    ok = lambda o, s: torch.is_tensor(o) and o.dtype == torch.int32 and tuple(o.shape) == s and o.is_contiguous() and o.device == dev  # noqa: E731
+    if out is not None and not all(ok(o, s) for o, s in zip(out, shapes)):
+        raise ValueError(f"{what}: out must be contiguous int32 tensors of {shapes} on {dev}")
+    if state is not None and not ok(state, (S, LINK_BOXES_STATE_WORDS)) and not (one and ok(state, (LINK_BOXES_STATE_WORDS,))):
+        raise ValueError(f"{what}: state must be a contiguous int32 tensor of {(S, LINK_BOXES_STATE_WORDS)} on {dev}")
+    with torch.cuda.device(dev):
+        if state is None:
+            state = torch.zeros((S, LINK_BOXES_STATE_WORDS), dtype=torch.int32, device=dev)
+        ids, tracks, ost = out if out is not None else (torch.empty(shapes[0], dtype=torch.int32, device=dev),
+                                                        torch.zeros(shapes[1], dtype=torch.int32, device=dev),
+                                                        torch.empty(shapes[2], dtype=torch.int32, device=dev))
+        L.check(L.lib().fusg_link_boxes(b.contiguous().data_ptr(), st.contiguous().data_ptr(), first.ctypes.data, t0a.ctypes.data, S, K, *par,
+                                        state.data_ptr(), ids.data_ptr(), tracks.data_ptr(), ost.data_ptr(), stream_ptr()), what)
+        if RECORDER is not None:
+            RECORDER.keep.extend([b, st, state])
+    return _link_boxes_split(ids, tracks, ost, state.view(S, -1), one, first)
+
+
+def link_boxes_host(boxes, stats, iou=(3, 10), max_gap: int = 2, predict: int = 1, max_tracks: int = 1024, state=None, t0=0, out=None):
+    """`link_boxes` on the CPU by the same code (fusg_link_boxes_host; no GPU needed): int32 numpy tables in and out.  A state that
+    is passed in is updated in place."""
+    what = "link_boxes_host"
+    as_np = lambda x: [_np.asarray(v) for v in x] if isinstance(x, (list, tuple)) else _np.asarray(x)  # noqa: E731
+    b, st, one, S, K, first, t0a, par = _link_boxes_args(as_np(boxes), as_np(stats), iou, max_gap, predict, max_tracks, t0, _np, what)
+    N, F = par[4], int(first[-1])
+    if not 1 <= N <= 2 ** 20:
+        raise ValueError(f"{what}: max_tracks = {N} (1..{2 ** 20})")
+    shapes = ((F, K), (S, N, 4), (S, 4))
+    ok = lambda o, s: isinstance(o, _np.ndarray) and o.dtype == _np.int32 and o.shape == s and o.flags.c_contiguous  # noqa: E731
+    if out is not None and not all(ok(o, s) for o, s in zip(out, shapes)):
+        raise ValueError(f"{what}: out must be contiguous int32 arrays of {shapes}")
+    if state is not None and not ok(state, (S, LINK_BOXES_STATE_WORDS)) and not (one and ok(state, (LINK_BOXES_STATE_WORDS,))):
+        raise ValueError(f"{what}: state must be a contiguous int32 array of {(S, LINK_BOXES_STATE_WORDS)}")
+    if state is None:
+        state = _np.zeros((S, LINK_BOXES_STATE_WORDS), dtype=_np.int32)
+    ids, tracks, ost = out if out is not None else (_np.zeros(shapes[0], dtype=_np.int32), _np.zeros(shapes[1], dtype=_np.int32),
+                                                    _np.zeros(shapes[2], dtype=_np.int32))
+    b, st = _np.ascontiguousarray(b), _np.ascontiguousarray(st)
+    L.check(L.lib().fusg_link_boxes_host(b.ctypes.data, st.ctypes.data, first.ctypes.data, t0a.ctypes.data, S, K, *par, state.ctypes.data,
+                                         ids.ctypes.data, tracks.ctypes.data, ost.ctypes.data), what)
+    return _link_boxes_split(ids, tracks, ost, state.reshape(S, -1), one, first)
+
+
+# ---------------------------------------------------------------------------------------------
 # profiler hooks (bench.py roofline leg)
 # ---------------------------------------------------------------------------------------------
 def prof_enable(on: bool) -> None:

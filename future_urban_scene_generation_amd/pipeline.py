@@ -1797,8 +1797,8 @@ class VehiclePipeline:
         A vehicle is a 4-connected blob of grid cells in which the frame differs from `background` (uint8 [H, W, 3] on the device,
         e.g. `estimate_background`'s, or one per scene) - `ops.foreground_boxes`, two launches per 64 scenes, and ONE `ops.d2h`
         for all of them (params: thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, max_boxes, roi - defaults tried on
-        synthetic scenes only).  Boxes are per frame: nothing links them across frames, and the read-back is the only way the
-        boxes reach `foreground_inpaint`.  Nothing is put into the scenes."""
+        synthetic scenes only).  Boxes are per frame (`track_vehicles` links them across frames), and the read-back is the only way
+        the boxes reach `foreground_inpaint`.  Nothing is put into the scenes."""
         from . import ops
         frames = [s["frame"] for s in scenes]
         if not frames:
@@ -1846,6 +1846,84 @@ class VehiclePipeline:
             found = [d["bboxes"] for d in self.detect_vehicles(sampled, bg, **params)]
             bg, count = ops.background_median(frames, [b - np.asarray([0, 0, 1, 1]) for b in found], margin=margin, min_valid=mv)   # inclusive ends
         return {"background": bg, "count": count, "frames": idx, "min_valid": mv, "bboxes": found}
+
+    def track_vehicles(self, scenes, background, iou=(3, 10), max_gap: int = 2, predict: int = 1, max_tracks: int = 1024,
+                       min_hits: int = 3, **params):
+        """A tracker's file without a tracker: the vehicles of a video's successive frames with an identity that lasts.  scenes:
+        the video's scenes in frame order (scene f is frame f), or a list of such lists for several cameras; background: uint8
+        [H, W, 3] on the device (e.g. `bootstrap_background`'s), one per camera for several.  Per window of at most 64 frames
+        `ops.foreground_boxes` finds each camera's boxes (params: thr, cell, ..., max_boxes, roi) and ONE `ops.link_boxes` launch
+        - a workgroup per camera, the state carried from window to window - gives them track ids (iou, max_gap, predict,
+        max_tracks), all on the stream; ONE `ops.d2h` at the end reads everything back.  Returns, per camera (a dict for one
+        video, a list of dicts for a list of videos):
+          'trajectories' float64 [R, 6] = (frame, id, x, y, w, h), the rows `parse_tracking_files` returns, ordered by frame and
+                         then detection, of the tracks with at least min_hits observations;
+          'scenes'       per scene {'bboxes' int64 [V, 4] half-open (x0, y0, x1, y1), 'ids' int64 [V]} of those rows, for the caller
+                         to assign;
+          'boxes', 'ids', 'tracks', 'stats', 'box_stats': the raw tables - int32 [T, K, 4], [T, K], [max_tracks, 4] = (first_t,
+                         last_t, hits, 0), [4] = `ops.LINK_BOXES_STATS` and the detector's [T, 4].
+        The defaults are tried on synthetic scenes only.  Nothing is put into the scenes."""
+        import numpy as np
+
+        from . import ops
+        one = len(scenes) == 0 or isinstance(scenes[0], dict)
+        videos = [scenes] if one else list(scenes)
+        bgs = [background] if one else list(background)
+        if len(bgs) != len(videos):
+            raise ValueError(f"track_vehicles: {len(bgs)} backgrounds for {len(videos)} videos")
+        S, K, N, W = len(videos), int(params.get("max_boxes", ops.FOREGROUND_BOXES_MAX)), int(max_tracks), ops.BACKGROUND_MAX_FRAMES
+        lens = [len(v) for v in videos]
+        if max(lens) == 0:
+            empty = [{"trajectories": np.zeros((0, 6)), "scenes": [], "boxes": np.zeros((0, K, 4), np.int32), "ids": np.zeros((0, K), np.int32),
+                      "tracks": np.zeros((N, 4), np.int32), "stats": np.zeros((4,), np.int32), "box_stats": np.zeros((0, 4), np.int32)} for _ in videos]
+            return empty[0] if one else empty
+        dev = bgs[0].device
+        state = tracks = ost = None
+        parts = []                                                 # per window and camera: [frames, 6 K + 4 ... ] rows
+        for a in range(0, max(lens), W):
+            wb, ws = [], []
+            for s, v in enumerate(videos):
+                b = min(len(v), a + W)
+                if b > a:
+                    boxes, _, stats = ops.foreground_boxes([sc["frame"] for sc in v[a:b]], bgs[s], **params)
+                else:
+                    boxes, stats = torch.zeros((0, K, 4), dtype=torch.int32, device=dev), torch.zeros((0, 4), dtype=torch.int32, device=dev)
+                wb.append(boxes)
+                ws.append(stats)
+            if state is None:
+                tracks = torch.zeros((S, N, 4), dtype=torch.int32, device=dev)
+                ost = torch.zeros((S, 4), dtype=torch.int32, device=dev)
+            ids = torch.empty((sum(int(x.shape[0]) for x in wb), K), dtype=torch.int32, device=dev)
+            idl, tracks, ost, state = ops.link_boxes(wb, ws, iou=iou, max_gap=max_gap, predict=predict, max_tracks=N, state=state, t0=a,
+                                                     out=(ids, tracks, ost))
+            parts.append([torch.cat([x.reshape(x.shape[0], 4 * K), i, y], dim=1) for x, i, y in zip(wb, idl, ws)])
+        flat = torch.cat([p.reshape(-1) for w in parts for p in w] + [tracks.reshape(-1), ost.reshape(-1)])
+        host = ops.d2h(flat)
+        rows, pos = [[] for _ in videos], 0
+        for w in parts:
+            for s, p in enumerate(w):
+                rows[s].append(host[pos:pos + p.numel()].reshape(tuple(p.shape)))
+                pos += p.numel()
+        tr = host[pos:pos + S * N * 4].reshape(S, N, 4)
+        st = host[pos + S * N * 4:].reshape(S, 4)
+        out = [self._tracked_rows(np.concatenate(rows[s]), tr[s], st[s], K, int(min_hits)) for s in range(S)]
+        return out[0] if one else out
+
+    @staticmethod
+    def _tracked_rows(table, tracks, stats, K: int, min_hits: int) -> Dict:
+        """`track_vehicles`' read-back of one camera, int32 [T, 5 K + 4] = per frame K boxes, K ids and the detector's stats -> its
+        dict: the rows of the tracks with at least min_hits observations, in the reference's (frame, id, x, y, w, h) form."""
+        import numpy as np
+        T = table.shape[0]
+        boxes, ids, box_stats = table[:, :4 * K].reshape(T, K, 4), table[:, 4 * K:5 * K], table[:, 5 * K:]
+        keep = (ids >= 0) & (tracks[np.maximum(ids, 0), 2] >= min_hits)
+        f, k = np.nonzero(keep)                                    # row-major: by frame, then detection
+        b = boxes[f, k].astype(np.float64)
+        traj = np.stack([f.astype(np.float64), ids[f, k].astype(np.float64), b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], axis=1) \
+            if len(f) else np.zeros((0, 6))
+        per = [{"bboxes": boxes[t][keep[t]].astype(np.int64), "ids": ids[t][keep[t]].astype(np.int64)} for t in range(T)]
+        return {"trajectories": traj, "scenes": per, "boxes": boxes.copy(), "ids": ids.copy(), "tracks": tracks.copy(), "stats": stats.copy(),
+                "box_stats": box_stats.copy()}
 
     @staticmethod
     def _composites(paste, out: Dict, box_geom=None) -> Dict:

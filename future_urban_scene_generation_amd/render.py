@@ -941,12 +941,103 @@ def first_geometry_batch_device(bank: CadBank, frames: Sequence[torch.Tensor], o
 
 
 # ---------------------------------------------------------------------------------------------- trajectories
+def tracking_box(row, shape, scale=None, img_scale=1.0) -> Tuple[int, int, int, int]:
+    """The reference's box of a tracker's row (frame, id, x, y, w, h) as it is used everywhere a row becomes pixels
+    (utils/bounding_box.py through GUI/app_interface.py:194 and utils/gps_utils.py:28): x, y, w, h times img_scale, each cut to an
+    integer towards zero; x1 = x0 + w; with a scale, width and height grow by int(size * scale - size), half of it (floored) on
+    each side; then x is clipped to [0, shape[0] - 1] and y to [0, shape[1] - 1] - shape is (width, height), as the reference
+    passes it.  -> (x0, y0, x1, y1), Python integers."""
+    x, y, w, h = (np.asarray(row, np.float64)[2:6] * img_scale).tolist()
+    x0, y0 = int(x), int(y)
+    x1, y1 = x0 + int(w), y0 + int(h)
+    if scale is not None:
+        if not scale > 0.0:
+            raise ValueError(f"tracking_box: scale = {scale} must be positive")
+        dw = int((x1 - x0) * scale - (x1 - x0))
+        x0, x1 = x0 - dw // 2, x1 + dw // 2
+        dh = int((y1 - y0) * scale - (y1 - y0))
+        y0, y1 = y0 - dh // 2, y1 + dh // 2
+    return max(0, x0), max(0, y0), min(shape[0] - 1, x1), min(shape[1] - 1, y1)
+
+
+def _geodesic_m(p1, p2) -> float:
+    """utils/gps_utils.py:7-16: the haversine distance of two (latitude, longitude) points in metres, Earth radius 6371 km."""
+    dlon = np.radians(p1[1]) - np.radians(p2[1])
+    dlat = np.radians(p1[0]) - np.radians(p2[0])
+    a = np.sin(dlat / 2) ** 2 + np.cos(np.radians(p2[0])) * np.cos(np.radians(p1[0])) * np.sin(dlon / 2) ** 2
+    return 6371.0 * (2 * np.arctan2(np.sqrt(a), np.sqrt(1 - a))) * 1000
+
+
+def trajectories_to_meters(car_track, inv_homography, scale, shape, img_scale) -> np.ndarray:
+    """utils/gps_utils.py:19-57 in its 'traj' mode: one vehicle's tracker rows [n, 6] -> its positions in metres [n, 2], float64,
+    the same operations in the same order.  Per row the middle of the lower edge of `tracking_box` (x0 + (x1 - x0) // 2, y1) goes
+    through the inverse homography to (latitude, longitude); the metres are each coordinate's share of the trajectory's own extent
+    times the geodesic length of that extent's side.  A trajectory without extent in a coordinate divides zero by zero there: the
+    values come back non-finite, as the reference's do."""
+    H = np.asarray(inv_homography)
+    gps = []
+    for row in np.asarray(car_track):
+        x0, _, x1, y1 = tracking_box(row, shape, scale, img_scale)
+        mid = np.asarray([[x0 + (x1 - x0) // 2, y1, 1]])
+        proj = (H @ mid.transpose()).transpose()[0]
+        proj = proj / proj[2]
+        gps.append(np.asarray(proj[:-1]))
+    gps = np.asarray(gps)
+    lo = [np.min(gps[:, 0]), np.min(gps[:, 1])]
+    hi = [np.max(gps[:, 0]), np.max(gps[:, 1])]
+    side = [_geodesic_m(hi, [lo[0], hi[1]]), _geodesic_m(hi, [hi[0], lo[1]])]
+    meters = np.zeros(gps.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        meters[:, 0] = ((gps[:, 0] - lo[0]) / (hi[0] - lo[0])) * side[0]
+        meters[:, 1] = ((gps[:, 1] - lo[1]) / (hi[1] - lo[1])) * side[1]
+    return meters
+
+
+def future_trajectories(trajectories, frame_id, ids, stride: int = 2, horizon: int = 5) -> List[np.ndarray]:
+    """GUI/app_interface.py:225-234: per selected id the rows of that vehicle from frame_id on, every stride-th of them up to
+    horizon future ones (rows 0, 2, ..., 10 of the vehicle's remaining rows: positions in its own table, so a vehicle the tracker
+    lost for a frame is not re-timed) -> one [n, 6] array per id, n <= horizon + 1, shorter where the track ends early."""
+    tr = np.asarray(trajectories, np.float64).reshape(-1, 6)
+    out = []
+    for i in ids:
+        rows = tr[np.bitwise_and(tr[:, 1] == i, tr[:, 0] >= frame_id)]
+        out.append(rows[0:stride * horizon + 1:stride])
+    return out
+
+
+def clip_from_trajectories(trajectories, frame_id, inv_homography, shape, bbox_scale=1.0, img_scale=1.0, stride: int = 2,
+                           horizon: int = 5) -> Dict:
+    """What a geometry-mode clip needs from a tracker's table (`VehiclePipeline.track_vehicles`' 'trajectories', or a parsed
+    tracking file) at frame_id: {'ids' int64 [V] and 'bboxes' int64 [V, 4] (`tracking_box`, x0, y0, x1, y1) of the vehicles in
+    that frame, in table order; 'steps': per future frame n = 1 .. the longest future, a list over the V vehicles of
+    `trajectory_steps`' (theta, tr) for `trajectories_to_meters` of the vehicle's `future_trajectories` rows, None where the
+    vehicle has no step n; 'rows': those rows per vehicle; 'skipped': the vehicles (positions in ids) with fewer than two rows or
+    metres that are not finite (no extent in a coordinate, e.g. a vehicle that stands), which have no steps at all}.  The scene
+    of future frame n takes scene['steps'] = the entries of steps[n - 1] of the vehicles it keeps."""
+    tr = np.asarray(trajectories, np.float64).reshape(-1, 6)
+    now = tr[tr[:, 0] == frame_id]
+    ids = now[:, 1].astype(np.int64)
+    bboxes = np.asarray([tracking_box(r, shape, bbox_scale, img_scale) for r in now], dtype=np.int64).reshape(-1, 4)
+    rows = future_trajectories(tr, frame_id, ids, stride, horizon)
+    per, skipped = [], []
+    for v, r in enumerate(rows):
+        m = trajectories_to_meters(r, inv_homography, bbox_scale, shape, img_scale) if len(r) >= 2 else None
+        if m is None or not np.all(np.isfinite(m)):
+            skipped.append(v)
+            per.append([])
+        else:
+            per.append(trajectory_steps(m))
+    n_future = max([len(p) for p in per], default=0)
+    steps = [[p[n] if n < len(p) else None for p in per] for n in range(n_future)]
+    return {"ids": ids, "bboxes": bboxes, "steps": steps, "rows": rows, "skipped": skipped}
+
+
 def trajectory_steps(meter_coords) -> List[Tuple[float, np.ndarray]]:
     """trajectory_inference.py:256-297: a vehicle's future positions in metres [N, 2] (row 0 = now) -> (theta, tr) per
     future step n = 1 .. N-1, for `v @ z_rot(theta) + tr` (:360-363).  theta = heading of the step relative to the mean
     heading of the first 19 steps; tr = (0, -distance, 0) @ z_rot(theta), or @ z_rot(0) where the turn is sharp (the
     reference's +-20 degree gates: the step's instant turn for interior steps, theta itself for the first and the last two).
-    `trajectories_to_meters` (dataset IO) is out of scope."""
+    `trajectories_to_meters` below gives the metres from a tracker's rows."""
     mc = np.asarray(meter_coords, np.float64).reshape(-1, 2)
     x_start, y_start = mc[0]
     theta_start = np.arctan2(np.mean(mc[1:20, 1] - y_start), np.mean(mc[1:20, 0] - x_start))

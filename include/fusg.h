@@ -1010,6 +1010,40 @@ int fusg_foreground_boxes_host(const void* const* frames, const void* const* bac
                                int32_t cell, int32_t min_count, int32_t open_r, int32_t close_r, int32_t min_area, int32_t min_w,
                                int32_t min_h, const int32_t* roi4, int32_t K, int32_t* boxes, int32_t* box_stats, int32_t* stats);
 
+/* ---- linking the boxes of successive frames into trajectories (a vehicle's identity across frames without a tracker's file;
+ * new entry points, FUSG_VERSION stays 118) */
+/* Per video s of S, on its own: the frames first[s] .. first[s + 1] - 1 of the tables, which have the absolute frame indices
+ * t0[s], t0[s] + 1, ...  Frame t holds clamp(stats[t][0], 0, K) detections boxes[t][k] = half-open (x0, y0, x1, y1):
+ * fusg_foreground_boxes_u8's boxes and stats as they are.  A track is live while t - last_t <= max_gap + 1; its expected box is
+ * its last box, with predict = 1 and two observations shifted by its centre's velocity (truncating division).  Within a frame the
+ * eligible pairs (intersection > 0 and intersection * iou_den >= iou_num * union) are matched best first, a tie going to the
+ * smaller track id and then the smaller detection index; a matched detection takes its track's id, the others found tracks with
+ * the next ids in detection order.  csrc/track_boxes.h states the definition step by step.
+ * boxes [frames][K][4], stats [frames][4], state [S][fusg_link_boxes_state_words()], ids [frames][K], tracks [S][max_tracks][4],
+ * out_stats [S][4]: DEVICE int32; first [S + 1] and t0 [S]: HOST int32, read before the call returns.
+ * ids: the track of each detection, -1 for the rows past the frame's detections, for a detection that is empty or leaves
+ * [0, 16384] (flag 1 BAD_BOX) and for one whose track could not be founded (2 TRACKS_FULL: max_tracks ids are used up;
+ * 4 LIVE_FULL: 128 tracks are live); written whole.  tracks: (first_t, last_t, hits, 0) per id, zeros from n_tracks on; rows
+ * of tracks that died in an earlier call on the same state are left as that call wrote them.  out_stats: n_tracks, n_live,
+ * n_linked (matched detections), flags - all since the state was zeroed.  state is read and written: zeros start a video, and
+ * successive calls that carry it (and tracks) give the bits of one call over all their frames.  A call with t0[s] at or below
+ * the last frame index the state has seen is refused on the device (flag 8 ORDER in out_stats, ids -1, nothing else touched),
+ * a state whose header is out of range likewise (16 BAD_STATE).
+ * Checked on the host before the launch (FUSG_ERR_INVALID): S 1..64, K 1..64, 0 < iou_num <= iou_den <= 1024, max_gap 0..255,
+ * predict 0 or 1, max_tracks 1..2^20, first[0] = 0 and not falling, t0 >= 0 with t0 + frames <= 2^30, no null pointer (boxes, stats
+ * and ids may be null when there is no frame at all).
+ * One launch, one workgroup per video, no atomics, integer arithmetic only; bit-identical to the host twin; recorded and
+ * replayed by a fusg_plan. */
+int fusg_link_boxes(const int32_t* boxes, const int32_t* stats, const int32_t* first, const int32_t* t0, int32_t S, int32_t K,
+                    int32_t iou_num, int32_t iou_den, int32_t max_gap, int32_t predict, int32_t max_tracks, int32_t* state,
+                    int32_t* ids, int32_t* tracks, int32_t* out_stats, void* stream);
+/* The same code on the CPU: every pointer is a HOST pointer, no GPU needed. */
+int fusg_link_boxes_host(const int32_t* boxes, const int32_t* stats, const int32_t* first, const int32_t* t0, int32_t S, int32_t K,
+                         int32_t iou_num, int32_t iou_den, int32_t max_gap, int32_t predict, int32_t max_tracks, int32_t* state,
+                         int32_t* ids, int32_t* tracks, int32_t* out_stats);
+/* int32 words of one video's state. */
+int32_t fusg_link_boxes_state_words(void);
+
 /* ---- recorded passes ------------------------------------------------------------------------ */
 /* A fusg_plan records the launch sequence of one pass (every fusg_* launch made by the recording thread between
  * fusg_plan_begin and fusg_plan_end, with its descriptors copied and its stream remembered; the calls also execute)
