@@ -21,12 +21,13 @@
 // frames past T never valid), so a lane holds them in registers.
 #pragma once
 #include <stdint.h>
-#include "resize.h"                                               // FUSG_HD
+#include "workgroup.h"
 
 namespace fusg {
 namespace bg {
 
-constexpr int MAX_T = 64, MAX_BOXES = 64, MAX_DIM = 32767, MAX_MARGIN = 32767;
+using wg::MAX_DIM;
+constexpr int MAX_T = 64, MAX_BOXES = 64, MAX_MARGIN = 32767;
 constexpr uint32_t ONES = 0x01010101u;
 
 FUSG_HD int bucket(int T) { return T <= 8 ? 8 : (T <= 16 ? 16 : (T <= 32 ? 32 : 64)); }

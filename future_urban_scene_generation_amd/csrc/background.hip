@@ -188,7 +188,7 @@ using namespace fusg;
 static int background_check(const void* const* frame_ptrs, int32_t T, int32_t H, int32_t W, const int32_t* boxes, const int32_t* box_offs,
                             int32_t margin, int32_t min_valid, uint8_t* bg_out, uint8_t* count, const char* what, BgK& k) {
     FUSG_CHECK(T >= 1 && T <= bg::MAX_T, "%s: T = %d frames (1..%d)", what, T, bg::MAX_T);
-    FUSG_CHECK(H >= 1 && W >= 1 && H <= bg::MAX_DIM && W <= bg::MAX_DIM, "%s: frames of %d x %d (H and W in 1..%d)", what, H, W, bg::MAX_DIM);
+    if (const int rc = wg::check_frame_size(H, W, what)) return rc;
     FUSG_CHECK(margin >= 0 && margin <= bg::MAX_MARGIN, "%s: margin = %d (0..%d)", what, margin, bg::MAX_MARGIN);
     FUSG_CHECK(min_valid >= 1 && min_valid <= T, "%s: min_valid = %d (1..T = %d)", what, min_valid, T);
     FUSG_CHECK(frame_ptrs && bg_out && count, "%s: frame_ptrs, bg or count is null", what);

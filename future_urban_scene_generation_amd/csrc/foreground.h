@@ -37,12 +37,13 @@
 // above it the same code runs on a scratch buffer of the caller's, PLANES * cap words per box.
 #pragma once
 #include <stdint.h>
-#include "resize.h"                                               // FUSG_HD
+#include "workgroup.h"
 
 namespace fusg {
 namespace fg {
 
-constexpr int MAX_THR = 254, MAX_OPEN = 3, MAX_CLOSE = 7, MAX_GROW = 15, MAX_DIM = 32767;
+using wg::MAX_DIM;
+constexpr int MAX_THR = 254, MAX_OPEN = 3, MAX_CLOSE = 7, MAX_GROW = 15;
 constexpr int PLANES = 2, THREADS = 256;
 constexpr long LDS_BUDGET = 32 * 1024;
 enum { FLAG_FALLBACK = 1, FLAG_BORDER = 2, FLAG_REFUSED = 4 };
@@ -162,8 +163,12 @@ FUSG_HD uint32_t fill(uint32_t g, uint32_t m) {
 }
 
 // one row of a flood sweep: pull from the rows above and below, fill along the row; true if the row changed.
-// mask(i, k): word k of row i of what the flood may enter.
-template <class Mask>
+// mask(i, k): word k of row i of what the flood may enter; it must not change during the flood.
+// CLOSED is the caller's word that every state word is closed under fill inside its mask word when the flood starts (a sweep
+// keeps it so: it only ever stores fill(g, m)).  Then a word whose neighbours bring nothing new (g & m == old) would be filled
+// to itself, and the fill is made only behind the test, at the rim of what has been reached: the same bits, sweep for sweep.
+// With a seed that is NOT closed, CLOSED = true ends the flood at the seed - wrong, and silently fast.
+template <bool CLOSED, class Mask>
 FUSG_HD bool flood_row(uint32_t* st, int i, int h, int nw, Mask mask) {
     uint32_t* row = st + i * nw;
     bool changed = false;
@@ -173,22 +178,23 @@ FUSG_HD bool flood_row(uint32_t* st, int i, int h, int nw, Mask mask) {
         uint32_t g = old | carry;
         if (i > 0) g |= st[(i - 1) * nw + k];
         if (i + 1 < h) g |= st[(i + 1) * nw + k];
-        g = fill(g & m, m);
-        if (g != old) { row[k] = g; changed = true; }
+        g &= m;
+        if (!CLOSED) g = fill(g, m);
+        if (g != old) { if (CLOSED) g = fill(g, m); row[k] = g; changed = true; }
         carry = g >> 31;
     }
     carry = 0u;
     for (int k = nw - 1; k >= 0; --k) {
         const uint32_t m = mask(i, k), old = row[k];
-        const uint32_t g = fill((old | carry) & m, m);
-        if (g != old) { row[k] = g; changed = true; }
+        uint32_t g = (old | carry) & m;
+        if (!CLOSED) g = fill(g, m);
+        if (g != old) { if (CLOSED) g = fill(g, m); row[k] = g; changed = true; }
         carry = (g & 1u) << 31;
     }
     return changed;
 }
 
-// Ex: who runs it.  tid() of nth() take part; sync() is a barrier between them, any(p) a vote and sum(v) a total over all of
-// them (both barriers too), threshold(bx, thr, A) fills plane A and ends with a barrier.  The host is one of one.
+// Ex: who runs it (workgroup.h).
 template <class Ex>
 FUSG_HD void square(Ex& ex, uint32_t* A, uint32_t* B, int h, int nw, int w, int r, bool erode, bool one) {
     if (r <= 0) return;
@@ -205,22 +211,30 @@ FUSG_HD void square(Ex& ex, uint32_t* A, uint32_t* B, int h, int nw, int w, int 
     ex.sync();
 }
 
-template <class Ex, class Mask>
+template <bool CLOSED, class Ex, class Mask>
 FUSG_HD void flood(Ex& ex, uint32_t* st, int h, int nw, Mask mask) {
     bool changed;
     do {
         changed = false;
-        for (int i = 2 * ex.tid(); i < h; i += 2 * ex.nth()) changed |= flood_row(st, i, h, nw, mask);
+        for (int i = 2 * ex.tid(); i < h; i += 2 * ex.nth()) changed |= flood_row<CLOSED>(st, i, h, nw, mask);
         ex.sync();
-        for (int i = 2 * ex.tid() + 1; i < h; i += 2 * ex.nth()) changed |= flood_row(st, i, h, nw, mask);
+        for (int i = 2 * ex.tid() + 1; i < h; i += 2 * ex.nth()) changed |= flood_row<CLOSED>(st, i, h, nw, mask);
     } while (ex.any(changed));
+}
+
+// plane A = F0: the only pass that touches the images
+template <class Ex>
+FUSG_HD void threshold(Ex& ex, const Box& bx, int thr, uint32_t* A) {
+    ex.plane(A, bx.h, bx.w, words(bx.w), false,
+             [&](int i, int j) { return over(bx.frame, bx.bgd, (long)(bx.y0 + i) * bx.W + bx.x0 + j, thr); },
+             [](bool p) { return p; }, [](bool) {});
 }
 
 template <class Ex>
 FUSG_HD void run_box(Ex& ex, const Box& bx, const Params& P, uint32_t* A, uint32_t* B) {
     const int h = bx.h, w = bx.w, nw = words(w), n = h * nw, t = ex.tid(), T = ex.nth();
     int flags = 0;
-    ex.threshold(bx, P.thr, A);
+    threshold(ex, bx, P.thr, A);
     int cnt = 0;
     for (int e = t; e < n; e += T) cnt += popc(A[e]);
     const int n_f0 = ex.sum(cnt);
@@ -237,13 +251,14 @@ FUSG_HD void run_box(Ex& ex, const Box& bx, const Params& P, uint32_t* A, uint32
     }
     const int n_seed = ex.sum(cnt);
     if (n_seed > 0) {
-        flood(ex, B, h, nw, [A, nw](int i, int k) { return A[i * nw + k]; });
+        // neither seed is closed under fill: F2 and the core here, the border pixels outside R below
+        flood<false>(ex, B, h, nw, [A, nw](int i, int k) { return A[i * nw + k]; });
         for (int e = t; e < n; e += T) {
             const int i = e / nw, k = e - i * nw;
             A[e] = ~B[e] & border(i, k, h, w);
         }
         ex.sync();
-        flood(ex, A, h, nw, [B, nw, w](int i, int k) { return ~B[i * nw + k] & span(k, 0, w); });
+        flood<false>(ex, A, h, nw, [B, nw, w](int i, int k) { return ~B[i * nw + k] & span(k, 0, w); });
         for (int e = t; e < n; e += T) {
             const int i = e / nw;
             A[e] = ~A[e] & span(e - i * nw, 0, w);
@@ -278,6 +293,15 @@ FUSG_HD void run_box(Ex& ex, const Box& bx, const Params& P, uint32_t* A, uint32
         bx.stats[2] = n_mask;
         bx.stats[3] = flags;
     }
+}
+
+// the ranges the masks and the boxes share, on the host, in the words of both
+inline int check_ranges(int H, int W, int thr, int open_r, int close_r, const char* what) {
+    if (const int rc = wg::check_frame_size(H, W, what)) return rc;
+    FUSG_CHECK(thr >= 0 && thr <= MAX_THR, "%s: thr = %d (0..%d)", what, thr, MAX_THR);
+    FUSG_CHECK(open_r >= 0 && open_r <= MAX_OPEN, "%s: open_r = %d (0..%d)", what, open_r, MAX_OPEN);
+    FUSG_CHECK(close_r >= 0 && close_r <= MAX_CLOSE, "%s: close_r = %d (0..%d)", what, close_r, MAX_CLOSE);
+    return FUSG_OK;
 }
 
 }  // namespace fg

@@ -5,7 +5,7 @@
 //                 consecutive pixels of a box row (3 bytes each from frame and background, consecutive lanes, consecutive
 //                 addresses) and its ballot is two words of plane A.  Everything after that works on the two bit planes - in LDS
 //                 when fg::in_lds(max_box) says so (dynamic LDS of exactly that size), else in the caller's scratch - and the
-//                 last pass writes one byte per box pixel.  Votes are __syncthreads_or, totals a shuffle and four LDS words.
+//                 last pass writes one byte per box pixel.  The workgroup is workgroup.h's wg::DevRed, the host twin wg::Host.
 //   erase         two launches: dst = frame (dwords where the pointers allow it), then 16 workgroups per box put the
 //                 background's three bytes wherever the box's mask byte is non-zero.  Overlapping boxes store equal bytes.
 // No atomics.  A refused box (foreground.h: accept) is flagged by thread 0 and nothing of it is read or written.
@@ -50,63 +50,6 @@ FUSG_HD bool fg_box(const FgK& k, int b, fg::Box& bx) {
     return true;
 }
 
-struct FgDev {
-    int* red;                                                     // LDS int [4]
-    __device__ int tid() const { return (int)threadIdx.x; }
-    __device__ int nth() const { return fg::THREADS; }
-    __device__ void sync() const { __syncthreads(); }
-    __device__ bool any(bool p) const { return __syncthreads_or(p ? 1 : 0) != 0; }
-    __device__ int sum(int v) const {
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        const int s = red[0] + red[1] + red[2] + red[3];
-        __syncthreads();
-        return s;
-    }
-    __device__ void threshold(const fg::Box& bx, int thr, uint32_t* A) const {
-        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        const int nw = fg::words(bx.w), chunks = (bx.w + 63) >> 6, items = bx.h * chunks;
-        constexpr int WAVES = fg::THREADS / 64, U = 8;            // U items a turn: their loads are all issued before the first ballot
-        for (int it0 = wave; it0 < items; it0 += WAVES * U) {
-            bool p[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int it = it0 + WAVES * u, i = it / chunks, j = (it - i * chunks) * 64 + lane;
-                p[u] = it < items && j < bx.w && fg::over(bx.frame, bx.bgd, (long)(bx.y0 + i) * bx.W + bx.x0 + j, thr);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int it = it0 + WAVES * u, i = it / chunks, c = it - i * chunks;
-                const unsigned long long bal = __ballot(p[u]);
-                if (lane == 0 && it < items) {
-                    A[i * nw + 2 * c] = (uint32_t)bal;
-                    if (2 * c + 1 < nw) A[i * nw + 2 * c + 1] = (uint32_t)(bal >> 32);
-                }
-            }
-        }
-        __syncthreads();
-    }
-};
-
-struct FgHost {
-    int tid() const { return 0; }
-    int nth() const { return 1; }
-    void sync() const {}
-    bool any(bool p) const { return p; }
-    int sum(int v) const { return v; }
-    void threshold(const fg::Box& bx, int thr, uint32_t* A) const {
-        const int nw = fg::words(bx.w);
-        for (int i = 0; i < bx.h; ++i)
-            for (int k = 0; k < nw; ++k) {
-                uint32_t v = 0u;
-                for (int j = 32 * k; j < bx.w && j < 32 * k + 32; ++j)
-                    v |= (uint32_t)fg::over(bx.frame, bx.bgd, (long)(bx.y0 + i) * bx.W + bx.x0 + j, thr) << (j & 31);
-                A[i * nw + k] = v;
-            }
-    }
-};
-
 template <bool LDS>
 __global__ __launch_bounds__(fg::THREADS) void foreground_masks_kernel(const FgK k) {
     extern __shared__ uint32_t s_planes[];
@@ -122,7 +65,7 @@ __global__ __launch_bounds__(fg::THREADS) void foreground_masks_kernel(const FgK
     }
     const long cap = fg::plane_words(k.max_h, k.max_w);
     uint32_t* A = LDS ? s_planes : k.scratch + (long)b * fg::PLANES * cap;
-    FgDev ex{s_red};
+    wg::DevRed<fg::THREADS> ex{{}, s_red};
     fg::run_box(ex, bx, k.P, A, A + cap);
 }
 
@@ -138,7 +81,7 @@ static int foreground_launch(FgK k, void* stream) {
 }
 
 static void foreground_host(const FgK& k) {
-    FgHost ex;
+    wg::Host ex;
     for (int b = 0; b < k.n; ++b) {
         fg::Box bx;
         if (!fg_box(k, b, bx)) {
@@ -225,10 +168,7 @@ static int foreground_check(const void* const* frames, const void* const* backgr
                             int32_t thr, int32_t open_r, int32_t close_r, int32_t grow, int32_t fallback, int32_t max_box_h,
                             int32_t max_box_w, uint8_t* mask, int64_t mask_len, int32_t* stats, const char* what, FgK& k) {
     FUSG_CHECK(n >= 0, "%s: n = %d boxes", what, n);
-    FUSG_CHECK(H >= 1 && W >= 1 && H <= fg::MAX_DIM && W <= fg::MAX_DIM, "%s: frames of %d x %d (H and W in 1..%d)", what, H, W, fg::MAX_DIM);
-    FUSG_CHECK(thr >= 0 && thr <= fg::MAX_THR, "%s: thr = %d (0..%d)", what, thr, fg::MAX_THR);
-    FUSG_CHECK(open_r >= 0 && open_r <= fg::MAX_OPEN, "%s: open_r = %d (0..%d)", what, open_r, fg::MAX_OPEN);
-    FUSG_CHECK(close_r >= 0 && close_r <= fg::MAX_CLOSE, "%s: close_r = %d (0..%d)", what, close_r, fg::MAX_CLOSE);
+    if (const int rc = fg::check_ranges(H, W, thr, open_r, close_r, what)) return rc;
     FUSG_CHECK(grow >= 0 && grow <= fg::MAX_GROW, "%s: grow = %d (0..%d)", what, grow, fg::MAX_GROW);
     FUSG_CHECK(max_box_h >= 0 && max_box_w >= 0 && max_box_h <= fg::MAX_DIM && max_box_w <= fg::MAX_DIM,
                "%s: max_box = %d x %d (0..%d)", what, max_box_h, max_box_w, fg::MAX_DIM);
@@ -243,11 +183,9 @@ static int foreground_check(const void* const* frames, const void* const* backgr
     FUSG_CHECK(frame_rows[0] == 0, "%s: frame_rows starts at %d, not at 0", what, frame_rows[0]);
     for (int f = 0; f < n_frames; ++f) {
         FUSG_CHECK(frame_rows[f + 1] >= frame_rows[f], "%s: frame_rows decreases at frame %d", what, f);
-        FUSG_CHECK(frames[f] != nullptr && backgrounds[f] != nullptr, "%s: frame or background %d is null", what, f);
-        k.frames[f] = (const unsigned char*)frames[f];
-        k.bgs[f] = (const unsigned char*)backgrounds[f];
         k.rows[f + 1] = frame_rows[f + 1];
     }
+    if (const int rc = wg::check_frame_pairs(frames, backgrounds, n_frames, k.frames, k.bgs, what)) return rc;
     FUSG_CHECK(frame_rows[n_frames] == n, "%s: frame_rows ends at %d, not at the %d boxes", what, frame_rows[n_frames], n);
     for (int f = n_frames; f < FUSG_MAX_FRAMES; ++f) k.rows[f + 1] = n;
     k.boxes = boxes; k.cores = cores; k.offs = offsets; k.mask = mask; k.mask_len = (long)mask_len; k.stats = stats;
@@ -294,7 +232,7 @@ extern "C" int fusg_foreground_masks_host(const void* const* frames, const void*
 static int erase_check(const uint8_t* frame, const uint8_t* background, int32_t H, int32_t W, const uint8_t* mask, int64_t mask_len,
                        const int64_t* offsets, const int32_t* boxes, int32_t n, uint8_t* dst, const char* what, EraseK& k) {
     FUSG_CHECK(n >= 0, "%s: n = %d boxes", what, n);
-    FUSG_CHECK(H >= 1 && W >= 1 && H <= fg::MAX_DIM && W <= fg::MAX_DIM, "%s: frames of %d x %d (H and W in 1..%d)", what, H, W, fg::MAX_DIM);
+    if (const int rc = wg::check_frame_size(H, W, what)) return rc;
     FUSG_CHECK(frame && background && dst, "%s: frame, background or dst is null", what);
     FUSG_CHECK(mask_len >= 0 && (mask != nullptr || mask_len == 0), "%s: a mask buffer of %lld bytes at %p", what, (long long)mask_len,
                (const void*)mask);

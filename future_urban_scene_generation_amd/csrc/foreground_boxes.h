@@ -25,9 +25,9 @@
 // extents in 4 bits each; cell <= 16) in a scratch table [T][gh][gw] that it writes whole.  The LABEL pass works on that table
 // alone: G0 as a bit plane (foreground.h's layout: one bit per cell, 32 per word, row stride words(gw), the bits past gw kept 0),
 // the four fg::square passes A -> B -> A, and then, while plane A - what is left of G2 - has a bit: its first bit in raster
-// order seeds plane B, a flood (fg::flood's sweeps, see flood_row below) grows B inside A, the records of B's cells are reduced
-// to (n_cells, area, extents), B is taken out of A and cleared, and the component is emitted or skipped.  TWO planes carry
-// everything: the morphology's second plane is free again when the labelling starts.
+// order seeds plane B, a flood (fg::flood<true>: the seed word is stored filled) grows B inside A, the records of B's cells are
+// reduced to (n_cells, area, extents), B is taken out of A and cleared, and the component is emitted or skipped.  TWO planes
+// carry everything: the morphology's second plane is free again when the labelling starts.
 // Why device and host agree bit for bit: the records and the morphology are pure functions of a cell's pixels and of a cell's
 // neighbourhood; a flood ends at the cells of A that are 4-connected to the seed, whatever the order of the sweeps (foreground.h);
 // the first remaining bit in raster order belongs to the component whose first cell it is, so the order of the components is
@@ -102,56 +102,22 @@ struct Acc {
     }
 };
 
-// fg::flood_row and fg::flood with the fills left out where they cannot add a bit.  Every word of the state is closed under
-// fg::fill inside its mask word - the seed is stored filled, and a sweep only ever stores fill(g, m) - so a word whose
-// neighbours bring nothing new (g & m == old) would be filled to itself: the same bits as fg::flood, sweep for sweep, with a
-// fill only at the rim of what has been reached.  The mask must not change during the flood.
-template <class Mask>
-FUSG_HD bool flood_row(uint32_t* st, int i, int h, int nw, Mask mask) {
-    uint32_t* row = st + i * nw;
-    bool changed = false;
-    uint32_t carry = 0u;
-    for (int k = 0; k < nw; ++k) {
-        const uint32_t m = mask(i, k), old = row[k];
-        uint32_t g = old | carry;
-        if (i > 0) g |= st[(i - 1) * nw + k];
-        if (i + 1 < h) g |= st[(i + 1) * nw + k];
-        g &= m;
-        if (g != old) { g = fg::fill(g, m); row[k] = g; changed = true; }
-        carry = g >> 31;
-    }
-    carry = 0u;
-    for (int k = nw - 1; k >= 0; --k) {
-        const uint32_t m = mask(i, k), old = row[k];
-        uint32_t g = (old | carry) & m;
-        if (g != old) { g = fg::fill(g, m); row[k] = g; changed = true; }
-        carry = (g & 1u) << 31;
-    }
-    return changed;
+// plane A = G0 from the frame's records; returns this member's share of the sum of cnt
+template <class Ex>
+FUSG_HD int grid0(Ex& ex, const uint32_t* rec, int gh, int gw, int min_count, uint32_t* A) {
+    int np = 0;
+    ex.plane(A, gh, gw, fg::words(gw), 0, [&](int i, int j) { return rec_cnt(rec[(long)i * gw + j]); },
+             [&](int cnt) { return cnt >= min_count; }, [&](int cnt) { np += cnt; });
+    return np;
 }
 
-template <class Ex, class Mask>
-FUSG_HD void flood(Ex& ex, uint32_t* st, int h, int nw, Mask mask) {
-    bool changed;
-    do {
-        changed = false;
-        for (int i = 2 * ex.tid(); i < h; i += 2 * ex.nth()) changed |= flood_row(st, i, h, nw, mask);
-        ex.sync();
-        for (int i = 2 * ex.tid() + 1; i < h; i += 2 * ex.nth()) changed |= flood_row(st, i, h, nw, mask);
-    } while (ex.any(changed));
-}
-
-// Ex: who runs it, as in foreground.h (tid, nth, sync, any), and
-//   grid0(rec, gh, gw, min_count, A)   plane A = G0 from the frame's records, ending with a barrier; returns this member's
-//                                      share of the sum of cnt
-//   sum(v), min(v)                     a total and a minimum over all members (barriers)
-//   total(acc)                         the members' Acc combined, in every member (barriers)
+// Ex: who runs it (workgroup.h), with total(acc): the members' Acc combined, in every member (barriers).
 // Every branch around a barrier below is on a value that came out of one of these: the same in every member.
 template <class Ex>
 FUSG_HD void label_frame(Ex& ex, const uint32_t* rec, int gh, int gw, const Params& P, uint32_t* A, uint32_t* B, int32_t* boxes,
                          int32_t* box_stats, int32_t* stats) {
     const int nw = fg::words(gw), n = gh * nw, t = ex.tid(), T = ex.nth();
-    const int n_p = ex.sum(ex.grid0(rec, gh, gw, P.min_count, A));
+    const int n_p = ex.sum(grid0(ex, rec, gh, gw, P.min_count, A));
     fg::square(ex, A, B, gh, nw, gw, P.open_r, true, false);
     fg::square(ex, A, B, gh, nw, gw, P.open_r, false, false);
     fg::square(ex, A, B, gh, nw, gw, P.close_r, false, false);
@@ -169,7 +135,7 @@ FUSG_HD void label_frame(Ex& ex, const uint32_t* rec, int gh, int gw, const Para
         ++n_exam;
         if (t == 0) B[first >> 5] = fg::fill(1u << (first & 31), A[first >> 5]);
         ex.sync();
-        flood(ex, B, gh, nw, [A, nw](int i, int k) { return A[i * nw + k]; });
+        fg::flood<true>(ex, B, gh, nw, [A, nw](int i, int k) { return A[i * nw + k]; });   // closed: the seed is stored filled
         Acc acc;
         for (int e = t; e < n; e += T) {
             uint32_t b = B[e];

@@ -7,7 +7,7 @@
 //                every ballot goes through fgb::CellAcc in registers, and it stores the cell's one record.  No LDS, no atomics.
 //   label pass   one workgroup of 256 per frame, the two bit planes in dynamic LDS (fgb::planes_bytes, checked against the
 //                budget on the host).  G0 by ballots over the records, the four fg::square passes, then the component loop of
-//                fgb::label_frame.  Votes are __syncthreads_or, totals and minima a shuffle and a few LDS words.
+//                fgb::label_frame.  The workgroup is workgroup.h's wg::DevRed with the Acc total added, the host twin wg::Host.
 #include <vector>
 #include "common.h"
 #include "foreground_boxes.h"
@@ -53,28 +53,7 @@ __global__ __launch_bounds__(fgb::THREADS) void foreground_cells_kernel(const Bo
     if (lane < OWNERS && j < k.gw) k.rec[((long)f * k.gh + i) * k.gw + j] = acc.pack();
 }
 
-struct BoxesDev {
-    int* red;                                                     // LDS int [BX_WAVES * 6]
-    __device__ int tid() const { return (int)threadIdx.x; }
-    __device__ int nth() const { return fgb::THREADS; }
-    __device__ void sync() const { __syncthreads(); }
-    __device__ bool any(bool p) const { return __syncthreads_or(p ? 1 : 0) != 0; }
-    __device__ int sum(int v) const {
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        const int s = red[0] + red[1] + red[2] + red[3];
-        __syncthreads();
-        return s;
-    }
-    __device__ int min(int v) const {
-        for (int o = 32; o > 0; o >>= 1) v = ::min(v, __shfl_xor(v, o));
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        const int s = ::min(::min(red[0], red[1]), ::min(red[2], red[3]));
-        __syncthreads();
-        return s;
-    }
+struct BoxesDev : wg::DevRed<fgb::THREADS> {                     // red: LDS int [BX_WAVES * 6]
     __device__ void total(fgb::Acc& a) const {
         for (int o = 32; o > 0; o >>= 1) {
             a.n_cells += __shfl_xor(a.n_cells, o);
@@ -101,57 +80,10 @@ struct BoxesDev {
         }
         __syncthreads();
     }
-    __device__ int grid0(const uint32_t* rec, int gh, int gw, int min_count, uint32_t* A) const {
-        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        const int nw = fg::words(gw), chunks = (gw + 63) >> 6, items = gh * chunks;
-        int np = 0;
-        constexpr int U = 8;                                      // U items a turn: their loads are all issued before the first ballot
-        for (int it0 = wave; it0 < items; it0 += BX_WAVES * U) {  // the same trips for every lane of a wave
-            int cnt[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int it = it0 + BX_WAVES * u, i = it / chunks, j = 64 * (it - i * chunks) + lane;
-                cnt[u] = it < items && j < gw ? fgb::rec_cnt(rec[(long)i * gw + j]) : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int it = it0 + BX_WAVES * u, i = it / chunks, c = it - i * chunks;
-                np += cnt[u];
-                const unsigned long long bal = __ballot(cnt[u] >= min_count);
-                if (lane == 0 && it < items) {
-                    A[i * nw + 2 * c] = (uint32_t)bal;
-                    if (2 * c + 1 < nw) A[i * nw + 2 * c + 1] = (uint32_t)(bal >> 32);
-                }
-            }
-        }
-        __syncthreads();
-        return np;
-    }
 };
 
-struct BoxesHost {
-    int tid() const { return 0; }
-    int nth() const { return 1; }
-    void sync() const {}
-    bool any(bool p) const { return p; }
-    int sum(int v) const { return v; }
-    int min(int v) const { return v; }
+struct BoxesHost : wg::Host {
     void total(fgb::Acc&) const {}
-    int grid0(const uint32_t* rec, int gh, int gw, int min_count, uint32_t* A) const {
-        const int nw = fg::words(gw);
-        int np = 0;
-        for (int i = 0; i < gh; ++i)
-            for (int k = 0; k < nw; ++k) {
-                uint32_t v = 0u;
-                for (int j = 32 * k; j < gw && j < 32 * k + 32; ++j) {
-                    const int cnt = fgb::rec_cnt(rec[(long)i * gw + j]);
-                    np += cnt;
-                    v |= (uint32_t)(cnt >= min_count) << (j & 31);
-                }
-                A[i * nw + k] = v;
-            }
-        return np;
-    }
 };
 
 // static LDS: the reductions' words and the 256 bytes __syncthreads_or takes (the resource-usage remark says 352 in all)
@@ -162,7 +94,7 @@ __global__ __launch_bounds__(fgb::THREADS) void foreground_label_kernel(const Bo
     __shared__ int s_red[BX_WAVES * 6];
     const int f = (int)blockIdx.x;
     const long cap = fgb::plane_words(k.gh, k.gw);
-    BoxesDev ex{s_red};
+    BoxesDev ex{{{}, s_red}};
     fgb::label_frame(ex, k.rec + (long)f * k.gh * k.gw, k.gh, k.gw, k.P, s_grid, s_grid + cap, k.boxes + 4L * k.P.K * f,
                      k.box_stats + 2L * k.P.K * f, k.stats + 4L * f);
 }
@@ -211,12 +143,9 @@ static int boxes_check(const void* const* frames, const void* const* backgrounds
                        const int32_t* roi, int32_t K, int32_t* boxes, int32_t* box_stats, int32_t* stats, const char* what, BoxesK& k) {
     FUSG_CHECK(T >= 1 && T <= FUSG_MAX_FRAMES, "%s: T = %d frames (1..%d)", what, T, FUSG_MAX_FRAMES);
     FUSG_CHECK(frames && backgrounds, "%s: frames or backgrounds is null", what);
-    FUSG_CHECK(H >= 1 && W >= 1 && H <= fg::MAX_DIM && W <= fg::MAX_DIM, "%s: frames of %d x %d (H and W in 1..%d)", what, H, W, fg::MAX_DIM);
-    FUSG_CHECK(thr >= 0 && thr <= fg::MAX_THR, "%s: thr = %d (0..%d)", what, thr, fg::MAX_THR);
+    if (const int rc = fg::check_ranges(H, W, thr, open_r, close_r, what)) return rc;
     FUSG_CHECK(cell == 4 || cell == 8 || cell == 16, "%s: cell = %d (4, 8 or 16)", what, cell);
     FUSG_CHECK(min_count >= 1 && min_count <= cell * cell, "%s: min_count = %d (1..%d for cell %d)", what, min_count, cell * cell, cell);
-    FUSG_CHECK(open_r >= 0 && open_r <= fg::MAX_OPEN, "%s: open_r = %d (0..%d)", what, open_r, fg::MAX_OPEN);
-    FUSG_CHECK(close_r >= 0 && close_r <= fg::MAX_CLOSE, "%s: close_r = %d (0..%d)", what, close_r, fg::MAX_CLOSE);
     FUSG_CHECK(min_area >= 1 && min_w >= 1 && min_h >= 1, "%s: min_area, min_w, min_h = %d, %d, %d (each >= 1)", what, min_area, min_w, min_h);
     FUSG_CHECK(K >= 1 && K <= fgb::MAX_K, "%s: K = %d boxes per frame (1..%d)", what, K, fgb::MAX_K);
     FUSG_CHECK(roi != nullptr, "%s: roi is null", what);
@@ -228,11 +157,7 @@ static int boxes_check(const void* const* frames, const void* const* backgrounds
     FUSG_CHECK(fgb::fits(gh, gw), "%s: a grid of %d x %d cells needs %ld bytes of LDS, the budget is %ld: raise cell (now %d)", what, gh, gw,
                fgb::planes_bytes(gh, gw) + fgb::LDS_STATIC, fgb::LDS_BUDGET, cell);
     memset(&k, 0, sizeof(k));
-    for (int f = 0; f < T; ++f) {
-        FUSG_CHECK(frames[f] != nullptr && backgrounds[f] != nullptr, "%s: frame or background %d is null", what, f);
-        k.frames[f] = (const unsigned char*)frames[f];
-        k.bgs[f] = (const unsigned char*)backgrounds[f];
-    }
+    if (const int rc = wg::check_frame_pairs(frames, backgrounds, T, k.frames, k.bgs, what)) return rc;
     k.boxes = boxes; k.box_stats = box_stats; k.stats = stats;
     k.T = T; k.H = H; k.W = W; k.gh = gh; k.gw = gw;
     k.P = fgb::Params{thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, K, roi[0], roi[1], roi[2], roi[3]};

@@ -4,10 +4,11 @@
 //   one workgroup of 256 per video, its frames in order.  The live table (twice, for the compaction), the frame's detections and
 //   expected boxes and the rounds' choices sit in static LDS (trk::Work).  In a round the 128 x 64 pairs are shared over the
 //   workgroup twice: threads 0..127 take a live track each over the detections, threads 128..255 a detection over one half of
-//   the live table, 64 pairs a thread either way; the votes that end the rounds and gate the compaction are __syncthreads_or.
+//   the live table, 64 pairs a thread either way; the workgroup is workgroup.h's wg::Dev, the host twin wg::Host.
 //   No atomics, no scratch memory, no floating point; every global store is a plain C++ store by a vector lane.
 #include "common.h"
 #include "track_boxes.h"
+#include "workgroup.h"
 
 namespace fusg {
 
@@ -23,20 +24,6 @@ struct LinkK {
     trk::Params P;
 };
 
-struct LinkDev {
-    __device__ int tid() const { return (int)threadIdx.x; }
-    __device__ int nth() const { return trk::THREADS; }
-    __device__ void sync() const { __syncthreads(); }
-    __device__ bool any(bool p) const { return __syncthreads_or(p ? 1 : 0) != 0; }
-};
-
-struct LinkHost {
-    int tid() const { return 0; }
-    int nth() const { return 1; }
-    void sync() const {}
-    bool any(bool p) const { return p; }
-};
-
 template <class Ex>
 FUSG_HD void link_one(Ex& ex, trk::Work& w, const LinkK& k, int s) {
     const long f0 = k.first[s];
@@ -46,7 +33,7 @@ FUSG_HD void link_one(Ex& ex, trk::Work& w, const LinkK& k, int s) {
 
 __global__ __launch_bounds__(trk::THREADS) void link_boxes_kernel(const LinkK k) {
     __shared__ trk::Work w;
-    LinkDev ex;
+    wg::Dev<trk::THREADS> ex;
     link_one(ex, w, k, (int)blockIdx.x);
 }
 
@@ -110,7 +97,7 @@ extern "C" int fusg_link_boxes_host(const int32_t* boxes, const int32_t* stats, 
     const int rc = link_check(boxes, stats, first, t0, S, K, iou_num, iou_den, max_gap, predict, max_tracks, state, ids, tracks, out_stats,
                               "link_boxes_host", k);
     if (rc != FUSG_OK) return rc;
-    LinkHost ex;
+    wg::Host ex;
     trk::Work w;
     for (int s = 0; s < S; ++s) link_one(ex, w, k, s);
     return FUSG_OK;

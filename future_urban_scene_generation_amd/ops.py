@@ -21,7 +21,9 @@ _DT = {torch.float32: L.F32, torch.uint8: L.U8, torch.int32: L.I32}
 # Arithmetic of the conv contraction (include/fusg.h fusg_precision): "f32" = exact fp32 MFMA,
 # "f16x3" = split-fp16 (fp32-class accuracy, 3 passes at the fp16 matrix rate).  Process-wide default,
 # overridable per call; FUSG_PRECISION in the environment sets the initial value.
+import contextlib as _contextlib
 import os as _os
+from types import SimpleNamespace as _SimpleNamespace
 import numpy as _np
 
 
@@ -1666,7 +1668,77 @@ def gan_terms_host(pred, label: float = 1.0, mask=None) -> _np.ndarray:
 # ---------------------------------------------------------------------------------------------
 BACKGROUND_MAX_FRAMES = 64
 BACKGROUND_MAX_BOXES = 64           # per frame
-BACKGROUND_MAX_DIM = 32767          # H, W and the margin
+BACKGROUND_MAX_DIM = 32767          # H, W and the margin (csrc/workgroup.h: wg::MAX_DIM)
+
+
+# Every function of the video front end comes as a pair: the device form takes CUDA tensors, its `_host` twin numpy arrays and
+# runs the kernel's code on the CPU.  A pair has ONE private body; what differs is asked of the side it runs on, _DEV or _HOST.
+@_contextlib.contextmanager
+def _device_side(ref: torch.Tensor, name: str):
+    """What only the device form does: the GPU check, the device's scope around the allocations and the launch, and `up` - a host
+    table to the device without a synchronisation (a tensor stays as it is) - whose results a pass that is being recorded keeps."""
+    _require_gpu(ref, name)
+    held = []
+
+    def up(t):
+        held.append(t if torch.is_tensor(t) else h2d(t, ref.device))
+        return held[-1]
+    with torch.cuda.device(ref.device):
+        yield up
+    if RECORDER is not None:
+        RECORDER.keep.extend(held)
+
+
+@_contextlib.contextmanager
+def _host_side(ref, name: str):
+    yield lambda t: t
+
+
+def _as_np(x):
+    return [_np.asarray(v) for v in x] if isinstance(x, (list, tuple)) else _np.asarray(x)
+
+
+_DEV = _SimpleNamespace(
+    tag="", noun="tensor", stream=True, side=_device_side, arrays=lambda x: x, is_array=torch.is_tensor,
+    u8=torch.uint8, i32=torch.int32, i64=torch.int64,
+    empty=lambda shape, dtype, ref: torch.empty(shape, dtype=dtype, device=ref.device),
+    zeros=lambda shape, dtype, ref: torch.zeros(shape, dtype=dtype, device=ref.device),
+    ptr=lambda a: a.data_ptr(), dense=lambda a: a.is_contiguous(), contiguous=lambda a: a.contiguous(), cat=torch.cat,
+    near=lambda a, ref: a.device == ref.device, at=lambda ref: f" on {ref.device}")
+_HOST = _SimpleNamespace(
+    tag="_host", noun="array", stream=False, side=_host_side, arrays=_as_np, is_array=lambda a: isinstance(a, _np.ndarray),
+    u8=_np.uint8, i32=_np.int32, i64=_np.int64,
+    empty=lambda shape, dtype, ref: _np.zeros(shape, dtype=dtype), zeros=lambda shape, dtype, ref: _np.zeros(shape, dtype=dtype),
+    ptr=lambda a: a.ctypes.data, dense=lambda a: a.flags.c_contiguous, contiguous=_np.ascontiguousarray, cat=_np.concatenate,
+    near=lambda a, ref: True, at=lambda ref: "")
+
+
+def _call(wh, what: str, entry: str, *args) -> None:
+    """The library's entry of this side: `entry` with the current stream appended, or its `_host` twin (fusg_x_u8 -> fusg_x_host)."""
+    if wh.stream:
+        return L.check(getattr(L.lib(), entry)(*args, stream_ptr()), what)
+    L.check(getattr(L.lib(), (entry[:-3] if entry.endswith("_u8") else entry) + "_host")(*args), what)
+
+
+def _fits(wh, a, dtype, shape, ref) -> bool:
+    """A dense array of this side, of this type and shape (None: any one-dimensional), where `ref` is."""
+    return wh.is_array(a) and a.dtype == dtype and (len(a.shape) == 1 if shape is None else tuple(a.shape) == tuple(shape)) \
+        and wh.dense(a) and wh.near(a, ref)
+
+
+def _ptrs(wh, arrays):
+    return (C.c_void_p * len(arrays))(*[wh.ptr(a) for a in arrays])
+
+
+def _int_rows4(table, what: str, name: str, row: str) -> _np.ndarray:
+    """An integer [n, 4] host table as int64 [n, 4], every entry inside int32: the caller casts after its own checks."""
+    b = _np.asarray(table)
+    if b.size and (b.dtype.kind not in "iu" or b.size % 4 or (b.ndim > 1 and b.shape[-1] != 4)):
+        raise ValueError(f"{what}: {name} must be an integer [n, 4] array, got {b.dtype} {b.shape}")
+    b = b.reshape(-1, 4).astype(_np.int64)
+    if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
+        raise ValueError(f"{what}: {row} does not fit int32")
+    return b
 
 
 def _background_frames(frames, u8, what: str):
@@ -1705,14 +1777,9 @@ def _background_args(T: int, boxes, margin, min_valid, what: str):
         raise ValueError(f"{what}: {len(boxes)} box lists for {T} frames")
     rows = []
     for t, b in enumerate(boxes):
-        b = _np.asarray(b)
-        if b.size and (b.dtype.kind not in "iu" or b.size % 4 or (b.ndim > 1 and b.shape[-1] != 4)):
-            raise ValueError(f"{what}: the boxes of frame {t} must be an integer [n, 4] array, got {b.dtype} {b.shape}")
-        b = b.reshape(-1, 4).astype(_np.int64)
+        b = _int_rows4(b, what, f"the boxes of frame {t}", f"a box of frame {t}")
         if b.shape[0] > BACKGROUND_MAX_BOXES:
             raise ValueError(f"{what}: frame {t} has {b.shape[0]} boxes (at most {BACKGROUND_MAX_BOXES})")
-        if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
-            raise ValueError(f"{what}: a box of frame {t} does not fit int32")
         rows.append(b.astype(_np.int32))
         offs[t + 1] = offs[t] + b.shape[0]
     return _np.ascontiguousarray(_np.concatenate(rows, axis=0)), offs, margin, min_valid
@@ -1725,44 +1792,36 @@ def background_median(frames, boxes=None, margin: int = 0, min_valid: int = 1, o
     uint8 [H, W, 3] tensors (separate allocations are fine) or one [T, H, W, 3] tensor; boxes: None or T host int arrays
     [nb_t, 4] of (x0, y0, x1, y1), both ends inclusive, at most 64 per frame.  out: an optional (bg, count) pair to write into.
     One launch on the current stream, no atomics, no host synchronisation (fusg_background_median_u8)."""
-    what = "background_median"
-    frames, T, H, W = _background_frames(frames, torch.uint8, what)
-    dev = frames[0].device
-    for t, f in enumerate(frames):
-        if f.device != dev:
-            raise ValueError(f"{what}: frame {t} is on {f.device}, frame 0 on {dev}")
-    flat, offs, margin, min_valid = _background_args(T, boxes, margin, min_valid, what)
-    _require_gpu(frames[0], "frames")
-    if out is not None:
-        bg, count = out
-        for name, o, shape in (("bg", bg, (H, W, 3)), ("count", count, (H, W))):
-            if o.dtype != torch.uint8 or tuple(o.shape) != shape or not o.is_contiguous() or o.device != dev:
-                raise ValueError(f"{what}: out's {name} must be a contiguous uint8 {shape} tensor on {dev}")
-    with torch.cuda.device(dev):
-        if out is None:
-            bg = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-            count = torch.empty((H, W), dtype=torch.uint8, device=dev)
-        dbox = h2d(flat, dev) if flat.shape[0] else None
-        ptrs = (C.c_void_p * T)(*[f.data_ptr() for f in frames])
-        L.check(L.lib().fusg_background_median_u8(ptrs, T, H, W, dbox.data_ptr() if dbox is not None else None, offs.ctypes.data, margin,
-                                                  min_valid, bg.data_ptr(), count.data_ptr(), stream_ptr()), what)
-        if RECORDER is not None and dbox is not None:
-            RECORDER.keep.append(dbox)
-    return bg, count
+    return _background_median(_DEV, frames, boxes, margin, min_valid, out)
 
 
 def background_median_host(frames, boxes=None, margin: int = 0, min_valid: int = 1):
     """`background_median` on the CPU by the same code (fusg_background_median_host; no GPU needed): numpy uint8 frames in,
     (bg, count) numpy arrays out."""
-    what = "background_median_host"
-    frames = [_np.asarray(f) for f in frames] if isinstance(frames, (list, tuple)) else _np.asarray(frames)
-    frames, T, H, W = _background_frames(frames, _np.uint8, what)
+    return _background_median(_HOST, frames, boxes, margin, min_valid, None)
+
+
+def _one_place(wh, arrays, what: str) -> None:
+    for a in arrays:
+        if not wh.near(a, arrays[0]):
+            raise ValueError(f"{what}: a frame or background is on {a.device}, frame 0 on {arrays[0].device}")
+
+
+def _background_median(wh, frames, boxes, margin, min_valid, out):
+    what = "background_median" + wh.tag
+    frames, T, H, W = _background_frames(wh.arrays(frames), wh.u8, what)
+    for t, f in enumerate(frames):
+        if not wh.near(f, frames[0]):
+            raise ValueError(f"{what}: frame {t} is on {f.device}, frame 0 on {frames[0].device}")
     flat, offs, margin, min_valid = _background_args(T, boxes, margin, min_valid, what)
-    bg = _np.zeros((H, W, 3), dtype=_np.uint8)
-    count = _np.zeros((H, W), dtype=_np.uint8)
-    ptrs = (C.c_void_p * T)(*[f.ctypes.data for f in frames])
-    L.check(L.lib().fusg_background_median_host(ptrs, T, H, W, flat.ctypes.data if flat.shape[0] else None, offs.ctypes.data, margin,
-                                                min_valid, bg.ctypes.data, count.ctypes.data), what)
+    shapes = {"bg": (H, W, 3), "count": (H, W)}
+    for (name, shape), o in zip(shapes.items(), out or ()):
+        if not _fits(wh, o, wh.u8, shape, frames[0]):
+            raise ValueError(f"{what}: out's {name} must be a contiguous uint8 {shape} {wh.noun}{wh.at(frames[0])}")
+    with wh.side(frames[0], "frames") as up:
+        bg, count = out if out is not None else [wh.empty(s, wh.u8, frames[0]) for s in shapes.values()]
+        _call(wh, what, "fusg_background_median_u8", _ptrs(wh, frames), T, H, W, wh.ptr(up(flat)) if flat.shape[0] else None,
+              offs.ctypes.data, margin, min_valid, wh.ptr(bg), wh.ptr(count))
     return bg, count
 
 
@@ -1776,14 +1835,9 @@ FOREGROUND_FALLBACK, FOREGROUND_BORDER, FOREGROUND_REFUSED = 1, 2, 4
 
 def _box_table(boxes, n, H, W, what: str, name: str, inside: bool) -> _np.ndarray:
     """An integer [n, 4] host table as int32; inside: every row a half-open rectangle of the W x H frame, as `_inpaint_args` asks."""
-    b = _np.asarray(boxes)
-    if b.size and (b.dtype.kind not in "iu" or b.size % 4 or (b.ndim > 1 and b.shape[-1] != 4)):
-        raise ValueError(f"{what}: {name} must be an integer [n, 4] array, got {b.dtype} {b.shape}")
-    b = b.reshape(-1, 4).astype(_np.int64)
+    b = _int_rows4(boxes, what, name, f"a row of {name}")
     if n is not None and b.shape[0] != n:
         raise ValueError(f"{what}: {b.shape[0]} {name} for {n} boxes")
-    if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
-        raise ValueError(f"{what}: a row of {name} does not fit int32")
     if inside:
         bad = (b[:, 0] < 0) | (b[:, 1] < 0) | (b[:, 2] < b[:, 0]) | (b[:, 3] < b[:, 1]) | (b[:, 2] > W) | (b[:, 3] > H)
         if bad.any():
@@ -1792,24 +1846,31 @@ def _box_table(boxes, n, H, W, what: str, name: str, inside: bool) -> _np.ndarra
     return _np.ascontiguousarray(b.astype(_np.int32))
 
 
-def _foreground_args(frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box, offs, u8, what):
-    """What both forms of `foreground_masks` check before anything is touched -> (frames, backgrounds, H, W, boxes int32 [n, 4],
-    cores int32 [n, 4], offsets int64 [n], the bytes the masks take, frame_rows int32 [F + 1], the five parameters, max_box)."""
+def _frames_and_backgrounds(frames, backgrounds, u8, what: str, name: str = "backgrounds"):
+    """One frame or up to 64, and one background for all of them or one each -> (frames, backgrounds, T, H, W), checked as
+    `_background_frames` checks the frames."""
     if hasattr(frames, "shape") and len(frames.shape) == 3:
         frames = [frames]
-    frames, F, H, W = _background_frames(frames, u8, what)
-    if hasattr(background, "shape") and len(background.shape) == 3:
-        background = [background] * F
-    if hasattr(background, "shape") and len(background.shape) != 4:
-        raise ValueError(f"{what}: background must be uint8 [H, W, 3], or one per frame")
-    bgs = [background[f] for f in range(len(background))]
-    if len(bgs) != F:
-        raise ValueError(f"{what}: {len(bgs)} backgrounds for {F} frames")
+    frames, T, H, W = _background_frames(frames, u8, what)
+    if hasattr(backgrounds, "shape") and len(backgrounds.shape) == 3:
+        backgrounds = [backgrounds] * T
+    if hasattr(backgrounds, "shape") and len(backgrounds.shape) != 4:
+        raise ValueError(f"{what}: {name} must be uint8 [H, W, 3], or one per frame")
+    bgs = [backgrounds[f] for f in range(len(backgrounds))]
+    if len(bgs) != T:
+        raise ValueError(f"{what}: {len(bgs)} backgrounds for {T} frames")
     for f, g in enumerate(bgs):
         if not hasattr(g, "shape") or g.dtype != u8 or tuple(g.shape) != (H, W, 3):
             raise ValueError(f"{what}: background {f} must be uint8 {(H, W, 3)}, got {getattr(g, 'dtype', type(g))} {tuple(getattr(g, 'shape', ()))}")
         if not (g.is_contiguous() if isinstance(g, torch.Tensor) else g.flags.c_contiguous):
             raise ValueError(f"{what}: background {f} is not contiguous")
+    return frames, bgs, T, H, W
+
+
+def _foreground_args(frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box, offs, u8, what):
+    """What both forms of `foreground_masks` check before anything is touched -> (frames, backgrounds, H, W, boxes int32 [n, 4],
+    cores int32 [n, 4], offsets int64 [n], the bytes the masks take, frame_rows int32 [F + 1], the five parameters, max_box)."""
+    frames, bgs, F, H, W = _frames_and_backgrounds(frames, background, u8, what, "background")
     par = []
     for name, v in (("thr", thr), ("open_r", open_r), ("close_r", close_r), ("grow", grow)):
         if int(v) != v or not 0 <= int(v) <= FOREGROUND_LIMITS[name]:
@@ -1859,60 +1920,39 @@ def foreground_masks(frames, background, boxes, cores, thr: int = 24, open_r: in
     (default: a fresh buffer, the offsets the running sum of h w).
     -> ((buffer uint8 [m], offsets int64 [n]) on the device - what `inpaint_inputs_boxed` takes as box_masks -, stats int32 [n, 4]
     on the device: `FOREGROUND_STATS`, flags = 1 fallback taken | 2 touches the box border | 4 refused, bytes not written)."""
-    what = "foreground_masks"
-    frames, bgs, H, W, bx, cr, offs, nbytes, rows, par, mb = _foreground_args(
-        frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box,
-        None if out is None else out[1], torch.uint8, what)
-    dev = frames[0].device
-    for t in frames + bgs:
-        if t.device != dev:
-            raise ValueError(f"{what}: a frame or background is on {t.device}, frame 0 on {dev}")
-    if out is not None and (not torch.is_tensor(out[0]) or out[0].dtype != torch.uint8 or out[0].dim() != 1 or not out[0].is_contiguous()
-                            or out[0].device != dev):
-        raise ValueError(f"{what}: out's buffer must be a contiguous uint8 [m] tensor on {dev}")
-    _require_gpu(frames[0], "frames")
-    n, F = bx.shape[0], len(frames)
-    with torch.cuda.device(dev):
-        buf = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if out is None else out[0]
-        stats = torch.empty((n, 4), dtype=torch.int32, device=dev)
-        if n == 0:
-            return (buf, torch.empty((0,), dtype=torch.int64, device=dev)), stats
-        tab = h2d(_np.concatenate([bx, cr]), dev)                 # one copy for both tables
-        off_d = h2d(offs, dev, torch.int64)
-        lib = L.lib()
-        sb = int(lib.fusg_foreground_masks_scratch_bytes(n, mb[0], mb[1]))
-        scratch = torch.empty((sb,), dtype=torch.uint8, device=dev) if sb > 0 else None
-        fp = (C.c_void_p * F)(*[f.data_ptr() for f in frames])
-        gp = (C.c_void_p * F)(*[g.data_ptr() for g in bgs])
-        L.check(lib.fusg_foreground_masks_u8(fp, gp, rows.ctypes.data, F, H, W, tab[:n].data_ptr(), tab[n:].data_ptr(), off_d.data_ptr(), n,
-                                             *par, mb[0], mb[1], buf.data_ptr() if buf.numel() else None, int(buf.numel()),
-                                             stats.data_ptr(), scratch.data_ptr() if scratch is not None else None, stream_ptr()), what)
-        if RECORDER is not None:
-            RECORDER.keep.extend(t for t in (tab, off_d, scratch) if t is not None)
-    return (buf, off_d), stats
+    return _foreground_masks(_DEV, frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box, out)
 
 
 def foreground_masks_host(frames, background, boxes, cores, thr: int = 24, open_r: int = 1, close_r: int = 3, grow: int = 0,
                           fallback: bool = True, frame_rows=None, max_box=None, out=None):
     """`foreground_masks` on the CPU by the same code (fusg_foreground_masks_host; no GPU needed): numpy uint8 images in,
     ((buffer uint8 [m], offsets int64 [n]), stats int32 [n, 4]) numpy arrays out."""
-    what = "foreground_masks_host"
-    as_np = lambda x: [_np.asarray(f) for f in x] if isinstance(x, (list, tuple)) else _np.asarray(x)  # noqa: E731
+    return _foreground_masks(_HOST, frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box, out)
+
+
+def _foreground_masks(wh, frames, background, boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box, out):
+    what = "foreground_masks" + wh.tag
     frames, bgs, H, W, bx, cr, offs, nbytes, rows, par, mb = _foreground_args(
-        as_np(frames), as_np(background), boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box,
-        None if out is None else out[1], _np.uint8, what)
-    if out is not None and (not isinstance(out[0], _np.ndarray) or out[0].dtype != _np.uint8 or out[0].ndim != 1
-                            or not out[0].flags.c_contiguous):
-        raise ValueError(f"{what}: out's buffer must be a contiguous uint8 [m] array")
-    n, F = bx.shape[0], len(frames)
-    buf = _np.zeros((nbytes,), dtype=_np.uint8) if out is None else out[0]
-    stats = _np.zeros((n, 4), dtype=_np.int32)
-    if n == 0:
-        return (buf, offs), stats
-    fp = (C.c_void_p * F)(*[f.ctypes.data for f in frames])
-    gp = (C.c_void_p * F)(*[g.ctypes.data for g in bgs])
-    L.check(L.lib().fusg_foreground_masks_host(fp, gp, rows.ctypes.data, F, H, W, bx.ctypes.data, cr.ctypes.data, offs.ctypes.data, n, *par,
-                                               mb[0], mb[1], buf.ctypes.data if buf.size else None, int(buf.size), stats.ctypes.data), what)
+        wh.arrays(frames), wh.arrays(background), boxes, cores, thr, open_r, close_r, grow, fallback, frame_rows, max_box,
+        None if out is None else out[1], wh.u8, what)
+    ref = frames[0]
+    _one_place(wh, frames + bgs, what)
+    if out is not None and not _fits(wh, out[0], wh.u8, None, ref):
+        raise ValueError(f"{what}: out's buffer must be a contiguous uint8 [m] {wh.noun}{wh.at(ref)}")
+    n = bx.shape[0]
+    with wh.side(ref, "frames") as up:
+        buf = wh.empty((nbytes,), wh.u8, ref) if out is None else out[0]
+        stats = wh.empty((n, 4), wh.i32, ref)
+        if n == 0:
+            return (buf, wh.empty((0,), wh.i64, ref)), stats
+        tab, offs = up(_np.concatenate([bx, cr])), up(offs)       # one copy for both tables
+        scratch = ()
+        if wh.stream:                                             # the planes of boxes that do not fit LDS
+            sb = int(L.lib().fusg_foreground_masks_scratch_bytes(n, mb[0], mb[1]))
+            scratch = (up(torch.empty((sb,), dtype=torch.uint8, device=ref.device)).data_ptr() if sb > 0 else None,)
+        _call(wh, what, "fusg_foreground_masks_u8", _ptrs(wh, frames), _ptrs(wh, bgs), rows.ctypes.data, len(frames), H, W,
+              wh.ptr(tab[:n]), wh.ptr(tab[n:]), wh.ptr(offs), n, *par, mb[0], mb[1], wh.ptr(buf) if buf.shape[0] else None,
+              int(buf.shape[0]), wh.ptr(stats), *scratch)
     return (buf, offs), stats
 
 
@@ -1939,38 +1979,30 @@ def erase_to_background(frame: torch.Tensor, background: torch.Tensor, box_masks
     stream): a compositing base that keeps the rest of the traffic.  frame, background CUDA uint8 [H, W, 3]; box_masks = the
     packed (buffer, offsets) pair of `foreground_masks` (offsets on the device or host); boxes host int [n, 4].  -> uint8 [H, W,
     3] (out: a buffer to write into, not overlapping the inputs)."""
-    what = "erase_to_background"
-    H, W, bx, buf, offs = _erase_args(frame, background, box_masks, boxes, torch.uint8, what)
-    dev = frame.device
-    if not torch.is_tensor(buf) or buf.device != dev or background.device != dev or not buf.is_contiguous():
-        raise ValueError(f"{what}: the frame, the background and the mask buffer must be contiguous tensors on one device")
-    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.device != dev):
-        raise ValueError(f"{what}: out must be a contiguous uint8 {(H, W, 3)} tensor on {dev}")
-    _require_gpu(frame, "frame")
-    n = bx.shape[0]
-    with torch.cuda.device(dev):
-        dst = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
-        off_d = offs.to(torch.int64).contiguous() if (torch.is_tensor(offs) and offs.is_cuda) else h2d(_np.asarray(offs, dtype=_np.int64), dev)
-        bx_d = h2d(bx, dev) if n else None
-        L.check(L.lib().fusg_erase_boxes_u8(frame.data_ptr(), background.data_ptr(), H, W, buf.data_ptr() if buf.numel() else None,
-                                            int(buf.numel()), off_d.data_ptr() if n else None, bx_d.data_ptr() if n else None, n,
-                                            dst.data_ptr(), stream_ptr()), what)
-        if RECORDER is not None:
-            RECORDER.keep.extend(t for t in (off_d, bx_d) if t is not None)
-    return dst
+    return _erase_to_background(_DEV, frame, background, box_masks, boxes, out)
 
 
 def erase_to_background_host(frame, background, box_masks, boxes) -> _np.ndarray:
     """`erase_to_background` on the CPU by the same code (fusg_erase_boxes_host): numpy in and out."""
-    what = "erase_to_background_host"
-    frame, background = _np.asarray(frame), _np.asarray(background)
     if isinstance(box_masks, tuple) and len(box_masks) == 2:
         box_masks = (_np.ascontiguousarray(box_masks[0]), _np.ascontiguousarray(box_masks[1], dtype=_np.int64))
-    H, W, bx, buf, offs = _erase_args(frame, background, box_masks, boxes, _np.uint8, what)
+    return _erase_to_background(_HOST, frame, background, box_masks, boxes, None)
+
+
+def _erase_to_background(wh, frame, background, box_masks, boxes, out):
+    what = "erase_to_background" + wh.tag
+    frame, background = wh.arrays(frame), wh.arrays(background)
+    H, W, bx, buf, offs = _erase_args(frame, background, box_masks, boxes, wh.u8, what)
+    if not _fits(wh, buf, wh.u8, None, frame) or not wh.near(background, frame):
+        raise ValueError(f"{what}: the frame, the background and the mask buffer must be contiguous tensors on one device")
+    if out is not None and not _fits(wh, out, wh.u8, (H, W, 3), frame):
+        raise ValueError(f"{what}: out must be a contiguous uint8 {(H, W, 3)} {wh.noun}{wh.at(frame)}")
     n = bx.shape[0]
-    dst = _np.zeros((H, W, 3), dtype=_np.uint8)
-    L.check(L.lib().fusg_erase_boxes_host(frame.ctypes.data, background.ctypes.data, H, W, buf.ctypes.data if buf.size else None, int(buf.size),
-                                          offs.ctypes.data if n else None, bx.ctypes.data if n else None, n, dst.ctypes.data), what)
+    with wh.side(frame, "frame") as up:
+        dst = wh.empty((H, W, 3), wh.u8, frame) if out is None else out
+        offs = up(offs.to(torch.int64).contiguous() if torch.is_tensor(offs) and offs.is_cuda else _np.asarray(offs, dtype=_np.int64))
+        _call(wh, what, "fusg_erase_boxes_u8", wh.ptr(frame), wh.ptr(background), H, W, wh.ptr(buf) if buf.shape[0] else None,
+              int(buf.shape[0]), wh.ptr(offs) if n else None, wh.ptr(up(bx)) if n else None, n, wh.ptr(dst))
     return dst
 
 
@@ -1986,21 +2018,7 @@ FOREGROUND_BOXES_OVERFLOW, FOREGROUND_BOXES_TRUNCATED = 1, 2
 def _foreground_boxes_args(frames, backgrounds, thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, max_boxes, roi, u8, what):
     """What both forms of `foreground_boxes` check themselves - the images and that every parameter is an integer; the ranges are
     the library's to refuse -> (frames, backgrounds, T, H, W, the eleven int32 parameters with K in place, roi int32 [4])."""
-    if hasattr(frames, "shape") and len(frames.shape) == 3:
-        frames = [frames]
-    frames, T, H, W = _background_frames(frames, u8, what)
-    if hasattr(backgrounds, "shape") and len(backgrounds.shape) == 3:
-        backgrounds = [backgrounds] * T
-    if hasattr(backgrounds, "shape") and len(backgrounds.shape) != 4:
-        raise ValueError(f"{what}: backgrounds must be uint8 [H, W, 3], or one per frame")
-    bgs = [backgrounds[f] for f in range(len(backgrounds))]
-    if len(bgs) != T:
-        raise ValueError(f"{what}: {len(bgs)} backgrounds for {T} frames")
-    for f, g in enumerate(bgs):
-        if not hasattr(g, "shape") or g.dtype != u8 or tuple(g.shape) != (H, W, 3):
-            raise ValueError(f"{what}: background {f} must be uint8 {(H, W, 3)}, got {getattr(g, 'dtype', type(g))} {tuple(getattr(g, 'shape', ()))}")
-        if not (g.is_contiguous() if isinstance(g, torch.Tensor) else g.flags.c_contiguous):
-            raise ValueError(f"{what}: background {f} is not contiguous")
+    frames, bgs, T, H, W = _frames_and_backgrounds(frames, backgrounds, u8, what)
     par = []
     for name, v in (("thr", thr), ("cell", cell), ("min_count", min_count), ("open_r", open_r), ("close_r", close_r),
                     ("min_area", min_area), ("min_w", min_w), ("min_h", min_h), ("max_boxes", max_boxes)):
@@ -2026,59 +2044,38 @@ def foreground_boxes(frames, backgrounds, thr: int = 24, cell: int = 8, min_coun
     -> (boxes int32 [T, K, 4] half-open (x0, y0, x1, y1), box_stats int32 [T, K, 2] = (area, n_cells), stats int32 [T, 4] =
     `FOREGROUND_BOXES_STATS`, flags 1 = more than K = max_boxes were kept, 2 = more than 256 components) on the device; the rows
     from min(n_kept, K) on are zeros."""
-    what = "foreground_boxes"
-    frames, bgs, T, H, W, par, r = _foreground_boxes_args(frames, backgrounds, thr, cell, min_count, open_r, close_r, min_area, min_w, min_h,
-                                                          max_boxes, roi, torch.uint8, what)
-    dev = frames[0].device
-    for t in frames + bgs:
-        if t.device != dev:
-            raise ValueError(f"{what}: a frame or background is on {t.device}, frame 0 on {dev}")
-    _require_gpu(frames[0], "frames")
-    K = par[-1]
-    if not 1 <= K <= FOREGROUND_BOXES_MAX:
-        raise ValueError(f"{what}: max_boxes = {K} (1..{FOREGROUND_BOXES_MAX})")
-    shapes = ((T, K, 4), (T, K, 2), (T, 4))
-    if out is not None:
-        for o, s in zip(out, shapes):
-            if not torch.is_tensor(o) or o.dtype != torch.int32 or tuple(o.shape) != s or not o.is_contiguous() or o.device != dev:
-                raise ValueError(f"{what}: out must be contiguous int32 tensors of {shapes} on {dev}")
-    with torch.cuda.device(dev):
-        lib = L.lib()
-        sb = int(lib.fusg_foreground_boxes_scratch_bytes(T, H, W, par[1]))
-        if sb < 0:
-            raise ValueError(f"{what}: cell = {par[1]} (4, 8 or 16)")
-        boxes, box_stats, stats = out if out is not None else [torch.empty(s, dtype=torch.int32, device=dev) for s in shapes]
-        scratch = torch.empty((sb // 4,), dtype=torch.int32, device=dev)
-        fp = (C.c_void_p * T)(*[f.data_ptr() for f in frames])
-        gp = (C.c_void_p * T)(*[g.data_ptr() for g in bgs])
-        L.check(lib.fusg_foreground_boxes_u8(fp, gp, T, H, W, *par[:8], r.ctypes.data, K, boxes.data_ptr(), box_stats.data_ptr(),
-                                             stats.data_ptr(), scratch.data_ptr(), stream_ptr()), what)
-        if RECORDER is not None:
-            RECORDER.keep.append(scratch)
-    return boxes, box_stats, stats
+    return _foreground_boxes(_DEV, frames, backgrounds, thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, max_boxes, roi, out)
 
 
 def foreground_boxes_host(frames, backgrounds, thr: int = 24, cell: int = 8, min_count: int = 16, open_r: int = 0, close_r: int = 1,
                           min_area: int = 400, min_w: int = 12, min_h: int = 12, max_boxes: int = 64, roi=None, out=None):
     """`foreground_boxes` on the CPU by the same code (fusg_foreground_boxes_host; no GPU needed): numpy uint8 images in, (boxes,
     box_stats, stats) int32 numpy arrays out."""
-    what = "foreground_boxes_host"
-    as_np = lambda x: [_np.asarray(f) for f in x] if isinstance(x, (list, tuple)) else _np.asarray(x)  # noqa: E731
-    frames, bgs, T, H, W, par, r = _foreground_boxes_args(as_np(frames), as_np(backgrounds), thr, cell, min_count, open_r, close_r, min_area,
-                                                          min_w, min_h, max_boxes, roi, _np.uint8, what)
+    return _foreground_boxes(_HOST, frames, backgrounds, thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, max_boxes, roi, out)
+
+
+def _foreground_boxes(wh, frames, backgrounds, thr, cell, min_count, open_r, close_r, min_area, min_w, min_h, max_boxes, roi, out):
+    what = "foreground_boxes" + wh.tag
+    frames, bgs, T, H, W, par, r = _foreground_boxes_args(wh.arrays(frames), wh.arrays(backgrounds), thr, cell, min_count, open_r, close_r,
+                                                          min_area, min_w, min_h, max_boxes, roi, wh.u8, what)
+    ref = frames[0]
+    _one_place(wh, frames + bgs, what)
     K = par[-1]
     if not 1 <= K <= FOREGROUND_BOXES_MAX:
         raise ValueError(f"{what}: max_boxes = {K} (1..{FOREGROUND_BOXES_MAX})")
     shapes = ((T, K, 4), (T, K, 2), (T, 4))
-    if out is not None:
-        for o, s in zip(out, shapes):
-            if not isinstance(o, _np.ndarray) or o.dtype != _np.int32 or o.shape != s or not o.flags.c_contiguous:
-                raise ValueError(f"{what}: out must be contiguous int32 arrays of {shapes}")
-    boxes, box_stats, stats = out if out is not None else [_np.zeros(s, dtype=_np.int32) for s in shapes]
-    fp = (C.c_void_p * T)(*[f.ctypes.data for f in frames])
-    gp = (C.c_void_p * T)(*[g.ctypes.data for g in bgs])
-    L.check(L.lib().fusg_foreground_boxes_host(fp, gp, T, H, W, *par[:8], r.ctypes.data, K, boxes.ctypes.data, box_stats.ctypes.data,
-                                               stats.ctypes.data), what)
+    if out is not None and not all(_fits(wh, o, wh.i32, s, ref) for o, s in zip(out, shapes)):
+        raise ValueError(f"{what}: out must be contiguous int32 {wh.noun}s of {shapes}{wh.at(ref)}")
+    with wh.side(ref, "frames") as up:
+        scratch = ()
+        if wh.stream:                                             # the cell pass's records
+            sb = int(L.lib().fusg_foreground_boxes_scratch_bytes(T, H, W, par[1]))
+            if sb < 0:
+                raise ValueError(f"{what}: cell = {par[1]} (4, 8 or 16)")
+            scratch = (up(torch.empty((sb // 4,), dtype=torch.int32, device=ref.device)).data_ptr(),)
+        boxes, box_stats, stats = out if out is not None else [wh.empty(s, wh.i32, ref) for s in shapes]
+        _call(wh, what, "fusg_foreground_boxes_u8", _ptrs(wh, frames), _ptrs(wh, bgs), T, H, W, *par[:8], r.ctypes.data, K,
+              wh.ptr(boxes), wh.ptr(box_stats), wh.ptr(stats), *scratch)
     return boxes, box_stats, stats
 
 
@@ -2092,17 +2089,16 @@ LINK_BOXES_MAX_VIDEOS = 64          # videos (workgroups) per call
 LINK_BOXES_STATE_WORDS = 8 + 128 * 13
 
 
-def _link_boxes_args(boxes, stats, iou, max_gap, predict, max_tracks, t0, lib_t, what):
+def _link_boxes_args(boxes, stats, iou, max_gap, predict, max_tracks, t0, wh, what):
     """What both forms of `link_boxes` check themselves - the tables' shapes and types and that every parameter is an integer;
     the ranges are the library's to refuse -> (boxes and stats as ONE table each, one video?, S, K, first int32 [S + 1], t0 int32
     [S], the five int32 parameters)."""
-    is_t = (lambda x: torch.is_tensor(x)) if lib_t is torch else (lambda x: isinstance(x, _np.ndarray))
+    is_t, i32 = wh.is_array, wh.i32
     one = is_t(boxes)
     bl, sl = ([boxes], [stats]) if one else (list(boxes), list(stats))
     S = len(bl)
     if S < 1 or len(sl) != S:
         raise ValueError(f"{what}: {S} box tables and {len(sl)} stats tables (one pair per video, at least one)")
-    i32 = torch.int32 if lib_t is torch else _np.int32
     K = None
     for s, (b, st) in enumerate(zip(bl, sl)):
         if not is_t(b) or not is_t(st) or b.dtype != i32 or st.dtype != i32 or len(b.shape) != 3 or b.shape[2] != 4 \
@@ -2127,7 +2123,7 @@ def _link_boxes_args(boxes, stats, iou, max_gap, predict, max_tracks, t0, lib_t,
     t0a = _np.asarray([t0] * S if _np.ndim(t0) == 0 else t0)
     if t0a.dtype.kind not in "iu" or t0a.shape != (S,) or t0a.min() < -2 ** 31 or t0a.max() >= 2 ** 31:
         raise ValueError(f"{what}: t0 must be an integer, or one per video, got {t0}")
-    cat = (lambda x: x[0] if len(x) == 1 else torch.cat(x)) if lib_t is torch else (lambda x: x[0] if len(x) == 1 else _np.concatenate(x))
+    cat = lambda x: wh.contiguous(x[0] if len(x) == 1 else wh.cat(x))  # noqa: E731
     return cat(bl), cat(sl), one, S, K, _np.ascontiguousarray(first.astype(_np.int32)), _np.ascontiguousarray(t0a.astype(_np.int32)), par
 
 
@@ -2153,56 +2149,36 @@ def link_boxes(boxes, stats, iou=(3, 10), max_gap: int = 2, predict: int = 1, ma
     -> (ids int32 [T, K], -1 where there is no box or none could be given; tracks int32 [max_tracks, 4] = (first_t, last_t, hits,
     0); stats int32 [4] = `LINK_BOXES_STATS`, flags `LINK_BOXES_*`; state int32 [`LINK_BOXES_STATE_WORDS`]) on the device - for a
     list, ids is a list of views and the others gain a leading axis S."""
-    what = "link_boxes"
-    b, st, one, S, K, first, t0a, par = _link_boxes_args(boxes, stats, iou, max_gap, predict, max_tracks, t0, torch, what)
-    dev = b.device
-    _require_gpu(b, "boxes")
-    if st.device != dev:
-        raise ValueError(f"{what}: stats is on {st.device}, boxes on {dev}")
-    N, F = par[4], int(first[-1])
-    if not 1 <= N <= 2 ** 20:
-        raise ValueError(f"{what}: max_tracks = {N} (1..{2 ** 20})")
-    shapes = ((F, K), (S, N, 4), (S, 4))
-    ok = lambda o, s: torch.is_tensor(o) and o.dtype == torch.int32 and tuple(o.shape) == s and o.is_contiguous() and o.device == dev  # noqa: E731
-    if out is not None and not all(ok(o, s) for o, s in zip(out, shapes)):
-        raise ValueError(f"{what}: out must be contiguous int32 tensors of {shapes} on {dev}")
-    if state is not None and not ok(state, (S, LINK_BOXES_STATE_WORDS)) and not (one and ok(state, (LINK_BOXES_STATE_WORDS,))):
-        raise ValueError(f"{what}: state must be a contiguous int32 tensor of {(S, LINK_BOXES_STATE_WORDS)} on {dev}")
-    with torch.cuda.device(dev):
-        if state is None:
-            state = torch.zeros((S, LINK_BOXES_STATE_WORDS), dtype=torch.int32, device=dev)
-        ids, tracks, ost = out if out is not None else (torch.empty(shapes[0], dtype=torch.int32, device=dev),
-                                                        torch.zeros(shapes[1], dtype=torch.int32, device=dev),
-                                                        torch.empty(shapes[2], dtype=torch.int32, device=dev))
-        L.check(L.lib().fusg_link_boxes(b.contiguous().data_ptr(), st.contiguous().data_ptr(), first.ctypes.data, t0a.ctypes.data, S, K, *par,
-                                        state.data_ptr(), ids.data_ptr(), tracks.data_ptr(), ost.data_ptr(), stream_ptr()), what)
-        if RECORDER is not None:
-            RECORDER.keep.extend([b, st, state])
-    return _link_boxes_split(ids, tracks, ost, state.view(S, -1), one, first)
+    return _link_boxes(_DEV, boxes, stats, iou, max_gap, predict, max_tracks, state, t0, out)
 
 
 def link_boxes_host(boxes, stats, iou=(3, 10), max_gap: int = 2, predict: int = 1, max_tracks: int = 1024, state=None, t0=0, out=None):
     """`link_boxes` on the CPU by the same code (fusg_link_boxes_host; no GPU needed): int32 numpy tables in and out.  A state that
     is passed in is updated in place."""
-    what = "link_boxes_host"
-    as_np = lambda x: [_np.asarray(v) for v in x] if isinstance(x, (list, tuple)) else _np.asarray(x)  # noqa: E731
-    b, st, one, S, K, first, t0a, par = _link_boxes_args(as_np(boxes), as_np(stats), iou, max_gap, predict, max_tracks, t0, _np, what)
+    return _link_boxes(_HOST, boxes, stats, iou, max_gap, predict, max_tracks, state, t0, out)
+
+
+def _link_boxes(wh, boxes, stats, iou, max_gap, predict, max_tracks, state, t0, out):
+    what = "link_boxes" + wh.tag
+    b, st, one, S, K, first, t0a, par = _link_boxes_args(wh.arrays(boxes), wh.arrays(stats), iou, max_gap, predict, max_tracks, t0, wh, what)
+    if not wh.near(st, b):
+        raise ValueError(f"{what}: stats is on {st.device}, boxes on {b.device}")
     N, F = par[4], int(first[-1])
     if not 1 <= N <= 2 ** 20:
         raise ValueError(f"{what}: max_tracks = {N} (1..{2 ** 20})")
     shapes = ((F, K), (S, N, 4), (S, 4))
-    ok = lambda o, s: isinstance(o, _np.ndarray) and o.dtype == _np.int32 and o.shape == s and o.flags.c_contiguous  # noqa: E731
-    if out is not None and not all(ok(o, s) for o, s in zip(out, shapes)):
-        raise ValueError(f"{what}: out must be contiguous int32 arrays of {shapes}")
-    if state is not None and not ok(state, (S, LINK_BOXES_STATE_WORDS)) and not (one and ok(state, (LINK_BOXES_STATE_WORDS,))):
-        raise ValueError(f"{what}: state must be a contiguous int32 array of {(S, LINK_BOXES_STATE_WORDS)}")
-    if state is None:
-        state = _np.zeros((S, LINK_BOXES_STATE_WORDS), dtype=_np.int32)
-    ids, tracks, ost = out if out is not None else (_np.zeros(shapes[0], dtype=_np.int32), _np.zeros(shapes[1], dtype=_np.int32),
-                                                    _np.zeros(shapes[2], dtype=_np.int32))
-    b, st = _np.ascontiguousarray(b), _np.ascontiguousarray(st)
-    L.check(L.lib().fusg_link_boxes_host(b.ctypes.data, st.ctypes.data, first.ctypes.data, t0a.ctypes.data, S, K, *par, state.ctypes.data,
-                                         ids.ctypes.data, tracks.ctypes.data, ost.ctypes.data), what)
+    if out is not None and not all(_fits(wh, o, wh.i32, s, b) for o, s in zip(out, shapes)):
+        raise ValueError(f"{what}: out must be contiguous int32 {wh.noun}s of {shapes}{wh.at(b)}")
+    if state is not None and not _fits(wh, state, wh.i32, (S, LINK_BOXES_STATE_WORDS), b) \
+            and not (one and _fits(wh, state, wh.i32, (LINK_BOXES_STATE_WORDS,), b)):
+        raise ValueError(f"{what}: state must be a contiguous int32 {wh.noun} of {(S, LINK_BOXES_STATE_WORDS)}{wh.at(b)}")
+    with wh.side(b, "boxes") as up:
+        if state is None:
+            state = wh.zeros((S, LINK_BOXES_STATE_WORDS), wh.i32, b)
+        ids, tracks, ost = out if out is not None else (wh.empty(shapes[0], wh.i32, b), wh.zeros(shapes[1], wh.i32, b),
+                                                        wh.empty(shapes[2], wh.i32, b))
+        _call(wh, what, "fusg_link_boxes", wh.ptr(up(b)), wh.ptr(up(st)), first.ctypes.data, t0a.ctypes.data, S, K, *par,
+              wh.ptr(up(state)), wh.ptr(ids), wh.ptr(tracks), wh.ptr(ost))
     return _link_boxes_split(ids, tracks, ost, state.reshape(S, -1), one, first)
 
 

@@ -1749,6 +1749,11 @@ class VehiclePipeline:
             raise ValueError(f"estimate_background: {n} scenes, max_frames = {max_frames} (at least one scene, max_frames in 1..64)")
         return list(range(n)) if n <= max_frames else [(i * n) // max_frames for i in range(max_frames)]
 
+    def _background_sample(self, scenes, max_frames: int, min_valid: Optional[int]) -> Tuple[List[int], int]:
+        """(the scenes `background_indices` samples, min_valid with its default: max(1, T // 8) of the T sampled)."""
+        idx = self.background_indices(len(scenes), max_frames)
+        return idx, max(1, len(idx) // 8) if min_valid is None else int(min_valid)
+
     def estimate_background(self, scenes, max_frames: int = 64, margin: int = 8, min_valid: Optional[int] = None) -> Dict:
         """The 'background' the default mode's composites start from (`_paste_base`; the reference reads background_frame.png,
         trajectory_inference.py:42-53, and has no code that makes it), estimated from the video itself: per pixel and channel the
@@ -1760,9 +1765,7 @@ class VehiclePipeline:
         import numpy as np
 
         from . import ops
-        idx = self.background_indices(len(scenes), max_frames)
-        T = len(idx)
-        mv = max(1, T // 8) if min_valid is None else int(min_valid)
+        idx, mv = self._background_sample(scenes, max_frames, min_valid)
         boxes = [np.asarray(scenes[i]["bboxes"]).reshape(-1, 4) for i in idx]
         bg, count = ops.background_median([scenes[i]["frame"] for i in idx], boxes, margin=margin, min_valid=mv)
         return {"background": bg, "count": count, "frames": idx, "min_valid": mv}
@@ -1800,28 +1803,42 @@ class VehiclePipeline:
         synthetic scenes only).  Boxes are per frame (`track_vehicles` links them across frames), and the read-back is the only way
         the boxes reach `foreground_inpaint`.  Nothing is put into the scenes."""
         from . import ops
-        frames = [s["frame"] for s in scenes]
-        if not frames:
+        if not scenes:
             return []
-        one = hasattr(background, "shape") and len(background.shape) == 3
-        rows = []
-        for a in range(0, len(frames), ops.BACKGROUND_MAX_FRAMES):
-            b = min(len(frames), a + ops.BACKGROUND_MAX_FRAMES)
-            boxes, box_stats, stats = ops.foreground_boxes(frames[a:b], background if one else [background[f] for f in range(a, b)], **params)
-            rows.append(torch.cat([boxes.view(b - a, -1), box_stats.view(b - a, -1), stats], dim=1))
+        rows = [self._pack_frame_tables(*tables) for tables in self._detect_windows(scenes, background, params)]
         return self._detected_rows(ops.d2h(rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)))
 
     @staticmethod
-    def _detected_rows(table) -> list:
+    def _detect_windows(scenes, background, params):
+        """`ops.foreground_boxes` over a video's scenes in windows of at most `ops.BACKGROUND_MAX_FRAMES` (background: one for all
+        scenes, or one per scene): yields each window's device tables (boxes, box_stats, stats), launched when it is asked for."""
+        from . import ops
+        one = hasattr(background, "shape") and len(background.shape) == 3
+        for a in range(0, len(scenes), ops.BACKGROUND_MAX_FRAMES):
+            b = min(len(scenes), a + ops.BACKGROUND_MAX_FRAMES)
+            yield ops.foreground_boxes([s["frame"] for s in scenes[a:b]], background if one else [background[f] for f in range(a, b)], **params)
+
+    @staticmethod
+    def _pack_frame_tables(boxes, mid, stats) -> torch.Tensor:
+        """Per-frame device tables - boxes [T, K, 4], a [T, K] or [T, K, c] table and stats [T, 4] - side by side as ONE int32 row
+        per frame, [T, (4 + c) K + 4], so that one `ops.d2h` reads them all; `_unpack_frame_tables` takes the read-back apart again."""
+        return torch.cat([boxes.flatten(1), mid.flatten(1), stats], dim=1)
+
+    @staticmethod
+    def _unpack_frame_tables(table, K: int, c: int):
+        T = table.shape[0]
+        return table[:, :4 * K].reshape(T, K, 4), table[:, 4 * K:(4 + c) * K].reshape(T, K, c), table[:, (4 + c) * K:]
+
+    @classmethod
+    def _detected_rows(cls, table) -> list:
         """`detect_vehicles`' read-back, int32 [T, 6 K + 4] = per frame K boxes, K (area, n_cells) and the four stats -> the rows
         of each frame that hold a box (the first min(n_kept, K))."""
         import numpy as np
         K = (table.shape[1] - 4) // 6
         out = []
-        for row in table:
-            v = min(int(row[6 * K]), K)
-            out.append({"bboxes": row[:4 * K].reshape(K, 4)[:v].astype(np.int64), "area": row[4 * K:6 * K].reshape(K, 2)[:v, 0].astype(np.int64),
-                        "stats": row[6 * K:].copy()})
+        for boxes, box_stats, stats in zip(*cls._unpack_frame_tables(table, K, 2)):
+            v = min(int(stats[0]), K)
+            out.append({"bboxes": boxes[:v].astype(np.int64), "area": box_stats[:v, 0].astype(np.int64), "stats": stats.copy()})
         return out
 
     def bootstrap_background(self, scenes, max_frames: int = 64, margin: int = 8, rounds: int = 1, min_valid: Optional[int] = None,
@@ -1835,9 +1852,7 @@ class VehiclePipeline:
         import numpy as np
 
         from . import ops
-        idx = self.background_indices(len(scenes), max_frames)
-        T = len(idx)
-        mv = max(1, T // 8) if min_valid is None else int(min_valid)
+        idx, mv = self._background_sample(scenes, max_frames, min_valid)
         sampled = [scenes[i] for i in idx]
         frames = [s["frame"] for s in sampled]
         bg, count = ops.background_median(frames, None, margin=margin, min_valid=mv)
@@ -1879,24 +1894,18 @@ class VehiclePipeline:
             return empty[0] if one else empty
         dev = bgs[0].device
         state = tracks = ost = None
-        parts = []                                                 # per window and camera: [frames, 6 K + 4 ... ] rows
+        parts = []                                                 # per window and camera: [frames, 5 K + 4] rows
+        none = (torch.zeros((0, K, 4), dtype=torch.int32, device=dev), None, torch.zeros((0, 4), dtype=torch.int32, device=dev))
+        windows = [self._detect_windows(v, bgs[s], params) for s, v in enumerate(videos)]
         for a in range(0, max(lens), W):
-            wb, ws = [], []
-            for s, v in enumerate(videos):
-                b = min(len(v), a + W)
-                if b > a:
-                    boxes, _, stats = ops.foreground_boxes([sc["frame"] for sc in v[a:b]], bgs[s], **params)
-                else:
-                    boxes, stats = torch.zeros((0, K, 4), dtype=torch.int32, device=dev), torch.zeros((0, 4), dtype=torch.int32, device=dev)
-                wb.append(boxes)
-                ws.append(stats)
+            wb, _, ws = zip(*[next(w, none) for w in windows])     # a camera that has ended brings no frames
             if state is None:
                 tracks = torch.zeros((S, N, 4), dtype=torch.int32, device=dev)
                 ost = torch.zeros((S, 4), dtype=torch.int32, device=dev)
             ids = torch.empty((sum(int(x.shape[0]) for x in wb), K), dtype=torch.int32, device=dev)
             idl, tracks, ost, state = ops.link_boxes(wb, ws, iou=iou, max_gap=max_gap, predict=predict, max_tracks=N, state=state, t0=a,
                                                      out=(ids, tracks, ost))
-            parts.append([torch.cat([x.reshape(x.shape[0], 4 * K), i, y], dim=1) for x, i, y in zip(wb, idl, ws)])
+            parts.append([self._pack_frame_tables(x, i, y) for x, i, y in zip(wb, idl, ws)])
         flat = torch.cat([p.reshape(-1) for w in parts for p in w] + [tracks.reshape(-1), ost.reshape(-1)])
         host = ops.d2h(flat)
         rows, pos = [[] for _ in videos], 0
@@ -1909,13 +1918,14 @@ class VehiclePipeline:
         out = [self._tracked_rows(np.concatenate(rows[s]), tr[s], st[s], K, int(min_hits)) for s in range(S)]
         return out[0] if one else out
 
-    @staticmethod
-    def _tracked_rows(table, tracks, stats, K: int, min_hits: int) -> Dict:
+    @classmethod
+    def _tracked_rows(cls, table, tracks, stats, K: int, min_hits: int) -> Dict:
         """`track_vehicles`' read-back of one camera, int32 [T, 5 K + 4] = per frame K boxes, K ids and the detector's stats -> its
         dict: the rows of the tracks with at least min_hits observations, in the reference's (frame, id, x, y, w, h) form."""
         import numpy as np
         T = table.shape[0]
-        boxes, ids, box_stats = table[:, :4 * K].reshape(T, K, 4), table[:, 4 * K:5 * K], table[:, 5 * K:]
+        boxes, ids, box_stats = cls._unpack_frame_tables(table, K, 1)
+        ids = ids[:, :, 0]
         keep = (ids >= 0) & (tracks[np.maximum(ids, 0), 2] >= min_hits)
         f, k = np.nonzero(keep)                                    # row-major: by frame, then detection
         b = boxes[f, k].astype(np.float64)

@@ -8,33 +8,10 @@
 // tables of exactly K rows, so that any access outside an image or a table is one outside an exactly-sized heap buffer.  Every
 // frame's n_P equals the count made here, the kept boxes lie inside the roi and are not empty, their areas add up to no more
 // than n_P, the rows past the last box are zeros; a checkerboard of cells is truncated at 256; bad arguments are refused.
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <functional>
 #include <vector>
-#include <hip/hip_runtime.h>
-#include "../../include/fusg.h"
-
-namespace fusg {                                    // what the translation unit expects of the rest of the library
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    std::fputc('\n', stderr);
-}
-bool plan_recording() { return false; }
-void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
-int32_t route_batch_now() { return 0; }
-struct RouteBatchScope {
-    int32_t prev;
-    explicit RouteBatchScope(int32_t r);
-    ~RouteBatchScope();
-};
-RouteBatchScope::RouteBatchScope(int32_t) : prev(0) {}
-RouteBatchScope::~RouteBatchScope() {}
-}  // namespace fusg
+#include "fusg_stubs.h"
 
 static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 

@@ -8,33 +8,10 @@
 // mask buffer of exactly the bytes the accepted boxes take, with refused boxes (out of the frame, over the bound, out of the
 // buffer) between them.  Every mask byte is 0 or 255, n_mask counts the 255s, a refused box is flagged and nothing else; the erase
 // equals the rule written out here, overlapping boxes included; bad arguments are refused.
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <functional>
 #include <vector>
-#include <hip/hip_runtime.h>
-#include "../../include/fusg.h"
-
-namespace fusg {                                    // what the translation unit expects of the rest of the library
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    std::fputc('\n', stderr);
-}
-bool plan_recording() { return false; }
-void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
-int32_t route_batch_now() { return 0; }
-struct RouteBatchScope {
-    int32_t prev;
-    explicit RouteBatchScope(int32_t r);
-    ~RouteBatchScope();
-};
-RouteBatchScope::RouteBatchScope(int32_t) : prev(0) {}
-RouteBatchScope::~RouteBatchScope() {}
-}  // namespace fusg
+#include "fusg_stubs.h"
 
 static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 

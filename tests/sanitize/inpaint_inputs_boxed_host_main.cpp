@@ -6,27 +6,12 @@
 // The frame-form program's three vehicles on its 70 x 90 frame, their masks packed box by box into exactly-sized heap buffers
 // (uint8, and float32 with a NaN), so that any read outside a packed mask is reported; the outputs must equal the frame form's
 // byte for byte, and a buffer one element short, a negative offset and an offset past the end are refused before anything is read.
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
-#include <functional>
 #include <vector>
-#include <hip/hip_runtime.h>
-#include "../../include/fusg.h"
-
-namespace fusg {                                    // what the translation unit expects of the rest of the library
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    std::fputc('\n', stderr);
-}
-bool plan_recording() { return false; }
-void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
-}  // namespace fusg
+#include "fusg_stubs.h"
 
 static fusg_tensor desc(void* p, int dtype, long n, long c, long h, long w, long sn, long sc, long sh, long sw) {
     fusg_tensor t{};

@@ -6,27 +6,12 @@
 // It runs three vehicles on a 70 x 90 frame (a box in the frame's corner with a blob on its border, a 5 x 7 box, a zero-extent
 // box) with exactly-sized heap buffers, so that any read or write outside the frame, the masks, the outputs or the scratch is
 // reported, and prints a checksum of the outputs.
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
-#include <functional>
 #include <vector>
-#include <hip/hip_runtime.h>
-#include "../../include/fusg.h"
-
-namespace fusg {                                    // what the translation unit expects of the rest of the library
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    std::fputc('\n', stderr);
-}
-bool plan_recording() { return false; }
-void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
-}  // namespace fusg
+#include "fusg_stubs.h"
 
 static fusg_tensor desc(void* p, int dtype, long n, long c, long h, long w, long sn, long sc, long sh, long sw) {
     fusg_tensor t{};

@@ -6,25 +6,10 @@
 // It runs J = 1, 9 and 200 rows at P = 5 and 7 with exactly-sized heap buffers (counts [J][7][2], covered [J], dst_vis [J][P],
 // valid [J], box rows [J][8]), so that any read or write outside them is reported, compares every output with the rule written
 // out here, and checks that J = 0 touches nothing and that bad arguments are refused.
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <functional>
 #include <vector>
-#include <hip/hip_runtime.h>
-#include "../../include/fusg.h"
-
-namespace fusg {                                    // what the translation unit expects of the rest of the library
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    std::fputc('\n', stderr);
-}
-bool plan_recording() { return false; }
-void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
-}  // namespace fusg
+#include "fusg_stubs.h"
 
 int main() {
     long visible = 0, invalid = 0;

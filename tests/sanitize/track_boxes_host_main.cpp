@@ -8,34 +8,11 @@
 // cut into two calls at every frame boundary; random videos with coordinates up to the bound (the int64 products at their
 // largest) whose ids stay inside [-1, n_tracks) and are -1 from n_t on; a refused call; bad arguments.
 #include <array>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <functional>
 #include <string>
 #include <vector>
-#include <hip/hip_runtime.h>
-#include "../../include/fusg.h"
-
-namespace fusg {                                    // what the translation unit expects of the rest of the library
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    std::fputc('\n', stderr);
-}
-bool plan_recording() { return false; }
-void plan_append(hipStream_t, std::function<int(hipStream_t)>) {}
-int32_t route_batch_now() { return 0; }
-struct RouteBatchScope {
-    int32_t prev;
-    explicit RouteBatchScope(int32_t r);
-    ~RouteBatchScope();
-};
-RouteBatchScope::RouteBatchScope(int32_t) : prev(0) {}
-RouteBatchScope::~RouteBatchScope() {}
-}  // namespace fusg
+#include "fusg_stubs.h"
 
 using Box = std::array<int32_t, 4>;
 using Frame = std::vector<Box>;
