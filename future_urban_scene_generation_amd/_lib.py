@@ -117,6 +117,10 @@ _SIGS = {
     "fusg_in_finalize_slots": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fusg_ln_finalize_slots": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fusg_up2_edge_entries": (C.c_int, [C.c_int32, C.c_int32]),
+    "fusg_up2_edge_fix": (C.c_int, [_TP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, _TP, C.c_void_p, C.c_int32, C.c_void_p]),
+    "fusg_ln_finalize_slots_delta": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fusg_affine_act": (C.c_int, [_TP, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, _TP, _TP, C.c_void_p]),
     "fusg_maxpool2": (C.c_int, [_TP, _TP, C.c_void_p]),
     "fusg_upsample2_add": (C.c_int, [_TP, _TP, _TP, C.c_void_p]),

@@ -426,9 +426,11 @@ static int route_conv(fusg_conv_desc* d, ConvRoute* r) {
         r->vec_epi = v ? 1 : 0;
     }
     if (d->stats_out) {
-        if (!(r->vec_epi && d->act == FUSG_ACT_NONE && !d->res0.data && !d->res1.data && d->store_mode == FUSG_STORE_NORMAL &&
+        // a DepthToSpace store only changes the store address (chan_offsets / pix_offsets): the slots are then per stacked column
+        if (!(r->vec_epi && d->act == FUSG_ACT_NONE && !d->res0.data && !d->res1.data &&
+              (d->store_mode == FUSG_STORE_NORMAL || d->store_mode == FUSG_STORE_D2S) &&
               nphase == 1 && d->ksplit <= 1 && ((long)d->qh * d->qw) % 32 == 0)) {
-            set_error("conv2d: fused statistics need act NONE, no residual, NORMAL store, nphase 1, ksplit 1, qh*qw%%32==0 "
+            set_error("conv2d: fused statistics need act NONE, no residual, NORMAL or D2S store, nphase 1, ksplit 1, qh*qw%%32==0 "
                       "and a channel-contiguous aligned dst with cout%%4==0");
             return FUSG_ERR_UNSUPPORTED;
         }

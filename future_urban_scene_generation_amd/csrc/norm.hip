@@ -198,9 +198,66 @@ __global__ __launch_bounds__(1024) void ln_finalize_slots_kernel(const float* __
     }
 }
 
+// The same for slots over `cols` stacked columns (a DepthToSpace launch: cols = 4 C, the same multiset of values) of an image
+// whose border ring then changed by fusg_up2_edge_fix: delta [B][nent][2] = (sum of the changes, sum of change * (2 old + change))
+// per workgroup of that pass, i.e. what the image's sum and sum of squares gained.  The one-pass fp64 moments above give
+// S1 = 32 sum(mean_s) and S2 = sum(M2_s) + 32 sum(mean_s^2); the deltas are added, in entry order, before mean and unbiased std.
+__global__ __launch_bounds__(1024) void ln_finalize_slots_delta_kernel(const float* __restrict__ slots, int nslots, int cols, int C,
+                                                                       float eps, const float* __restrict__ gamma,
+                                                                       const float* __restrict__ beta, const double* __restrict__ delta,
+                                                                       int nent, float* __restrict__ scale, float* __restrict__ shift) {
+    __shared__ double red[3][1024];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const long total = (long)nslots * cols;               // (slot, column) pairs, 32 pixels each
+    const float2* s = (const float2*)slots + (long)b * total;
+    double sm = 0.0, sq = 0.0, s2 = 0.0;
+#pragma unroll 4
+    for (long k = t; k < total; k += 1024) {
+        const float2 v = s[k];
+        sm += (double)v.x;
+        sq += (double)v.x * (double)v.x;
+        s2 += (double)v.y;
+    }
+    red[0][t] = sm; red[1][t] = sq; red[2][t] = s2;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if (t < w) { red[0][t] += red[0][t + w]; red[1][t] += red[1][t + w]; red[2][t] += red[2][t + w]; }
+        __syncthreads();
+    }
+    double d1 = 0.0, d2 = 0.0;                            // every thread sums the few entries itself, in order
+    for (int k = 0; k < nent; ++k) { d1 += delta[((long)b * nent + k) * 2]; d2 += delta[((long)b * nent + k) * 2 + 1]; }
+    const double n = 32.0 * (double)total;
+    const double S1 = 32.0 * red[0][0] + d1;
+    const double mean = S1 / n;
+    // centred about the slots' own mean m0 (sum x^2 - n mean^2 in raw sums would cancel at mean >> std):
+    // sum (x - m0)^2 of the old image = M2 part; the change adds d2 - 2 m0 d1; then re-centre from m0 to the new mean
+    const double m0 = red[0][0] / (double)total;
+    double m2 = red[2][0] + 32.0 * (red[1][0] - red[0][0] * m0) + (d2 - 2.0 * m0 * d1) - n * (mean - m0) * (mean - m0);
+    if (m2 < 0.0) m2 = 0.0;
+    const double sd = sqrt(m2 / (n - 1.0));                                // unbiased std
+    const double inv = 1.0 / (sd + (double)eps);
+    for (int c = t; c < C; c += 1024) {
+        const double sc = (double)gamma[c] * inv;
+        scale[(long)b * C + c] = (float)sc;
+        shift[(long)b * C + c] = (float)((double)beta[c] - mean * sc);
+    }
+}
+
 }  // namespace fusg
 
 using namespace fusg;
+
+static int ln_finalize_slots_delta_impl(const float* slots, int32_t batch, int32_t nslots, int32_t columns, int32_t channels, float eps,
+                                        const float* gamma, const float* beta, const double* delta, int32_t n_entries,
+                                        float* scale, float* shift, void* stream) {
+    FUSG_CHECK(slots && scale && shift && gamma && beta && delta && batch >= 1 && nslots >= 1 && columns >= 1 && channels >= 1 &&
+               n_entries >= 1 && (long)nslots * columns * 32 > 1, "ln_finalize_slots_delta: bad arguments");
+    hipLaunchKernelGGL(ln_finalize_slots_delta_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, slots, nslots,
+                       columns, channels, eps, gamma, beta, delta, n_entries, scale, shift);
+    FUSG_LAUNCH_CHECK("ln_finalize_slots_delta");
+    return FUSG_OK;
+}
+extern "C" int fusg_ln_finalize_slots_delta(const float* slots, int32_t batch, int32_t nslots, int32_t columns, int32_t channels, float eps, const float* gamma, const float* beta, const double* delta, int32_t n_entries, float* scale, float* shift, void* stream) { return fusg::plan_dispatch(ln_finalize_slots_delta_impl, stream, slots, batch, nslots, columns, channels, eps, gamma, beta, delta, n_entries, scale, shift); }
 
 static int in_finalize_slots_impl(const float* slots, int32_t batch, int32_t nslots, int32_t channels, float eps,
                                       float* scale, float* shift, void* stream) {

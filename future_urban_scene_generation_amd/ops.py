@@ -551,7 +551,7 @@ def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *,
          ksplit: int = 0, precision: Optional[str] = None, want_stats: bool = False,
          out_stride: int = 1, out_off: Tuple[int, int] = (0, 0), tiles: Optional[torch.Tensor] = None,
          q_window: Optional[Tuple[int, int, int, int]] = None, q_size: Optional[Tuple[int, int]] = None,
-         stats_into: Optional[Tuple[torch.Tensor, int]] = None, tap_sparse: Optional[int] = None):
+         stats_into: Optional[Tuple[torch.Tensor, int]] = None, tap_sparse: Optional[int] = None, stats_d2s: bool = False):
     """One fused convolution launch (fusg_conv2d).  Returns the output tensor (allocated NHWC-physical
     unless `out` is given or `nchw_out` asks for a standard-contiguous NCHW result).
     out_stride / out_off: write output pixel (qy, qx) at (qy*out_stride + out_off[0], qx*out_stride + out_off[1])
@@ -560,7 +560,9 @@ def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *,
     same positions of `out`, which must be given).  q_size = (qh, qw): output grid of a launch whose padding is not
     symmetric (transposed-conv phases; zero padding only).  stats_into = (buffer [B, slots, cout, 2], first_slot): write
     this launch's fused statistics slots there (the launch must qualify).  tap_sparse: the fusg_conv_desc.tap_sparse pattern
-    of this launch (0 runs a tap-sparse plan's weights dense: same bytes); None: the plan's if TAP_SPARSE_LAUNCH, else 0."""
+    of this launch (0 runs a tap-sparse plan's weights dense: same bytes); None: the plan's if TAP_SPARSE_LAUNCH, else 0.
+    stats_d2s: with want_stats, a DepthToSpace launch may fuse its statistics too - the slots are then per STACKED column
+    ([B, slots, plan.cout = 4 C, 2]: the same multiset of values per image, which is all LayerNorm needs; conv_up2 asks for it)."""
     d, out = _conv_desc(plan, x0, x1, out=out, out_c_off=out_c_off, res0=res0, res1=res1, pre_op=pre_op, pre=pre,
                         pre_bstride=pre_bstride, act=act, store=store, nchw_out=nchw_out, tile=tile, ksplit=ksplit,
                         precision=precision, want_stats=want_stats, out_stride=out_stride, out_off=out_off, tiles=tiles,
@@ -583,13 +585,16 @@ def conv(plan: ConvPlan, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, *,
     if want_stats:
         # fused norm statistics when the launch qualifies (include/fusg.h, stats_out: no tile list, no window origin
         # either); else the caller falls back to the separate streaming pass
-        if (d.ksplit <= 1 and plan.nphase == 1 and store == L.STORE_NORMAL and act == L.ACT_NONE and res0 is None
+        # (a DepthToSpace store only moves the stores; its 16-byte epilogue needs cout/4 % 4 == 0)
+        if (d.ksplit <= 1 and plan.nphase == 1 and (store == L.STORE_NORMAL or (stats_d2s and store == L.STORE_D2S and plan.cout % 16 == 0))
+                and act == L.ACT_NONE and res0 is None
                 and res1 is None and (qh * qw) % 32 == 0 and plan.cout % 4 == 0 and out_c_off % 4 == 0 and is_nhwc(out)
                 and out.stride(3) % 4 == 0 and not _env_set("FUSG_NO_VEC_EPI") and q_window is None and tiles is None):
             stats = torch.empty((b, qh * qw // 32, plan.cout, 2), device=x0.device, dtype=torch.float32)
             d.stats_out = stats.data_ptr()
     if stats_into is not None:
         buf, first = stats_into
+        assert store == L.STORE_NORMAL                # (slots of a DepthToSpace launch are per stacked column: want_stats + stats_d2s)
         assert buf.dtype == torch.float32 and buf.is_contiguous() and buf.shape[0] == b and buf.shape[2] == plan.cout
         assert (qh * qw) % 32 == 0 and first + qh * qw // 32 <= buf.shape[1]
         d.stats_out = buf.data_ptr() + first * plan.cout * 2 * 4
@@ -902,8 +907,36 @@ def up2_phases_ok(x: torch.Tensor, precision: Optional[str] = None) -> bool:
     return h >= 2 and w >= 2 and _os.environ.get("FUSG_NO_UP2_PHASES") is None
 
 
+def up2_edge_ok(edge, phases, x: torch.Tensor, pre_op: int, ring) -> bool:
+    """Does `conv_up2` correct the border ring additively (fusg_up2_edge_fix)?  The single DepthToSpace phase plan, the edge
+    taps packed (pack.pack_conv_up2_edge: cin % 32, cout % 16), pre-op NONE or AFFINE_RELU.  FUSG_NO_UP2_EDGE=1, read per call,
+    restores the four 25-tap windows."""
+    return (edge is not None and isinstance(phases, ConvPlan) and ring is None and not _env_set("FUSG_NO_UP2_EDGE")
+            and pre_op in (L.PRE_NONE, L.PRE_AFFINE_RELU) and x.shape[1] == edge.cin and is_nhwc(x))
+
+
+def up2_edge_fix(edge, x: torch.Tensor, out: torch.Tensor, *, pre_op: int = L.PRE_NONE, pre=None, pre_bstride: int = 0,
+                 want_delta: bool = False) -> Optional[torch.Tensor]:
+    """out += conv5x5(reflect-padded - replicate-padded up2(f(x))) on the outermost ring, in place (fusg_up2_edge_fix); with
+    want_delta returns [B, entries, 2] float64 = per workgroup (sum of the changes, sum of change * (2 old + change))."""
+    b, c, h, w = x.shape
+    lib = L.lib()
+    delta, n = None, 0
+    if want_delta:
+        n = int(lib.fusg_up2_edge_entries(h, w))
+        delta = torch.empty((b, n, 2), device=x.device, dtype=torch.float64)
+    if RECORDER is not None:
+        RECORDER.keep.append(edge.w)
+        if pre is not None:
+            RECORDER.keep.append(pre)
+    L.check(lib.fusg_up2_edge_fix(C.byref(desc(x)), int(pre_op), pre[0].data_ptr() if pre is not None else None,
+                                  pre[1].data_ptr() if pre is not None else None, int(pre_bstride), edge.w.data_ptr(),
+                                  C.byref(desc(out)), delta.data_ptr() if delta is not None else None, n, stream_ptr()), "up2_edge_fix")
+    return delta
+
+
 def conv_up2(exact: ConvPlan, phases, x: torch.Tensor, *, pre_op: int = L.PRE_NONE, pre=None, pre_bstride: int = 0,
-             precision: Optional[str] = None, ring: Optional[dict] = None) -> torch.Tensor:
+             precision: Optional[str] = None, ring: Optional[dict] = None, edge=None, ln=None):
     """nn.Upsample(2) -> ReflectionPad2d(2) -> 5x5 conv.  `exact` = the 25-tap plan with the upsample fused into its
     gather (pack_conv(..., upsample=1)); `phases` = pack_conv_up2_d2s (one launch) or pack_conv_up2_phases (four) of the same filter.  When the shapes qualify,
     four 3x3 phase launches on the low-res input (9 MACs per output instead of 25) write the interleaved output; the
@@ -912,15 +945,41 @@ def conv_up2(exact: ConvPlan, phases, x: torch.Tensor, *, pre_op: int = L.PRE_NO
     (pack.pack_conv_up2_ring) - by twelve small 3x3 launches whose weights are regrouped for the border (9 MACs there
     too).  Measured (round 3, same card): the twelve launches, eight of them 32 - 4000 output pixels small, cost as much as the
     four efficient 25-tap windows (conv 23.2 vs 23.3 - 23.7 ms per step, 1437 vs 1426 crops/s), so the networks do not
-    pass `ring` unless FUSG_UP2_RING9 is set."""
+    pass `ring` unless FUSG_UP2_RING9 is set.
+    `edge` (pack.pack_conv_up2_edge) where up2_edge_ok: the ring is not recomputed at all - the phase form is the convolution
+    of the REPLICATE-padded image everywhere, and fusg_up2_edge_fix adds the convolution of (reflect - replicate), which lives
+    on the ring and uses the 5 (corner: 9) taps on the padding frame only.
+    `ln` = (gamma, beta, eps): also return the ICN LayerNorm's (scale, shift) of the result -> (out, (scale, shift)).  On the
+    edge route they come from the phase launch's epilogue slots plus the two sums per workgroup of the ring correction
+    (fusg_ln_finalize_slots_delta) where the launch qualifies for fused statistics; else from layernorm_stats."""
+    def with_ln(o, ss=None):
+        if ln is None:
+            return o
+        return o, (ss if ss is not None else layernorm_stats(o, ln[0], ln[1], ln[2]))
+
     if phases is None or not up2_phases_ok(x, precision):
-        return conv(exact, x, pre_op=pre_op, pre=pre, pre_bstride=pre_bstride, precision=precision)
+        return with_ln(conv(exact, x, pre_op=pre_op, pre=pre, pre_bstride=pre_bstride, precision=precision))
     b, c, h, w = x.shape
     out = nhwc_empty(b, exact.cout, 2 * h, 2 * w, x.device)
     # split-K launches do not use the halo kernel: keep K whole where the phase launches qualify for it
     halo = (((precision or PRECISION) in ("f16x3", "bf16", "f16") or ((precision or PRECISION) == "f32" and not _env_set("FUSG_NO_F32_HALO")))
             and c % 32 == 0 and h % 8 == 0 and w % 16 == 0 and _os.environ.get("FUSG_NO_HALO") is None)
-    if isinstance(phases, ConvPlan):                               # all four phases in one launch, DepthToSpace store
+    if up2_edge_ok(edge, phases, x, pre_op, ring):
+        r = conv(phases, x, out=out, store=L.STORE_D2S, pre_op=pre_op, pre=pre, pre_bstride=pre_bstride,
+                 precision=precision, ksplit=1 if halo else 0, want_stats=ln is not None, stats_d2s=True)
+        stats = r[1] if ln is not None else None
+        if ln is None or stats is not None:
+            delta = up2_edge_fix(edge, x, out, pre_op=pre_op, pre=pre, pre_bstride=pre_bstride, want_delta=stats is not None)
+            if ln is None:
+                return out
+            nslots, cols = stats.shape[1], stats.shape[2]
+            ss = torch.empty((2, b, exact.cout), device=x.device, dtype=torch.float32)
+            L.check(L.lib().fusg_ln_finalize_slots_delta(stats.data_ptr(), b, nslots, cols, exact.cout, float(ln[2]), ln[0].data_ptr(),
+                                                         ln[1].data_ptr(), delta.data_ptr(), delta.shape[1], ss[0].data_ptr(),
+                                                         ss[1].data_ptr(), stream_ptr()), "ln_finalize_slots_delta")
+            return out, (ss[0], ss[1])
+        # the phase launch does not qualify for fused statistics (split K, qh*qw % 32): today's windows and streamed statistics
+    elif isinstance(phases, ConvPlan):                             # all four phases in one launch, DepthToSpace store
         conv(phases, x, out=out, store=L.STORE_D2S, pre_op=pre_op, pre=pre, pre_bstride=pre_bstride,
              precision=precision, ksplit=1 if halo else 0)
     else:
@@ -933,11 +992,11 @@ def conv_up2(exact: ConvPlan, phases, x: torch.Tensor, *, pre_op: int = L.PRE_NO
             if win[2] > 0 and win[3] > 0:
                 conv(ring[(ry, rx)], x, out=out, q_window=win, out_stride=2, out_off=off, pre_op=pre_op, pre=pre,
                      pre_bstride=pre_bstride, precision=precision)
-        return out
+        return with_ln(out)
     # the outermost ring of output pixels, with the 25-tap form: four one-pixel-wide windows of the full convolution
     for win in ((0, 0, 1, 2 * w), (2 * h - 1, 0, 1, 2 * w), (0, 0, 2 * h, 1), (0, 2 * w - 1, 2 * h, 1)):
         conv(exact, x, out=out, q_window=win, pre_op=pre_op, pre=pre, pre_bstride=pre_bstride, precision=precision)
-    return out
+    return with_ln(out)
 
 
 def conv_transpose_phases(phases, x: torch.Tensor, *, pre_op: int = L.PRE_NONE, pre=None, pre_bstride: int = 0,

@@ -386,6 +386,90 @@ def pack_conv_up2_ring(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> di
     return {k: pack_conv(up2_border_weights(weight, *k), bias, stride=1, pad=1, pad_mode=L.PAD_REPLICATE) for k in kinds}
 
 
+# ---- the border ring additively (fusg_up2_edge_fix, csrc/up2_edge.h) ----
+# The phase form equals the 5x5 convolution of the REPLICATE-padded upsampled image; the reflect-padded one differs from it only
+# on the outermost frame of the padded image, so the ring is corrected by the taps that land on that frame: row ky = 0 of the
+# filter on the top side, ky = 4 on the bottom, column kx = 0 on the left, kx = 4 on the right.
+UP2_EDGE_SIDES = ("top", "bottom", "left", "right")
+
+
+def up2_edge_taps(weight: torch.Tensor) -> torch.Tensor:
+    """[4 sides, 5 taps, cout, cin]: the frame taps of a [cout, cin, 5, 5] filter, side order UP2_EDGE_SIDES, tap t running along
+    the side (kx on top / bottom, ky on left / right).  Plain copies: no sums, so no summation order to fix."""
+    w = weight.detach().to("cpu")
+    assert w.shape[2] == 5 and w.shape[3] == 5, w.shape
+    return torch.stack([w[:, :, 0, :], w[:, :, 4, :], w[:, :, :, 0], w[:, :, :, 4]]).permute(0, 3, 1, 2).contiguous()
+
+
+@dataclass
+class Up2Edge:
+    """pack_conv_up2_edge's result: `w` fp32 [4, 5, cin/16, cout/16, 64, 4] in the order the kernel's lanes read it (lane
+    l = 16 g + n of 16-channel group c16 and column tile ct holds w[co = 16 ct + n][ci = 16 c16 + 4 g + e], e = 0..3)."""
+    w: torch.Tensor
+    cin: int
+    cout: int
+
+    def to(self, device) -> "Up2Edge":
+        self.w = self.w.to(device)
+        return self
+
+    def taps(self) -> torch.Tensor:
+        """Back to [4, 5, cout, cin] (what up2_edge_taps gave)."""
+        v = self.w.reshape(4, 5, self.cin // 16, self.cout // 16, 4, 16, 4)           # side, tap, c16, ct, g, n, e
+        return v.permute(0, 1, 3, 5, 2, 4, 6).reshape(4, 5, self.cout, self.cin)
+
+
+def pack_conv_up2_edge(weight: torch.Tensor) -> Optional[Up2Edge]:
+    """The frame taps of the 5x5 filter after nn.Upsample(2) -> ReflectionPad2d(2), fp32, for fusg_up2_edge_fix; None when the
+    kernel does not take the shape (cin % 32, cout % 16, cout <= 256).  No bias: the phase launch has added it."""
+    cout, cin = weight.shape[:2]
+    if cin % 32 or cout % 16 or cout > 256 or cin < 32:
+        return None
+    t = up2_edge_taps(weight.detach().to("cpu", torch.float32))                      # [4, 5, cout, cin]
+    v = t.reshape(4, 5, cout // 16, 16, cin // 16, 4, 4)                              # side, tap, ct, n, c16, g, e
+    return Up2Edge(w=v.permute(0, 1, 4, 2, 5, 3, 6).reshape(4, 5, cin // 16, cout // 16, 64, 4).contiguous(), cin=cin, cout=cout)
+
+
+def up2_edge_frame(fx: torch.Tensor):
+    """The non-zero part of D = reflect-padded - replicate-padded up2(fx), fx = f(x) [B, C, h, w]: per side the line E[P],
+    P = -2 .. L+1 (index P + 2), L = 2w (top, bottom) or 2h (left, right); the four frame corners sit at the ends of the top and
+    bottom lines and are zero on the left and right ones.  Returns [top, bottom, left, right], each [B, C, L + 4]."""
+    b, c, h, w = fx.shape
+
+    def line(a1, a0, L, corner0, corner1):
+        j = (torch.arange(-2, L + 2).clamp(0, L - 1) // 2)
+        e = (a1 - a0)[:, :, j].clone()
+        e[:, :, 0], e[:, :, L + 3] = corner0, corner1
+        return e
+
+    z = torch.zeros_like(fx[:, :, 0, 0])
+    return [line(fx[:, :, 1, :], fx[:, :, 0, :], 2 * w, fx[:, :, 1, 1] - fx[:, :, 0, 0], fx[:, :, 1, w - 2] - fx[:, :, 0, w - 1]),
+            line(fx[:, :, h - 2, :], fx[:, :, h - 1, :], 2 * w, fx[:, :, h - 2, 1] - fx[:, :, h - 1, 0],
+                 fx[:, :, h - 2, w - 2] - fx[:, :, h - 1, w - 1]),
+            line(fx[:, :, :, 1], fx[:, :, :, 0], 2 * h, z, z),
+            line(fx[:, :, :, w - 2], fx[:, :, :, w - 1], 2 * h, z, z)]
+
+
+def up2_edge_delta(taps: torch.Tensor, fx: torch.Tensor) -> torch.Tensor:
+    """What fusg_up2_edge_fix adds, in torch (any dtype): [B, cout, 2h, 2w], zero off the outermost ring.  `taps` as
+    up2_edge_taps / Up2Edge.taps give them, fx = f(x) the pre-processed low-res source."""
+    b, c, h, w = fx.shape
+    out = torch.zeros(b, taps.shape[2], 2 * h, 2 * w, dtype=fx.dtype)
+    tp = taps.to(fx.dtype)
+    for side, e in enumerate(up2_edge_frame(fx)):
+        L = e.shape[2] - 4
+        d = sum(torch.einsum("oc,bcp->bop", tp[side, t], e[:, :, t:t + L]) for t in range(5))      # [B, cout, L]
+        if side == 0:
+            out[:, :, 0, :] += d
+        elif side == 1:
+            out[:, :, 2 * h - 1, :] += d
+        elif side == 2:
+            out[:, :, :, 0] += d
+        else:
+            out[:, :, :, 2 * w - 1] += d
+    return out
+
+
 def pack_conv_up2_d2s(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> ConvPlan:
     """The four phase convolutions of up2_phase_weights stacked along the output channels - phase 2*py+px in channel
     block [(2*py+px)*cout, +cout) - as ONE 3x3 conv (edge-replicate padding 1) whose DepthToSpace store

@@ -130,7 +130,7 @@ class G_Resnet(FusedNet):
              "down": [self._pack_block(enc[1 + i], device) for i in range(nd)],
              "enc_res": self._pack_res(enc[1 + nd], device),
              "dec_res": self._pack_res(dec[0], device),
-             "up": [], "up_phases": [], "up_ring": [], "ln": [],
+             "up": [], "up_phases": [], "up_ring": [], "up_edge": [], "ln": [],
              "head": self._pack_head(dec[1 + 2 * nd], device)}
         for i in range(nd):
             blk = dec[2 + 2 * i]
@@ -145,6 +145,10 @@ class G_Resnet(FusedNet):
             # outermost ring of output pixels as twelve border-specific 3x3 launches (pack.pack_conv_up2_ring)
             P["up_ring"].append({k: v.to(device) for k, v in pack.pack_conv_up2_ring(blk.conv.weight, blk.conv.bias).items()}
                                 if ok and ops._env_set("FUSG_UP2_RING9") else None)
+            # ... and the border ring as an additive correction of the phase form: the frame taps in fp32 (pack.pack_conv_up2_edge;
+            # None where the kernel does not take the channel counts)
+            ed = pack.pack_conv_up2_edge(blk.conv.weight) if ok else None
+            P["up_edge"].append(ed.to(device) if ed is not None else None)
             P["ln"].append((dev_vec(blk.norm.gamma, device), dev_vec(blk.norm.beta, device), blk.norm.eps))
         return P
 
@@ -167,10 +171,10 @@ class G_Resnet(FusedNet):
     def _decode(self, P, y: torch.Tensor) -> torch.Tensor:
         y = self._resblocks(P["dec_res"], y)
         pre_op, pre, bs = L.PRE_NONE, None, 0
-        for p, ph, rg, (gamma, beta, eps) in zip(P["up"], P["up_phases"], P["up_ring"], P["ln"]):
+        for p, ph, rg, ed, (gamma, beta, eps) in zip(P["up"], P["up_phases"], P["up_ring"], P["up_edge"], P["ln"]):
             if ph is not None and ops.up2_phases_ok(y):
-                y = ops.conv_up2(p, ph, y, pre_op=pre_op, pre=pre, pre_bstride=bs, ring=rg)
-                pre = ops.layernorm_stats(y, gamma, beta, eps)     # the border pass rewrites pixels: no fused statistics
+                # (scale, shift) from the phase launch's epilogue plus the ring correction's sums on the edge route, else streamed
+                y, pre = ops.conv_up2(p, ph, y, pre_op=pre_op, pre=pre, pre_bstride=bs, ring=rg, edge=ed, ln=(gamma, beta, eps))
             else:
                 y, pre = ops.conv_ln(p, y, gamma, beta, eps, pre_op=pre_op, pre=pre, pre_bstride=bs)
             pre_op, bs = L.PRE_AFFINE_RELU, y.shape[1]

@@ -184,7 +184,8 @@ typedef struct fusg_conv_desc {
     /* Optional fused normalisation statistics of the conv OUTPUT (bias included): per image and per
      * 32-pixel slot (slot order is kernel-defined; finalisation is order-independent) the mean and the
      * centred sum of squares of every output channel: float [B][qh*qw/32][cout][2].  Requires
-     * act == NONE, no residual, NORMAL store, nphase 1, ksplit <= 1, qh*qw % 32 == 0 and a
+     * act == NONE, no residual, NORMAL or D2S store (D2S: slots per stacked column, cout of them), nphase 1,
+     * ksplit <= 1, qh*qw % 32 == 0 and a
      * channel-contiguous 16-byte aligned dst with cout % 4 == 0 (else FUSG_ERR_UNSUPPORTED).
      * Feed to fusg_in_finalize_slots / fusg_ln_finalize_slots. */
     float*         stats_out;
@@ -429,6 +430,29 @@ int fusg_in_finalize_slots(const float* slots, int32_t batch, int32_t nslots, in
                            float* scale, float* shift, void* stream);
 int fusg_ln_finalize_slots(const float* slots, int32_t batch, int32_t nslots, int32_t channels, float eps,
                            const float* gamma, const float* beta, float* scale, float* shift, void* stream);
+
+/* ---- border ring of nn.Upsample(2) -> ReflectionPad2d(2) -> 5x5 after the phase-form launch (new entry points, FUSG_VERSION
+ * stays 118: nothing existing changed its layout, and 118 is what the suite pins) ---------------------------------------------
+ * The phase-form launch (3x3 on the low-res input, edge-replicate padding, DepthToSpace store) equals the 5x5 convolution of the
+ * REPLICATE-padded upsampled image.  fusg_up2_edge_fix adds, in place, the 5x5 convolution of (reflect-padded - replicate-padded),
+ * which is non-zero on the outermost ring of output pixels only and uses only the taps on the padding frame (csrc/up2_edge.h).
+ *   src     low-res source [B, Cin, h, w], NHWC-physical, Cin % 32 == 0, h, w >= 2
+ *   pre_op  FUSG_PRE_NONE or FUSG_PRE_AFFINE_RELU with scale / shift [b * pre_bstride + c], as fusg_conv_desc takes them
+ *   wedge   the frame taps in fp32, [4 sides][5 taps][Cin/16][Cout/16][64][4] (pack.pack_conv_up2_edge)
+ *   dst     the phase-form output [B, Cout, 2h, 2w], NHWC-physical, Cout % 16 == 0, Cout <= 256; ring pixels become old + delta
+ *   delta   NULL, or [B][n_entries][2] doubles: per workgroup (sum of delta, sum of delta * (2 old + delta)) over its pixels, the
+ *           change of the image's sum and sum of squares; n_entries = fusg_up2_edge_entries(h, w)
+ * Exact fp32 arithmetic (v_mfma_f32_16x16x4_f32) whatever the precision of the phase launch; no range guard.  Two launches on the
+ * stream (rows, then columns); work split and summation orders depend on (h, w, Cin, Cout) only. */
+int fusg_up2_edge_entries(int32_t h, int32_t w);
+int fusg_up2_edge_fix(const fusg_tensor* src, int32_t pre_op, const float* pre_scale, const float* pre_shift, int64_t pre_bstride,
+                      const float* wedge, const fusg_tensor* dst, double* delta, int32_t n_entries, void* stream);
+/* fusg_ln_finalize_slots of slots over `columns` stacked columns (a DepthToSpace launch: 4 * channels of them, the same multiset of
+ * values) whose image then changed by fusg_up2_edge_fix: the sum of `delta`'s first entries is added to the sum and of its second
+ * entries to the sum of squares before mean and unbiased std.  gamma / beta / scale / shift have `channels` entries. */
+int fusg_ln_finalize_slots_delta(const float* slots, int32_t batch, int32_t nslots, int32_t columns, int32_t channels, float eps,
+                                 const float* gamma, const float* beta, const double* delta, int32_t n_entries,
+                                 float* scale, float* shift, void* stream);
 
 /* ---- elementwise / data movement ------------------------------------------------------------ */
 
